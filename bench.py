@@ -8,7 +8,12 @@ and handed over by device pointer (mi355enc_submit_device).  One independent str
 GPU (north_star: one live stream does not shard; no RCCL on the data path) -- ranks only
 meet at the barriers that bracket the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 1080p_ippp|1080p_intra|2160p_ippp|720p_ippp]
+A plain run sets up, warms up, times the steps and prints the headline line.  --full adds
+everything else the line used to carry: the quality pass (PSNR), host-input and latency legs,
+the IDR probe, the GStreamer legs, the roofline / per-stage figures and the CPU baseline.
+--dump-outputs DIR writes what the timed path handed its caller for the last step (.npy).
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 1080p_ippp|1080p_intra|2160p_ippp|720p_ippp] [--full] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -195,6 +200,25 @@ def third_party_decode(aus, width, height):
             for i in range(len(raw) // fsz)]
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array (float32 or float64) as <path>/<name>.npy, 64 MB at most in all: an array that would not fit is
+    replaced by a fixed sample (seed 0) of its elements, the sample's indices beside it as <name>_sample_index.npy."""
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if a.nbytes > left:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, max(0, left // (a.itemsize + 8) - 1), replace=False))
+            np.save(os.path.join(path, name + "_sample_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+            left -= idx.size * 8
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -202,10 +226,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=60)
     ap.add_argument("--workload", default="1080p_ippp", choices=sorted(WORKLOADS))
     ap.add_argument("--unique", type=int, default=32, help="distinct synthetic pictures kept in HBM")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-gst-latency", action="store_true", help="skip the live GStreamer latency probe (M2)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed host-input / latency / IDR-probe legs as well (for kernel traces: the trace then holds the timed "
-                    "region's schedule, its warm-up and the quality pass only)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the quality pass, the untimed host-input / latency / IDR-probe legs, the GStreamer legs, "
+                    "the roofline and per-stage figures and the CPU baseline (the --no-* switches below thin that out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the timed path returned for its last step (per stream: the access unit's "
+                    "bytes, and keyframe / pts / QP / size) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-gst-latency", action="store_true", help="with --full: skip the GStreamer legs (M2 latency, throughput through the element)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the untimed host-input / latency / IDR-probe legs as well (for kernel traces: the trace then "
+                    "holds the timed region's schedule, its warm-up and the quality pass only)")
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--fixed-qp", type=int, default=-1)
     ap.add_argument("--depth", type=int, default=2, help="pipeline_depth: pictures in flight - 1 (2: the device never waits for the host)")
@@ -288,6 +316,7 @@ def main():
                 cur = b
         return cur
 
+    # (the stage timers are sampled with or without --full, which only reports them: the timed path is the same either way)
     if args.sample > 0:  # a short run (the driver's --steps 20) still gets at least four sampled pictures inside the timed region
         args.sample = max(1, min(args.sample, args.steps // 4 if args.steps >= 4 else 1))
     # the coding tools, the same in every encoder this script opens (None: the library's default)
@@ -301,7 +330,10 @@ def main():
     encs = [make_encoder() for _ in range(S)]
     e = encs[0]
 
-    def run_one(enc, n, first_index, shift):
+    last = [None] * S  # per stream: (size, keyframe, pts, qp) of the last access unit collected
+
+    def run_one(k, n, first_index, shift):
+        enc = encs[k]
         qps, nbytes, last_bps = [], 0, None
         for i in range(n):
             if script:
@@ -312,21 +344,21 @@ def main():
             p = base + bounce(first_index + i + shift, args.unique) * fbytes
             enc.submit_device(p, stride, p + height * stride, stride, pts=first_index + i)
             if enc.pending > args.depth:
-                sz, _, _, qp = enc.collect(copy=False)
+                sz, _, _, qp = last[k] = enc.collect(copy=False)
                 qps.append(qp)
                 nbytes += sz
         while enc.pending:
-            sz, _, _, qp = enc.collect(copy=False)
+            sz, _, _, qp = last[k] = enc.collect(copy=False)
             qps.append(qp)
             nbytes += sz
         return qps, nbytes
 
     def run(n, first_index):
         if S == 1:
-            return run_one(e, n, first_index, 0)
+            return run_one(0, n, first_index, 0)
         import threading  # one host thread per stream; the C ABI releases the GIL for the duration of every call
         res = [None] * S
-        th = [threading.Thread(target=lambda k=k: res.__setitem__(k, run_one(encs[k], n, first_index, 5 * k))) for k in range(S)]
+        th = [threading.Thread(target=lambda k=k: res.__setitem__(k, run_one(k, n, first_index, 5 * k))) for k in range(S)]
         for t in th:
             t.start()
         for t in th:
@@ -339,11 +371,20 @@ def main():
     dt, (qps, nbytes) = ranks.timed(lambda: run(args.steps, args.warmup), sync=torch.cuda.synchronize)
     st = e.stats()
     p_rows, i_rows = e.p_slice_rows, e.slice_rows  # rows per slice of P / I pictures (0: one slice)
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        # collect(copy=False) leaves the access unit it reports in the encoder's output buffer: the last one is still there
+        outs = {}
+        for k, enc in enumerate(encs):
+            sfx = "" if S == 1 else "_stream%d" % k
+            sz, key, pts, qp = last[k]
+            outs["access_unit" + sfx] = enc._out[:sz].astype(np.float32)
+            outs["access_unit_info" + sfx] = np.array([key, pts, qp, sz], np.float64)  # keyframe, pts, QP, bytes
+        dump_outputs(args.dump_outputs, outs)
     for enc in encs:  # (closed before the untimed extras open encoders of their own: several encoders in one process run their stages in order)
         enc.close()
 
     extra = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         # Untimed extras.  (1) quality: a separate pass over two GOPs of the same clip with the same rate control (and the same
         # setpoint script), reconstruction fetched after every picture -- mean PSNR of Y, Cb, Cr over ALL its pictures.
         from ceracoder_amd import synth
@@ -446,7 +487,7 @@ def main():
                              "qp": int(round(float(np.mean(qps))))}
         extra["idr_probe"] = idr_probe
 
-    if rank == 0 and world == 1 and not args.no_gst_latency:
+    if rank == 0 and world == 1 and args.full and not args.no_gst_latency:
         extra["latency_gst_ms"] = gst_latency(width, height, fps, gop, bps, dev)
         g = gst_throughput(width, height, fps, gop, bps, dev, args.depth, clip=frames_np)
         extra["gst_throughput"] = g
@@ -454,7 +495,7 @@ def main():
         extra["gst_appsrc_frames_per_s"] = (g.get("element_appsrc_pinned") or {}).get("frames_per_s")  # pre-rendered pictures in pinned memory through appsrc
         extra["third_party"] = third_party_probe()
 
-    if rank == 0:
+    if rank == 0 and args.full:  # the roofline and per-stage figures, from the stage timers sampled in the timed region
         # HBM traffic of the kernels comes from separate rocprofv3 --pmc passes (cannot be collected from inside this
         # process); the committed summary of the latest pass for this workload is attached for cross-checking.
         prof = None
@@ -582,31 +623,11 @@ def main():
         n_p_all = int(st.frames - st.idr_frames - st.skip_pictures)
         t_p = (dt * 1e3 - n_idr * t_i) / max(1, n_p_all)  # (per encoder: with several streams per GPU each one coded its own `steps` pictures in dt)
         gop_fps = (1e3 * gop / ((gop - 1) * t_p + t_i)) if (gop > 1 and st.n_me and t_i > 0 and t_p > 0) else None
-        out = {
-            "metric": "1080p H.264 encoded frames/sec per GPU" if args.workload.startswith("1080p") else "H.264 encoded frames/sec per GPU",
-            "value": round(world * S * (args.steps - int(st.skip_pictures)) / dt, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / (S * args.steps) * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u8", "data": "synthetic (S2: panning texture + 12 moving rectangles, seed 0x5EED), resident in HBM",
-            "idr_in_timed_region": n_idr, "skip_pictures_in_timed_region": int(st.skip_pictures),
-            "device_wait_recoveries": int(st.recoveries), "safe_level": int(st.safe_level),  # must be 0 / 0: a recovery means a bounded device-side wait ran out
-            "value_kind": ("P pictures only: the timed region holds no IDR picture -- gop_weighted_frames_per_s is the rate over whole GOPs" if (n_idr == 0 and gop > 1) else
-                           "whole GOPs" if gop > 1 and args.steps % gop == 0 else "all-intra" if gop == 1 else "%d IDR pictures among %d" % (n_idr, args.steps)),
-            "value_note": ("over whole GOPs the device sustains gop_weighted_frames_per_s (below); " if (n_idr == 0 and gop > 1) else "") +
-                          "value = pictures that went through the device per second: rate control's all-skip pictures (one P_Skip run written by the host, no kernel) are not counted",
-            "frames_per_s_including_skip_pictures": round(world * S * args.steps / dt, 2),
+        full = {
             "gop_weighted_frames_per_s": round(gop_fps, 1) if gop_fps else None,
             "gop_weighted_note": "gop / ((gop-1) * t_P + t_IDR): t_IDR = an IDR picture's stage timers (its stages run in order), t_P = (wall time - IDR pictures * t_IDR) / "
                                  "P pictures of the timed region -- what the device sustains over whole GOPs, however many IDR pictures the timed region happened to contain",
             "gop_weighted_t_idr_ms": round(t_i, 4) if t_i else None, "gop_weighted_t_idr_source": t_i_src,
-            "config": {"workload": args.workload, "width": width, "height": height, "fps_nominal": fps, "gop": gop, "h2d_in_timed_region": False,
-                       "rate_control": ("fixed qp %d" % args.fixed_qp) if args.fixed_qp >= 0 else ("cbr %d bit/s" % bps) if not script else
-                       "cbr, setpoint driven by the reference's '%s' balancer script (%d..%d kbit/s, tests/golden/balancer_%s.txt)" % (
-                           script_name, min(b for _, b in script) // 1000, max(b for _, b in script) // 1000, script_name),
-                       "me": "full search +-16 integer-pel SAD (surfaces kept) + 3 median-regularised selection iterations + half-sample SAD / quarter-sample SATD refinement", "streams_per_gpu": S, "hip_streams_per_encoder": 1 if ((S >= 2 or shared_gpu) if args.single_stream < 0 else bool(args.single_stream)) else 4, "parallelism": "%d independent streams" % (world * S),
-                       "pipeline_depth": args.depth, "exclusive_device": bool(S == 1 and not shared_gpu), "devices_on_box": n_dev, "ranks_share_devices": bool(world > n_dev),
-                       "rank0_cpus": rank_cpus if world > 1 else None, "rank0_numa_node": int(os.environ.get("MI355_BENCH_NUMA_NODE", "-1")), "dct8x8": bool(args.dct8x8), "i8x8": bool(args.i8x8), "aq_mode": int(args.aq), "cavlc_threads": int(st.cavlc_threads),
-                       "p_slice_rows": int(p_rows), "i_slice_rows": int(i_rows), "slices_per_p_picture": (coded(height) // 16 + p_rows - 1) // p_rows if p_rows else 1,
-                       "slice_local_deblocking": (args.slice_deblock != 0)},
             "roofline": roof,
             "roofline_kernels": kernels,
             "stage_timers": ("HIP events on every %d-th P picture, on the streams the kernels are launched on" % args.sample) + (
@@ -622,12 +643,39 @@ def main():
                                      "gpu_total": round(est_total / max(1, st.frames), 4),
                                      "host_cavlc": round(st.ms_entropy / max(1, st.frames), 4),
                                      "host_wait": round(st.ms_wait / max(1, st.frames), 4)},
+        }
+
+    if rank == 0:
+        n_idr = int(st.idr_frames)
+        out = {
+            "metric": "1080p H.264 encoded frames/sec per GPU" if args.workload.startswith("1080p") else "H.264 encoded frames/sec per GPU",
+            "value": round(world * S * (args.steps - int(st.skip_pictures)) / dt, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / (S * args.steps) * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "u8", "data": "synthetic (S2: panning texture + 12 moving rectangles, seed 0x5EED), resident in HBM",
+            "idr_in_timed_region": n_idr, "skip_pictures_in_timed_region": int(st.skip_pictures),
+            "device_wait_recoveries": int(st.recoveries), "safe_level": int(st.safe_level),  # must be 0 / 0: a recovery means a bounded device-side wait ran out
+            "value_kind": ("P pictures only: the timed region holds no IDR picture -- gop_weighted_frames_per_s (--full) is the rate over whole GOPs" if (n_idr == 0 and gop > 1) else
+                           "whole GOPs" if gop > 1 and args.steps % gop == 0 else "all-intra" if gop == 1 else "%d IDR pictures among %d" % (n_idr, args.steps)),
+            "value_note": ("over whole GOPs the device sustains gop_weighted_frames_per_s (--full); " if (n_idr == 0 and gop > 1) else "") +
+                          "value = pictures that went through the device per second: rate control's all-skip pictures (one P_Skip run written by the host, no kernel) are not counted",
+            "frames_per_s_including_skip_pictures": round(world * S * args.steps / dt, 2),
+            "config": {"workload": args.workload, "width": width, "height": height, "fps_nominal": fps, "gop": gop, "h2d_in_timed_region": False,
+                       "rate_control": ("fixed qp %d" % args.fixed_qp) if args.fixed_qp >= 0 else ("cbr %d bit/s" % bps) if not script else
+                       "cbr, setpoint driven by the reference's '%s' balancer script (%d..%d kbit/s, tests/golden/balancer_%s.txt)" % (
+                           script_name, min(b for _, b in script) // 1000, max(b for _, b in script) // 1000, script_name),
+                       "me": "full search +-16 integer-pel SAD (surfaces kept) + 3 median-regularised selection iterations + half-sample SAD / quarter-sample SATD refinement", "streams_per_gpu": S, "hip_streams_per_encoder": 1 if ((S >= 2 or shared_gpu) if args.single_stream < 0 else bool(args.single_stream)) else 4, "parallelism": "%d independent streams" % (world * S),
+                       "pipeline_depth": args.depth, "exclusive_device": bool(S == 1 and not shared_gpu), "devices_on_box": n_dev, "ranks_share_devices": bool(world > n_dev),
+                       "rank0_cpus": rank_cpus if world > 1 else None, "rank0_numa_node": int(os.environ.get("MI355_BENCH_NUMA_NODE", "-1")), "dct8x8": bool(args.dct8x8), "i8x8": bool(args.i8x8), "aq_mode": int(args.aq), "cavlc_threads": int(st.cavlc_threads),
+                       "p_slice_rows": int(p_rows), "i_slice_rows": int(i_rows), "slices_per_p_picture": (coded(height) // 16 + p_rows - 1) // p_rows if p_rows else 1,
+                       "slice_local_deblocking": (args.slice_deblock != 0)},
             "bitrate_out_bps": round(nbytes * 8 * fps / (S * args.steps)),
             "bitrate_setpoint_mean_bps": round(float(np.mean([setpoint(args.warmup + i) for i in range(args.steps)]))) if script else bps, "mean_qp": round(float(np.mean(qps)), 2),
         }
-        out.update(extra)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(frames_np, width, height, fps, gop, qps)
+        if args.full:
+            out.update(full)
+            out.update(extra)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(frames_np, width, height, fps, gop, qps)
         print(json.dumps(out), flush=True)
     ranks.close()
 
