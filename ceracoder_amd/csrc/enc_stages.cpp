@@ -27,6 +27,8 @@ int mi355enc_stage_csc(mi355enc_t *h, int fmt, const uint8_t *const planes[3], c
 static void stage_touched(mi355enc_t *h) { h->have_ref = 0; h->rec_epoch[0] = h->rec_epoch[1] = 0; h->dbI_busy[0] = h->dbI_busy[1] = 0; }
 static int stage_ctx(mi355enc_t *h, int qp, bool src_is_staging, int drop = 0, int idr = 0) {
     if (h->pending) return MI355ENC_ERR_STATE;
+    // slice-local deblocking: a band of the deblocker never spans two slices (mi355enc_dev.h); the two settings are made separately, so the pair is checked here
+    if (h->stage_slice_dbf == 2 && h->stage_slice_rows % MI355_BAND_ROWS != 0) return MI355ENC_ERR_ARG;
     slot_t *s = &h->slot[0];
     frame_ctx_t *c = s->h_ctx;
     c->src_y = src_is_staging ? s->d_src_y : nullptr; c->src_uv = src_is_staging ? s->d_src_uv : nullptr; c->src_stride = h->W;

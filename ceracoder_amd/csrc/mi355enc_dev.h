@@ -133,8 +133,10 @@ int k_launch_deblock_bands(const frame_ctx_t *h_ctx, int mbh, int band0, int ban
                             uint8_t *d_ip_strips, unsigned *d_ip_done /* both non-null (with d_ip_progress and d_row_done): the picture's intra macroblock rows run as the launch's
                                                                             leading workgroups; each counts itself in d_ip_done when its records and levels are in memory */,
                             unsigned *d_qpc, unsigned qpc_base /* adaptive quantisation (h_ctx->qp_off): the launch's first workgroup resolves the QP_Y chain and counts the rows in *d_qpc from qpc_base */,
-                            unsigned *d_part_cnt /* may be null; 2 words per band, zeroed once: P pictures walk every band as two workgroups, cut at a column where the filter does nothing;
-                                                    each part adds one when its lines are in memory (the counts only grow: two per band, plane and launch) */, hipStream_t s);
+                            unsigned *d_part_cnt /* may be null; 6 words per band, zeroed once: P pictures walk every band as two workgroups, cut at a column where the filter does nothing.
+                                                    Words 0 .. 2*nb-1 (nb bands): the parts' counters, {luma, chroma} per band -- each part adds one when its lines are in
+                                                    memory (the counts only grow: two per band, plane and launch); then 2*nb uint2 granules {cut column, picture epoch},
+                                                    {luma, chroma} per band, that the band below reads (0: an idle band, mbw: walked whole) */, hipStream_t s);
 int k_intra_band_rows(void);
 size_t k_deblock_partab_bytes(int mbw, int mbh); // scratch of the band kernel: one parameter word per (edge, segment) of every macroblock
 size_t k_deblock_gran_bytes(int mbw, int mbh);

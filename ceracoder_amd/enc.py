@@ -18,6 +18,9 @@ MBINFO_DTYPE = np.dtype(
 )
 
 FETCH_RECON_Y, FETCH_RECON_UV, FETCH_PREFILTER_Y, FETCH_PREFILTER_UV, FETCH_MBINFO, FETCH_LEVELS = range(6)
+FETCH_BAND_CUTS, FETCH_ERROR_WORD = 102, 103  # development: Encoder.band_cuts(), Encoder.error_word()
+BAND_ROWS = 4  # MI355_BAND_ROWS: macroblock rows per band of the band deblocker
+ERR_ARG, ERR_STATE = -1, -6
 FMT_NV12, FMT_I420, FMT_YUY2, FMT_UYVY = range(4)
 IDEC = np.dtype([("modes4", "u1", (16,)), ("mode16", "u1"), ("cmode", "u1"), ("use_i4", "u1"), ("pad", "u1"), ("cost", "<u4"), ("cost_luma", "<u4"), ("rsv", "<u4")])
 IMV_DTYPE = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("sad", "<u2"), ("bits", "<u2")])
@@ -373,6 +376,26 @@ class Encoder:
             a = np.empty((n, LEVELS_PER_MB), np.int16)
         self._chk(self.L.mi355enc_fetch(self.h, what, _p(a), a.nbytes), "fetch")
         return a
+
+    def band_cuts(self):
+        """Development: what the band deblocker's last launch with the cut left (mi355enc_dev.h, d_part_cnt) -- a record with "count"
+        (bands, 2): per band and plane the parts' counter; "cut" and "epoch" (bands, 2): per band and plane the column where the band
+        was cut and the picture's epoch.  None where bands are walked whole (MI355ENC_NO_SPLIT)."""
+        nb = (self.mbh + BAND_ROWS - 1) // BAND_ROWS
+        layout = np.dtype([("count", "<u4", (nb, 2)), ("gran", [("cut", "<u4"), ("epoch", "<u4")], (nb, 2))])
+        a = np.zeros(1, layout)
+        r = self.L.mi355enc_fetch(self.h, FETCH_BAND_CUTS, _p(a), a.nbytes)
+        if r == ERR_STATE:
+            return None
+        self._chk(r, "fetch")
+        g = a[0]["gran"]
+        return {"count": a[0]["count"].copy(), "cut": g["cut"].astype(np.int64), "epoch": g["epoch"].copy()}
+
+    def error_word(self):
+        """Development: the device's sticky error word (a bounded wait that ran out leaves its code there; 0: none did)."""
+        a = np.zeros(1, np.uint32)
+        self._chk(self.L.mi355enc_fetch(self.h, FETCH_ERROR_WORD, _p(a), a.nbytes), "fetch")
+        return int(a[0])
 
     # ---- single-stage entry points (coded-size host planes)
     def stage_me(self, cur_y, ref_y, qp):

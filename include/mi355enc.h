@@ -284,6 +284,8 @@ int mi355enc_stage_set_slice_rows(mi355enc_t *h, int rows);
 int mi355enc_slice_rows(const mi355enc_t *h); /* rows per slice of this handle's I pictures (0: one slice) */
 int mi355enc_p_slice_rows(const mi355enc_t *h); /* ... and of its P pictures */
 int mi355enc_stage_set_slice_deblock(mi355enc_t *h, int idc); /* the single-stage entry points: disable_deblocking_filter_idc of the picture's slices, 0 (default) or 2 */
+/* (with idc 2 every slice is a whole number of the deblocker's bands, four macroblock rows: a single-stage call made with idc 2 and slice rows
+ * that are not a multiple of four returns MI355ENC_ERR_ARG, whichever of the two settings came first) */
 /* the same slice through the packed hand-over format and `threads` row-parallel host threads (bit-identical result) */
 int mi355enc_host_write_slice_packed(int mbw, int mbh, int is_idr, int frame_num, int idr_pic_id, int qp, int t8, int threads, const void *mbinfo,
                                      const int16_t *levels, uint8_t *out, size_t cap, size_t *out_len);
