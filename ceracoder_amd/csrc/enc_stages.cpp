@@ -119,6 +119,7 @@ static int download_picture(mi355enc_t *h, void *mbinfo, uint8_t *rec_y, uint8_t
 int mi355enc_stage_inter(mi355enc_t *h, const uint8_t *src_y, const uint8_t *src_uv, const uint8_t *ref_y, const uint8_t *ref_uv,
                          int qp, void *mbinfo_inout, uint8_t *rec_y, uint8_t *rec_uv, int16_t *levels) {
     if (!h || !src_y || !src_uv || !ref_y || !ref_uv || !mbinfo_inout || !rec_y || !rec_uv || !levels || qp < 0 || qp > 51) return MI355ENC_ERR_ARG;
+    if (h->cfg.transform8x8 == 2) return MI355ENC_ERR_ARG; // the two-kernel form has no per-macroblock transform choice (the fused stage has: mi355enc_stage_pmb)
     HIPCHK(hipSetDevice(h->cfg.device_id));
     STAGE_IDLE(h);
     int r = upload_planes4(h, src_y, src_uv, ref_y, ref_uv); if (r) return r;

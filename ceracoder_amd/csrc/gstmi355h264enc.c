@@ -54,6 +54,7 @@ typedef struct {
     gint dct8x8, i8x8, aq_mode, intra_in_p, slices, slice_deblock;
     gint intra_slices;
     gboolean single_stream;
+    gboolean dct8x8_adaptive; /* with dct8x8: the transform size is chosen per P macroblock (cfg.transform8x8 = 2) */
     /* streaming state */
     mi355enc_t *enc;
     GstVideoCodecState *input_state;
@@ -70,7 +71,7 @@ typedef struct { GstVideoEncoderClass parent_class; } GstMi355H264EncClass;
 G_DEFINE_TYPE(GstMi355H264Enc, gst_mi355h264enc, GST_TYPE_VIDEO_ENCODER)
 
 enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME_RANGE, PROP_QP, PROP_PIPELINE_DEPTH,
-       PROP_SPEED_PRESET, PROP_STATS, PROP_DCT8X8, PROP_THREADS, PROP_SCENECUT, PROP_VBV, PROP_INTRA_IN_P, PROP_EXCLUSIVE, PROP_PINNED_INPUT, PROP_AQ_MODE, PROP_SINGLE_STREAM, PROP_INTRA_SLICES, PROP_I8X8, PROP_SLICES, PROP_SLICE_DEBLOCK };
+       PROP_SPEED_PRESET, PROP_STATS, PROP_DCT8X8, PROP_THREADS, PROP_SCENECUT, PROP_VBV, PROP_INTRA_IN_P, PROP_EXCLUSIVE, PROP_PINNED_INPUT, PROP_AQ_MODE, PROP_SINGLE_STREAM, PROP_INTRA_SLICES, PROP_I8X8, PROP_SLICES, PROP_SLICE_DEBLOCK, PROP_DCT8X8_ADAPTIVE };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
     GST_STATIC_CAPS("video/x-raw, format=(string){ NV12, I420, YUY2, UYVY }, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]"));
@@ -139,6 +140,7 @@ static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *
     case PROP_SPEED_PRESET: s->speed_preset = g_value_get_enum(val); break;
     case PROP_STATS: s->stats = g_value_get_boolean(val); break;
     case PROP_DCT8X8: s->dct8x8 = g_value_get_boolean(val) ? 1 : 0; break;
+    case PROP_DCT8X8_ADAPTIVE: s->dct8x8_adaptive = g_value_get_boolean(val); break;
     case PROP_THREADS: s->threads = g_value_get_int(val); break;
     case PROP_SCENECUT: s->scenecut = g_value_get_boolean(val); break;
     case PROP_EXCLUSIVE: s->exclusive_gpu = g_value_get_boolean(val); break;
@@ -171,6 +173,7 @@ static void get_property(GObject *obj, guint id, GValue *val, GParamSpec *ps) {
     case PROP_SPEED_PRESET: g_value_set_enum(val, s->speed_preset); break;
     case PROP_STATS: g_value_set_boolean(val, s->stats); break;
     case PROP_DCT8X8: g_value_set_boolean(val, t.dct8x8 != 0); break;
+    case PROP_DCT8X8_ADAPTIVE: g_value_set_boolean(val, s->dct8x8_adaptive); break;
     case PROP_THREADS: g_value_set_int(val, s->threads); break;
     case PROP_SCENECUT: g_value_set_boolean(val, s->scenecut); break;
     case PROP_EXCLUSIVE: g_value_set_boolean(val, s->exclusive_gpu); break;
@@ -238,7 +241,7 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     {
         toolset_t t;
         effective_tools(s, &t);
-        cfg.transform8x8 = t.dct8x8; cfg.i8x8 = t.i8x8; cfg.aq_mode = t.aq_mode; cfg.partitions = t.partitions; cfg.intra_in_p = t.intra_in_p;
+        cfg.transform8x8 = t.dct8x8 ? (s->dct8x8_adaptive ? 2 : 1) : 0; cfg.i8x8 = t.i8x8; cfg.aq_mode = t.aq_mode; cfg.partitions = t.partitions; cfg.intra_in_p = t.intra_in_p;
         if (t.slices >= 0) cfg.slices = t.slices;               /* (-1: mi355enc_default_cfg's) */
         if (t.slice_deblock >= 0) cfg.slice_deblock = t.slice_deblock;
     }
@@ -475,6 +478,9 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
         "Code an IDR picture two pictures after a scene cut (detected from the summed motion cost; x264 decides inside its lookahead instead)", TRUE, F));
     g_object_class_install_property(g, PROP_DCT8X8, g_param_spec_boolean("dct8x8", "8x8 transform",
         "Adaptive spatial transform size as in x264enc: High-profile stream, P macroblocks use the 8x8 transform", FALSE, F));
+    g_object_class_install_property(g, PROP_DCT8X8_ADAPTIVE, g_param_spec_boolean("dct8x8-adaptive", "Per-macroblock transform size",
+        "With dct8x8: every coded P macroblock chooses between the 4x4 and the 8x8 transform (SA8D against SATD of its prediction residual), as x264enc's dct8x8 does; "
+        "without dct8x8 ignored. speed-preset does not set it", FALSE, F));
     g_object_class_install_property(g, PROP_STATS, g_param_spec_boolean("stats", "Print stats", "Print a JSON line with counters when the encoder closes", FALSE, F));
     gst_element_class_add_static_pad_template(e, &sink_tmpl);
     gst_element_class_add_static_pad_template(e, &src_tmpl);
@@ -485,7 +491,7 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
 }
 static void gst_mi355h264enc_init(GstMi355H264Enc *s) {
     s->rate_raw = 2048; s->rate_is_bps = FALSE; s->key_int_max = 60; s->device_id = 0; s->me_range = 16; s->qp = -1; s->pipeline_depth = 0; s->speed_preset = 0;
-    s->stats = FALSE; s->dct8x8 = -1; s->threads = 0; s->scenecut = TRUE; s->exclusive_gpu = FALSE; s->vbv_ms = 600; s->intra_in_p = -1; s->pinned_input = TRUE; s->aq_mode = -1; s->slices = -1; s->slice_deblock = -1; s->intra_slices = 0; s->i8x8 = -1; s->single_stream = FALSE; s->enc = NULL; s->input_state = NULL; s->max_au = 0; s->au_buf = NULL; s->last_pts = GST_CLOCK_TIME_NONE;
+    s->stats = FALSE; s->dct8x8 = -1; s->threads = 0; s->scenecut = TRUE; s->exclusive_gpu = FALSE; s->vbv_ms = 600; s->intra_in_p = -1; s->pinned_input = TRUE; s->aq_mode = -1; s->slices = -1; s->slice_deblock = -1; s->intra_slices = 0; s->i8x8 = -1; s->single_stream = FALSE; s->dct8x8_adaptive = FALSE; s->enc = NULL; s->input_state = NULL; s->max_au = 0; s->au_buf = NULL; s->last_pts = GST_CLOCK_TIME_NONE;
     s->us_map = s->us_submit = s->us_collect = s->us_output = s->us_push = s->us_frames = 0;
 }
 

@@ -614,6 +614,30 @@ DEV unsigned pmb_satd(int lane, unsigned curw, unsigned pw) {
     }
     return (unsigned)wave64_sum(acc);
 }
+// sum of |H8 d H8^T| over the macroblock's four 8x8 blocks for prediction word pw (unhalved; wave-uniform result).  An 8x8 block's row is lane bit 0
+// (its two halves), its rows are lane bits 2 .. 4: the 4-point Hadamard of the lane's word, one butterfly with the other half, three down the rows.
+DEV unsigned pmb_sa8d(int lane, unsigned curw, unsigned pw) {
+    const int s0 = (lane & 1) ? -1 : 1, s1 = (lane & 4) ? -1 : 1, s2 = (lane & 8) ? -1 : 1, s3 = (lane & 16) ? -1 : 1;
+    const int d0 = byte_of(curw, 0) - byte_of(pw, 0), d1 = byte_of(curw, 1) - byte_of(pw, 1), d2 = byte_of(curw, 2) - byte_of(pw, 2), d3 = byte_of(curw, 3) - byte_of(pw, 3);
+    const int a = d0 + d3, b = d1 + d2, c = d1 - d2, e = d0 - d3;
+    int t[4] = {a + b, e + c, a - b, e - c};
+    int acc = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        int u = mad24(t[i], s0, quad_xor<1>(t[i]));   // columns: the row's other half
+        u = mad24(u, s1, row_xor4(u));                 // rows r and r ^ 1
+        u = mad24(u, s2, row_xor8(u));                 // ... r ^ 2
+        u = mad24(u, s3, __shfl_xor(u, 16, 64));       // ... r ^ 4
+        acc += iabs(u);
+    }
+    return (unsigned)wave64_sum(acc);
+}
+// transform8x8 = 2: the inter macroblock's luma takes the 8x8 transform when its prediction residual's SA8D, normalised, beats its SATD (x264's transform
+// analysis for the fast presets); a tie keeps 4x4 (wave-uniform)
+DEV bool pmb_pick_t8(int lane, unsigned curw, unsigned pw) {
+    const unsigned raw4 = pmb_satd(lane, curw, pw), raw8 = pmb_sa8d(lane, curw, pw);
+    return __builtin_amdgcn_readfirstlane((int)(((raw8 + 2) >> 2) < (raw4 >> 1))) != 0;
+}
 // write a macroblock that carries no residual: the prediction is the reconstruction, every level is zero
 template <bool SC1>
 DEV void pmb_store_pred_only(const frame_ctx_t *__restrict__ ctx, int16_t *lv, int lane, int x0, int y0, unsigned pw, const int *pd) {
@@ -790,7 +814,8 @@ DEV pmb_pre_t pmb_preload(const frame_ctx_t *__restrict__ ctx, const int mbn, co
     p.ds = (unsigned)*(const GAS uint16_t *)(ctx->surf + (size_t)mbn * SURF_U16 + ((p.fp.sy >> 2) + 16) * SURF_COLS + (p.fp.sx >> 2) + 16);
     return p;
 }
-template <bool SC1, bool PART, bool T8>
+// T8: 0 the 4x4 transform, 1 the 8x8 transform for every coded inter macroblock, 2 the choice of pmb_pick_t8 per macroblock
+template <bool SC1, bool PART, int T8>
 DEV void pmb_mb(const frame_ctx_t *__restrict__ ctx, sp_lds *L, const int mbn, const int lane, const int refine, const pmb_pre_t &pre) {
     const int mbw = ctx->mbw, mbh = ctx->mbh, stride = ctx->stride, W = mbw * 16, H = mbh * 16, qp = mb_qp_dev(ctx, mbn), lambda = ctx->lambda; // (quantisation only: search, refinement and decisions keep the picture's lambda)
     const int my = mbn / mbw, mx = mbn - my * mbw, x0 = mx * 16, y0 = my * 16;
@@ -1020,7 +1045,8 @@ DEV void pmb_mb(const frame_ctx_t *__restrict__ ctx, sp_lds *L, const int mbn, c
     }
     PMB_MARK(8); // chroma prediction loaded
     unsigned nz_luma;
-    if (T8) {
+    const bool t8 = T8 == 1 || (T8 == 2 && pmb_pick_t8(lane, curw, pw));
+    if (t8) {
         nz_luma = pmb_luma_t8<SC1>(ctx, (int *)L, lane, curw, pw, qp, mbn, x0, y0);
         // the sub-blocks without levels keep their zeros: the macroblock's levels are cleared first
     } else {
@@ -1046,7 +1072,7 @@ DEV void pmb_mb(const frame_ctx_t *__restrict__ ctx, sp_lds *L, const int mbn, c
         unsigned nzm = nz_luma | (nz_c << 16);
         if (dc_c & 1) nzm |= NZ_CBDC;
         if (dc_c & 2) nzm |= NZ_CRDC;
-        if (T8 && nz_luma) nzm |= NZ_T8; // transform_size_8x8_flag: sent (and read by the deblocker) only with luma levels
+        if (t8 && nz_luma) nzm |= NZ_T8; // transform_size_8x8_flag: sent (and read by the deblocker) only with luma levels
         mb_info_t m;
         m.mvx = (int16_t)bqx; m.mvy = (int16_t)bqy; m.mb_type = 1; m.i16_mode = (uint8_t)shape; m.chroma_mode = 0; m.qp = (uint8_t)qp; m.nzmask = nzm; m.cost = di;
         st_mbinfo_x<SC1>(mb, m);
@@ -1074,7 +1100,7 @@ DEV void pmb_mb(const frame_ctx_t *__restrict__ ctx, sp_lds *L, const int mbn, c
 // and resident, takes its macroblocks row by row behind them.
 // ROWS (only with GATED): the picture's deblocking launch is already on the chip and waits for this kernel's rows -- samples and records
 // are stored through to memory (sc1) and every macroblock is counted for its row.
-template <bool GATED, bool ROWS, bool PART, bool T8>
+template <bool GATED, bool ROWS, bool PART, int T8>
 __global__ __launch_bounds__(256) void pmb_kernel(const frame_ctx_t cv, int mb0, int mb1, int refine, const unsigned *__restrict__ gate_done, unsigned ref_epoch, unsigned *err, unsigned *row_done) {
     const frame_ctx_t *__restrict__ ctx = &cv;
     __shared__ __attribute__((aligned(16))) sp_lds LD[4];
@@ -1185,16 +1211,20 @@ void k_launch_pmb(const frame_ctx_t *h_ctx, int mbw, int row0, int row1, int ref
     const int n = mbw * (row1 - row0), g = (n + 3) / 4;
     if (n <= 0) return;
 #define PMB_LAUNCH(G, R, P, T) hipLaunchKernelGGL((pmb_kernel<G, R, P, T>), dim3(g), dim3(256), 0, s, *h_ctx, row0 * mbw, row1 * mbw, refine, gate_done, ref_epoch, d_err, d_row_done)
-    if (h_ctx->t8) { // High profile: 8x8 transform for the inter macroblocks' luma (no partitions on this path)
-        if (gate_done && d_row_done) PMB_LAUNCH(true, true, false, true);
-        else if (gate_done) PMB_LAUNCH(true, false, false, true);
-        else PMB_LAUNCH(false, false, false, true);
+    if (h_ctx->t8 == 2) { // High profile, 4x4 or 8x8 transform chosen per inter macroblock
+        if (gate_done && d_row_done) PMB_LAUNCH(true, true, false, 2);
+        else if (gate_done) PMB_LAUNCH(true, false, false, 2);
+        else PMB_LAUNCH(false, false, false, 2);
+    } else if (h_ctx->t8) { // High profile: 8x8 transform for the inter macroblocks' luma (no partitions on this path)
+        if (gate_done && d_row_done) PMB_LAUNCH(true, true, false, 1);
+        else if (gate_done) PMB_LAUNCH(true, false, false, 1);
+        else PMB_LAUNCH(false, false, false, 1);
     } else if (h_ctx->partitions) {
-        if (gate_done && d_row_done) PMB_LAUNCH(true, true, true, false);
-        else if (gate_done) PMB_LAUNCH(true, false, true, false);
-        else PMB_LAUNCH(false, false, true, false);
-    } else if (gate_done && d_row_done) PMB_LAUNCH(true, true, false, false);
-    else if (gate_done) PMB_LAUNCH(true, false, false, false);
-    else PMB_LAUNCH(false, false, false, false);
+        if (gate_done && d_row_done) PMB_LAUNCH(true, true, true, 0);
+        else if (gate_done) PMB_LAUNCH(true, false, true, 0);
+        else PMB_LAUNCH(false, false, true, 0);
+    } else if (gate_done && d_row_done) PMB_LAUNCH(true, true, false, 0);
+    else if (gate_done) PMB_LAUNCH(true, false, false, 0);
+    else PMB_LAUNCH(false, false, false, 0);
 #undef PMB_LAUNCH
 }

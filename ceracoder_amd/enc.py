@@ -275,7 +275,7 @@ class Encoder:
             cfg.slice_deblock = int(slice_deblock)  # the deblocking filter stops at slice boundaries (disable_deblocking_filter_idc 2)
         cfg.subpel = int(subpel)
         cfg.i4x4 = int(i4x4)
-        cfg.transform8x8 = int(transform8x8)
+        cfg.transform8x8 = int(transform8x8)  # 0 / False: Constrained Baseline; 1 / True: High, 8x8 transform for every coded inter macroblock; 2: High, 4x4 or 8x8 per macroblock
         self.h = C.c_void_p()
         self._chk(self.L.mi355enc_open(C.byref(cfg), C.byref(self.h)), "open", close_on_fail=True)
         self.width, self.height = width, height

@@ -59,7 +59,11 @@ typedef struct {
                                  the stream by several per cent */
     int use_graphs;           /* 1: replay the per-picture launch sequence as a hipGraph  */
     int keep_prefilter;       /* 1: keep a copy of the picture before deblocking (tests)  */
-    int transform8x8;         /* 1: High-profile stream, P macroblocks use the 8x8 transform; 0 (default): Constrained Baseline */
+    int transform8x8;         /* 0 (default): Constrained Baseline.  1: High-profile stream, every coded inter macroblock of a P picture uses the 8x8
+                                 transform.  2: High-profile stream (the same SPS and PPS as 1), every coded inter macroblock chooses between the
+                                 4x4 and the 8x8 transform: 8x8 iff (SA8D + 2) >> 2 < SATD >> 1 of its luma prediction residual, both unhalved
+                                 Hadamard sums (x264's transform analysis for its fast presets).  I pictures, intra macroblocks of P
+                                 pictures and i8x8 behave as with 1; mi355enc_stage_inter refuses 2 (MI355ENC_ERR_ARG) */
     int i4x4;                 /* 1 (default): try Intra_4x4 besides Intra_16x16 in I pictures */
     int subpel;               /* 1 (default): half- then quarter-sample refinement after the integer search */
     int deblock_mode;         /* 0: persistent band kernel (x+y order, three waves per macroblock row; boundary strengths in its prologue);
