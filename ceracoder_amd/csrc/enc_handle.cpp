@@ -226,7 +226,8 @@ int mi355enc_open(const mi355enc_cfg_t *cfg, mi355enc_t **out) {
     }
     HIPCHK(hipMalloc((void **)&h->d_ip_progress, (size_t)h->mbh * MI355_PROG_STRIDE * sizeof(unsigned)));
     HIPCHK(hipMemsetAsync(h->d_ip_progress, 0, (size_t)h->mbh * MI355_PROG_STRIDE * sizeof(unsigned), h->stream)); // epoch-tagged: the epoch starts at 1
-    HIPCHK(hipMalloc((void **)&h->d_ip_strips, (size_t)h->nmb * 32));
+    HIPCHK(hipMalloc((void **)&h->d_ip_strips, (size_t)h->nmb * IP_STRIP_BYTES));
+    HIPCHK(hipMemsetAsync(h->d_ip_strips, 0, (size_t)h->nmb * IP_STRIP_BYTES, h->stream)); // epoch-tagged granules: the epoch starts at 1
     if (cfg->keep_prefilter) {
         HIPCHK(hipMalloc((void **)&h->d_pre_y, h->ysz));
         HIPCHK(hipMalloc((void **)&h->d_pre_uv, h->csz));

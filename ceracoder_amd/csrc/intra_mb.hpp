@@ -161,6 +161,7 @@ struct intra_lds {
     __attribute__((aligned(4))) uint8_t z4[2 * 16];   // Intra_4x4: the neighbour line of the (up to two) blocks of a sub-step
     unsigned cflags[2];                               // chroma wave -> luma wave: ballots of its blocks' AC / DC flags
     unsigned cseq;                                    // ... valid once this equals macroblock number + 1
+    unsigned cack;                                    // luma wave -> chroma wave: the flags of macroblock cack - 1 are read (intra_p_row)
     __attribute__((aligned(4))) uint8_t bot_y[4][16], bot_c[4][16];
     __attribute__((aligned(4))) uint8_t right_y[16], right_c[2][8];
     int corner[3];                                    // bottom-right sample of the macroblock before the one in right_*: the next corner
@@ -558,37 +559,64 @@ DEV void intra_compute(const frame_ctx_t *__restrict__ ctx, const dev_tables *T,
 
 // =================================================================== intra macroblocks of P pictures
 // pmb_kernel has reconstructed every inter macroblock and left type + modes in the records of the ones it decided to code
-// intra (Intra_16x16 only); those predict from their neighbours' reconstructed samples (8.3; constrained_intra_pred_flag = 0).
-// One workgroup (luma wave + chroma wave, as everywhere in this file) per macroblock ROW walks the row's intra
-// macroblocks from left to right:
-//  * the left neighbour, when it is intra itself, was this workgroup's previous macroblock: its right column is still in LDS;
-//  * the row above publishes, per macroblock it finishes, a 32-byte strip (bottom luma line, bottom chroma line) with `sc1`
-//    stores and then a progress word = "every macroblock left of this column is final" (epoch in the upper bits, so nothing is
-//    ever cleared); a macroblock whose top or top-left neighbour is intra polls that word and reads the strips with `sc1`
-//    loads (MI355X_MICROARCH.md, "Valid forms": sc1 stores, vmcnt(0), barrier, sc1 flag / sc1 poll, sc1 loads);
-//  * every other neighbour sample comes from the picture: inter macroblocks were final before this launch.
-// Rows only ever wait for the row above, so the wait graph is acyclic whatever the dispatch order (every spin is bounded and
-// reports through `err`).  A row without intra macroblocks publishes "done" and leaves.  Oracle: orc_intra_p_frame.
+// intra; those predict from their neighbours' reconstructed samples (8.3; constrained_intra_pred_flag = 0): left, top and top-left
+// (an Intra_4x4 macroblock here never reads the macroblock above-right: block 5 skips the modes that would).
+// One workgroup per macroblock ROW.  The row's intra macroblocks fall into runs of horizontally adjacent ones; run k of the row goes to
+// wave pair k % IP_PAIRS (luma wave + chroma wave, as everywhere in this file), which walks it from left to right:
+//  * the left neighbour, when it is intra itself, is the pair's previous macroblock: its right column is still in the pair's LDS;
+//  * every intra macroblock leaves its bottom lines for the row below as eight epoch-tagged granules ({4 samples, epoch}, one 8-byte
+//    `sc1` store each: MI355X_MICROARCH.md hand-off R2, no flag); a macroblock whose top or top-left neighbour is intra polls exactly
+//    the granules it reads, each wave those of its own plane, so it waits for those two macroblocks and not for a prefix of the row;
+//  * every other neighbour sample comes from the picture: inter macroblocks were final before this launch.  Those loads, the decision
+//    words and the source samples are issued before any wait.
+// The two waves of a pair share nothing but the record hand-shake (cseq / cack): the planes of a macroblock run side by side.
+// One more wave keeps the row's progress word for the deblocker, "every macroblock left of this column is final" (epoch in the upper bits,
+// so nothing is ever cleared): a monotone prefix, stored by one lane only.  A wave marks its plane of a macroblock done in LDS behind its own
+// `s_waitcnt vmcnt(0)` (the samples went out `sc1`, the record plain as before), and the publisher stores the word once it has seen both
+// planes' marks of every macroblock the word covers (MI355X_MICROARCH.md, "Valid forms": sc1 stores, each wave's vmcnt(0), an LDS count,
+// one lane's sc1 flag / sc1 poll, sc1 loads).
+// The wait graph is acyclic whatever the dispatch order: a pair waits for granules of the row above only (whose pairs wait for the row
+// above them, down to the first row, which waits for nothing in this launch) and for its partner wave, which walks the same macroblocks
+// in the same order; the publisher waits for its own row's pairs, and nothing in this launch waits for the publisher.  Every spin on
+// another workgroup is bounded and reports through `err`; a wave whose spin ran out goes on with what it has, so its partner and the
+// publisher still end.  Oracle: orc_intra_p_frame.
 struct ip_args { frame_ctx_t ctx; unsigned *progress; uint8_t *strips; unsigned *err; };
 #define IP_EPOCH(e) (((e) & 0xFFFFFu) << 12)
-// One macroblock row, run by threads 0..127 of the calling workgroup (luma wave, chroma wave; any other wave of the workgroup must have ended:
-// the barriers below then count these two).  row_done / row_need (may be null): the fused P stage of the same picture may still be running;
+#define IP_PAIRS 4                     // wave pairs per row: a row of a 1080p P picture seldom holds more runs than that
+#define IP_THREADS (128 * IP_PAIRS + 64) // ... and the publisher wave
+// the source samples intra_compute reads for this lane (its `presrc`), loaded ahead of the waits
+DEV uint2 ip_src(const frame_ctx_t *__restrict__ ctx, const int plane, const int lane, const int x0, const int y0) {
+    const int ss = ctx->src_stride, py = (lane >> 2) & 3;
+    if (plane == 0) {
+        int sy = y0 + 4 * (lane >> 4) + py;
+        sy = sy < ctx->vis_h ? sy : ctx->vis_h - 1;
+        return make_uint2(ldg32(ctx->src_y + (size_t)sy * ss + x0 + 4 * (lane & 3)), 0u);
+    }
+    const int vh2 = ctx->vis_h >> 1;
+    int sy = (y0 >> 1) + 4 * ((lane >> 4) & 1) + py;
+    sy = sy < vh2 ? sy : vh2 - 1;
+    return ldg64(ctx->src_uv + (size_t)sy * ss + 2 * ((x0 >> 1) + 4 * (lane & 1)));
+}
+// One macroblock row, run by threads 0..IP_THREADS-1 of the calling workgroup (any other wave of the workgroup must have ended: the
+// barriers below then count these).  row_done / row_need (may be null): the fused P stage of the same picture may still be running;
 // the row starts when its own macroblocks and those of the row above are complete (pmb_kernel<GATED, ROWS> counts them).
 DEV void intra_p_row(const ip_args &a, const int my, const unsigned *row_done, const unsigned row_need) {
     const frame_ctx_t *__restrict__ ctx = &a.ctx;
     if (my == 0) tl_first(ctx, 5);
-    __shared__ intra_lds LD;
+    __shared__ intra_lds LD[IP_PAIRS];
     __shared__ unsigned tabw[TAB_DWORDS];
-    __shared__ unsigned ibits[16]; // which macroblocks of this row are intra (mbw <= 512)
-    __shared__ int sh_bad;
+    __shared__ unsigned ibits[16], abits[16]; // which macroblocks of this row / of the row above (none where it is not available) are intra (mbw <= 512)
+    __shared__ unsigned dbits[2][16];         // per plane: the macroblocks of this row whose samples are out
     const dev_tables *T = (const dev_tables *)tabw;
-    const int mbw = ctx->mbw, stride = ctx->stride;
+    const int mbw = ctx->mbw, stride = ctx->stride, nw = (mbw + 31) / 32;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); // an SGPR: what is derived from it is scalar control flow
     const uint8_t *__restrict__ ry = ctx->rec_y;
     const uint8_t *__restrict__ ruv = ctx->rec_uv;
-    const unsigned ep = IP_EPOCH(ctx->epoch);
-    if (threadIdx.x < 16) ibits[threadIdx.x] = 0;
-    if (threadIdx.x == 0) sh_bad = 0;
+    const unsigned ep = IP_EPOCH(ctx->epoch), tag = ctx->epoch; // (the epoch is never 0; the granules start zeroed)
+    const bool has_top = row_has_top(ctx, my); // (a P slice's first row: nothing above it is available, 6.4.8)
+    uint2 *strips = (uint2 *)a.strips;
+    if (threadIdx.x < 16) { ibits[threadIdx.x] = 0; abits[threadIdx.x] = 0; dbits[0][threadIdx.x] = 0; dbits[1][threadIdx.x] = 0; }
+    if (threadIdx.x < IP_PAIRS) { LD[threadIdx.x].cseq = 0; LD[threadIdx.x].cack = 0; }
     if (row_done) { // the records of this row say which macroblocks are intra; the samples of this row and the row above are what they predict from
         if (threadIdx.x < 64) {
             const int r = my - 1 + (int)threadIdx.x;
@@ -605,99 +633,116 @@ DEV void intra_p_row(const ip_args &a, const int my, const unsigned *row_done, c
         }
     }
     __syncthreads();
-    for (int x = threadIdx.x; x < ((mbw + 63) & ~63); x += 128) {
+    for (int x = threadIdx.x; x < ((mbw + 63) & ~63); x += IP_THREADS) { // (whole waves: IP_THREADS is a multiple of 64)
         const bool in = x < mbw && (ldg32(&ctx->mbi[my * mbw + x].mb_type) & 255u) != 1u;
-        const unsigned long long b = __ballot(in);
-        if (lane == 0) { ibits[(x >> 5)] = (unsigned)b; ibits[(x >> 5) + 1] = (unsigned)(b >> 32); }
+        const bool ina = has_top && x < mbw && (ldg32(&ctx->mbi[(my - 1) * mbw + x].mb_type) & 255u) != 1u; // (intra stays intra when the row above rewrites its records)
+        const unsigned long long b = __ballot(in), ba = __ballot(ina);
+        if (lane == 0) { ibits[x >> 5] = (unsigned)b; ibits[(x >> 5) + 1] = (unsigned)(b >> 32); abits[x >> 5] = (unsigned)ba; abits[(x >> 5) + 1] = (unsigned)(ba >> 32); }
     }
-    for (int i = threadIdx.x; i < TAB_DWORDS; i += 128) tabw[i] = ((const unsigned *)&g_tab)[i];
+    for (int i = threadIdx.x; i < TAB_DWORDS; i += IP_THREADS) tabw[i] = ((const unsigned *)&g_tab)[i];
     __syncthreads();
-    if (threadIdx.x == 0) { // everything left of the row's first intra macroblock is final already (pmb_kernel): the deblocker may start on it
-        int nx = mbw;
-        for (int w2 = (mbw + 31) / 32 - 1; w2 >= 0; w2--) if (ibits[w2]) nx = 32 * w2 + __builtin_ctz(ibits[w2]);
-        if (nx < mbw) st_sc1(&a.progress[my * MI355_PROG_STRIDE], ep | (unsigned)nx);
-    }
-    int prev_x = -2; // the macroblock this workgroup reconstructed last (its right column is in LD)
-    for (int w = 0; w < (mbw + 31) / 32; w++) {
-        unsigned bits = ibits[w];
-        while (bits) {
-            const int mx = 32 * w + __builtin_ctz(bits);
-            bits &= bits - 1;
-            const int mbn = my * mbw + mx, x0 = mx * 16, y0 = my * 16, cx0 = x0 >> 1, cy0 = y0 >> 1;
-            const bool has_top = row_has_top(ctx, my), has_left = mx > 0; // (a P slice's first row: nothing above it is available, 6.4.8)
-            const bool b_intra = has_top && (ldg32(&ctx->mbi[mbn - mbw].mb_type) & 255u) != 1u;
-            const bool d_intra = has_top && has_left && (ldg32(&ctx->mbi[mbn - mbw - 1].mb_type) & 255u) != 1u;
-            const bool a_intra = has_left && prev_x == mx - 1;
-            __syncthreads(); // the previous macroblock is done with LD.top / LD.left (its right column and bottom lines stay)
-            if (threadIdx.x == 0) {
-                LD.cseq = 0;
-                if (b_intra || d_intra) { // the row above must have passed column mx
+    if (wave == 2 * IP_PAIRS) { // ---- the publisher: the row's progress word follows the first macroblock not yet done in both planes
+        if (lane == 0) {
+            int pub = -1, spins = 0;
+            for (;;) {
+                int nx = mbw;
+                for (int w = 0; w < nw; w++) {
+                    const unsigned pend = ibits[w] & ~(__hip_atomic_load(&dbits[0][w], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) &
+                                                       __hip_atomic_load(&dbits[1][w], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
+                    if (pend) { nx = 32 * w + __builtin_ctz(pend); break; }
+                }
+                if (nx > pub) {
+#ifdef DBG_DELAY_IP /* adversarial-schedule build: every progress word after the first comes ~20 us late, so the deblocker that follows this kernel catches up with it at every intra macroblock */
+                    if (pub >= 0) for (int i = 0; i < 6; i++) __builtin_amdgcn_s_sleep(127);
+#endif
+                    st_sc1(&a.progress[my * MI355_PROG_STRIDE], ep | (unsigned)nx);
+                    pub = nx;
+                    spins = 0;
+                    if (nx == mbw) break;
+                } else {
+                    __builtin_amdgcn_s_sleep(1);
+                    if (++spins > DB_SPIN_MAX) { st_sc1(a.err, 15u); break; } // (the pairs wait for the row above)
+                    if ((spins & 1023) == 0 && ld_sc1(a.err)) break;
+                }
+            }
+        }
+    } else { // ---- wave pair `pair`, plane 0 (luma) or 1 (chroma)
+        const int pair = wave >> 1, plane = wave & 1;
+        intra_lds &L = LD[pair];
+        int run = -1, last = -2, prev_x = -2; // last: the row's previous intra macroblock; prev_x: the one this pair reconstructed last
+        for (int w = 0; w < nw; w++) {
+            unsigned bits = __builtin_amdgcn_readfirstlane(ibits[w]);
+            while (bits) {
+                const int mx = 32 * w + __builtin_ctz(bits);
+                bits &= bits - 1;
+                if (mx != last + 1) run++;
+                last = mx;
+                if (run % IP_PAIRS != pair) continue;
+                const int mbn = my * mbw + mx, x0 = mx * 16, y0 = my * 16, cx0 = x0 >> 1, cy0 = y0 >> 1;
+                const bool has_left = mx > 0;
+                const bool b_intra = (abits[mx >> 5] >> (mx & 31)) & 1u;
+                const bool d_intra = has_left && ((abits[(mx - 1) >> 5] >> ((mx - 1) & 31)) & 1u);
+                const bool a_intra = prev_x == mx - 1; // (then the left neighbour is of this run: this pair's previous macroblock)
+                // loads that wait for nothing: decisions, source, the samples of inter neighbours
+                const uint4 dec0 = ldg128(ctx->idec + (size_t)mbn * IDEC_BYTES); // the sixteen Intra_4x4 modes (ctx->intra_p == 2; zeros otherwise)
+                const uint2 dec1 = ldg64(ctx->idec + (size_t)mbn * IDEC_BYTES + 16);
+                const uint2 src = ip_src(ctx, plane, lane, x0, y0);
+                // neighbour samples ([plane][i + 1] = sample i, [0] = corner): luma lanes 0..16 top line + corner, 32..47 left column;
+                // chroma lanes 0..17 top lines + corners (Cb, Cr), 32..47 left columns
+                int v = 0, gb = 0;
+                const uint2 *g = nullptr;
+                if (lane < (plane ? 18 : 17)) {
+                    const int c = plane ? lane / 9 : 0, i = plane ? lane % 9 - 1 : lane - 1;
+                    if (has_top && (i >= 0 || has_left)) {
+                        if (i >= 0 ? b_intra : d_intra) { // the granule of the intra macroblock above (above-left) that holds the sample
+                            const int k = plane ? 2 * (i >= 0 ? i : 7) + c : (i >= 0 ? i : 15); // byte of the bottom line (chroma: interleaved)
+                            g = strips + (size_t)(mbn - mbw + (i >= 0 ? 0 : -1)) * 8 + 4 * plane + (k >> 2);
+                            gb = k & 3;
+                        } else v = plane ? (int)ldg8(ruv + (size_t)(cy0 - 1) * stride + 2 * (cx0 + i) + c) : (int)ldg8(ry + (size_t)(y0 - 1) * stride + x0 + i);
+                    }
+                } else if (lane >= 32 && lane < 48 && has_left && !a_intra) {
+                    const int i = lane - 32;
+                    v = plane ? (int)ldg8(ruv + (size_t)(cy0 + (i & 7)) * stride + 2 * (cx0 - 1) + (i >> 3)) : (int)ldg8(ry + (size_t)(y0 + i) * stride + x0 - 1);
+                }
+                if (plane == 1 && lane == 0) // the luma wave has read the chroma flags of this pair's previous macroblock (intra_compute overwrites them)
+                    while (__hip_atomic_load(&L.cack, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != L.cseq) __builtin_amdgcn_s_sleep(1);
+                if (__ballot(g != nullptr)) { // wait for exactly the granules this wave reads
+                    bool pend = g != nullptr;
+                    uint2 gv = make_uint2(0u, 0u);
                     int spins = 0;
                     for (;;) {
-                        const unsigned v = ld_sc1(&a.progress[(my - 1) * MI355_PROG_STRIDE]);
-                        if ((v & ~0xFFFu) == ep && (int)(v & 0xFFFu) > mx) break;
+                        if (pend) { gv = ld64_sc1(g); pend = gv.y != tag; }
+                        if (!__ballot(pend)) break;
                         __builtin_amdgcn_s_sleep(1);
-                        if (++spins > DB_SPIN_MAX) { st_sc1(a.err, 15u); sh_bad = 1; break; } if ((spins & 1023) == 0 && ld_sc1(a.err)) { sh_bad = 1; break; }
+                        if (++spins > DB_SPIN_MAX) { if (lane == 0) st_sc1(a.err, 15u); break; }
+                        if ((spins & 1023) == 0 && __builtin_amdgcn_readfirstlane(ld_sc1(a.err))) break;
                     }
+                    if (g) v = (int)(gv.x >> (8 * gb)) & 255;
                 }
-            }
-            __syncthreads();
-            if (sh_bad) return; // uniform: the error word is set, the host reports it
-            const uint4 dec0 = ldg128(ctx->idec + (size_t)mbn * IDEC_BYTES); // the sixteen Intra_4x4 modes (ctx->intra_p == 2; zeros otherwise)
-            const uint2 dec1 = ldg64(ctx->idec + (size_t)mbn * IDEC_BYTES + 16);
-            // neighbour samples into LD.top / LD.left ([plane][i + 1] = sample i, [0] = corner)
-            if (wave == 0 && lane < 17) { // luma top line + corner
-                const int i = lane - 1;
-                int v = 0;
-                if (has_top && (i >= 0 || has_left)) {
-                    const bool from_strip = i >= 0 ? b_intra : d_intra;
-                    if (from_strip) v = (int)(ld_sc1((const unsigned *)(a.strips + (size_t)(mbn - mbw + (i >= 0 ? 0 : -1)) * 32) + ((i >= 0 ? i : 15) >> 2)) >> (8 * ((i >= 0 ? i : 15) & 3))) & 255;
-                    else v = (int)ldg8(ry + (size_t)(y0 - 1) * stride + x0 + i);
+                if (lane < (plane ? 18 : 17)) L.top[plane ? 1 + lane / 9 : 0][plane ? lane % 9 : lane] = v;
+                else if (lane >= 32 && lane < 48) {
+                    const int i = lane - 32;
+                    if (plane) L.left[1 + (i >> 3)][(i & 7) + 1] = a_intra ? (int)L.right_c[i >> 3][i & 7] : v;
+                    else L.left[0][i + 1] = a_intra ? (int)L.right_y[i] : v;
                 }
-                LD.top[0][i + 1] = v;
-            } else if (wave == 0 && lane >= 32 && lane < 48) { // luma left column
-                const int i = lane - 32;
-                LD.left[0][i + 1] = !has_left ? 0 : a_intra ? (int)LD.right_y[i] : (int)ldg8(ry + (size_t)(y0 + i) * stride + x0 - 1);
-            } else if (wave == 1 && lane < 18) { // chroma top lines + corners
-                const int c = lane / 9, i = lane % 9 - 1;
-                int v = 0;
-                if (has_top && (i >= 0 || has_left)) {
-                    const bool from_strip = i >= 0 ? b_intra : d_intra;
-                    const int k = 2 * (i >= 0 ? i : 7) + c; // byte of the interleaved 16-byte bottom chroma line
-                    if (from_strip) v = (int)(ld_sc1((const unsigned *)(a.strips + (size_t)(mbn - mbw + (i >= 0 ? 0 : -1)) * 32 + 16) + (k >> 2)) >> (8 * (k & 3))) & 255;
-                    else v = (int)ldg8(ruv + (size_t)(cy0 - 1) * stride + 2 * (cx0 + i) + c);
+                WAVE_SYNC();
+                if (lane == 0) {
+                    if (plane) { L.left[1][0] = L.top[1][0]; L.left[2][0] = L.top[2][0]; }
+                    else L.left[0][0] = L.top[0][0];
                 }
-                LD.top[1 + c][i + 1] = v;
-            } else if (wave == 1 && lane >= 32 && lane < 48) { // chroma left columns
-                const int c = (lane - 32) >> 3, i = (lane - 32) & 7;
-                LD.left[1 + c][i + 1] = !has_left ? 0 : a_intra ? (int)LD.right_c[c][i] : (int)ldg8(ruv + (size_t)(cy0 + i) * stride + 2 * (cx0 - 1) + c);
+                WAVE_SYNC();
+                intra_compute<true, true>(ctx, T, &L, mx, my, plane, lane, dec0, dec1, &src);
+                WAVE_SYNC(); // bot_* / right_* of this macroblock are in LDS
+                if (lane < 4) st64_sc1(strips + (size_t)mbn * 8 + 4 * plane + lane,
+                                       make_uint2(plane ? *(const unsigned *)&L.bot_c[mx & 3][4 * lane] : *(const unsigned *)&L.bot_y[mx & 3][4 * lane], tag));
+                if (plane == 0 && lane == 0) __hip_atomic_store(&L.cack, (unsigned)mbn + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wave's samples (and, luma, the record) are out
+                if (lane == 0) __hip_atomic_fetch_or(&dbits[plane][mx >> 5], 1u << (mx & 31), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                prev_x = mx;
             }
-            __syncthreads();
-            if (threadIdx.x == 0) { LD.left[0][0] = LD.top[0][0]; LD.left[1][0] = LD.top[1][0]; LD.left[2][0] = LD.top[2][0]; }
-            __syncthreads();
-            intra_compute<true, true>(ctx, T, &LD, mx, my, wave, lane, dec0, dec1);
-            __syncthreads(); // bot_y / bot_c / right_* of this macroblock are in LD
-            // publish the bottom lines for the row below: 32 bytes, sc1
-            if (threadIdx.x < 8) {
-                const int slot = mx & 3;
-                const unsigned v = threadIdx.x < 4 ? *(const unsigned *)&LD.bot_y[slot][4 * threadIdx.x] : *(const unsigned *)&LD.bot_c[slot][4 * (threadIdx.x - 4)];
-                st_sc1((unsigned *)(a.strips + (size_t)mbn * 32) + threadIdx.x, v);
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-#ifdef DBG_DELAY_IP /* adversarial-schedule build: every progress word comes ~20 us late, so the deblocker that follows this kernel catches up with it at every intra macroblock */
-            for (int i = 0; i < 6; i++) __builtin_amdgcn_s_sleep(127);
-#endif
-            if (threadIdx.x == 0) { // everything left of the next intra macroblock of this row (or the whole row) is final now
-                unsigned rest = bits;
-                int nx = rest ? 32 * w + __builtin_ctz(rest) : -1;
-                for (int w2 = w + 1; nx < 0 && w2 < (mbw + 31) / 32; w2++) if (ibits[w2]) nx = 32 * w2 + __builtin_ctz(ibits[w2]);
-                st_sc1(&a.progress[my * MI355_PROG_STRIDE], ep | (unsigned)(nx < 0 ? mbw : nx));
-            }
-            prev_x = mx;
         }
     }
-    if (prev_x == -2 && threadIdx.x == 0) st_sc1(&a.progress[my * MI355_PROG_STRIDE], ep | (unsigned)mbw); // no intra macroblock in this row
+    __syncthreads();
     tl_last(ctx, 6);
 }
 #endif

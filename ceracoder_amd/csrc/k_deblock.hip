@@ -930,7 +930,7 @@ DEV void qp_chain_rows(const db_args &a) {
     }
 }
 
-// FUSED_IP: the intra macroblocks of the same P picture ride in this launch -- its first a.nip workgroups run intra_p_row (two waves each, the
+// FUSED_IP: the intra macroblocks of the same P picture ride in this launch -- its first a.nip workgroups run intra_p_row (IP_THREADS threads each, the
 // other waves end at once), one macroblock row each, behind the same row counts of pmb_kernel<GATED, ROWS> the bands wait for.  As a kernel of
 // its own intra_p_kernel could only follow pmb_kernel in stream order, i.e. after its LAST row -- and with two deblocking launches in flight the
 // bands of a launch that starts early would sit at every row's first intra macroblock until then (device timeline: band 0 done 280 us after
@@ -946,7 +946,8 @@ __global__ __launch_bounds__(192 * ROWS) void deblock_rows3_kernel(db_args a) {
     }
     if (FUSED_IP) {
         if (bi < a.nip) {
-            if (threadIdx.x >= 128) return;
+            static_assert(IP_THREADS <= 192 * ROWS, "the row's wave pairs and publisher fit the workgroup");
+            if (threadIdx.x >= IP_THREADS) return;
             ip_args ia;
             ia.ctx = a.ctx; ia.progress = a.ip_progress_w; ia.strips = a.ip_strips; ia.err = a.err;
             intra_p_row(ia, bi, a.row_done, a.row_need);

@@ -906,12 +906,12 @@ void k_launch_intra_analyse(const frame_ctx_t *h_ctx, int mbw, int mbh, int gate
 }
 
 // =================================================================== intra macroblocks of P pictures (body: intra_mb.hpp, intra_p_row)
-__global__ __launch_bounds__(128) void intra_p_kernel(ip_args a) { intra_p_row(a, (int)blockIdx.x, nullptr, 0u); }
+__global__ __launch_bounds__(IP_THREADS) void intra_p_kernel(ip_args a) { intra_p_row(a, (int)blockIdx.x, nullptr, 0u); }
 void k_launch_intra_p(const frame_ctx_t *h_ctx, int mbw, int mbh, unsigned *d_progress, uint8_t *d_strips, unsigned *d_err, hipStream_t s) {
     (void)mbw;
     ip_args a;
     a.ctx = *h_ctx; a.progress = d_progress; a.strips = d_strips; a.err = d_err;
-    hipLaunchKernelGGL(intra_p_kernel, dim3(mbh), dim3(128), 0, s, a);
+    hipLaunchKernelGGL(intra_p_kernel, dim3(mbh), dim3(IP_THREADS), 0, s, a);
 }
 void k_launch_intra_diag(const frame_ctx_t *d_ctx, int mbw, int mbh, int diag, hipStream_t s) {
     int y_lo = diag - (mbw - 1) > 0 ? diag - (mbw - 1) : 0;

@@ -42,6 +42,9 @@ typedef struct {
 #ifndef MI355_PROG_STRIDE
 #define MI355_PROG_STRIDE 1024
 #endif
+/* Per macroblock of a P picture, the bottom lines an intra macroblock leaves for the row below: eight 8-byte {4 samples, epoch} granules (four of
+ * the luma line, four of the interleaved chroma line) */
+#define IP_STRIP_BYTES 64
 #define ME_ITERS 3          /* Jacobi iterations of the vector selection after the search's own (oracle: ORC_ME_ITERS) */
 #define SEL_BONUS 2         /* oracle: ORC_SEL_BONUS */
 #define SKIP_MARGIN_BITS 4  /* oracle: ORC_SKIP_MARGIN_BITS */
