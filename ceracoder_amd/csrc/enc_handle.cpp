@@ -132,6 +132,7 @@ int mi355enc_open(const mi355enc_cfg_t *cfg, mi355enc_t **out) {
     h->ysz = (size_t)h->W * h->H; h->csz = h->ysz / 2;
     h->head = h->tail = h->pending = 0;
     h->cur = 0; h->have_ref = 0; h->frames_since_idr = 0; h->idr_count = 0; h->last_collected_rec = 0; h->last_slot = nullptr;
+    h->ir_on = 0; h->ir_pos = 0; h->ir_R = 0; h->ir_skip_owed = 0;
     for (int i = 0; i < NSET; i++) { h->g_intra[i] = h->g_deblock[i] = nullptr; h->d_ctx2[i] = nullptr; h->d_surf[i] = nullptr; h->d_idec2[i] = nullptr; h->d_mbi_set[i] = nullptr; h->d_levels_set[i] = nullptr; h->d_qp_off[i] = nullptr; }
     h->prev_slot = nullptr;
     h->d_ctx = nullptr; h->d_pre_y = h->d_pre_uv = nullptr; memset(h->d_imv, 0, sizeof h->d_imv); h->d_psrc[0] = h->d_psrc[1] = nullptr; h->psrc_cur = 0; h->fstream = nullptr; h->ustream = nullptr; h->d_ip_progress = nullptr; h->d_ip_strips = nullptr; h->epoch = 0; h->istream = nullptr; h->ev_pmb = nullptr; h->d_db_gran = nullptr; h->d_db_done = nullptr; h->rec_epoch[0] = h->rec_epoch[1] = 0; h->db_started_total = 0; h->ip_done_total = 0; h->d_row_done = nullptr; h->pmb_rows_total = 0; h->d_db_par = nullptr; h->d_db_part = nullptr; h->d_ib_gran = nullptr; h->d_iband_done = nullptr; h->ev_dbI[0] = h->ev_dbI[1] = nullptr; h->dbI_busy[0] = h->dbI_busy[1] = 0; h->d_progress = nullptr; h->d_off = nullptr; h->d_isad = nullptr; h->d_dbrec = nullptr; h->d_idec = nullptr;
@@ -369,6 +370,13 @@ int mi355enc_set_fixed_qp(mi355enc_t *h, int qp) {
 int mi355enc_set_fixed_drop(mi355enc_t *h, int drop) {
     if (!h || drop < 0 || (drop > DROP_MAX && drop != DROP_SKIP)) return MI355ENC_ERR_ARG;
     h->fixed_drop.store(drop, std::memory_order_relaxed);
+    return MI355ENC_OK;
+}
+int mi355enc_set_intra_refresh(mi355enc_t *h, int on) {
+    if (!h || h->n_submitted) return MI355ENC_ERR_ARG; // (before the first submit: the stream's structure is fixed from its first picture on)
+    // gop <= 256: the recovery point SEI's recovery_frame_cnt = gop - 1 may not exceed MaxFrameNum - 1 (D.2.8), and the SPS sends frame_num in 8 bits
+    if (on && (h->cfg.intra_in_p == 0 || h->cfg.partitions || h->cfg.gop < 2 || h->cfg.gop > MI355ENC_IR_MAX_PERIOD)) return MI355ENC_ERR_ARG;
+    h->ir_on = on ? 1 : 0;
     return MI355ENC_OK;
 }
 int mi355enc_pending(const mi355enc_t *h) { return h ? h->pending : 0; }

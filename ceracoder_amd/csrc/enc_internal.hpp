@@ -55,6 +55,7 @@ struct slot_t {
     int all_skip;              // the picture is one run of P_Skip macroblocks: written by the host alone, no device work
     uint64_t index;            // position of the picture in the stream
     int is_idr, qp, drop, frame_num, idr_pic_id, rec_index, set;
+    int ir_start;              // periodic intra refresh: the first picture of a refresh cycle (SPS, PPS and a recovery point SEI lead its access unit; a sync point)
     int rc_picked;             // rate control booked this picture (rc_pick): its size is reported back (rc_update) or the booking taken back (rc_cancel)
     int64_t pts;
     // entropy coding on the handle's worker thread (pipeline_depth >= 1): the access unit is coded here while the caller submits the next picture
@@ -118,6 +119,9 @@ struct mi355enc {
     slot_t slot[NSLOT];
     int head, tail, pending;
     int cur, have_ref, frames_since_idr, idr_count, last_collected_rec;
+    // periodic intra refresh (mi355enc_set_intra_refresh): on, the cycle position j of the next P picture, the first column not yet
+    // refreshed in the current cycle, and an all-skip picture that rate control wanted for the last picture of a cycle and that moves to the next picture
+    int ir_on, ir_pos, ir_R, ir_skip_owed;
     slot_t *last_slot;
     hipGraphExec_t g_intra[NSET], g_deblock[NSET]; // per context
     h264_writer_t *writer;

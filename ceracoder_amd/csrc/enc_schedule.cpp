@@ -92,6 +92,7 @@ void fill_ctx(mi355enc_t *h, frame_ctx_t *c, int qp, int drop, int idr, int set)
     c->i8 = (idr && h->cfg.transform8x8 && h->cfg.i8x8 && h->cfg.intra_mode == 0 && !c->iac_drop && qp <= I8_QP_MAX) ? 1 : 0;
     c->qp_off = h->cfg.aq_mode ? h->d_qp_off[set] : nullptr;
     c->intra_p = h->cfg.intra_in_p ? (h->cfg.i4x4 && h->cfg.intra_in_p > 1 ? 2 : 1) : 0; // 2: Intra_4x4 as well
+    c->ir_c0 = 0; c->ir_c1 = 0; c->ir_clean = -1; // (enqueue_picture sets the refresh columns of a picture of an intra-refresh stream)
 }
 // P picture, front part (front stream): nothing here depends on the coding of the picture before
 static int run_p_front(mi355enc_t *h, const frame_ctx_t *hc, slot_t *s, int prof) {
@@ -139,9 +140,9 @@ static int run_p_back(mi355enc_t *h, const frame_ctx_t *hc, slot_t *s, int prof,
 // Enqueue every device step of one picture whose source is described by (src_y, src_uv, src_stride).  Anything the caller
 // uploaded for this picture was enqueued on the same stream.
 int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_t *src_uv, int src_stride, int64_t pts, int force_idr) {
-    const int idr = force_idr || !h->have_ref || h->frames_since_idr >= h->cfg.gop ||
+    const int idr = force_idr || !h->have_ref || (!h->ir_on && h->frames_since_idr >= h->cfg.gop) || // (intra refresh: no periodic IDR picture)
                     (h->n_submitted == h->sc_force_at && h->frames_since_idr >= sc_lag(h)); // scene-cut recovery, see collect(): not when an IDR picture came in between
-    if (idr) h->frames_since_idr = 0;
+    if (idr) { h->frames_since_idr = 0; h->ir_pos = 0; h->ir_R = 0; h->ir_skip_owed = 0; }
     // rate control: latch the setpoint written by the control thread, pick this picture's QP (and, below QP 51, its drop level)
     rc_set_bitrate(&h->rc, h->want_bps.load(std::memory_order_relaxed));
     int fq = h->fixed_qp.load(std::memory_order_relaxed);
@@ -149,6 +150,16 @@ int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_
     if (fq >= 0) { qp = fq; drop = h->fixed_drop.load(std::memory_order_relaxed); s->rc_picked = 0; } // (no pick: collect() / recover() then leave rate control alone for this picture)
     else { rc_pick(&h->rc, idr, &qp, &drop); s->rc_picked = 1; }
     if (idr && drop == DROP_SKIP) drop = 0; // an IDR picture is never skipped; it has a ladder of its own
+    // Periodic intra refresh: P picture p >= 1 after the IDR picture is picture j = (p - 1) mod N of a cycle (N = cfg.gop) and
+    // refreshes the columns [max(R - 1, 0), a(j + 1)), a(j) = floor(j * mbw / N), R the first column the cycle has not refreshed yet (= a(j) unless an
+    // all-skip picture refreshed nothing).  The last picture of a cycle is never an all-skip picture: that moves to the next one.
+    const int ir_j = (h->ir_on && !idr) ? h->ir_pos : -1; // (= (p - 1) mod N, kept as a counter of its own: p itself is unbounded on a live stream)
+    if (ir_j >= 0) {
+        if (ir_j == 0) h->ir_R = 0;
+        const bool last = ir_j == h->cfg.gop - 1;
+        if (drop == DROP_SKIP && last) { drop = DROP_MAX; h->ir_skip_owed = 1; }
+        else if (h->ir_skip_owed && !last) { drop = DROP_SKIP; h->ir_skip_owed = 0; }
+    }
     const int all_skip = !idr && drop == DROP_SKIP;
     const int nxt = all_skip ? h->cur : (h->cur ^ 1); // an all-skip picture IS its reference: nothing is written
     const int set = (int)(h->n_submitted % NSET), ci = set;
@@ -177,6 +188,13 @@ int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_
         c->vis_h = h->cfg.height;
         fill_ctx(h, c, qp, drop, idr, set);
         c->mbi = h->d_mbi_set[set]; c->levels = h->d_levels_set[set];
+        if (ir_j >= 0) {
+            const int R = h->ir_R;
+            c->ir_c0 = R > 0 ? R - 1 : 0; // (one column of overlap: deblocking left the last columns of column R - 1 dirty in the reference)
+            c->ir_c1 = (int)((long long)(ir_j + 1) * h->mbw / h->cfg.gop);
+            c->ir_clean = R > 0 ? 16 * R - 4 : -1;
+            h->ir_R = c->ir_c1;
+        }
         // Every kernel of the default path takes the context by value; only the kernels replayed from a hipGraph
         // (intra_mode 1, deblock_mode 1) read the device copy, so only those pictures pay for an upload.
         if ((idr && h->cfg.intra_mode == 1) || h->cfg.deblock_mode != 0) HIPCHK(hipMemcpyAsync(dctx, c, sizeof *c, hipMemcpyHostToDevice, h->stream));
@@ -260,11 +278,15 @@ int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_
         HIPCHK(hipEventRecord(s->done, pst));
     }
     h->n_submitted++;
-    s->is_idr = idr; s->qp = qp; s->drop = drop; s->frame_num = h->frames_since_idr; s->idr_pic_id = h->idr_count & 0xFFFF;
+    s->is_idr = idr; s->qp = qp; s->drop = drop; s->frame_num = h->frames_since_idr; s->idr_pic_id = h->idr_count & 0xFFFF; s->ir_start = ir_j == 0;
     s->src_y = src_y; s->src_uv = src_uv; s->src_stride = src_stride; s->force_idr = force_idr;
     s->pts = pts; s->rec_index = nxt; s->set = set; s->prof = prof; s->fused = fused && !idr; s->index = h->n_submitted - 1; s->all_skip = all_skip;
     if (idr) h->idr_count++;
     h->frames_since_idr++;
+    if (ir_j >= 0) h->ir_pos = ir_j + 1 < h->cfg.gop ? ir_j + 1 : 0;
+    // intra refresh: no periodic IDR picture resets the count, so it is kept bounded; frame_num is sent modulo MaxFrameNum = 256 (h264_host.c), and the
+    // count stays >= 256, past the scene-cut rule's sc_lag()
+    if (h->ir_on && h->frames_since_idr >= 512) h->frames_since_idr -= 256;
     h->cur = nxt; h->have_ref = 1; h->prev_slot = s;
     const int slot_index = (int)(s - h->slot);
     h->head = (h->head + 1) % NSLOT; h->pending++;
@@ -298,9 +320,14 @@ int upload_and_convert(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const p
 // ---- the entropy-coding worker: one picture at a time, in submission order
 static size_t code_access_unit(mi355enc_t *h, slot_t *s, uint8_t *out, size_t cap) {
     size_t n = 0;
-    if (s->is_idr) {
+    if (s->is_idr || s->ir_start) {
         n = h264_write_headers(out, cap, h->cfg.width, h->cfg.height, h->cfg.fps_num, h->cfg.fps_den, h->cfg.transform8x8);
         if (!n) return 0;
+    }
+    if (s->ir_start) { // a refresh cycle starts: a decoder that joins here outputs exact pictures from the cycle's last one on
+        const size_t k = h264_write_recovery_sei(out + n, cap - n, h->cfg.gop - 1);
+        if (!k) return 0;
+        n += k;
     }
     h264_writer_set_p_slices(h->writer, s->all_skip ? 0 : h->pslice_rows, h->slice_dbf); // (an all-skip picture is one run of P_Skip macroblocks in one slice)
     const size_t m = h264_write_slice_packed_rows(h->writer, out + n, cap - n, s->is_idr, s->frame_num, s->idr_pic_id, s->qp, s->h_mbi, s->h_levels, s->h_hdr + 2);
@@ -549,7 +576,7 @@ int mi355enc_collect(mi355enc_t *h, uint8_t *out, size_t out_cap, size_t *out_le
         h->st.ms_entropy += now_ms() - t1;
     }
     *out_len = n + m;
-    if (is_keyframe) *is_keyframe = s->is_idr;
+    if (is_keyframe) *is_keyframe = s->is_idr || s->ir_start; // (intra refresh: a cycle's first picture is a recovery point)
     if (pts) *pts = s->pts;
     if (qp) *qp = s->qp;
     if (s->rc_picked) rc_update(&h->rc, s->is_idr, s->qp, s->drop, n + m); // picks and updates stay paired: a picture coded at a fixed QP booked nothing

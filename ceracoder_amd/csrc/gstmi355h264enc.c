@@ -55,6 +55,7 @@ typedef struct {
     gint intra_slices;
     gboolean single_stream;
     gboolean dct8x8_adaptive; /* with dct8x8: the transform size is chosen per P macroblock (cfg.transform8x8 = 2) */
+    gboolean intra_refresh;   /* periodic intra refresh instead of periodic IDR pictures (mi355enc_set_intra_refresh); key-int-max is the refresh period */
     /* streaming state */
     mi355enc_t *enc;
     GstVideoCodecState *input_state;
@@ -71,7 +72,7 @@ typedef struct { GstVideoEncoderClass parent_class; } GstMi355H264EncClass;
 G_DEFINE_TYPE(GstMi355H264Enc, gst_mi355h264enc, GST_TYPE_VIDEO_ENCODER)
 
 enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME_RANGE, PROP_QP, PROP_PIPELINE_DEPTH,
-       PROP_SPEED_PRESET, PROP_STATS, PROP_DCT8X8, PROP_THREADS, PROP_SCENECUT, PROP_VBV, PROP_INTRA_IN_P, PROP_EXCLUSIVE, PROP_PINNED_INPUT, PROP_AQ_MODE, PROP_SINGLE_STREAM, PROP_INTRA_SLICES, PROP_I8X8, PROP_SLICES, PROP_SLICE_DEBLOCK, PROP_DCT8X8_ADAPTIVE };
+       PROP_SPEED_PRESET, PROP_STATS, PROP_DCT8X8, PROP_THREADS, PROP_SCENECUT, PROP_VBV, PROP_INTRA_IN_P, PROP_EXCLUSIVE, PROP_PINNED_INPUT, PROP_AQ_MODE, PROP_SINGLE_STREAM, PROP_INTRA_SLICES, PROP_I8X8, PROP_SLICES, PROP_SLICE_DEBLOCK, PROP_DCT8X8_ADAPTIVE, PROP_INTRA_REFRESH };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
     GST_STATIC_CAPS("video/x-raw, format=(string){ NV12, I420, YUY2, UYVY }, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]"));
@@ -141,6 +142,7 @@ static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *
     case PROP_STATS: s->stats = g_value_get_boolean(val); break;
     case PROP_DCT8X8: s->dct8x8 = g_value_get_boolean(val) ? 1 : 0; break;
     case PROP_DCT8X8_ADAPTIVE: s->dct8x8_adaptive = g_value_get_boolean(val); break;
+    case PROP_INTRA_REFRESH: s->intra_refresh = g_value_get_boolean(val); break;
     case PROP_THREADS: s->threads = g_value_get_int(val); break;
     case PROP_SCENECUT: s->scenecut = g_value_get_boolean(val); break;
     case PROP_EXCLUSIVE: s->exclusive_gpu = g_value_get_boolean(val); break;
@@ -174,6 +176,7 @@ static void get_property(GObject *obj, guint id, GValue *val, GParamSpec *ps) {
     case PROP_STATS: g_value_set_boolean(val, s->stats); break;
     case PROP_DCT8X8: g_value_set_boolean(val, t.dct8x8 != 0); break;
     case PROP_DCT8X8_ADAPTIVE: g_value_set_boolean(val, s->dct8x8_adaptive); break;
+    case PROP_INTRA_REFRESH: g_value_set_boolean(val, s->intra_refresh); break;
     case PROP_THREADS: g_value_set_int(val, s->threads); break;
     case PROP_SCENECUT: g_value_set_boolean(val, s->scenecut); break;
     case PROP_EXCLUSIVE: g_value_set_boolean(val, s->exclusive_gpu); break;
@@ -245,8 +248,11 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
         if (t.slices >= 0) cfg.slices = t.slices;               /* (-1: mi355enc_default_cfg's) */
         if (t.slice_deblock >= 0) cfg.slice_deblock = t.slice_deblock;
     }
+    const gboolean intra_refresh = s->intra_refresh;
+    if (intra_refresh) { cfg.partitions = 0; if (!cfg.intra_in_p) cfg.intra_in_p = 1; } /* (the refresh columns are intra macroblocks of P pictures; no partitions) */
     GST_OBJECT_UNLOCK(s);
     int r = mi355enc_open(&cfg, &e);
+    if (r == MI355ENC_OK && intra_refresh) r = mi355enc_set_intra_refresh(e, 1); /* (refused with key-int-max < 2) */
     if (r != MI355ENC_OK) {
         if (e) mi355enc_close(e);
         GST_ELEMENT_ERROR(s, LIBRARY, INIT, ("mi355h264enc: cannot open the MI355X encoder: %s", mi355enc_strerror(r)),
@@ -307,7 +313,7 @@ static GstFlowReturn collect_into(GstMi355H264Enc *s, GstVideoCodecFrame *frame)
     if (GST_CLOCK_TIME_IS_VALID(frame->pts) && GST_CLOCK_TIME_IS_VALID(s->last_pts) && frame->pts < s->last_pts) frame->pts = s->last_pts;
     if (GST_CLOCK_TIME_IS_VALID(frame->pts)) s->last_pts = frame->pts;
     frame->dts = frame->pts;
-    GST_LOG_OBJECT(s, "access unit %" G_GSIZE_FORMAT " bytes, %s, qp %d, pts %" GST_TIME_FORMAT, len, key ? "IDR" : "P", qp, GST_TIME_ARGS(frame->pts));
+    GST_LOG_OBJECT(s, "access unit %" G_GSIZE_FORMAT " bytes, %s, qp %d, pts %" GST_TIME_FORMAT, len, key ? "sync point" : "P", qp, GST_TIME_ARGS(frame->pts));
     const gint64 t2 = g_get_monotonic_time();
     s->us_output += t2 - t1;
     fr = gst_video_encoder_finish_frame(ve, frame); /* the base class's bookkeeping and the push into whatever follows (a queue in the reference's pipelines) */
@@ -481,6 +487,10 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
     g_object_class_install_property(g, PROP_DCT8X8_ADAPTIVE, g_param_spec_boolean("dct8x8-adaptive", "Per-macroblock transform size",
         "With dct8x8: every coded P macroblock chooses between the 4x4 and the 8x8 transform (SA8D against SATD of its prediction residual), as x264enc's dct8x8 does; "
         "without dct8x8 ignored. speed-preset does not set it", FALSE, F));
+    g_object_class_install_property(g, PROP_INTRA_REFRESH, g_param_spec_boolean("intra-refresh", "Intra refresh",
+        "Use periodic intra refresh instead of IDR frames, as in x264enc: a column of intra macroblocks sweeps the picture once every key-int-max frames "
+        "(2 .. 256; opening fails otherwise), which start with SPS, PPS and a recovery point SEI and are marked as sync points; IDR frames only for the first frame, forced key units and "
+        "scene cuts. Implies intra macroblocks in P frames and no partitions", FALSE, F));
     g_object_class_install_property(g, PROP_STATS, g_param_spec_boolean("stats", "Print stats", "Print a JSON line with counters when the encoder closes", FALSE, F));
     gst_element_class_add_static_pad_template(e, &sink_tmpl);
     gst_element_class_add_static_pad_template(e, &src_tmpl);
@@ -491,7 +501,7 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
 }
 static void gst_mi355h264enc_init(GstMi355H264Enc *s) {
     s->rate_raw = 2048; s->rate_is_bps = FALSE; s->key_int_max = 60; s->device_id = 0; s->me_range = 16; s->qp = -1; s->pipeline_depth = 0; s->speed_preset = 0;
-    s->stats = FALSE; s->dct8x8 = -1; s->threads = 0; s->scenecut = TRUE; s->exclusive_gpu = FALSE; s->vbv_ms = 600; s->intra_in_p = -1; s->pinned_input = TRUE; s->aq_mode = -1; s->slices = -1; s->slice_deblock = -1; s->intra_slices = 0; s->i8x8 = -1; s->single_stream = FALSE; s->dct8x8_adaptive = FALSE; s->enc = NULL; s->input_state = NULL; s->max_au = 0; s->au_buf = NULL; s->last_pts = GST_CLOCK_TIME_NONE;
+    s->stats = FALSE; s->dct8x8 = -1; s->threads = 0; s->scenecut = TRUE; s->exclusive_gpu = FALSE; s->vbv_ms = 600; s->intra_in_p = -1; s->pinned_input = TRUE; s->aq_mode = -1; s->slices = -1; s->slice_deblock = -1; s->intra_slices = 0; s->i8x8 = -1; s->single_stream = FALSE; s->dct8x8_adaptive = FALSE; s->intra_refresh = FALSE; s->enc = NULL; s->input_state = NULL; s->max_au = 0; s->au_buf = NULL; s->last_pts = GST_CLOCK_TIME_NONE;
     s->us_map = s->us_submit = s->us_collect = s->us_output = s->us_push = s->us_frames = 0;
 }
 

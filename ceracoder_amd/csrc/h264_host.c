@@ -152,6 +152,27 @@ size_t h264_write_headers(uint8_t *out, size_t cap, int width, int height, int f
     return a + c;
 }
 
+/* 7.3.2.3 sei_rbsp with one D.1.8 recovery_point message; nal_ref_idc 0 */
+size_t h264_write_recovery_sei(uint8_t *out, size_t cap, int recovery_frame_cnt) {
+    uint8_t pl[16], rb[24];
+    bits_t b;
+    bits_init(&b, pl, sizeof pl);
+    bits_ue(&b, (uint32_t)recovery_frame_cnt);
+    bits_put(&b, 1, 1); /* exact_match_flag */
+    bits_put(&b, 1, 0); /* broken_link_flag */
+    bits_put(&b, 2, 0); /* changing_slice_group_idc */
+    /* the payload is 2k + 1 + 4 bits, never byte-aligned: sei_payload ends with bit_equal_to_one and zeros up to the byte boundary (what bits_finish writes) */
+    const size_t np = bits_finish(&b, pl);
+    if (b.overflow || np > sizeof rb - 3) return 0;
+    size_t n = 0;
+    rb[n++] = 6;           /* payloadType: recovery point */
+    rb[n++] = (uint8_t)np; /* payloadSize */
+    memcpy(rb + n, pl, np);
+    n += np;
+    rb[n++] = 0x80;        /* rbsp_trailing_bits */
+    return emit_nal(out, cap, 0, 6, rb, n);
+}
+
 /* ------------------------------------------------------------------ residual block (9.2) */
 /* coef: 16 int16 in scan order, 16-byte aligned group; `skip_first` drops coef[0]
  * (Intra16x16 AC / chroma AC: maxNumCoeff 15).  Returns TotalCoeff. */

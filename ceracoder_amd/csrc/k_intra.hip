@@ -312,6 +312,9 @@ __global__ __launch_bounds__(256) void intra_analyse_kernel(const frame_ctx_t cv
 // P pictures: only the macroblocks whose search cost reaches the gate; the others leave at once.  (r04 tried a wave per EIGHT macroblocks, analysing the gated ones one after
 // the other, as the later selection passes do: 5 % FEWER frames/s at 1080p, +-0 at 2160p -- an analysis is a microsecond or two of work, and a wave with three of them in a row
 // makes the launch, which sits between the selection and the fused stage, longer than the 8 160 waves it saves are worth.)
+// IR: periodic intra refresh -- the refresh columns pass the gate (pmb_kernel codes them intra whatever they cost).  The one read of the unrefreshed side an
+// intra macroblock could make, Intra_4x4 block 5's above-right samples (modes 3 and 7) in the rightmost refresh column, mode4_ok never allows.
+template <bool IR = false>
 __global__ __launch_bounds__(256) void intra_analyse_gated_kernel(const frame_ctx_t cv) {
     const frame_ctx_t *__restrict__ ctx = &cv;
     const int nmb = ctx->mbw * ctx->mbh;
@@ -319,7 +322,11 @@ __global__ __launch_bounds__(256) void intra_analyse_gated_kernel(const frame_ct
     const int mbn = blockIdx.x * 4 + wave;
     if (mbn >= nmb) return;
     const uint2 iv = ldg64(k_final_imv_dev(ctx) + mbn);
-    if ((iv.y & 0xFFFFu) + (unsigned)ctx->lambda * (iv.y >> 16) < INTRA_GATE(ctx->lambda)) return;
+    if ((iv.y & 0xFFFFu) + (unsigned)ctx->lambda * (iv.y >> 16) < INTRA_GATE(ctx->lambda)) {
+        if (!IR) return;
+        const int mx = mbn % ctx->mbw;
+        if (mx < ctx->ir_c0 || mx >= ctx->ir_c1) return;
+    }
     intra_analyse_mb<true>(ctx, mbn, true, lane, wave);
 }
 // One launch per anti-diagonal x + y (replayed as a hipGraph): neighbours come from the reconstructed picture in global
@@ -901,7 +908,8 @@ void k_launch_intra_rows(const frame_ctx_t *h_ctx, int mbh, uint2 *d_gran, unsig
 // =================================================================== launchers
 int k_intra_diags(int mbw, int mbh) { return mbw + mbh - 1; }
 void k_launch_intra_analyse(const frame_ctx_t *h_ctx, int mbw, int mbh, int gate_p, hipStream_t s) {
-    if (gate_p) hipLaunchKernelGGL(intra_analyse_gated_kernel, dim3((mbw * mbh + 3) / 4), dim3(256), 0, s, *h_ctx);
+    if (gate_p && h_ctx->ir_c1 > 0) hipLaunchKernelGGL(intra_analyse_gated_kernel<true>, dim3((mbw * mbh + 3) / 4), dim3(256), 0, s, *h_ctx); // (refresh columns in this picture)
+    else if (gate_p) hipLaunchKernelGGL(intra_analyse_gated_kernel<false>, dim3((mbw * mbh + 3) / 4), dim3(256), 0, s, *h_ctx);
     else hipLaunchKernelGGL(intra_analyse_kernel, dim3((mbw * mbh + 3) / 4), dim3(256), 0, s, *h_ctx);
 }
 

@@ -814,15 +814,39 @@ DEV pmb_pre_t pmb_preload(const frame_ctx_t *__restrict__ ctx, const int mbn, co
     p.ds = (unsigned)*(const GAS uint16_t *)(ctx->surf + (size_t)mbn * SURF_U16 + ((p.fp.sy >> 2) + 16) * SURF_COLS + (p.fp.sx >> 2) + 16);
     return p;
 }
+// Periodic intra refresh: may the inter macroblock of column mx predict from horizontal luma vector mvx (quarter samples)?  Left of the
+// refresh columns (mx < ir_c0) it reads the clean part of the reference only: luma columns <= ir_clean counting the six-tap support of a quarter-sample
+// position, chroma columns <= ir_clean / 2 counting the bilinear neighbour of an eighth-sample one (8.4.2.2).  Wave-uniform.
+DEV bool ir_ok(const frame_ctx_t *__restrict__ ctx, int mx, int mvx) {
+    return mx >= ctx->ir_c0 || (16 * mx + 15 + (mvx >> 2) + ((mvx & 3) ? 3 : 0) <= ctx->ir_clean && 8 * mx + 7 + (mvx >> 3) + ((mvx & 7) ? 1 : 0) <= (ctx->ir_clean >> 1));
+}
+// the largest whole-sample vector (quarter-sample units) ir_ok accepts in column mx < ir_c0
+DEV int ir_max_whole(const frame_ctx_t *__restrict__ ctx, int mx) {
+    const int kl = ctx->ir_clean - 16 * mx - 15, kc = 2 * ((ctx->ir_clean >> 1) - 8 * mx - 7); // luma: k <= kl; chroma: ceil(k / 2) <= kc / 2
+    return 4 * (kl < kc ? kl : kc);
+}
+// an intra macroblock of a P picture: type and modes from the analysis (dw: idec words 4 .. 7), intra_p_kernel reconstructs
+template <bool SC1>
+DEV void pmb_store_intra(mb_info_t *mb, const uint4 dw, int qp, int lane) {
+    if (lane == 0) {
+        const bool i4 = ((dw.x >> 16) & 255u) != 0;
+        mb_info_t m;
+        m.mvx = 0; m.mvy = 0; m.mb_type = i4 ? 2 : 0; m.i16_mode = i4 ? 0 : (uint8_t)(dw.x & 255u); m.chroma_mode = (uint8_t)((dw.x >> 8) & 255u);
+        m.qp = (uint8_t)qp; m.nzmask = 0; m.cost = dw.y;
+        st_mbinfo_x<SC1>(mb, m);
+    }
+}
 // T8: 0 the 4x4 transform, 1 the 8x8 transform for every coded inter macroblock, 2 the choice of pmb_pick_t8 per macroblock
-template <bool SC1, bool PART, int T8>
+// IR: periodic intra refresh -- the picture's refresh columns are intra before any inter work, and the vectors left of them stay inside the clean part
+template <bool SC1, bool PART, int T8, bool IR>
 DEV void pmb_mb(const frame_ctx_t *__restrict__ ctx, sp_lds *L, const int mbn, const int lane, const int refine, const pmb_pre_t &pre) {
     const int mbw = ctx->mbw, mbh = ctx->mbh, stride = ctx->stride, W = mbw * 16, H = mbh * 16, qp = mb_qp_dev(ctx, mbn), lambda = ctx->lambda; // (quantisation only: search, refinement and decisions keep the picture's lambda)
     const int my = mbn / mbw, mx = mbn - my * mbw, x0 = mx * 16, y0 = my * 16;
     const dev_tables *T = &g_tab;
     PMB_MARK0();
     const uint2 selfw = pre.selfw;
-    const int imx = (int)(int16_t)(selfw.x & 0xFFFF), imy = (int)(int16_t)(selfw.x >> 16); // whole-sample winner, quarter-sample units
+    int imx = (int)(int16_t)(selfw.x & 0xFFFF); // whole-sample winner, quarter-sample units
+    const int imy = (int)(int16_t)(selfw.x >> 16);
     const unsigned di = selfw.y & 0xFFFFu, ibits = selfw.y >> 16;
     const fpred_t fp = pre.fp;
     const int pr = lane >> 2, pc = (lane & 3) * 4; // luma: lane owns row pr, columns pc .. pc+3
@@ -837,11 +861,17 @@ DEV void pmb_mb(const frame_ctx_t *__restrict__ ctx, sp_lds *L, const int mbn, c
     }
     int16_t *lv = ctx->levels + (size_t)mbn * MB_LEVELS;
     mb_info_t *mb = &ctx->mbi[mbn];
+    if (IR && mx >= ctx->ir_c0 && mx < ctx->ir_c1) { // a refresh column: intra at every drop level (the analysis ran for it whatever its search cost)
+        pmb_store_intra<SC1>(mb, pre.dw, qp, lane);
+        PMB_FLUSH();
+        return;
+    }
     // ---- 2. skip probe
     {
         const unsigned ds = pre.ds;
-        bool pass = ctx->drop_sad && ds < ctx->drop_sad;
-        const bool worth = ds <= di + (unsigned)(lambda * SKIP_MARGIN_BITS);
+        const bool skip_ok = !IR || ir_ok(ctx, mx, fp.sx); // (IR: an illegal skip vector means the macroblock is not skipped)
+        bool pass = ctx->drop_sad && ds < ctx->drop_sad && skip_ok;
+        const bool worth = ds <= di + (unsigned)(lambda * SKIP_MARGIN_BITS) && skip_ok;
         PMB_MARK(0); // the field, the predictors and the skip candidate's SAD have arrived
         if (pass || worth) {
             const int X = x0 + (fp.sx >> 2), Y = y0 + (fp.sy >> 2);
@@ -871,6 +901,7 @@ DEV void pmb_mb(const frame_ctx_t *__restrict__ ctx, sp_lds *L, const int mbn, c
         }
     }
     // ---- 3. refinement around the whole-sample winner
+    if (IR && !ir_ok(ctx, mx, imx)) imx = ir_max_whole(ctx, mx); // (only column ir_c0 - 1 can get here: vectors reach 16.75 samples)
     const int ix = x0 + (imx >> 2), iy = y0 + (imy >> 2);
     const uint8_t *__restrict__ ref = ctx->ref_y;
     if (ix - 3 >= 0 && iy - 3 >= 0 && ((ix - 3) & ~3) + 28 <= W && iy + 19 < H) {
@@ -927,7 +958,7 @@ DEV void pmb_mb(const frame_ctx_t *__restrict__ ctx, sp_lds *L, const int mbn, c
                 const int qx = cqx + (k % 3 - 1) * 2, qy = cqy + (k / 3 - 1) * 2;
                 const unsigned sad = (acc[c8 >> 1] >> (16 * (c8 & 1))) & 0xFFFFu;
                 const unsigned cost = sad + (unsigned)(lambda * (mvq_bits(qx - fp.px) + mvq_bits(qy - fp.py)));
-                if (cost < best) { best = cost; bqx = qx; bqy = qy; }
+                if (cost < best && (!IR || ir_ok(ctx, mx, qx))) { best = cost; bqx = qx; bqy = qy; }
             }
         }
         hbx = bqx; hby = bqy;
@@ -952,7 +983,7 @@ DEV void pmb_mb(const frame_ctx_t *__restrict__ ctx, sp_lds *L, const int mbn, c
                 }
                 const unsigned d = pmb_satd(lane, curw, cw) >> 1;
                 const unsigned cost = d + (unsigned)(lambda * (mvq_bits(qx - fp.px) + mvq_bits(qy - fp.py)));
-                if (cost < best) { best = cost; bqx = qx; bqy = qy; }
+                if (cost < best && (!IR || ir_ok(ctx, mx, qx))) { best = cost; bqx = qx; bqy = qy; }
             }
         }
     }
@@ -1008,13 +1039,7 @@ DEV void pmb_mb(const frame_ctx_t *__restrict__ ctx, sp_lds *L, const int mbn, c
         const uint4 dw = pre.dw;
         const unsigned jintra = dw.z + (dw.z >> 3) + (unsigned)(lambda * 12);
         if (jintra < jinter) {
-            if (lane == 0) {
-                const bool i4 = ((dw.x >> 16) & 255u) != 0;
-                mb_info_t m;
-                m.mvx = 0; m.mvy = 0; m.mb_type = i4 ? 2 : 0; m.i16_mode = i4 ? 0 : (uint8_t)(dw.x & 255u); m.chroma_mode = (uint8_t)((dw.x >> 8) & 255u);
-                m.qp = (uint8_t)qp; m.nzmask = 0; m.cost = dw.y;
-                st_mbinfo_x<SC1>(mb, m);
-            }
+            pmb_store_intra<SC1>(mb, dw, qp, lane);
             PMB_FLUSH();
             return;
         }
@@ -1100,7 +1125,7 @@ DEV void pmb_mb(const frame_ctx_t *__restrict__ ctx, sp_lds *L, const int mbn, c
 // and resident, takes its macroblocks row by row behind them.
 // ROWS (only with GATED): the picture's deblocking launch is already on the chip and waits for this kernel's rows -- samples and records
 // are stored through to memory (sc1) and every macroblock is counted for its row.
-template <bool GATED, bool ROWS, bool PART, int T8>
+template <bool GATED, bool ROWS, bool PART, int T8, bool IR = false>
 __global__ __launch_bounds__(256) void pmb_kernel(const frame_ctx_t cv, int mb0, int mb1, int refine, const unsigned *__restrict__ gate_done, unsigned ref_epoch, unsigned *err, unsigned *row_done) {
     const frame_ctx_t *__restrict__ ctx = &cv;
     __shared__ __attribute__((aligned(16))) sp_lds LD[4];
@@ -1143,7 +1168,7 @@ __global__ __launch_bounds__(256) void pmb_kernel(const frame_ctx_t cv, int mb0,
         tl_last(ctx, 3);
     }
     if (mbn >= mb1) return; // wave-uniform
-    pmb_mb<ROWS, PART, T8>(ctx, &LD[wave], mbn, lane, refine, pre);
+    pmb_mb<ROWS, PART, T8, IR>(ctx, &LD[wave], mbn, lane, refine, pre);
     if (ROWS) { // this macroblock's samples and record are in memory: count it for its row (the picture's deblocking launch, already on the chip, waits for whole rows)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (lane == 0) __hip_atomic_fetch_add(row_done + (mbn / ctx->mbw) * MI355_PROG_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1211,7 +1236,20 @@ void k_launch_pmb(const frame_ctx_t *h_ctx, int mbw, int row0, int row1, int ref
     const int n = mbw * (row1 - row0), g = (n + 3) / 4;
     if (n <= 0) return;
 #define PMB_LAUNCH(G, R, P, T) hipLaunchKernelGGL((pmb_kernel<G, R, P, T>), dim3(g), dim3(256), 0, s, *h_ctx, row0 * mbw, row1 * mbw, refine, gate_done, ref_epoch, d_err, d_row_done)
-    if (h_ctx->t8 == 2) { // High profile, 4x4 or 8x8 transform chosen per inter macroblock
+#define PMB_LAUNCH_IR(G, R, T) hipLaunchKernelGGL((pmb_kernel<G, R, false, T, true>), dim3(g), dim3(256), 0, s, *h_ctx, row0 * mbw, row1 * mbw, refine, gate_done, ref_epoch, d_err, d_row_done)
+    if (h_ctx->ir_c1 > 0) { // periodic intra refresh (never with partitions: mi355enc_set_intra_refresh refuses them); a picture without refresh columns has no clean bound either
+        if (h_ctx->t8 == 2) {
+            if (gate_done && d_row_done) PMB_LAUNCH_IR(true, true, 2);
+            else if (gate_done) PMB_LAUNCH_IR(true, false, 2);
+            else PMB_LAUNCH_IR(false, false, 2);
+        } else if (h_ctx->t8) {
+            if (gate_done && d_row_done) PMB_LAUNCH_IR(true, true, 1);
+            else if (gate_done) PMB_LAUNCH_IR(true, false, 1);
+            else PMB_LAUNCH_IR(false, false, 1);
+        } else if (gate_done && d_row_done) PMB_LAUNCH_IR(true, true, 0);
+        else if (gate_done) PMB_LAUNCH_IR(true, false, 0);
+        else PMB_LAUNCH_IR(false, false, 0);
+    } else if (h_ctx->t8 == 2) { // High profile, 4x4 or 8x8 transform chosen per inter macroblock
         if (gate_done && d_row_done) PMB_LAUNCH(true, true, false, 2);
         else if (gate_done) PMB_LAUNCH(true, false, false, 2);
         else PMB_LAUNCH(false, false, false, 2);
@@ -1227,4 +1265,5 @@ void k_launch_pmb(const frame_ctx_t *h_ctx, int mbw, int row0, int row1, int ref
     else if (gate_done) PMB_LAUNCH(true, false, false, 0);
     else PMB_LAUNCH(false, false, false, 0);
 #undef PMB_LAUNCH
+#undef PMB_LAUNCH_IR
 }

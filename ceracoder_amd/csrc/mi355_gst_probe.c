@@ -167,11 +167,11 @@ int main(int argc, char **argv) {
             if (!enc) enc = gst_bin_get_by_name(GST_BIN(pipe), "venc_kbps");
             if (!enc) { fprintf(stderr, "--props needs an element named venc_bps or venc_kbps\n"); return 2; }
             gint preset = 0, aq = 0, iip = 0, slices = 0, islices = 0;
-            gboolean dct = FALSE, dcta = FALSE, i8 = FALSE, sdb = FALSE;
+            gboolean dct = FALSE, dcta = FALSE, i8 = FALSE, sdb = FALSE, irf = FALSE;
             g_object_get(enc, "speed-preset", &preset, "dct8x8", &dct, "dct8x8-adaptive", &dcta, "i8x8", &i8, "aq-mode", &aq, "intra-in-p", &iip, "slices", &slices,
-                         "slice-deblock", &sdb, "intra-slices", &islices, NULL);
-            printf("{\"speed_preset\":%d,\"dct8x8\":%d,\"dct8x8_adaptive\":%d,\"i8x8\":%d,\"aq_mode\":%d,\"intra_in_p\":%d,\"slices\":%d,\"slice_deblock\":%d,\"intra_slices\":%d,\"has_partitions_property\":%d}\n",
-                   preset, dct, dcta, i8, aq, iip, slices, sdb, islices, g_object_class_find_property(G_OBJECT_GET_CLASS(enc), "partitions") != NULL);
+                         "slice-deblock", &sdb, "intra-slices", &islices, "intra-refresh", &irf, NULL);
+            printf("{\"speed_preset\":%d,\"dct8x8\":%d,\"dct8x8_adaptive\":%d,\"i8x8\":%d,\"aq_mode\":%d,\"intra_in_p\":%d,\"slices\":%d,\"slice_deblock\":%d,\"intra_slices\":%d,\"intra_refresh\":%d,\"has_partitions_property\":%d}\n",
+                   preset, dct, dcta, i8, aq, iip, slices, sdb, islices, irf, g_object_class_find_property(G_OBJECT_GET_CLASS(enc), "partitions") != NULL);
             return 0;
         }
     for (int i = 2; i < argc; i++) {

@@ -97,6 +97,11 @@ typedef struct {
     int32_t slice_dbf;             /* disable_deblocking_filter_idc of the picture's slices: 0 the deblocking filter runs across slice boundaries, 2 it stops at them
                                       (slice_rows is then a multiple of MI355_BAND_ROWS: a band of the deblocker never spans two slices) */
     int32_t i8;                    /* I pictures: try Intra_8x8 (High profile; intra_mode 0 only: the macroblock above-right has to be complete) */
+    /* periodic intra refresh (P pictures of a stream with mi355enc_set_intra_refresh; all three 0 / 0 / -1 otherwise): the macroblocks of columns
+       [ir_c0, ir_c1) are intra whatever they cost, and every inter macroblock of a column < ir_c0 predicts from reference luma columns <= ir_clean
+       and chroma columns <= ir_clean / 2 only (the clean part: DESIGN.md section 9) */
+    int32_t ir_c0, ir_c1;
+    int32_t ir_clean;
 } frame_ctx_t;
 
 #ifdef __cplusplus

@@ -30,7 +30,7 @@ STAGE_ME, STAGE_INTER, STAGE_INTRA, STAGE_DEBLOCK, STAGE_SUBPEL, STAGE_CSC_I420,
 
 EXPORTS = [
     "mi355enc_abi_version", "mi355enc_strerror", "mi355enc_default_cfg", "mi355enc_open", "mi355enc_close",
-    "mi355enc_set_bitrate", "mi355enc_get_bitrate", "mi355enc_set_fixed_qp", "mi355enc_set_fixed_drop", "mi355enc_stage_me_select", "mi355enc_stage_me_select_next", "mi355enc_encode", "mi355enc_submit",
+    "mi355enc_set_bitrate", "mi355enc_get_bitrate", "mi355enc_set_fixed_qp", "mi355enc_set_fixed_drop", "mi355enc_set_intra_refresh", "mi355enc_stage_me_select", "mi355enc_stage_me_select_next", "mi355enc_encode", "mi355enc_submit",
     "mi355enc_submit_device", "mi355enc_pending", "mi355enc_collect", "mi355enc_get_stats", "mi355enc_reset_stats",
     "mi355enc_max_au_bytes", "mi355enc_fetch", "mi355enc_mb_width", "mi355enc_mb_height", "mi355enc_stage_me",
     "mi355enc_stage_subpel", "mi355enc_stage_inter", "mi355enc_stage_pmb", "mi355enc_stage_intra", "mi355enc_stage_intra_analyse", "mi355enc_stage_csc", "mi355enc_submit_fmt", "mi355enc_host_write_slice_packed", "mi355enc_stage_deblock", "mi355enc_time_stage",
@@ -77,6 +77,7 @@ def load():
         L.mi355enc_get_bitrate.argtypes = [vp]
         L.mi355enc_set_fixed_qp.argtypes = [vp, C.c_int]
         L.mi355enc_set_fixed_drop.argtypes = [vp, C.c_int]
+        L.mi355enc_set_intra_refresh.argtypes = [vp, C.c_int]
         L.mi355enc_encode.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, vp, C.c_size_t,
                                       C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
         L.mi355enc_submit.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int]
@@ -242,7 +243,7 @@ class Encoder:
     (bitrate in bits/s as written through `bps`, key-int-max -> gop)."""
 
     def __init__(self, width, height, fps=60, gop=60, bitrate_bps=6_000_000, device_id=0, fixed_qp=-1, me_range=16,
-                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror"):
+                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False):
         self.L = load()
         cfg = Cfg()
         self.L.mi355enc_default_cfg(C.byref(cfg), width, height, fps, fps_den)
@@ -281,6 +282,8 @@ class Encoder:
         self.width, self.height = width, height
         self.mbw, self.mbh = self.L.mi355enc_mb_width(self.h), self.L.mi355enc_mb_height(self.h)
         self._out = np.empty(self.L.mi355enc_max_au_bytes(self.h), np.uint8)
+        if intra_refresh:  # periodic intra refresh instead of periodic IDR pictures (refresh period: gop)
+            self._chk(self.L.mi355enc_set_intra_refresh(self.h, 1), "set_intra_refresh", close_on_fail=True)
 
     def _chk(self, r, what, close_on_fail=False):
         if r != 0:
@@ -305,6 +308,9 @@ class Encoder:
 
     def set_fixed_drop(self, drop):
         self._chk(self.L.mi355enc_set_fixed_drop(self.h, int(drop)), "set_fixed_drop")
+
+    def set_intra_refresh(self, on):
+        self._chk(self.L.mi355enc_set_intra_refresh(self.h, int(bool(on))), "set_intra_refresh")
 
     def encode(self, y, uv, pts=0, force_idr=False):
         y = np.ascontiguousarray(y, np.uint8)

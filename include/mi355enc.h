@@ -176,6 +176,16 @@ int mi355enc_set_fixed_qp(mi355enc_t *h, int qp);
 /* With a constant QP: the level of rate control's ladder below QP 51 for the next P pictures (tests): 0 off .. 12: P macroblocks
  * whose prediction error is small enough carry no residual / take the P_Skip vector; 255: whole pictures as one P_Skip run. */
 int mi355enc_set_fixed_drop(mi355enc_t *h, int drop);
+/* Periodic intra refresh instead of periodic IDR pictures (x264's intra-refresh), off by default.  Valid only before the
+ * first submit.  On: an IDR picture is coded only for the first picture, a forced key unit, a scene cut or a recovery re-encode, never because
+ * cfg.gop pictures have passed.  Instead a column of intra macroblocks sweeps the picture from left to right once every cfg.gop (= N) P pictures,
+ * and the inter macroblocks left of it predict only from the part of the reference it has refreshed.  The access unit of every cycle's first
+ * picture carries SPS, PPS and a recovery point SEI (recovery_frame_cnt N - 1, exact_match_flag 1), and collect() reports it as a keyframe: a
+ * decoder that starts there outputs exact pictures from N - 1 pictures later on.  MI355ENC_ERR_ARG after the first submit, and for `on` with
+ * cfg.intra_in_p 0, cfg.partitions, cfg.gop < 2 or cfg.gop > MI355ENC_IR_MAX_PERIOD (recovery_frame_cnt = N - 1 must stay below MaxFrameNum,
+ * which the SPS fixes at 256).  The single-stage entry points ignore it. */
+#define MI355ENC_IR_MAX_PERIOD 256
+int mi355enc_set_intra_refresh(mi355enc_t *h, int on);
 
 /* Synchronous: one NV12 picture in host memory -> one Annex-B access unit
  * (SPS+PPS precede every IDR).  Borrowed input, caller-owned output. */
