@@ -133,6 +133,7 @@ int mi355enc_open(const mi355enc_cfg_t *cfg, mi355enc_t **out) {
     h->head = h->tail = h->pending = 0;
     h->cur = 0; h->have_ref = 0; h->frames_since_idr = 0; h->idr_count = 0; h->last_collected_rec = 0; h->last_slot = nullptr;
     h->ir_on = 0; h->ir_pos = 0; h->ir_R = 0; h->ir_skip_owed = 0;
+    h->in_w = cfg->width; h->in_h = cfg->height; h->sar_w = h->sar_h = 0; h->scaling = false; h->d_scale_tab = nullptr; h->scale_tab_bytes = 0; memset(&h->scale, 0, sizeof h->scale);
     for (int i = 0; i < NSET; i++) { h->g_intra[i] = h->g_deblock[i] = nullptr; h->d_ctx2[i] = nullptr; h->d_surf[i] = nullptr; h->d_idec2[i] = nullptr; h->d_mbi_set[i] = nullptr; h->d_levels_set[i] = nullptr; h->d_qp_off[i] = nullptr; }
     h->prev_slot = nullptr;
     h->d_ctx = nullptr; h->d_pre_y = h->d_pre_uv = nullptr; memset(h->d_imv, 0, sizeof h->d_imv); h->d_psrc[0] = h->d_psrc[1] = nullptr; h->psrc_cur = 0; h->fstream = nullptr; h->ustream = nullptr; h->d_ip_progress = nullptr; h->d_ip_strips = nullptr; h->epoch = 0; h->istream = nullptr; h->ev_pmb = nullptr; h->d_db_gran = nullptr; h->d_db_done = nullptr; h->rec_epoch[0] = h->rec_epoch[1] = 0; h->db_started_total = 0; h->ip_done_total = 0; h->d_row_done = nullptr; h->pmb_rows_total = 0; h->d_db_par = nullptr; h->d_db_part = nullptr; h->d_ib_gran = nullptr; h->d_iband_done = nullptr; h->ev_dbI[0] = h->ev_dbI[1] = nullptr; h->dbI_busy[0] = h->dbI_busy[1] = 0; h->d_progress = nullptr; h->d_off = nullptr; h->d_isad = nullptr; h->d_dbrec = nullptr; h->d_idec = nullptr;
@@ -337,6 +338,7 @@ void mi355enc_close(mi355enc_t *h) {
     if (h->d_iband_done) (void)hipFree(h->d_iband_done);
     for (int i = 0; i < 2; i++) if (h->ev_dbI[i]) (void)hipEventDestroy(h->ev_dbI[i]);
     if (h->d_off) (void)hipFree(h->d_off);
+    if (h->d_scale_tab) (void)hipFree(h->d_scale_tab);
     for (int k = 0; k < NSET; k++) {
         if (h->d_surf[k]) (void)hipFree(h->d_surf[k]);
         for (int i = 0; i < 3; i++) if (h->d_imv[k][i]) (void)hipFree(h->d_imv[k][i]);
@@ -405,6 +407,7 @@ int mi355enc_fetch(mi355enc_t *h, int what, void *dst, size_t n) {
     case MI355ENC_FETCH_PREFILTER_Y: src = h->d_pre_y; need = h->ysz; break;
     case MI355ENC_FETCH_PREFILTER_UV: src = h->d_pre_uv; need = h->csz; break;
     case MI355ENC_FETCH_MBINFO: src = h->last_slot ? h->last_slot->h_mbi : nullptr; need = (size_t)h->nmb * sizeof(mb_info_t); host = true; break;
+    case MI355ENC_FETCH_SCALE_TABLES: src = h->d_scale_tab; need = h->scale_tab_bytes; break;
     case MI355ENC_FETCH_LEVELS: src = h->last_slot ? h->d_levels_set[h->last_slot->set] : nullptr; need = (size_t)h->nmb * MB_LEVELS * 2; break; // dense, from HBM
     case 102: src = h->d_db_part; need = h->d_db_part ? 6 * (size_t)k_deblock_bands16(h->mbh) * sizeof(unsigned) : 0; break; /* development: per band and plane the parts' counter, then {cut column, epoch} of the last launch */
     case 103: src = h->d_progress; need = sizeof(unsigned); break; /* development: the sticky error word of bounded device-side waits (0: none ran out) */

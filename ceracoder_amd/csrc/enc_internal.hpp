@@ -47,7 +47,7 @@ struct slot_t {
     unsigned *h_hdr;      // pinned: [0] blocks in the stream, [1] error word of the band deblocker, [2 + r] first block of macroblock row r
     uint8_t *h_src;              // pinned staging for pictures submitted from pageable host memory (allocated on first use): rows at stride W
     uint8_t *d_src_y, *d_src_uv; // staging for host / unaligned input
-    uint8_t *d_raw;              // staging of non-NV12 input before the conversion kernel (allocated on first use)
+    uint8_t *d_raw;              // staging of non-NV12 input before the conversion kernel, and of every input before the scale kernel (allocated on first use, raw_bytes())
     hipEvent_t done, gpu_done, ev[12];
     hipEvent_t ev_up;          // the source has arrived (upload stream; only when that is a stream of its own)
     hipEvent_t ev_front;       // the front stream's part of the picture is done (source in place, search + selection + analysis)
@@ -135,6 +135,13 @@ struct mi355enc {
     // (what exclusive_device and a single encoder per process allow); 1: kernels run in stream order, the only waits left are those between the
     // workgroups of ONE persistent launch (bands of the intra wavefront / the deblocker); 2: one launch per wavefront step, no wait on the device at all.
     int safe_level;
+    // the input size (mi355enc_set_input_size): in_w x in_h, = cfg.width x cfg.height unless the picture is scaled down on the way in (scaling; the
+    // scale kernel then writes the coded-size surfaces instead of the copy / conversion), the SAR the scale makes (0:0 = square, no VUI field), the
+    // tables on the device and where the kernel finds them
+    int in_w, in_h, sar_w, sar_h;
+    bool scaling;
+    uint8_t *d_scale_tab; size_t scale_tab_bytes;
+    scale_plan_t scale;
     uint32_t n_recoveries, last_error_word;
     // the entropy-coding worker (started by open() when pipeline_depth >= 1)
     std::thread wk;
@@ -178,4 +185,7 @@ void fill_ctx(mi355enc_t *h, frame_ctx_t *c, int qp, int drop, int idr, int set 
 int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_t *src_uv, int src_stride, int64_t pts, int force_idr);
 void entropy_worker(mi355enc_t *h);
 int upload_and_convert(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const planes[3], const int strides[3], hipStream_t up);
+// a picture of the input size tightly into the slot's raw staging buffer (any format); p / st: where its planes lie on the device then
+int upload_raw(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const planes[3], const int strides[3], hipStream_t up, const uint8_t *p[3], int st[3]);
+size_t raw_bytes(const mi355enc_t *h); // size of a slot's raw staging buffer
 #endif

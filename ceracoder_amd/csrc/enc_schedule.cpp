@@ -294,11 +294,12 @@ int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_
     return MI355ENC_OK;
 }
 
-// Upload the planes of a non-NV12 picture tightly into the slot's raw staging buffer and convert into its NV12 staging surfaces.
-int upload_and_convert(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const planes[3], const int strides[3], hipStream_t up) {
-    const int w = h->cfg.width, ht = h->cfg.height;
-    if (fmt < MI355ENC_FMT_I420 || fmt > MI355ENC_FMT_UYVY || !planes || !strides || !planes[0]) return MI355ENC_ERR_ARG;
-    if (!s->d_raw) HIPCHK(hipMalloc((void **)&s->d_raw, (size_t)(2 * h->W + 32) * h->H + 64));
+// Upload the planes of a picture of the input size tightly into the slot's raw staging buffer (rows at multiples of 16 bytes).
+int upload_raw(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const planes[3], const int strides[3], hipStream_t up, const uint8_t *p[3], int st[3]) {
+    const int w = h->in_w, ht = h->in_h;
+    if (fmt < MI355ENC_FMT_NV12 || fmt > MI355ENC_FMT_UYVY || !planes || !strides || !planes[0]) return MI355ENC_ERR_ARG;
+    if (!s->d_raw) HIPCHK(hipMalloc((void **)&s->d_raw, raw_bytes(h)));
+    p[1] = p[2] = nullptr; st[1] = st[2] = 0;
     if (fmt == MI355ENC_FMT_I420) {
         if (!planes[1] || !planes[2] || strides[0] < w || strides[1] < w / 2 || strides[2] < w / 2) return MI355ENC_ERR_ARG;
         const int r0 = (w + 15) & ~15, r1 = (w / 2 + 15) & ~15;
@@ -306,13 +307,33 @@ int upload_and_convert(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const p
         HIPCHK(hipMemcpy2DAsync(dy, r0, planes[0], strides[0], w, ht, hipMemcpyHostToDevice, up));
         HIPCHK(hipMemcpy2DAsync(du, r1, planes[1], strides[1], w / 2, ht / 2, hipMemcpyHostToDevice, up));
         HIPCHK(hipMemcpy2DAsync(dv, r1, planes[2], strides[2], w / 2, ht / 2, hipMemcpyHostToDevice, up));
-        if (k_launch_csc(fmt, dy, du, dv, r0, r1, r1, s->d_src_y, s->d_src_uv, w, ht, h->W, h->H, up)) return MI355ENC_ERR_ARG;
+        p[0] = dy; p[1] = du; p[2] = dv; st[0] = r0; st[1] = st[2] = r1;
+    } else if (fmt == MI355ENC_FMT_NV12) {
+        if (!planes[1] || strides[0] < w || strides[1] < w) return MI355ENC_ERR_ARG;
+        const int r0 = (w + 15) & ~15;
+        uint8_t *dy = s->d_raw, *duv = dy + (size_t)r0 * ht;
+        HIPCHK(hipMemcpy2DAsync(dy, r0, planes[0], strides[0], w, ht, hipMemcpyHostToDevice, up));
+        HIPCHK(hipMemcpy2DAsync(duv, r0, planes[1], strides[1], w, ht / 2, hipMemcpyHostToDevice, up));
+        p[0] = dy; p[1] = duv; st[0] = st[1] = r0;
     } else {
         if (strides[0] < 2 * w) return MI355ENC_ERR_ARG;
         const int r0 = (2 * w + 15) & ~15;
         HIPCHK(hipMemcpy2DAsync(s->d_raw, r0, planes[0], strides[0], 2 * w, ht, hipMemcpyHostToDevice, up));
-        if (k_launch_csc(fmt, s->d_raw, nullptr, nullptr, r0, 0, 0, s->d_src_y, s->d_src_uv, w, ht, h->W, h->H, up)) return MI355ENC_ERR_ARG;
+        p[0] = s->d_raw; st[0] = r0;
     }
+    return MI355ENC_OK;
+}
+// ... and convert (or, with an input size of its own, scale) it into the slot's NV12 staging surfaces.  NV12 only when scaling: unscaled, it is
+// transferred straight into the surfaces (mi355enc_submit).
+int upload_and_convert(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const planes[3], const int strides[3], hipStream_t up) {
+    if (fmt == MI355ENC_FMT_NV12 && !h->scaling) return MI355ENC_ERR_ARG;
+    const uint8_t *p[3];
+    int st[3];
+    int r = upload_raw(h, s, fmt, planes, strides, up, p, st);
+    if (r) return r;
+    if (h->scaling) r = k_launch_scale(fmt, p[0], p[1], p[2], st[0], st[1], st[2], s->d_src_y, s->d_src_uv, h->W, h->H, &h->scale, up);
+    else r = k_launch_csc(fmt, p[0], p[1], p[2], st[0], st[1], st[2], s->d_src_y, s->d_src_uv, h->cfg.width, h->cfg.height, h->W, h->H, up);
+    if (r) return MI355ENC_ERR_ARG;
     HIPCHK(hipGetLastError());
     return MI355ENC_OK;
 }
@@ -321,7 +342,7 @@ int upload_and_convert(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const p
 static size_t code_access_unit(mi355enc_t *h, slot_t *s, uint8_t *out, size_t cap) {
     size_t n = 0;
     if (s->is_idr || s->ir_start) {
-        n = h264_write_headers(out, cap, h->cfg.width, h->cfg.height, h->cfg.fps_num, h->cfg.fps_den, h->cfg.transform8x8);
+        n = h264_write_headers_sar(out, cap, h->cfg.width, h->cfg.height, h->cfg.fps_num, h->cfg.fps_den, h->cfg.transform8x8, h->sar_w, h->sar_h);
         if (!n) return 0;
     }
     if (s->ir_start) { // a refresh cycle starts: a decoder that joins here outputs exact pictures from the cycle's last one on
@@ -460,36 +481,40 @@ extern "C" {
 // this thread, into the slot's pinned staging buffer and leaves from there in one asynchronous transfer per plane, on the front stream,
 // beside the kernels of the pictures before it.
 int mi355enc_submit(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t *uv, int uv_stride, int64_t pts, int force_idr) {
-    if (!h || !y || !uv || y_stride < h->cfg.width || uv_stride < h->cfg.width) return MI355ENC_ERR_ARG;
+    if (!h || !y || !uv || y_stride < h->in_w || uv_stride < h->in_w) return MI355ENC_ERR_ARG;
     if (h->pending > h->cfg.pipeline_depth) return MI355ENC_ERR_STATE;
     HIPCHK(hipSetDevice(h->cfg.device_id));
     slot_t *s = &h->slot[h->head];
-    const int w = h->cfg.width, ht = h->cfg.height;
+    const int w = h->in_w, ht = h->in_h;
     hipStream_t up = upload_stream(h);
+    // where the planes go: the staging surfaces at the coded stride, or -- to be scaled -- the raw staging buffer at the input's
+    if (h->scaling && !s->d_raw) HIPCHK(hipMalloc((void **)&s->d_raw, raw_bytes(h)));
+    const int ds = h->scaling ? (w + 15) & ~15 : h->W;
+    uint8_t *dev_y = h->scaling ? s->d_raw : s->d_src_y, *dev_uv = h->scaling ? s->d_raw + (size_t)ds * ht : s->d_src_uv;
     const bool pinned = host_range_pinned(y, (size_t)y_stride * (ht - 1) + w) && host_range_pinned(uv, (size_t)uv_stride * (ht / 2 - 1) + w);
     if (pinned || h->cfg.pipeline_depth == 0) {
         // pinned: transferred in place.  pipeline_depth 0 (the latency mode: collect() follows at once, there is nothing to run beside): the
         // runtime's own pageable path, which stages and transfers in chunks on its side of the call (measured 0.06 ms less per 1080p picture
         // than staging here and transferring afterwards)
-        HIPCHK(hipMemcpy2DAsync(s->d_src_y, h->W, y, y_stride, w, ht, hipMemcpyHostToDevice, up));
-        HIPCHK(hipMemcpy2DAsync(s->d_src_uv, h->W, uv, uv_stride, w, ht / 2, hipMemcpyHostToDevice, up));
+        HIPCHK(hipMemcpy2DAsync(dev_y, ds, y, y_stride, w, ht, hipMemcpyHostToDevice, up));
+        HIPCHK(hipMemcpy2DAsync(dev_uv, ds, uv, uv_stride, w, ht / 2, hipMemcpyHostToDevice, up));
         h->st.pinned_inputs += pinned ? 1 : 0;
     } else {
-        if (!s->h_src) HIPCHK(hipHostMalloc((void **)&s->h_src, h->ysz + h->csz, hipHostMallocDefault));
+        if (!s->h_src) HIPCHK(hipHostMalloc((void **)&s->h_src, h->scaling ? (size_t)ds * ht * 3 / 2 : h->ysz + h->csz, hipHostMallocDefault));
         // rows at the coded stride, so that a range of rows is one contiguous transfer; in pieces (luma thirds or sixths, the chroma plane in one or two), each
         // sent as soon as it is staged: the transfer of one piece runs beside the staging of the next, and with the helper threads three pieces are
         // staged side by side (a single thread copies 3.1 MB in 0.15-0.2 ms, as long as the device needs for the whole picture)
-        uint8_t *hy = s->h_src, *huv = s->h_src + (size_t)h->W * ht;
+        uint8_t *hy = s->h_src, *huv = s->h_src + (size_t)ds * ht;
         mi355enc::stage_job jobs[8];
         int nj = 0;
         const int ny = h->stg_on ? 6 : 3, nc = h->stg_on ? 2 : 1;
         for (int k = 0; k < ny; k++) {
             const int r0 = (ht * k / ny) & ~1, r1 = k == ny - 1 ? ht : (ht * (k + 1) / ny) & ~1;
-            if (r1 > r0) jobs[nj++] = {y + (size_t)r0 * y_stride, hy + (size_t)r0 * h->W, s->d_src_y + (size_t)r0 * h->W, y_stride, r1 - r0, w, (size_t)h->W};
+            if (r1 > r0) jobs[nj++] = {y + (size_t)r0 * y_stride, hy + (size_t)r0 * ds, dev_y + (size_t)r0 * ds, y_stride, r1 - r0, w, (size_t)ds};
         }
         for (int k = 0; k < nc; k++) {
             const int r0 = (ht / 2) * k / nc, r1 = (ht / 2) * (k + 1) / nc;
-            if (r1 > r0) jobs[nj++] = {uv + (size_t)r0 * uv_stride, huv + (size_t)r0 * h->W, s->d_src_uv + (size_t)r0 * h->W, uv_stride, r1 - r0, w, (size_t)h->W};
+            if (r1 > r0) jobs[nj++] = {uv + (size_t)r0 * uv_stride, huv + (size_t)r0 * ds, dev_uv + (size_t)r0 * ds, uv_stride, r1 - r0, w, (size_t)ds};
         }
         if (h->stg_on) {
             { std::lock_guard<std::mutex> g(h->stg_mu); for (int i = 0; i < nj; i++) h->stg_job[i] = jobs[i]; h->stg_n = nj; h->stg_next = 0; h->stg_done = 0; h->stg_err = 0; h->stg_gen++; }
@@ -505,7 +530,8 @@ int mi355enc_submit(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t
         } else
             for (int i = 0; i < nj; i++) if (stage_piece(h, jobs[i], up)) return MI355ENC_ERR_HIP;
     }
-    if (w != h->W) k_launch_pad(s->d_src_y, s->d_src_uv, h->W, w, ht, h->W, h->H, up);
+    if (h->scaling) { if (k_launch_scale(MI355ENC_FMT_NV12, dev_y, dev_uv, nullptr, ds, ds, 0, s->d_src_y, s->d_src_uv, h->W, h->H, &h->scale, up)) return MI355ENC_ERR_ARG; }
+    else if (w != h->W) k_launch_pad(s->d_src_y, s->d_src_uv, h->W, w, ht, h->W, h->H, up);
     { int r = upload_done(h, s); if (r) return r; }
     return enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
 }
@@ -523,10 +549,17 @@ int mi355enc_submit_fmt(mi355enc_t *h, int fmt, const uint8_t *const planes[3], 
 }
 
 int mi355enc_submit_device(mi355enc_t *h, const void *d_y, int y_stride, const void *d_uv, int uv_stride, int64_t pts, int force_idr) {
-    if (!h || !d_y || !d_uv || y_stride < h->cfg.width || uv_stride < h->cfg.width) return MI355ENC_ERR_ARG;
+    if (!h || !d_y || !d_uv || y_stride < h->in_w || uv_stride < h->in_w) return MI355ENC_ERR_ARG;
     if (h->pending > h->cfg.pipeline_depth) return MI355ENC_ERR_STATE;
     HIPCHK(hipSetDevice(h->cfg.device_id));
     slot_t *s = &h->slot[h->head];
+    if (h->scaling) { // scaled from where the planes lie into the slot's staging surfaces
+        if (k_launch_scale(MI355ENC_FMT_NV12, (const uint8_t *)d_y, (const uint8_t *)d_uv, nullptr, y_stride, uv_stride, 0, s->d_src_y, s->d_src_uv, h->W, h->H, &h->scale,
+                           upload_stream(h))) return MI355ENC_ERR_ARG;
+        HIPCHK(hipGetLastError());
+        { int r = upload_done(h, s); if (r) return r; }
+        return enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
+    }
     const int w = h->cfg.width, ht = h->cfg.height;
     hipStream_t up = upload_stream(h);
     const bool direct = w == h->W && y_stride == uv_stride && (y_stride & 15) == 0 && (((uintptr_t)d_y | (uintptr_t)d_uv) & 15) == 0;

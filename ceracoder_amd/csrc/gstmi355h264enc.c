@@ -56,6 +56,7 @@ typedef struct {
     gboolean single_stream;
     gboolean dct8x8_adaptive; /* with dct8x8: the transform size is chosen per P macroblock (cfg.transform8x8 = 2) */
     gboolean intra_refresh;   /* periodic intra refresh instead of periodic IDR pictures (mi355enc_set_intra_refresh); key-int-max is the refresh period */
+    gint out_w, out_h;        /* coded size (mpph265enc's width / height): 0 = the input's; smaller: scaled down on the device (mi355enc_set_input_size) */
     /* streaming state */
     mi355enc_t *enc;
     GstVideoCodecState *input_state;
@@ -72,7 +73,7 @@ typedef struct { GstVideoEncoderClass parent_class; } GstMi355H264EncClass;
 G_DEFINE_TYPE(GstMi355H264Enc, gst_mi355h264enc, GST_TYPE_VIDEO_ENCODER)
 
 enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME_RANGE, PROP_QP, PROP_PIPELINE_DEPTH,
-       PROP_SPEED_PRESET, PROP_STATS, PROP_DCT8X8, PROP_THREADS, PROP_SCENECUT, PROP_VBV, PROP_INTRA_IN_P, PROP_EXCLUSIVE, PROP_PINNED_INPUT, PROP_AQ_MODE, PROP_SINGLE_STREAM, PROP_INTRA_SLICES, PROP_I8X8, PROP_SLICES, PROP_SLICE_DEBLOCK, PROP_DCT8X8_ADAPTIVE, PROP_INTRA_REFRESH };
+       PROP_SPEED_PRESET, PROP_STATS, PROP_DCT8X8, PROP_THREADS, PROP_SCENECUT, PROP_VBV, PROP_INTRA_IN_P, PROP_EXCLUSIVE, PROP_PINNED_INPUT, PROP_AQ_MODE, PROP_SINGLE_STREAM, PROP_INTRA_SLICES, PROP_I8X8, PROP_SLICES, PROP_SLICE_DEBLOCK, PROP_DCT8X8_ADAPTIVE, PROP_INTRA_REFRESH, PROP_WIDTH, PROP_HEIGHT };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
     GST_STATIC_CAPS("video/x-raw, format=(string){ NV12, I420, YUY2, UYVY }, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]"));
@@ -143,6 +144,8 @@ static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *
     case PROP_DCT8X8: s->dct8x8 = g_value_get_boolean(val) ? 1 : 0; break;
     case PROP_DCT8X8_ADAPTIVE: s->dct8x8_adaptive = g_value_get_boolean(val); break;
     case PROP_INTRA_REFRESH: s->intra_refresh = g_value_get_boolean(val); break;
+    case PROP_WIDTH: s->out_w = g_value_get_int(val); break;
+    case PROP_HEIGHT: s->out_h = g_value_get_int(val); break;
     case PROP_THREADS: s->threads = g_value_get_int(val); break;
     case PROP_SCENECUT: s->scenecut = g_value_get_boolean(val); break;
     case PROP_EXCLUSIVE: s->exclusive_gpu = g_value_get_boolean(val); break;
@@ -177,6 +180,8 @@ static void get_property(GObject *obj, guint id, GValue *val, GParamSpec *ps) {
     case PROP_DCT8X8: g_value_set_boolean(val, t.dct8x8 != 0); break;
     case PROP_DCT8X8_ADAPTIVE: g_value_set_boolean(val, s->dct8x8_adaptive); break;
     case PROP_INTRA_REFRESH: g_value_set_boolean(val, s->intra_refresh); break;
+    case PROP_WIDTH: g_value_set_int(val, s->out_w); break;
+    case PROP_HEIGHT: g_value_set_int(val, s->out_h); break;
     case PROP_THREADS: g_value_set_int(val, s->threads); break;
     case PROP_SCENECUT: g_value_set_boolean(val, s->scenecut); break;
     case PROP_EXCLUSIVE: g_value_set_boolean(val, s->exclusive_gpu); break;
@@ -235,7 +240,11 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     if (fn <= 0 || fd <= 0) { fn = 30; fd = 1; } /* variable framerate: rate control assumes 30 */
     if (s->enc) drain(s, TRUE); /* renegotiation in mid-stream: the picture still on the device belongs to the old format (x264enc flushes here too) */
     close_encoder(s);
-    mi355enc_default_cfg(&cfg, GST_VIDEO_INFO_WIDTH(vi), GST_VIDEO_INFO_HEIGHT(vi), fn, fd);
+    const int in_w = GST_VIDEO_INFO_WIDTH(vi), in_h = GST_VIDEO_INFO_HEIGHT(vi);
+    GST_OBJECT_LOCK(s);
+    const int out_w = s->out_w > 0 ? s->out_w : in_w, out_h = s->out_h > 0 ? s->out_h : in_h; /* (0: the input's size) */
+    GST_OBJECT_UNLOCK(s);
+    mi355enc_default_cfg(&cfg, out_w, out_h, fn, fd);
     GST_OBJECT_LOCK(s);
     cfg.gop = s->key_int_max ? (int)s->key_int_max : 250;
     cfg.me_range = s->me_range; cfg.bitrate_bps = target_bps(s); cfg.device_id = s->device_id; cfg.fixed_qp = s->qp;
@@ -253,10 +262,11 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     GST_OBJECT_UNLOCK(s);
     int r = mi355enc_open(&cfg, &e);
     if (r == MI355ENC_OK && intra_refresh) r = mi355enc_set_intra_refresh(e, 1); /* (refused with key-int-max < 2) */
+    if (r == MI355ENC_OK && (in_w != out_w || in_h != out_h)) r = mi355enc_set_input_size(e, in_w, in_h); /* (refused: upscaling, a ratio above 8, odd sizes) */
     if (r != MI355ENC_OK) {
         if (e) mi355enc_close(e);
         GST_ELEMENT_ERROR(s, LIBRARY, INIT, ("mi355h264enc: cannot open the MI355X encoder: %s", mi355enc_strerror(r)),
-                          ("mi355enc_open(%dx%d, device-id=%d) returned %d", cfg.width, cfg.height, cfg.device_id, r));
+                          ("mi355enc_open(%dx%d from %dx%d input, device-id=%d) returned %d", cfg.width, cfg.height, in_w, in_h, cfg.device_id, r));
         return FALSE;
     }
     GST_OBJECT_LOCK(s);
@@ -278,6 +288,12 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     GstCaps *caps = gst_caps_new_simple("video/x-h264", "stream-format", G_TYPE_STRING, "byte-stream", "alignment", G_TYPE_STRING, "au",
                                         "profile", G_TYPE_STRING, cfg.transform8x8 ? "high" : "constrained-baseline", NULL);
     GstVideoCodecState *out = gst_video_encoder_set_output_state(ve, caps, state);
+    if (in_w != out_w || in_h != out_h) { /* the coded size; a scale that changes the aspect ratio changes the samples' (the SPS VUI carries the same) */
+        out->info.width = out_w; out->info.height = out_h;
+        gint pn = 1, pd = 1;
+        gst_util_fraction_multiply(GST_VIDEO_INFO_PAR_N(vi), GST_VIDEO_INFO_PAR_D(vi), in_w * out_h, in_h * out_w, &pn, &pd);
+        out->info.par_n = pn; out->info.par_d = pd;
+    }
     gst_video_codec_state_unref(out);
     if (cfg.pipeline_depth > 0) {
         GstClockTime d = gst_util_uint64_scale(GST_SECOND, (guint64)fd * cfg.pipeline_depth, fn);
@@ -406,6 +422,18 @@ static void pin_free(GstAllocator *a, GstMemory *m) { (void)a; (void)m; } /* nev
 static void gst_mi355_pin_allocator_class_init(GstMi355PinAllocatorClass *k) { GST_ALLOCATOR_CLASS(k)->alloc = pin_alloc; GST_ALLOCATOR_CLASS(k)->free = pin_free; }
 static void gst_mi355_pin_allocator_init(GstMi355PinAllocator *a) { GST_OBJECT_FLAG_SET(a, GST_ALLOCATOR_FLAG_CUSTOM_ALLOC); }
 
+/* With a coded size of its own (width / height) the element decouples the sizes of its two pads: what downstream accepts (video/x-h264 at the
+ * coded size) says nothing about the input's size, so downstream's caps are not proxied upstream as the base class does by default. */
+static GstCaps *enc_getcaps(GstVideoEncoder *ve, GstCaps *filter) {
+    GstMi355H264Enc *s = GST_MI355H264ENC(ve);
+    GST_OBJECT_LOCK(s);
+    const gboolean scaled = s->out_w > 0 || s->out_h > 0;
+    GST_OBJECT_UNLOCK(s);
+    if (!scaled) return gst_video_encoder_proxy_getcaps(ve, NULL, filter);
+    GstCaps *t = gst_pad_get_pad_template_caps(GST_VIDEO_ENCODER_SINK_PAD(ve));
+    if (filter) { GstCaps *i = gst_caps_intersect_full(filter, t, GST_CAPS_INTERSECT_FIRST); gst_caps_unref(t); t = i; }
+    return t;
+}
 static gboolean enc_propose_allocation(GstVideoEncoder *ve, GstQuery *q) {
     GstMi355H264Enc *s = GST_MI355H264ENC(ve);
     GstCaps *caps = NULL;
@@ -491,12 +519,16 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
         "Use periodic intra refresh instead of IDR frames, as in x264enc: a column of intra macroblocks sweeps the picture once every key-int-max frames "
         "(2 .. 256; opening fails otherwise), which start with SPS, PPS and a recovery point SEI and are marked as sync points; IDR frames only for the first frame, forced key units and "
         "scene cuts. Implies intra macroblocks in P frames and no partitions", FALSE, F));
+    g_object_class_install_property(g, PROP_WIDTH, g_param_spec_int("width", "Coded width",
+        "Width of the coded picture; 0: the input's.  Smaller than the input: the picture is scaled down on the GPU (up to 8:1 per axis, even sizes)", 0, 8192, 0, F));
+    g_object_class_install_property(g, PROP_HEIGHT, g_param_spec_int("height", "Coded height",
+        "Height of the coded picture; 0: the input's.  Smaller than the input: the picture is scaled down on the GPU (up to 8:1 per axis, even sizes)", 0, 8192, 0, F));
     g_object_class_install_property(g, PROP_STATS, g_param_spec_boolean("stats", "Print stats", "Print a JSON line with counters when the encoder closes", FALSE, F));
     gst_element_class_add_static_pad_template(e, &sink_tmpl);
     gst_element_class_add_static_pad_template(e, &src_tmpl);
     gst_element_class_set_static_metadata(e, "MI355X H.264 encoder", "Codec/Encoder/Video/Hardware",
         "H.264 (Constrained Baseline) encoder on AMD Instinct MI355X via hand-written HIP kernels", "ceracoder-amd");
-    v->start = enc_start; v->stop = enc_stop; v->set_format = enc_set_format; v->handle_frame = enc_handle_frame;
+    v->start = enc_start; v->stop = enc_stop; v->set_format = enc_set_format; v->handle_frame = enc_handle_frame; v->getcaps = enc_getcaps;
     v->finish = enc_finish; v->flush = enc_flush; v->propose_allocation = enc_propose_allocation;
 }
 static void gst_mi355h264enc_init(GstMi355H264Enc *s) {

@@ -99,6 +99,9 @@ static int pick_level(int mbw, int mbh, int fps_num, int fps_den) { /* Table A-1
 }
 
 size_t h264_write_headers(uint8_t *out, size_t cap, int width, int height, int fps_num, int fps_den, int t8) {
+    return h264_write_headers_sar(out, cap, width, height, fps_num, fps_den, t8, 0, 0);
+}
+size_t h264_write_headers_sar(uint8_t *out, size_t cap, int width, int height, int fps_num, int fps_den, int t8, int sar_w, int sar_h) {
     uint8_t rb[160];
     bits_t b;
     const int mbw = (width + 15) / 16, mbh = (height + 15) / 16;
@@ -121,7 +124,10 @@ size_t h264_write_headers(uint8_t *out, size_t cap, int width, int height, int f
     if (cr || cb) { bits_put(&b, 1, 1); bits_ue(&b, 0); bits_ue(&b, (uint32_t)cr); bits_ue(&b, 0); bits_ue(&b, (uint32_t)cb); }
     else bits_put(&b, 1, 0);
     bits_put(&b, 1, 1);  /* vui_parameters_present_flag */
-    bits_put(&b, 4, 0);  /* aspect_ratio, overscan, video_signal_type, chroma_loc: absent */
+    if (sar_w > 0 && sar_h > 0) { /* E.1.1: aspect_ratio_idc 255 (Extended_SAR) with the sample aspect ratio of a scaled picture */
+        bits_put(&b, 1, 1); bits_put(&b, 8, 255); bits_put(&b, 16, (uint32_t)sar_w); bits_put(&b, 16, (uint32_t)sar_h);
+        bits_put(&b, 3, 0); /* overscan, video_signal_type, chroma_loc: absent */
+    } else bits_put(&b, 4, 0);  /* aspect_ratio, overscan, video_signal_type, chroma_loc: absent */
     bits_put(&b, 1, 1);  /* timing_info_present_flag */
     bits_put(&b, 16, (uint32_t)fps_den >> 16); bits_put(&b, 16, (uint32_t)fps_den & 0xFFFF);
     bits_put(&b, 16, (uint32_t)(2 * fps_num) >> 16); bits_put(&b, 16, (uint32_t)(2 * fps_num) & 0xFFFF);

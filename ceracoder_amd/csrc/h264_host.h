@@ -16,6 +16,8 @@ void h264_writer_free(h264_writer_t *w);
 size_t h264_max_au_bytes(int mbw, int mbh);
 /* SPS + PPS (Annex B).  Returns bytes written, 0 if `cap` is too small. */
 size_t h264_write_headers(uint8_t *out, size_t cap, int width, int height, int fps_num, int fps_den, int transform8x8);
+/* the same with a sample aspect ratio in the VUI (aspect_ratio_idc 255) unless sar_w or sar_h is 0 (then the bytes of h264_write_headers) */
+size_t h264_write_headers_sar(uint8_t *out, size_t cap, int width, int height, int fps_num, int fps_den, int transform8x8, int sar_w, int sar_h);
 /* SEI NAL unit with one recovery point message (D.1.8): recovery_frame_cnt, exact_match_flag 1, broken_link_flag 0, changing_slice_group_idc 0.
  * Returns bytes written, 0 if `cap` is too small. */
 size_t h264_write_recovery_sei(uint8_t *out, size_t cap, int recovery_frame_cnt);

@@ -166,12 +166,12 @@ int main(int argc, char **argv) {
         if (!strcmp(argv[i], "--props")) {
             if (!enc) enc = gst_bin_get_by_name(GST_BIN(pipe), "venc_kbps");
             if (!enc) { fprintf(stderr, "--props needs an element named venc_bps or venc_kbps\n"); return 2; }
-            gint preset = 0, aq = 0, iip = 0, slices = 0, islices = 0;
+            gint preset = 0, aq = 0, iip = 0, slices = 0, islices = 0, ow = 0, oh = 0;
             gboolean dct = FALSE, dcta = FALSE, i8 = FALSE, sdb = FALSE, irf = FALSE;
             g_object_get(enc, "speed-preset", &preset, "dct8x8", &dct, "dct8x8-adaptive", &dcta, "i8x8", &i8, "aq-mode", &aq, "intra-in-p", &iip, "slices", &slices,
-                         "slice-deblock", &sdb, "intra-slices", &islices, "intra-refresh", &irf, NULL);
-            printf("{\"speed_preset\":%d,\"dct8x8\":%d,\"dct8x8_adaptive\":%d,\"i8x8\":%d,\"aq_mode\":%d,\"intra_in_p\":%d,\"slices\":%d,\"slice_deblock\":%d,\"intra_slices\":%d,\"intra_refresh\":%d,\"has_partitions_property\":%d}\n",
-                   preset, dct, dcta, i8, aq, iip, slices, sdb, islices, irf, g_object_class_find_property(G_OBJECT_GET_CLASS(enc), "partitions") != NULL);
+                         "slice-deblock", &sdb, "intra-slices", &islices, "intra-refresh", &irf, "width", &ow, "height", &oh, NULL);
+            printf("{\"speed_preset\":%d,\"dct8x8\":%d,\"dct8x8_adaptive\":%d,\"i8x8\":%d,\"aq_mode\":%d,\"intra_in_p\":%d,\"slices\":%d,\"slice_deblock\":%d,\"intra_slices\":%d,\"intra_refresh\":%d,\"has_partitions_property\":%d,\"width\":%d,\"height\":%d}\n",
+                   preset, dct, dcta, i8, aq, iip, slices, sdb, islices, irf, g_object_class_find_property(G_OBJECT_GET_CLASS(enc), "partitions") != NULL, ow, oh);
             return 0;
         }
     for (int i = 2; i < argc; i++) {

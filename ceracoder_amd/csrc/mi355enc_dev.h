@@ -158,6 +158,23 @@ void k_launch_intra_band(const frame_ctx_t *h_ctx, int mbh, uint2 *d_gran, unsig
 void k_launch_intra_rows(const frame_ctx_t *h_ctx, int mbh, uint2 *d_gran, unsigned *d_err, unsigned *d_row_done, hipStream_t s);
 int k_launch_csc(int fmt, const uint8_t *p0, const uint8_t *p1, const uint8_t *p2, int s0, int s1, int s2, uint8_t *dy, uint8_t *duv,
                  int vw, int vh, int W, int H, hipStream_t s);
+/* Downscaling of the input picture to the coded size (k_scale.hip; the rule: DESIGN.md section 10).  Tables built on the host
+ * (enc_scale.cpp), five of them: 0 luma horizontal, 1 luma vertical, 2 chroma horizontal, 3 chroma vertical from 4:2:0 input, 4 chroma
+ * vertical from 4:2:2 input.  Entry i of table t: first[t][i] (first source index, not clamped) and q[t][i * taps[t] + k]. */
+#define SCALE_TABLES 5
+#define SCALE_TILE_W 64 /* output bytes per tile row: 64 luma samples, or 32 chroma pairs */
+#define SCALE_TILE_H 16 /* output rows per tile */
+#define SCALE_CHUNK 8   /* source rows staged in LDS at a time by the horizontal pass */
+typedef struct {
+    int in_w, in_h, out_w, out_h;
+    const int *first[SCALE_TABLES];
+    const int16_t *q[SCALE_TABLES];
+    int taps[SCALE_TABLES];
+    int hrows[3]; /* most source rows one tile's vertical pass reads: luma, chroma from 4:2:0, chroma from 4:2:2 */
+    int span[2];  /* most source samples one tile's horizontal pass reads per row: luma, chroma (per component) */
+} scale_plan_t;
+int k_launch_scale(int fmt, const uint8_t *p0, const uint8_t *p1, const uint8_t *p2, int s0, int s1, int s2, uint8_t *dy, uint8_t *duv,
+                   int W, int H, const scale_plan_t *plan, hipStream_t s);
 void k_launch_pack(const mb_info_t *d_mbi, const int16_t *d_levels, int nmb, int mbw, unsigned *d_off, mb_info_t *h_mbi, int16_t *h_packed,
                    unsigned *h_hdr, const unsigned *d_err, hipStream_t s);
 int k_deblock_diags(int mbw, int mbh);

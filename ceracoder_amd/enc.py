@@ -18,10 +18,12 @@ MBINFO_DTYPE = np.dtype(
 )
 
 FETCH_RECON_Y, FETCH_RECON_UV, FETCH_PREFILTER_Y, FETCH_PREFILTER_UV, FETCH_MBINFO, FETCH_LEVELS = range(6)
+FETCH_SCALE_TABLES = 6  # the device's copy of the scale tables (Encoder.scale_tables_device())
 FETCH_BAND_CUTS, FETCH_ERROR_WORD = 102, 103  # development: Encoder.band_cuts(), Encoder.error_word()
 BAND_ROWS = 4  # MI355_BAND_ROWS: macroblock rows per band of the band deblocker
 ERR_ARG, ERR_STATE = -1, -6
 FMT_NV12, FMT_I420, FMT_YUY2, FMT_UYVY = range(4)
+SCALE_LUMA, SCALE_CHROMA_V, SCALE_CHROMA_H, SCALE_CHROMA_V422 = range(4)  # kinds of scale_table()
 IDEC = np.dtype([("modes4", "u1", (16,)), ("mode16", "u1"), ("cmode", "u1"), ("use_i4", "u1"), ("pad", "u1"), ("cost", "<u4"), ("cost_luma", "<u4"), ("rsv", "<u4")])
 IMV_DTYPE = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("sad", "<u2"), ("bits", "<u2")])
 SURF_ROWS, SURF_COLS = 35, 36
@@ -36,6 +38,7 @@ EXPORTS = [
     "mi355enc_stage_subpel", "mi355enc_stage_inter", "mi355enc_stage_pmb", "mi355enc_stage_intra", "mi355enc_stage_intra_analyse", "mi355enc_stage_csc", "mi355enc_submit_fmt", "mi355enc_host_write_slice_packed", "mi355enc_stage_deblock", "mi355enc_time_stage",
     "mi355enc_host_write_headers", "mi355enc_host_write_slice", "mi355enc_host_set_slice_rows", "mi355enc_host_set_p_slices", "mi355enc_stage_set_slice_rows", "mi355enc_slice_rows", "mi355enc_p_slice_rows", "mi355enc_stage_set_slice_deblock", "mi355enc_rc_init", "mi355enc_rc_set_bitrate",
     "mi355enc_rc_pick", "mi355enc_rc_update", "mi355enc_host_cavlc_block", "mi355enc_debug_trip_wait", "mi355enc_host_alloc", "mi355enc_host_free",
+    "mi355enc_set_input_size", "mi355enc_stage_scale", "mi355enc_scale_table",
 ]
 
 
@@ -104,6 +107,9 @@ def load():
         L.mi355enc_submit_fmt.argtypes = [vp, C.c_int, vp, vp, C.c_int64, C.c_int]
         L.mi355enc_stage_csc.argtypes = [vp, C.c_int, vp, vp, vp, vp]
         L.mi355enc_debug_trip_wait.argtypes = [vp, C.c_uint]
+        L.mi355enc_set_input_size.argtypes = [vp, C.c_int, C.c_int]
+        L.mi355enc_stage_scale.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+        L.mi355enc_scale_table.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t, C.POINTER(C.c_int)]
         L.mi355enc_host_alloc.restype = vp
         L.mi355enc_host_alloc.argtypes = [C.c_size_t]
         L.mi355enc_host_free.restype = None
@@ -186,6 +192,21 @@ def host_write_slice_packed(mbw, mbh, is_idr, frame_num, idr_pic_id, qp, mbinfo,
     return bytes(out[: n.value])
 
 
+def scale_table(n_in, n_out, kind):
+    """The library's downscaling table (host only): `kind` one of SCALE_*; n_in / n_out luma samples of the axis.
+    -> (first: int32 (n,), the first source index of every entry's taps; coef: int16 (n, taps), 14-bit weights)."""
+    L = load()
+    taps = C.c_int(0)
+    n = L.mi355enc_scale_table(int(n_in), int(n_out), int(kind), None, None, 0, C.byref(taps))
+    if n < 0:
+        raise EncoderError("mi355enc_scale_table(%d, %d, %d): %s (%d)" % (n_in, n_out, kind, L.mi355enc_strerror(n).decode(), n))
+    first, coef = np.zeros(n, np.int32), np.zeros((n, taps.value), np.int16)
+    r = L.mi355enc_scale_table(int(n_in), int(n_out), int(kind), _p(first), _p(coef), coef.size, C.byref(taps))
+    if r != n:
+        raise EncoderError("mi355enc_scale_table: %d" % r)
+    return first, coef
+
+
 RC_BYTES = 512  # include/mi355enc.h MI355ENC_RC_BYTES
 
 
@@ -243,7 +264,7 @@ class Encoder:
     (bitrate in bits/s as written through `bps`, key-int-max -> gop)."""
 
     def __init__(self, width, height, fps=60, gop=60, bitrate_bps=6_000_000, device_id=0, fixed_qp=-1, me_range=16,
-                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False):
+                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False, input_size=None):
         self.L = load()
         cfg = Cfg()
         self.L.mi355enc_default_cfg(C.byref(cfg), width, height, fps, fps_den)
@@ -284,6 +305,10 @@ class Encoder:
         self._out = np.empty(self.L.mi355enc_max_au_bytes(self.h), np.uint8)
         if intra_refresh:  # periodic intra refresh instead of periodic IDR pictures (refresh period: gop)
             self._chk(self.L.mi355enc_set_intra_refresh(self.h, 1), "set_intra_refresh", close_on_fail=True)
+        self.input_size = (width, height)
+        if input_size is not None:  # (w, h) of the submitted pictures: scaled down on the device to width x height
+            self._chk(self.L.mi355enc_set_input_size(self.h, int(input_size[0]), int(input_size[1])), "set_input_size", close_on_fail=True)
+            self.input_size = (int(input_size[0]), int(input_size[1]))
 
     def _chk(self, r, what, close_on_fail=False):
         if r != 0:
@@ -342,6 +367,38 @@ class Encoder:
         ouv = np.empty((self.mbh * 8, self.mbw * 16), np.uint8)
         self._chk(self.L.mi355enc_stage_csc(self.h, fmt, pp, ss, _p(oy), _p(ouv)), "stage_csc")
         return oy, ouv
+
+    def set_input_size(self, w, h):
+        """pictures submitted from now on are w x h (before the first submit; the coded size returns to the unscaled path)"""
+        self._chk(self.L.mi355enc_set_input_size(self.h, int(w), int(h)), "set_input_size")
+        self.input_size = (int(w), int(h))
+
+    def stage_scale(self, fmt, planes):
+        """The scale kernel alone: planes of the input size (row strides as the arrays have them) -> the coded-size NV12 surfaces."""
+        arrs = [a if a.dtype == np.uint8 and a.strides[-1] == 1 else np.ascontiguousarray(a, np.uint8) for a in planes]
+        pp = (C.c_void_p * 3)(*([a.ctypes.data for a in arrs] + [None] * (3 - len(arrs))))
+        ss = (C.c_int * 3)(*([a.strides[0] for a in arrs] + [0] * (3 - len(arrs))))
+        oy = np.empty((self.mbh * 16, self.mbw * 16), np.uint8)
+        ouv = np.empty((self.mbh * 8, self.mbw * 16), np.uint8)
+        self._chk(self.L.mi355enc_stage_scale(self.h, fmt, pp, ss, _p(oy), _p(ouv)), "stage_scale")
+        return oy, ouv
+
+    def scale_tables_device(self):
+        """The device's copy of the scale tables: [(first, coef)] for luma horizontal, luma vertical, chroma horizontal, chroma vertical
+        from 4:2:0 and from 4:2:2 (include/mi355enc.h MI355ENC_FETCH_SCALE_TABLES)."""
+        (iw, ih), (ow, oh) = self.input_size, (self.width, self.height)
+        spec = [(iw, ow, SCALE_LUMA), (ih, oh, SCALE_LUMA), (iw, ow, SCALE_CHROMA_H), (ih, oh, SCALE_CHROMA_V), (ih, oh, SCALE_CHROMA_V422)]
+        shapes = [scale_table(*a)[1].shape for a in spec]
+        sizes = [(n * 4 + n * t * 2 + 15) // 16 * 16 for n, t in shapes]
+        blob = np.zeros(sum(sizes), np.uint8)
+        self._chk(self.L.mi355enc_fetch(self.h, FETCH_SCALE_TABLES, _p(blob), blob.nbytes), "fetch")
+        out, o = [], 0
+        for (n, t), sz in zip(shapes, sizes):
+            first = blob[o:o + 4 * n].view(np.int32).copy()
+            coef = blob[o + 4 * n:o + 4 * n + 2 * n * t].view(np.int16).reshape(n, t).copy()
+            out.append((first, coef))
+            o += sz
+        return out
 
     def submit_device(self, y_ptr, y_stride, uv_ptr, uv_stride, pts=0, force_idr=False):
         self._chk(self.L.mi355enc_submit_device(self.h, y_ptr, y_stride, uv_ptr, uv_stride, pts, int(force_idr)), "submit_device")

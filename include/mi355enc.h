@@ -216,6 +216,22 @@ int mi355enc_submit_fmt(mi355enc_t *h, int fmt, const uint8_t *const planes[3], 
 int mi355enc_stage_csc(mi355enc_t *h, int fmt, const uint8_t *const planes[3], const int strides[3], uint8_t *out_y, uint8_t *out_uv);
 int mi355enc_submit_device(mi355enc_t *h, const void *d_y, int y_stride, const void *d_uv,
                            int uv_stride, int64_t pts, int force_idr);
+/* Downscaling on the way in.  The pictures submitted from now on are in_w x in_h; the device scales them to the
+ * coded size cfg.width x cfg.height with a separable Catmull-Rom filter (integer arithmetic, tables built once here), in the launch
+ * that would otherwise copy or convert them.  Per axis cfg size <= in <= 8 * cfg size, even sizes (MI355ENC_ERR_ARG otherwise); the cfg
+ * size itself returns to the unscaled path.  Valid only before the first submit (MI355ENC_ERR_STATE after it).  A scale that changes the
+ * aspect ratio writes the sample aspect ratio into the SPS VUI (aspect_ratio_idc 255). */
+int mi355enc_set_input_size(mi355enc_t *h, int in_w, int in_h);
+/* scale stage alone (tests): planes of the input size in `fmt` (NV12: Y, UV) -> the coded-size NV12 surfaces, like mi355enc_stage_csc;
+ * MI355ENC_ERR_STATE before mi355enc_set_input_size */
+int mi355enc_stage_scale(mi355enc_t *h, int fmt, const uint8_t *const planes[3], const int strides[3], uint8_t *out_y, uint8_t *out_uv);
+/* The scale tables (host only, no device needed).  kind: MI355ENC_SCALE_LUMA (either axis: `in` -> `out` samples), MI355ENC_SCALE_CHROMA_V
+ * (4:2:0 chroma rows: in / 2 -> out / 2), MI355ENC_SCALE_CHROMA_H (chroma columns, cosited: in / 2 -> out / 2), MI355ENC_SCALE_CHROMA_V422
+ * (4:2:2 chroma rows: in -> out / 2); in and out are luma sizes of the axis.  Entry i: first[i], the first source index of its taps (not
+ * clamped), and coef[i * taps + k], k < *taps, 14-bit weights that sum to 16384.  Returns the number of entries (with first and coef NULL:
+ * only that and *taps), MI355ENC_ERR_ARG for upscaling, a ratio above 8 or odd sizes. */
+enum { MI355ENC_SCALE_LUMA = 0, MI355ENC_SCALE_CHROMA_V = 1, MI355ENC_SCALE_CHROMA_H = 2, MI355ENC_SCALE_CHROMA_V422 = 3 };
+int mi355enc_scale_table(int in, int out, int kind, int *first, int16_t *coef, size_t coef_cap, int *taps);
 int mi355enc_pending(const mi355enc_t *h);
 int mi355enc_collect(mi355enc_t *h, uint8_t *out, size_t out_cap, size_t *out_len, int *is_keyframe,
                      int64_t *pts, int *qp);
@@ -237,8 +253,11 @@ int mi355enc_abi_version(void);
  * MI355ENC_FETCH_MBINFO returns the records as they were handed to the entropy coder.  With adaptive quantisation (aq_mode 1) the `qp` byte of a macroblock that sends
  * no mb_qp_delta (P_Skip, or no coded block and not Intra_16x16) is NOT defined there: the deblocking launch's QP_Y chain rewrites it on the device (7.4.5: the QP_Y of the
  * macroblock before it) while the hand-over copies the records, and the entropy coder never reads it -- take `qp` only from macroblocks that send a delta. */
+/* MI355ENC_FETCH_SCALE_TABLES: the device's copy of the scale tables (after mi355enc_set_input_size): the luma horizontal, luma vertical,
+ * chroma horizontal, chroma vertical 4:2:0 and chroma vertical 4:2:2 tables in this order, each as int32 first[n] then int16 coef[n][taps]
+ * (mi355enc_scale_table's), padded to a multiple of 16 bytes. */
 enum { MI355ENC_FETCH_RECON_Y = 0, MI355ENC_FETCH_RECON_UV = 1, MI355ENC_FETCH_PREFILTER_Y = 2,
-       MI355ENC_FETCH_PREFILTER_UV = 3, MI355ENC_FETCH_MBINFO = 4, MI355ENC_FETCH_LEVELS = 5 };
+       MI355ENC_FETCH_PREFILTER_UV = 3, MI355ENC_FETCH_MBINFO = 4, MI355ENC_FETCH_LEVELS = 5, MI355ENC_FETCH_SCALE_TABLES = 6 };
 int mi355enc_fetch(mi355enc_t *h, int what, void *dst, size_t dst_bytes);
 int mi355enc_mb_width(const mi355enc_t *h);
 int mi355enc_mb_height(const mi355enc_t *h);
