@@ -48,6 +48,7 @@ struct slot_t {
     uint8_t *h_src;              // pinned staging for pictures submitted from pageable host memory (allocated on first use): rows at stride W
     uint8_t *d_src_y, *d_src_uv; // staging for host / unaligned input
     uint8_t *d_raw;              // staging of non-NV12 input before the conversion kernel, and of every input before the scale kernel (allocated on first use, raw_bytes())
+    uint8_t *d_csc;              // the formats of k_csc.hip with an input size of their own: the NV12 picture of the input size between conversion and scale (allocated on first use)
     hipEvent_t done, gpu_done, ev[12];
     hipEvent_t ev_up;          // the source has arrived (upload stream; only when that is a stream of its own)
     hipEvent_t ev_front;       // the front stream's part of the picture is done (source in place, search + selection + analysis)
@@ -142,6 +143,10 @@ struct mi355enc {
     bool scaling;
     uint8_t *d_scale_tab; size_t scale_tab_bytes;
     scale_plan_t scale;
+    // colorimetry (mi355enc_set_colorimetry): what every SPS says about the samples (0, 2, 2, 2: nothing), and the RGB -> Y'CbCr matrix that follows from it
+    // (csc_coef: the ten words of mi355enc_csc_coefficients; csc_ok false: the matrix code is not one RGB input can be converted with)
+    int col_full, col_prim, col_trc, col_mat;
+    int csc_coef[10]; bool csc_ok;
     uint32_t n_recoveries, last_error_word;
     // the entropy-coding worker (started by open() when pipeline_depth >= 1)
     std::thread wk;
@@ -188,4 +193,6 @@ int upload_and_convert(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const p
 // a picture of the input size tightly into the slot's raw staging buffer (any format); p / st: where its planes lie on the device then
 int upload_raw(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const planes[3], const int strides[3], hipStream_t up, const uint8_t *p[3], int st[3]);
 size_t raw_bytes(const mi355enc_t *h); // size of a slot's raw staging buffer
+// enc_csc.cpp
+void csc_resolve(mi355enc_t *h); // fills csc_coef / csc_ok from col_mat, col_full and the coded size
 #endif

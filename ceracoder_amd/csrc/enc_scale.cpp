@@ -128,7 +128,7 @@ static void scale_sar(int in_w, int in_h, int out_w, int out_h, int *sw, int *sh
 
 size_t raw_bytes(const mi355enc_t *h) {
     const int w = h->in_w > h->W ? h->in_w : h->W, ht = h->in_h > h->H ? h->in_h : h->H;
-    return (size_t)(2 * w + 32) * ht + 64;
+    return (size_t)(4 * w + 48) * ht + 64; // the largest: four bytes per pixel, or three planes of the picture's size, rows at multiples of 16 bytes
 }
 
 extern "C" {
@@ -163,6 +163,7 @@ int mi355enc_set_input_size(mi355enc_t *h, int in_w, int in_h) {
     for (int i = 0; i < NSLOT; i++) { // staging buffers follow the input size (allocated again on first use)
         slot_t *s = &h->slot[i];
         if (s->d_raw) { (void)hipFree(s->d_raw); s->d_raw = nullptr; }
+        if (s->d_csc) { (void)hipFree(s->d_csc); s->d_csc = nullptr; }
         if (s->h_src) { (void)hipHostFree(s->h_src); s->h_src = nullptr; }
     }
     return MI355ENC_OK;
@@ -176,10 +177,15 @@ int mi355enc_stage_scale(mi355enc_t *h, int fmt, const uint8_t *const planes[3],
     slot_t *s = &h->slot[0];
     const uint8_t *p[3];
     int st[3];
-    int r = upload_raw(h, s, fmt, planes, strides, h->stream, p, st);
-    if (r) return r;
-    if (k_launch_scale(fmt, p[0], p[1], p[2], st[0], st[1], st[2], s->d_src_y, s->d_src_uv, h->W, h->H, &h->scale, h->stream)) return MI355ENC_ERR_ARG;
-    HIPCHK(hipGetLastError());
+    if (fmt >= MI355ENC_FMT_Y42B) { // converted at the input size, then scaled as NV12
+        int r = upload_and_convert(h, s, fmt, planes, strides, h->stream);
+        if (r) return r;
+    } else {
+        int r = upload_raw(h, s, fmt, planes, strides, h->stream, p, st);
+        if (r) return r;
+        if (k_launch_scale(fmt, p[0], p[1], p[2], st[0], st[1], st[2], s->d_src_y, s->d_src_uv, h->W, h->H, &h->scale, h->stream)) return MI355ENC_ERR_ARG;
+        HIPCHK(hipGetLastError());
+    }
     HIPCHK(hipMemcpyAsync(out_y, s->d_src_y, h->ysz, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(out_uv, s->d_src_uv, h->csz, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));

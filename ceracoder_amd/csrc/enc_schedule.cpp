@@ -297,7 +297,7 @@ int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_
 // Upload the planes of a picture of the input size tightly into the slot's raw staging buffer (rows at multiples of 16 bytes).
 int upload_raw(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const planes[3], const int strides[3], hipStream_t up, const uint8_t *p[3], int st[3]) {
     const int w = h->in_w, ht = h->in_h;
-    if (fmt < MI355ENC_FMT_NV12 || fmt > MI355ENC_FMT_UYVY || !planes || !strides || !planes[0]) return MI355ENC_ERR_ARG;
+    if (fmt < MI355ENC_FMT_NV12 || fmt > MI355ENC_FMT_RGB || !planes || !strides || !planes[0]) return MI355ENC_ERR_ARG;
     if (!s->d_raw) HIPCHK(hipMalloc((void **)&s->d_raw, raw_bytes(h)));
     p[1] = p[2] = nullptr; st[1] = st[2] = 0;
     if (fmt == MI355ENC_FMT_I420) {
@@ -308,30 +308,61 @@ int upload_raw(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const planes[3]
         HIPCHK(hipMemcpy2DAsync(du, r1, planes[1], strides[1], w / 2, ht / 2, hipMemcpyHostToDevice, up));
         HIPCHK(hipMemcpy2DAsync(dv, r1, planes[2], strides[2], w / 2, ht / 2, hipMemcpyHostToDevice, up));
         p[0] = dy; p[1] = du; p[2] = dv; st[0] = r0; st[1] = st[2] = r1;
-    } else if (fmt == MI355ENC_FMT_NV12) {
+    } else if (fmt == MI355ENC_FMT_Y42B || fmt == MI355ENC_FMT_Y444) { // three planes: chroma of the full height, half or full width
+        const int cw = fmt == MI355ENC_FMT_Y444 ? w : w / 2;
+        if (!planes[1] || !planes[2] || strides[0] < w || strides[1] < cw || strides[2] < cw) return MI355ENC_ERR_ARG;
+        const int r0 = (w + 15) & ~15, r1 = (cw + 15) & ~15;
+        uint8_t *dy = s->d_raw, *du = dy + (size_t)r0 * ht, *dv = du + (size_t)r1 * ht;
+        HIPCHK(hipMemcpy2DAsync(dy, r0, planes[0], strides[0], w, ht, hipMemcpyHostToDevice, up));
+        HIPCHK(hipMemcpy2DAsync(du, r1, planes[1], strides[1], cw, ht, hipMemcpyHostToDevice, up));
+        HIPCHK(hipMemcpy2DAsync(dv, r1, planes[2], strides[2], cw, ht, hipMemcpyHostToDevice, up));
+        p[0] = dy; p[1] = du; p[2] = dv; st[0] = r0; st[1] = st[2] = r1;
+    } else if (fmt >= MI355ENC_FMT_BGRX) { // one packed plane of four or three bytes per pixel
+        const int bpp = fmt >= MI355ENC_FMT_BGR ? 3 : 4;
+        if (strides[0] < bpp * w) return MI355ENC_ERR_ARG;
+        const int r0 = (bpp * w + 15) & ~15;
+        HIPCHK(hipMemcpy2DAsync(s->d_raw, r0, planes[0], strides[0], (size_t)bpp * w, ht, hipMemcpyHostToDevice, up));
+        p[0] = s->d_raw; st[0] = r0;
+    } else if (fmt == MI355ENC_FMT_NV12 || fmt == MI355ENC_FMT_NV21) {
         if (!planes[1] || strides[0] < w || strides[1] < w) return MI355ENC_ERR_ARG;
         const int r0 = (w + 15) & ~15;
         uint8_t *dy = s->d_raw, *duv = dy + (size_t)r0 * ht;
         HIPCHK(hipMemcpy2DAsync(dy, r0, planes[0], strides[0], w, ht, hipMemcpyHostToDevice, up));
         HIPCHK(hipMemcpy2DAsync(duv, r0, planes[1], strides[1], w, ht / 2, hipMemcpyHostToDevice, up));
         p[0] = dy; p[1] = duv; st[0] = st[1] = r0;
-    } else {
+    } else if (fmt == MI355ENC_FMT_YUY2 || fmt == MI355ENC_FMT_UYVY) {
         if (strides[0] < 2 * w) return MI355ENC_ERR_ARG;
         const int r0 = (2 * w + 15) & ~15;
         HIPCHK(hipMemcpy2DAsync(s->d_raw, r0, planes[0], strides[0], 2 * w, ht, hipMemcpyHostToDevice, up));
         p[0] = s->d_raw; st[0] = r0;
-    }
+    } else return MI355ENC_ERR_ARG; // (YV12 arrives here as I420 with its chroma planes exchanged)
     return MI355ENC_OK;
 }
 // ... and convert (or, with an input size of its own, scale) it into the slot's NV12 staging surfaces.  NV12 only when scaling: unscaled, it is
 // transferred straight into the surfaces (mi355enc_submit).
 int upload_and_convert(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const planes[3], const int strides[3], hipStream_t up) {
     if (fmt == MI355ENC_FMT_NV12 && !h->scaling) return MI355ENC_ERR_ARG;
+    if (!planes || !strides) return MI355ENC_ERR_ARG;
+    if (fmt == MI355ENC_FMT_YV12) { // I420 with V before U
+        const uint8_t *const pl[3] = {planes[0], planes[2], planes[1]};
+        const int sl[3] = {strides[0], strides[2], strides[1]};
+        return upload_and_convert(h, s, MI355ENC_FMT_I420, pl, sl, up);
+    }
+    if (fmt >= MI355ENC_FMT_BGRX && fmt <= MI355ENC_FMT_RGB && !h->csc_ok) return MI355ENC_ERR_ARG; // (a matrix code RGB cannot be converted with: before anything is uploaded)
     const uint8_t *p[3];
     int st[3];
     int r = upload_raw(h, s, fmt, planes, strides, up, p, st);
     if (r) return r;
-    if (h->scaling) r = k_launch_scale(fmt, p[0], p[1], p[2], st[0], st[1], st[2], s->d_src_y, s->d_src_uv, h->W, h->H, &h->scale, up);
+    if (fmt >= MI355ENC_FMT_Y42B) { // the formats of k_csc.hip; with an input size of its own: converted at that size, then scaled as NV12
+        if (!h->scaling) r = k_launch_csc2(fmt, p[0], p[1], p[2], st[0], st[1], st[2], s->d_src_y, s->d_src_uv, h->cfg.width, h->cfg.height, h->W, h->H, h->csc_coef, up);
+        else {
+            const int wi = (h->in_w + 15) & ~15;
+            if (!s->d_csc) HIPCHK(hipMalloc((void **)&s->d_csc, (size_t)wi * h->in_h * 3 / 2 + SURF_PAD));
+            uint8_t *cy = s->d_csc, *cuv = cy + (size_t)wi * h->in_h;
+            r = k_launch_csc2(fmt, p[0], p[1], p[2], st[0], st[1], st[2], cy, cuv, h->in_w, h->in_h, wi, h->in_h, h->csc_coef, up);
+            if (!r) r = k_launch_scale(MI355ENC_FMT_NV12, cy, cuv, nullptr, wi, wi, 0, s->d_src_y, s->d_src_uv, h->W, h->H, &h->scale, up);
+        }
+    } else if (h->scaling) r = k_launch_scale(fmt, p[0], p[1], p[2], st[0], st[1], st[2], s->d_src_y, s->d_src_uv, h->W, h->H, &h->scale, up);
     else r = k_launch_csc(fmt, p[0], p[1], p[2], st[0], st[1], st[2], s->d_src_y, s->d_src_uv, h->cfg.width, h->cfg.height, h->W, h->H, up);
     if (r) return MI355ENC_ERR_ARG;
     HIPCHK(hipGetLastError());
@@ -342,7 +373,8 @@ int upload_and_convert(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const p
 static size_t code_access_unit(mi355enc_t *h, slot_t *s, uint8_t *out, size_t cap) {
     size_t n = 0;
     if (s->is_idr || s->ir_start) {
-        n = h264_write_headers_sar(out, cap, h->cfg.width, h->cfg.height, h->cfg.fps_num, h->cfg.fps_den, h->cfg.transform8x8, h->sar_w, h->sar_h);
+        n = h264_write_headers_vui(out, cap, h->cfg.width, h->cfg.height, h->cfg.fps_num, h->cfg.fps_den, h->cfg.transform8x8, h->sar_w, h->sar_h,
+                                   h->col_full, h->col_prim, h->col_trc, h->col_mat);
         if (!n) return 0;
     }
     if (s->ir_start) { // a refresh cycle starts: a decoder that joins here outputs exact pictures from the cycle's last one on

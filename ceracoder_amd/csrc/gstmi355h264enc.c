@@ -76,7 +76,7 @@ enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME
        PROP_SPEED_PRESET, PROP_STATS, PROP_DCT8X8, PROP_THREADS, PROP_SCENECUT, PROP_VBV, PROP_INTRA_IN_P, PROP_EXCLUSIVE, PROP_PINNED_INPUT, PROP_AQ_MODE, PROP_SINGLE_STREAM, PROP_INTRA_SLICES, PROP_I8X8, PROP_SLICES, PROP_SLICE_DEBLOCK, PROP_DCT8X8_ADAPTIVE, PROP_INTRA_REFRESH, PROP_WIDTH, PROP_HEIGHT };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
-    GST_STATIC_CAPS("video/x-raw, format=(string){ NV12, I420, YUY2, UYVY }, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]"));
+    GST_STATIC_CAPS("video/x-raw, format=(string){ NV12, I420, YUY2, UYVY, Y42B, Y444, YV12, NV21, BGRx, RGBx, xRGB, xBGR, BGRA, RGBA, ARGB, ABGR, BGR, RGB }, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]"));
 static GstStaticPadTemplate src_tmpl = GST_STATIC_PAD_TEMPLATE("src", GST_PAD_SRC, GST_PAD_ALWAYS,
     GST_STATIC_CAPS("video/x-h264, stream-format=(string)byte-stream, alignment=(string)au, profile=(string){ constrained-baseline, high }, "
                     "width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]"));
@@ -231,6 +231,60 @@ static gboolean enc_start(GstVideoEncoder *ve) {
     return TRUE; /* geometry is unknown until set_format; the device is opened there, still before data flows */
 }
 
+/* the formats of mi355enc.h beyond the first four; -1: none of them.  An alpha byte is ignored like a padding byte */
+static int rgb_or_planar_fmt(GstVideoFormat f) {
+    switch (f) {
+    case GST_VIDEO_FORMAT_Y42B: return MI355ENC_FMT_Y42B;
+    case GST_VIDEO_FORMAT_Y444: return MI355ENC_FMT_Y444;
+    case GST_VIDEO_FORMAT_YV12: return MI355ENC_FMT_YV12;
+    case GST_VIDEO_FORMAT_NV21: return MI355ENC_FMT_NV21;
+    case GST_VIDEO_FORMAT_BGRx: case GST_VIDEO_FORMAT_BGRA: return MI355ENC_FMT_BGRX;
+    case GST_VIDEO_FORMAT_RGBx: case GST_VIDEO_FORMAT_RGBA: return MI355ENC_FMT_RGBX;
+    case GST_VIDEO_FORMAT_xRGB: case GST_VIDEO_FORMAT_ARGB: return MI355ENC_FMT_XRGB;
+    case GST_VIDEO_FORMAT_xBGR: case GST_VIDEO_FORMAT_ABGR: return MI355ENC_FMT_XBGR;
+    case GST_VIDEO_FORMAT_BGR: return MI355ENC_FMT_BGR;
+    case GST_VIDEO_FORMAT_RGB: return MI355ENC_FMT_RGB;
+    default: return -1;
+    }
+}
+/* GstVideoColorimetry -> the code points of H.264 Tables E-3 / E-4 / E-5 (GStreamer 1.14 has no gst_video_color_*_to_iso); what has no code point: 2,
+ * unspecified.  The transfer function of BT.709 beside the BT.601 matrix is written as 6 (SMPTE 170M: the same curve under its standard-definition
+ * name, what later GStreamer versions call GST_VIDEO_TRANSFER_BT601), so that `colorimetry=bt601` reads 6 / 6 / 6. */
+static void colorimetry_codes(const GstVideoColorimetry *c, int *full, int *prim, int *trc, int *mat) {
+    *full = c->range == GST_VIDEO_COLOR_RANGE_0_255;
+    switch (c->primaries) {
+    case GST_VIDEO_COLOR_PRIMARIES_BT709: *prim = 1; break;
+    case GST_VIDEO_COLOR_PRIMARIES_BT470M: *prim = 4; break;
+    case GST_VIDEO_COLOR_PRIMARIES_BT470BG: *prim = 5; break;
+    case GST_VIDEO_COLOR_PRIMARIES_SMPTE170M: *prim = 6; break;
+    case GST_VIDEO_COLOR_PRIMARIES_SMPTE240M: *prim = 7; break;
+    case GST_VIDEO_COLOR_PRIMARIES_FILM: *prim = 8; break;
+    case GST_VIDEO_COLOR_PRIMARIES_BT2020: *prim = 9; break;
+    default: *prim = 2; break;
+    }
+    switch (c->matrix) {
+    case GST_VIDEO_COLOR_MATRIX_RGB: *mat = 0; break;
+    case GST_VIDEO_COLOR_MATRIX_FCC: *mat = 4; break;
+    case GST_VIDEO_COLOR_MATRIX_BT709: *mat = 1; break;
+    case GST_VIDEO_COLOR_MATRIX_BT601: *mat = 6; break;
+    case GST_VIDEO_COLOR_MATRIX_SMPTE240M: *mat = 7; break;
+    case GST_VIDEO_COLOR_MATRIX_BT2020: *mat = 9; break;
+    default: *mat = 2; break;
+    }
+    switch (c->transfer) {
+    case GST_VIDEO_TRANSFER_GAMMA10: *trc = 8; break;
+    case GST_VIDEO_TRANSFER_GAMMA22: *trc = 4; break;
+    case GST_VIDEO_TRANSFER_GAMMA28: *trc = 5; break;
+    case GST_VIDEO_TRANSFER_BT709: *trc = c->matrix == GST_VIDEO_COLOR_MATRIX_BT601 ? 6 : 1; break;
+    case GST_VIDEO_TRANSFER_SMPTE240M: *trc = 7; break;
+    case GST_VIDEO_TRANSFER_SRGB: *trc = 13; break;
+    case GST_VIDEO_TRANSFER_LOG100: *trc = 9; break;
+    case GST_VIDEO_TRANSFER_LOG316: *trc = 10; break;
+    case GST_VIDEO_TRANSFER_BT2020_12: *trc = 15; break;
+    default: *trc = 2; break;
+    }
+}
+
 static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     GstMi355H264Enc *s = GST_MI355H264ENC(ve);
     GstVideoInfo *vi = &state->info;
@@ -262,6 +316,16 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     GST_OBJECT_UNLOCK(s);
     int r = mi355enc_open(&cfg, &e);
     if (r == MI355ENC_OK && intra_refresh) r = mi355enc_set_intra_refresh(e, 1); /* (refused with key-int-max < 2) */
+    if (r == MI355ENC_OK) { /* what the samples mean goes into the SPS (x264enc copies its input caps' colorimetry likewise); YUV input is only labelled */
+        int full, prim, trc, mat;
+        colorimetry_codes(&vi->colorimetry, &full, &prim, &trc, &mat);
+        if (GST_VIDEO_INFO_IS_RGB(vi) && mat != 1 && mat != 6 && mat != 9) {
+            /* RGB is converted here: with what `videoconvert` would have negotiated for the encoder's input -- BT.709 for HD, BT.601 below, limited range */
+            prim = trc = mat = (out_w > 1024 || out_h > 576) ? 1 : 6;
+            full = 0;
+        } else if (GST_VIDEO_INFO_IS_RGB(vi)) full = 0;
+        r = mi355enc_set_colorimetry(e, full, prim, trc, mat);
+    }
     if (r == MI355ENC_OK && (in_w != out_w || in_h != out_h)) r = mi355enc_set_input_size(e, in_w, in_h); /* (refused: upscaling, a ratio above 8, odd sizes) */
     if (r != MI355ENC_OK) {
         if (e) mi355enc_close(e);
@@ -352,14 +416,14 @@ static GstFlowReturn enc_handle_frame(GstVideoEncoder *ve, GstVideoCodecFrame *f
         gst_video_encoder_finish_frame(ve, frame);
         return GST_FLOW_ERROR;
     }
-    /* NV12 goes in as is; I420 (x264enc's native format) and packed 4:2:2 are converted on the device, so the
+    /* NV12 goes in as is; I420 (x264enc's native format), packed and planar 4:2:2, 4:4:4 and RGB are converted on the device, so the
      * `videoconvert` in front of the encoder (pipeline/generic/x264_superfast_camlink:4) degenerates to a pass-through */
     int fmt = MI355ENC_FMT_NV12;
     switch (GST_VIDEO_INFO_FORMAT(&s->input_state->info)) {
     case GST_VIDEO_FORMAT_I420: fmt = MI355ENC_FMT_I420; break;
     case GST_VIDEO_FORMAT_YUY2: fmt = MI355ENC_FMT_YUY2; break;
     case GST_VIDEO_FORMAT_UYVY: fmt = MI355ENC_FMT_UYVY; break;
-    default: break;
+    default: { const int f = rgb_or_planar_fmt(GST_VIDEO_INFO_FORMAT(&s->input_state->info)); if (f >= 0) fmt = f; break; } /* converted on the device as well */
     }
     const uint8_t *planes[3] = {NULL, NULL, NULL};
     int strides[3] = {0, 0, 0};

@@ -102,7 +102,12 @@ size_t h264_write_headers(uint8_t *out, size_t cap, int width, int height, int f
     return h264_write_headers_sar(out, cap, width, height, fps_num, fps_den, t8, 0, 0);
 }
 size_t h264_write_headers_sar(uint8_t *out, size_t cap, int width, int height, int fps_num, int fps_den, int t8, int sar_w, int sar_h) {
-    uint8_t rb[160];
+    return h264_write_headers_vui(out, cap, width, height, fps_num, fps_den, t8, sar_w, sar_h, 0, 2, 2, 2);
+}
+size_t h264_write_headers_vui(uint8_t *out, size_t cap, int width, int height, int fps_num, int fps_den, int t8, int sar_w, int sar_h,
+                              int full_range, int primaries, int transfer, int matrix) {
+    uint8_t rb[160]; /* the longest SPS (High, cropped, Extended_SAR, colour description) is under 60 bytes */
+    if ((full_range | 1) != 1 || ((primaries | transfer | matrix) & ~255)) return 0;
     bits_t b;
     const int mbw = (width + 15) / 16, mbh = (height + 15) / 16;
     /* 7.3.2.1.1 seq_parameter_set_data: Constrained Baseline */
@@ -126,8 +131,16 @@ size_t h264_write_headers_sar(uint8_t *out, size_t cap, int width, int height, i
     bits_put(&b, 1, 1);  /* vui_parameters_present_flag */
     if (sar_w > 0 && sar_h > 0) { /* E.1.1: aspect_ratio_idc 255 (Extended_SAR) with the sample aspect ratio of a scaled picture */
         bits_put(&b, 1, 1); bits_put(&b, 8, 255); bits_put(&b, 16, (uint32_t)sar_w); bits_put(&b, 16, (uint32_t)sar_h);
-        bits_put(&b, 3, 0); /* overscan, video_signal_type, chroma_loc: absent */
-    } else bits_put(&b, 4, 0);  /* aspect_ratio, overscan, video_signal_type, chroma_loc: absent */
+    } else bits_put(&b, 1, 0);  /* aspect_ratio: absent */
+    bits_put(&b, 1, 0);  /* overscan: absent */
+    const int desc = primaries != 2 || transfer != 2 || matrix != 2;
+    if (full_range || desc) { /* video_signal_type: what the samples mean (without it a player assumes limited range and guesses the matrix from the size) */
+        bits_put(&b, 1, 1); bits_put(&b, 3, 5); /* video_format 5: unspecified */
+        bits_put(&b, 1, (uint32_t)full_range);
+        bits_put(&b, 1, (uint32_t)desc);
+        if (desc) { bits_put(&b, 8, (uint32_t)primaries); bits_put(&b, 8, (uint32_t)transfer); bits_put(&b, 8, (uint32_t)matrix); }
+    } else bits_put(&b, 1, 0);
+    bits_put(&b, 1, 0);  /* chroma_loc: absent (the default siting, type 0) */
     bits_put(&b, 1, 1);  /* timing_info_present_flag */
     bits_put(&b, 16, (uint32_t)fps_den >> 16); bits_put(&b, 16, (uint32_t)fps_den & 0xFFFF);
     bits_put(&b, 16, (uint32_t)(2 * fps_num) >> 16); bits_put(&b, 16, (uint32_t)(2 * fps_num) & 0xFFFF);

@@ -18,6 +18,11 @@ size_t h264_max_au_bytes(int mbw, int mbh);
 size_t h264_write_headers(uint8_t *out, size_t cap, int width, int height, int fps_num, int fps_den, int transform8x8);
 /* the same with a sample aspect ratio in the VUI (aspect_ratio_idc 255) unless sar_w or sar_h is 0 (then the bytes of h264_write_headers) */
 size_t h264_write_headers_sar(uint8_t *out, size_t cap, int width, int height, int fps_num, int fps_den, int transform8x8, int sar_w, int sar_h);
+/* ... and with the colorimetry of the samples in the VUI (E.1.1 video_signal_type: video_format 5, video_full_range_flag, and -- unless all three are 2,
+ * "unspecified" -- colour_primaries, transfer_characteristics, matrix_coefficients: code points of Tables E-3 / E-4 / E-5, 0 .. 255).  full_range 0 with
+ * 2, 2, 2: no video_signal_type, the bytes of h264_write_headers_sar.  0 for arguments out of range */
+size_t h264_write_headers_vui(uint8_t *out, size_t cap, int width, int height, int fps_num, int fps_den, int transform8x8, int sar_w, int sar_h,
+                              int full_range, int primaries, int transfer, int matrix);
 /* SEI NAL unit with one recovery point message (D.1.8): recovery_frame_cnt, exact_match_flag 1, broken_link_flag 0, changing_slice_group_idc 0.
  * Returns bytes written, 0 if `cap` is too small. */
 size_t h264_write_recovery_sei(uint8_t *out, size_t cap, int recovery_frame_cnt);

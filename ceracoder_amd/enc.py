@@ -23,6 +23,7 @@ FETCH_BAND_CUTS, FETCH_ERROR_WORD = 102, 103  # development: Encoder.band_cuts()
 BAND_ROWS = 4  # MI355_BAND_ROWS: macroblock rows per band of the band deblocker
 ERR_ARG, ERR_STATE = -1, -6
 FMT_NV12, FMT_I420, FMT_YUY2, FMT_UYVY = range(4)
+FMT_Y42B, FMT_Y444, FMT_YV12, FMT_NV21, FMT_BGRX, FMT_RGBX, FMT_XRGB, FMT_XBGR, FMT_BGR, FMT_RGB = range(4, 14)  # converted by k_csc.hip
 SCALE_LUMA, SCALE_CHROMA_V, SCALE_CHROMA_H, SCALE_CHROMA_V422 = range(4)  # kinds of scale_table()
 IDEC = np.dtype([("modes4", "u1", (16,)), ("mode16", "u1"), ("cmode", "u1"), ("use_i4", "u1"), ("pad", "u1"), ("cost", "<u4"), ("cost_luma", "<u4"), ("rsv", "<u4")])
 IMV_DTYPE = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("sad", "<u2"), ("bits", "<u2")])
@@ -39,6 +40,7 @@ EXPORTS = [
     "mi355enc_host_write_headers", "mi355enc_host_write_slice", "mi355enc_host_set_slice_rows", "mi355enc_host_set_p_slices", "mi355enc_stage_set_slice_rows", "mi355enc_slice_rows", "mi355enc_p_slice_rows", "mi355enc_stage_set_slice_deblock", "mi355enc_rc_init", "mi355enc_rc_set_bitrate",
     "mi355enc_rc_pick", "mi355enc_rc_update", "mi355enc_host_cavlc_block", "mi355enc_debug_trip_wait", "mi355enc_host_alloc", "mi355enc_host_free",
     "mi355enc_set_input_size", "mi355enc_stage_scale", "mi355enc_scale_table",
+    "mi355enc_set_colorimetry", "mi355enc_csc_coefficients", "mi355enc_host_write_headers_vui", "mi355enc_stage_csc_device",
 ]
 
 
@@ -110,6 +112,10 @@ def load():
         L.mi355enc_set_input_size.argtypes = [vp, C.c_int, C.c_int]
         L.mi355enc_stage_scale.argtypes = [vp, C.c_int, vp, vp, vp, vp]
         L.mi355enc_scale_table.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t, C.POINTER(C.c_int)]
+        L.mi355enc_set_colorimetry.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.mi355enc_csc_coefficients.argtypes = [C.c_int, C.c_int, vp]
+        L.mi355enc_host_write_headers_vui.argtypes = [C.c_int] * 11 + [vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.mi355enc_stage_csc_device.argtypes = [vp, C.c_int, vp, vp, vp, vp]
         L.mi355enc_host_alloc.restype = vp
         L.mi355enc_host_alloc.argtypes = [C.c_size_t]
         L.mi355enc_host_free.restype = None
@@ -151,13 +157,29 @@ def host_cavlc_block(coef, maxnum, nC):
     return "".join("{:08b}".format(b) for b in out)[:n]
 
 
-def host_write_headers(width, height, fps_num, fps_den=1, transform8x8=False):
+def host_write_headers(width, height, fps_num, fps_den=1, transform8x8=False, colorimetry=None, sar=None):
+    """SPS + PPS.  colorimetry: (full_range, primaries, transfer, matrix) for the VUI (Encoder.set_colorimetry); sar: (w, h) sample aspect ratio."""
     L = load()
     out, n = np.empty(256, np.uint8), C.c_size_t(0)
-    r = L.mi355enc_host_write_headers(width, height, fps_num, fps_den, int(transform8x8), out.ctypes.data_as(C.c_void_p), out.size, C.byref(n))
+    if colorimetry is None and sar is None:
+        r = L.mi355enc_host_write_headers(width, height, fps_num, fps_den, int(transform8x8), out.ctypes.data_as(C.c_void_p), out.size, C.byref(n))
+    else:
+        fr, p, t, m = colorimetry if colorimetry is not None else (0, 2, 2, 2)
+        sw, sh = sar if sar is not None else (0, 0)
+        r = L.mi355enc_host_write_headers_vui(width, height, fps_num, fps_den, int(transform8x8), int(sw), int(sh), int(fr), int(p), int(t), int(m),
+                                              out.ctypes.data_as(C.c_void_p), out.size, C.byref(n))
     if r:
         raise RuntimeError("mi355enc_host_write_headers: %d" % r)
     return bytes(out[: n.value])
+
+
+def csc_coefficients(matrix, full_range):
+    """The library's integer RGB -> Y'CbCr matrix (host only): int32 (10,) = yr, yg, yb, br, bg, bb, rr, rg, rb in 2^-16 units and the luma offset."""
+    c = np.zeros(10, np.int32)
+    r = load().mi355enc_csc_coefficients(int(matrix), int(full_range), c.ctypes.data_as(C.c_void_p))
+    if r:
+        raise EncoderError("mi355enc_csc_coefficients(%d, %d): %d" % (matrix, full_range, r))
+    return c
 
 
 def host_set_slice_rows(rows):
@@ -264,7 +286,7 @@ class Encoder:
     (bitrate in bits/s as written through `bps`, key-int-max -> gop)."""
 
     def __init__(self, width, height, fps=60, gop=60, bitrate_bps=6_000_000, device_id=0, fixed_qp=-1, me_range=16,
-                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False, input_size=None):
+                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False, input_size=None, colorimetry=None):
         self.L = load()
         cfg = Cfg()
         self.L.mi355enc_default_cfg(C.byref(cfg), width, height, fps, fps_den)
@@ -305,6 +327,8 @@ class Encoder:
         self._out = np.empty(self.L.mi355enc_max_au_bytes(self.h), np.uint8)
         if intra_refresh:  # periodic intra refresh instead of periodic IDR pictures (refresh period: gop)
             self._chk(self.L.mi355enc_set_intra_refresh(self.h, 1), "set_intra_refresh", close_on_fail=True)
+        if colorimetry is not None:  # (full_range, primaries, transfer, matrix): the VUI of every SPS, and the matrix RGB input is converted with
+            self._chk(self.L.mi355enc_set_colorimetry(self.h, *[int(v) for v in colorimetry]), "set_colorimetry", close_on_fail=True)
         self.input_size = (width, height)
         if input_size is not None:  # (w, h) of the submitted pictures: scaled down on the device to width x height
             self._chk(self.L.mi355enc_set_input_size(self.h, int(input_size[0]), int(input_size[1])), "set_input_size", close_on_fail=True)
@@ -337,6 +361,10 @@ class Encoder:
     def set_intra_refresh(self, on):
         self._chk(self.L.mi355enc_set_intra_refresh(self.h, int(bool(on))), "set_intra_refresh")
 
+    def set_colorimetry(self, full_range, primaries, transfer, matrix):
+        """H.264 Table E-3 / E-4 / E-5 code points for the VUI of every SPS from now on (before the first submit); RGB input is converted with them"""
+        self._chk(self.L.mi355enc_set_colorimetry(self.h, int(full_range), int(primaries), int(transfer), int(matrix)), "set_colorimetry")
+
     def encode(self, y, uv, pts=0, force_idr=False):
         y = np.ascontiguousarray(y, np.uint8)
         uv = np.ascontiguousarray(uv, np.uint8)
@@ -357,7 +385,9 @@ class Encoder:
         return arrs, pp, ss
 
     def submit_fmt(self, fmt, planes, pts=0, force_idr=False):
-        """fmt: FMT_I420 (planes Y, U, V), FMT_YUY2 / FMT_UYVY (one packed plane, 2 bytes per pixel), FMT_NV12 (Y, UV)."""
+        """fmt: FMT_I420 / FMT_YV12 / FMT_Y42B / FMT_Y444 (three planes), FMT_YUY2 / FMT_UYVY (one packed plane, 2 bytes per pixel), FMT_NV12 / FMT_NV21
+        (Y and interleaved chroma), FMT_BGRX .. FMT_XBGR (one plane, 4 bytes per pixel), FMT_BGR / FMT_RGB (3 bytes per pixel).  A contiguous plane is taken where
+        it lies (so one inside a PinnedBuffer is transferred in place)."""
         arrs, pp, ss = self._planes(planes)
         self._chk(self.L.mi355enc_submit_fmt(self.h, fmt, pp, ss, pts, int(force_idr)), "submit_fmt")
 
@@ -367,6 +397,12 @@ class Encoder:
         ouv = np.empty((self.mbh * 8, self.mbw * 16), np.uint8)
         self._chk(self.L.mi355enc_stage_csc(self.h, fmt, pp, ss, _p(oy), _p(ouv)), "stage_csc")
         return oy, ouv
+
+    def stage_csc_device(self, fmt, plane_ptrs, strides, out_y_ptr, out_uv_ptr):
+        """The conversion launch alone on device-resident planes (addresses as ints, any alignment and stride) into device surfaces of the coded size."""
+        pp = (C.c_void_p * 3)(*(list(plane_ptrs) + [None] * (3 - len(plane_ptrs))))
+        ss = (C.c_int * 3)(*(list(strides) + [0] * (3 - len(strides))))
+        self._chk(self.L.mi355enc_stage_csc_device(self.h, fmt, pp, ss, out_y_ptr, out_uv_ptr), "stage_csc_device")
 
     def set_input_size(self, w, h):
         """pictures submitted from now on are w x h (before the first submit; the coded size returns to the unscaled path)"""

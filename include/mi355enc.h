@@ -209,11 +209,33 @@ int mi355enc_submit(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t
                     int64_t pts, int force_idr);
 /* Raw input formats other than NV12 are converted on the device (no `videoconvert` hop): I420 (planes Y, U, V), and
  * packed 4:2:2 YUY2 / UYVY (plane 0 only; chroma rows are averaged pairwise with rounding to reach 4:2:0). */
-enum { MI355ENC_FMT_NV12 = 0, MI355ENC_FMT_I420 = 1, MI355ENC_FMT_YUY2 = 2, MI355ENC_FMT_UYVY = 3 };
+enum { MI355ENC_FMT_NV12 = 0, MI355ENC_FMT_I420 = 1, MI355ENC_FMT_YUY2 = 2, MI355ENC_FMT_UYVY = 3,
+/* ... and planar 4:2:2 Y42B (planes Y, U, V; chroma half width, full height: rows averaged like YUY2's), planar 4:4:4 Y444 (chroma
+ * filtered to 4:2:0 with the taps [1 2 1] x [1 1], cosited with the even luma columns), YV12 (I420 with V before U), NV21 (NV12 with V before U), and RGB
+ * of 0 .. 255 in four 4-byte orders (the byte X is ignored: BGRA, RGBA, ARGB, ABGR are submitted as these) and two 3-byte orders, plane 0 only, converted
+ * to Y'CbCr with the matrix and range of mi355enc_set_colorimetry.  mi355enc_submit_device stays NV12. */
+       MI355ENC_FMT_Y42B = 4, MI355ENC_FMT_Y444 = 5, MI355ENC_FMT_YV12 = 6, MI355ENC_FMT_NV21 = 7,
+       MI355ENC_FMT_BGRX = 8, MI355ENC_FMT_RGBX = 9, MI355ENC_FMT_XRGB = 10, MI355ENC_FMT_XBGR = 11, MI355ENC_FMT_BGR = 12, MI355ENC_FMT_RGB = 13 };
+/* What the samples mean: written into the VUI of every SPS the handle writes from now on (E.1.1 video_signal_type; each IDR picture, each refresh cycle's
+ * start, recovery re-encodes), and -- for RGB input -- the matrix and range the device converts with.  full_range 0 / 1; primaries, transfer, matrix: code
+ * points of H.264 Tables E-3 / E-4 / E-5, 0 .. 255 (2: unspecified); MI355ENC_ERR_ARG outside.  Valid only before the first submit (MI355ENC_ERR_STATE
+ * after it).  A handle on which this was never called writes no video_signal_type (0, 2, 2, 2: the stream of earlier versions).  YUV input is only
+ * labelled, never converted.  RGB input: matrix 1 (BT.709), 5 / 6 (BT.601) or 9 (BT.2020 non-constant) convert with that matrix; 2 converts with 1 when the
+ * coded picture is wider than 1024 or higher than 576, else with 6 (and the SPS still says 2: signal what you convert with); any other code makes the
+ * submit of an RGB picture fail with MI355ENC_ERR_ARG.  full_range 0: Y' 16 .. 235, CbCr 16 .. 240; 1: 0 .. 255. */
+int mi355enc_set_colorimetry(mi355enc_t *h, int full_range, int primaries, int transfer, int matrix);
+/* The RGB -> Y'CbCr matrix in the device's integer arithmetic (host only): coef[0..2] yr, yg, yb; [3..5] br, bg, bb (Cb); [6..8] rr, rg, rb (Cr), in units
+ * of 2^-16; coef[9] the luma offset (16 or 0).  Y' = clip((yr R + yg G + yb B + (off << 16) + 2^15) >> 16); Cb = clip((br S_R + bg S_G + bb S_B + (128 << 19)
+ * + 2^18) >> 19) from the eight-weight sums S of the 2 x 2 site, Cr likewise.  matrix: 1, 5, 6 or 9, else MI355ENC_ERR_ARG. */
+int mi355enc_csc_coefficients(int matrix, int full_range, int32_t coef[10]);
 /* like mi355enc_submit, from host memory in `fmt`; planes[]/strides[]: as many entries as the format has planes */
 int mi355enc_submit_fmt(mi355enc_t *h, int fmt, const uint8_t *const planes[3], const int strides[3], int64_t pts, int force_idr);
 /* conversion stage alone (tests): writes the coded-size NV12 surfaces (16*mbw x 16*mbh luma, then interleaved chroma) */
 int mi355enc_stage_csc(mi355enc_t *h, int fmt, const uint8_t *const planes[3], const int strides[3], uint8_t *out_y, uint8_t *out_uv);
+/* ... on planes that lie in this GPU's memory, into device memory (tests of unaligned planes, probes: no transfer, one launch): the planes as they are --
+ * any address, any stride -- of the coded visible size, into coded-size surfaces of stride 16 * mb_width at 8-byte aligned addresses.  Every format but
+ * NV12 (which has no conversion); ignores mi355enc_set_input_size.  Returns when the launch has completed. */
+int mi355enc_stage_csc_device(mi355enc_t *h, int fmt, const void *const d_planes[3], const int strides[3], void *d_out_y, void *d_out_uv);
 int mi355enc_submit_device(mi355enc_t *h, const void *d_y, int y_stride, const void *d_uv,
                            int uv_stride, int64_t pts, int force_idr);
 /* Downscaling on the way in.  The pictures submitted from now on are in_w x in_h; the device scales them to the
@@ -306,6 +328,10 @@ int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms);
  * SPS+PPS, and one CAVLC slice NAL from macroblock records + levels.  *out_len = bytes. */
 int mi355enc_host_write_headers(int width, int height, int fps_num, int fps_den, int transform8x8, uint8_t *out, size_t out_cap,
                                 size_t *out_len);
+/* ... with a sample aspect ratio (sar_w : sar_h; 0: none) and the colorimetry of mi355enc_set_colorimetry in the VUI; (0, 0, 0, 2, 2, 2) gives the bytes of
+ * mi355enc_host_write_headers */
+int mi355enc_host_write_headers_vui(int width, int height, int fps_num, int fps_den, int transform8x8, int sar_w, int sar_h, int full_range, int primaries,
+                                    int transfer, int matrix, uint8_t *out, size_t out_cap, size_t *out_len);
 int mi355enc_host_write_slice(int mb_width, int mb_height, int is_idr, int frame_num, int idr_pic_id, int slice_qp, int transform8x8,
                               const void *mbinfo, const int16_t *levels, uint8_t *out, size_t out_cap, size_t *out_len);
 /* process-wide, for the two host stage functions below: I pictures are written as slices of `rows` macroblock rows (0, the default: one slice) */
