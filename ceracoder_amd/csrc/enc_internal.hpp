@@ -57,6 +57,7 @@ struct slot_t {
     uint64_t index;            // position of the picture in the stream
     int is_idr, qp, drop, frame_num, idr_pic_id, rec_index, set;
     int ir_start;              // periodic intra refresh: the first picture of a refresh cycle (SPS, PPS and a recovery point SEI lead its access unit; a sync point)
+    int fixed_qp, fixed_drop;  // the constant-QP override this picture was submitted under (-1: none): recover() re-encodes it under the same one
     int rc_picked;             // rate control booked this picture (rc_pick): its size is reported back (rc_update) or the booking taken back (rc_cancel)
     int64_t pts;
     // entropy coding on the handle's worker thread (pipeline_depth >= 1): the access unit is coded here while the caller submits the next picture

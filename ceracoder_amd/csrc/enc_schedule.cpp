@@ -147,7 +147,8 @@ int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_
     rc_set_bitrate(&h->rc, h->want_bps.load(std::memory_order_relaxed));
     int fq = h->fixed_qp.load(std::memory_order_relaxed);
     int qp, drop;
-    if (fq >= 0) { qp = fq; drop = h->fixed_drop.load(std::memory_order_relaxed); s->rc_picked = 0; } // (no pick: collect() / recover() then leave rate control alone for this picture)
+    s->fixed_qp = fq; s->fixed_drop = 0;
+    if (fq >= 0) { qp = fq; drop = s->fixed_drop = h->fixed_drop.load(std::memory_order_relaxed); s->rc_picked = 0; } // (no pick: collect() / recover() then leave rate control alone for this picture)
     else { rc_pick(&h->rc, idr, &qp, &drop); s->rc_picked = 1; }
     if (idr && drop == DROP_SKIP) drop = 0; // an IDR picture is never skipped; it has a ladder of its own
     // Periodic intra refresh: P picture p >= 1 after the IDR picture is picture j = (p - 1) mod N of a cycle (N = cfg.gop) and
@@ -462,17 +463,21 @@ static int recover(mi355enc_t *h, unsigned code) {
     h->pmb_rows_total = 0; h->db_started_total = 0; h->ip_done_total = 0; h->qpc_total = 0; h->rec_epoch[0] = h->rec_epoch[1] = 0; h->dbI_busy[0] = h->dbI_busy[1] = 0;
     if (h->safe_level == 2) { h->cfg.deblock_mode = 1; h->cfg.intra_mode = 1; }
     const int n = h->pending;
-    struct { const uint8_t *y, *uv; int stride, force_idr; int64_t pts; } again[NSLOT];
+    struct { const uint8_t *y, *uv; int stride, force_idr; int64_t pts; int fixed_qp, fixed_drop; } again[NSLOT];
     for (int i = 0; i < n; i++) {
         slot_t *p = &h->slot[(h->tail + i) % NSLOT];
-        again[i] = {p->src_y, p->src_uv, p->src_stride, p->force_idr, p->pts};
+        again[i] = {p->src_y, p->src_uv, p->src_stride, p->force_idr, p->pts, p->fixed_qp, p->fixed_drop};
         if (p->is_idr) h->idr_count--;
         p->h_hdr[1] = 0;
         if (p->rc_picked) rc_cancel(&h->rc); // their rate-control bookings (rc_cancel takes back the newest one outstanding: only the count matters)
     }
     h->n_submitted -= (uint64_t)n; h->head = h->tail; h->pending = 0; h->have_ref = 0;
+    // a picture submitted under a constant-QP override is coded again under that one, not under whatever mi355enc_set_fixed_qp() has said since
+    const int now_qp = h->fixed_qp.load(std::memory_order_relaxed), now_drop = h->fixed_drop.load(std::memory_order_relaxed);
     for (int i = 0; i < n; i++) {
+        if (again[i].fixed_qp >= 0) { h->fixed_qp.store(again[i].fixed_qp, std::memory_order_relaxed); h->fixed_drop.store(again[i].fixed_drop, std::memory_order_relaxed); }
         int r = enqueue_picture(h, &h->slot[h->head], again[i].y, again[i].uv, again[i].stride, again[i].pts, i == 0 ? 1 : again[i].force_idr);
+        h->fixed_qp.store(now_qp, std::memory_order_relaxed); h->fixed_drop.store(now_drop, std::memory_order_relaxed);
         if (r) return r;
     }
     return MI355ENC_OK;

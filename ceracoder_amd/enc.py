@@ -281,6 +281,15 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _rows(a):
+    """A picture plane as the library takes it.  A uint8 array of rows of adjacent samples is taken where it lies, at the
+    row stride it has (a view into a wider or taller array, a plane inside a PinnedBuffer); anything else is made
+    contiguous first."""
+    if isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.ndim == 2 and a.strides[-1] == 1 and a.strides[0] >= a.shape[1]:
+        return a
+    return np.ascontiguousarray(a, np.uint8)
+
+
 class Encoder:
     """One H.264 stream on one GPU.  Arguments mirror the element's properties
     (bitrate in bits/s as written through `bps`, key-int-max -> gop)."""
@@ -366,16 +375,14 @@ class Encoder:
         self._chk(self.L.mi355enc_set_colorimetry(self.h, int(full_range), int(primaries), int(transfer), int(matrix)), "set_colorimetry")
 
     def encode(self, y, uv, pts=0, force_idr=False):
-        y = np.ascontiguousarray(y, np.uint8)
-        uv = np.ascontiguousarray(uv, np.uint8)
+        y, uv = _rows(y), _rows(uv)
         n, key = C.c_size_t(0), C.c_int(0)
         self._chk(self.L.mi355enc_encode(self.h, _p(y), y.strides[0], _p(uv), uv.strides[0], pts, int(force_idr),
                                          _p(self._out), self._out.size, C.byref(n), C.byref(key)), "encode")
         return bytes(self._out[: n.value]), bool(key.value)
 
     def submit(self, y, uv, pts=0, force_idr=False):
-        y = np.ascontiguousarray(y, np.uint8)
-        uv = np.ascontiguousarray(uv, np.uint8)
+        y, uv = _rows(y), _rows(uv)
         self._chk(self.L.mi355enc_submit(self.h, _p(y), y.strides[0], _p(uv), uv.strides[0], pts, int(force_idr)), "submit")
 
     def _planes(self, planes):

@@ -204,7 +204,11 @@ void mi355enc_host_free(void *p);
 /* Split form.  submit() enqueues all device work of a picture and returns; collect()
  * entropy-codes the oldest submitted picture.  At most pipeline_depth+1 pictures may be
  * outstanding.  submit_device() takes planes already resident in this GPU's memory
- * (the bench's timed region; they must stay valid until the matching collect()). */
+ * (the bench's timed region; they must stay valid until the matching collect()).
+ * Which way submit_device() takes (without mi355enc_set_input_size): the kernels read the planes where they lie,
+ * at the caller's stride, when the width is a multiple of 16, y_stride == uv_stride and a multiple of 16, and
+ * both addresses are 16-byte aligned; anything else is first copied on the device into the encoder's own
+ * surfaces (and a width that is not a multiple of 16 padded there).  The stream is the same either way. */
 int mi355enc_submit(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t *uv, int uv_stride,
                     int64_t pts, int force_idr);
 /* Raw input formats other than NV12 are converted on the device (no `videoconvert` hop): I420 (planes Y, U, V), and

@@ -1,7 +1,6 @@
 """GPU: downscaling on the way in (mi355enc_set_input_size, k_scale.hip) -- the kernel bit-exact against tests/scaleref.py, streams
 submitted at the input size equal to the same pictures scaled by numpy and submitted unscaled, the SPS's sample aspect ratio, the call
 order, and the element's width / height."""
-import ctypes as C
 import os
 import subprocess
 
@@ -9,6 +8,7 @@ import numpy as np
 import pytest
 
 from tests import scaleref as R
+from tests.inputref import device_planes
 
 pytestmark = pytest.mark.gpu
 
@@ -108,22 +108,6 @@ def run_stream(E, e, feed, n, oracle=None):
             y, uv = dec.decode(au)
         assert np.array_equal(y, e.fetch(E.FETCH_RECON_Y)) and np.array_equal(uv, e.fetch(E.FETCH_RECON_UV))
     return aus
-
-
-def device_planes(E, host, rows, cols, stride, offset):
-    """`host` (rows x cols per plane, in order) copied into one hipMalloc'd buffer at `stride` from byte `offset` on; -> (buffer, plane pointers)"""
-    hip = C.CDLL("libamdhip64.so.7")  # (the runtime the library itself runs on)
-    size = offset + sum(r * stride for r in rows)
-    buf = C.c_void_p()
-    assert hip.hipMalloc(C.byref(buf), C.c_size_t(size)) == 0
-    ptrs, o = [], offset
-    for a, r, w in zip(host, rows, cols):
-        a = np.ascontiguousarray(a)
-        assert hip.hipMemcpy2D(C.c_void_p(buf.value + o), C.c_size_t(stride), a.ctypes.data_as(C.c_void_p), C.c_size_t(w), C.c_size_t(w),
-                               C.c_size_t(r), 1) == 0  # hipMemcpyHostToDevice
-        ptrs.append(buf.value + o)
-        o += r * stride
-    return hip, buf, ptrs
 
 
 @pytest.fixture(scope="module")
