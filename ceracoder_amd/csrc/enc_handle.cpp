@@ -135,6 +135,7 @@ int mi355enc_open(const mi355enc_cfg_t *cfg, mi355enc_t **out) {
     h->ir_on = 0; h->ir_pos = 0; h->ir_R = 0; h->ir_skip_owed = 0;
     h->in_w = cfg->width; h->in_h = cfg->height; h->sar_w = h->sar_h = 0; h->scaling = false; h->d_scale_tab = nullptr; h->scale_tab_bytes = 0; memset(&h->scale, 0, sizeof h->scale);
     h->col_full = 0; h->col_prim = h->col_trc = h->col_mat = 2; csc_resolve(h);
+    h->q_on = false; h->q_have = false; h->d_qacc = nullptr; h->h_qres = nullptr; for (int i = 0; i < NSLOT; i++) h->ev_q[i] = nullptr; memset(&h->q_last, 0, sizeof h->q_last); memset(&h->q_tot, 0, sizeof h->q_tot);
     for (int i = 0; i < NSET; i++) { h->g_intra[i] = h->g_deblock[i] = nullptr; h->d_ctx2[i] = nullptr; h->d_surf[i] = nullptr; h->d_idec2[i] = nullptr; h->d_mbi_set[i] = nullptr; h->d_levels_set[i] = nullptr; h->d_qp_off[i] = nullptr; }
     h->prev_slot = nullptr;
     h->d_ctx = nullptr; h->d_pre_y = h->d_pre_uv = nullptr; memset(h->d_imv, 0, sizeof h->d_imv); h->d_psrc[0] = h->d_psrc[1] = nullptr; h->psrc_cur = 0; h->fstream = nullptr; h->ustream = nullptr; h->d_ip_progress = nullptr; h->d_ip_strips = nullptr; h->epoch = 0; h->istream = nullptr; h->ev_pmb = nullptr; h->d_db_gran = nullptr; h->d_db_done = nullptr; h->rec_epoch[0] = h->rec_epoch[1] = 0; h->db_started_total = 0; h->ip_done_total = 0; h->d_row_done = nullptr; h->pmb_rows_total = 0; h->d_db_par = nullptr; h->d_db_part = nullptr; h->d_ib_gran = nullptr; h->d_iband_done = nullptr; h->ev_dbI[0] = h->ev_dbI[1] = nullptr; h->dbI_busy[0] = h->dbI_busy[1] = 0; h->d_progress = nullptr; h->d_off = nullptr; h->d_isad = nullptr; h->d_dbrec = nullptr; h->d_idec = nullptr;
@@ -341,6 +342,7 @@ void mi355enc_close(mi355enc_t *h) {
     for (int i = 0; i < 2; i++) if (h->ev_dbI[i]) (void)hipEventDestroy(h->ev_dbI[i]);
     if (h->d_off) (void)hipFree(h->d_off);
     if (h->d_scale_tab) (void)hipFree(h->d_scale_tab);
+    quality_free(h);
     for (int k = 0; k < NSET; k++) {
         if (h->d_surf[k]) (void)hipFree(h->d_surf[k]);
         for (int i = 0; i < 3; i++) if (h->d_imv[k][i]) (void)hipFree(h->d_imv[k][i]);
@@ -397,7 +399,7 @@ int mi355enc_get_stats(mi355enc_t *h, mi355enc_stats_t *st) {
     st->recoveries = h->n_recoveries; st->last_error_word = h->last_error_word; st->safe_level = (uint32_t)h->safe_level;
     return MI355ENC_OK;
 }
-void mi355enc_reset_stats(mi355enc_t *h) { if (h) { memset(&h->st, 0, sizeof h->st); h->n_skip_pictures = 0; } }
+void mi355enc_reset_stats(mi355enc_t *h) { if (h) { memset(&h->st, 0, sizeof h->st); h->n_skip_pictures = 0; memset(&h->q_tot, 0, sizeof h->q_tot); } }
 
 int mi355enc_fetch(mi355enc_t *h, int what, void *dst, size_t n) {
     if (!h || !dst) return MI355ENC_ERR_ARG;

@@ -149,6 +149,14 @@ struct mi355enc {
     int col_full, col_prim, col_trc, col_mat;
     int csc_coef[10]; bool csc_ok;
     uint32_t n_recoveries, last_error_word;
+    // quality metrics (mi355enc_set_quality_metrics; everything null / 0 while they are off and no stage call has asked for them):
+    // per slot, and one more for the single-stage entry points, a block of QUALITY_WORDS accumulator words on the device and of result words in pinned
+    // host memory (the launch's last workgroup writes them); per slot the event behind the launch, which collect() waits for
+    bool q_on;
+    unsigned long long *d_qacc, *h_qres;
+    hipEvent_t ev_q[NSLOT];
+    mi355enc_quality_t q_last, q_tot; // the last collected picture's / the integer sums since open or reset_stats
+    bool q_have;
     // the entropy-coding worker (started by open() when pipeline_depth >= 1)
     std::thread wk;
     std::mutex wk_mu;
@@ -194,6 +202,14 @@ int upload_and_convert(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const p
 // a picture of the input size tightly into the slot's raw staging buffer (any format); p / st: where its planes lie on the device then
 int upload_raw(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const planes[3], const int strides[3], hipStream_t up, const uint8_t *p[3], int st[3]);
 size_t raw_bytes(const mi355enc_t *h); // size of a slot's raw staging buffer
+// enc_quality.cpp
+int quality_alloc(mi355enc_t *h);   // the accumulator and result blocks (idempotent)
+void quality_free(mi355enc_t *h);
+// the picture of slot s: source (src_y, src_uv, src_stride) against reconstruction buffer `rec`, behind everything enqueued on st so far; records the slot's event
+int quality_enqueue(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_t *src_uv, int src_stride, int rec, hipStream_t st);
+int quality_collect(mi355enc_t *h, slot_t *s); // waits for the slot's metrics, books them as the last picture's and into the totals
+// one launch on the handle's main stream with the block of the stage entry points, waited for
+int quality_run(mi355enc_t *h, const uint8_t *src_y, const uint8_t *src_uv, int src_stride, const uint8_t *rec_y, const uint8_t *rec_uv, mi355enc_quality_t *q);
 // enc_csc.cpp
 void csc_resolve(mi355enc_t *h); // fills csc_coef / csc_ok from col_mat, col_full and the coded size
 #endif

@@ -182,6 +182,13 @@ int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_
             HIPCHK(hipMemcpyAsync(h->d_pre_y, h->d_rec_y[nxt], h->ysz, hipMemcpyDeviceToDevice, h->stream));
             HIPCHK(hipMemcpyAsync(h->d_pre_uv, h->d_rec_uv[nxt], h->csz, hipMemcpyDeviceToDevice, h->stream));
         }
+        if (h->q_on) { // quality metrics: the picture repeats its reference, so that is what the source is measured against -- on the main stream, behind the reference's
+            // deblocking (an IDR picture's may have run on the intra stream) and behind the source's arrival on the front stream, which nothing else of this picture waits for
+            HIPCHK(hipEventRecord(s->ev_front, h->fstream));
+            HIPCHK(hipStreamWaitEvent(h->stream, s->ev_front, 0));
+            if (h->dbI_busy[nxt]) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_dbI[nxt], 0)); h->dbI_busy[nxt] = 0; }
+            int r = quality_enqueue(h, s, src_y, src_uv, src_stride, nxt, h->stream); if (r) return r;
+        }
     } else {
         c->src_y = src_y; c->src_uv = src_uv; c->src_stride = src_stride;
         c->ref_y = h->d_rec_y[h->cur]; c->ref_uv = h->d_rec_uv[h->cur];
@@ -265,11 +272,16 @@ int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_
         }
         if (isplit) {
             int r = run_deblock(h, ci, c, h->istream, nullptr, h->d_iband_done + (size_t)nxt * h->mbh, h->d_db_done + (size_t)nxt * nbd); if (r) return r;
+            if (h->q_on) { r = quality_enqueue(h, s, src_y, src_uv, src_stride, nxt, h->istream); if (r) return r; } // in front of the event the buffer's next writer waits for
             HIPCHK(hipEventRecord(h->ev_dbI[nxt], h->istream));
             h->dbI_busy[nxt] = 1;
         } else if (!fip) { int r = run_deblock(h, ci, c, mst, (split || (pgate && c->intra_p)) ? h->d_ip_progress : nullptr, nullptr, h->d_db_done + (size_t)nxt * nbd, prows != 0); if (r) return r; }
         h->rec_epoch[nxt] = h->cfg.deblock_mode == 0 ? c->epoch : 0;
         if (prof) { HIPCHK(hipEventRecord(s->ev[3], h->stream)); HIPCHK(hipEventRecord(s->ev[4], h->stream)); }
+        // Quality metrics: directly behind the picture's deblocking launch, on its stream.  Whatever writes this reconstruction buffer next (the picture after next) is
+        // either behind it in the main stream's order, or a gated fused P stage on the intra stream, which starts only when the deblocking launch of the picture
+        // between the two is on the chip -- a launch that sits behind this one in the main stream.
+        if (h->q_on && !isplit) { int r = quality_enqueue(h, s, src_y, src_uv, src_stride, nxt, mst); if (r) return r; }
         // Hand-over, enqueued after the deblocking launches so that it cannot be dispatched ahead of them: the device packs the non-zero
         // blocks straight into the pinned host buffer while the band deblocker runs.
         hipStream_t pst = h->cstream;
@@ -459,6 +471,7 @@ static int recover(mi355enc_t *h, unsigned code) {
     if (h->d_db_part) HIPCHK(hipMemsetAsync(h->d_db_part, 0, 6 * (size_t)k_deblock_bands16(h->mbh) * sizeof(unsigned), h->stream));
     HIPCHK(hipMemsetAsync(h->d_db_done, 0, 2 * k_deblock_done_bytes(), h->stream));
     HIPCHK(hipMemsetAsync(h->d_iband_done, 0, 2 * (size_t)h->mbh * sizeof(unsigned), h->stream));
+    if (h->d_qacc) HIPCHK(hipMemsetAsync(h->d_qacc, 0, (size_t)(NSLOT + 1) * QUALITY_ACC_WORDS * sizeof(unsigned long long), h->stream)); // (every launch has completed and left its block clear; kept with the other device-side words)
     HIPCHK(hipStreamSynchronize(h->stream));
     h->pmb_rows_total = 0; h->db_started_total = 0; h->ip_done_total = 0; h->qpc_total = 0; h->rec_epoch[0] = h->rec_epoch[1] = 0; h->dbI_busy[0] = h->dbI_busy[1] = 0;
     if (h->safe_level == 2) { h->cfg.deblock_mode = 1; h->cfg.intra_mode = 1; }
@@ -645,6 +658,7 @@ int mi355enc_collect(mi355enc_t *h, uint8_t *out, size_t out_cap, size_t *out_le
         if (!m) return MI355ENC_ERR_OVERFLOW;
         h->st.ms_entropy += now_ms() - t1;
     }
+    if (h->q_on) { int r = quality_collect(h, s); if (r) return r; } // (a picture that came back through recover(): the re-encode's)
     *out_len = n + m;
     if (is_keyframe) *is_keyframe = s->is_idr || s->ir_start; // (intra refresh: a cycle's first picture is a recovery point)
     if (pts) *pts = s->pts;

@@ -188,6 +188,28 @@ int mi355enc_stage_deblock(mi355enc_t *h, uint8_t *rec_y, uint8_t *rec_uv, const
     HIPCHK(hipStreamSynchronize(h->stream));
     return MI355ENC_OK;
 }
+// quality metrics, the kernel alone: host planes of the coded size through the encoder's own surfaces ...
+int mi355enc_stage_quality(mi355enc_t *h, const uint8_t *src_y, const uint8_t *src_uv, const uint8_t *rec_y, const uint8_t *rec_uv, mi355enc_quality_t *q) {
+    if (!h || !src_y || !src_uv || !rec_y || !rec_uv || !q) return MI355ENC_ERR_ARG;
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    STAGE_IDLE(h);
+    HIPCHK(hipStreamSynchronize(h->cstream));
+    { int r = sync_compute(h); if (r) return r; }
+    slot_t *s = &h->slot[0];
+    HIPCHK(hipMemcpyAsync(s->d_src_y, src_y, h->ysz, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(s->d_src_uv, src_uv, h->csz, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_rec_y[1], rec_y, h->ysz, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_rec_uv[1], rec_uv, h->csz, hipMemcpyHostToDevice, h->stream));
+    stage_touched(h);
+    return quality_run(h, s->d_src_y, s->d_src_uv, h->W, h->d_rec_y[1], h->d_rec_uv[1], q);
+}
+// ... and planes that lie on the device, where they lie
+int mi355enc_stage_quality_device(mi355enc_t *h, const void *d_src_y, const void *d_src_uv, int src_stride, const void *d_rec_y, const void *d_rec_uv, mi355enc_quality_t *q) {
+    if (!h || !d_src_y || !d_src_uv || !d_rec_y || !d_rec_uv || !q || src_stride < h->cfg.width) return MI355ENC_ERR_ARG;
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    STAGE_IDLE(h);
+    return quality_run(h, (const uint8_t *)d_src_y, (const uint8_t *)d_src_uv, src_stride, (const uint8_t *)d_rec_y, (const uint8_t *)d_rec_uv, q);
+}
 int mi355enc_debug_trip_wait(mi355enc_t *h, unsigned code) {
     if (!h || !code) return MI355ENC_ERR_ARG;
     HIPCHK(hipSetDevice(h->cfg.device_id));
@@ -197,7 +219,7 @@ int mi355enc_debug_trip_wait(mi355enc_t *h, unsigned code) {
     return MI355ENC_OK;
 }
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
-    if (!h || !avg_ms || iters < 1 || stage < 0 || stage > 10) return MI355ENC_ERR_ARG;
+    if (!h || !avg_ms || iters < 1 || stage < 0 || stage > 11) return MI355ENC_ERR_ARG;
     if (h->pending) return MI355ENC_ERR_STATE;
     HIPCHK(hipSetDevice(h->cfg.device_id));
     slot_t *s = &h->slot[0];
@@ -212,7 +234,8 @@ int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
         HIPCHK(hipMemcpyAsync(h->d_ctx, s->h_ctx, sizeof(frame_ctx_t), hipMemcpyHostToDevice, h->stream));
         stage_touched(h);
     }
-    if (stage >= 5 && !s->d_raw) { // input conversion (5 I420, 6 YUY2, 7 UYVY): any bytes will do as a source
+    if (stage == 11) { int r = quality_alloc(h); if (r) return r; } // (the block of the stage entry points)
+    if (stage >= 5 && stage <= 7 && !s->d_raw) { // input conversion (5 I420, 6 YUY2, 7 UYVY): any bytes will do as a source
         HIPCHK(hipMalloc((void **)&s->d_raw, raw_bytes(h)));
         HIPCHK(hipMemsetAsync(s->d_raw, 0x55, raw_bytes(h), h->stream));
     }
@@ -225,6 +248,8 @@ int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
             else if (stage == 4) k_launch_subpel(h->slot[0].h_ctx, h->mbw, 0, h->mbh, h->stream);
             else if (stage == 8) k_launch_me_select(h->slot[0].h_ctx, h->mbw, 0, h->mbh, h->d_imv[0][0], h->d_imv[0][1], nullptr, 0, h->stream);
             else if (stage == 9) k_launch_pmb(h->slot[0].h_ctx, h->mbw, 0, h->mbh, 1, nullptr, 0, err_word(h), nullptr, h->stream);
+            else if (stage == 11) k_launch_quality(s->d_src_y, s->d_src_uv, h->W, h->d_rec_y[1], h->d_rec_uv[1], h->W, h->cfg.width, h->cfg.height, h->d_qacc + (size_t)NSLOT * QUALITY_ACC_WORDS,
+                                                   h->h_qres + (size_t)NSLOT * QUALITY_WORDS, h->stream);
             else if (stage == 10) k_launch_intra_p(h->slot[0].h_ctx, h->mbw, h->mbh, h->d_ip_progress, h->d_ip_strips, err_word(h), h->stream);
             else if (stage >= 5) {
                 const int w = h->cfg.width, ht = h->cfg.height, r0 = stage == 5 ? (w + 15) & ~15 : (2 * w + 15) & ~15, r1 = (w / 2 + 15) & ~15;

@@ -55,6 +55,7 @@ typedef struct {
     gint intra_slices;
     gboolean single_stream;
     gboolean dct8x8_adaptive; /* with dct8x8: the transform size is chosen per P macroblock (cfg.transform8x8 = 2) */
+    gboolean quality_stats;   /* per-picture PSNR / SSIM computed on the device (mi355enc_set_quality_metrics); with stats=true the stream's figures are printed at close */
     gboolean intra_refresh;   /* periodic intra refresh instead of periodic IDR pictures (mi355enc_set_intra_refresh); key-int-max is the refresh period */
     gint out_w, out_h;        /* coded size (mpph265enc's width / height): 0 = the input's; smaller: scaled down on the device (mi355enc_set_input_size) */
     /* streaming state */
@@ -73,7 +74,7 @@ typedef struct { GstVideoEncoderClass parent_class; } GstMi355H264EncClass;
 G_DEFINE_TYPE(GstMi355H264Enc, gst_mi355h264enc, GST_TYPE_VIDEO_ENCODER)
 
 enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME_RANGE, PROP_QP, PROP_PIPELINE_DEPTH,
-       PROP_SPEED_PRESET, PROP_STATS, PROP_DCT8X8, PROP_THREADS, PROP_SCENECUT, PROP_VBV, PROP_INTRA_IN_P, PROP_EXCLUSIVE, PROP_PINNED_INPUT, PROP_AQ_MODE, PROP_SINGLE_STREAM, PROP_INTRA_SLICES, PROP_I8X8, PROP_SLICES, PROP_SLICE_DEBLOCK, PROP_DCT8X8_ADAPTIVE, PROP_INTRA_REFRESH, PROP_WIDTH, PROP_HEIGHT };
+       PROP_SPEED_PRESET, PROP_STATS, PROP_DCT8X8, PROP_THREADS, PROP_SCENECUT, PROP_VBV, PROP_INTRA_IN_P, PROP_EXCLUSIVE, PROP_PINNED_INPUT, PROP_AQ_MODE, PROP_SINGLE_STREAM, PROP_INTRA_SLICES, PROP_I8X8, PROP_SLICES, PROP_SLICE_DEBLOCK, PROP_DCT8X8_ADAPTIVE, PROP_INTRA_REFRESH, PROP_WIDTH, PROP_HEIGHT, PROP_QUALITY_STATS };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
     GST_STATIC_CAPS("video/x-raw, format=(string){ NV12, I420, YUY2, UYVY, Y42B, Y444, YV12, NV21, BGRx, RGBx, xRGB, xBGR, BGRA, RGBA, ARGB, ABGR, BGR, RGB }, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]"));
@@ -144,6 +145,7 @@ static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *
     case PROP_DCT8X8: s->dct8x8 = g_value_get_boolean(val) ? 1 : 0; break;
     case PROP_DCT8X8_ADAPTIVE: s->dct8x8_adaptive = g_value_get_boolean(val); break;
     case PROP_INTRA_REFRESH: s->intra_refresh = g_value_get_boolean(val); break;
+    case PROP_QUALITY_STATS: s->quality_stats = g_value_get_boolean(val); break;
     case PROP_WIDTH: s->out_w = g_value_get_int(val); break;
     case PROP_HEIGHT: s->out_h = g_value_get_int(val); break;
     case PROP_THREADS: s->threads = g_value_get_int(val); break;
@@ -180,6 +182,7 @@ static void get_property(GObject *obj, guint id, GValue *val, GParamSpec *ps) {
     case PROP_DCT8X8: g_value_set_boolean(val, t.dct8x8 != 0); break;
     case PROP_DCT8X8_ADAPTIVE: g_value_set_boolean(val, s->dct8x8_adaptive); break;
     case PROP_INTRA_REFRESH: g_value_set_boolean(val, s->intra_refresh); break;
+    case PROP_QUALITY_STATS: g_value_set_boolean(val, s->quality_stats); break;
     case PROP_WIDTH: g_value_set_int(val, s->out_w); break;
     case PROP_HEIGHT: g_value_set_int(val, s->out_h); break;
     case PROP_THREADS: g_value_set_int(val, s->threads); break;
@@ -214,6 +217,10 @@ static void close_encoder(GstMi355H264Enc *s) {
                            st.ms_entropy, st.ms_wait, st.last_qp, st.ms_open, st.target_bps, (double)s->us_map / (double)(s->us_frames ? s->us_frames : 1),
                            (double)s->us_submit / (double)(s->us_frames ? s->us_frames : 1), (double)s->us_collect / (double)(s->us_frames ? s->us_frames : 1),
                            (double)s->us_output / (double)(s->us_frames ? s->us_frames : 1), (double)s->us_push / (double)(s->us_frames ? s->us_frames : 1));
+            mi355enc_quality_t q; /* (MI355ENC_ERR_STATE unless quality-stats=true) */
+            if (mi355enc_quality_totals(e, &q) == 0 && q.pictures)
+                g_printerr("{\"element\":\"mi355h264enc\",\"quality\":{\"pictures\":%" G_GUINT64_FORMAT ",\"psnr_y\":%.3f,\"psnr_cb\":%.3f,\"psnr_cr\":%.3f,\"ssim\":%.5f}}\n",
+                           q.pictures, q.psnr[0], q.psnr[1], q.psnr[2], q.ssim);
         }
         mi355enc_close(e);
     }
@@ -311,7 +318,7 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
         if (t.slices >= 0) cfg.slices = t.slices;               /* (-1: mi355enc_default_cfg's) */
         if (t.slice_deblock >= 0) cfg.slice_deblock = t.slice_deblock;
     }
-    const gboolean intra_refresh = s->intra_refresh;
+    const gboolean intra_refresh = s->intra_refresh, quality_stats = s->quality_stats;
     if (intra_refresh) { cfg.partitions = 0; if (!cfg.intra_in_p) cfg.intra_in_p = 1; } /* (the refresh columns are intra macroblocks of P pictures; no partitions) */
     GST_OBJECT_UNLOCK(s);
     int r = mi355enc_open(&cfg, &e);
@@ -327,6 +334,7 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
         r = mi355enc_set_colorimetry(e, full, prim, trc, mat);
     }
     if (r == MI355ENC_OK && (in_w != out_w || in_h != out_h)) r = mi355enc_set_input_size(e, in_w, in_h); /* (refused: upscaling, a ratio above 8, odd sizes) */
+    if (r == MI355ENC_OK && quality_stats) r = mi355enc_set_quality_metrics(e, 1);
     if (r != MI355ENC_OK) {
         if (e) mi355enc_close(e);
         GST_ELEMENT_ERROR(s, LIBRARY, INIT, ("mi355h264enc: cannot open the MI355X encoder: %s", mi355enc_strerror(r)),
@@ -587,6 +595,9 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
         "Width of the coded picture; 0: the input's.  Smaller than the input: the picture is scaled down on the GPU (up to 8:1 per axis, even sizes)", 0, 8192, 0, F));
     g_object_class_install_property(g, PROP_HEIGHT, g_param_spec_int("height", "Coded height",
         "Height of the coded picture; 0: the input's.  Smaller than the input: the picture is scaled down on the GPU (up to 8:1 per axis, even sizes)", 0, 8192, 0, F));
+    g_object_class_install_property(g, PROP_QUALITY_STATS, g_param_spec_boolean("quality-stats", "Quality metrics",
+        "Measure every coded picture on the GPU (PSNR of Y, Cb, Cr and SSIM of the luma, source against reconstruction); with stats=true the stream's figures are printed when the encoder closes. Read when the encoder opens", FALSE,
+        (GParamFlags)(G_PARAM_READWRITE | G_PARAM_STATIC_STRINGS | GST_PARAM_MUTABLE_READY)));
     g_object_class_install_property(g, PROP_STATS, g_param_spec_boolean("stats", "Print stats", "Print a JSON line with counters when the encoder closes", FALSE, F));
     gst_element_class_add_static_pad_template(e, &sink_tmpl);
     gst_element_class_add_static_pad_template(e, &src_tmpl);
@@ -597,7 +608,7 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
 }
 static void gst_mi355h264enc_init(GstMi355H264Enc *s) {
     s->rate_raw = 2048; s->rate_is_bps = FALSE; s->key_int_max = 60; s->device_id = 0; s->me_range = 16; s->qp = -1; s->pipeline_depth = 0; s->speed_preset = 0;
-    s->stats = FALSE; s->dct8x8 = -1; s->threads = 0; s->scenecut = TRUE; s->exclusive_gpu = FALSE; s->vbv_ms = 600; s->intra_in_p = -1; s->pinned_input = TRUE; s->aq_mode = -1; s->slices = -1; s->slice_deblock = -1; s->intra_slices = 0; s->i8x8 = -1; s->single_stream = FALSE; s->dct8x8_adaptive = FALSE; s->intra_refresh = FALSE; s->enc = NULL; s->input_state = NULL; s->max_au = 0; s->au_buf = NULL; s->last_pts = GST_CLOCK_TIME_NONE;
+    s->stats = FALSE; s->dct8x8 = -1; s->threads = 0; s->scenecut = TRUE; s->exclusive_gpu = FALSE; s->vbv_ms = 600; s->intra_in_p = -1; s->pinned_input = TRUE; s->aq_mode = -1; s->slices = -1; s->slice_deblock = -1; s->intra_slices = 0; s->i8x8 = -1; s->single_stream = FALSE; s->dct8x8_adaptive = FALSE; s->intra_refresh = FALSE; s->quality_stats = FALSE; s->enc = NULL; s->input_state = NULL; s->max_au = 0; s->au_buf = NULL; s->last_pts = GST_CLOCK_TIME_NONE;
     s->us_map = s->us_submit = s->us_collect = s->us_output = s->us_push = s->us_frames = 0;
 }
 

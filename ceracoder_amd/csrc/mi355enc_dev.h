@@ -186,5 +186,16 @@ int k_deblock_diags(int mbw, int mbh);
  * final -- the QP_Y of macroblocks that send no mb_qp_delta (7.4.5: that of the macroblock before them), which the deblocker reads (orc_qp_chain) */
 void k_launch_aq(const frame_ctx_t *h_ctx, int8_t *d_off, hipStream_t s);
 void k_launch_qp_chain(mb_info_t *d_mbi, int nmb, int slice_qp, int slice_mbs, hipStream_t s);
+/* Quality metrics of one picture (k_quality.hip; the rule: DESIGN.md section 12): NV12 source against NV12 reconstruction over the visible width x height.
+ * d_acc: QUALITY_ACC_WORDS 64-bit words on the device, zero before the first launch (every launch leaves them zero again): QUALITY_SHARDS sets of five
+ * accumulators, QUALITY_SHARD_STRIDE words (4 KB: another memory channel) apart, and the ticket; out: five words (a block of QUALITY_WORDS) -- SSE of Y, Cb, Cr,
+ * the sum of the windows' q, the number of windows -- written by the launch's last workgroup (device or pinned host memory, 8-byte aligned). */
+#define QUALITY_WORDS 8
+#define QUALITY_SHARDS 32
+#define QUALITY_SHARD_STRIDE 512
+#define QUALITY_TICKET_WORD 8
+#define QUALITY_ACC_WORDS (QUALITY_SHARDS * QUALITY_SHARD_STRIDE)
+void k_launch_quality(const uint8_t *src_y, const uint8_t *src_uv, int src_stride, const uint8_t *rec_y, const uint8_t *rec_uv, int rec_stride,
+                      int width, int height, unsigned long long *d_acc, unsigned long long *out, hipStream_t s);
 #endif
 #endif

@@ -29,7 +29,7 @@ IDEC = np.dtype([("modes4", "u1", (16,)), ("mode16", "u1"), ("cmode", "u1"), ("u
 IMV_DTYPE = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("sad", "<u2"), ("bits", "<u2")])
 SURF_ROWS, SURF_COLS = 35, 36
 DROP_MAX, DROP_SKIP = 12, 255
-STAGE_ME, STAGE_INTER, STAGE_INTRA, STAGE_DEBLOCK, STAGE_SUBPEL, STAGE_CSC_I420, STAGE_CSC_YUY2, STAGE_CSC_UYVY, STAGE_ME_SELECT, STAGE_PMB, STAGE_INTRA_P = range(11)
+STAGE_ME, STAGE_INTER, STAGE_INTRA, STAGE_DEBLOCK, STAGE_SUBPEL, STAGE_CSC_I420, STAGE_CSC_YUY2, STAGE_CSC_UYVY, STAGE_ME_SELECT, STAGE_PMB, STAGE_INTRA_P, STAGE_QUALITY = range(12)
 
 EXPORTS = [
     "mi355enc_abi_version", "mi355enc_strerror", "mi355enc_default_cfg", "mi355enc_open", "mi355enc_close",
@@ -41,6 +41,7 @@ EXPORTS = [
     "mi355enc_rc_pick", "mi355enc_rc_update", "mi355enc_host_cavlc_block", "mi355enc_debug_trip_wait", "mi355enc_host_alloc", "mi355enc_host_free",
     "mi355enc_set_input_size", "mi355enc_stage_scale", "mi355enc_scale_table",
     "mi355enc_set_colorimetry", "mi355enc_csc_coefficients", "mi355enc_host_write_headers_vui", "mi355enc_stage_csc_device",
+    "mi355enc_set_quality_metrics", "mi355enc_last_quality", "mi355enc_quality_totals", "mi355enc_stage_quality", "mi355enc_stage_quality_device",
 ]
 
 
@@ -58,6 +59,16 @@ class Stats(C.Structure):
                 ("n_inter", C.c_uint64), ("n_intra", C.c_uint64), ("n_deblock", C.c_uint64), ("ms_entropy", C.c_double),
                 ("ms_wait", C.c_double), ("n_total_gpu", C.c_uint64), ("ms_deblock_idr", C.c_double), ("n_deblock_idr", C.c_uint64), ("cavlc_threads", C.c_uint32), ("last_drop", C.c_uint32), ("ms_select", C.c_double), ("ms_analyse_p", C.c_double), ("ms_intra_p", C.c_double), ("skip_pictures", C.c_uint64), ("ms_open", C.c_double),
                 ("recoveries", C.c_uint32), ("last_error_word", C.c_uint32), ("safe_level", C.c_uint32), ("pinned_inputs", C.c_uint64)]
+
+
+class Quality(C.Structure):
+    """mi355enc_quality_t: sse / samples of Y, Cb, Cr, the fixed-point SSIM sum and its window count, and what the host derives from them"""
+    _fields_ = [("sse", C.c_uint64 * 3), ("samples", C.c_uint64 * 3), ("ssim_sum", C.c_int64), ("ssim_windows", C.c_uint64),
+                ("psnr", C.c_double * 3), ("ssim", C.c_double), ("pts", C.c_int64), ("pictures", C.c_uint64)]
+
+    def ints(self):
+        """the integers the device computed: (sse_y, sse_cb, sse_cr, ssim_sum, ssim_windows)"""
+        return (int(self.sse[0]), int(self.sse[1]), int(self.sse[2]), int(self.ssim_sum), int(self.ssim_windows))
 
 
 _lib = None
@@ -116,6 +127,11 @@ def load():
         L.mi355enc_csc_coefficients.argtypes = [C.c_int, C.c_int, vp]
         L.mi355enc_host_write_headers_vui.argtypes = [C.c_int] * 11 + [vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.mi355enc_stage_csc_device.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+        L.mi355enc_set_quality_metrics.argtypes = [vp, C.c_int]
+        L.mi355enc_last_quality.argtypes = [vp, C.POINTER(Quality)]
+        L.mi355enc_quality_totals.argtypes = [vp, C.POINTER(Quality)]
+        L.mi355enc_stage_quality.argtypes = [vp, vp, vp, vp, vp, C.POINTER(Quality)]
+        L.mi355enc_stage_quality_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.POINTER(Quality)]
         L.mi355enc_host_alloc.restype = vp
         L.mi355enc_host_alloc.argtypes = [C.c_size_t]
         L.mi355enc_host_free.restype = None
@@ -442,6 +458,36 @@ class Encoder:
             out.append((first, coef))
             o += sz
         return out
+
+    def set_quality_metrics(self, on=True):
+        """per-picture PSNR / SSIM computed on the device from now on (before the first submit); last_quality() after every collect()"""
+        self._chk(self.L.mi355enc_set_quality_metrics(self.h, int(bool(on))), "set_quality_metrics")
+
+    def last_quality(self):
+        """Quality of the last collected picture (EncoderError with metrics off or nothing collected)"""
+        q = Quality()
+        self._chk(self.L.mi355enc_last_quality(self.h, C.byref(q)), "last_quality")
+        return q
+
+    def quality_totals(self):
+        """Quality summed over the pictures collected since open / reset_stats(): global PSNR, mean SSIM"""
+        q = Quality()
+        self._chk(self.L.mi355enc_quality_totals(self.h, C.byref(q)), "quality_totals")
+        return q
+
+    def stage_quality(self, src_y, src_uv, rec_y, rec_uv):
+        """The metrics kernel alone on host planes of the coded size (16 mbh x 16 mbw luma, 8 mbh x 16 mbw interleaved chroma)."""
+        a = [np.ascontiguousarray(p, np.uint8) for p in (src_y, src_uv, rec_y, rec_uv)]
+        assert a[0].shape == a[2].shape == (self.mbh * 16, self.mbw * 16) and a[1].shape == a[3].shape == (self.mbh * 8, self.mbw * 16)
+        q = Quality()
+        self._chk(self.L.mi355enc_stage_quality(self.h, _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), C.byref(q)), "stage_quality")
+        return q
+
+    def stage_quality_device(self, src_y_ptr, src_uv_ptr, src_stride, rec_y_ptr, rec_uv_ptr):
+        """... on device-resident planes (addresses as ints): the source at any address and stride, the reconstruction at stride 16 mbw."""
+        q = Quality()
+        self._chk(self.L.mi355enc_stage_quality_device(self.h, src_y_ptr, src_uv_ptr, int(src_stride), rec_y_ptr, rec_uv_ptr, C.byref(q)), "stage_quality_device")
+        return q
 
     def submit_device(self, y_ptr, y_stride, uv_ptr, uv_stride, pts=0, force_idr=False):
         self._chk(self.L.mi355enc_submit_device(self.h, y_ptr, y_stride, uv_ptr, uv_stride, pts, int(force_idr)), "submit_device")

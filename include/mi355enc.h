@@ -269,6 +269,46 @@ int mi355enc_debug_trip_wait(mi355enc_t *h, unsigned code);
 
 int mi355enc_get_stats(mi355enc_t *h, mi355enc_stats_t *st);
 void mi355enc_reset_stats(mi355enc_t *h);
+
+/* ---- quality metrics of the coded pictures, computed on the device ----
+ * Source against deblocked reconstruction, both as the coding kernels see them: NV12 at the coded size, the source AFTER conversion, scaling
+ * and padding (with mi355enc_set_input_size or a format other than NV12 the comparison is against the converted / scaled surface, not the
+ * caller's picture).  Only the visible cfg.width x cfg.height samples count (chroma: width / 2 x height / 2 per component), never the margin
+ * of the coded size.
+ *   sse[c]        sum of (src - rec)^2 over the visible samples of Y, Cb, Cr: exact integers.
+ *   SSIM of luma  x264's integer form: 4x4 blocks anchored at (0, 0), width / 4 x height / 4 of them (a remainder of two columns or rows is
+ *                 left out); a window is a 2x2 group of blocks at every block position; per window, with s1 = sum src, s2 = sum rec,
+ *                 ss = sum src^2 + sum rec^2, s12 = sum src rec over its 64 samples, C1 = 416, C2 = 235963:
+ *                 q = rint((2 s1 s2 + C1)(2 (64 s12 - s1 s2) + C2) / ((s1^2 + s2^2 + C1)(64 ss - s1^2 - s2^2 + C2)) * 2^30), the integers
+ *                 exact, the two products and the quotient one IEEE binary64 rounding each, round-half-even: bit-reproducible.
+ *                 ssim_sum = sum of q, ssim_windows = their number.
+ *   derived on the host: psnr[c] = 10 log10(255^2 samples[c] / sse[c]) (100.0 when sse[c] is 0), ssim = ssim_sum / (ssim_windows * 2^30). */
+typedef struct {
+    uint64_t sse[3];          /* Y, Cb, Cr over the visible samples */
+    uint64_t samples[3];
+    int64_t  ssim_sum;        /* sum of rint(ssim_window * 2^30)    */
+    uint64_t ssim_windows;
+    double   psnr[3], ssim;   /* derived on the host                */
+    int64_t  pts;
+    uint64_t pictures;        /* mi355enc_quality_totals only       */
+} mi355enc_quality_t;
+/* Off by default; valid only before the first submit (MI355ENC_ERR_STATE after it).  Off: nothing is allocated, launched or waited for.  On: one more
+ * launch per picture behind its deblocking launch, and collect() of a picture returns only when that picture's metrics have landed.  The access
+ * units are byte for byte the same either way.  A picture re-encoded by a recovery reports the metrics of the re-encode; all-skip pictures are
+ * measured against the reference they repeat. */
+int mi355enc_set_quality_metrics(mi355enc_t *h, int on);
+/* the metrics of the last collected picture; MI355ENC_ERR_STATE with metrics off or before the first collect */
+int mi355enc_last_quality(mi355enc_t *h, mi355enc_quality_t *q);
+/* integer sums over all pictures collected since open or mi355enc_reset_stats (`pictures` of them; pts: the last one's); psnr[] and ssim are
+ * derived from the summed integers (global PSNR, mean SSIM).  MI355ENC_ERR_STATE with metrics off. */
+int mi355enc_quality_totals(mi355enc_t *h, mi355enc_quality_t *q);
+/* The kernel alone (tests): host planes of the coded size, stride 16 * mb_width; the visible size is the handle's.  Works with metrics off.  Like
+ * every single-stage call it overwrites the encoder's surfaces: the next picture submitted is coded as an IDR picture. */
+int mi355enc_stage_quality(mi355enc_t *h, const uint8_t *src_y, const uint8_t *src_uv, const uint8_t *rec_y, const uint8_t *rec_uv, mi355enc_quality_t *q);
+/* ... on planes that already lie in this GPU's memory: any address; the source at any stride >= width (an address or stride that is not a multiple
+ * of four takes the kernel's byte-wise path), the reconstruction at stride 16 * mb_width.  Touches nothing of the encoder's. */
+int mi355enc_stage_quality_device(mi355enc_t *h, const void *d_src_y, const void *d_src_uv, int src_stride,
+                                  const void *d_rec_y, const void *d_rec_uv, mi355enc_quality_t *q);
 size_t mi355enc_max_au_bytes(const mi355enc_t *h);
 const char *mi355enc_strerror(int code);
 int mi355enc_abi_version(void);
@@ -323,7 +363,8 @@ int mi355enc_stage_intra_analyse(mi355enc_t *h, const uint8_t *src_y, const uint
 int mi355enc_stage_deblock(mi355enc_t *h, uint8_t *rec_y, uint8_t *rec_uv, const void *mbinfo);
 /* Time `iters` back-to-back launches of one stage on the handle's stream with HIP events;
  * stage: 0 ME, 1 inter, 2 intra (whole wavefront), 3 deblock (whole wavefront), 4 sub-sample refinement,
- * 5 / 6 / 7 input conversion from I420 / YUY2 / UYVY, 8 one vector-selection iteration, 9 fused P stage, 10 intra macroblocks of a P picture.
+ * 5 / 6 / 7 input conversion from I420 / YUY2 / UYVY, 8 one vector-selection iteration, 9 fused P stage, 10 intra macroblocks of a P picture,
+ * 11 the quality-metrics launch (slot 0's source surfaces against reconstruction buffer 1).
  * Uses whatever the handle's surfaces currently hold.  Returns average ms per launch. */
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms);
 
