@@ -135,6 +135,7 @@ int mi355enc_open(const mi355enc_cfg_t *cfg, mi355enc_t **out) {
     h->ir_on = 0; h->ir_pos = 0; h->ir_R = 0; h->ir_skip_owed = 0;
     h->in_w = cfg->width; h->in_h = cfg->height; h->sar_w = h->sar_h = 0; h->scaling = false; h->d_scale_tab = nullptr; h->scale_tab_bytes = 0; memset(&h->scale, 0, sizeof h->scale);
     h->col_full = 0; h->col_prim = h->col_trc = h->col_mat = 2; csc_resolve(h);
+    h->ov_len = 0; h->ov_last_have = 0; h->ov_last_len = 0; mi355enc_overlay_default_style(&h->ov_style);
     h->q_on = false; h->q_have = false; h->d_qacc = nullptr; h->h_qres = nullptr; for (int i = 0; i < NSLOT; i++) h->ev_q[i] = nullptr; memset(&h->q_last, 0, sizeof h->q_last); memset(&h->q_tot, 0, sizeof h->q_tot);
     for (int i = 0; i < NSET; i++) { h->g_intra[i] = h->g_deblock[i] = nullptr; h->d_ctx2[i] = nullptr; h->d_surf[i] = nullptr; h->d_idec2[i] = nullptr; h->d_mbi_set[i] = nullptr; h->d_levels_set[i] = nullptr; h->d_qp_off[i] = nullptr; }
     h->prev_slot = nullptr;

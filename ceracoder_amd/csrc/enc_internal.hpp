@@ -2,6 +2,7 @@
 // the handle, the per-picture slot, and the helpers used by more than one of
 //   enc_handle.cpp    open / close / setters / statistics / fetch
 //   enc_schedule.cpp  the picture pipeline: submit*, the stream schedule of one picture, collect
+//   enc_overlay.cpp   the text overlay: setters, latch, layout, launch
 //   enc_stages.cpp    single-stage entry points (parity tests, probes) and the host-only stages
 #ifndef MI355_ENC_INTERNAL_HPP
 #define MI355_ENC_INTERNAL_HPP
@@ -64,6 +65,8 @@ struct slot_t {
     uint8_t *au; size_t au_len; int au_state; // 0 not submitted to the worker, 1 queued / being coded, 2 coded (au_len 0: did not fit), 3 the hand-over carried an error word
     double au_ms;
     const uint8_t *src_y, *src_uv; int src_stride, force_idr; // what enqueue_picture() was given: a recovery re-enqueues the pictures in flight from here
+    // text overlay: what submit latched for this picture and drew into its source surfaces (ov_len 0: nothing); a recovery keeps it -- the surfaces carry the text
+    int ov_len; char ov_text[256]; mi355enc_overlay_style_t ov_style;
 };
 
 struct mi355enc {
@@ -157,6 +160,11 @@ struct mi355enc {
     hipEvent_t ev_q[NSLOT];
     mi355enc_quality_t q_last, q_tot; // the last collected picture's / the integer sums since open or reset_stats
     bool q_have;
+    // text overlay (mi355enc_set_overlay_text / _style): what the control thread set last (under ov_mu; submit latches it per picture),
+    // and the text of the last collected picture
+    std::mutex ov_mu;
+    int ov_len; char ov_text[256]; mi355enc_overlay_style_t ov_style;
+    int ov_last_have, ov_last_len; char ov_last[256];
     // the entropy-coding worker (started by open() when pipeline_depth >= 1)
     std::thread wk;
     std::mutex wk_mu;
@@ -210,6 +218,9 @@ int quality_enqueue(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_
 int quality_collect(mi355enc_t *h, slot_t *s); // waits for the slot's metrics, books them as the last picture's and into the totals
 // one launch on the handle's main stream with the block of the stage entry points, waited for
 int quality_run(mi355enc_t *h, const uint8_t *src_y, const uint8_t *src_uv, int src_stride, const uint8_t *rec_y, const uint8_t *rec_uv, mi355enc_quality_t *q);
+// enc_overlay.cpp
+void overlay_latch(mi355enc_t *h, slot_t *s);                 // the text and style set last become the slot's (the first thing a submit does)
+int overlay_draw(mi355enc_t *h, slot_t *s, hipStream_t st);   // the slot's text into its source surfaces, behind everything enqueued on st so far; nothing with no text
 // enc_csc.cpp
 void csc_resolve(mi355enc_t *h); // fills csc_coef / csc_ok from col_mat, col_full and the coded size
 #endif

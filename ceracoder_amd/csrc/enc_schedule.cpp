@@ -1,7 +1,7 @@
 // enc_schedule.cpp -- the picture pipeline of the C-ABI shim.
 //
 // Per picture:
-//   front stream: [H2D source | conversion] -> P: me_kernel (SAD surfaces + first selection) -> me_select_kernel x ME_ITERS
+//   front stream: [H2D source | conversion | scale] -> [text overlay, if a text is set] -> P: me_kernel (SAD surfaces + first selection) -> me_select_kernel x ME_ITERS
 //                 -> intra analysis of the badly predicted macroblocks;  IDR: the source copy the next search runs against
 //   back stream:  IDR: intra analysis (flat) -> intra wavefront (persistent bands) | P: pmb_kernel -> intra_p_kernel
 //                 -> deblocking (persistent band kernel)
@@ -535,6 +535,7 @@ int mi355enc_submit(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t
     if (h->pending > h->cfg.pipeline_depth) return MI355ENC_ERR_STATE;
     HIPCHK(hipSetDevice(h->cfg.device_id));
     slot_t *s = &h->slot[h->head];
+    overlay_latch(h, s);
     const int w = h->in_w, ht = h->in_h;
     hipStream_t up = upload_stream(h);
     // where the planes go: the staging surfaces at the coded stride, or -- to be scaled -- the raw staging buffer at the input's
@@ -582,6 +583,7 @@ int mi355enc_submit(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t
     }
     if (h->scaling) { if (k_launch_scale(MI355ENC_FMT_NV12, dev_y, dev_uv, nullptr, ds, ds, 0, s->d_src_y, s->d_src_uv, h->W, h->H, &h->scale, up)) return MI355ENC_ERR_ARG; }
     else if (w != h->W) k_launch_pad(s->d_src_y, s->d_src_uv, h->W, w, ht, h->W, h->H, up);
+    { int r = overlay_draw(h, s, up); if (r) return r; }
     { int r = upload_done(h, s); if (r) return r; }
     return enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
 }
@@ -592,8 +594,10 @@ int mi355enc_submit_fmt(mi355enc_t *h, int fmt, const uint8_t *const planes[3], 
     if (h->pending > h->cfg.pipeline_depth) return MI355ENC_ERR_STATE;
     HIPCHK(hipSetDevice(h->cfg.device_id));
     slot_t *s = &h->slot[h->head];
+    overlay_latch(h, s);
     int r = upload_and_convert(h, s, fmt, planes, strides, upload_stream(h));
     if (r) return r;
+    r = overlay_draw(h, s, upload_stream(h)); if (r) return r;
     r = upload_done(h, s); if (r) return r;
     return enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
 }
@@ -603,20 +607,24 @@ int mi355enc_submit_device(mi355enc_t *h, const void *d_y, int y_stride, const v
     if (h->pending > h->cfg.pipeline_depth) return MI355ENC_ERR_STATE;
     HIPCHK(hipSetDevice(h->cfg.device_id));
     slot_t *s = &h->slot[h->head];
+    overlay_latch(h, s);
     if (h->scaling) { // scaled from where the planes lie into the slot's staging surfaces
         if (k_launch_scale(MI355ENC_FMT_NV12, (const uint8_t *)d_y, (const uint8_t *)d_uv, nullptr, y_stride, uv_stride, 0, s->d_src_y, s->d_src_uv, h->W, h->H, &h->scale,
                            upload_stream(h))) return MI355ENC_ERR_ARG;
         HIPCHK(hipGetLastError());
+        { int r = overlay_draw(h, s, upload_stream(h)); if (r) return r; }
         { int r = upload_done(h, s); if (r) return r; }
         return enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
     }
     const int w = h->cfg.width, ht = h->cfg.height;
     hipStream_t up = upload_stream(h);
-    const bool direct = w == h->W && y_stride == uv_stride && (y_stride & 15) == 0 && (((uintptr_t)d_y | (uintptr_t)d_uv) & 15) == 0;
+    // in place -- unless a text is to be drawn: that goes into the encoder's own surfaces, never into the caller's planes
+    const bool direct = !s->ov_len && w == h->W && y_stride == uv_stride && (y_stride & 15) == 0 && (((uintptr_t)d_y | (uintptr_t)d_uv) & 15) == 0;
     if (direct) return enqueue_picture(h, s, (const uint8_t *)d_y, (const uint8_t *)d_uv, y_stride, pts, force_idr);
     HIPCHK(hipMemcpy2DAsync(s->d_src_y, h->W, d_y, y_stride, w, ht, hipMemcpyDeviceToDevice, up));
     HIPCHK(hipMemcpy2DAsync(s->d_src_uv, h->W, d_uv, uv_stride, w, ht / 2, hipMemcpyDeviceToDevice, up));
     if (w != h->W) k_launch_pad(s->d_src_y, s->d_src_uv, h->W, w, ht, h->W, h->H, up);
+    { int r = overlay_draw(h, s, up); if (r) return r; }
     { int r = upload_done(h, s); if (r) return r; }
     return enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
 }
@@ -705,6 +713,7 @@ int mi355enc_collect(mi355enc_t *h, uint8_t *out, size_t out_cap, size_t *out_le
     h->st.frames++; h->st.idr_frames += s->is_idr; h->st.bytes += n + m;
     h->st.last_qp = (uint32_t)s->qp; h->st.last_drop = (uint32_t)s->drop; h->n_skip_pictures += s->all_skip; h->st.last_bytes = (uint32_t)(n + m); h->st.target_bps = h->want_bps.load();
     h->last_slot = s; h->last_collected_rec = s->rec_index;
+    h->ov_last_have = 1; h->ov_last_len = s->ov_len; if (s->ov_len) memcpy(h->ov_last, s->ov_text, (size_t)s->ov_len);
     h->tail = (h->tail + 1) % NSLOT; h->pending--;
     return MI355ENC_OK;
 }

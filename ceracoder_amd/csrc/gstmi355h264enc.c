@@ -57,6 +57,10 @@ typedef struct {
     gboolean dct8x8_adaptive; /* with dct8x8: the transform size is chosen per P macroblock (cfg.transform8x8 = 2) */
     gboolean quality_stats;   /* per-picture PSNR / SSIM computed on the device (mi355enc_set_quality_metrics); with stats=true the stream's figures are printed at close */
     gboolean intra_refresh;   /* periodic intra refresh instead of periodic IDR pictures (mi355enc_set_intra_refresh); key-int-max is the refresh period */
+    /* text overlay drawn on the device (mi355enc_set_overlay_text / _style): written through the overlay-* properties or by the
+     * custom event of an `mi355textoverlay` element upstream; stored here (object lock) and forwarded to the open encoder, which latches it per picture */
+    gchar ov_text[MI355ENC_OVERLAY_MAX_TEXT + 1];
+    mi355enc_overlay_style_t ov_style;
     gint out_w, out_h;        /* coded size (mpph265enc's width / height): 0 = the input's; smaller: scaled down on the device (mi355enc_set_input_size) */
     /* streaming state */
     mi355enc_t *enc;
@@ -74,7 +78,8 @@ typedef struct { GstVideoEncoderClass parent_class; } GstMi355H264EncClass;
 G_DEFINE_TYPE(GstMi355H264Enc, gst_mi355h264enc, GST_TYPE_VIDEO_ENCODER)
 
 enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME_RANGE, PROP_QP, PROP_PIPELINE_DEPTH,
-       PROP_SPEED_PRESET, PROP_STATS, PROP_DCT8X8, PROP_THREADS, PROP_SCENECUT, PROP_VBV, PROP_INTRA_IN_P, PROP_EXCLUSIVE, PROP_PINNED_INPUT, PROP_AQ_MODE, PROP_SINGLE_STREAM, PROP_INTRA_SLICES, PROP_I8X8, PROP_SLICES, PROP_SLICE_DEBLOCK, PROP_DCT8X8_ADAPTIVE, PROP_INTRA_REFRESH, PROP_WIDTH, PROP_HEIGHT, PROP_QUALITY_STATS };
+       PROP_SPEED_PRESET, PROP_STATS, PROP_DCT8X8, PROP_THREADS, PROP_SCENECUT, PROP_VBV, PROP_INTRA_IN_P, PROP_EXCLUSIVE, PROP_PINNED_INPUT, PROP_AQ_MODE, PROP_SINGLE_STREAM, PROP_INTRA_SLICES, PROP_I8X8, PROP_SLICES, PROP_SLICE_DEBLOCK, PROP_DCT8X8_ADAPTIVE, PROP_INTRA_REFRESH, PROP_WIDTH, PROP_HEIGHT, PROP_QUALITY_STATS,
+       PROP_OV_TEXT, PROP_OV_HALIGN, PROP_OV_VALIGN, PROP_OV_XPAD, PROP_OV_YPAD, PROP_OV_SCALE, PROP_OV_SHADED };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
     GST_STATIC_CAPS("video/x-raw, format=(string){ NV12, I420, YUY2, UYVY, Y42B, Y444, YV12, NV21, BGRx, RGBx, xRGB, xBGR, BGRA, RGBA, ARGB, ABGR, BGR, RGB }, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]"));
@@ -129,10 +134,39 @@ static guint clamp_bps(guint64 v) { return v < 1000 ? 1000u : v > 1000000000u ? 
  * the element has its name, and g_object_set followed by gst_object_set_name does the same -- a unit applied at write time would be wrong. */
 static guint target_bps(GstMi355H264Enc *s) { return clamp_bps((guint64)s->rate_raw * (s->rate_is_bps ? bps_unit(s) : 1000u)); }
 
+/* textoverlay's alignment words; the values are those of mi355enc_overlay_style_t ("baseline" is taken as bottom).  Shared with gstmi355textoverlay.c */
+GType gst_mi355_overlay_halign_type(void) {
+    static GType t = 0;
+    static const GEnumValue v[] = {{0, "left", "left"}, {1, "center", "center"}, {2, "right", "right"}, {0, NULL, NULL}};
+    if (!t) t = g_enum_register_static("GstMi355OverlayHAlign", v);
+    return t;
+}
+GType gst_mi355_overlay_valign_type(void) {
+    static GType t = 0;
+    static const GEnumValue v[] = {{0, "top", "top"}, {1, "center", "center"}, {2, "bottom", "bottom"}, {3, "baseline", "baseline"}, {0, NULL, NULL}};
+    if (!t) t = g_enum_register_static("GstMi355OverlayVAlign", v);
+    return t;
+}
+/* stored text / style -> the encoder, if one is open (object lock held; the library only stores: no GPU call, any thread) */
+static void overlay_forward(GstMi355H264Enc *s) {
+    if (!s->enc) return;
+    /* (the property ranges and the event's checks keep the style inside what the library takes: a refusal would leave element and encoder apart, so it is said) */
+    if (mi355enc_set_overlay_style(s->enc, &s->ov_style) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the overlay style: it keeps its previous one");
+    if (mi355enc_set_overlay_text(s->enc, s->ov_text) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the overlay text");
+}
+static void overlay_store_text(GstMi355H264Enc *s, const gchar *t) { g_strlcpy(s->ov_text, t ? t : "", sizeof s->ov_text); }
+
 static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *ps) {
     GstMi355H264Enc *s = GST_MI355H264ENC(obj);
     GST_OBJECT_LOCK(s);
     switch (id) {
+    case PROP_OV_TEXT: overlay_store_text(s, g_value_get_string(val)); overlay_forward(s); break;
+    case PROP_OV_HALIGN: s->ov_style.halign = g_value_get_enum(val); overlay_forward(s); break;
+    case PROP_OV_VALIGN: s->ov_style.valign = g_value_get_enum(val) > 2 ? 2 : g_value_get_enum(val); overlay_forward(s); break;
+    case PROP_OV_XPAD: s->ov_style.xpad = g_value_get_int(val); overlay_forward(s); break;
+    case PROP_OV_YPAD: s->ov_style.ypad = g_value_get_int(val); overlay_forward(s); break;
+    case PROP_OV_SCALE: s->ov_style.scale = g_value_get_int(val); overlay_forward(s); break;
+    case PROP_OV_SHADED: s->ov_style.shaded_background = g_value_get_boolean(val) ? 1 : 0; overlay_forward(s); break;
     case PROP_BPS: s->rate_raw = g_value_get_uint(val); s->rate_is_bps = TRUE; if (s->enc) mi355enc_set_bitrate(s->enc, target_bps(s)); break;
     case PROP_BITRATE: s->rate_raw = g_value_get_uint(val); s->rate_is_bps = FALSE; if (s->enc) mi355enc_set_bitrate(s->enc, target_bps(s)); break;
     case PROP_KEY_INT_MAX: s->key_int_max = g_value_get_uint(val); break;
@@ -170,6 +204,13 @@ static void get_property(GObject *obj, guint id, GValue *val, GParamSpec *ps) {
     GST_OBJECT_LOCK(s);
     effective_tools(s, &t); /* a tool property reads as what the encoder will use: the explicit value, or the preset's */
     switch (id) {
+    case PROP_OV_TEXT: g_value_set_string(val, s->ov_text); break;
+    case PROP_OV_HALIGN: g_value_set_enum(val, s->ov_style.halign); break;
+    case PROP_OV_VALIGN: g_value_set_enum(val, s->ov_style.valign); break;
+    case PROP_OV_XPAD: g_value_set_int(val, s->ov_style.xpad); break;
+    case PROP_OV_YPAD: g_value_set_int(val, s->ov_style.ypad); break;
+    case PROP_OV_SCALE: g_value_set_int(val, s->ov_style.scale); break;
+    case PROP_OV_SHADED: g_value_set_boolean(val, s->ov_style.shaded_background != 0); break;
     case PROP_BPS: g_value_set_uint(val, s->rate_is_bps ? s->rate_raw : target_bps(s) / bps_unit(s)); break;
     case PROP_BITRATE: g_value_set_uint(val, target_bps(s) / 1000u); break;
     case PROP_KEY_INT_MAX: g_value_set_uint(val, s->key_int_max); break;
@@ -345,6 +386,7 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     s->enc = e;
     s->open_depth = cfg.pipeline_depth;
     mi355enc_set_bitrate(e, target_bps(s)); /* a write that raced with open() must not be lost */
+    overlay_forward(s);                     /* ... nor the overlay's text and style, set before the device was opened */
     GST_OBJECT_UNLOCK(s);
     s->max_au = mi355enc_max_au_bytes(e);
     g_free(s->au_buf);
@@ -531,6 +573,27 @@ static gboolean enc_propose_allocation(GstVideoEncoder *ve, GstQuery *q) {
     gst_query_add_allocation_meta(q, GST_VIDEO_META_API_TYPE, NULL);
     return GST_VIDEO_ENCODER_CLASS(gst_mi355h264enc_parent_class)->propose_allocation(ve, q);
 }
+/* The custom downstream event of `mi355textoverlay` (gstmi355textoverlay.c): serialized, so it arrives on the streaming thread in front of the picture it
+ * was sent before -- through `queue` and `videoconvert` as well.  Fields that are present replace the element's own; the event ends here. */
+static gboolean enc_sink_event(GstVideoEncoder *ve, GstEvent *ev) {
+    GstMi355H264Enc *s = GST_MI355H264ENC(ve);
+    if (GST_EVENT_TYPE(ev) == GST_EVENT_CUSTOM_DOWNSTREAM && gst_event_has_name(ev, "mi355-overlay")) {
+        const GstStructure *st = gst_event_get_structure(ev);
+        gint v; gboolean b;
+        GST_OBJECT_LOCK(s);
+        if (gst_structure_has_field(st, "text")) overlay_store_text(s, gst_structure_get_string(st, "text"));
+        if (gst_structure_get_int(st, "halign", &v) && v >= 0 && v <= 2) s->ov_style.halign = v;
+        if (gst_structure_get_int(st, "valign", &v) && v >= 0 && v <= 2) s->ov_style.valign = v;
+        if (gst_structure_get_int(st, "xpad", &v) && v >= 0 && v <= 8192) s->ov_style.xpad = v;
+        if (gst_structure_get_int(st, "ypad", &v) && v >= 0 && v <= 8192) s->ov_style.ypad = v;
+        if (gst_structure_get_boolean(st, "shaded-background", &b)) s->ov_style.shaded_background = b ? 1 : 0;
+        overlay_forward(s);
+        GST_OBJECT_UNLOCK(s);
+        gst_event_unref(ev);
+        return TRUE;
+    }
+    return GST_VIDEO_ENCODER_CLASS(gst_mi355h264enc_parent_class)->sink_event(ve, ev);
+}
 static void finalize(GObject *obj) {
     enc_stop(GST_VIDEO_ENCODER(obj));
     G_OBJECT_CLASS(gst_mi355h264enc_parent_class)->finalize(obj);
@@ -598,25 +661,37 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
     g_object_class_install_property(g, PROP_QUALITY_STATS, g_param_spec_boolean("quality-stats", "Quality metrics",
         "Measure every coded picture on the GPU (PSNR of Y, Cb, Cr and SSIM of the luma, source against reconstruction); with stats=true the stream's figures are printed when the encoder closes. Read when the encoder opens", FALSE,
         (GParamFlags)(G_PARAM_READWRITE | G_PARAM_STATIC_STRINGS | GST_PARAM_MUTABLE_READY)));
+    g_object_class_install_property(g, PROP_OV_TEXT, g_param_spec_string("overlay-text", "Overlay text",
+        "Text drawn into every picture on the GPU (built-in 8x16 bitmap font, printable ASCII, newline starts a line, at most 255 bytes, no markup); empty: off. "
+        "Settable while playing: the write only stores, the next picture carries it. An mi355textoverlay element upstream writes it through an event", "", F));
+    g_object_class_install_property(g, PROP_OV_HALIGN, g_param_spec_enum("overlay-halignment", "Overlay horizontal alignment", "Where the text box sits, and how its lines are aligned inside it", gst_mi355_overlay_halign_type(), 2, F));
+    g_object_class_install_property(g, PROP_OV_VALIGN, g_param_spec_enum("overlay-valignment", "Overlay vertical alignment", "Where the text box sits (baseline: bottom)", gst_mi355_overlay_valign_type(), 0, F));
+    g_object_class_install_property(g, PROP_OV_XPAD, g_param_spec_int("overlay-xpad", "Overlay horizontal padding", "Luma samples between the text box and the left / right picture edge", 0, 8192, 16, F));
+    g_object_class_install_property(g, PROP_OV_YPAD, g_param_spec_int("overlay-ypad", "Overlay vertical padding", "Luma samples between the text box and the top / bottom picture edge", 0, 8192, 16, F));
+    g_object_class_install_property(g, PROP_OV_SCALE, g_param_spec_int("overlay-scale", "Overlay scale", "Luma samples per font pixel, 1..8; 0: height / 540, at least 1 (720p 1, 1080p 2, 2160p 4)", 0, 8, 0, F));
+    g_object_class_install_property(g, PROP_OV_SHADED, g_param_spec_boolean("overlay-shaded-background", "Overlay shaded background", "Darken the text box", FALSE, F));
     g_object_class_install_property(g, PROP_STATS, g_param_spec_boolean("stats", "Print stats", "Print a JSON line with counters when the encoder closes", FALSE, F));
     gst_element_class_add_static_pad_template(e, &sink_tmpl);
     gst_element_class_add_static_pad_template(e, &src_tmpl);
     gst_element_class_set_static_metadata(e, "MI355X H.264 encoder", "Codec/Encoder/Video/Hardware",
         "H.264 (Constrained Baseline) encoder on AMD Instinct MI355X via hand-written HIP kernels", "ceracoder-amd");
     v->start = enc_start; v->stop = enc_stop; v->set_format = enc_set_format; v->handle_frame = enc_handle_frame; v->getcaps = enc_getcaps;
-    v->finish = enc_finish; v->flush = enc_flush; v->propose_allocation = enc_propose_allocation;
+    v->finish = enc_finish; v->flush = enc_flush; v->propose_allocation = enc_propose_allocation; v->sink_event = enc_sink_event;
 }
 static void gst_mi355h264enc_init(GstMi355H264Enc *s) {
     s->rate_raw = 2048; s->rate_is_bps = FALSE; s->key_int_max = 60; s->device_id = 0; s->me_range = 16; s->qp = -1; s->pipeline_depth = 0; s->speed_preset = 0;
     s->stats = FALSE; s->dct8x8 = -1; s->threads = 0; s->scenecut = TRUE; s->exclusive_gpu = FALSE; s->vbv_ms = 600; s->intra_in_p = -1; s->pinned_input = TRUE; s->aq_mode = -1; s->slices = -1; s->slice_deblock = -1; s->intra_slices = 0; s->i8x8 = -1; s->single_stream = FALSE; s->dct8x8_adaptive = FALSE; s->intra_refresh = FALSE; s->quality_stats = FALSE; s->enc = NULL; s->input_state = NULL; s->max_au = 0; s->au_buf = NULL; s->last_pts = GST_CLOCK_TIME_NONE;
     s->us_map = s->us_submit = s->us_collect = s->us_output = s->us_push = s->us_frames = 0;
+    s->ov_text[0] = 0; mi355enc_overlay_default_style(&s->ov_style);
 }
 
 GType gst_mi355tsmux_get_type(void); /* gstmi355tsmux.c */
+GType gst_mi355textoverlay_get_type(void); /* gstmi355textoverlay.c */
 static gboolean plugin_init(GstPlugin *p) {
     GST_DEBUG_CATEGORY_INIT(mi355_debug, "mi355h264enc", 0, "MI355X H.264 encoder");
     return gst_element_register(p, "mi355h264enc", GST_RANK_NONE, GST_TYPE_MI355H264ENC) &&
-           gst_element_register(p, "mi355tsmux", GST_RANK_NONE, gst_mi355tsmux_get_type());
+           gst_element_register(p, "mi355tsmux", GST_RANK_NONE, gst_mi355tsmux_get_type()) &&
+           gst_element_register(p, "mi355textoverlay", GST_RANK_NONE, gst_mi355textoverlay_get_type());
 }
 GST_PLUGIN_DEFINE(GST_VERSION_MAJOR, GST_VERSION_MINOR, mi355h264enc, "MI355X-native H.264 encoder for ceracoder", plugin_init, VERSION,
                   "LGPL", PACKAGE, "https://github.com/CERALIVE/ceracoder")

@@ -195,6 +195,20 @@ void k_launch_qp_chain(mb_info_t *d_mbi, int nmb, int slice_qp, int slice_mbs, h
 #define QUALITY_SHARD_STRIDE 512
 #define QUALITY_TICKET_WORD 8
 #define QUALITY_ACC_WORDS (QUALITY_SHARDS * QUALITY_SHARD_STRIDE)
+/* Text overlay (k_overlay.hip; the rule: DESIGN.md section 13).  Everything the launch needs, by value: the surface, the visible size, the box
+ * (bx, by: origin, even, >= 0; bw x bh: its unclipped size), the quads the grid covers ([gx0, gx1) x [gy0, gy1), even: the visible part of the
+ * box; where it reaches the last visible column / row, the owners of the last quads write the margin up to the coded size W x H as well), the resolved style and the text:
+ * nlines lines, line i = text[(i ? line_end[i - 1] + 1 : 0) .. line_end[i]), the longest of maxlen bytes. */
+typedef struct {
+    uint8_t *y, *uv;
+    int32_t stride, vw, vh, W, H;
+    int32_t bx, by, bw, bh;
+    int32_t gx0, gy0, gx1, gy1;
+    int32_t scale, halign, shaded, nlines, maxlen;
+    uint8_t text[256];
+    uint8_t line_end[256];
+} overlay_args_t;
+void k_launch_overlay(const overlay_args_t *a, hipStream_t s);
 void k_launch_quality(const uint8_t *src_y, const uint8_t *src_uv, int src_stride, const uint8_t *rec_y, const uint8_t *rec_uv, int rec_stride,
                       int width, int height, unsigned long long *d_acc, unsigned long long *out, hipStream_t s);
 #endif

@@ -42,6 +42,7 @@ EXPORTS = [
     "mi355enc_set_input_size", "mi355enc_stage_scale", "mi355enc_scale_table",
     "mi355enc_set_colorimetry", "mi355enc_csc_coefficients", "mi355enc_host_write_headers_vui", "mi355enc_stage_csc_device",
     "mi355enc_set_quality_metrics", "mi355enc_last_quality", "mi355enc_quality_totals", "mi355enc_stage_quality", "mi355enc_stage_quality_device",
+    "mi355enc_overlay_default_style", "mi355enc_set_overlay_style", "mi355enc_set_overlay_text", "mi355enc_last_overlay", "mi355enc_overlay_glyph", "mi355enc_stage_overlay",
 ]
 
 
@@ -71,6 +72,12 @@ class Quality(C.Structure):
         return (int(self.sse[0]), int(self.sse[1]), int(self.sse[2]), int(self.ssim_sum), int(self.ssim_windows))
 
 
+class OverlayStyle(C.Structure):
+    """mi355enc_overlay_style_t: halign / valign 0 left / top, 1 centre, 2 right / bottom; pads in luma samples; scale 0 = auto, 1 .. 8"""
+    _fields_ = [("halign", C.c_int), ("valign", C.c_int), ("xpad", C.c_int), ("ypad", C.c_int), ("scale", C.c_int), ("shaded_background", C.c_int)]
+
+
+OVERLAY_MAX_TEXT = 255
 _lib = None
 
 
@@ -132,6 +139,13 @@ def load():
         L.mi355enc_quality_totals.argtypes = [vp, C.POINTER(Quality)]
         L.mi355enc_stage_quality.argtypes = [vp, vp, vp, vp, vp, C.POINTER(Quality)]
         L.mi355enc_stage_quality_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.POINTER(Quality)]
+        L.mi355enc_overlay_default_style.restype = None
+        L.mi355enc_overlay_default_style.argtypes = [C.POINTER(OverlayStyle)]
+        L.mi355enc_set_overlay_style.argtypes = [vp, C.POINTER(OverlayStyle)]
+        L.mi355enc_set_overlay_text.argtypes = [vp, C.c_char_p]
+        L.mi355enc_last_overlay.argtypes = [vp, vp, C.c_size_t]
+        L.mi355enc_overlay_glyph.argtypes = [C.c_int, vp]
+        L.mi355enc_stage_overlay.argtypes = [vp, C.c_char_p, C.POINTER(OverlayStyle), vp, vp]
         L.mi355enc_host_alloc.restype = vp
         L.mi355enc_host_alloc.argtypes = [C.c_size_t]
         L.mi355enc_host_free.restype = None
@@ -243,6 +257,30 @@ def scale_table(n_in, n_out, kind):
     if r != n:
         raise EncoderError("mi355enc_scale_table: %d" % r)
     return first, coef
+
+
+def overlay_style(**kw):
+    """The library's default style (right, top, pads 16, auto scale, no shading) with the given fields replaced."""
+    st = OverlayStyle()
+    load().mi355enc_overlay_default_style(C.byref(st))
+    for k, v in kw.items():
+        if k not in dict(OverlayStyle._fields_):
+            raise TypeError("no such overlay style field: %s" % k)
+        setattr(st, k, int(v))
+    return st
+
+
+def overlay_glyph(ch):
+    """The built-in font (host only): the 16 rows of the 8 x 16 cell of character code `ch`, MSB = left pixel."""
+    rows = np.zeros(16, np.uint8)
+    r = load().mi355enc_overlay_glyph(int(ch), rows.ctypes.data_as(C.c_void_p))
+    if r:
+        raise EncoderError("mi355enc_overlay_glyph(%d): %d" % (ch, r))
+    return rows
+
+
+def _text_bytes(text):
+    return text.encode("latin-1") if isinstance(text, str) else (bytes(text) if text is not None else None)
 
 
 RC_BYTES = 512  # include/mi355enc.h MI355ENC_RC_BYTES
@@ -488,6 +526,31 @@ class Encoder:
         q = Quality()
         self._chk(self.L.mi355enc_stage_quality_device(self.h, src_y_ptr, src_uv_ptr, int(src_stride), rec_y_ptr, rec_uv_ptr, C.byref(q)), "stage_quality_device")
         return q
+
+    def set_overlay_text(self, text):
+        """The text drawn into every picture submitted from now on (str or bytes; None or "": off).  Thread-safe, no GPU call."""
+        self._chk(self.L.mi355enc_set_overlay_text(self.h, _text_bytes(text)), "set_overlay_text")
+
+    def set_overlay_style(self, style=None, **kw):
+        """An OverlayStyle, or the default style with fields replaced (halign=, valign=, xpad=, ypad=, scale=, shaded_background=)"""
+        st = style if style is not None else overlay_style(**kw)
+        self._chk(self.L.mi355enc_set_overlay_style(self.h, C.byref(st)), "set_overlay_style")
+
+    def last_overlay(self):
+        """The text drawn into the last collected picture, as bytes (b"": none)"""
+        buf = C.create_string_buffer(OVERLAY_MAX_TEXT + 1)
+        n = self.L.mi355enc_last_overlay(self.h, buf, len(buf))
+        if n < 0:
+            self._chk(n, "last_overlay")
+        return buf.raw[:n]
+
+    def stage_overlay(self, text, y, uv, style=None, **kw):
+        """The overlay kernel alone on host planes of the coded size; returns the drawn copies."""
+        st = style if style is not None else overlay_style(**kw)
+        y, uv = np.ascontiguousarray(y, np.uint8).copy(), np.ascontiguousarray(uv, np.uint8).copy()
+        assert y.shape == (self.mbh * 16, self.mbw * 16) and uv.shape == (self.mbh * 8, self.mbw * 16)
+        self._chk(self.L.mi355enc_stage_overlay(self.h, _text_bytes(text), C.byref(st), _p(y), _p(uv)), "stage_overlay")
+        return y, uv
 
     def submit_device(self, y_ptr, y_stride, uv_ptr, uv_stride, pts=0, force_idr=False):
         self._chk(self.L.mi355enc_submit_device(self.h, y_ptr, y_stride, uv_ptr, uv_stride, pts, int(force_idr)), "submit_device")

@@ -309,6 +309,28 @@ int mi355enc_stage_quality(mi355enc_t *h, const uint8_t *src_y, const uint8_t *s
  * of four takes the kernel's byte-wise path), the reconstruction at stride 16 * mb_width.  Touches nothing of the encoder's. */
 int mi355enc_stage_quality_device(mi355enc_t *h, const void *d_src_y, const void *d_src_uv, int src_stride,
                                   const void *d_rec_y, const void *d_rec_uv, mi355enc_quality_t *q);
+
+/* ---- text overlay ---------------------------------------------
+ * A few lines of text (the reference's on-screen statistics line) drawn into every submitted picture on the GPU, in place of a `textoverlay`
+ * element in front of the encoder: a built-in 8 x 16 monospace bitmap font (printable ASCII; any other byte but '\n' draws as '?'; '\n'
+ * starts a new line; at most 255 bytes are used; no markup), white text with a black outline, optionally on a shaded box.  The text is drawn
+ * into the NV12 picture of the coded visible size -- after conversion and scaling, before the padding to whole macroblocks -- so the stream is
+ * byte for byte that of the same pictures with the text already in them.  Off (no text, or ""): nothing is allocated or launched. */
+typedef struct { int halign, valign;      /* 0 left/top, 1 centre, 2 right/bottom */
+                 int xpad, ypad;          /* luma samples, >= 0                    */
+                 int scale;               /* 0 auto, 1..8                          */
+                 int shaded_background; } mi355enc_overlay_style_t;
+#define MI355ENC_OVERLAY_MAX_TEXT 255
+void mi355enc_overlay_default_style(mi355enc_overlay_style_t *st);     /* right, top, 16, 16, auto, 0 */
+int  mi355enc_set_overlay_style(mi355enc_t *h, const mi355enc_overlay_style_t *st); /* ERR_ARG out of range; any time, latched per picture */
+int  mi355enc_set_overlay_text(mi355enc_t *h, const char *text);       /* NULL or "" : off; thread-safe; no GPU call */
+int  mi355enc_last_overlay(mi355enc_t *h, char *buf, size_t cap);      /* text drawn into the last collected picture; returns its length, ERR_STATE before the first collect */
+int  mi355enc_overlay_glyph(int ch, uint8_t rows[16]);                 /* host only: the font, MSB = left pixel; ERR_ARG outside 0x20..0x7E */
+int  mi355enc_stage_overlay(mi355enc_t *h, const char *text, const mi355enc_overlay_style_t *st,
+                            uint8_t *y, uint8_t *uv);                  /* kernel alone (tests): coded-size host planes, stride 16*mbw, in place */
+/* (mi355enc_last_overlay: the text is cut to cap - 1 bytes and always terminated; the length returned is that of the whole text.
+ * mi355enc_set_overlay_text and mi355enc_set_overlay_style may be called from any thread while another one submits: a picture carries exactly
+ * one of the texts that were set.  With a text set, mi355enc_submit_device copies the caller's planes: they are never written.) */
 size_t mi355enc_max_au_bytes(const mi355enc_t *h);
 const char *mi355enc_strerror(int code);
 int mi355enc_abi_version(void);
