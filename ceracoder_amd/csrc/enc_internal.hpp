@@ -3,6 +3,7 @@
 //   enc_handle.cpp    open / close / setters / statistics / fetch
 //   enc_schedule.cpp  the picture pipeline: submit*, the stream schedule of one picture, collect
 //   enc_overlay.cpp   the text overlay: setters, latch, layout, launch
+//   enc_jpeg.cpp      MJPEG input: coefficient buffers, host decode, transfer + launch, its stage entry points
 //   enc_stages.cpp    single-stage entry points (parity tests, probes) and the host-only stages
 #ifndef MI355_ENC_INTERNAL_HPP
 #define MI355_ENC_INTERNAL_HPP
@@ -50,6 +51,8 @@ struct slot_t {
     uint8_t *d_src_y, *d_src_uv; // staging for host / unaligned input
     uint8_t *d_raw;              // staging of non-NV12 input before the conversion kernel, and of every input before the scale kernel (allocated on first use, raw_bytes())
     uint8_t *d_csc;              // the formats of k_csc.hip with an input size of their own: the NV12 picture of the input size between conversion and scale (allocated on first use)
+    uint8_t *h_jpeg, *d_jpeg;    // MJPEG input (allocated on first use): the quantisation tables and the coefficient blocks of the picture, pinned / on the device
+    uint8_t *d_jpeg_planar;      // ... and the planar picture of a 4:4:4 one between the JPEG launch and the conversion
     hipEvent_t done, gpu_done, ev[12];
     hipEvent_t ev_up;          // the source has arrived (upload stream; only when that is a stream of its own)
     hipEvent_t ev_front;       // the front stream's part of the picture is done (source in place, search + selection + analysis)
@@ -221,6 +224,12 @@ int quality_run(mi355enc_t *h, const uint8_t *src_y, const uint8_t *src_uv, int 
 // enc_overlay.cpp
 void overlay_latch(mi355enc_t *h, slot_t *s);                 // the text and style set last become the slot's (the first thing a submit does)
 int overlay_draw(mi355enc_t *h, slot_t *s, hipStream_t st);   // the slot's text into its source surfaces, behind everything enqueued on st so far; nothing with no text
+// enc_jpeg.cpp
+int jpeg_alloc(mi355enc_t *h, slot_t *s);  // the slot's coefficient buffers (idempotent)
+void jpeg_free(slot_t *s);
+int jpeg_decode_host(mi355enc_t *h, slot_t *s, const uint8_t *data, size_t len, mi355enc_jpeg_info_t *info); // parse, check the size, entropy decode into the slot's pinned buffer
+int jpeg_enqueue(mi355enc_t *h, slot_t *s, const mi355enc_jpeg_info_t *info, hipStream_t up);               // transfer + launch (+ scale) into the slot's staging surfaces
+int jpeg_time_launch(mi355enc_t *h, slot_t *s);
 // enc_csc.cpp
 void csc_resolve(mi355enc_t *h); // fills csc_coef / csc_ok from col_mat, col_full and the coded size
 #endif

@@ -164,6 +164,7 @@ int mi355enc_set_input_size(mi355enc_t *h, int in_w, int in_h) {
         slot_t *s = &h->slot[i];
         if (s->d_raw) { (void)hipFree(s->d_raw); s->d_raw = nullptr; }
         if (s->d_csc) { (void)hipFree(s->d_csc); s->d_csc = nullptr; }
+        jpeg_free(s);
         if (s->h_src) { (void)hipHostFree(s->h_src); s->h_src = nullptr; }
     }
     return MI355ENC_OK;

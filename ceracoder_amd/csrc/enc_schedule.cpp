@@ -1,7 +1,7 @@
 // enc_schedule.cpp -- the picture pipeline of the C-ABI shim.
 //
 // Per picture:
-//   front stream: [H2D source | conversion | scale] -> [text overlay, if a text is set] -> P: me_kernel (SAD surfaces + first selection) -> me_select_kernel x ME_ITERS
+//   front stream: [H2D source | conversion | JPEG coefficients + inverse DCT | scale] -> [text overlay, if a text is set] -> P: me_kernel (SAD surfaces + first selection) -> me_select_kernel x ME_ITERS
 //                 -> intra analysis of the badly predicted macroblocks;  IDR: the source copy the next search runs against
 //   back stream:  IDR: intra analysis (flat) -> intra wavefront (persistent bands) | P: pmb_kernel -> intra_p_kernel
 //                 -> deblocking (persistent band kernel)
@@ -597,6 +597,23 @@ int mi355enc_submit_fmt(mi355enc_t *h, int fmt, const uint8_t *const planes[3], 
     overlay_latch(h, s);
     int r = upload_and_convert(h, s, fmt, planes, strides, upload_stream(h));
     if (r) return r;
+    r = overlay_draw(h, s, upload_stream(h)); if (r) return r;
+    r = upload_done(h, s); if (r) return r;
+    return enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
+}
+
+// MJPEG input: the host decodes the entropy-coded data into the slot's pinned coefficient buffer first -- a picture that is refused or does not decode has
+// touched nothing else -- then the transfer and the JPEG launch take the place of the conversion launch.
+int mi355enc_submit_jpeg(mi355enc_t *h, const uint8_t *data, size_t len, int64_t pts, int force_idr) {
+    if (!h || !data) return MI355ENC_ERR_ARG;
+    if (h->pending > h->cfg.pipeline_depth) return MI355ENC_ERR_STATE;
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    slot_t *s = &h->slot[h->head];
+    mi355enc_jpeg_info_t info;
+    int r = jpeg_decode_host(h, s, data, len, &info);
+    if (r) return r;
+    overlay_latch(h, s);
+    r = jpeg_enqueue(h, s, &info, upload_stream(h)); if (r) return r;
     r = overlay_draw(h, s, upload_stream(h)); if (r) return r;
     r = upload_done(h, s); if (r) return r;
     return enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);

@@ -219,7 +219,7 @@ int mi355enc_debug_trip_wait(mi355enc_t *h, unsigned code) {
     return MI355ENC_OK;
 }
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
-    if (!h || !avg_ms || iters < 1 || stage < 0 || stage > 11) return MI355ENC_ERR_ARG;
+    if (!h || !avg_ms || iters < 1 || stage < 0 || stage > 12) return MI355ENC_ERR_ARG;
     if (h->pending) return MI355ENC_ERR_STATE;
     HIPCHK(hipSetDevice(h->cfg.device_id));
     slot_t *s = &h->slot[0];
@@ -239,6 +239,7 @@ int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
         HIPCHK(hipMalloc((void **)&s->d_raw, raw_bytes(h)));
         HIPCHK(hipMemsetAsync(s->d_raw, 0x55, raw_bytes(h), h->stream));
     }
+    if (stage == 12) { int r = jpeg_alloc(h, s); if (r) return r; }
     for (int warm = 0; warm < 2; warm++) {
         if (warm) HIPCHK(hipEventRecord(s->ev[0], h->stream));
         for (int i = 0; i < (warm ? iters : 1); i++) {
@@ -250,6 +251,7 @@ int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
             else if (stage == 9) k_launch_pmb(h->slot[0].h_ctx, h->mbw, 0, h->mbh, 1, nullptr, 0, err_word(h), nullptr, h->stream);
             else if (stage == 11) k_launch_quality(s->d_src_y, s->d_src_uv, h->W, h->d_rec_y[1], h->d_rec_uv[1], h->W, h->cfg.width, h->cfg.height, h->d_qacc + (size_t)NSLOT * QUALITY_ACC_WORDS,
                                                    h->h_qres + (size_t)NSLOT * QUALITY_WORDS, h->stream);
+            else if (stage == 12) { int r = jpeg_time_launch(h, s); if (r) return r; }
             else if (stage == 10) k_launch_intra_p(h->slot[0].h_ctx, h->mbw, h->mbh, h->d_ip_progress, h->d_ip_strips, err_word(h), h->stream);
             else if (stage >= 5) {
                 const int w = h->cfg.width, ht = h->cfg.height, r0 = stage == 5 ? (w + 15) & ~15 : (2 * w + 15) & ~15, r1 = (w / 2 + 15) & ~15;

@@ -50,6 +50,8 @@ typedef struct {
     gboolean scenecut, exclusive_gpu;
     guint vbv_ms;
     gboolean pinned_input;
+    gboolean jpeg;    /* the sink caps are image/jpeg: buffers are JPEG pictures, decoded on the way in (mi355enc_submit_jpeg) */
+    gint jpeg_refused; /* ... and how many of them in a row the encoder has refused */
     /* coding tools: -1 = not set on the element, i.e. what speed-preset selects (preset_tools); an explicit write wins */
     gint dct8x8, i8x8, aq_mode, intra_in_p, slices, slice_deblock;
     gint intra_slices;
@@ -82,7 +84,8 @@ enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME
        PROP_OV_TEXT, PROP_OV_HALIGN, PROP_OV_VALIGN, PROP_OV_XPAD, PROP_OV_YPAD, PROP_OV_SCALE, PROP_OV_SHADED };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
-    GST_STATIC_CAPS("video/x-raw, format=(string){ NV12, I420, YUY2, UYVY, Y42B, Y444, YV12, NV21, BGRx, RGBx, xRGB, xBGR, BGRA, RGBA, ARGB, ABGR, BGR, RGB }, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]"));
+    GST_STATIC_CAPS("video/x-raw, format=(string){ NV12, I420, YUY2, UYVY, Y42B, Y444, YV12, NV21, BGRx, RGBx, xRGB, xBGR, BGRA, RGBA, ARGB, ABGR, BGR, RGB }, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]; "
+                    "image/jpeg, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]"));
 static GstStaticPadTemplate src_tmpl = GST_STATIC_PAD_TEMPLATE("src", GST_PAD_SRC, GST_PAD_ALWAYS,
     GST_STATIC_CAPS("video/x-h264, stream-format=(string)byte-stream, alignment=(string)au, profile=(string){ constrained-baseline, high }, "
                     "width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]"));
@@ -343,6 +346,13 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     if (s->enc) drain(s, TRUE); /* renegotiation in mid-stream: the picture still on the device belongs to the old format (x264enc flushes here too) */
     close_encoder(s);
     const int in_w = GST_VIDEO_INFO_WIDTH(vi), in_h = GST_VIDEO_INFO_HEIGHT(vi);
+    /* MJPEG input: size and framerate come from the caps, the pictures are decoded on the way in */
+    const GstStructure *cs = state->caps ? gst_caps_get_structure(state->caps, 0) : NULL;
+    const gboolean jpeg = cs && gst_structure_has_name(cs, "image/jpeg");
+    if (jpeg && (in_w < 16 || in_h < 16)) {
+        GST_ELEMENT_ERROR(s, CORE, NEGOTIATION, ("mi355h264enc: image/jpeg caps need width and height"), ("caps without a size"));
+        return FALSE;
+    }
     GST_OBJECT_LOCK(s);
     const int out_w = s->out_w > 0 ? s->out_w : in_w, out_h = s->out_h > 0 ? s->out_h : in_h; /* (0: the input's size) */
     GST_OBJECT_UNLOCK(s);
@@ -367,6 +377,7 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     if (r == MI355ENC_OK) { /* what the samples mean goes into the SPS (x264enc copies its input caps' colorimetry likewise); YUV input is only labelled */
         int full, prim, trc, mat;
         colorimetry_codes(&vi->colorimetry, &full, &prim, &trc, &mat);
+        if (jpeg && !gst_structure_has_field(cs, "colorimetry")) { full = 1; mat = 6; prim = trc = 2; } /* JFIF: what the caps of a `jpegdec` in front would have said */
         if (GST_VIDEO_INFO_IS_RGB(vi) && mat != 1 && mat != 6 && mat != 9) {
             /* RGB is converted here: with what `videoconvert` would have negotiated for the encoder's input -- BT.709 for HD, BT.601 below, limited range */
             prim = trc = mat = (out_w > 1024 || out_h > 576) ? 1 : 6;
@@ -385,6 +396,7 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     GST_OBJECT_LOCK(s);
     s->enc = e;
     s->open_depth = cfg.pipeline_depth;
+    s->jpeg = jpeg; s->jpeg_refused = 0;
     mi355enc_set_bitrate(e, target_bps(s)); /* a write that raced with open() must not be lost */
     overlay_forward(s);                     /* ... nor the overlay's text and style, set before the device was opened */
     GST_OBJECT_UNLOCK(s);
@@ -462,6 +474,37 @@ static GstFlowReturn enc_handle_frame(GstVideoEncoder *ve, GstVideoCodecFrame *f
         return gst_video_encoder_finish_frame(ve, frame);
     }
     const gint64 t0 = g_get_monotonic_time();
+    if (s->jpeg) { /* a picture the encoder refuses (not baseline, another size, corrupt data) is dropped; ten in a row: this is not a stream it can take */
+        GstMapInfo mi;
+        if (!gst_buffer_map(frame->input_buffer, &mi, GST_MAP_READ)) { gst_video_encoder_finish_frame(ve, frame); return GST_FLOW_ERROR; }
+        const gint64 t1 = g_get_monotonic_time();
+        const int r = mi355enc_submit_jpeg(s->enc, mi.data, mi.size, (int64_t)frame->pts, GST_VIDEO_CODEC_FRAME_IS_FORCE_KEYFRAME(frame) ? 1 : 0);
+        s->us_map += t1 - t0; s->us_submit += g_get_monotonic_time() - t1;
+        gst_buffer_unmap(frame->input_buffer, &mi); /* (the coefficients are in the encoder's own memory) */
+        if (r == MI355ENC_ERR_ARG) {
+            GST_WARNING_OBJECT(s, "JPEG picture refused (pts %" GST_TIME_FORMAT "): dropped", GST_TIME_ARGS(frame->pts));
+            if (++s->jpeg_refused >= 10) {
+                GST_ELEMENT_ERROR(s, STREAM, DECODE, ("mi355h264enc: ten JPEG pictures in a row refused"), ("baseline JPEG of %dx%d expected",
+                                  GST_VIDEO_INFO_WIDTH(&s->input_state->info), GST_VIDEO_INFO_HEIGHT(&s->input_state->info)));
+                gst_video_encoder_finish_frame(ve, frame);
+                return GST_FLOW_ERROR;
+            }
+            return gst_video_encoder_finish_frame(ve, frame); /* no output buffer: dropped */
+        }
+        if (r != MI355ENC_OK) {
+            GST_ELEMENT_ERROR(s, STREAM, ENCODE, ("mi355h264enc: submit failed: %s", mi355enc_strerror(r)), ("mi355enc_submit_jpeg returned %d", r));
+            gst_video_encoder_finish_frame(ve, frame);
+            return GST_FLOW_ERROR;
+        }
+        s->jpeg_refused = 0;
+        GstFlowReturn fr = GST_FLOW_OK;
+        if (mi355enc_pending(s->enc) > s->open_depth) {
+            GstVideoCodecFrame *old = gst_video_encoder_get_oldest_frame(ve);
+            if (old) fr = collect_into(s, old);
+        }
+        gst_video_codec_frame_unref(frame);
+        return fr;
+    }
     if (!gst_video_frame_map(&vf, &s->input_state->info, frame->input_buffer, GST_MAP_READ)) {
         gst_video_encoder_finish_frame(ve, frame);
         return GST_FLOW_ERROR;
@@ -554,7 +597,7 @@ static gboolean enc_propose_allocation(GstVideoEncoder *ve, GstQuery *q) {
     gboolean need_pool = FALSE;
     GstVideoInfo vi;
     gst_query_parse_allocation(q, &caps, &need_pool);
-    if (s->pinned_input && caps && gst_video_info_from_caps(&vi, caps)) {
+    if (s->pinned_input && caps && gst_video_info_from_caps(&vi, caps) && GST_VIDEO_INFO_FORMAT(&vi) != GST_VIDEO_FORMAT_ENCODED) { /* (raw caps only: a JPEG source keeps its own buffers) */
         GstAllocator *alloc = (GstAllocator *)g_object_new(gst_mi355_pin_allocator_get_type(), NULL);
         GstAllocationParams params;
         gst_allocation_params_init(&params);

@@ -209,6 +209,11 @@ typedef struct {
     uint8_t line_end[256];
 } overlay_args_t;
 void k_launch_overlay(const overlay_args_t *a, hipStream_t s);
+/* MJPEG input (k_jpeg.hip; the rule: DESIGN.md section 14): a picture of vw x vh (even) with luma sampling hs x vs and `comps` components, coefficient blocks and
+ * quantisation tables on the device as mi355enc_jpeg_entropy_decode lays them out, into NV12 surfaces of stride W and coded size W x H (the margin repeats the last
+ * visible row, column and chroma pair).  d_planar: scratch of 3 * ((vw + 15) & ~15) * vh bytes, read and written for 4:4:4 only.  -1: not a sampling it takes. */
+int k_launch_jpeg(const int16_t *d_coef, const uint16_t *d_qt, int hs, int vs, int comps, int vw, int vh, uint8_t *dy, uint8_t *duv, int W, int H,
+                  uint8_t *d_planar, hipStream_t s);
 void k_launch_quality(const uint8_t *src_y, const uint8_t *src_uv, int src_stride, const uint8_t *rec_y, const uint8_t *rec_uv, int rec_stride,
                       int width, int height, unsigned long long *d_acc, unsigned long long *out, hipStream_t s);
 #endif

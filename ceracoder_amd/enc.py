@@ -29,7 +29,7 @@ IDEC = np.dtype([("modes4", "u1", (16,)), ("mode16", "u1"), ("cmode", "u1"), ("u
 IMV_DTYPE = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("sad", "<u2"), ("bits", "<u2")])
 SURF_ROWS, SURF_COLS = 35, 36
 DROP_MAX, DROP_SKIP = 12, 255
-STAGE_ME, STAGE_INTER, STAGE_INTRA, STAGE_DEBLOCK, STAGE_SUBPEL, STAGE_CSC_I420, STAGE_CSC_YUY2, STAGE_CSC_UYVY, STAGE_ME_SELECT, STAGE_PMB, STAGE_INTRA_P, STAGE_QUALITY = range(12)
+STAGE_ME, STAGE_INTER, STAGE_INTRA, STAGE_DEBLOCK, STAGE_SUBPEL, STAGE_CSC_I420, STAGE_CSC_YUY2, STAGE_CSC_UYVY, STAGE_ME_SELECT, STAGE_PMB, STAGE_INTRA_P, STAGE_QUALITY, STAGE_JPEG = range(13)
 
 EXPORTS = [
     "mi355enc_abi_version", "mi355enc_strerror", "mi355enc_default_cfg", "mi355enc_open", "mi355enc_close",
@@ -43,6 +43,7 @@ EXPORTS = [
     "mi355enc_set_colorimetry", "mi355enc_csc_coefficients", "mi355enc_host_write_headers_vui", "mi355enc_stage_csc_device",
     "mi355enc_set_quality_metrics", "mi355enc_last_quality", "mi355enc_quality_totals", "mi355enc_stage_quality", "mi355enc_stage_quality_device",
     "mi355enc_overlay_default_style", "mi355enc_set_overlay_style", "mi355enc_set_overlay_text", "mi355enc_last_overlay", "mi355enc_overlay_glyph", "mi355enc_stage_overlay",
+    "mi355enc_jpeg_info", "mi355enc_jpeg_entropy_decode", "mi355enc_submit_jpeg", "mi355enc_stage_jpeg", "mi355enc_stage_jpeg_blocks",
 ]
 
 
@@ -70,6 +71,11 @@ class Quality(C.Structure):
     def ints(self):
         """the integers the device computed: (sse_y, sse_cb, sse_cr, ssim_sum, ssim_windows)"""
         return (int(self.sse[0]), int(self.sse[1]), int(self.sse[2]), int(self.ssim_sum), int(self.ssim_windows))
+
+
+class JpegInfo(C.Structure):
+    """mi355enc_jpeg_info_t: what the markers in front of a JPEG picture's scan say (hs, vs: luma sampling factors)"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("components", C.c_int), ("hs", C.c_int), ("vs", C.c_int), ("restart_interval", C.c_int), ("has_dht", C.c_int)]
 
 
 class OverlayStyle(C.Structure):
@@ -146,6 +152,11 @@ def load():
         L.mi355enc_last_overlay.argtypes = [vp, vp, C.c_size_t]
         L.mi355enc_overlay_glyph.argtypes = [C.c_int, vp]
         L.mi355enc_stage_overlay.argtypes = [vp, C.c_char_p, C.POINTER(OverlayStyle), vp, vp]
+        L.mi355enc_jpeg_info.argtypes = [vp, C.c_size_t, C.POINTER(JpegInfo)]
+        L.mi355enc_jpeg_entropy_decode.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp, C.POINTER(JpegInfo)]
+        L.mi355enc_submit_jpeg.argtypes = [vp, vp, C.c_size_t, C.c_int64, C.c_int]
+        L.mi355enc_stage_jpeg.argtypes = [vp, vp, C.c_size_t, vp, vp]
+        L.mi355enc_stage_jpeg_blocks.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
         L.mi355enc_host_alloc.restype = vp
         L.mi355enc_host_alloc.argtypes = [C.c_size_t]
         L.mi355enc_host_free.restype = None
@@ -257,6 +268,41 @@ def scale_table(n_in, n_out, kind):
     if r != n:
         raise EncoderError("mi355enc_scale_table: %d" % r)
     return first, coef
+
+
+def jpeg_info(data):
+    """The header of a JPEG picture (host only): a JpegInfo; EncoderError for a stream the encoder does not take."""
+    info = JpegInfo()
+    buf = np.frombuffer(bytes(data), np.uint8)
+    r = load().mi355enc_jpeg_info(_p(buf) if buf.size else None, buf.size, C.byref(info))
+    if r != 0:
+        raise EncoderError("mi355enc_jpeg_info: %s (%d)" % (load().mi355enc_strerror(r).decode(), r))
+    return info
+
+
+def jpeg_layout(info):
+    """[(blocks per row, block rows)] of each component's MCU-padded plane"""
+    mcux, mcuy = -(-info.width // (8 * info.hs)), -(-info.height // (8 * info.vs))
+    return [(mcux * (1 if c else info.hs), mcuy * (1 if c else info.vs)) for c in range(info.components)]
+
+
+def jpeg_entropy_decode(data, coef_cap=None):
+    """The host's entropy decode of a JPEG picture (no device): (info, [per component an int16 array (block rows, blocks per row, 8, 8)], uint16 qt[3][8][8]).
+    coef_cap: the room offered, in int16 (default: what the picture needs)."""
+    info = jpeg_info(data)
+    lay = jpeg_layout(info)
+    need = sum(bw * bh for bw, bh in lay) * 64
+    coef = np.zeros(max(need if coef_cap is None else int(coef_cap), 1), np.int16)
+    qt = np.zeros((3, 64), np.uint16)
+    buf = np.frombuffer(bytes(data), np.uint8)
+    r = load().mi355enc_jpeg_entropy_decode(_p(buf), buf.size, _p(coef), coef.size if coef_cap is None else int(coef_cap), _p(qt), C.byref(info))
+    if r != 0:
+        raise EncoderError("mi355enc_jpeg_entropy_decode: %s (%d)" % (load().mi355enc_strerror(r).decode(), r))
+    out, o = [], 0
+    for bw, bh in lay:
+        out.append(coef[o:o + bw * bh * 64].reshape(bh, bw, 8, 8))
+        o += bw * bh * 64
+    return info, out, qt.reshape(3, 8, 8)
 
 
 def overlay_style(**kw):
@@ -457,6 +503,30 @@ class Encoder:
         oy = np.empty((self.mbh * 16, self.mbw * 16), np.uint8)
         ouv = np.empty((self.mbh * 8, self.mbw * 16), np.uint8)
         self._chk(self.L.mi355enc_stage_csc(self.h, fmt, pp, ss, _p(oy), _p(ouv)), "stage_csc")
+        return oy, ouv
+
+    def submit_jpeg(self, data, pts=0, force_idr=False):
+        """A baseline JPEG picture of the input size (bytes): entropy decode on the host, everything else on the device.  EncoderError (MI355ENC_ERR_ARG)
+        for a picture that is refused or does not decode; nothing is enqueued then."""
+        buf = np.frombuffer(bytes(data), np.uint8)
+        self._chk(self.L.mi355enc_submit_jpeg(self.h, _p(buf) if buf.size else None, buf.size, pts, int(force_idr)), "submit_jpeg")
+
+    def _surfaces(self):
+        return np.empty((self.mbh * 16, self.mbw * 16), np.uint8), np.empty((self.mbh * 8, self.mbw * 16), np.uint8)
+
+    def stage_jpeg(self, data):
+        """The JPEG path alone: the coded-size NV12 surfaces of a picture, like stage_csc."""
+        buf = np.frombuffer(bytes(data), np.uint8)
+        oy, ouv = self._surfaces()
+        self._chk(self.L.mi355enc_stage_jpeg(self.h, _p(buf) if buf.size else None, buf.size, _p(oy), _p(ouv)), "stage_jpeg")
+        return oy, ouv
+
+    def stage_jpeg_blocks(self, hs, vs, components, coef, qt):
+        """The JPEG kernel alone on made-up coefficients: coef a list of per-component int16 arrays (block rows, blocks per row, 8, 8) or one flat array, qt uint16 (3, 64)."""
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(c, np.int16).ravel() for c in coef]) if isinstance(coef, (list, tuple)) else coef, np.int16)
+        q = np.ascontiguousarray(np.asarray(qt, np.uint16).reshape(3, 64))
+        oy, ouv = self._surfaces()
+        self._chk(self.L.mi355enc_stage_jpeg_blocks(self.h, hs, vs, components, _p(flat), _p(q), _p(oy), _p(ouv)), "stage_jpeg_blocks")
         return oy, ouv
 
     def stage_csc_device(self, fmt, plane_ptrs, strides, out_y_ptr, out_uv_ptr):

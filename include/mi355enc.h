@@ -258,6 +258,27 @@ int mi355enc_stage_scale(mi355enc_t *h, int fmt, const uint8_t *const planes[3],
  * only that and *taps), MI355ENC_ERR_ARG for upscaling, a ratio above 8 or odd sizes. */
 enum { MI355ENC_SCALE_LUMA = 0, MI355ENC_SCALE_CHROMA_V = 1, MI355ENC_SCALE_CHROMA_H = 2, MI355ENC_SCALE_CHROMA_V422 = 3 };
 int mi355enc_scale_table(int in, int out, int kind, int *first, int16_t *coef, size_t coef_cap, int *taps);
+/* ---- MJPEG input ----------------------------------------------
+ * A baseline JPEG picture goes straight in: the host parses the markers and runs the serial Huffman decode, the device does dequantisation,
+ * the 8x8 inverse DCT (IJG's accurate integer one: what libjpeg's ISLOW produces), level shift, clamp and the step from 4:2:2 / 4:4:4 to
+ * 4:2:0, into the coded NV12 surfaces.  Accepted: SOF0 / SOF1, 8 bit, Huffman coded, one interleaved scan; one component, or three with
+ * chroma sampling 1x1 and luma sampling 2x2, 2x1 or 1x1; 8-bit quantisation tables; DRI / RSTn; APPn / COM skipped; a picture without DHT
+ * uses the typical tables of T.81 Annex K.3.  Everything else, and every picture whose data does not decode, is MI355ENC_ERR_ARG. */
+typedef struct { int width, height, components, hs, vs, restart_interval, has_dht; } mi355enc_jpeg_info_t;
+/* host only: what the markers in front of the scan say (hs, vs: the luma sampling factors; 1, 1 for a single component) */
+int mi355enc_jpeg_info(const uint8_t *data, size_t len, mi355enc_jpeg_info_t *info);
+/* host only: the entropy decode.  coef (coef_cap int16 of room, MI355ENC_ERR_OVERFLOW when that is too little): per component, the blocks of
+ * its MCU-padded plane in raster order, each 64 int16 in natural (row-major) order, quantisation not applied.  qt[c]: component c's
+ * quantisation table in natural order.  info may be NULL. */
+int mi355enc_jpeg_entropy_decode(const uint8_t *data, size_t len, int16_t *coef, size_t coef_cap, uint16_t qt[3][64], mi355enc_jpeg_info_t *info);
+/* like mi355enc_submit_fmt, from a JPEG picture whose size is the handle's input size (even width and height).  The bytes are the caller's
+ * again when the call returns.  A refused or corrupt picture (MI355ENC_ERR_ARG) leaves the handle exactly as it was: nothing is enqueued. */
+int mi355enc_submit_jpeg(mi355enc_t *h, const uint8_t *data, size_t len, int64_t pts, int force_idr);
+/* decode stage alone (tests): writes the coded-size NV12 surfaces, like mi355enc_stage_csc */
+int mi355enc_stage_jpeg(mi355enc_t *h, const uint8_t *data, size_t len, uint8_t *out_y, uint8_t *out_uv);
+/* ... and the kernel alone, on coefficients the caller made up: a picture of the handle's input size with luma sampling hs x vs and
+ * `components` components, coef and qt laid out as mi355enc_jpeg_entropy_decode writes them */
+int mi355enc_stage_jpeg_blocks(mi355enc_t *h, int hs, int vs, int components, const int16_t *coef, const uint16_t qt[3][64], uint8_t *out_y, uint8_t *out_uv);
 int mi355enc_pending(const mi355enc_t *h);
 int mi355enc_collect(mi355enc_t *h, uint8_t *out, size_t out_cap, size_t *out_len, int *is_keyframe,
                      int64_t *pts, int *qp);
@@ -386,7 +407,8 @@ int mi355enc_stage_deblock(mi355enc_t *h, uint8_t *rec_y, uint8_t *rec_uv, const
 /* Time `iters` back-to-back launches of one stage on the handle's stream with HIP events;
  * stage: 0 ME, 1 inter, 2 intra (whole wavefront), 3 deblock (whole wavefront), 4 sub-sample refinement,
  * 5 / 6 / 7 input conversion from I420 / YUY2 / UYVY, 8 one vector-selection iteration, 9 fused P stage, 10 intra macroblocks of a P picture,
- * 11 the quality-metrics launch (slot 0's source surfaces against reconstruction buffer 1).
+ * 11 the quality-metrics launch (slot 0's source surfaces against reconstruction buffer 1),
+ * 12 the JPEG launch for the handle's input size as 4:2:2, on whatever slot 0's coefficient buffer holds.
  * Uses whatever the handle's surfaces currently hold.  Returns average ms per launch. */
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms);
 
