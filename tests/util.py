@@ -214,3 +214,134 @@ def window_edge_pattern(mbw, mbh):
         else:
             p[y, :] = False
     return p
+
+
+# ---- content at the arithmetic limits (tests/test_extremes_cpu.py checks on the oracle that each reaches the branch it was built for;
+# ---- tests/test_extremes_gpu.py runs the kernels on it).  Seeded, numpy only; every function returns NV12 planes (y (h, w), uv (h / 2, w)).
+
+def _nv12(u, v):
+    uv = np.empty((u.shape[0], 2 * u.shape[1]), np.uint8)
+    uv[:, 0::2], uv[:, 1::2] = u, v
+    return uv
+
+
+def _blocks01(g, h, w, blk, share=0.5):
+    """(h, w) uint8 of blk x blk blocks, each 0 or 255 (`share` of them 255)"""
+    b = (g.random(((h + blk - 1) // blk, (w + blk - 1) // blk)) < share).astype(np.uint8) * np.uint8(255)
+    return np.kron(b, np.ones((blk, blk), np.uint8))[:h, :w]
+
+
+def sat_blocks(w, h, blk, seed):
+    """Every blk x blk block (blk 16, 8, 4 or 1) is 0 or 255, in luma and in both chroma components (blocks of blk chroma samples):
+    residuals of +-255 over whole blocks (the quantiser's |level| <= 2047 clamp at QP 0), SADs of 65 280, reconstruction at both rails."""
+    g = np.random.Generator(np.random.PCG64(seed))
+    y = _blocks01(g, h, w, blk)
+    return y, _nv12(_blocks01(g, h // 2, w // 2, blk), _blocks01(g, h // 2, w // 2, blk))
+
+
+def stripes(w, h, period, axis, phase=0):
+    """0 / 255 stripes of `period` samples (the first (period + 1) // 2 of every period are 255), axis "v" (vertical stripes), "h" (horizontal) or
+    "both" (a checkerboard), moved by `phase` samples along the striped axes; chroma the same pattern on its own grid.  The six-tap filter overshoots
+    between two samples of 255 flanked by zeros and undershoots between two zeros flanked by 255; the checkerboard does both in both passes, which
+    takes the centre half sample's unrounded intermediates to the two ends of their range."""
+    on = (period + 1) // 2
+
+    def plane(ph, pw):
+        yy, xx = np.mgrid[0:ph, 0:pw]
+        sv, sh = ((xx + phase) % period) < on, ((yy + phase) % period) < on
+        m = sv if axis == "v" else sh if axis == "h" else sv ^ sh
+        return np.where(m, 255, 0).astype(np.uint8)
+    c = plane(h // 2, w // 2)
+    return plane(h, w), _nv12(c, c)
+
+
+def shifted_pair(w, h, dx, dy, seed, half=False):
+    """-> ((cur_y, cur_uv), (ref_y, ref_uv)): a full-range texture (uniform noise low-passed once with (1, 2, 1) / 4 in both directions, contrast doubled
+    around mid-grey so that it reaches both rails) as the reference, and the same texture displaced as the current picture: cur(x, y) = ref(x + dx, y + dy),
+    so the vector of every macroblock whose displaced block lies inside the picture is (dx, dy) whole samples -- with |dx| = |dy| = 16 the corner of the
+    +-16 window.  half: the current picture is the rounded average of the displacements (dx, dy) and (dx + sign(dx), dy) -- half a sample further out."""
+    g = np.random.Generator(np.random.PCG64(seed))
+    m = 40  # margin: the window, the half sample and the filter's support
+
+    def texture(th, tw):
+        n = g.integers(0, 256, (th, tw)).astype(np.int64)
+        n = (np.roll(n, 1, 1) + 2 * n + np.roll(n, -1, 1) + 2) >> 2
+        n = (np.roll(n, 1, 0) + 2 * n + np.roll(n, -1, 0) + 2) >> 2
+        return np.clip(2 * (n - 128) + 128, 0, 255)
+
+    def pair(t, ph, pw, mm, sx, sy, hx):
+        ref = t[mm:mm + ph, mm:mm + pw]
+        cur = t[mm + sy:mm + sy + ph, mm + sx:mm + sx + pw]
+        if half:
+            cur = (cur + t[mm + sy:mm + sy + ph, mm + sx + hx:mm + sx + hx + pw] + 1) >> 1
+        return cur.astype(np.uint8), ref.astype(np.uint8)
+    sgn = 1 if dx > 0 else -1
+    cy, ry = pair(texture(h + 2 * m, w + 2 * m), h, w, m, dx, dy, sgn)
+    tu, tv = texture(h // 2 + m, w // 2 + m), texture(h // 2 + m, w // 2 + m)
+    cu, ru = pair(tu, h // 2, w // 2, m // 2, dx // 2, dy // 2, sgn)
+    cv, rv = pair(tv, h // 2, w // 2, m // 2, dx // 2, dy // 2, sgn)
+    return (cy, _nv12(cu, cv)), (ry, _nv12(ru, rv))
+
+
+def near_sat_ramps(w, h, seed):
+    """Steep planes that run into the rails: every 32 x 32 tile (16 x 16 in chroma) is clip(v0 + sx (x - xc) + sy (y - yc)) with |sx|, |sy| in 3 .. 10 per
+    sample, (xc, yc) a point near the tile's centre and v0 within 12 of 0 or of 255 (alternating from tile to tile).  The top row and the left column of the tile's macroblocks are gradients
+    that end at a rail, the macroblocks right of and below the tile's first continue their neighbours' plane, and plane prediction (Intra_16x16 and chroma:
+    8.3.3.4, 8.3.4.4) extrapolates it below 0 and above 255; the Intra_4x4 / Intra_8x8 modes see the same gradients at the scale of their blocks."""
+    g = np.random.Generator(np.random.PCG64(seed))
+
+    def plane(ph, pw, tile):
+        ty, tx = (ph + tile - 1) // tile, (pw + tile - 1) // tile
+        up = lambda a: np.kron(a, np.ones((tile, tile), np.int64))[:ph, :pw]
+        sx = up(g.integers(3, 11, (ty, tx)) * g.choice([-1, 1], (ty, tx)))
+        sy = up(g.integers(3, 11, (ty, tx)) * g.choice([-1, 1], (ty, tx)))
+        low = (np.add.outer(np.arange(ty), np.arange(tx)) + seed) % 2 == 0  # the rails alternate from tile to tile: both occur in any picture of two tiles
+        v0 = up(np.where(low, g.integers(0, 13, (ty, tx)), 255 - g.integers(0, 13, (ty, tx))))
+        xc, yc = up(g.integers(tile // 2 - 3, tile // 2 + 4, (ty, tx))), up(g.integers(tile // 2 - 3, tile // 2 + 4, (ty, tx)))
+        yy, xx = np.mgrid[0:ph, 0:pw]
+        return np.clip(v0 + sx * (xx % tile - xc) + sy * (yy % tile - yc), 0, 255).astype(np.uint8)
+    y = plane(h, w, 32)
+    return y, _nv12(plane(h // 2, w // 2, 16), plane(h // 2, w // 2, 16))
+
+
+def db_picture_sat(mbw, mbh, seed):
+    """db_picture's twin at the rails: samples of 0 .. 6 in the left half of the picture and of 249 .. 255 in the right half, with steps of 2 .. 9 between
+    4x4 blocks of luma and of either chroma component (six of seven towards the rail, clipped to 0 .. 255: blocks that lie on the rail but for a few low
+    samples, beside blocks a few levels off it) -- |p0 - q0| stays under alpha from the middle QPs up, and p0 + delta / q0 - delta reach and leave
+    0 .. 255 (8.7.2.3: the Clip1 of the bS < 4 filter)."""
+    g = np.random.Generator(np.random.PCG64(seed))
+    H, W = mbh * 16, mbw * 16
+
+    def field(h, w, blk):
+        base = g.integers(0, 7, (h, w))
+        step = g.integers(2, 10, (h // blk, w // blk)) * np.where(g.random((h // blk, w // blk)) < 6 / 7, -1, 1)
+        v = np.clip(base + np.kron(step, np.ones((blk, blk), np.int64)), 0, 255)
+        v[:, w // 2:] = 255 - v[:, w // 2:]
+        return v.astype(np.uint8)
+    y = field(H, W, 4)
+    return y, _nv12(field(H // 2, W // 2, 4), field(H // 2, W // 2, 4))
+
+
+def sat_clip(w, h, n, seed):
+    """n pictures; every macroblock of every picture is drawn from: flat 0, flat 255, flat mid-grey (variance 0: adaptive quantisation's lowest offset),
+    a sat_blocks tile of 8 x 8 blocks, a sat_blocks tile of single samples, or -- from the second picture on -- the macroblock of the picture before
+    (P_Skip beside saturated neighbours).  Luma and both chroma components alike.  The share of samples at 255 in a single-sample tile is drawn per
+    macroblock from 1/2 (the largest variance there is), 1/16 and 1/128, so that adaptive quantisation sees more than its two end offsets."""
+    g = np.random.Generator(np.random.PCG64(seed))
+    mbw, mbh = (w + 15) // 16, (h + 15) // 16
+    y, uv = np.zeros((mbh * 16, mbw * 16), np.uint8), np.zeros((mbh * 8, mbw * 16), np.uint8)
+    out = []
+    for i in range(n):
+        kind = g.integers(0, 6 if i else 5, (mbh, mbw))
+        for my in range(mbh):
+            for mx in range(mbw):
+                k = int(kind[my, mx])
+                ys, cs = (slice(my * 16, my * 16 + 16), slice(mx * 16, mx * 16 + 16)), (slice(my * 8, my * 8 + 8), slice(mx * 16, mx * 16 + 16))
+                if k < 3:
+                    y[ys], uv[cs] = (0, 255, 128)[k], (0, 255, 128)[k]
+                elif k < 5:
+                    blk, share = (8, 0.5) if k == 3 else (1, (0.5, 0.5, 1 / 16, 1 / 128)[int(g.integers(0, 4))])
+                    y[ys] = _blocks01(g, 16, 16, blk, share)
+                    uv[cs] = _nv12(_blocks01(g, 8, 8, blk, share), _blocks01(g, 8, 8, blk, share))
+        out.append((y[:h, :w].copy(), uv[:h // 2, :w].copy()))
+    return out
