@@ -320,6 +320,7 @@ void mi355enc_close(mi355enc_t *h) {
         if (s->d_src_uv) (void)hipFree(s->d_src_uv);
         if (s->d_raw) (void)hipFree(s->d_raw);
         if (s->d_csc) (void)hipFree(s->d_csc);
+        orient_free(s);
         jpeg_free(s);
         if (s->done) (void)hipEventDestroy(s->done);
         if (s->gpu_done) (void)hipEventDestroy(s->gpu_done);

@@ -3,6 +3,7 @@
 //   enc_handle.cpp    open / close / setters / statistics / fetch
 //   enc_schedule.cpp  the picture pipeline: submit*, the stream schedule of one picture, collect
 //   enc_overlay.cpp   the text overlay: setters, latch, layout, launch
+//   enc_orient.cpp    orientation of the input picture: setter, the slot's pre-orientation picture, launch, its stage entry points
 //   enc_jpeg.cpp      MJPEG input: coefficient buffers, host decode, transfer + launch, its stage entry points
 //   enc_stages.cpp    single-stage entry points (parity tests, probes) and the host-only stages
 #ifndef MI355_ENC_INTERNAL_HPP
@@ -51,6 +52,7 @@ struct slot_t {
     uint8_t *d_src_y, *d_src_uv; // staging for host / unaligned input
     uint8_t *d_raw;              // staging of non-NV12 input before the conversion kernel, and of every input before the scale kernel (allocated on first use, raw_bytes())
     uint8_t *d_csc;              // the formats of k_csc.hip with an input size of their own: the NV12 picture of the input size between conversion and scale (allocated on first use)
+    uint8_t *d_pre;              // orientation (allocated on first use): the NV12 picture of the pre-orientation visible size, which the decode / conversion / scale / copy writes instead of d_src_*
     uint8_t *h_jpeg, *d_jpeg;    // MJPEG input (allocated on first use): the quantisation tables and the coefficient blocks of the picture, pinned / on the device
     uint8_t *d_jpeg_planar;      // ... and the planar picture of a 4:4:4 one between the JPEG launch and the conversion
     hipEvent_t done, gpu_done, ev[12];
@@ -148,6 +150,10 @@ struct mi355enc {
     // tables on the device and where the kernel finds them
     int in_w, in_h, sar_w, sar_h;
     bool scaling;
+    // orientation (mi355enc_set_orientation): the method, and whether mi355enc_set_input_size has been called (otherwise the input size
+    // follows the method: the pre-orientation target pre_w() x pre_h())
+    int orient;
+    bool in_set;
     uint8_t *d_scale_tab; size_t scale_tab_bytes;
     scale_plan_t scale;
     // colorimetry (mi355enc_set_colorimetry): what every SPS says about the samples (0, 2, 2, 2: nothing), and the RGB -> Y'CbCr matrix that follows from it
@@ -224,6 +230,20 @@ int quality_run(mi355enc_t *h, const uint8_t *src_y, const uint8_t *src_uv, int 
 // enc_overlay.cpp
 void overlay_latch(mi355enc_t *h, slot_t *s);                 // the text and style set last become the slot's (the first thing a submit does)
 int overlay_draw(mi355enc_t *h, slot_t *s, hipStream_t st);   // the slot's text into its source surfaces, behind everything enqueued on st so far; nothing with no text
+// enc_scale.cpp
+// the one place the input geometry of a handle is decided (both setters end here): validates, then rebuilds tables, sizes, SAR and staging buffers; ERR_ARG leaves the handle as it was
+int geometry_apply(mi355enc_t *h, int orient, bool in_set, int in_w, int in_h);
+// enc_orient.cpp
+static inline bool orient_transposes(int m) { return m == MI355ENC_ORIENT_90R || m == MI355ENC_ORIENT_90L || m == MI355ENC_ORIENT_UL_LR || m == MI355ENC_ORIENT_UR_LL; }
+static inline int pre_w(const mi355enc_t *h) { return orient_transposes(h->orient) ? h->cfg.height : h->cfg.width; } // the pre-orientation target: what decode / conversion / scale produce
+static inline int pre_h(const mi355enc_t *h) { return orient_transposes(h->orient) ? h->cfg.width : h->cfg.height; }
+// Where the step in front of the orientation writes its NV12 picture, and with what sizes: the slot's coded surfaces (identity: stride W, visible cfg size, margin up
+// to W x H), or the slot's pre-orientation picture (visible size only: W = its stride, H = its height).  Every submit path asks here ...
+struct in_target_t { uint8_t *y, *uv; int vw, vh, W, H; };
+int input_target(mi355enc_t *h, slot_t *s, in_target_t *t);
+// ... and ends here: with a method, the orientation launch from (src_y, src_uv; null: the slot's pre-orientation picture) into the slot's coded surfaces (nothing with identity)
+int input_finish(mi355enc_t *h, slot_t *s, hipStream_t up, const uint8_t *src_y = nullptr, int y_stride = 0, const uint8_t *src_uv = nullptr, int uv_stride = 0);
+void orient_free(slot_t *s);
 // enc_jpeg.cpp
 int jpeg_alloc(mi355enc_t *h, slot_t *s);  // the slot's coefficient buffers (idempotent)
 void jpeg_free(slot_t *s);

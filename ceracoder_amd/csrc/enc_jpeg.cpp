@@ -53,23 +53,28 @@ int jpeg_enqueue(mi355enc_t *h, slot_t *s, const mi355enc_jpeg_info_t *info, hip
     HIPCHK(hipMemcpyAsync(s->d_jpeg, s->h_jpeg, bytes, hipMemcpyHostToDevice, up));
     const int16_t *dc = (const int16_t *)(s->d_jpeg + JPEG_QT_BYTES);
     const uint16_t *dq = (const uint16_t *)s->d_jpeg;
-    int r;
-    if (!h->scaling) r = k_launch_jpeg(dc, dq, info->hs, info->vs, info->components, h->cfg.width, h->cfg.height, s->d_src_y, s->d_src_uv, h->W, h->H, s->d_jpeg_planar, up);
+    in_target_t t;
+    int r = input_target(h, s, &t);
+    if (r) return r;
+    if (!h->scaling) r = k_launch_jpeg(dc, dq, info->hs, info->vs, info->components, t.vw, t.vh, t.y, t.uv, t.W, t.H, s->d_jpeg_planar, up);
     else {
         const int wi = (h->in_w + 15) & ~15;
         if (!s->d_csc) HIPCHK(hipMalloc((void **)&s->d_csc, (size_t)wi * h->in_h * 3 / 2 + SURF_PAD));
         uint8_t *cy = s->d_csc, *cuv = cy + (size_t)wi * h->in_h;
         r = k_launch_jpeg(dc, dq, info->hs, info->vs, info->components, h->in_w, h->in_h, cy, cuv, wi, h->in_h, s->d_jpeg_planar, up);
-        if (!r) r = k_launch_scale(MI355ENC_FMT_NV12, cy, cuv, nullptr, wi, wi, 0, s->d_src_y, s->d_src_uv, h->W, h->H, &h->scale, up);
+        if (!r) r = k_launch_scale(MI355ENC_FMT_NV12, cy, cuv, nullptr, wi, wi, 0, t.y, t.uv, t.W, t.H, &h->scale, up);
     }
     if (r) return MI355ENC_ERR_ARG;
     HIPCHK(hipGetLastError());
-    return MI355ENC_OK;
+    return input_finish(h, s, up);
 }
 
 // the launch alone for mi355enc_time_stage: the coded size as 4:2:2, on whatever slot 0's coefficient buffer holds
 int jpeg_time_launch(mi355enc_t *h, slot_t *s) {
-    return k_launch_jpeg((const int16_t *)(s->d_jpeg + JPEG_QT_BYTES), (const uint16_t *)s->d_jpeg, 2, 1, 3, h->cfg.width, h->cfg.height, s->d_src_y, s->d_src_uv, h->W, h->H,
+    in_target_t t;
+    int r = input_target(h, s, &t);
+    if (r) return r;
+    return k_launch_jpeg((const int16_t *)(s->d_jpeg + JPEG_QT_BYTES), (const uint16_t *)s->d_jpeg, 2, 1, 3, t.vw, t.vh, t.y, t.uv, t.W, t.H,
                          s->d_jpeg_planar, h->stream) ? MI355ENC_ERR_ARG : MI355ENC_OK;
 }
 

@@ -68,9 +68,10 @@ static int scale_tile_reach(const std::vector<int> &first, int taps, int n_out, 
     return most;
 }
 
-// Builds the five tables for in_w x in_h -> the coded visible size, copies them to the device (one allocation per handle) and fills h->scale.
+// Builds the five tables for in_w x in_h -> the pre-orientation target (the coded visible size, exchanged under a transposing method), copies them to the
+// device (one allocation per handle) and fills h->scale.
 static int scale_setup(mi355enc_t *h, int in_w, int in_h) {
-    const int ow = h->cfg.width, oh = h->cfg.height;
+    const int ow = pre_w(h), oh = pre_h(h);
     const int ins[SCALE_TABLES] = {in_w, in_h, in_w, in_h, in_h}, outs[SCALE_TABLES] = {ow, oh, ow, oh, oh};
     const int kinds[SCALE_TABLES] = {MI355ENC_SCALE_LUMA, MI355ENC_SCALE_LUMA, MI355ENC_SCALE_CHROMA_H, MI355ENC_SCALE_CHROMA_V, MI355ENC_SCALE_CHROMA_V422};
     std::vector<int> first[SCALE_TABLES];
@@ -131,6 +132,41 @@ size_t raw_bytes(const mi355enc_t *h) {
     return (size_t)(4 * w + 48) * ht + 64; // the largest: four bytes per pixel, or three planes of the picture's size, rows at multiples of 16 bytes
 }
 
+// The input geometry of a handle: the method, and the input size (in_set: the one mi355enc_set_input_size gave; otherwise it follows the method).  The scaler's
+// target is the pre-orientation size, so its limits hold against that; the SAR it makes is written with its terms exchanged when the picture is transposed afterwards.
+int geometry_apply(mi355enc_t *h, int orient, bool in_set, int in_w, int in_h) {
+    if (h->n_submitted) return MI355ENC_ERR_STATE; // (the stream's geometry is fixed from its first picture on)
+    if (orient < MI355ENC_ORIENT_IDENTITY || orient > MI355ENC_ORIENT_UR_LL) return MI355ENC_ERR_ARG;
+    const bool tr = orient_transposes(orient);
+    const int ow = tr ? h->cfg.height : h->cfg.width, oh = tr ? h->cfg.width : h->cfg.height;
+    if (!in_set) { in_w = ow; in_h = oh; }
+    if (in_w > 8192 || in_h > 8192 || (in_w & 1) || (in_h & 1) || in_w < ow || in_h < oh || in_w > 8 * ow || in_h > 8 * oh) return MI355ENC_ERR_ARG;
+    if (orient == h->orient && in_set == h->in_set && in_w == h->in_w && in_h == h->in_h && (!in_set || h->d_scale_tab)) return MI355ENC_OK; // nothing changes: nothing is touched
+    if (h->pending) return MI355ENC_ERR_STATE;
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    { int r = sync_compute(h); if (r) return r; }
+    HIPCHK(hipStreamSynchronize(h->cstream));
+    const int was = h->orient;
+    h->orient = orient; // (scale_setup builds for the pre-orientation target)
+    if (in_set) { int r = scale_setup(h, in_w, in_h); if (r) { h->orient = was; return r; } } // (a handle whose input size was never set has no tables, as before)
+    h->in_set = in_set;
+    h->in_w = in_w; h->in_h = in_h;
+    h->scaling = in_w != ow || in_h != oh;
+    if (h->scaling) scale_sar(in_w, in_h, ow, oh, &h->sar_w, &h->sar_h);
+    else h->sar_w = h->sar_h = in_set ? 1 : 0;
+    if (h->sar_w == h->sar_h) h->sar_w = h->sar_h = 0; // square samples: no aspect_ratio_info in the VUI (the headers of an unscaled stream)
+    else if (tr) { const int t = h->sar_w; h->sar_w = h->sar_h; h->sar_h = t; } // the samples are turned with the picture
+    for (int i = 0; i < NSLOT; i++) { // staging buffers follow the input size (allocated again on first use)
+        slot_t *s = &h->slot[i];
+        if (s->d_raw) { (void)hipFree(s->d_raw); s->d_raw = nullptr; }
+        if (s->d_csc) { (void)hipFree(s->d_csc); s->d_csc = nullptr; }
+        orient_free(s);
+        jpeg_free(s);
+        if (s->h_src) { (void)hipHostFree(s->h_src); s->h_src = nullptr; }
+    }
+    return MI355ENC_OK;
+}
+
 extern "C" {
 
 int mi355enc_scale_table(int in, int out, int kind, int *first, int16_t *coef, size_t coef_cap, int *taps) {
@@ -146,28 +182,7 @@ int mi355enc_scale_table(int in, int out, int kind, int *first, int16_t *coef, s
 
 int mi355enc_set_input_size(mi355enc_t *h, int in_w, int in_h) {
     if (!h) return MI355ENC_ERR_ARG;
-    if (h->n_submitted) return MI355ENC_ERR_STATE; // (the stream's geometry is fixed from its first picture on)
-    const int ow = h->cfg.width, oh = h->cfg.height;
-    if (in_w > 8192 || in_h > 8192 || (in_w & 1) || (in_h & 1) || in_w < ow || in_h < oh || in_w > 8 * ow || in_h > 8 * oh) return MI355ENC_ERR_ARG;
-    if (h->pending) return MI355ENC_ERR_STATE;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    { int r = sync_compute(h); if (r) return r; }
-    HIPCHK(hipStreamSynchronize(h->cstream));
-    int r = scale_setup(h, in_w, in_h);
-    if (r) return r;
-    h->in_w = in_w; h->in_h = in_h;
-    h->scaling = in_w != ow || in_h != oh;
-    if (h->scaling) scale_sar(in_w, in_h, ow, oh, &h->sar_w, &h->sar_h);
-    else h->sar_w = h->sar_h = 1;
-    if (h->sar_w == h->sar_h) h->sar_w = h->sar_h = 0; // square samples: no aspect_ratio_info in the VUI (the headers of an unscaled stream)
-    for (int i = 0; i < NSLOT; i++) { // staging buffers follow the input size (allocated again on first use)
-        slot_t *s = &h->slot[i];
-        if (s->d_raw) { (void)hipFree(s->d_raw); s->d_raw = nullptr; }
-        if (s->d_csc) { (void)hipFree(s->d_csc); s->d_csc = nullptr; }
-        jpeg_free(s);
-        if (s->h_src) { (void)hipHostFree(s->h_src); s->h_src = nullptr; }
-    }
-    return MI355ENC_OK;
+    return geometry_apply(h, h->orient, true, in_w, in_h);
 }
 
 int mi355enc_stage_scale(mi355enc_t *h, int fmt, const uint8_t *const planes[3], const int strides[3], uint8_t *out_y, uint8_t *out_uv) {
@@ -184,8 +199,13 @@ int mi355enc_stage_scale(mi355enc_t *h, int fmt, const uint8_t *const planes[3],
     } else {
         int r = upload_raw(h, s, fmt, planes, strides, h->stream, p, st);
         if (r) return r;
-        if (k_launch_scale(fmt, p[0], p[1], p[2], st[0], st[1], st[2], s->d_src_y, s->d_src_uv, h->W, h->H, &h->scale, h->stream)) return MI355ENC_ERR_ARG;
+        in_target_t t;
+        r = input_target(h, s, &t);
+        if (r) return r;
+        if (k_launch_scale(fmt, p[0], p[1], p[2], st[0], st[1], st[2], t.y, t.uv, t.W, t.H, &h->scale, h->stream)) return MI355ENC_ERR_ARG;
         HIPCHK(hipGetLastError());
+        r = input_finish(h, s, h->stream);
+        if (r) return r;
     }
     HIPCHK(hipMemcpyAsync(out_y, s->d_src_y, h->ysz, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(out_uv, s->d_src_uv, h->csz, hipMemcpyDeviceToHost, h->stream));

@@ -366,20 +366,23 @@ int upload_and_convert(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const p
     int st[3];
     int r = upload_raw(h, s, fmt, planes, strides, up, p, st);
     if (r) return r;
+    in_target_t t; // the coded surfaces, or with an orientation the slot's pre-orientation picture
+    r = input_target(h, s, &t);
+    if (r) return r;
     if (fmt >= MI355ENC_FMT_Y42B) { // the formats of k_csc.hip; with an input size of its own: converted at that size, then scaled as NV12
-        if (!h->scaling) r = k_launch_csc2(fmt, p[0], p[1], p[2], st[0], st[1], st[2], s->d_src_y, s->d_src_uv, h->cfg.width, h->cfg.height, h->W, h->H, h->csc_coef, up);
+        if (!h->scaling) r = k_launch_csc2(fmt, p[0], p[1], p[2], st[0], st[1], st[2], t.y, t.uv, t.vw, t.vh, t.W, t.H, h->csc_coef, up);
         else {
             const int wi = (h->in_w + 15) & ~15;
             if (!s->d_csc) HIPCHK(hipMalloc((void **)&s->d_csc, (size_t)wi * h->in_h * 3 / 2 + SURF_PAD));
             uint8_t *cy = s->d_csc, *cuv = cy + (size_t)wi * h->in_h;
             r = k_launch_csc2(fmt, p[0], p[1], p[2], st[0], st[1], st[2], cy, cuv, h->in_w, h->in_h, wi, h->in_h, h->csc_coef, up);
-            if (!r) r = k_launch_scale(MI355ENC_FMT_NV12, cy, cuv, nullptr, wi, wi, 0, s->d_src_y, s->d_src_uv, h->W, h->H, &h->scale, up);
+            if (!r) r = k_launch_scale(MI355ENC_FMT_NV12, cy, cuv, nullptr, wi, wi, 0, t.y, t.uv, t.W, t.H, &h->scale, up);
         }
-    } else if (h->scaling) r = k_launch_scale(fmt, p[0], p[1], p[2], st[0], st[1], st[2], s->d_src_y, s->d_src_uv, h->W, h->H, &h->scale, up);
-    else r = k_launch_csc(fmt, p[0], p[1], p[2], st[0], st[1], st[2], s->d_src_y, s->d_src_uv, h->cfg.width, h->cfg.height, h->W, h->H, up);
+    } else if (h->scaling) r = k_launch_scale(fmt, p[0], p[1], p[2], st[0], st[1], st[2], t.y, t.uv, t.W, t.H, &h->scale, up);
+    else r = k_launch_csc(fmt, p[0], p[1], p[2], st[0], st[1], st[2], t.y, t.uv, t.vw, t.vh, t.W, t.H, up);
     if (r) return MI355ENC_ERR_ARG;
     HIPCHK(hipGetLastError());
-    return MI355ENC_OK;
+    return input_finish(h, s, up);
 }
 
 // ---- the entropy-coding worker: one picture at a time, in submission order
@@ -539,9 +542,12 @@ int mi355enc_submit(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t
     const int w = h->in_w, ht = h->in_h;
     hipStream_t up = upload_stream(h);
     // where the planes go: the staging surfaces at the coded stride, or -- to be scaled -- the raw staging buffer at the input's
+    // (with an orientation, `the staging surfaces' are the slot's pre-orientation picture at its own stride: input_target)
     if (h->scaling && !s->d_raw) HIPCHK(hipMalloc((void **)&s->d_raw, raw_bytes(h)));
-    const int ds = h->scaling ? (w + 15) & ~15 : h->W;
-    uint8_t *dev_y = h->scaling ? s->d_raw : s->d_src_y, *dev_uv = h->scaling ? s->d_raw + (size_t)ds * ht : s->d_src_uv;
+    in_target_t t;
+    { int r = input_target(h, s, &t); if (r) return r; }
+    const int ds = h->scaling ? (w + 15) & ~15 : t.W;
+    uint8_t *dev_y = h->scaling ? s->d_raw : t.y, *dev_uv = h->scaling ? s->d_raw + (size_t)ds * ht : t.uv;
     const bool pinned = host_range_pinned(y, (size_t)y_stride * (ht - 1) + w) && host_range_pinned(uv, (size_t)uv_stride * (ht / 2 - 1) + w);
     if (pinned || h->cfg.pipeline_depth == 0) {
         // pinned: transferred in place.  pipeline_depth 0 (the latency mode: collect() follows at once, there is nothing to run beside): the
@@ -551,7 +557,7 @@ int mi355enc_submit(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t
         HIPCHK(hipMemcpy2DAsync(dev_uv, ds, uv, uv_stride, w, ht / 2, hipMemcpyHostToDevice, up));
         h->st.pinned_inputs += pinned ? 1 : 0;
     } else {
-        if (!s->h_src) HIPCHK(hipHostMalloc((void **)&s->h_src, h->scaling ? (size_t)ds * ht * 3 / 2 : h->ysz + h->csz, hipHostMallocDefault));
+        if (!s->h_src) HIPCHK(hipHostMalloc((void **)&s->h_src, (h->scaling || h->orient) ? (size_t)ds * ht * 3 / 2 : h->ysz + h->csz, hipHostMallocDefault));
         // rows at the coded stride, so that a range of rows is one contiguous transfer; in pieces (luma thirds or sixths, the chroma plane in one or two), each
         // sent as soon as it is staged: the transfer of one piece runs beside the staging of the next, and with the helper threads three pieces are
         // staged side by side (a single thread copies 3.1 MB in 0.15-0.2 ms, as long as the device needs for the whole picture)
@@ -581,8 +587,9 @@ int mi355enc_submit(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t
         } else
             for (int i = 0; i < nj; i++) if (stage_piece(h, jobs[i], up)) return MI355ENC_ERR_HIP;
     }
-    if (h->scaling) { if (k_launch_scale(MI355ENC_FMT_NV12, dev_y, dev_uv, nullptr, ds, ds, 0, s->d_src_y, s->d_src_uv, h->W, h->H, &h->scale, up)) return MI355ENC_ERR_ARG; }
-    else if (w != h->W) k_launch_pad(s->d_src_y, s->d_src_uv, h->W, w, ht, h->W, h->H, up);
+    if (h->scaling) { if (k_launch_scale(MI355ENC_FMT_NV12, dev_y, dev_uv, nullptr, ds, ds, 0, t.y, t.uv, t.W, t.H, &h->scale, up)) return MI355ENC_ERR_ARG; }
+    else if (!h->orient && w != h->W) k_launch_pad(s->d_src_y, s->d_src_uv, h->W, w, ht, h->W, h->H, up); // (the orientation launch writes the margin itself)
+    { int r = input_finish(h, s, up); if (r) return r; }
     { int r = overlay_draw(h, s, up); if (r) return r; }
     { int r = upload_done(h, s); if (r) return r; }
     return enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
@@ -626,15 +633,24 @@ int mi355enc_submit_device(mi355enc_t *h, const void *d_y, int y_stride, const v
     slot_t *s = &h->slot[h->head];
     overlay_latch(h, s);
     if (h->scaling) { // scaled from where the planes lie into the slot's staging surfaces
-        if (k_launch_scale(MI355ENC_FMT_NV12, (const uint8_t *)d_y, (const uint8_t *)d_uv, nullptr, y_stride, uv_stride, 0, s->d_src_y, s->d_src_uv, h->W, h->H, &h->scale,
+        in_target_t t;
+        { int r = input_target(h, s, &t); if (r) return r; }
+        if (k_launch_scale(MI355ENC_FMT_NV12, (const uint8_t *)d_y, (const uint8_t *)d_uv, nullptr, y_stride, uv_stride, 0, t.y, t.uv, t.W, t.H, &h->scale,
                            upload_stream(h))) return MI355ENC_ERR_ARG;
         HIPCHK(hipGetLastError());
+        { int r = input_finish(h, s, upload_stream(h)); if (r) return r; }
         { int r = overlay_draw(h, s, upload_stream(h)); if (r) return r; }
         { int r = upload_done(h, s); if (r) return r; }
         return enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
     }
-    const int w = h->cfg.width, ht = h->cfg.height;
     hipStream_t up = upload_stream(h);
+    if (h->orient) { // oriented from where the planes lie, at their stride and address, into the slot's staging surfaces: never in place, the caller's planes are only read
+        { int r = input_finish(h, s, up, (const uint8_t *)d_y, y_stride, (const uint8_t *)d_uv, uv_stride); if (r) return r; }
+        { int r = overlay_draw(h, s, up); if (r) return r; }
+        { int r = upload_done(h, s); if (r) return r; }
+        return enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
+    }
+    const int w = h->cfg.width, ht = h->cfg.height;
     // in place -- unless a text is to be drawn: that goes into the encoder's own surfaces, never into the caller's planes
     const bool direct = !s->ov_len && w == h->W && y_stride == uv_stride && (y_stride & 15) == 0 && (((uintptr_t)d_y | (uintptr_t)d_uv) & 15) == 0;
     if (direct) return enqueue_picture(h, s, (const uint8_t *)d_y, (const uint8_t *)d_uv, y_stride, pts, force_idr);

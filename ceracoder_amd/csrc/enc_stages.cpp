@@ -219,7 +219,7 @@ int mi355enc_debug_trip_wait(mi355enc_t *h, unsigned code) {
     return MI355ENC_OK;
 }
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
-    if (!h || !avg_ms || iters < 1 || stage < 0 || stage > 12) return MI355ENC_ERR_ARG;
+    if (!h || !avg_ms || iters < 1 || stage < 0 || stage > 13) return MI355ENC_ERR_ARG;
     if (h->pending) return MI355ENC_ERR_STATE;
     HIPCHK(hipSetDevice(h->cfg.device_id));
     slot_t *s = &h->slot[0];
@@ -235,7 +235,7 @@ int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
         stage_touched(h);
     }
     if (stage == 11) { int r = quality_alloc(h); if (r) return r; } // (the block of the stage entry points)
-    if (stage >= 5 && stage <= 7 && !s->d_raw) { // input conversion (5 I420, 6 YUY2, 7 UYVY): any bytes will do as a source
+    if (((stage >= 5 && stage <= 7) || stage == 13) && !s->d_raw) { // input conversion (5 I420, 6 YUY2, 7 UYVY), orientation (13): any bytes will do as a source
         HIPCHK(hipMalloc((void **)&s->d_raw, raw_bytes(h)));
         HIPCHK(hipMemsetAsync(s->d_raw, 0x55, raw_bytes(h), h->stream));
     }
@@ -252,6 +252,11 @@ int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
             else if (stage == 11) k_launch_quality(s->d_src_y, s->d_src_uv, h->W, h->d_rec_y[1], h->d_rec_uv[1], h->W, h->cfg.width, h->cfg.height, h->d_qacc + (size_t)NSLOT * QUALITY_ACC_WORDS,
                                                    h->h_qres + (size_t)NSLOT * QUALITY_WORDS, h->stream);
             else if (stage == 12) { int r = jpeg_time_launch(h, s); if (r) return r; }
+            else if (stage == 13) { // an NV12 picture of the pre-orientation size in the raw staging buffer -> the coded surfaces
+                const int m = h->orient ? h->orient : MI355ENC_ORIENT_90R, pw = orient_transposes(m) ? h->cfg.height : h->cfg.width, ph = orient_transposes(m) ? h->cfg.width : h->cfg.height;
+                const int ps = (pw + 15) & ~15;
+                if (k_launch_orient(m, s->d_raw, ps, s->d_raw + (size_t)ps * ph, ps, pw, ph, s->d_src_y, s->d_src_uv, h->W, h->H, h->stream)) return MI355ENC_ERR_ARG;
+            }
             else if (stage == 10) k_launch_intra_p(h->slot[0].h_ctx, h->mbw, h->mbh, h->d_ip_progress, h->d_ip_strips, err_word(h), h->stream);
             else if (stage >= 5) {
                 const int w = h->cfg.width, ht = h->cfg.height, r0 = stage == 5 ? (w + 15) & ~15 : (2 * w + 15) & ~15, r1 = (w / 2 + 15) & ~15;

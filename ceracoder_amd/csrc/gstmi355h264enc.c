@@ -63,6 +63,9 @@ typedef struct {
      * custom event of an `mi355textoverlay` element upstream; stored here (object lock) and forwarded to the open encoder, which latches it per picture */
     gchar ov_text[MI355ENC_OVERLAY_MAX_TEXT + 1];
     mi355enc_overlay_style_t ov_style;
+    /* orientation on the device (mi355enc_set_orientation): the video-direction property (GstVideoOrientationMethod, AUTO follows the
+     * upstream image-orientation tag), what the last such tag said, and the method the open encoder was opened with (a change reopens it at the next picture) */
+    gint direction, tag_direction, open_direction;
     gint out_w, out_h;        /* coded size (mpph265enc's width / height): 0 = the input's; smaller: scaled down on the device (mi355enc_set_input_size) */
     /* streaming state */
     mi355enc_t *enc;
@@ -77,11 +80,11 @@ typedef struct { GstVideoEncoderClass parent_class; } GstMi355H264EncClass;
 
 #define GST_TYPE_MI355H264ENC (gst_mi355h264enc_get_type())
 #define GST_MI355H264ENC(o) (G_TYPE_CHECK_INSTANCE_CAST((o), GST_TYPE_MI355H264ENC, GstMi355H264Enc))
-G_DEFINE_TYPE(GstMi355H264Enc, gst_mi355h264enc, GST_TYPE_VIDEO_ENCODER)
+G_DEFINE_TYPE_WITH_CODE(GstMi355H264Enc, gst_mi355h264enc, GST_TYPE_VIDEO_ENCODER, G_IMPLEMENT_INTERFACE(GST_TYPE_VIDEO_DIRECTION, NULL))
 
 enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME_RANGE, PROP_QP, PROP_PIPELINE_DEPTH,
        PROP_SPEED_PRESET, PROP_STATS, PROP_DCT8X8, PROP_THREADS, PROP_SCENECUT, PROP_VBV, PROP_INTRA_IN_P, PROP_EXCLUSIVE, PROP_PINNED_INPUT, PROP_AQ_MODE, PROP_SINGLE_STREAM, PROP_INTRA_SLICES, PROP_I8X8, PROP_SLICES, PROP_SLICE_DEBLOCK, PROP_DCT8X8_ADAPTIVE, PROP_INTRA_REFRESH, PROP_WIDTH, PROP_HEIGHT, PROP_QUALITY_STATS,
-       PROP_OV_TEXT, PROP_OV_HALIGN, PROP_OV_VALIGN, PROP_OV_XPAD, PROP_OV_YPAD, PROP_OV_SCALE, PROP_OV_SHADED };
+       PROP_OV_TEXT, PROP_OV_HALIGN, PROP_OV_VALIGN, PROP_OV_XPAD, PROP_OV_YPAD, PROP_OV_SCALE, PROP_OV_SHADED, PROP_VIDEO_DIRECTION };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
     GST_STATIC_CAPS("video/x-raw, format=(string){ NV12, I420, YUY2, UYVY, Y42B, Y444, YV12, NV21, BGRx, RGBx, xRGB, xBGR, BGRA, RGBA, ARGB, ABGR, BGR, RGB }, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]; "
@@ -183,6 +186,7 @@ static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *
     case PROP_DCT8X8_ADAPTIVE: s->dct8x8_adaptive = g_value_get_boolean(val); break;
     case PROP_INTRA_REFRESH: s->intra_refresh = g_value_get_boolean(val); break;
     case PROP_QUALITY_STATS: s->quality_stats = g_value_get_boolean(val); break;
+    case PROP_VIDEO_DIRECTION: { const gint d = g_value_get_enum(val); s->direction = d >= 0 && d <= GST_VIDEO_ORIENTATION_AUTO ? d : 0; break; } /* (CUSTOM: nothing here to be custom about) */
     case PROP_WIDTH: s->out_w = g_value_get_int(val); break;
     case PROP_HEIGHT: s->out_h = g_value_get_int(val); break;
     case PROP_THREADS: s->threads = g_value_get_int(val); break;
@@ -227,6 +231,7 @@ static void get_property(GObject *obj, guint id, GValue *val, GParamSpec *ps) {
     case PROP_DCT8X8_ADAPTIVE: g_value_set_boolean(val, s->dct8x8_adaptive); break;
     case PROP_INTRA_REFRESH: g_value_set_boolean(val, s->intra_refresh); break;
     case PROP_QUALITY_STATS: g_value_set_boolean(val, s->quality_stats); break;
+    case PROP_VIDEO_DIRECTION: g_value_set_enum(val, s->direction); break;
     case PROP_WIDTH: g_value_set_int(val, s->out_w); break;
     case PROP_HEIGHT: g_value_set_int(val, s->out_h); break;
     case PROP_THREADS: g_value_set_int(val, s->threads); break;
@@ -336,6 +341,29 @@ static void colorimetry_codes(const GstVideoColorimetry *c, int *full, int *prim
     }
 }
 
+/* video-direction: the method in force (object lock held) -- the property, or with AUTO what the last image-orientation tag said */
+static int effective_direction(GstMi355H264Enc *s) { return s->direction == GST_VIDEO_ORIENTATION_AUTO ? s->tag_direction : s->direction; }
+static gboolean direction_transposes(int d) { return d == GST_VIDEO_ORIENTATION_90R || d == GST_VIDEO_ORIENTATION_90L || d == GST_VIDEO_ORIENTATION_UL_LR || d == GST_VIDEO_ORIENTATION_UR_LL; }
+/* image-orientation tag -> direction (the table of gst_video_orientation_from_tag, which GStreamer has from 1.20 on); FALSE: no such tag, or a value outside the table */
+static gboolean direction_from_tag(GstTagList *tl, int *dir) {
+#if GST_CHECK_VERSION(1, 20, 0)
+    GstVideoOrientationMethod m;
+    if (!gst_video_orientation_from_tag(tl, &m)) return FALSE;
+    *dir = (int)m;
+    return TRUE;
+#else
+    static const struct { const char *tag; int dir; } tab[] = {{"rotate-0", GST_VIDEO_ORIENTATION_IDENTITY}, {"rotate-90", GST_VIDEO_ORIENTATION_90R}, {"rotate-180", GST_VIDEO_ORIENTATION_180},
+        {"rotate-270", GST_VIDEO_ORIENTATION_90L}, {"flip-rotate-0", GST_VIDEO_ORIENTATION_HORIZ}, {"flip-rotate-90", GST_VIDEO_ORIENTATION_UR_LL},
+        {"flip-rotate-180", GST_VIDEO_ORIENTATION_VERT}, {"flip-rotate-270", GST_VIDEO_ORIENTATION_UL_LR}};
+    gchar *v = NULL;
+    gboolean ok = FALSE;
+    if (!gst_tag_list_get_string(tl, GST_TAG_IMAGE_ORIENTATION, &v) || !v) return FALSE;
+    for (guint i = 0; i < G_N_ELEMENTS(tab); i++) if (!g_ascii_strcasecmp(v, tab[i].tag)) { *dir = tab[i].dir; ok = TRUE; }
+    g_free(v);
+    return ok;
+#endif
+}
+
 static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     GstMi355H264Enc *s = GST_MI355H264ENC(ve);
     GstVideoInfo *vi = &state->info;
@@ -354,8 +382,12 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
         return FALSE;
     }
     GST_OBJECT_LOCK(s);
-    const int out_w = s->out_w > 0 ? s->out_w : in_w, out_h = s->out_h > 0 ? s->out_h : in_h; /* (0: the input's size) */
+    const int dir = effective_direction(s);
+    const gboolean tr = direction_transposes(dir);
+    /* width / height mean the coded, i.e. oriented, size; 0: the oriented input's.  What the input is scaled to is that size turned back */
+    const int out_w = s->out_w > 0 ? s->out_w : (tr ? in_h : in_w), out_h = s->out_h > 0 ? s->out_h : (tr ? in_w : in_h);
     GST_OBJECT_UNLOCK(s);
+    const int pre_w = tr ? out_h : out_w, pre_h = tr ? out_w : out_h;
     mi355enc_default_cfg(&cfg, out_w, out_h, fn, fd);
     GST_OBJECT_LOCK(s);
     cfg.gop = s->key_int_max ? (int)s->key_int_max : 250;
@@ -385,7 +417,8 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
         } else if (GST_VIDEO_INFO_IS_RGB(vi)) full = 0;
         r = mi355enc_set_colorimetry(e, full, prim, trc, mat);
     }
-    if (r == MI355ENC_OK && (in_w != out_w || in_h != out_h)) r = mi355enc_set_input_size(e, in_w, in_h); /* (refused: upscaling, a ratio above 8, odd sizes) */
+    if (r == MI355ENC_OK && dir != 0) r = mi355enc_set_orientation(e, dir); /* (first: the input size is then checked against the pre-orientation target) */
+    if (r == MI355ENC_OK && (in_w != pre_w || in_h != pre_h)) r = mi355enc_set_input_size(e, in_w, in_h); /* (refused: upscaling, a ratio above 8, odd sizes) */
     if (r == MI355ENC_OK && quality_stats) r = mi355enc_set_quality_metrics(e, 1);
     if (r != MI355ENC_OK) {
         if (e) mi355enc_close(e);
@@ -396,6 +429,7 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     GST_OBJECT_LOCK(s);
     s->enc = e;
     s->open_depth = cfg.pipeline_depth;
+    s->open_direction = dir;
     s->jpeg = jpeg; s->jpeg_refused = 0;
     mi355enc_set_bitrate(e, target_bps(s)); /* a write that raced with open() must not be lost */
     overlay_forward(s);                     /* ... nor the overlay's text and style, set before the device was opened */
@@ -414,11 +448,12 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     GstCaps *caps = gst_caps_new_simple("video/x-h264", "stream-format", G_TYPE_STRING, "byte-stream", "alignment", G_TYPE_STRING, "au",
                                         "profile", G_TYPE_STRING, cfg.transform8x8 ? "high" : "constrained-baseline", NULL);
     GstVideoCodecState *out = gst_video_encoder_set_output_state(ve, caps, state);
-    if (in_w != out_w || in_h != out_h) { /* the coded size; a scale that changes the aspect ratio changes the samples' (the SPS VUI carries the same) */
+    if (in_w != out_w || in_h != out_h || tr) { /* the coded size; a scale that changes the aspect ratio changes the samples' (the SPS VUI carries the same), and a
+                                                   transposing direction exchanges the size and the two terms of the pixel-aspect-ratio */
         out->info.width = out_w; out->info.height = out_h;
         gint pn = 1, pd = 1;
-        gst_util_fraction_multiply(GST_VIDEO_INFO_PAR_N(vi), GST_VIDEO_INFO_PAR_D(vi), in_w * out_h, in_h * out_w, &pn, &pd);
-        out->info.par_n = pn; out->info.par_d = pd;
+        gst_util_fraction_multiply(GST_VIDEO_INFO_PAR_N(vi), GST_VIDEO_INFO_PAR_D(vi), in_w * pre_h, in_h * pre_w, &pn, &pd);
+        out->info.par_n = tr ? pd : pn; out->info.par_d = tr ? pn : pd;
     }
     gst_video_codec_state_unref(out);
     if (cfg.pipeline_depth > 0) {
@@ -467,6 +502,15 @@ static GstFlowReturn enc_handle_frame(GstVideoEncoder *ve, GstVideoCodecFrame *f
     GstMi355H264Enc *s = GST_MI355H264ENC(ve);
     GstVideoFrame vf;
     if (!s->enc || !s->input_state) { gst_video_encoder_finish_frame(ve, frame); return GST_FLOW_NOT_NEGOTIATED; }
+    GST_OBJECT_LOCK(s);
+    const gboolean turn = effective_direction(s) != s->open_direction;
+    GST_OBJECT_UNLOCK(s);
+    if (turn) { /* the direction changed while running (property or tag): exactly what a caps change does -- drain, reopen (this picture is an IDR picture), renegotiate the source caps */
+        GstVideoCodecState *st = gst_video_codec_state_ref(s->input_state);
+        const gboolean ok = enc_set_format(ve, st);
+        gst_video_codec_state_unref(st);
+        if (!ok) { gst_video_encoder_finish_frame(ve, frame); return GST_FLOW_NOT_NEGOTIATED; }
+    }
     if (GST_BUFFER_FLAG_IS_SET(frame->input_buffer, GST_BUFFER_FLAG_DROPPABLE)) {
         /* what `identity name=ptsfixup` does to a picture that arrived too early to get a slot on its PTS grid (ceracoder.c:414-419:
          * "dropping an input buffer"): it keeps its raw, non-monotone PTS.  Not coded, no output buffer. */
@@ -584,7 +628,7 @@ static void gst_mi355_pin_allocator_init(GstMi355PinAllocator *a) { GST_OBJECT_F
 static GstCaps *enc_getcaps(GstVideoEncoder *ve, GstCaps *filter) {
     GstMi355H264Enc *s = GST_MI355H264ENC(ve);
     GST_OBJECT_LOCK(s);
-    const gboolean scaled = s->out_w > 0 || s->out_h > 0;
+    const gboolean scaled = s->out_w > 0 || s->out_h > 0 || s->direction != GST_VIDEO_ORIENTATION_IDENTITY; /* (a direction may exchange the size: the pads' sizes are decoupled as well) */
     GST_OBJECT_UNLOCK(s);
     if (!scaled) return gst_video_encoder_proxy_getcaps(ve, NULL, filter);
     GstCaps *t = gst_pad_get_pad_template_caps(GST_VIDEO_ENCODER_SINK_PAD(ve));
@@ -634,6 +678,24 @@ static gboolean enc_sink_event(GstVideoEncoder *ve, GstEvent *ev) {
         GST_OBJECT_UNLOCK(s);
         gst_event_unref(ev);
         return TRUE;
+    }
+    if (GST_EVENT_TYPE(ev) == GST_EVENT_TAG) { /* video-direction=auto follows the upstream image-orientation tag; the picture leaves upright, so the tag ends here */
+        GstTagList *tl = NULL;
+        int dir = 0;
+        gst_event_parse_tag(ev, &tl);
+        if (tl && direction_from_tag(tl, &dir)) {
+            GST_OBJECT_LOCK(s);
+            s->tag_direction = dir;
+            const gboolean follow = s->direction == GST_VIDEO_ORIENTATION_AUTO;
+            GST_OBJECT_UNLOCK(s);
+            if (follow) {
+                GstTagList *rest = gst_tag_list_copy(tl);
+                gst_tag_list_remove_tag(rest, GST_TAG_IMAGE_ORIENTATION);
+                gst_event_unref(ev);
+                if (gst_tag_list_is_empty(rest)) { gst_tag_list_unref(rest); return TRUE; }
+                ev = gst_event_new_tag(rest);
+            }
+        }
     }
     return GST_VIDEO_ENCODER_CLASS(gst_mi355h264enc_parent_class)->sink_event(ve, ev);
 }
@@ -713,6 +775,7 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
     g_object_class_install_property(g, PROP_OV_YPAD, g_param_spec_int("overlay-ypad", "Overlay vertical padding", "Luma samples between the text box and the top / bottom picture edge", 0, 8192, 16, F));
     g_object_class_install_property(g, PROP_OV_SCALE, g_param_spec_int("overlay-scale", "Overlay scale", "Luma samples per font pixel, 1..8; 0: height / 540, at least 1 (720p 1, 1080p 2, 2160p 4)", 0, 8, 0, F));
     g_object_class_install_property(g, PROP_OV_SHADED, g_param_spec_boolean("overlay-shaded-background", "Overlay shaded background", "Darken the text box", FALSE, F));
+    g_object_class_override_property(g, PROP_VIDEO_DIRECTION, "video-direction"); /* GstVideoDirection: identity, 90r, 180, 90l, horiz, vert, ul-lr, ur-ll, auto -- as on videoflip */
     g_object_class_install_property(g, PROP_STATS, g_param_spec_boolean("stats", "Print stats", "Print a JSON line with counters when the encoder closes", FALSE, F));
     gst_element_class_add_static_pad_template(e, &sink_tmpl);
     gst_element_class_add_static_pad_template(e, &src_tmpl);
@@ -726,6 +789,7 @@ static void gst_mi355h264enc_init(GstMi355H264Enc *s) {
     s->stats = FALSE; s->dct8x8 = -1; s->threads = 0; s->scenecut = TRUE; s->exclusive_gpu = FALSE; s->vbv_ms = 600; s->intra_in_p = -1; s->pinned_input = TRUE; s->aq_mode = -1; s->slices = -1; s->slice_deblock = -1; s->intra_slices = 0; s->i8x8 = -1; s->single_stream = FALSE; s->dct8x8_adaptive = FALSE; s->intra_refresh = FALSE; s->quality_stats = FALSE; s->enc = NULL; s->input_state = NULL; s->max_au = 0; s->au_buf = NULL; s->last_pts = GST_CLOCK_TIME_NONE;
     s->us_map = s->us_submit = s->us_collect = s->us_output = s->us_push = s->us_frames = 0;
     s->ov_text[0] = 0; mi355enc_overlay_default_style(&s->ov_style);
+    s->direction = s->tag_direction = s->open_direction = GST_VIDEO_ORIENTATION_IDENTITY;
 }
 
 GType gst_mi355tsmux_get_type(void); /* gstmi355tsmux.c */

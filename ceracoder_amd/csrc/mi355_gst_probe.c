@@ -23,7 +23,11 @@
  * With --props the description is parsed, the coding-tool properties of the encoder element (named venc_bps or venc_kbps) are printed as they will be used --
  * an explicit property, else what speed-preset selects -- and nothing runs (no device needed).
  *
- * usage: mi355_gst_probe "PIPELINE DESCRIPTION" [--no-encoder | --appsrc N W H [pinned] | --props]
+ * With --dump FILE every sample is written to FILE as a record {u32 length, u32 width, u32 height of the sample's caps, bytes}: tests compare access units and
+ * the source caps' size.  --tag VALUE sends an image-orientation tag event with VALUE into the encoder's sink pad in front of the first buffer; --set K PROP VALUE
+ * sets the encoder's property PROP to VALUE (as gst-launch would parse it) in front of buffer K (counted from 0), on the streaming thread.
+ *
+ * usage: mi355_gst_probe "PIPELINE DESCRIPTION" [--no-encoder | --appsrc N W H [pinned] | --props] [--dump FILE] [--tag VALUE] [--set K PROP VALUE]
  */
 #include <arpa/inet.h>
 #include <gst/app/gstappsink.h>
@@ -56,11 +60,19 @@ static int tx = -1, rx = -1, exit_code;
 static struct sockaddr_in dst;
 static unsigned char pkt[PKT];
 static int pkt_len;
+static FILE *dump;                       /* --dump */
+static const char *tag_value;            /* --tag */
+static int set_at = -1, n_in;            /* --set K PROP VALUE; buffers seen at the encoder's sink pad */
+static const char *set_prop, *set_value;
+static GstElement *the_enc;
 
 static GstPadProbeReturn on_enc_sink(GstPad *pad, GstPadProbeInfo *info, gpointer u) {
     (void)pad; (void)u;
     GstBuffer *b = GST_PAD_PROBE_INFO_BUFFER(info);
     if (b) {
+        if (n_in == 0 && tag_value) gst_pad_send_event(pad, gst_event_new_tag(gst_tag_list_new(GST_TAG_IMAGE_ORIENTATION, tag_value, NULL))); /* (streaming thread: in front of this buffer) */
+        if (n_in == set_at && the_enc) gst_util_set_object_arg(G_OBJECT(the_enc), set_prop, set_value);
+        n_in++;
         g_mutex_lock(&lock);
         ring[head % RING].pts = GST_BUFFER_PTS(b); ring[head % RING].t0 = g_get_monotonic_time(); head++;
         g_mutex_unlock(&lock);
@@ -87,6 +99,13 @@ static GstFlowReturn on_sample(GstAppSink *sink, gpointer u) {
     GstBuffer *b = gst_sample_get_buffer(s);
     GstMapInfo m;
     if (gst_buffer_map(b, &m, GST_MAP_READ)) {
+        if (dump) {
+            gint cw = 0, ch = 0;
+            GstCaps *c = gst_sample_get_caps(s);
+            if (c) { const GstStructure *st = gst_caps_get_structure(c, 0); gst_structure_get_int(st, "width", &cw); gst_structure_get_int(st, "height", &ch); }
+            const guint32 hdr[3] = {(guint32)m.size, (guint32)cw, (guint32)ch};
+            fwrite(hdr, sizeof hdr, 1, dump); fwrite(m.data, 1, m.size, dump);
+        }
         send_regrouped(m.data, m.size);
         const gint64 t2 = g_get_monotonic_time();
         const guint64 pts = GST_BUFFER_PTS(b);
@@ -179,6 +198,9 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--appsrc") && i + 3 < argc) { use_appsrc = 1; ai = i; i += 3; }
         else if (!strcmp(argv[i], "pinned")) pinned = 1;
         else if (!strcmp(argv[i], "--clip") && i + 1 < argc) feed.clip = argv[++i];
+        else if (!strcmp(argv[i], "--dump") && i + 1 < argc) { dump = fopen(argv[++i], "wb"); if (!dump) { fprintf(stderr, "cannot write %s\n", argv[i]); return 2; } }
+        else if (!strcmp(argv[i], "--tag") && i + 1 < argc) tag_value = argv[++i];
+        else if (!strcmp(argv[i], "--set") && i + 3 < argc) { set_at = atoi(argv[i + 1]); set_prop = argv[i + 2]; set_value = argv[i + 3]; i += 3; }
     }
     if (use_appsrc) {
         feed.src = gst_bin_get_by_name(GST_BIN(pipe), "src");
@@ -209,6 +231,7 @@ int main(int argc, char **argv) {
         g_object_set(feed.src, "format", GST_FORMAT_TIME, NULL);
     }
     if ((!enc && !no_enc) || !sink) { fprintf(stderr, "the description needs elements named venc_bps and appsink\n"); return 2; }
+    the_enc = enc;
     if (enc) {
         GstPad *sp = gst_element_get_static_pad(enc, "sink");
         gst_pad_add_probe(sp, GST_PAD_PROBE_TYPE_BUFFER, on_enc_sink, NULL, NULL);
@@ -232,6 +255,7 @@ int main(int argc, char **argv) {
     if (ft && exit_code == 0) g_thread_join(ft);
     const double secs = (g_get_monotonic_time() - t_start) / 1e6;
     gst_element_set_state(pipe, GST_STATE_NULL);
+    if (dump) fclose(dump);
     printf("{\"samples\":%" G_GUINT64_FORMAT ",\"bytes\":%" G_GUINT64_FORMAT ",\"seconds\":%.3f,\"datagrams_1316\":%" G_GUINT64_FORMAT, n_samples, n_bytes, secs, n_dgrams);
     {
         const guint64 n = n_samples < MAXN ? n_samples : MAXN;

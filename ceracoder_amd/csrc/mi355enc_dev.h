@@ -214,6 +214,10 @@ void k_launch_overlay(const overlay_args_t *a, hipStream_t s);
  * visible row, column and chroma pair).  d_planar: scratch of 3 * ((vw + 15) & ~15) * vh bytes, read and written for 4:4:4 only.  -1: not a sampling it takes. */
 int k_launch_jpeg(const int16_t *d_coef, const uint16_t *d_qt, int hs, int vs, int comps, int vw, int vh, uint8_t *dy, uint8_t *duv, int W, int H,
                   uint8_t *d_planar, hipStream_t s);
+/* Orientation of the input picture (k_orient.hip; the rule: DESIGN.md section 15): NV12 planes of the pre-orientation visible size in_w x in_h (even), at any
+ * address and stride, by method 1 .. 7 (MI355ENC_ORIENT_*) into NV12 surfaces of stride W and coded size W x H of the oriented picture, margin included.
+ * -1: not such a method, or sizes that do not fit each other. */
+int k_launch_orient(int method, const uint8_t *sy, int ssy, const uint8_t *suv, int ssuv, int in_w, int in_h, uint8_t *dy, uint8_t *duv, int W, int H, hipStream_t s);
 void k_launch_quality(const uint8_t *src_y, const uint8_t *src_uv, int src_stride, const uint8_t *rec_y, const uint8_t *rec_uv, int rec_stride,
                       int width, int height, unsigned long long *d_acc, unsigned long long *out, hipStream_t s);
 #endif

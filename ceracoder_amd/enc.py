@@ -29,7 +29,10 @@ IDEC = np.dtype([("modes4", "u1", (16,)), ("mode16", "u1"), ("cmode", "u1"), ("u
 IMV_DTYPE = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("sad", "<u2"), ("bits", "<u2")])
 SURF_ROWS, SURF_COLS = 35, 36
 DROP_MAX, DROP_SKIP = 12, 255
-STAGE_ME, STAGE_INTER, STAGE_INTRA, STAGE_DEBLOCK, STAGE_SUBPEL, STAGE_CSC_I420, STAGE_CSC_YUY2, STAGE_CSC_UYVY, STAGE_ME_SELECT, STAGE_PMB, STAGE_INTRA_P, STAGE_QUALITY, STAGE_JPEG = range(13)
+STAGE_ME, STAGE_INTER, STAGE_INTRA, STAGE_DEBLOCK, STAGE_SUBPEL, STAGE_CSC_I420, STAGE_CSC_YUY2, STAGE_CSC_UYVY, STAGE_ME_SELECT, STAGE_PMB, STAGE_INTRA_P, STAGE_QUALITY, STAGE_JPEG, STAGE_ORIENT = range(14)
+# mi355enc_set_orientation: GstVideoOrientationMethod's numbers
+ORIENT_IDENTITY, ORIENT_90R, ORIENT_180, ORIENT_90L, ORIENT_HORIZ, ORIENT_VERT, ORIENT_UL_LR, ORIENT_UR_LL = range(8)
+ORIENT_NAMES = ("identity", "90r", "180", "90l", "horiz", "vert", "ul-lr", "ur-ll")
 
 EXPORTS = [
     "mi355enc_abi_version", "mi355enc_strerror", "mi355enc_default_cfg", "mi355enc_open", "mi355enc_close",
@@ -44,6 +47,8 @@ EXPORTS = [
     "mi355enc_set_quality_metrics", "mi355enc_last_quality", "mi355enc_quality_totals", "mi355enc_stage_quality", "mi355enc_stage_quality_device",
     "mi355enc_overlay_default_style", "mi355enc_set_overlay_style", "mi355enc_set_overlay_text", "mi355enc_last_overlay", "mi355enc_overlay_glyph", "mi355enc_stage_overlay",
     "mi355enc_jpeg_info", "mi355enc_jpeg_entropy_decode", "mi355enc_submit_jpeg", "mi355enc_stage_jpeg", "mi355enc_stage_jpeg_blocks",
+    "mi355enc_set_orientation", "mi355enc_get_orientation", "mi355enc_orient_size", "mi355enc_orient_source", "mi355enc_stage_orient", "mi355enc_stage_orient_device",
+    "mi355enc_debug_orient_bytes",
 ]
 
 
@@ -157,6 +162,14 @@ def load():
         L.mi355enc_submit_jpeg.argtypes = [vp, vp, C.c_size_t, C.c_int64, C.c_int]
         L.mi355enc_stage_jpeg.argtypes = [vp, vp, C.c_size_t, vp, vp]
         L.mi355enc_stage_jpeg_blocks.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+        L.mi355enc_set_orientation.argtypes = [vp, C.c_int]
+        L.mi355enc_get_orientation.argtypes = [vp]
+        L.mi355enc_orient_size.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.mi355enc_orient_source.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.mi355enc_stage_orient.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]
+        L.mi355enc_stage_orient_device.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]
+        L.mi355enc_debug_orient_bytes.restype = C.c_size_t
+        L.mi355enc_debug_orient_bytes.argtypes = [vp]
         L.mi355enc_host_alloc.restype = vp
         L.mi355enc_host_alloc.argtypes = [C.c_size_t]
         L.mi355enc_host_free.restype = None
@@ -268,6 +281,29 @@ def scale_table(n_in, n_out, kind):
     if r != n:
         raise EncoderError("mi355enc_scale_table: %d" % r)
     return first, coef
+
+
+def orient_method(m):
+    """a method as its number: 0 .. 7, or one of ORIENT_NAMES"""
+    return ORIENT_NAMES.index(m) if isinstance(m, str) else int(m)
+
+
+def orient_size(method, in_w, in_h):
+    """(w, h) of a picture of in_w x in_h after orientation (host only)"""
+    w, h = C.c_int(0), C.c_int(0)
+    r = load().mi355enc_orient_size(orient_method(method), int(in_w), int(in_h), C.byref(w), C.byref(h))
+    if r != 0:
+        raise EncoderError("mi355enc_orient_size: %d" % r)
+    return w.value, h.value
+
+
+def orient_source(method, out_w, out_h, x, y):
+    """(sx, sy): the input sample that output sample (x, y) of an oriented out_w x out_h picture comes from (host only)"""
+    sx, sy = C.c_int(0), C.c_int(0)
+    r = load().mi355enc_orient_source(orient_method(method), int(out_w), int(out_h), int(x), int(y), C.byref(sx), C.byref(sy))
+    if r != 0:
+        raise EncoderError("mi355enc_orient_source: %d" % r)
+    return sx.value, sy.value
 
 
 def jpeg_info(data):
@@ -395,7 +431,7 @@ class Encoder:
     (bitrate in bits/s as written through `bps`, key-int-max -> gop)."""
 
     def __init__(self, width, height, fps=60, gop=60, bitrate_bps=6_000_000, device_id=0, fixed_qp=-1, me_range=16,
-                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False, input_size=None, colorimetry=None):
+                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False, input_size=None, colorimetry=None, orientation=None):
         self.L = load()
         cfg = Cfg()
         self.L.mi355enc_default_cfg(C.byref(cfg), width, height, fps, fps_den)
@@ -439,9 +475,16 @@ class Encoder:
         if colorimetry is not None:  # (full_range, primaries, transfer, matrix): the VUI of every SPS, and the matrix RGB input is converted with
             self._chk(self.L.mi355enc_set_colorimetry(self.h, *[int(v) for v in colorimetry]), "set_colorimetry", close_on_fail=True)
         self.input_size = (width, height)
+        self.orientation, self._in_set = ORIENT_IDENTITY, False
+        if orientation is not None:  # 0 .. 7 or a name of ORIENT_NAMES: the pictures submitted are turned / mirrored on the device; width x height is the oriented size
+            try:
+                self.set_orientation(orientation)
+            except EncoderError:
+                self.close()
+                raise
         if input_size is not None:  # (w, h) of the submitted pictures: scaled down on the device to width x height
             self._chk(self.L.mi355enc_set_input_size(self.h, int(input_size[0]), int(input_size[1])), "set_input_size", close_on_fail=True)
-            self.input_size = (int(input_size[0]), int(input_size[1]))
+            self.input_size, self._in_set = (int(input_size[0]), int(input_size[1])), True
 
     def _chk(self, r, what, close_on_fail=False):
         if r != 0:
@@ -538,7 +581,38 @@ class Encoder:
     def set_input_size(self, w, h):
         """pictures submitted from now on are w x h (before the first submit; the coded size returns to the unscaled path)"""
         self._chk(self.L.mi355enc_set_input_size(self.h, int(w), int(h)), "set_input_size")
-        self.input_size = (int(w), int(h))
+        self.input_size, self._in_set = (int(w), int(h)), True
+
+    def set_orientation(self, method):
+        """orientation of the pictures submitted from now on (before the first submit): 0 .. 7 or "identity", "90r", "180", "90l", "horiz", "vert", "ul-lr",
+        "ur-ll".  With a transposing method and no input size of its own the pictures submitted are height x width."""
+        m = orient_method(method)
+        self._chk(self.L.mi355enc_set_orientation(self.h, m), "set_orientation")
+        self.orientation = m
+        if not self._in_set:  # (it follows the method unless set_input_size gave one)
+            self.input_size = self.pre_size()
+
+    def pre_size(self):
+        """(w, h) before orientation: what decode / conversion / scaling produce, and what is submitted unless set_input_size says otherwise"""
+        return (self.height, self.width) if self.orientation in (ORIENT_90R, ORIENT_90L, ORIENT_UL_LR, ORIENT_UR_LL) else (self.width, self.height)
+
+    def get_orientation(self):
+        return self.L.mi355enc_get_orientation(self.h)
+
+    def orient_bytes(self):
+        """development: device memory held for pre-orientation pictures (0 with identity)"""
+        return int(self.L.mi355enc_debug_orient_bytes(self.h))
+
+    def stage_orient(self, method, y, uv):
+        """The orientation kernel alone: NV12 host planes of the pre-orientation size (row strides as the arrays have them) -> the coded-size surfaces."""
+        y, uv = _rows(y), _rows(uv)
+        oy, ouv = self._surfaces()
+        self._chk(self.L.mi355enc_stage_orient(self.h, orient_method(method), _p(y), y.strides[0], _p(uv), uv.strides[0], _p(oy), _p(ouv)), "stage_orient")
+        return oy, ouv
+
+    def stage_orient_device(self, method, y_ptr, y_stride, uv_ptr, uv_stride, out_y_ptr, out_uv_ptr):
+        """... on device-resident planes (addresses as ints, any alignment and stride) into device surfaces of the coded size, stride 16 mbw."""
+        self._chk(self.L.mi355enc_stage_orient_device(self.h, orient_method(method), y_ptr, int(y_stride), uv_ptr, int(uv_stride), out_y_ptr, out_uv_ptr), "stage_orient_device")
 
     def stage_scale(self, fmt, planes):
         """The scale kernel alone: planes of the input size (row strides as the arrays have them) -> the coded-size NV12 surfaces."""
@@ -553,7 +627,7 @@ class Encoder:
     def scale_tables_device(self):
         """The device's copy of the scale tables: [(first, coef)] for luma horizontal, luma vertical, chroma horizontal, chroma vertical
         from 4:2:0 and from 4:2:2 (include/mi355enc.h MI355ENC_FETCH_SCALE_TABLES)."""
-        (iw, ih), (ow, oh) = self.input_size, (self.width, self.height)
+        (iw, ih), (ow, oh) = self.input_size, self.pre_size()
         spec = [(iw, ow, SCALE_LUMA), (ih, oh, SCALE_LUMA), (iw, ow, SCALE_CHROMA_H), (ih, oh, SCALE_CHROMA_V), (ih, oh, SCALE_CHROMA_V422)]
         shapes = [scale_table(*a)[1].shape for a in spec]
         sizes = [(n * 4 + n * t * 2 + 15) // 16 * 16 for n, t in shapes]

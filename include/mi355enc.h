@@ -279,6 +279,35 @@ int mi355enc_stage_jpeg(mi355enc_t *h, const uint8_t *data, size_t len, uint8_t 
 /* ... and the kernel alone, on coefficients the caller made up: a picture of the handle's input size with luma sampling hs x vs and
  * `components` components, coef and qt laid out as mi355enc_jpeg_entropy_decode writes them */
 int mi355enc_stage_jpeg_blocks(mi355enc_t *h, int hs, int vs, int components, const int16_t *coef, const uint16_t qt[3][64], uint8_t *out_y, uint8_t *out_uv);
+
+/* ---- orientation of the input picture on the device: what `videoflip` does in front of an encoder ----
+ * The eight methods of GstVideoOrientationMethod, as a permutation of samples: luma as a plane of bytes, chroma as a plane of (Cb, Cr) pairs of half the
+ * size (a pair is never split; the half-sample shift in chroma siting that a rotation implies is ignored, as videoflip ignores it).
+ * cfg.width x cfg.height stays the coded, visible size: that of the ORIENTED picture.  With a transposing method (90r, 90l, ul-lr, ur-ll) the pictures
+ * submitted are cfg.height x cfg.width, or -- with mi355enc_set_input_size(in_w, in_h) -- in_w x in_h, scaled to cfg.height x cfg.width and then
+ * oriented; the per-axis limits of mi355enc_set_input_size hold against that pre-orientation target, and the sample aspect ratio in the SPS is the
+ * scaler's with its two terms exchanged.  A JPEG picture has the pre-orientation input size.  Orientation runs after decode / conversion / scaling and
+ * before the text overlay (the text stays upright); the quality metrics measure against the oriented source.
+ * mi355enc_set_orientation: before the first submit only (MI355ENC_ERR_STATE after it); MI355ENC_ERR_ARG outside 0 .. 7, and for a method whose
+ * pre-orientation target the input size set before does not fit (the handle stays as it was).  It may be called before or after
+ * mi355enc_set_input_size: the handle ends up the same.  Identity (the default) is today's input path, untouched. */
+enum { MI355ENC_ORIENT_IDENTITY = 0, MI355ENC_ORIENT_90R, MI355ENC_ORIENT_180, MI355ENC_ORIENT_90L,
+       MI355ENC_ORIENT_HORIZ, MI355ENC_ORIENT_VERT, MI355ENC_ORIENT_UL_LR, MI355ENC_ORIENT_UR_LL };
+int mi355enc_set_orientation(mi355enc_t *h, int method);
+int mi355enc_get_orientation(const mi355enc_t *h);
+/* host only: size of the oriented picture, and for an output sample the input sample it comes from */
+int mi355enc_orient_size(int method, int in_w, int in_h, int *out_w, int *out_h);
+int mi355enc_orient_source(int method, int out_w, int out_h, int x, int y, int *sx, int *sy);
+/* kernel alone (tests): NV12 host planes of the pre-orientation size (cfg.height x cfg.width for a transposing method, else cfg.width x cfg.height) at
+ * the given strides -> coded-size surfaces, stride 16 * mb_width.  Methods 1 .. 7; ignores the handle's own method and input size. */
+int mi355enc_stage_orient(mi355enc_t *h, int method, const uint8_t *y, int y_stride, const uint8_t *uv, int uv_stride,
+                          uint8_t *out_y, uint8_t *out_uv);
+/* ... on planes in this GPU's memory, any address and stride, into device surfaces of stride 16 * mb_width; touches nothing of the encoder's.
+ * Returns when the launch has completed. */
+int mi355enc_stage_orient_device(mi355enc_t *h, int method, const void *d_y, int y_stride, const void *d_uv, int uv_stride,
+                                 void *d_out_y, void *d_out_uv);
+/* development: bytes of device memory the handle holds for pre-orientation pictures (0 until an oriented picture is submitted; always 0 with identity) */
+size_t mi355enc_debug_orient_bytes(const mi355enc_t *h);
 int mi355enc_pending(const mi355enc_t *h);
 int mi355enc_collect(mi355enc_t *h, uint8_t *out, size_t out_cap, size_t *out_len, int *is_keyframe,
                      int64_t *pts, int *qp);
@@ -408,7 +437,8 @@ int mi355enc_stage_deblock(mi355enc_t *h, uint8_t *rec_y, uint8_t *rec_uv, const
  * stage: 0 ME, 1 inter, 2 intra (whole wavefront), 3 deblock (whole wavefront), 4 sub-sample refinement,
  * 5 / 6 / 7 input conversion from I420 / YUY2 / UYVY, 8 one vector-selection iteration, 9 fused P stage, 10 intra macroblocks of a P picture,
  * 11 the quality-metrics launch (slot 0's source surfaces against reconstruction buffer 1),
- * 12 the JPEG launch for the handle's input size as 4:2:2, on whatever slot 0's coefficient buffer holds.
+ * 12 the JPEG launch for the handle's input size as 4:2:2, on whatever slot 0's coefficient buffer holds,
+ * 13 the orientation launch at the handle's size (the handle's method; 90r on a handle without one), on whatever slot 0's raw staging buffer holds.
  * Uses whatever the handle's surfaces currently hold.  Returns average ms per launch. */
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms);
 
