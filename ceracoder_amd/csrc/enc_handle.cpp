@@ -344,7 +344,7 @@ void mi355enc_close(mi355enc_t *h) {
     if (h->d_iband_done) (void)hipFree(h->d_iband_done);
     for (int i = 0; i < 2; i++) if (h->ev_dbI[i]) (void)hipEventDestroy(h->ev_dbI[i]);
     if (h->d_off) (void)hipFree(h->d_off);
-    if (h->d_scale_tab) (void)hipFree(h->d_scale_tab);
+    scale_free(h);
     quality_free(h);
     for (int k = 0; k < NSET; k++) {
         if (h->d_surf[k]) (void)hipFree(h->d_surf[k]);

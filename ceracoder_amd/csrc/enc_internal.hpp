@@ -156,6 +156,15 @@ struct mi355enc {
     bool in_set;
     uint8_t *d_scale_tab; size_t scale_tab_bytes;
     scale_plan_t scale;
+    // the input geometry (mi355enc_set_input_geometry / mi355enc_set_crop).  d_scale_tab then holds NSLOT copies of the tables, geom_room bytes
+    // apart, one per slot: a picture in flight keeps the crop it was submitted under.  h_geom_tab (pinned): the slots' copies on their way to the device, then the
+    // current tables (what `scale` describes; its table pointers are null, geom_off says where the tables lie in a copy), then set_crop's candidate.  geom_gen counts
+    // the changes of the current tables; a slot whose geom_slot_gen differs gets them in front of its next launch (scale_plan_for).
+    bool geom_on;
+    mi355enc_geometry_t geom;
+    uint8_t *h_geom_tab; size_t geom_room, geom_bytes, geom_off[2 * SCALE_TABLES];
+    uint32_t geom_gen, geom_slot_gen[NSLOT];
+    scale_plan_t geom_plan[NSLOT];
     // colorimetry (mi355enc_set_colorimetry): what every SPS says about the samples (0, 2, 2, 2: nothing), and the RGB -> Y'CbCr matrix that follows from it
     // (csc_coef: the ten words of mi355enc_csc_coefficients; csc_ok false: the matrix code is not one RGB input can be converted with)
     int col_full, col_prim, col_trc, col_mat;
@@ -232,7 +241,10 @@ void overlay_latch(mi355enc_t *h, slot_t *s);                 // the text and st
 int overlay_draw(mi355enc_t *h, slot_t *s, hipStream_t st);   // the slot's text into its source surfaces, behind everything enqueued on st so far; nothing with no text
 // enc_scale.cpp
 // the one place the input geometry of a handle is decided (both setters end here): validates, then rebuilds tables, sizes, SAR and staging buffers; ERR_ARG leaves the handle as it was
-int geometry_apply(mi355enc_t *h, int orient, bool in_set, int in_w, int in_h);
+int geometry_apply(mi355enc_t *h, int orient, bool in_set, int in_w, int in_h, const mi355enc_geometry_t *geom = nullptr); // geom: the geometry in place of an input size
+// the plan the scale launch of slot s's picture runs with, on stream `up` (with a geometry: the slot's copy of the tables, brought up to date in stream order); null: HIP error
+const scale_plan_t *scale_plan_for(mi355enc_t *h, slot_t *s, hipStream_t up);
+void scale_free(mi355enc_t *h); // the tables, on the device and pinned
 // enc_orient.cpp
 static inline bool orient_transposes(int m) { return m == MI355ENC_ORIENT_90R || m == MI355ENC_ORIENT_90L || m == MI355ENC_ORIENT_UL_LR || m == MI355ENC_ORIENT_UR_LL; }
 static inline int pre_w(const mi355enc_t *h) { return orient_transposes(h->orient) ? h->cfg.height : h->cfg.width; } // the pre-orientation target: what decode / conversion / scale produce

@@ -62,7 +62,9 @@ int jpeg_enqueue(mi355enc_t *h, slot_t *s, const mi355enc_jpeg_info_t *info, hip
         if (!s->d_csc) HIPCHK(hipMalloc((void **)&s->d_csc, (size_t)wi * h->in_h * 3 / 2 + SURF_PAD));
         uint8_t *cy = s->d_csc, *cuv = cy + (size_t)wi * h->in_h;
         r = k_launch_jpeg(dc, dq, info->hs, info->vs, info->components, h->in_w, h->in_h, cy, cuv, wi, h->in_h, s->d_jpeg_planar, up);
-        if (!r) r = k_launch_scale(MI355ENC_FMT_NV12, cy, cuv, nullptr, wi, wi, 0, t.y, t.uv, t.W, t.H, &h->scale, up);
+        const scale_plan_t *pl = scale_plan_for(h, s, up);
+        if (!pl) return MI355ENC_ERR_HIP;
+        if (!r) r = k_launch_scale(MI355ENC_FMT_NV12, cy, cuv, nullptr, wi, wi, 0, t.y, t.uv, t.W, t.H, pl, up);
     }
     if (r) return MI355ENC_ERR_ARG;
     HIPCHK(hipGetLastError());

@@ -55,7 +55,7 @@ int mi355enc_orient_source(int method, int out_w, int out_h, int x, int y, int *
 
 int mi355enc_set_orientation(mi355enc_t *h, int method) {
     if (!h) return MI355ENC_ERR_ARG;
-    return geometry_apply(h, method, h->in_set, h->in_w, h->in_h);
+    return geometry_apply(h, method, h->in_set, h->in_w, h->in_h, h->geom_on ? &h->geom : nullptr);
 }
 
 int mi355enc_get_orientation(const mi355enc_t *h) { return h ? h->orient : MI355ENC_ERR_ARG; }

@@ -369,6 +369,8 @@ int upload_and_convert(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const p
     in_target_t t; // the coded surfaces, or with an orientation the slot's pre-orientation picture
     r = input_target(h, s, &t);
     if (r) return r;
+    const scale_plan_t *pl = h->scaling ? scale_plan_for(h, s, up) : nullptr;
+    if (h->scaling && !pl) return MI355ENC_ERR_HIP;
     if (fmt >= MI355ENC_FMT_Y42B) { // the formats of k_csc.hip; with an input size of its own: converted at that size, then scaled as NV12
         if (!h->scaling) r = k_launch_csc2(fmt, p[0], p[1], p[2], st[0], st[1], st[2], t.y, t.uv, t.vw, t.vh, t.W, t.H, h->csc_coef, up);
         else {
@@ -376,9 +378,9 @@ int upload_and_convert(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const p
             if (!s->d_csc) HIPCHK(hipMalloc((void **)&s->d_csc, (size_t)wi * h->in_h * 3 / 2 + SURF_PAD));
             uint8_t *cy = s->d_csc, *cuv = cy + (size_t)wi * h->in_h;
             r = k_launch_csc2(fmt, p[0], p[1], p[2], st[0], st[1], st[2], cy, cuv, h->in_w, h->in_h, wi, h->in_h, h->csc_coef, up);
-            if (!r) r = k_launch_scale(MI355ENC_FMT_NV12, cy, cuv, nullptr, wi, wi, 0, t.y, t.uv, t.W, t.H, &h->scale, up);
+            if (!r) r = k_launch_scale(MI355ENC_FMT_NV12, cy, cuv, nullptr, wi, wi, 0, t.y, t.uv, t.W, t.H, pl, up);
         }
-    } else if (h->scaling) r = k_launch_scale(fmt, p[0], p[1], p[2], st[0], st[1], st[2], t.y, t.uv, t.W, t.H, &h->scale, up);
+    } else if (h->scaling) r = k_launch_scale(fmt, p[0], p[1], p[2], st[0], st[1], st[2], t.y, t.uv, t.W, t.H, pl, up);
     else r = k_launch_csc(fmt, p[0], p[1], p[2], st[0], st[1], st[2], t.y, t.uv, t.vw, t.vh, t.W, t.H, up);
     if (r) return MI355ENC_ERR_ARG;
     HIPCHK(hipGetLastError());
@@ -587,7 +589,11 @@ int mi355enc_submit(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t
         } else
             for (int i = 0; i < nj; i++) if (stage_piece(h, jobs[i], up)) return MI355ENC_ERR_HIP;
     }
-    if (h->scaling) { if (k_launch_scale(MI355ENC_FMT_NV12, dev_y, dev_uv, nullptr, ds, ds, 0, t.y, t.uv, t.W, t.H, &h->scale, up)) return MI355ENC_ERR_ARG; }
+    if (h->scaling) {
+        const scale_plan_t *pl = scale_plan_for(h, s, up);
+        if (!pl) return MI355ENC_ERR_HIP;
+        if (k_launch_scale(MI355ENC_FMT_NV12, dev_y, dev_uv, nullptr, ds, ds, 0, t.y, t.uv, t.W, t.H, pl, up)) return MI355ENC_ERR_ARG;
+    }
     else if (!h->orient && w != h->W) k_launch_pad(s->d_src_y, s->d_src_uv, h->W, w, ht, h->W, h->H, up); // (the orientation launch writes the margin itself)
     { int r = input_finish(h, s, up); if (r) return r; }
     { int r = overlay_draw(h, s, up); if (r) return r; }
@@ -635,8 +641,9 @@ int mi355enc_submit_device(mi355enc_t *h, const void *d_y, int y_stride, const v
     if (h->scaling) { // scaled from where the planes lie into the slot's staging surfaces
         in_target_t t;
         { int r = input_target(h, s, &t); if (r) return r; }
-        if (k_launch_scale(MI355ENC_FMT_NV12, (const uint8_t *)d_y, (const uint8_t *)d_uv, nullptr, y_stride, uv_stride, 0, t.y, t.uv, t.W, t.H, &h->scale,
-                           upload_stream(h))) return MI355ENC_ERR_ARG;
+        const scale_plan_t *pl = scale_plan_for(h, s, upload_stream(h));
+        if (!pl) return MI355ENC_ERR_HIP;
+        if (k_launch_scale(MI355ENC_FMT_NV12, (const uint8_t *)d_y, (const uint8_t *)d_uv, nullptr, y_stride, uv_stride, 0, t.y, t.uv, t.W, t.H, pl, upload_stream(h))) return MI355ENC_ERR_ARG;
         HIPCHK(hipGetLastError());
         { int r = input_finish(h, s, upload_stream(h)); if (r) return r; }
         { int r = overlay_draw(h, s, upload_stream(h)); if (r) return r; }

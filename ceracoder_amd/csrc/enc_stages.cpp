@@ -219,7 +219,8 @@ int mi355enc_debug_trip_wait(mi355enc_t *h, unsigned code) {
     return MI355ENC_OK;
 }
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
-    if (!h || !avg_ms || iters < 1 || stage < 0 || stage > 13) return MI355ENC_ERR_ARG;
+    if (!h || !avg_ms || iters < 1 || stage < 0 || stage > 14) return MI355ENC_ERR_ARG;
+    if (stage == 14 && !h->d_scale_tab) return MI355ENC_ERR_STATE; // (mi355enc_set_input_size or mi355enc_set_input_geometry first)
     if (h->pending) return MI355ENC_ERR_STATE;
     HIPCHK(hipSetDevice(h->cfg.device_id));
     slot_t *s = &h->slot[0];
@@ -235,11 +236,13 @@ int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
         stage_touched(h);
     }
     if (stage == 11) { int r = quality_alloc(h); if (r) return r; } // (the block of the stage entry points)
-    if (((stage >= 5 && stage <= 7) || stage == 13) && !s->d_raw) { // input conversion (5 I420, 6 YUY2, 7 UYVY), orientation (13): any bytes will do as a source
+    if (((stage >= 5 && stage <= 7) || stage == 13 || stage == 14) && !s->d_raw) { // input conversion (5 I420, 6 YUY2, 7 UYVY), orientation (13), scale / geometry (14): any bytes will do as a source
         HIPCHK(hipMalloc((void **)&s->d_raw, raw_bytes(h)));
         HIPCHK(hipMemsetAsync(s->d_raw, 0x55, raw_bytes(h), h->stream));
     }
     if (stage == 12) { int r = jpeg_alloc(h, s); if (r) return r; }
+    const scale_plan_t *scale_pl = stage == 14 ? scale_plan_for(h, s, h->stream) : nullptr; // (a stale slot copy of the tables travels here, not inside the timed loop)
+    if (stage == 14 && !scale_pl) return MI355ENC_ERR_HIP;
     for (int warm = 0; warm < 2; warm++) {
         if (warm) HIPCHK(hipEventRecord(s->ev[0], h->stream));
         for (int i = 0; i < (warm ? iters : 1); i++) {
@@ -256,6 +259,13 @@ int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
                 const int m = h->orient ? h->orient : MI355ENC_ORIENT_90R, pw = orient_transposes(m) ? h->cfg.height : h->cfg.width, ph = orient_transposes(m) ? h->cfg.width : h->cfg.height;
                 const int ps = (pw + 15) & ~15;
                 if (k_launch_orient(m, s->d_raw, ps, s->d_raw + (size_t)ps * ph, ps, pw, ph, s->d_src_y, s->d_src_uv, h->W, h->H, h->stream)) return MI355ENC_ERR_ARG;
+            }
+            else if (stage == 14) { // the scale / geometry launch: an NV12 picture of the input size in the raw staging buffer -> the input target
+                const int ds = (h->in_w + 15) & ~15;
+                in_target_t t;
+                int r = input_target(h, s, &t);
+                if (r) return r;
+                if (k_launch_scale(MI355ENC_FMT_NV12, s->d_raw, s->d_raw + (size_t)ds * h->in_h, nullptr, ds, ds, 0, t.y, t.uv, t.W, t.H, scale_pl, h->stream)) return MI355ENC_ERR_ARG;
             }
             else if (stage == 10) k_launch_intra_p(h->slot[0].h_ctx, h->mbw, h->mbh, h->d_ip_progress, h->d_ip_strips, err_word(h), h->stream);
             else if (stage >= 5) {

@@ -67,6 +67,15 @@ typedef struct {
      * upstream image-orientation tag), what the last such tag said, and the method the open encoder was opened with (a change reopens it at the next picture) */
     gint direction, tag_direction, open_direction;
     gint out_w, out_h;        /* coded size (mpph265enc's width / height): 0 = the input's; smaller: scaled down on the device (mi355enc_set_input_size) */
+    /* input geometry on the device (mi355enc_set_input_geometry / _set_crop): videocrop's crop-* (input samples; odd values count as the even
+     * value below), videoscale's add-borders (the picture keeps its shape inside width x height), upscale (width / height may exceed the input), border-color
+     * (0xYYCbCr).  All at their defaults: none of this is used.  open_geom: the open handle has a geometry, with the crop open_crop (left, right, top, bottom); a
+     * crop that changes while playing is latched in front of the next picture (as the direction is) and goes through mi355enc_set_crop where that is enough */
+    gint crop[4];
+    gboolean add_borders, upscale;
+    guint border_color;
+    gboolean open_geom;
+    gint open_crop[4];
     /* streaming state */
     mi355enc_t *enc;
     GstVideoCodecState *input_state;
@@ -84,7 +93,8 @@ G_DEFINE_TYPE_WITH_CODE(GstMi355H264Enc, gst_mi355h264enc, GST_TYPE_VIDEO_ENCODE
 
 enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME_RANGE, PROP_QP, PROP_PIPELINE_DEPTH,
        PROP_SPEED_PRESET, PROP_STATS, PROP_DCT8X8, PROP_THREADS, PROP_SCENECUT, PROP_VBV, PROP_INTRA_IN_P, PROP_EXCLUSIVE, PROP_PINNED_INPUT, PROP_AQ_MODE, PROP_SINGLE_STREAM, PROP_INTRA_SLICES, PROP_I8X8, PROP_SLICES, PROP_SLICE_DEBLOCK, PROP_DCT8X8_ADAPTIVE, PROP_INTRA_REFRESH, PROP_WIDTH, PROP_HEIGHT, PROP_QUALITY_STATS,
-       PROP_OV_TEXT, PROP_OV_HALIGN, PROP_OV_VALIGN, PROP_OV_XPAD, PROP_OV_YPAD, PROP_OV_SCALE, PROP_OV_SHADED, PROP_VIDEO_DIRECTION };
+       PROP_OV_TEXT, PROP_OV_HALIGN, PROP_OV_VALIGN, PROP_OV_XPAD, PROP_OV_YPAD, PROP_OV_SCALE, PROP_OV_SHADED, PROP_VIDEO_DIRECTION,
+       PROP_CROP_LEFT, PROP_CROP_RIGHT, PROP_CROP_TOP, PROP_CROP_BOTTOM, PROP_ADD_BORDERS, PROP_UPSCALE, PROP_BORDER_COLOR };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
     GST_STATIC_CAPS("video/x-raw, format=(string){ NV12, I420, YUY2, UYVY, Y42B, Y444, YV12, NV21, BGRx, RGBx, xRGB, xBGR, BGRA, RGBA, ARGB, ABGR, BGR, RGB }, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]; "
@@ -188,6 +198,10 @@ static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *
     case PROP_QUALITY_STATS: s->quality_stats = g_value_get_boolean(val); break;
     case PROP_VIDEO_DIRECTION: { const gint d = g_value_get_enum(val); s->direction = d >= 0 && d <= GST_VIDEO_ORIENTATION_AUTO ? d : 0; break; } /* (CUSTOM: nothing here to be custom about) */
     case PROP_WIDTH: s->out_w = g_value_get_int(val); break;
+    case PROP_CROP_LEFT: case PROP_CROP_RIGHT: case PROP_CROP_TOP: case PROP_CROP_BOTTOM: s->crop[id - PROP_CROP_LEFT] = g_value_get_int(val); break;
+    case PROP_ADD_BORDERS: s->add_borders = g_value_get_boolean(val); break;
+    case PROP_UPSCALE: s->upscale = g_value_get_boolean(val); break;
+    case PROP_BORDER_COLOR: s->border_color = g_value_get_uint(val); break;
     case PROP_HEIGHT: s->out_h = g_value_get_int(val); break;
     case PROP_THREADS: s->threads = g_value_get_int(val); break;
     case PROP_SCENECUT: s->scenecut = g_value_get_boolean(val); break;
@@ -233,6 +247,10 @@ static void get_property(GObject *obj, guint id, GValue *val, GParamSpec *ps) {
     case PROP_QUALITY_STATS: g_value_set_boolean(val, s->quality_stats); break;
     case PROP_VIDEO_DIRECTION: g_value_set_enum(val, s->direction); break;
     case PROP_WIDTH: g_value_set_int(val, s->out_w); break;
+    case PROP_CROP_LEFT: case PROP_CROP_RIGHT: case PROP_CROP_TOP: case PROP_CROP_BOTTOM: g_value_set_int(val, s->crop[id - PROP_CROP_LEFT]); break;
+    case PROP_ADD_BORDERS: g_value_set_boolean(val, s->add_borders); break;
+    case PROP_UPSCALE: g_value_set_boolean(val, s->upscale); break;
+    case PROP_BORDER_COLOR: g_value_set_uint(val, s->border_color); break;
     case PROP_HEIGHT: g_value_set_int(val, s->out_h); break;
     case PROP_THREADS: g_value_set_int(val, s->threads); break;
     case PROP_SCENECUT: g_value_set_boolean(val, s->scenecut); break;
@@ -384,10 +402,38 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     GST_OBJECT_LOCK(s);
     const int dir = effective_direction(s);
     const gboolean tr = direction_transposes(dir);
-    /* width / height mean the coded, i.e. oriented, size; 0: the oriented input's.  What the input is scaled to is that size turned back */
-    const int out_w = s->out_w > 0 ? s->out_w : (tr ? in_h : in_w), out_h = s->out_h > 0 ? s->out_h : (tr ? in_w : in_h);
+    /* the crop rectangle (section 16): all four at 0 is the whole input */
+    int crop[4];
+    for (int i = 0; i < 4; i++) crop[i] = s->crop[i] & ~1;
+    const int crop_w = in_w - crop[0] - crop[1], crop_h = in_h - crop[2] - crop[3];
+    const gboolean add_borders = s->add_borders, upscale = s->upscale;
+    const guint border = s->border_color;
+    /* width / height mean the coded, i.e. oriented, size; 0: the oriented (cropped) input's.  What the input is scaled to is that size turned back */
+    const int out_w = s->out_w > 0 ? s->out_w : (tr ? crop_h : crop_w), out_h = s->out_h > 0 ? s->out_h : (tr ? crop_w : crop_h);
     GST_OBJECT_UNLOCK(s);
     const int pre_w = tr ? out_h : out_w, pre_h = tr ? out_w : out_h;
+    /* a geometry only where today's path cannot do it: a crop, borders, or a size above the input's that `upscale` allows */
+    const gboolean geom = crop[0] || crop[1] || crop[2] || crop[3] || add_borders || (upscale && (pre_w > in_w || pre_h > in_h));
+    mi355enc_geometry_t gm;
+    memset(&gm, 0, sizeof gm);
+    if (geom) {
+        if (crop_w < 2 || crop_h < 2 || out_w < 16 || out_h < 16) {
+            GST_ELEMENT_ERROR(s, CORE, NEGOTIATION, ("mi355h264enc: the crop leaves no picture"), ("crop %d/%d/%d/%d of %dx%d", crop[0], crop[1], crop[2], crop[3], in_w, in_h));
+            return FALSE;
+        }
+        gm.in_w = in_w; gm.in_h = in_h;
+        gm.crop_x = crop[0]; gm.crop_y = crop[2]; gm.crop_w = crop_w; gm.crop_h = crop_h;
+        gm.dst_w = pre_w; gm.dst_h = pre_h;
+        if (add_borders) { /* the picture keeps its shape; the rounding to even sizes is not an aspect ratio anybody meant: nothing from it in the SPS */
+            mi355enc_fit_rect(crop_w, crop_h, pre_w, pre_h, &gm.dst_x, &gm.dst_y, &gm.dst_w, &gm.dst_h);
+            gm.flags = MI355ENC_GEOM_KEEP_SAR;
+        }
+        gm.border_y = (border >> 16) & 255; gm.border_cb = (border >> 8) & 255; gm.border_cr = border & 255;
+        if (!upscale && (gm.dst_w > crop_w || gm.dst_h > crop_h)) {
+            GST_ELEMENT_ERROR(s, CORE, NEGOTIATION, ("mi355h264enc: width / height above the input's need upscale=true"), ("%dx%d from %dx%d", gm.dst_w, gm.dst_h, crop_w, crop_h));
+            return FALSE;
+        }
+    }
     mi355enc_default_cfg(&cfg, out_w, out_h, fn, fd);
     GST_OBJECT_LOCK(s);
     cfg.gop = s->key_int_max ? (int)s->key_int_max : 250;
@@ -418,7 +464,8 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
         r = mi355enc_set_colorimetry(e, full, prim, trc, mat);
     }
     if (r == MI355ENC_OK && dir != 0) r = mi355enc_set_orientation(e, dir); /* (first: the input size is then checked against the pre-orientation target) */
-    if (r == MI355ENC_OK && (in_w != pre_w || in_h != pre_h)) r = mi355enc_set_input_size(e, in_w, in_h); /* (refused: upscaling, a ratio above 8, odd sizes) */
+    if (r == MI355ENC_OK && geom) r = mi355enc_set_input_geometry(e, &gm); /* (refused: a ratio above 8 either way, odd sizes) */
+    else if (r == MI355ENC_OK && (in_w != pre_w || in_h != pre_h)) r = mi355enc_set_input_size(e, in_w, in_h); /* (refused: upscaling, a ratio above 8, odd sizes) */
     if (r == MI355ENC_OK && quality_stats) r = mi355enc_set_quality_metrics(e, 1);
     if (r != MI355ENC_OK) {
         if (e) mi355enc_close(e);
@@ -430,6 +477,8 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     s->enc = e;
     s->open_depth = cfg.pipeline_depth;
     s->open_direction = dir;
+    s->open_geom = geom;
+    memcpy(s->open_crop, crop, sizeof crop);
     s->jpeg = jpeg; s->jpeg_refused = 0;
     mi355enc_set_bitrate(e, target_bps(s)); /* a write that raced with open() must not be lost */
     overlay_forward(s);                     /* ... nor the overlay's text and style, set before the device was opened */
@@ -452,7 +501,9 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
                                                    transposing direction exchanges the size and the two terms of the pixel-aspect-ratio */
         out->info.width = out_w; out->info.height = out_h;
         gint pn = 1, pd = 1;
-        gst_util_fraction_multiply(GST_VIDEO_INFO_PAR_N(vi), GST_VIDEO_INFO_PAR_D(vi), in_w * pre_h, in_h * pre_w, &pn, &pd);
+        if (geom && add_borders) { pn = GST_VIDEO_INFO_PAR_N(vi); pd = GST_VIDEO_INFO_PAR_D(vi); } /* (the picture keeps its shape, so the samples keep theirs) */
+        else if (geom) gst_util_fraction_multiply(GST_VIDEO_INFO_PAR_N(vi), GST_VIDEO_INFO_PAR_D(vi), crop_w * pre_h, crop_h * pre_w, &pn, &pd);
+        else gst_util_fraction_multiply(GST_VIDEO_INFO_PAR_N(vi), GST_VIDEO_INFO_PAR_D(vi), in_w * pre_h, in_h * pre_w, &pn, &pd);
         out->info.par_n = tr ? pd : pn; out->info.par_d = tr ? pn : pd;
     }
     gst_video_codec_state_unref(out);
@@ -503,8 +554,21 @@ static GstFlowReturn enc_handle_frame(GstVideoEncoder *ve, GstVideoCodecFrame *f
     GstVideoFrame vf;
     if (!s->enc || !s->input_state) { gst_video_encoder_finish_frame(ve, frame); return GST_FLOW_NOT_NEGOTIATED; }
     GST_OBJECT_LOCK(s);
-    const gboolean turn = effective_direction(s) != s->open_direction;
+    gboolean turn = effective_direction(s) != s->open_direction;
+    int crop[4];
+    for (int i = 0; i < 4; i++) crop[i] = s->crop[i] & ~1;
+    const gboolean recrop = memcmp(crop, s->open_crop, sizeof crop) != 0;
+    const gboolean same_size = s->out_w > 0 && s->out_h > 0; /* (width / height at 0 follow the crop: the coded size changes with it) */
     GST_OBJECT_UNLOCK(s);
+    if (recrop && !turn) { /* the crop changed while playing: latched here, in front of the next picture.  Where the handle can take it -- same coded size, and without
+                              add-borders the same aspect ratio -- it is mi355enc_set_crop and nothing else changes; otherwise what a caps change does */
+        const int in_w = GST_VIDEO_INFO_WIDTH(&s->input_state->info), in_h = GST_VIDEO_INFO_HEIGHT(&s->input_state->info);
+        if (s->open_geom && same_size && mi355enc_set_crop(s->enc, crop[0], crop[2], in_w - crop[0] - crop[1], in_h - crop[2] - crop[3]) == MI355ENC_OK) {
+            GST_OBJECT_LOCK(s);
+            memcpy(s->open_crop, crop, sizeof crop);
+            GST_OBJECT_UNLOCK(s);
+        } else turn = TRUE;
+    }
     if (turn) { /* the direction changed while running (property or tag): exactly what a caps change does -- drain, reopen (this picture is an IDR picture), renegotiate the source caps */
         GstVideoCodecState *st = gst_video_codec_state_ref(s->input_state);
         const gboolean ok = enc_set_format(ve, st);
@@ -763,6 +827,14 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
         "Width of the coded picture; 0: the input's.  Smaller than the input: the picture is scaled down on the GPU (up to 8:1 per axis, even sizes)", 0, 8192, 0, F));
     g_object_class_install_property(g, PROP_HEIGHT, g_param_spec_int("height", "Coded height",
         "Height of the coded picture; 0: the input's.  Smaller than the input: the picture is scaled down on the GPU (up to 8:1 per axis, even sizes)", 0, 8192, 0, F));
+    g_object_class_install_property(g, PROP_CROP_LEFT, g_param_spec_int("crop-left", "Crop left", "Input samples to crop at the left, on the GPU (as videocrop; odd values count as the even value below; may change while playing)", 0, 8192, 0, F));
+    g_object_class_install_property(g, PROP_CROP_RIGHT, g_param_spec_int("crop-right", "Crop right", "Input samples to crop at the right", 0, 8192, 0, F));
+    g_object_class_install_property(g, PROP_CROP_TOP, g_param_spec_int("crop-top", "Crop top", "Input samples to crop at the top", 0, 8192, 0, F));
+    g_object_class_install_property(g, PROP_CROP_BOTTOM, g_param_spec_int("crop-bottom", "Crop bottom", "Input samples to crop at the bottom", 0, 8192, 0, F));
+    g_object_class_install_property(g, PROP_ADD_BORDERS, g_param_spec_boolean("add-borders", "Add borders",
+        "Keep the picture's shape inside width x height and fill the rest with border-color (as videoscale add-borders=true), on the GPU", FALSE, F));
+    g_object_class_install_property(g, PROP_UPSCALE, g_param_spec_boolean("upscale", "Allow upscaling", "Let width / height exceed the input's (up to 8:1 per axis)", FALSE, F));
+    g_object_class_install_property(g, PROP_BORDER_COLOR, g_param_spec_uint("border-color", "Border colour", "Packed 0xYYCbCr", 0, 0xFFFFFF, 0x108080, F));
     g_object_class_install_property(g, PROP_QUALITY_STATS, g_param_spec_boolean("quality-stats", "Quality metrics",
         "Measure every coded picture on the GPU (PSNR of Y, Cb, Cr and SSIM of the luma, source against reconstruction); with stats=true the stream's figures are printed when the encoder closes. Read when the encoder opens", FALSE,
         (GParamFlags)(G_PARAM_READWRITE | G_PARAM_STATIC_STRINGS | GST_PARAM_MUTABLE_READY)));
@@ -790,6 +862,7 @@ static void gst_mi355h264enc_init(GstMi355H264Enc *s) {
     s->us_map = s->us_submit = s->us_collect = s->us_output = s->us_push = s->us_frames = 0;
     s->ov_text[0] = 0; mi355enc_overlay_default_style(&s->ov_style);
     s->direction = s->tag_direction = s->open_direction = GST_VIDEO_ORIENTATION_IDENTITY;
+    s->border_color = 0x108080;
 }
 
 GType gst_mi355tsmux_get_type(void); /* gstmi355tsmux.c */

@@ -176,6 +176,12 @@ typedef struct {
     int taps[SCALE_TABLES];
     int hrows[3]; /* most source rows one tile's vertical pass reads: luma, chroma from 4:2:0, chroma from 4:2:2 */
     int span[2];  /* most source samples one tile's horizontal pass reads per row: luma, chroma (per component) */
+    /* the input geometry; geom 0: a plain downscale of the whole picture over the whole target, and everything below is unused */
+    int geom, plain;                        /* plain: the geometry is that plain downscale after all (the tables are section 10's): the plain instance runs */
+    int lo[SCALE_TABLES], hi[SCALE_TABLES]; /* source indices are clamped into [lo, hi] per table: the crop rectangle (chroma tables in chroma samples / rows) */
+    int dx, dy, dw, dh;                     /* destination rectangle inside out_w x out_h, luma samples; everything else is border */
+    int border[3];                          /* Y, Cb, Cr */
+    int cap_taps[SCALE_TABLES];             /* LDS room for coefficients, fixed when the geometry was set (taps[] changes with the crop) */
 } scale_plan_t;
 int k_launch_scale(int fmt, const uint8_t *p0, const uint8_t *p1, const uint8_t *p2, int s0, int s1, int s2, uint8_t *dy, uint8_t *duv,
                    int W, int H, const scale_plan_t *plan, hipStream_t s);

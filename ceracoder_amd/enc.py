@@ -29,7 +29,7 @@ IDEC = np.dtype([("modes4", "u1", (16,)), ("mode16", "u1"), ("cmode", "u1"), ("u
 IMV_DTYPE = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("sad", "<u2"), ("bits", "<u2")])
 SURF_ROWS, SURF_COLS = 35, 36
 DROP_MAX, DROP_SKIP = 12, 255
-STAGE_ME, STAGE_INTER, STAGE_INTRA, STAGE_DEBLOCK, STAGE_SUBPEL, STAGE_CSC_I420, STAGE_CSC_YUY2, STAGE_CSC_UYVY, STAGE_ME_SELECT, STAGE_PMB, STAGE_INTRA_P, STAGE_QUALITY, STAGE_JPEG, STAGE_ORIENT = range(14)
+STAGE_ME, STAGE_INTER, STAGE_INTRA, STAGE_DEBLOCK, STAGE_SUBPEL, STAGE_CSC_I420, STAGE_CSC_YUY2, STAGE_CSC_UYVY, STAGE_ME_SELECT, STAGE_PMB, STAGE_INTRA_P, STAGE_QUALITY, STAGE_JPEG, STAGE_ORIENT, STAGE_SCALE = range(15)
 # mi355enc_set_orientation: GstVideoOrientationMethod's numbers
 ORIENT_IDENTITY, ORIENT_90R, ORIENT_180, ORIENT_90L, ORIENT_HORIZ, ORIENT_VERT, ORIENT_UL_LR, ORIENT_UR_LL = range(8)
 ORIENT_NAMES = ("identity", "90r", "180", "90l", "horiz", "vert", "ul-lr", "ur-ll")
@@ -49,6 +49,8 @@ EXPORTS = [
     "mi355enc_jpeg_info", "mi355enc_jpeg_entropy_decode", "mi355enc_submit_jpeg", "mi355enc_stage_jpeg", "mi355enc_stage_jpeg_blocks",
     "mi355enc_set_orientation", "mi355enc_get_orientation", "mi355enc_orient_size", "mi355enc_orient_source", "mi355enc_stage_orient", "mi355enc_stage_orient_device",
     "mi355enc_debug_orient_bytes",
+    "mi355enc_set_input_geometry", "mi355enc_get_input_geometry", "mi355enc_set_crop", "mi355enc_geometry_table", "mi355enc_fit_rect", "mi355enc_stage_geometry",
+    "mi355enc_geometry_check", "mi355enc_geometry_sar",
 ]
 
 
@@ -88,6 +90,14 @@ class OverlayStyle(C.Structure):
     _fields_ = [("halign", C.c_int), ("valign", C.c_int), ("xpad", C.c_int), ("ypad", C.c_int), ("scale", C.c_int), ("shaded_background", C.c_int)]
 
 
+class Geometry(C.Structure):
+    """mi355enc_geometry_t: the submitted size, the crop rectangle inside it, the destination rectangle inside the pre-orientation target, the border colour, flags"""
+    _fields_ = [("in_w", C.c_int), ("in_h", C.c_int), ("crop_x", C.c_int), ("crop_y", C.c_int), ("crop_w", C.c_int), ("crop_h", C.c_int),
+                ("dst_x", C.c_int), ("dst_y", C.c_int), ("dst_w", C.c_int), ("dst_h", C.c_int),
+                ("border_y", C.c_int), ("border_cb", C.c_int), ("border_cr", C.c_int), ("flags", C.c_uint)]
+
+
+GEOM_KEEP_SAR = 1  # mi355enc_geometry_t.flags: no aspect ratio from the geometry in the SPS
 OVERLAY_MAX_TEXT = 255
 _lib = None
 
@@ -170,6 +180,14 @@ def load():
         L.mi355enc_stage_orient_device.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]
         L.mi355enc_debug_orient_bytes.restype = C.c_size_t
         L.mi355enc_debug_orient_bytes.argtypes = [vp]
+        L.mi355enc_set_input_geometry.argtypes = [vp, C.POINTER(Geometry)]
+        L.mi355enc_get_input_geometry.argtypes = [vp, C.POINTER(Geometry)]
+        L.mi355enc_set_crop.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.mi355enc_geometry_table.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t, C.POINTER(C.c_int)]
+        L.mi355enc_fit_rect.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int)] * 4
+        L.mi355enc_stage_geometry.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+        L.mi355enc_geometry_check.argtypes = [C.POINTER(Geometry), C.c_int, C.c_int]
+        L.mi355enc_geometry_sar.argtypes = [C.POINTER(Geometry), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.mi355enc_host_alloc.restype = vp
         L.mi355enc_host_alloc.argtypes = [C.c_size_t]
         L.mi355enc_host_free.restype = None
@@ -281,6 +299,53 @@ def scale_table(n_in, n_out, kind):
     if r != n:
         raise EncoderError("mi355enc_scale_table: %d" % r)
     return first, coef
+
+
+def geometry_table(crop_off, crop, dst, kind):
+    """scale_table's counterpart with a crop offset and upscaling (host only): `crop` luma samples from luma offset crop_off on -> `dst` luma samples;
+    first counts in the whole source plane.  -> (first, coef) as scale_table."""
+    L = load()
+    taps = C.c_int(0)
+    n = L.mi355enc_geometry_table(int(crop_off), int(crop), int(dst), int(kind), None, None, 0, C.byref(taps))
+    if n < 0:
+        raise EncoderError("mi355enc_geometry_table(%d, %d, %d, %d): %s (%d)" % (crop_off, crop, dst, kind, L.mi355enc_strerror(n).decode(), n))
+    first, coef = np.zeros(n, np.int32), np.zeros((n, taps.value), np.int16)
+    r = L.mi355enc_geometry_table(int(crop_off), int(crop), int(dst), int(kind), _p(first), _p(coef), coef.size, C.byref(taps))
+    if r != n:
+        raise EncoderError("mi355enc_geometry_table: %d" % r)
+    return first, coef
+
+
+def fit_rect(src_w, src_h, tw, th):
+    """(dx, dy, dw, dh): the largest even rectangle of src_w : src_h inside tw x th, centred at even offsets (host only)"""
+    v = [C.c_int(0) for _ in range(4)]
+    r = load().mi355enc_fit_rect(int(src_w), int(src_h), int(tw), int(th), *[C.byref(x) for x in v])
+    if r:
+        raise EncoderError("mi355enc_fit_rect: %d" % r)
+    return tuple(x.value for x in v)
+
+
+def geometry(in_size, crop=None, dst=None, target=None, border=(16, 128, 128), keep_sar=False):
+    """A Geometry: in_size (w, h); crop (x, y, w, h), default the whole input; dst (x, y, w, h), default the whole `target` (w, h)"""
+    iw, ih = in_size
+    cx, cy, cw, ch = crop if crop is not None else (0, 0, iw, ih)
+    dx, dy, dw, dh = dst if dst is not None else (0, 0, target[0], target[1])
+    return Geometry(int(iw), int(ih), int(cx), int(cy), int(cw), int(ch), int(dx), int(dy), int(dw), int(dh),
+                    int(border[0]), int(border[1]), int(border[2]), GEOM_KEEP_SAR if keep_sar else 0)
+
+
+def geometry_valid(g, tw, th):
+    """does Geometry g pass the validity rule against a pre-orientation target of tw x th? (host only)"""
+    return load().mi355enc_geometry_check(C.byref(g), int(tw), int(th)) == 0
+
+
+def geometry_sar(g, transposed=False):
+    """(sar_w, sar_h) Geometry g puts into the SPS, None for none (host only)"""
+    a, b = C.c_int(0), C.c_int(0)
+    r = load().mi355enc_geometry_sar(C.byref(g), int(bool(transposed)), C.byref(a), C.byref(b))
+    if r:
+        raise EncoderError("mi355enc_geometry_sar: %d" % r)
+    return (a.value, b.value) if a.value and b.value else None
 
 
 def orient_method(m):
@@ -431,7 +496,7 @@ class Encoder:
     (bitrate in bits/s as written through `bps`, key-int-max -> gop)."""
 
     def __init__(self, width, height, fps=60, gop=60, bitrate_bps=6_000_000, device_id=0, fixed_qp=-1, me_range=16,
-                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False, input_size=None, colorimetry=None, orientation=None):
+                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False, input_size=None, colorimetry=None, orientation=None, geometry=None):
         self.L = load()
         cfg = Cfg()
         self.L.mi355enc_default_cfg(C.byref(cfg), width, height, fps, fps_den)
@@ -485,6 +550,12 @@ class Encoder:
         if input_size is not None:  # (w, h) of the submitted pictures: scaled down on the device to width x height
             self._chk(self.L.mi355enc_set_input_size(self.h, int(input_size[0]), int(input_size[1])), "set_input_size", close_on_fail=True)
             self.input_size, self._in_set = (int(input_size[0]), int(input_size[1])), True
+        if geometry is not None:  # a Geometry (geometry()): crop -> destination rectangle of the pre-orientation target, border around it
+            try:
+                self.set_input_geometry(geometry)
+            except EncoderError:
+                self.close()
+                raise
 
     def _chk(self, r, what, close_on_fail=False):
         if r != 0:
@@ -583,6 +654,24 @@ class Encoder:
         self._chk(self.L.mi355enc_set_input_size(self.h, int(w), int(h)), "set_input_size")
         self.input_size, self._in_set = (int(w), int(h)), True
 
+    def set_input_geometry(self, g):
+        """crop / scale / letterbox of the pictures submitted from now on (before the first submit): a Geometry; replaces set_input_size"""
+        self._chk(self.L.mi355enc_set_input_geometry(self.h, C.byref(g)), "set_input_geometry")
+        self.input_size, self._in_set = (g.in_w, g.in_h), True
+
+    def get_input_geometry(self):
+        g = Geometry()
+        self._chk(self.L.mi355enc_get_input_geometry(self.h, C.byref(g)), "get_input_geometry")
+        return g
+
+    def set_crop(self, x, y, w, h):
+        """the crop rectangle of the pictures submitted from now on (between submits, on an encoder with a geometry); pictures in flight keep theirs"""
+        self._chk(self.L.mi355enc_set_crop(self.h, int(x), int(y), int(w), int(h)), "set_crop")
+
+    def stage_geometry(self, fmt, planes):
+        """The geometry launch alone: planes of the input size (row strides as the arrays have them) -> the coded-size NV12 surfaces."""
+        return self.stage_scale(fmt, planes, entry="stage_geometry")
+
     def set_orientation(self, method):
         """orientation of the pictures submitted from now on (before the first submit): 0 .. 7 or "identity", "90r", "180", "90l", "horiz", "vert", "ul-lr",
         "ur-ll".  With a transposing method and no input size of its own the pictures submitted are height x width."""
@@ -614,14 +703,14 @@ class Encoder:
         """... on device-resident planes (addresses as ints, any alignment and stride) into device surfaces of the coded size, stride 16 mbw."""
         self._chk(self.L.mi355enc_stage_orient_device(self.h, orient_method(method), y_ptr, int(y_stride), uv_ptr, int(uv_stride), out_y_ptr, out_uv_ptr), "stage_orient_device")
 
-    def stage_scale(self, fmt, planes):
+    def stage_scale(self, fmt, planes, entry="stage_scale"):
         """The scale kernel alone: planes of the input size (row strides as the arrays have them) -> the coded-size NV12 surfaces."""
         arrs = [a if a.dtype == np.uint8 and a.strides[-1] == 1 else np.ascontiguousarray(a, np.uint8) for a in planes]
         pp = (C.c_void_p * 3)(*([a.ctypes.data for a in arrs] + [None] * (3 - len(arrs))))
         ss = (C.c_int * 3)(*([a.strides[0] for a in arrs] + [0] * (3 - len(arrs))))
         oy = np.empty((self.mbh * 16, self.mbw * 16), np.uint8)
         ouv = np.empty((self.mbh * 8, self.mbw * 16), np.uint8)
-        self._chk(self.L.mi355enc_stage_scale(self.h, fmt, pp, ss, _p(oy), _p(ouv)), "stage_scale")
+        self._chk(getattr(self.L, "mi355enc_" + entry)(self.h, fmt, pp, ss, _p(oy), _p(ouv)), entry)
         return oy, ouv
 
     def scale_tables_device(self):

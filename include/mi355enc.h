@@ -258,6 +258,43 @@ int mi355enc_stage_scale(mi355enc_t *h, int fmt, const uint8_t *const planes[3],
  * only that and *taps), MI355ENC_ERR_ARG for upscaling, a ratio above 8 or odd sizes. */
 enum { MI355ENC_SCALE_LUMA = 0, MI355ENC_SCALE_CHROMA_V = 1, MI355ENC_SCALE_CHROMA_H = 2, MI355ENC_SCALE_CHROMA_V422 = 3 };
 int mi355enc_scale_table(int in, int out, int kind, int *first, int16_t *coef, size_t coef_cap, int *taps);
+/* ---- input geometry: crop, upscale, letterbox: what `videocrop ! videoscale add-borders=true ! videobox` do in front of an encoder ----
+ * The crop rectangle (crop_*) of the submitted in_w x in_h picture is resampled into the destination rectangle (dst_*) of the pre-orientation target
+ * (cfg.width x cfg.height, exchanged under a transposing orientation); everything else of the target takes the border colour.  The filter is section 10's,
+ * with the unstretched kernel where an axis is scaled up; a tap outside the crop rectangle is clamped to the rectangle's edge, and nothing outside it is read.
+ * Valid: all numbers even and >= 0, rectangle sizes >= 2, both rectangles inside their pictures, in_w, in_h <= 8192, per axis crop <= 8 dst and dst <= 8 crop,
+ * border components 0 .. 255.  The SPS carries the exact sample aspect ratio (crop_w dst_h) : (crop_h dst_w) (exchanged under a transposing orientation, absent
+ * when 1:1) -- or, with MI355ENC_GEOM_KEEP_SAR, none: the headers of an unscaled stream.
+ * mi355enc_set_input_geometry: before the first submit only (MI355ENC_ERR_STATE after it); MI355ENC_ERR_ARG for a geometry that is not valid (the handle stays as
+ * it was).  It replaces an earlier mi355enc_set_input_size and is replaced by a later one; either order with mi355enc_set_orientation gives the same handle.
+ * mi355enc_set_crop: between submits, on a handle with a geometry (MI355ENC_ERR_STATE without): the crop of the pictures submitted from now on; input size,
+ * destination and border stay.  Pictures in flight keep theirs.  Host work only: the tables are rebuilt and travel to the device with the next submit, in stream
+ * order; nothing is allocated on the device, no stream is waited for.  MI355ENC_ERR_ARG for a crop outside the rule, and -- without MI355ENC_GEOM_KEEP_SAR -- for
+ * one whose crop_w : crop_h differs from the geometry's (the SPS would have to change). */
+enum { MI355ENC_GEOM_KEEP_SAR = 1 };
+typedef struct {
+    int in_w, in_h;                         /* the submitted pictures */
+    int crop_x, crop_y, crop_w, crop_h;     /* inside them */
+    int dst_x, dst_y, dst_w, dst_h;         /* inside the pre-orientation target */
+    int border_y, border_cb, border_cr;     /* (16, 128, 128): black */
+    unsigned flags;                         /* MI355ENC_GEOM_* */
+} mi355enc_geometry_t;
+int mi355enc_set_input_geometry(mi355enc_t *h, const mi355enc_geometry_t *g);
+int mi355enc_get_input_geometry(const mi355enc_t *h, mi355enc_geometry_t *g); /* MI355ENC_ERR_STATE: the handle has none */
+int mi355enc_set_crop(mi355enc_t *h, int crop_x, int crop_y, int crop_w, int crop_h);
+/* host only: mi355enc_scale_table's counterpart with a crop offset and upscaling: `crop` luma samples from luma offset crop_off on -> `dst` luma samples
+ * of the axis; first[] counts in the whole source plane (chroma kinds: in chroma samples / rows).  With crop_off 0 and crop >= dst it is
+ * mi355enc_scale_table's table, entry for entry.  MI355ENC_ERR_ARG for odd or negative values, sizes below 2 and a ratio beyond 8 either way. */
+int mi355enc_geometry_table(int crop_off, int crop, int dst, int kind, int *first, int16_t *coef, size_t coef_cap, int *taps);
+/* host only: the largest rectangle of src_w : src_h inside tw x th (even), centred: the constrained axis is filled, the other one is 2 round(other / 2)
+ * (half up; at least 2, at most the target's), dx = ((tw - dw) / 4) 2 and dy likewise */
+int mi355enc_fit_rect(int src_w, int src_h, int tw, int th, int *dx, int *dy, int *dw, int *dh);
+/* host only: the validity rule against a pre-orientation target tw x th (MI355ENC_OK or MI355ENC_ERR_ARG), and the sample aspect ratio a geometry puts into
+ * the SPS (0:0: none), with its terms exchanged for a transposing orientation */
+int mi355enc_geometry_check(const mi355enc_geometry_t *g, int tw, int th);
+int mi355enc_geometry_sar(const mi355enc_geometry_t *g, int transposed, int *sar_w, int *sar_h);
+/* the launch alone (tests), like mi355enc_stage_scale; MI355ENC_ERR_STATE before mi355enc_set_input_geometry */
+int mi355enc_stage_geometry(mi355enc_t *h, int fmt, const uint8_t *const planes[3], const int strides[3], uint8_t *out_y, uint8_t *out_uv);
 /* ---- MJPEG input ----------------------------------------------
  * A baseline JPEG picture goes straight in: the host parses the markers and runs the serial Huffman decode, the device does dequantisation,
  * the 8x8 inverse DCT (IJG's accurate integer one: what libjpeg's ISLOW produces), level shift, clamp and the step from 4:2:2 / 4:4:4 to
@@ -438,7 +475,8 @@ int mi355enc_stage_deblock(mi355enc_t *h, uint8_t *rec_y, uint8_t *rec_uv, const
  * 5 / 6 / 7 input conversion from I420 / YUY2 / UYVY, 8 one vector-selection iteration, 9 fused P stage, 10 intra macroblocks of a P picture,
  * 11 the quality-metrics launch (slot 0's source surfaces against reconstruction buffer 1),
  * 12 the JPEG launch for the handle's input size as 4:2:2, on whatever slot 0's coefficient buffer holds,
- * 13 the orientation launch at the handle's size (the handle's method; 90r on a handle without one), on whatever slot 0's raw staging buffer holds.
+ * 13 the orientation launch at the handle's size (the handle's method; 90r on a handle without one), on whatever slot 0's raw staging buffer holds,
+ * 14 the scale / geometry launch for an NV12 picture of the handle's input size (MI355ENC_ERR_STATE without mi355enc_set_input_size / _geometry), likewise.
  * Uses whatever the handle's surfaces currently hold.  Returns average ms per launch. */
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms);
 
