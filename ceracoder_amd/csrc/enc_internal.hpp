@@ -3,6 +3,7 @@
 //   enc_handle.cpp    open / close / setters / statistics / fetch
 //   enc_schedule.cpp  the picture pipeline: submit*, the stream schedule of one picture, collect
 //   enc_overlay.cpp   the text overlay: setters, latch, layout, launch
+//   enc_image.cpp    image layers: setters, latch, upload + prepare, blend launches, retirement
 //   enc_orient.cpp    orientation of the input picture: setter, the slot's pre-orientation picture, launch, its stage entry points
 //   enc_jpeg.cpp      MJPEG input: coefficient buffers, host decode, transfer + launch, its stage entry points
 //   enc_stages.cpp    single-stage entry points (parity tests, probes) and the host-only stages
@@ -43,6 +44,16 @@ static const uint8_t k_lambda[52] = {1,  1,  1,  1,  1,  1,  1,  1,  1,  1,  1, 
 #define SURF_PAD 256 /* bytes past each surface: unaligned-pair loads may touch 4 bytes beyond */
 
 
+// One image a layer was given (mi355enc_set_image).  The control thread makes it from the caller's pixels; the first picture that latches
+// it uploads it from pinned staging and prepares it on the device, after which nothing writes it again.  refs (under mi355enc::img_mu): the layer that shows it
+// and every slot whose picture latched it; at 0 it is retired -- its buffers go to the handle's pool for the next upload, nothing is freed before close.
+struct image_buf_t { uint8_t *h_pin; uint32_t *d_pix; size_t cap; hipEvent_t ev; bool busy; image_buf_t *next; }; // pinned staging + device words of cap bytes; ev: behind the last transfer out of h_pin; busy: an image owns it
+struct image_t {
+    uint8_t *host;      // malloc: the caller's pixels, rows of 4 w bytes (freed once they are in pinned staging)
+    image_buf_t *buf;   // null until the first picture that carries the image is submitted
+    int fmt, w, h, refs;
+};
+
 struct slot_t {
     frame_ctx_t *h_ctx;   // pinned
     mb_info_t *h_mbi;     // pinned
@@ -72,6 +83,8 @@ struct slot_t {
     const uint8_t *src_y, *src_uv; int src_stride, force_idr; // what enqueue_picture() was given: a recovery re-enqueues the pictures in flight from here
     // text overlay: what submit latched for this picture and drew into its source surfaces (ov_len 0: nothing); a recovery keeps it -- the surfaces carry the text
     int ov_len; char ov_text[256]; mi355enc_overlay_style_t ov_style;
+    // image layers: what submit latched for this picture and blended into its source surfaces (img[l] null: nothing of layer l); a recovery keeps it likewise
+    image_t *img[MI355ENC_IMAGE_LAYERS]; int img_x[MI355ENC_IMAGE_LAYERS], img_y[MI355ENC_IMAGE_LAYERS], img_op[MI355ENC_IMAGE_LAYERS]; uint32_t img_serial[MI355ENC_IMAGE_LAYERS];
 };
 
 struct mi355enc {
@@ -183,6 +196,14 @@ struct mi355enc {
     std::mutex ov_mu;
     int ov_len; char ov_text[256]; mi355enc_overlay_style_t ov_style;
     int ov_last_have, ov_last_len; char ov_last[256];
+    // image layers (mi355enc_set_image / _set_image_place): per layer the image the control thread set last, its place, opacity and serial
+    // (under img_mu; submit latches them per picture), every buffer made so far (those of retired images wait there for the next upload; freed at close), the
+    // device bytes held, and what the last collected picture carried
+    std::mutex img_mu;
+    image_t *img_cur[MI355ENC_IMAGE_LAYERS]; int img_x[MI355ENC_IMAGE_LAYERS], img_y[MI355ENC_IMAGE_LAYERS], img_op[MI355ENC_IMAGE_LAYERS]; uint32_t img_serial[MI355ENC_IMAGE_LAYERS];
+    image_buf_t *img_bufs;
+    size_t img_dev_bytes;
+    mi355enc_image_info_t img_last[MI355ENC_IMAGE_LAYERS];
     // the entropy-coding worker (started by open() when pipeline_depth >= 1)
     std::thread wk;
     std::mutex wk_mu;
@@ -239,6 +260,13 @@ int quality_run(mi355enc_t *h, const uint8_t *src_y, const uint8_t *src_uv, int 
 // enc_overlay.cpp
 void overlay_latch(mi355enc_t *h, slot_t *s);                 // the text and style set last become the slot's (the first thing a submit does)
 int overlay_draw(mi355enc_t *h, slot_t *s, hipStream_t st);   // the slot's text into its source surfaces, behind everything enqueued on st so far; nothing with no text
+// enc_image.cpp
+int image_latch(mi355enc_t *h, slot_t *s);                  // the layers set last become the slot's (beside overlay_latch); ERR_ARG: an active layer and a matrix RGB cannot be converted with
+static inline bool image_active(const slot_t *s) { for (int l = 0; l < MI355ENC_IMAGE_LAYERS; l++) if (s->img[l] && s->img_op[l]) return true; return false; }
+int image_draw(mi355enc_t *h, slot_t *s, hipStream_t st);   // the slot's layers into its source surfaces in index order, behind everything enqueued on st so far (an image not yet on the device goes there first); nothing with no layer
+void image_collected(mi355enc_t *h, slot_t *s);             // collect(): books what the picture carried as the last picture's and lets go of the slot's images
+void image_free(mi355enc_t *h);                             // close(): everything
+int image_time_prepare(mi355enc_t *h, image_args_t *a);     // mi355enc_time_stage 15: layer 0's image on the device, the launch's arguments at its current place; ERR_STATE without one
 // enc_scale.cpp
 // the one place the input geometry of a handle is decided (both setters end here): validates, then rebuilds tables, sizes, SAR and staging buffers; ERR_ARG leaves the handle as it was
 int geometry_apply(mi355enc_t *h, int orient, bool in_set, int in_w, int in_h, const mi355enc_geometry_t *geom = nullptr); // geom: the geometry in place of an input size

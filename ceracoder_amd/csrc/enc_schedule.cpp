@@ -1,7 +1,7 @@
 // enc_schedule.cpp -- the picture pipeline of the C-ABI shim.
 //
 // Per picture:
-//   front stream: [H2D source | conversion | JPEG coefficients + inverse DCT | scale] -> [text overlay, if a text is set] -> P: me_kernel (SAD surfaces + first selection) -> me_select_kernel x ME_ITERS
+//   front stream: [H2D source | conversion | JPEG coefficients + inverse DCT | scale] -> [image layers, if one is set] -> [text overlay, if a text is set] -> P: me_kernel (SAD surfaces + first selection) -> me_select_kernel x ME_ITERS
 //                 -> intra analysis of the badly predicted macroblocks;  IDR: the source copy the next search runs against
 //   back stream:  IDR: intra analysis (flat) -> intra wavefront (persistent bands) | P: pmb_kernel -> intra_p_kernel
 //                 -> deblocking (persistent band kernel)
@@ -541,6 +541,7 @@ int mi355enc_submit(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t
     HIPCHK(hipSetDevice(h->cfg.device_id));
     slot_t *s = &h->slot[h->head];
     overlay_latch(h, s);
+    { int r = image_latch(h, s); if (r) return r; }
     const int w = h->in_w, ht = h->in_h;
     hipStream_t up = upload_stream(h);
     // where the planes go: the staging surfaces at the coded stride, or -- to be scaled -- the raw staging buffer at the input's
@@ -596,6 +597,7 @@ int mi355enc_submit(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t
     }
     else if (!h->orient && w != h->W) k_launch_pad(s->d_src_y, s->d_src_uv, h->W, w, ht, h->W, h->H, up); // (the orientation launch writes the margin itself)
     { int r = input_finish(h, s, up); if (r) return r; }
+    { int r = image_draw(h, s, up); if (r) return r; }
     { int r = overlay_draw(h, s, up); if (r) return r; }
     { int r = upload_done(h, s); if (r) return r; }
     return enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
@@ -608,8 +610,10 @@ int mi355enc_submit_fmt(mi355enc_t *h, int fmt, const uint8_t *const planes[3], 
     HIPCHK(hipSetDevice(h->cfg.device_id));
     slot_t *s = &h->slot[h->head];
     overlay_latch(h, s);
+    { int r = image_latch(h, s); if (r) return r; }
     int r = upload_and_convert(h, s, fmt, planes, strides, upload_stream(h));
     if (r) return r;
+    r = image_draw(h, s, upload_stream(h)); if (r) return r;
     r = overlay_draw(h, s, upload_stream(h)); if (r) return r;
     r = upload_done(h, s); if (r) return r;
     return enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
@@ -626,7 +630,9 @@ int mi355enc_submit_jpeg(mi355enc_t *h, const uint8_t *data, size_t len, int64_t
     int r = jpeg_decode_host(h, s, data, len, &info);
     if (r) return r;
     overlay_latch(h, s);
+    r = image_latch(h, s); if (r) return r;
     r = jpeg_enqueue(h, s, &info, upload_stream(h)); if (r) return r;
+    r = image_draw(h, s, upload_stream(h)); if (r) return r;
     r = overlay_draw(h, s, upload_stream(h)); if (r) return r;
     r = upload_done(h, s); if (r) return r;
     return enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
@@ -638,6 +644,7 @@ int mi355enc_submit_device(mi355enc_t *h, const void *d_y, int y_stride, const v
     HIPCHK(hipSetDevice(h->cfg.device_id));
     slot_t *s = &h->slot[h->head];
     overlay_latch(h, s);
+    { int r = image_latch(h, s); if (r) return r; }
     if (h->scaling) { // scaled from where the planes lie into the slot's staging surfaces
         in_target_t t;
         { int r = input_target(h, s, &t); if (r) return r; }
@@ -646,6 +653,7 @@ int mi355enc_submit_device(mi355enc_t *h, const void *d_y, int y_stride, const v
         if (k_launch_scale(MI355ENC_FMT_NV12, (const uint8_t *)d_y, (const uint8_t *)d_uv, nullptr, y_stride, uv_stride, 0, t.y, t.uv, t.W, t.H, pl, upload_stream(h))) return MI355ENC_ERR_ARG;
         HIPCHK(hipGetLastError());
         { int r = input_finish(h, s, upload_stream(h)); if (r) return r; }
+        { int r = image_draw(h, s, upload_stream(h)); if (r) return r; }
         { int r = overlay_draw(h, s, upload_stream(h)); if (r) return r; }
         { int r = upload_done(h, s); if (r) return r; }
         return enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
@@ -653,17 +661,19 @@ int mi355enc_submit_device(mi355enc_t *h, const void *d_y, int y_stride, const v
     hipStream_t up = upload_stream(h);
     if (h->orient) { // oriented from where the planes lie, at their stride and address, into the slot's staging surfaces: never in place, the caller's planes are only read
         { int r = input_finish(h, s, up, (const uint8_t *)d_y, y_stride, (const uint8_t *)d_uv, uv_stride); if (r) return r; }
+        { int r = image_draw(h, s, up); if (r) return r; }
         { int r = overlay_draw(h, s, up); if (r) return r; }
         { int r = upload_done(h, s); if (r) return r; }
         return enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
     }
     const int w = h->cfg.width, ht = h->cfg.height;
-    // in place -- unless a text is to be drawn: that goes into the encoder's own surfaces, never into the caller's planes
-    const bool direct = !s->ov_len && w == h->W && y_stride == uv_stride && (y_stride & 15) == 0 && (((uintptr_t)d_y | (uintptr_t)d_uv) & 15) == 0;
+    // in place -- unless a text is to be drawn or an image blended in: that goes into the encoder's own surfaces, never into the caller's planes
+    const bool direct = !s->ov_len && !image_active(s) && w == h->W && y_stride == uv_stride && (y_stride & 15) == 0 && (((uintptr_t)d_y | (uintptr_t)d_uv) & 15) == 0;
     if (direct) return enqueue_picture(h, s, (const uint8_t *)d_y, (const uint8_t *)d_uv, y_stride, pts, force_idr);
     HIPCHK(hipMemcpy2DAsync(s->d_src_y, h->W, d_y, y_stride, w, ht, hipMemcpyDeviceToDevice, up));
     HIPCHK(hipMemcpy2DAsync(s->d_src_uv, h->W, d_uv, uv_stride, w, ht / 2, hipMemcpyDeviceToDevice, up));
     if (w != h->W) k_launch_pad(s->d_src_y, s->d_src_uv, h->W, w, ht, h->W, h->H, up);
+    { int r = image_draw(h, s, up); if (r) return r; }
     { int r = overlay_draw(h, s, up); if (r) return r; }
     { int r = upload_done(h, s); if (r) return r; }
     return enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
@@ -754,6 +764,7 @@ int mi355enc_collect(mi355enc_t *h, uint8_t *out, size_t out_cap, size_t *out_le
     h->st.last_qp = (uint32_t)s->qp; h->st.last_drop = (uint32_t)s->drop; h->n_skip_pictures += s->all_skip; h->st.last_bytes = (uint32_t)(n + m); h->st.target_bps = h->want_bps.load();
     h->last_slot = s; h->last_collected_rec = s->rec_index;
     h->ov_last_have = 1; h->ov_last_len = s->ov_len; if (s->ov_len) memcpy(h->ov_last, s->ov_text, (size_t)s->ov_len);
+    image_collected(h, s);
     h->tail = (h->tail + 1) % NSLOT; h->pending--;
     return MI355ENC_OK;
 }

@@ -27,6 +27,7 @@
 #include <gst/gst.h>
 #include <gst/video/gstvideoencoder.h>
 #include <gst/video/video.h>
+#include <math.h>
 #include <string.h>
 
 #include "../../include/mi355enc.h"
@@ -63,6 +64,13 @@ typedef struct {
      * custom event of an `mi355textoverlay` element upstream; stored here (object lock) and forwarded to the open encoder, which latches it per picture */
     gchar ov_text[MI355ENC_OVERLAY_MAX_TEXT + 1];
     mi355enc_overlay_style_t ov_style;
+    /* image layer 0 blended in on the device (mi355enc_set_image / _set_image_place), in place of a gdkpixbufoverlay upstream: the file
+     * image-location named last (a Netpbm PAM, read when the property is written), its RGBA pixels, and the place and alpha; stored here (object lock) and
+     * forwarded to the open encoder, which latches them per picture.  img_rgba NULL: the layer is off */
+    gchar *img_location;
+    guint8 *img_rgba;
+    gint img_w, img_h, img_x, img_y;
+    gdouble img_alpha;
     /* orientation on the device (mi355enc_set_orientation): the video-direction property (GstVideoOrientationMethod, AUTO follows the
      * upstream image-orientation tag), what the last such tag said, and the method the open encoder was opened with (a change reopens it at the next picture) */
     gint direction, tag_direction, open_direction;
@@ -94,7 +102,8 @@ G_DEFINE_TYPE_WITH_CODE(GstMi355H264Enc, gst_mi355h264enc, GST_TYPE_VIDEO_ENCODE
 enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME_RANGE, PROP_QP, PROP_PIPELINE_DEPTH,
        PROP_SPEED_PRESET, PROP_STATS, PROP_DCT8X8, PROP_THREADS, PROP_SCENECUT, PROP_VBV, PROP_INTRA_IN_P, PROP_EXCLUSIVE, PROP_PINNED_INPUT, PROP_AQ_MODE, PROP_SINGLE_STREAM, PROP_INTRA_SLICES, PROP_I8X8, PROP_SLICES, PROP_SLICE_DEBLOCK, PROP_DCT8X8_ADAPTIVE, PROP_INTRA_REFRESH, PROP_WIDTH, PROP_HEIGHT, PROP_QUALITY_STATS,
        PROP_OV_TEXT, PROP_OV_HALIGN, PROP_OV_VALIGN, PROP_OV_XPAD, PROP_OV_YPAD, PROP_OV_SCALE, PROP_OV_SHADED, PROP_VIDEO_DIRECTION,
-       PROP_CROP_LEFT, PROP_CROP_RIGHT, PROP_CROP_TOP, PROP_CROP_BOTTOM, PROP_ADD_BORDERS, PROP_UPSCALE, PROP_BORDER_COLOR };
+       PROP_CROP_LEFT, PROP_CROP_RIGHT, PROP_CROP_TOP, PROP_CROP_BOTTOM, PROP_ADD_BORDERS, PROP_UPSCALE, PROP_BORDER_COLOR,
+       PROP_IMG_LOCATION, PROP_IMG_X, PROP_IMG_Y, PROP_IMG_ALPHA };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
     GST_STATIC_CAPS("video/x-raw, format=(string){ NV12, I420, YUY2, UYVY, Y42B, Y444, YV12, NV21, BGRx, RGBx, xRGB, xBGR, BGRA, RGBA, ARGB, ABGR, BGR, RGB }, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]; "
@@ -172,10 +181,59 @@ static void overlay_forward(GstMi355H264Enc *s) {
 }
 static void overlay_store_text(GstMi355H264Enc *s, const gchar *t) { g_strlcpy(s->ov_text, t ? t : "", sizeof s->ov_text); }
 
+/* stored image, place and alpha -> layer 0 of the encoder, if one is open (object lock held; the library only copies and stores: no GPU call, any thread).
+ * pixels: the image itself has changed (or the encoder is new); otherwise only place and opacity travel */
+static int image_opacity(const GstMi355H264Enc *s) { return (int)rint(256.0 * s->img_alpha); }
+static void image_forward(GstMi355H264Enc *s, gboolean pixels) {
+    if (!s->enc) return;
+    if (!s->img_rgba) { if (pixels) mi355enc_set_image(s->enc, 0, NULL); return; }
+    if (pixels) {
+        const mi355enc_image_layer_t im = {MI355ENC_FMT_RGBX, s->img_rgba, s->img_w, s->img_h, 4 * s->img_w, s->img_x, s->img_y, image_opacity(s)};
+        if (mi355enc_set_image(s->enc, 0, &im) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the image: it keeps its previous one");
+    } else if (mi355enc_set_image_place(s->enc, 0, s->img_x, s->img_y, image_opacity(s)) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the image's place");
+}
+/* image-location: the file is read here, in the setter, outside the object lock (the warning goes to the bus).  "" or NULL: off.  A file that cannot be read or
+ * that the PAM reader refuses leaves the layer as it was */
+static void image_set_location(GstMi355H264Enc *s, const gchar *path) {
+    guint8 *rgba = NULL;
+    gint w = 0, h = 0;
+    if (path && *path) {
+        gchar *data = NULL;
+        gsize len = 0;
+        GError *err = NULL;
+        if (!g_file_get_contents(path, &data, &len, &err)) {
+            GST_ELEMENT_WARNING(s, RESOURCE, OPEN_READ, ("mi355h264enc: cannot read image-location \"%s\": the image layer stays as it was", path), ("%s", err ? err->message : "?"));
+            g_clear_error(&err);
+            return;
+        }
+        int r = mi355enc_image_load_pam((const guint8 *)data, len, &w, &h, NULL, 0);
+        if (r == MI355ENC_OK) {
+            rgba = g_malloc((gsize)w * h * 4);
+            r = mi355enc_image_load_pam((const guint8 *)data, len, &w, &h, rgba, (gsize)w * h * 4);
+        }
+        g_free(data);
+        if (r != MI355ENC_OK) {
+            g_free(rgba);
+            GST_ELEMENT_WARNING(s, STREAM, FORMAT, ("mi355h264enc: image-location \"%s\" is not a PAM file this element takes (P7, RGB_ALPHA or RGB, MAXVAL 255, at most 4096 x 4096): "
+                                                    "the image layer stays as it was", path), ("mi355enc_image_load_pam returned %d", r));
+            return;
+        }
+    }
+    GST_OBJECT_LOCK(s);
+    g_free(s->img_location); s->img_location = g_strdup(path ? path : "");
+    g_free(s->img_rgba); s->img_rgba = rgba; s->img_w = w; s->img_h = h;
+    image_forward(s, TRUE);
+    GST_OBJECT_UNLOCK(s);
+}
+
 static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *ps) {
     GstMi355H264Enc *s = GST_MI355H264ENC(obj);
+    if (id == PROP_IMG_LOCATION) { image_set_location(s, g_value_get_string(val)); return; }
     GST_OBJECT_LOCK(s);
     switch (id) {
+    case PROP_IMG_X: s->img_x = g_value_get_int(val); image_forward(s, FALSE); break;
+    case PROP_IMG_Y: s->img_y = g_value_get_int(val); image_forward(s, FALSE); break;
+    case PROP_IMG_ALPHA: s->img_alpha = g_value_get_double(val); image_forward(s, FALSE); break;
     case PROP_OV_TEXT: overlay_store_text(s, g_value_get_string(val)); overlay_forward(s); break;
     case PROP_OV_HALIGN: s->ov_style.halign = g_value_get_enum(val); overlay_forward(s); break;
     case PROP_OV_VALIGN: s->ov_style.valign = g_value_get_enum(val) > 2 ? 2 : g_value_get_enum(val); overlay_forward(s); break;
@@ -225,6 +283,10 @@ static void get_property(GObject *obj, guint id, GValue *val, GParamSpec *ps) {
     GST_OBJECT_LOCK(s);
     effective_tools(s, &t); /* a tool property reads as what the encoder will use: the explicit value, or the preset's */
     switch (id) {
+    case PROP_IMG_LOCATION: g_value_set_string(val, s->img_location ? s->img_location : ""); break;
+    case PROP_IMG_X: g_value_set_int(val, s->img_x); break;
+    case PROP_IMG_Y: g_value_set_int(val, s->img_y); break;
+    case PROP_IMG_ALPHA: g_value_set_double(val, s->img_alpha); break;
     case PROP_OV_TEXT: g_value_set_string(val, s->ov_text); break;
     case PROP_OV_HALIGN: g_value_set_enum(val, s->ov_style.halign); break;
     case PROP_OV_VALIGN: g_value_set_enum(val, s->ov_style.valign); break;
@@ -482,6 +544,7 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     s->jpeg = jpeg; s->jpeg_refused = 0;
     mi355enc_set_bitrate(e, target_bps(s)); /* a write that raced with open() must not be lost */
     overlay_forward(s);                     /* ... nor the overlay's text and style, set before the device was opened */
+    image_forward(s, TRUE);                 /* ... nor the image layer */
     GST_OBJECT_UNLOCK(s);
     s->max_au = mi355enc_max_au_bytes(e);
     g_free(s->au_buf);
@@ -765,6 +828,8 @@ static gboolean enc_sink_event(GstVideoEncoder *ve, GstEvent *ev) {
 }
 static void finalize(GObject *obj) {
     enc_stop(GST_VIDEO_ENCODER(obj));
+    g_free(GST_MI355H264ENC(obj)->img_location);
+    g_free(GST_MI355H264ENC(obj)->img_rgba);
     G_OBJECT_CLASS(gst_mi355h264enc_parent_class)->finalize(obj);
 }
 
@@ -847,6 +912,12 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
     g_object_class_install_property(g, PROP_OV_YPAD, g_param_spec_int("overlay-ypad", "Overlay vertical padding", "Luma samples between the text box and the top / bottom picture edge", 0, 8192, 16, F));
     g_object_class_install_property(g, PROP_OV_SCALE, g_param_spec_int("overlay-scale", "Overlay scale", "Luma samples per font pixel, 1..8; 0: height / 540, at least 1 (720p 1, 1080p 2, 2160p 4)", 0, 8, 0, F));
     g_object_class_install_property(g, PROP_OV_SHADED, g_param_spec_boolean("overlay-shaded-background", "Overlay shaded background", "Darken the text box", FALSE, F));
+    g_object_class_install_property(g, PROP_IMG_LOCATION, g_param_spec_string("image-location", "Image location",
+        "A Netpbm PAM file (P7; RGB_ALPHA or RGB, MAXVAL 255, at most 4096 x 4096) blended into every picture on the GPU, 1:1, under the overlay text (as gdkpixbufoverlay's location; "
+        "PNG is not read: convert with `pngtopam -alphapam`). Read when the property is written, also while playing; a file that cannot be taken posts a warning and changes nothing; empty: off", "", F));
+    g_object_class_install_property(g, PROP_IMG_X, g_param_spec_int("image-offset-x", "Image X offset", "Luma samples from the picture's left edge to the image's (negative: the image starts outside)", -16384, 16384, 0, F));
+    g_object_class_install_property(g, PROP_IMG_Y, g_param_spec_int("image-offset-y", "Image Y offset", "Luma samples from the picture's top edge to the image's", -16384, 16384, 0, F));
+    g_object_class_install_property(g, PROP_IMG_ALPHA, g_param_spec_double("image-alpha", "Image alpha", "Global alpha of the image, multiplied onto its own (as gdkpixbufoverlay's alpha)", 0.0, 1.0, 1.0, F));
     g_object_class_override_property(g, PROP_VIDEO_DIRECTION, "video-direction"); /* GstVideoDirection: identity, 90r, 180, 90l, horiz, vert, ul-lr, ur-ll, auto -- as on videoflip */
     g_object_class_install_property(g, PROP_STATS, g_param_spec_boolean("stats", "Print stats", "Print a JSON line with counters when the encoder closes", FALSE, F));
     gst_element_class_add_static_pad_template(e, &sink_tmpl);
@@ -861,6 +932,7 @@ static void gst_mi355h264enc_init(GstMi355H264Enc *s) {
     s->stats = FALSE; s->dct8x8 = -1; s->threads = 0; s->scenecut = TRUE; s->exclusive_gpu = FALSE; s->vbv_ms = 600; s->intra_in_p = -1; s->pinned_input = TRUE; s->aq_mode = -1; s->slices = -1; s->slice_deblock = -1; s->intra_slices = 0; s->i8x8 = -1; s->single_stream = FALSE; s->dct8x8_adaptive = FALSE; s->intra_refresh = FALSE; s->quality_stats = FALSE; s->enc = NULL; s->input_state = NULL; s->max_au = 0; s->au_buf = NULL; s->last_pts = GST_CLOCK_TIME_NONE;
     s->us_map = s->us_submit = s->us_collect = s->us_output = s->us_push = s->us_frames = 0;
     s->ov_text[0] = 0; mi355enc_overlay_default_style(&s->ov_style);
+    s->img_location = NULL; s->img_rgba = NULL; s->img_w = s->img_h = s->img_x = s->img_y = 0; s->img_alpha = 1.0;
     s->direction = s->tag_direction = s->open_direction = GST_VIDEO_ORIENTATION_IDENTITY;
     s->border_color = 0x108080;
 }

@@ -215,6 +215,21 @@ typedef struct {
     uint8_t line_end[256];
 } overlay_args_t;
 void k_launch_overlay(const overlay_args_t *a, hipStream_t s);
+/* Image layers (k_image.hip; the rule: DESIGN.md section 17).  prepare: n pixels of 4 bytes in byte order fmt (MI355ENC_FMT_BGRX .. MI355ENC_FMT_XBGR, X = A) at
+ * `pix` become one word {Yi, Cbi << 8, Cri << 16, A << 24} each, in place; coef: the ten words of mi355enc_csc_coefficients.  blend: one layer -- iw x ih
+ * prepared words, rows adjacent, top-left at (x, y) of the visible picture vw x vh, opacity 0 .. 256 -- into NV12 surfaces of stride `stride` and coded size
+ * W x H.  The grid covers the quads [gx0, gx1) x [gy0, gy1) (even, inside the visible picture): the visible intersection from an even origin; where it reaches the
+ * last visible column / row, the owners of the last quads write the margin up to W / H as well. */
+typedef struct {
+    uint8_t *y, *uv;
+    const uint32_t *img;
+    int32_t stride, vw, vh, W, H;
+    int32_t iw, ih, x, y0, opacity;
+    int32_t gx0, gy0, gx1, gy1;
+} image_args_t;
+int k_launch_image_prepare(uint32_t *pix, size_t n, int fmt, const int *coef, hipStream_t s); /* -1: not one of the four orders */
+bool k_image_grid(image_args_t *a);  /* fills gx0 .. gy1 from the place and the sizes; false: nothing of the image is visible (no launch) */
+void k_launch_image_blend(const image_args_t *a, hipStream_t s);
 /* MJPEG input (k_jpeg.hip; the rule: DESIGN.md section 14): a picture of vw x vh (even) with luma sampling hs x vs and `comps` components, coefficient blocks and
  * quantisation tables on the device as mi355enc_jpeg_entropy_decode lays them out, into NV12 surfaces of stride W and coded size W x H (the margin repeats the last
  * visible row, column and chroma pair).  d_planar: scratch of 3 * ((vw + 15) & ~15) * vh bytes, read and written for 4:4:4 only.  -1: not a sampling it takes. */

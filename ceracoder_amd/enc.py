@@ -29,7 +29,7 @@ IDEC = np.dtype([("modes4", "u1", (16,)), ("mode16", "u1"), ("cmode", "u1"), ("u
 IMV_DTYPE = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("sad", "<u2"), ("bits", "<u2")])
 SURF_ROWS, SURF_COLS = 35, 36
 DROP_MAX, DROP_SKIP = 12, 255
-STAGE_ME, STAGE_INTER, STAGE_INTRA, STAGE_DEBLOCK, STAGE_SUBPEL, STAGE_CSC_I420, STAGE_CSC_YUY2, STAGE_CSC_UYVY, STAGE_ME_SELECT, STAGE_PMB, STAGE_INTRA_P, STAGE_QUALITY, STAGE_JPEG, STAGE_ORIENT, STAGE_SCALE = range(15)
+STAGE_ME, STAGE_INTER, STAGE_INTRA, STAGE_DEBLOCK, STAGE_SUBPEL, STAGE_CSC_I420, STAGE_CSC_YUY2, STAGE_CSC_UYVY, STAGE_ME_SELECT, STAGE_PMB, STAGE_INTRA_P, STAGE_QUALITY, STAGE_JPEG, STAGE_ORIENT, STAGE_SCALE, STAGE_IMAGE = range(16)
 # mi355enc_set_orientation: GstVideoOrientationMethod's numbers
 ORIENT_IDENTITY, ORIENT_90R, ORIENT_180, ORIENT_90L, ORIENT_HORIZ, ORIENT_VERT, ORIENT_UL_LR, ORIENT_UR_LL = range(8)
 ORIENT_NAMES = ("identity", "90r", "180", "90l", "horiz", "vert", "ul-lr", "ur-ll")
@@ -46,6 +46,7 @@ EXPORTS = [
     "mi355enc_set_colorimetry", "mi355enc_csc_coefficients", "mi355enc_host_write_headers_vui", "mi355enc_stage_csc_device",
     "mi355enc_set_quality_metrics", "mi355enc_last_quality", "mi355enc_quality_totals", "mi355enc_stage_quality", "mi355enc_stage_quality_device",
     "mi355enc_overlay_default_style", "mi355enc_set_overlay_style", "mi355enc_set_overlay_text", "mi355enc_last_overlay", "mi355enc_overlay_glyph", "mi355enc_stage_overlay",
+    "mi355enc_set_image", "mi355enc_set_image_place", "mi355enc_last_image", "mi355enc_stage_image", "mi355enc_debug_image_bytes", "mi355enc_image_pixel", "mi355enc_image_load_pam",
     "mi355enc_jpeg_info", "mi355enc_jpeg_entropy_decode", "mi355enc_submit_jpeg", "mi355enc_stage_jpeg", "mi355enc_stage_jpeg_blocks",
     "mi355enc_set_orientation", "mi355enc_get_orientation", "mi355enc_orient_size", "mi355enc_orient_source", "mi355enc_stage_orient", "mi355enc_stage_orient_device",
     "mi355enc_debug_orient_bytes",
@@ -90,6 +91,20 @@ class OverlayStyle(C.Structure):
     _fields_ = [("halign", C.c_int), ("valign", C.c_int), ("xpad", C.c_int), ("ypad", C.c_int), ("scale", C.c_int), ("shaded_background", C.c_int)]
 
 
+class ImageLayer(C.Structure):
+    """mi355enc_image_layer_t: 4-byte pixels with straight alpha in byte order fmt (FMT_BGRX = BGRA, FMT_RGBX = RGBA, FMT_XRGB = ARGB, FMT_XBGR = ABGR), rows `stride`
+    bytes apart, the top-left pixel at (x, y) of the coded visible picture, opacity 0 .. 256"""
+    _fields_ = [("fmt", C.c_int), ("pixels", C.c_void_p), ("w", C.c_int), ("h", C.c_int), ("stride", C.c_int), ("x", C.c_int), ("y", C.c_int), ("opacity", C.c_int)]
+
+
+class ImageInfo(C.Structure):
+    """mi355enc_image_info_t: what a layer put into a picture (serial 0, w = h = 0: nothing)"""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("x", C.c_int), ("y", C.c_int), ("opacity", C.c_int), ("serial", C.c_uint32)]
+
+    def as_tuple(self):
+        return (self.w, self.h, self.x, self.y, self.opacity, int(self.serial))
+
+
 class Geometry(C.Structure):
     """mi355enc_geometry_t: the submitted size, the crop rectangle inside it, the destination rectangle inside the pre-orientation target, the border colour, flags"""
     _fields_ = [("in_w", C.c_int), ("in_h", C.c_int), ("crop_x", C.c_int), ("crop_y", C.c_int), ("crop_w", C.c_int), ("crop_h", C.c_int),
@@ -97,6 +112,7 @@ class Geometry(C.Structure):
                 ("border_y", C.c_int), ("border_cb", C.c_int), ("border_cr", C.c_int), ("flags", C.c_uint)]
 
 
+IMAGE_LAYERS, IMAGE_MAX_DIM = 4, 4096
 GEOM_KEEP_SAR = 1  # mi355enc_geometry_t.flags: no aspect ratio from the geometry in the SPS
 OVERLAY_MAX_TEXT = 255
 _lib = None
@@ -167,6 +183,14 @@ def load():
         L.mi355enc_last_overlay.argtypes = [vp, vp, C.c_size_t]
         L.mi355enc_overlay_glyph.argtypes = [C.c_int, vp]
         L.mi355enc_stage_overlay.argtypes = [vp, C.c_char_p, C.POINTER(OverlayStyle), vp, vp]
+        L.mi355enc_set_image.argtypes = [vp, C.c_int, C.POINTER(ImageLayer)]
+        L.mi355enc_set_image_place.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.mi355enc_last_image.argtypes = [vp, C.c_int, C.POINTER(ImageInfo)]
+        L.mi355enc_stage_image.argtypes = [vp, C.POINTER(ImageLayer), C.c_int, vp, vp]
+        L.mi355enc_debug_image_bytes.restype = C.c_size_t
+        L.mi355enc_debug_image_bytes.argtypes = [vp]
+        L.mi355enc_image_pixel.argtypes = [C.c_int] * 5 + [vp]
+        L.mi355enc_image_load_pam.argtypes = [vp, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), vp, C.c_size_t]
         L.mi355enc_jpeg_info.argtypes = [vp, C.c_size_t, C.POINTER(JpegInfo)]
         L.mi355enc_jpeg_entropy_decode.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp, C.POINTER(JpegInfo)]
         L.mi355enc_submit_jpeg.argtypes = [vp, vp, C.c_size_t, C.c_int64, C.c_int]
@@ -424,6 +448,46 @@ def overlay_glyph(ch):
     if r:
         raise EncoderError("mi355enc_overlay_glyph(%d): %d" % (ch, r))
     return rows
+
+
+def image_layer(pixels, x=0, y=0, opacity=256, fmt=FMT_RGBX):
+    """An ImageLayer for pixels (h, w, 4) uint8 in byte order fmt; None: a layer without an image (off).  The array it points into is kept alive as `.keep`."""
+    im = ImageLayer()
+    im.fmt, im.x, im.y, im.opacity = int(fmt), int(x), int(y), int(opacity)
+    if pixels is not None:
+        a = np.asarray(pixels)
+        if not (a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 4 and a.strides[2] == 1 and a.strides[1] == 4 and a.strides[0] >= 4 * a.shape[1]):
+            a = np.ascontiguousarray(a, np.uint8)
+        assert a.ndim == 3 and a.shape[2] == 4, "pixels: (h, w, 4)"
+        im.keep = a
+        im.pixels, im.w, im.h, im.stride = a.ctypes.data, a.shape[1], a.shape[0], a.strides[0]
+    return im
+
+
+def image_pixel(matrix, full_range, r, g, b):
+    """(Y', Cb, Cr) of one colour as the image layers use it (host only)"""
+    out = np.zeros(3, np.uint8)
+    rc = load().mi355enc_image_pixel(int(matrix), int(full_range), int(r), int(g), int(b), out.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise EncoderError("mi355enc_image_pixel: %s (%d)" % (load().mi355enc_strerror(rc).decode(), rc))
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def load_pam(data, size_only=False):
+    """A Netpbm PAM (P7) file as bytes -> RGBA pixels (h, w, 4) uint8, or (w, h) with size_only (host only)"""
+    buf = np.frombuffer(bytes(data), np.uint8)
+    w, h = C.c_int(0), C.c_int(0)
+    L = load()
+    rc = L.mi355enc_image_load_pam(_p(buf) if buf.size else None, buf.size, C.byref(w), C.byref(h), None, 0)
+    if rc:
+        raise EncoderError("mi355enc_image_load_pam: %s (%d)" % (L.mi355enc_strerror(rc).decode(), rc))
+    if size_only:
+        return w.value, h.value
+    out = np.empty((h.value, w.value, 4), np.uint8)
+    rc = L.mi355enc_image_load_pam(_p(buf), buf.size, C.byref(w), C.byref(h), _p(out), out.nbytes)
+    if rc:
+        raise EncoderError("mi355enc_image_load_pam: %s (%d)" % (L.mi355enc_strerror(rc).decode(), rc))
+    return out
 
 
 def _text_bytes(text):
@@ -783,6 +847,34 @@ class Encoder:
         y, uv = np.ascontiguousarray(y, np.uint8).copy(), np.ascontiguousarray(uv, np.uint8).copy()
         assert y.shape == (self.mbh * 16, self.mbw * 16) and uv.shape == (self.mbh * 8, self.mbw * 16)
         self._chk(self.L.mi355enc_stage_overlay(self.h, _text_bytes(text), C.byref(st), _p(y), _p(uv)), "stage_overlay")
+        return y, uv
+
+    def set_image(self, layer, pixels, x=0, y=0, opacity=256, fmt=FMT_RGBX):
+        """The image blended into every picture submitted from now on as layer 0 .. 3: pixels (h, w, 4) uint8 with straight alpha in byte order fmt, its
+        top-left pixel at (x, y) of the coded visible picture, opacity 0 .. 256 (None: the layer is off).  The pixels are copied.  Thread-safe, no GPU call."""
+        im = image_layer(pixels, x, y, opacity, fmt)
+        self._chk(self.L.mi355enc_set_image(self.h, int(layer), C.byref(im) if pixels is not None else None), "set_image")
+
+    def set_image_place(self, layer, x, y, opacity=256):
+        """place and opacity of a layer's image from the next submitted picture on (EncoderError on a layer that is off)"""
+        self._chk(self.L.mi355enc_set_image_place(self.h, int(layer), int(x), int(y), int(opacity)), "set_image_place")
+
+    def last_image(self, layer=0):
+        """(w, h, x, y, opacity, serial) of what layer `layer` put into the last collected picture; all 0: nothing"""
+        info = ImageInfo()
+        self._chk(self.L.mi355enc_last_image(self.h, int(layer), C.byref(info)), "last_image")
+        return info.as_tuple()
+
+    def image_bytes(self):
+        """development: device memory held for images (0 until a picture with an active layer is submitted)"""
+        return int(self.L.mi355enc_debug_image_bytes(self.h))
+
+    def stage_image(self, layers, y, uv):
+        """The image kernels alone on host planes of the coded size: layers a list of up to four ImageLayer (image_layer()), blended in order; returns the blended copies."""
+        y, uv = np.ascontiguousarray(y, np.uint8).copy(), np.ascontiguousarray(uv, np.uint8).copy()
+        assert y.shape == (self.mbh * 16, self.mbw * 16) and uv.shape == (self.mbh * 8, self.mbw * 16)
+        arr = (ImageLayer * max(len(layers), 1))(*layers)
+        self._chk(self.L.mi355enc_stage_image(self.h, arr, len(layers), _p(y), _p(uv)), "stage_image")
         return y, uv
 
     def submit_device(self, y_ptr, y_stride, uv_ptr, uv_stride, pts=0, force_idr=False):

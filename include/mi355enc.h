@@ -418,6 +418,39 @@ int  mi355enc_stage_overlay(mi355enc_t *h, const char *text, const mi355enc_over
 /* (mi355enc_last_overlay: the text is cut to cap - 1 bytes and always terminated; the length returned is that of the whole text.
  * mi355enc_set_overlay_text and mi355enc_set_overlay_style may be called from any thread while another one submits: a picture carries exactly
  * one of the texts that were set.  With a text set, mi355enc_submit_device copies the caller's planes: they are never written.) */
+
+/* ---- image layers ----------------------------------------------
+ * Up to MI355ENC_IMAGE_LAYERS images with straight (not premultiplied) alpha -- a logo, a watermark, a scoreboard bitmap -- blended into every
+ * submitted picture on the GPU, in place of a `gdkpixbufoverlay` in front of the encoder.  A layer is drawn 1:1 (never scaled) with its top-left
+ * pixel at (x, y) of the coded visible picture, luma samples, any integer in -16384 .. 16384; what falls outside the picture is clipped.  Layers
+ * are blended in index order, after conversion, scaling and orientation (the image stays upright) and before the text overlay (text is on top) and
+ * the padding to whole macroblocks: the stream is byte for byte that of the same pictures with the images already in them.  fmt: one of the four
+ * 4-byte orders, the byte they call X being A -- MI355ENC_FMT_BGRX = BGRA, RGBX = RGBA, XRGB = ARGB, XBGR = ABGR.  The colour is converted with the
+ * matrix and range RGB input is converted with (the colorimetry setter's rule); a matrix code RGB input refuses makes the submit of a picture with an
+ * active layer fail with MI355ENC_ERR_ARG.  opacity 0 .. 256 scales the image's alpha: a = (A * opacity + 128) >> 8.  With no layer ever set nothing
+ * is allocated or launched. */
+#define MI355ENC_IMAGE_LAYERS 4
+#define MI355ENC_IMAGE_MAX_DIM 4096
+typedef struct { int fmt; const uint8_t *pixels; int w, h, stride;   /* stride in bytes, >= 4 w */
+                 int x, y, opacity; } mi355enc_image_layer_t;
+typedef struct { int w, h, x, y, opacity; uint32_t serial; } mi355enc_image_info_t;
+/* img NULL or pixels NULL: the layer is off.  Copies the pixels; thread-safe against a running submit; no GPU call; any time.  Every successful call
+ * on a layer adds one to that layer's serial.  ERR_ARG (the handle stays as it was): no handle, a layer outside 0 .. 3, a fmt outside the four orders,
+ * sizes outside 1 .. 4096, stride < 4 w, a place outside -16384 .. 16384, an opacity outside 0 .. 256. */
+int mi355enc_set_image(mi355enc_t *h, int layer, const mi355enc_image_layer_t *img);
+/* place and opacity of a layer's image: any time, latched per picture; ERR_STATE on a layer that is off */
+int mi355enc_set_image_place(mi355enc_t *h, int layer, int x, int y, int opacity);
+/* what was blended into the last collected picture for one layer; serial 0 and w = h = 0: nothing */
+int mi355enc_last_image(mi355enc_t *h, int layer, mi355enc_image_info_t *info);
+/* the kernels alone (tests): coded-size host planes, stride 16*mbw, in place; layers 0 .. n - 1, n <= 4 (an entry without pixels is skipped);
+ * ERR_STATE with pictures pending */
+int mi355enc_stage_image(mi355enc_t *h, const mi355enc_image_layer_t *layers, int n, uint8_t *y, uint8_t *uv);
+size_t mi355enc_debug_image_bytes(const mi355enc_t *h); /* device memory held for images: 0 until a picture with an active layer is submitted */
+/* host only: Y', Cb, Cr of one colour as the layers use it; ERR_ARG for a matrix outside 1, 5, 6, 9, a range outside 0, 1 or a component outside 0 .. 255 */
+int mi355enc_image_pixel(int matrix, int full_range, int r, int g, int b, uint8_t ycbcr[3]);
+/* host only: a Netpbm PAM (P7) file, TUPLTYPE RGB_ALPHA with DEPTH 4 or RGB with DEPTH 3 (alpha 255), MAXVAL 255, sizes 1 .. 4096, as RGBA into
+ * rgba (cap bytes of room).  rgba NULL: only *w and *h.  ERR_OVERFLOW: cap is too small; ERR_ARG: anything else.  (PNG would need an inflate: out of scope.) */
+int mi355enc_image_load_pam(const uint8_t *data, size_t len, int *w, int *h, uint8_t *rgba, size_t cap);
 size_t mi355enc_max_au_bytes(const mi355enc_t *h);
 const char *mi355enc_strerror(int code);
 int mi355enc_abi_version(void);
@@ -476,7 +509,8 @@ int mi355enc_stage_deblock(mi355enc_t *h, uint8_t *rec_y, uint8_t *rec_uv, const
  * 11 the quality-metrics launch (slot 0's source surfaces against reconstruction buffer 1),
  * 12 the JPEG launch for the handle's input size as 4:2:2, on whatever slot 0's coefficient buffer holds,
  * 13 the orientation launch at the handle's size (the handle's method; 90r on a handle without one), on whatever slot 0's raw staging buffer holds,
- * 14 the scale / geometry launch for an NV12 picture of the handle's input size (MI355ENC_ERR_STATE without mi355enc_set_input_size / _geometry), likewise.
+ * 14 the scale / geometry launch for an NV12 picture of the handle's input size (MI355ENC_ERR_STATE without mi355enc_set_input_size / _geometry), likewise,
+ * 15 the blend launch of image layer 0 at its current place into slot 0's source surfaces (MI355ENC_ERR_STATE without an image on layer 0).
  * Uses whatever the handle's surfaces currently hold.  Returns average ms per launch. */
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms);
 
