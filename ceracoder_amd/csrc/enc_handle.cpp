@@ -138,6 +138,7 @@ int mi355enc_open(const mi355enc_cfg_t *cfg, mi355enc_t **out) {
     h->ov_len = 0; h->ov_last_have = 0; h->ov_last_len = 0; mi355enc_overlay_default_style(&h->ov_style);
     for (int l = 0; l < MI355ENC_IMAGE_LAYERS; l++) { h->img_cur[l] = nullptr; h->img_x[l] = h->img_y[l] = 0; h->img_op[l] = 256; h->img_serial[l] = 0; }
     h->img_bufs = nullptr; h->img_dev_bytes = 0; memset(h->img_last, 0, sizeof h->img_last);
+    snapshot_init(h);
     h->q_on = false; h->q_have = false; h->d_qacc = nullptr; h->h_qres = nullptr; for (int i = 0; i < NSLOT; i++) h->ev_q[i] = nullptr; memset(&h->q_last, 0, sizeof h->q_last); memset(&h->q_tot, 0, sizeof h->q_tot);
     for (int i = 0; i < NSET; i++) { h->g_intra[i] = h->g_deblock[i] = nullptr; h->d_ctx2[i] = nullptr; h->d_surf[i] = nullptr; h->d_idec2[i] = nullptr; h->d_mbi_set[i] = nullptr; h->d_levels_set[i] = nullptr; h->d_qp_off[i] = nullptr; }
     h->prev_slot = nullptr;
@@ -348,6 +349,7 @@ void mi355enc_close(mi355enc_t *h) {
     if (h->d_off) (void)hipFree(h->d_off);
     scale_free(h);
     quality_free(h);
+    snapshot_free(h);
     image_free(h);
     for (int k = 0; k < NSET; k++) {
         if (h->d_surf[k]) (void)hipFree(h->d_surf[k]);

@@ -6,6 +6,7 @@
 //   enc_image.cpp    image layers: setters, latch, upload + prepare, blend launches, retirement
 //   enc_orient.cpp    orientation of the input picture: setter, the slot's pre-orientation picture, launch, its stage entry points
 //   enc_jpeg.cpp      MJPEG input: coefficient buffers, host decode, transfer + launch, its stage entry points
+//   enc_snapshot.cpp  JPEG stills: request / take, the blocks the levels land in, the launch, its stage entry points
 //   enc_stages.cpp    single-stage entry points (parity tests, probes) and the host-only stages
 #ifndef MI355_ENC_INTERNAL_HPP
 #define MI355_ENC_INTERNAL_HPP
@@ -25,6 +26,7 @@
 
 #include "h264_host.h"
 #include "mi355enc_dev.h"
+#include "snapshot_host.h"
 
 #define HIPCHK(expr)                                                                                 \
     do {                                                                                             \
@@ -52,6 +54,19 @@ struct image_t {
     uint8_t *host;      // malloc: the caller's pixels, rows of 4 w bytes (freed once they are in pinned staging)
     image_buf_t *buf;   // null until the first picture that carries the image is submitted
     int fmt, w, h, refs;
+};
+
+// One still's landing place (mi355enc_request_snapshot): pinned host memory -- the quality's snapshot_tab_t (SNAP_TAB_BYTES), then the levels,
+// then one hint byte per block -- and the table's copy on the device.  state (under mi355enc::snap_mu): 0 free, 1 a picture in flight owns it, 2 the ready
+// still, 3 replaced by a newer still while `readers` takers were still coding it (the last one frees it).
+#define SNAP_TAB_BYTES 1024
+#define SNAP_BLOCKS (NSLOT + 3) /* one per picture in flight, the ready one, one replaced while being read; the last one belongs to the stage entry points */
+struct snap_block_t {
+    uint8_t *h_mem; void *d_tab; size_t cap;
+    int state, readers, ow, oh;
+    size_t nblk;
+    uint16_t qt[2][64];
+    mi355enc_snapshot_info_t info;
 };
 
 struct slot_t {
@@ -85,6 +100,8 @@ struct slot_t {
     int ov_len; char ov_text[256]; mi355enc_overlay_style_t ov_style;
     // image layers: what submit latched for this picture and blended into its source surfaces (img[l] null: nothing of layer l); a recovery keeps it likewise
     image_t *img[MI355ENC_IMAGE_LAYERS]; int img_x[MI355ENC_IMAGE_LAYERS], img_y[MI355ENC_IMAGE_LAYERS], img_op[MI355ENC_IMAGE_LAYERS]; uint32_t img_serial[MI355ENC_IMAGE_LAYERS];
+    // stills: the block this picture's still lands in, + 1 (0: the picture is not armed), and the request it was armed with; a recovery keeps both
+    int snap; mi355enc_snapshot_req_t snap_req;
 };
 
 struct mi355enc {
@@ -204,6 +221,17 @@ struct mi355enc {
     image_buf_t *img_bufs;
     size_t img_dev_bytes;
     mi355enc_image_info_t img_last[MI355ENC_IMAGE_LAYERS];
+    // stills: the request the control thread made last (armed: the next submitted picture takes it), the blocks, the ready one (-1: none),
+    // all under snap_mu; per slot the event behind its still's launch, which collect() waits for (created with the first armed picture); recovering: recover()
+    // is enqueueing the pictures in flight again (they keep their blocks)
+    std::mutex snap_mu;
+    std::atomic<bool> snap_armed; // (read without the mutex by every enqueue_picture: with no request the picture path takes no lock)
+    bool recovering;
+    mi355enc_snapshot_req_t snap_req, snap_last_req;
+    snap_block_t snap_blk[SNAP_BLOCKS];
+    int snap_ready;
+    std::atomic<size_t> snap_bytes;
+    hipEvent_t ev_snap[NSLOT];
     // the entropy-coding worker (started by open() when pipeline_depth >= 1)
     std::thread wk;
     std::mutex wk_mu;
@@ -290,6 +318,15 @@ void jpeg_free(slot_t *s);
 int jpeg_decode_host(mi355enc_t *h, slot_t *s, const uint8_t *data, size_t len, mi355enc_jpeg_info_t *info); // parse, check the size, entropy decode into the slot's pinned buffer
 int jpeg_enqueue(mi355enc_t *h, slot_t *s, const mi355enc_jpeg_info_t *info, hipStream_t up);               // transfer + launch (+ scale) into the slot's staging surfaces
 int jpeg_time_launch(mi355enc_t *h, slot_t *s);
+// enc_snapshot.cpp
+void snapshot_latch(mi355enc_t *h, slot_t *s);  // enqueue_picture of a newly submitted picture: an armed request becomes the slot's, with a block to land in
+// the slot's still from NV12 planes (the source, or the reconstruction) behind everything enqueued on st so far; records the slot's event
+int snapshot_enqueue(mi355enc_t *h, slot_t *s, const uint8_t *y, const uint8_t *uv, int stride, hipStream_t st);
+int snapshot_collect(mi355enc_t *h, slot_t *s); // waits for the slot's still and makes it the ready one
+int snapshot_time_prepare(mi355enc_t *h);       // mi355enc_time_stage 16: the stage block and its tables
+int snapshot_time_launch(mi355enc_t *h, slot_t *s);
+void snapshot_init(mi355enc_t *h);
+void snapshot_free(mi355enc_t *h);
 // enc_csc.cpp
 void csc_resolve(mi355enc_t *h); // fills csc_coef / csc_ok from col_mat, col_full and the coded size
 #endif

@@ -140,6 +140,7 @@ static int run_p_back(mi355enc_t *h, const frame_ctx_t *hc, slot_t *s, int prof,
 // Enqueue every device step of one picture whose source is described by (src_y, src_uv, src_stride).  Anything the caller
 // uploaded for this picture was enqueued on the same stream.
 int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_t *src_uv, int src_stride, int64_t pts, int force_idr) {
+    if (!h->recovering) snapshot_latch(h, s); // stills: an armed request becomes this picture's (a picture recover() enqueues again keeps what it had)
     const int idr = force_idr || !h->have_ref || (!h->ir_on && h->frames_since_idr >= h->cfg.gop) || // (intra refresh: no periodic IDR picture)
                     (h->n_submitted == h->sc_force_at && h->frames_since_idr >= sc_lag(h)); // scene-cut recovery, see collect(): not when an IDR picture came in between
     if (idr) { h->frames_since_idr = 0; h->ir_pos = 0; h->ir_R = 0; h->ir_skip_owed = 0; }
@@ -188,6 +189,10 @@ int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_
             HIPCHK(hipStreamWaitEvent(h->stream, s->ev_front, 0));
             if (h->dbI_busy[nxt]) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_dbI[nxt], 0)); h->dbI_busy[nxt] = 0; }
             int r = quality_enqueue(h, s, src_y, src_uv, src_stride, nxt, h->stream); if (r) return r;
+        }
+        if (s->snap && s->snap_req.what == 1) { // a still of what a decoder shows: the reference the picture repeats, behind that picture's deblocking
+            if (h->dbI_busy[nxt]) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_dbI[nxt], 0)); h->dbI_busy[nxt] = 0; }
+            int r = snapshot_enqueue(h, s, h->d_rec_y[nxt], h->d_rec_uv[nxt], h->W, h->stream); if (r) return r;
         }
     } else {
         c->src_y = src_y; c->src_uv = src_uv; c->src_stride = src_stride;
@@ -273,6 +278,7 @@ int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_
         if (isplit) {
             int r = run_deblock(h, ci, c, h->istream, nullptr, h->d_iband_done + (size_t)nxt * h->mbh, h->d_db_done + (size_t)nxt * nbd); if (r) return r;
             if (h->q_on) { r = quality_enqueue(h, s, src_y, src_uv, src_stride, nxt, h->istream); if (r) return r; } // in front of the event the buffer's next writer waits for
+            if (s->snap && s->snap_req.what == 1) { r = snapshot_enqueue(h, s, h->d_rec_y[nxt], h->d_rec_uv[nxt], h->W, h->istream); if (r) return r; } // likewise
             HIPCHK(hipEventRecord(h->ev_dbI[nxt], h->istream));
             h->dbI_busy[nxt] = 1;
         } else if (!fip) { int r = run_deblock(h, ci, c, mst, (split || (pgate && c->intra_p)) ? h->d_ip_progress : nullptr, nullptr, h->d_db_done + (size_t)nxt * nbd, prows != 0); if (r) return r; }
@@ -282,6 +288,8 @@ int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_
         // either behind it in the main stream's order, or a gated fused P stage on the intra stream, which starts only when the deblocking launch of the picture
         // between the two is on the chip -- a launch that sits behind this one in the main stream.
         if (h->q_on && !isplit) { int r = quality_enqueue(h, s, src_y, src_uv, src_stride, nxt, mst); if (r) return r; }
+        // A still of the reconstruction sits in the same place, for the same reason; with metrics on, both launches sit there.
+        if (s->snap && s->snap_req.what == 1 && !isplit) { int r = snapshot_enqueue(h, s, h->d_rec_y[nxt], h->d_rec_uv[nxt], h->W, mst); if (r) return r; }
         // Hand-over, enqueued after the deblocking launches so that it cannot be dispatched ahead of them: the device packs the non-zero
         // blocks straight into the pinned host buffer while the band deblocker runs.
         hipStream_t pst = h->cstream;
@@ -290,6 +298,9 @@ int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(s->done, pst));
     }
+    // A still of the coded source: on the front stream, where the source is in place, behind everything of this picture that runs there (it delays none of it);
+    // the source stays valid until the picture's collect() returns, and collect() waits for the still.
+    if (s->snap && s->snap_req.what == 0) { int r = snapshot_enqueue(h, s, src_y, src_uv, src_stride, h->fstream); if (r) return r; }
     h->n_submitted++;
     s->is_idr = idr; s->qp = qp; s->drop = drop; s->frame_num = h->frames_since_idr; s->idr_pic_id = h->idr_count & 0xFFFF; s->ir_start = ir_j == 0;
     s->src_y = src_y; s->src_uv = src_uv; s->src_stride = src_stride; s->force_idr = force_idr;
@@ -492,12 +503,14 @@ static int recover(mi355enc_t *h, unsigned code) {
     h->n_submitted -= (uint64_t)n; h->head = h->tail; h->pending = 0; h->have_ref = 0;
     // a picture submitted under a constant-QP override is coded again under that one, not under whatever mi355enc_set_fixed_qp() has said since
     const int now_qp = h->fixed_qp.load(std::memory_order_relaxed), now_drop = h->fixed_drop.load(std::memory_order_relaxed);
+    h->recovering = true;
     for (int i = 0; i < n; i++) {
         if (again[i].fixed_qp >= 0) { h->fixed_qp.store(again[i].fixed_qp, std::memory_order_relaxed); h->fixed_drop.store(again[i].fixed_drop, std::memory_order_relaxed); }
         int r = enqueue_picture(h, &h->slot[h->head], again[i].y, again[i].uv, again[i].stride, again[i].pts, i == 0 ? 1 : again[i].force_idr);
         h->fixed_qp.store(now_qp, std::memory_order_relaxed); h->fixed_drop.store(now_drop, std::memory_order_relaxed);
-        if (r) return r;
+        if (r) { h->recovering = false; return r; }
     }
+    h->recovering = false;
     return MI355ENC_OK;
 }
 
@@ -717,6 +730,7 @@ int mi355enc_collect(mi355enc_t *h, uint8_t *out, size_t out_cap, size_t *out_le
         h->st.ms_entropy += now_ms() - t1;
     }
     if (h->q_on) { int r = quality_collect(h, s); if (r) return r; } // (a picture that came back through recover(): the re-encode's)
+    if (s->snap) { int r = snapshot_collect(h, s); if (r) return r; } // an armed picture: its still becomes the one mi355enc_take_snapshot codes
     *out_len = n + m;
     if (is_keyframe) *is_keyframe = s->is_idr || s->ir_start; // (intra refresh: a cycle's first picture is a recovery point)
     if (pts) *pts = s->pts;

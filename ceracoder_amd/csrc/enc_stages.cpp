@@ -219,7 +219,7 @@ int mi355enc_debug_trip_wait(mi355enc_t *h, unsigned code) {
     return MI355ENC_OK;
 }
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
-    if (!h || !avg_ms || iters < 1 || stage < 0 || stage > 15) return MI355ENC_ERR_ARG;
+    if (!h || !avg_ms || iters < 1 || stage < 0 || stage > 16) return MI355ENC_ERR_ARG;
     if (stage == 14 && !h->d_scale_tab) return MI355ENC_ERR_STATE; // (mi355enc_set_input_size or mi355enc_set_input_geometry first)
     if (h->pending) return MI355ENC_ERR_STATE;
     HIPCHK(hipSetDevice(h->cfg.device_id));
@@ -241,6 +241,7 @@ int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
         HIPCHK(hipMemsetAsync(s->d_raw, 0x55, raw_bytes(h), h->stream));
     }
     if (stage == 12) { int r = jpeg_alloc(h, s); if (r) return r; }
+    if (stage == 16) { int r = snapshot_time_prepare(h); if (r) return r; } // (the block of the stage entry points)
     const scale_plan_t *scale_pl = stage == 14 ? scale_plan_for(h, s, h->stream) : nullptr; // (a stale slot copy of the tables travels here, not inside the timed loop)
     if (stage == 14 && !scale_pl) return MI355ENC_ERR_HIP;
     image_args_t img_a; // stage 15: layer 0's image on the device and prepared here, not inside the timed loop
@@ -270,6 +271,7 @@ int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
                 if (k_launch_scale(MI355ENC_FMT_NV12, s->d_raw, s->d_raw + (size_t)ds * h->in_h, nullptr, ds, ds, 0, t.y, t.uv, t.W, t.H, scale_pl, h->stream)) return MI355ENC_ERR_ARG;
             }
             else if (stage == 15) k_launch_image_blend(&img_a, h->stream);
+            else if (stage == 16) { int r = snapshot_time_launch(h, s); if (r) return r; }
             else if (stage == 10) k_launch_intra_p(h->slot[0].h_ctx, h->mbw, h->mbh, h->d_ip_progress, h->d_ip_strips, err_word(h), h->stream);
             else if (stage >= 5) {
                 const int w = h->cfg.width, ht = h->cfg.height, r0 = stage == 5 ? (w + 15) & ~15 : (2 * w + 15) & ~15, r1 = (w / 2 + 15) & ~15;

@@ -27,7 +27,10 @@
 #include <gst/gst.h>
 #include <gst/video/gstvideoencoder.h>
 #include <gst/video/video.h>
+#include <errno.h>
+#include <glib/gstdio.h>
 #include <math.h>
+#include <stdio.h>
 #include <string.h>
 
 #include "../../include/mi355enc.h"
@@ -92,6 +95,24 @@ typedef struct {
     GstClockTime last_pts;
     /* where the streaming thread's time goes, per stage (microseconds, summed; printed with stats=true): what separates the element's rate from the C ABI's */
     gint64 us_map, us_submit, us_collect, us_output, us_push, us_frames;
+    /* JPEG stills of the running stream (mi355enc_request_snapshot / _take_snapshot).  Properties (object lock): the file (empty: off), the
+     * interval in ms of stream time, quality, reduction, source (0 the coded source, 1 the decoded picture).  The streaming thread arms a picture every interval and
+     * wakes the helper for the collects that may have completed it; the helper -- never the streaming thread -- takes the still (the Huffman coding runs there),
+     * writes location.tmp, renames it over location and posts `mi355-snapshot`.  snap_enc_mu: held by the helper while it uses the encoder and by whoever
+     * closes or opens it (s->enc and snap_gen change under it, taken in front of the object lock).  snap_mu / snap_cv: the helper's wake-ups, and snap_count.
+     * snap_next: object lock.  snap_gen counts the encoders opened: a new one resets what the helper remembers of the last still it wrote. */
+    gchar *snap_location;
+    guint snap_interval;
+    gint snap_quality, snap_reduce, snap_source;
+    GstClockTime snap_next;   /* stream time of the next picture to arm (NONE: the next one) */
+    gint snap_watch;          /* collects to come that may complete an armed picture */
+    GMutex snap_mu, snap_enc_mu;
+    GCond snap_cv;
+    GThread *snap_thread;
+    gint snap_wake;
+    gboolean snap_stop;
+    guint64 snap_count;
+    guint snap_gen;
 } GstMi355H264Enc;
 typedef struct { GstVideoEncoderClass parent_class; } GstMi355H264EncClass;
 
@@ -103,7 +124,8 @@ enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME
        PROP_SPEED_PRESET, PROP_STATS, PROP_DCT8X8, PROP_THREADS, PROP_SCENECUT, PROP_VBV, PROP_INTRA_IN_P, PROP_EXCLUSIVE, PROP_PINNED_INPUT, PROP_AQ_MODE, PROP_SINGLE_STREAM, PROP_INTRA_SLICES, PROP_I8X8, PROP_SLICES, PROP_SLICE_DEBLOCK, PROP_DCT8X8_ADAPTIVE, PROP_INTRA_REFRESH, PROP_WIDTH, PROP_HEIGHT, PROP_QUALITY_STATS,
        PROP_OV_TEXT, PROP_OV_HALIGN, PROP_OV_VALIGN, PROP_OV_XPAD, PROP_OV_YPAD, PROP_OV_SCALE, PROP_OV_SHADED, PROP_VIDEO_DIRECTION,
        PROP_CROP_LEFT, PROP_CROP_RIGHT, PROP_CROP_TOP, PROP_CROP_BOTTOM, PROP_ADD_BORDERS, PROP_UPSCALE, PROP_BORDER_COLOR,
-       PROP_IMG_LOCATION, PROP_IMG_X, PROP_IMG_Y, PROP_IMG_ALPHA };
+       PROP_IMG_LOCATION, PROP_IMG_X, PROP_IMG_Y, PROP_IMG_ALPHA,
+       PROP_SNAP_LOCATION, PROP_SNAP_INTERVAL, PROP_SNAP_QUALITY, PROP_SNAP_REDUCE, PROP_SNAP_SOURCE };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
     GST_STATIC_CAPS("video/x-raw, format=(string){ NV12, I420, YUY2, UYVY, Y42B, Y444, YV12, NV21, BGRx, RGBx, xRGB, xBGR, BGRA, RGBA, ARGB, ABGR, BGR, RGB }, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]; "
@@ -111,6 +133,13 @@ static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_
 static GstStaticPadTemplate src_tmpl = GST_STATIC_PAD_TEMPLATE("src", GST_PAD_SRC, GST_PAD_ALWAYS,
     GST_STATIC_CAPS("video/x-h264, stream-format=(string)byte-stream, alignment=(string)au, profile=(string){ constrained-baseline, high }, "
                     "width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]"));
+
+static GType snapshot_source_type(void) {
+    static GType t = 0;
+    static const GEnumValue v[] = {{0, "The coded source", "source"}, {1, "The decoded picture", "decoded"}, {0, NULL, NULL}};
+    if (!t) t = g_enum_register_static("GstMi355H264EncSnapshotSource", v);
+    return t;
+}
 
 /* x264enc's speed-preset enum, accepted so that an x264enc line converts by changing only the factory name */
 static GType speed_preset_type(void) {
@@ -231,6 +260,11 @@ static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *
     if (id == PROP_IMG_LOCATION) { image_set_location(s, g_value_get_string(val)); return; }
     GST_OBJECT_LOCK(s);
     switch (id) {
+    case PROP_SNAP_LOCATION: g_free(s->snap_location); s->snap_location = g_value_dup_string(val); s->snap_next = GST_CLOCK_TIME_NONE; break;
+    case PROP_SNAP_INTERVAL: s->snap_interval = g_value_get_uint(val); break;
+    case PROP_SNAP_QUALITY: s->snap_quality = g_value_get_int(val); break;
+    case PROP_SNAP_REDUCE: { const gint r = g_value_get_int(val); if (r == 1 || r == 2 || r == 4 || r == 8) s->snap_reduce = r; else GST_WARNING_OBJECT(s, "snapshot-reduce %d: not 1, 2, 4 or 8; stays %d", r, s->snap_reduce); break; }
+    case PROP_SNAP_SOURCE: s->snap_source = g_value_get_enum(val); break;
     case PROP_IMG_X: s->img_x = g_value_get_int(val); image_forward(s, FALSE); break;
     case PROP_IMG_Y: s->img_y = g_value_get_int(val); image_forward(s, FALSE); break;
     case PROP_IMG_ALPHA: s->img_alpha = g_value_get_double(val); image_forward(s, FALSE); break;
@@ -284,6 +318,11 @@ static void get_property(GObject *obj, guint id, GValue *val, GParamSpec *ps) {
     effective_tools(s, &t); /* a tool property reads as what the encoder will use: the explicit value, or the preset's */
     switch (id) {
     case PROP_IMG_LOCATION: g_value_set_string(val, s->img_location ? s->img_location : ""); break;
+    case PROP_SNAP_LOCATION: g_value_set_string(val, s->snap_location ? s->snap_location : ""); break;
+    case PROP_SNAP_INTERVAL: g_value_set_uint(val, s->snap_interval); break;
+    case PROP_SNAP_QUALITY: g_value_set_int(val, s->snap_quality); break;
+    case PROP_SNAP_REDUCE: g_value_set_int(val, s->snap_reduce); break;
+    case PROP_SNAP_SOURCE: g_value_set_enum(val, s->snap_source); break;
     case PROP_IMG_X: g_value_set_int(val, s->img_x); break;
     case PROP_IMG_Y: g_value_set_int(val, s->img_y); break;
     case PROP_IMG_ALPHA: g_value_set_double(val, s->img_alpha); break;
@@ -333,9 +372,11 @@ static void get_property(GObject *obj, guint id, GValue *val, GParamSpec *ps) {
 
 static void close_encoder(GstMi355H264Enc *s) {
     mi355enc_t *e;
+    g_mutex_lock(&s->snap_enc_mu); /* (the stills' helper is not inside the encoder from here on) */
     GST_OBJECT_LOCK(s);
     e = s->enc; s->enc = NULL;
     GST_OBJECT_UNLOCK(s);
+    g_mutex_unlock(&s->snap_enc_mu);
     if (e) {
         if (s->stats) {
             mi355enc_stats_t st;
@@ -350,12 +391,105 @@ static void close_encoder(GstMi355H264Enc *s) {
             if (mi355enc_quality_totals(e, &q) == 0 && q.pictures)
                 g_printerr("{\"element\":\"mi355h264enc\",\"quality\":{\"pictures\":%" G_GUINT64_FORMAT ",\"psnr_y\":%.3f,\"psnr_cb\":%.3f,\"psnr_cr\":%.3f,\"ssim\":%.5f}}\n",
                            q.pictures, q.psnr[0], q.psnr[1], q.psnr[2], q.ssim);
+            g_mutex_lock(&s->snap_mu);
+            const guint64 n_stills = s->snap_count;
+            g_mutex_unlock(&s->snap_mu);
+            if (n_stills) g_printerr("{\"element\":\"mi355h264enc\",\"snapshots\":%" G_GUINT64_FORMAT "}\n", n_stills);
         }
         mi355enc_close(e);
     }
 }
+/* ---- JPEG stills: the helper thread */
+static void snapshot_write_file(GstMi355H264Enc *s, const guint8 *data, gsize len, const mi355enc_snapshot_info_t *info) {
+    GST_OBJECT_LOCK(s);
+    gchar *loc = g_strdup(s->snap_location ? s->snap_location : "");
+    GST_OBJECT_UNLOCK(s);
+    if (*loc) {
+        gchar *tmp = g_strconcat(loc, ".tmp", NULL);
+        int why = 0; /* errno of the step that failed first */
+        FILE *f = fopen(tmp, "wb");
+        gboolean ok = f != NULL;
+        if (!ok) why = errno;
+        if (ok && fwrite(data, 1, len, f) != len) { ok = FALSE; why = errno; }
+        if (f && fclose(f) != 0 && ok) { ok = FALSE; why = errno; }
+        if (ok && g_rename(tmp, loc) != 0) { ok = FALSE; why = errno; }
+        if (ok) {
+            g_mutex_lock(&s->snap_mu);
+            s->snap_count++;
+            g_mutex_unlock(&s->snap_mu);
+            gst_element_post_message(GST_ELEMENT(s), gst_message_new_element(GST_OBJECT(s), gst_structure_new("mi355-snapshot", "location", G_TYPE_STRING, loc,
+                "width", G_TYPE_INT, info->width, "height", G_TYPE_INT, info->height, "pts", G_TYPE_UINT64, (guint64)info->pts, "bytes", G_TYPE_UINT64, (guint64)len, NULL)));
+        } else GST_ELEMENT_WARNING(s, RESOURCE, WRITE, ("mi355h264enc: cannot write the still %s", loc), ("%s", g_strerror(why))); /* a warning, never an error: the stream goes on */
+        g_free(tmp);
+    }
+    g_free(loc);
+}
+static gpointer snapshot_helper(gpointer u) {
+    GstMi355H264Enc *s = (GstMi355H264Enc *)u;
+    guint8 *buf = NULL;
+    gsize cap = 0;
+    gboolean have_last = FALSE;
+    guint64 last_index = 0;
+    gint64 last_pts = 0;
+    guint gen = 0;
+    for (;;) {
+        g_mutex_lock(&s->snap_mu);
+        while (!s->snap_wake && !s->snap_stop) g_cond_wait(&s->snap_cv, &s->snap_mu);
+        const gboolean stop = s->snap_stop;
+        s->snap_wake = 0;
+        g_mutex_unlock(&s->snap_mu);
+        if (stop) break;
+        mi355enc_snapshot_info_t info;
+        size_t len = 0;
+        int r = MI355ENC_ERR_STATE;
+        g_mutex_lock(&s->snap_enc_mu);
+        if (s->snap_gen != gen) { gen = s->snap_gen; have_last = FALSE; } /* another encoder: its pictures count from 0 again */
+        if (s->enc) {
+            r = mi355enc_take_snapshot(s->enc, buf, cap, &len, &info);
+            if (r == MI355ENC_ERR_OVERFLOW && !(have_last && info.index == last_index && info.pts == last_pts)) { /* a new still that needs more room */
+                g_free(buf); cap = len + len / 4; buf = (guint8 *)g_malloc(cap);
+                r = mi355enc_take_snapshot(s->enc, buf, cap, &len, &info);
+            }
+        }
+        g_mutex_unlock(&s->snap_enc_mu);
+        if (r != MI355ENC_OK || (have_last && info.index == last_index && info.pts == last_pts)) continue; /* nothing ready, or the still already written */
+        have_last = TRUE; last_index = info.index; last_pts = info.pts;
+        snapshot_write_file(s, buf, len, &info);
+    }
+    g_free(buf);
+    return NULL;
+}
+static void snapshot_wake(GstMi355H264Enc *s) {
+    g_mutex_lock(&s->snap_mu);
+    if (!s->snap_thread) { s->snap_stop = FALSE; s->snap_thread = g_thread_new("mi355-snapshot", snapshot_helper, s); }
+    s->snap_wake = 1;
+    g_cond_signal(&s->snap_cv);
+    g_mutex_unlock(&s->snap_mu);
+}
+static void snapshot_stop(GstMi355H264Enc *s) {
+    g_mutex_lock(&s->snap_mu);
+    GThread *t = s->snap_thread;
+    s->snap_thread = NULL; s->snap_stop = TRUE;
+    g_cond_signal(&s->snap_cv);
+    g_mutex_unlock(&s->snap_mu);
+    if (t) g_thread_join(t);
+}
+/* streaming thread, in front of a picture's submit: every snapshot-interval of stream time one picture is armed */
+static void snapshot_maybe_arm(GstMi355H264Enc *s, GstVideoCodecFrame *frame) {
+    GST_OBJECT_LOCK(s);
+    const gboolean on = s->snap_location && *s->snap_location;
+    const mi355enc_snapshot_req_t req = {s->snap_source, s->snap_reduce, s->snap_quality};
+    const GstClockTime step = (GstClockTime)s->snap_interval * GST_MSECOND, pts = frame->pts;
+    const gboolean due = !(GST_CLOCK_TIME_IS_VALID(s->snap_next) && GST_CLOCK_TIME_IS_VALID(pts) && pts < s->snap_next);
+    if (on && due) s->snap_next = GST_CLOCK_TIME_IS_VALID(pts) ? pts + step : GST_CLOCK_TIME_NONE;
+    GST_OBJECT_UNLOCK(s);
+    if (!on || !due) return;
+    if (mi355enc_request_snapshot(s->enc, &req) != MI355ENC_OK) return;
+    s->snap_watch = s->open_depth + 2;
+}
 static gboolean enc_stop(GstVideoEncoder *ve) {
     GstMi355H264Enc *s = GST_MI355H264ENC(ve);
+    snapshot_stop(s);
     close_encoder(s);
     if (s->input_state) { gst_video_codec_state_unref(s->input_state); s->input_state = NULL; }
     g_free(s->au_buf); s->au_buf = NULL;
@@ -535,8 +669,10 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
                           ("mi355enc_open(%dx%d from %dx%d input, device-id=%d) returned %d", cfg.width, cfg.height, in_w, in_h, cfg.device_id, r));
         return FALSE;
     }
+    g_mutex_lock(&s->snap_enc_mu); /* (the stills' helper sees the encoder change under this one; same order as close_encoder) */
     GST_OBJECT_LOCK(s);
     s->enc = e;
+    s->snap_gen++; s->snap_next = GST_CLOCK_TIME_NONE; s->snap_watch = 0; /* stills start over with the new encoder */
     s->open_depth = cfg.pipeline_depth;
     s->open_direction = dir;
     s->open_geom = geom;
@@ -546,6 +682,7 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     overlay_forward(s);                     /* ... nor the overlay's text and style, set before the device was opened */
     image_forward(s, TRUE);                 /* ... nor the image layer */
     GST_OBJECT_UNLOCK(s);
+    g_mutex_unlock(&s->snap_enc_mu);
     s->max_au = mi355enc_max_au_bytes(e);
     g_free(s->au_buf);
     s->au_buf = g_malloc(s->max_au);
@@ -593,6 +730,7 @@ static GstFlowReturn collect_into(GstMi355H264Enc *s, GstVideoCodecFrame *frame)
         gst_video_encoder_finish_frame(ve, frame);
         return GST_FLOW_ERROR;
     }
+    if (s->snap_watch > 0) { s->snap_watch--; snapshot_wake(s); } /* an armed picture may just have been collected: the helper looks */
     GstFlowReturn fr = gst_video_encoder_allocate_output_frame(ve, frame, len);
     if (fr != GST_FLOW_OK) { gst_video_encoder_finish_frame(ve, frame); return fr; }
     gst_buffer_fill(frame->output_buffer, 0, s->au_buf, len);
@@ -644,6 +782,7 @@ static GstFlowReturn enc_handle_frame(GstVideoEncoder *ve, GstVideoCodecFrame *f
         GST_DEBUG_OBJECT(s, "input picture flagged DROPPABLE (pts %" GST_TIME_FORMAT "): not coded", GST_TIME_ARGS(frame->pts));
         return gst_video_encoder_finish_frame(ve, frame);
     }
+    snapshot_maybe_arm(s, frame);
     const gint64 t0 = g_get_monotonic_time();
     if (s->jpeg) { /* a picture the encoder refuses (not baseline, another size, corrupt data) is dropped; ten in a row: this is not a stream it can take */
         GstMapInfo mi;
@@ -830,6 +969,8 @@ static void finalize(GObject *obj) {
     enc_stop(GST_VIDEO_ENCODER(obj));
     g_free(GST_MI355H264ENC(obj)->img_location);
     g_free(GST_MI355H264ENC(obj)->img_rgba);
+    g_free(GST_MI355H264ENC(obj)->snap_location);
+    g_mutex_clear(&GST_MI355H264ENC(obj)->snap_mu); g_mutex_clear(&GST_MI355H264ENC(obj)->snap_enc_mu); g_cond_clear(&GST_MI355H264ENC(obj)->snap_cv);
     G_OBJECT_CLASS(gst_mi355h264enc_parent_class)->finalize(obj);
 }
 
@@ -918,6 +1059,12 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
     g_object_class_install_property(g, PROP_IMG_X, g_param_spec_int("image-offset-x", "Image X offset", "Luma samples from the picture's left edge to the image's (negative: the image starts outside)", -16384, 16384, 0, F));
     g_object_class_install_property(g, PROP_IMG_Y, g_param_spec_int("image-offset-y", "Image Y offset", "Luma samples from the picture's top edge to the image's", -16384, 16384, 0, F));
     g_object_class_install_property(g, PROP_IMG_ALPHA, g_param_spec_double("image-alpha", "Image alpha", "Global alpha of the image, multiplied onto its own (as gdkpixbufoverlay's alpha)", 0.0, 1.0, 1.0, F));
+    g_object_class_install_property(g, PROP_SNAP_LOCATION, g_param_spec_string("snapshot-location", "Still location",
+        "File a JPEG still of the running stream is written to every snapshot-interval (through location.tmp and a rename; an element message mi355-snapshot follows each); empty: off. The still is transformed on the GPU and Huffman coded on a helper thread; the stream's bytes do not change", "", F));
+    g_object_class_install_property(g, PROP_SNAP_INTERVAL, g_param_spec_uint("snapshot-interval", "Still interval (ms)", "Stream time between two stills", 0, G_MAXUINT, 1000, F));
+    g_object_class_install_property(g, PROP_SNAP_QUALITY, g_param_spec_int("snapshot-quality", "Still quality", "libjpeg's quality scale", 1, 100, 75, F));
+    g_object_class_install_property(g, PROP_SNAP_REDUCE, g_param_spec_int("snapshot-reduce", "Still reduction", "1, 2, 4 or 8: the still is the picture's size divided by it (rounded up)", 1, 8, 4, F));
+    g_object_class_install_property(g, PROP_SNAP_SOURCE, g_param_spec_enum("snapshot-source", "Still source", "source: the picture that is coded, with scaling, orientation, image and text in it; decoded: what a decoder shows", snapshot_source_type(), 0, F));
     g_object_class_override_property(g, PROP_VIDEO_DIRECTION, "video-direction"); /* GstVideoDirection: identity, 90r, 180, 90l, horiz, vert, ul-lr, ur-ll, auto -- as on videoflip */
     g_object_class_install_property(g, PROP_STATS, g_param_spec_boolean("stats", "Print stats", "Print a JSON line with counters when the encoder closes", FALSE, F));
     gst_element_class_add_static_pad_template(e, &sink_tmpl);
@@ -935,6 +1082,9 @@ static void gst_mi355h264enc_init(GstMi355H264Enc *s) {
     s->img_location = NULL; s->img_rgba = NULL; s->img_w = s->img_h = s->img_x = s->img_y = 0; s->img_alpha = 1.0;
     s->direction = s->tag_direction = s->open_direction = GST_VIDEO_ORIENTATION_IDENTITY;
     s->border_color = 0x108080;
+    s->snap_location = NULL; s->snap_interval = 1000; s->snap_quality = 75; s->snap_reduce = 4; s->snap_source = 0; s->snap_next = GST_CLOCK_TIME_NONE; s->snap_watch = 0;
+    g_mutex_init(&s->snap_mu); g_mutex_init(&s->snap_enc_mu); g_cond_init(&s->snap_cv);
+    s->snap_thread = NULL; s->snap_wake = 0; s->snap_stop = FALSE; s->snap_count = 0; s->snap_gen = 0;
 }
 
 GType gst_mi355tsmux_get_type(void); /* gstmi355tsmux.c */

@@ -27,7 +27,9 @@
  * the source caps' size.  --tag VALUE sends an image-orientation tag event with VALUE into the encoder's sink pad in front of the first buffer; --set K PROP VALUE
  * sets the encoder's property PROP to VALUE (as gst-launch would parse it) in front of buffer K (counted from 0), on the streaming thread.
  *
- * usage: mi355_gst_probe "PIPELINE DESCRIPTION" [--no-encoder | --appsrc N W H [pinned] | --props] [--dump FILE] [--tag VALUE] [--set K PROP VALUE]
+ * With --stills every `mi355-snapshot` element message (the encoder's snapshot-location property: a JPEG still was written) is printed to stderr as one JSON line.
+ *
+ * usage: mi355_gst_probe "PIPELINE DESCRIPTION" [--no-encoder | --appsrc N W H [pinned] | --props] [--dump FILE] [--tag VALUE] [--set K PROP VALUE] [--stills]
  */
 #include <arpa/inet.h>
 #include <gst/app/gstappsink.h>
@@ -65,6 +67,7 @@ static const char *tag_value;            /* --tag */
 static int set_at = -1, n_in;            /* --set K PROP VALUE; buffers seen at the encoder's sink pad */
 static const char *set_prop, *set_value;
 static GstElement *the_enc;
+static int print_stills;                 /* --stills */
 
 static GstPadProbeReturn on_enc_sink(GstPad *pad, GstPadProbeInfo *info, gpointer u) {
     (void)pad; (void)u;
@@ -133,6 +136,12 @@ static gboolean on_bus(GstBus *bus, GstMessage *msg, gpointer u) {
         g_error_free(e); g_free(dbg);
         exit_code = 3; g_main_loop_quit(loop);
     } else if (GST_MESSAGE_TYPE(msg) == GST_MESSAGE_EOS) g_main_loop_quit(loop);
+    else if (GST_MESSAGE_TYPE(msg) == GST_MESSAGE_ELEMENT && print_stills && gst_message_has_name(msg, "mi355-snapshot")) {
+        const GstStructure *st = gst_message_get_structure(msg);
+        gint w = 0, h = 0; guint64 pts = 0, bytes = 0;
+        gst_structure_get_int(st, "width", &w); gst_structure_get_int(st, "height", &h); gst_structure_get_uint64(st, "pts", &pts); gst_structure_get_uint64(st, "bytes", &bytes);
+        fprintf(stderr, "{\"still\":\"%s\",\"width\":%d,\"height\":%d,\"pts\":%" G_GUINT64_FORMAT ",\"bytes\":%" G_GUINT64_FORMAT "}\n", gst_structure_get_string(st, "location"), w, h, pts, bytes);
+    }
     return TRUE;
 }
 /* ---- --appsrc: eight pictures of a texture panning by (+3, -2) per picture, pushed forwards and backwards */
@@ -200,6 +209,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--clip") && i + 1 < argc) feed.clip = argv[++i];
         else if (!strcmp(argv[i], "--dump") && i + 1 < argc) { dump = fopen(argv[++i], "wb"); if (!dump) { fprintf(stderr, "cannot write %s\n", argv[i]); return 2; } }
         else if (!strcmp(argv[i], "--tag") && i + 1 < argc) tag_value = argv[++i];
+        else if (!strcmp(argv[i], "--stills")) print_stills = 1;
         else if (!strcmp(argv[i], "--set") && i + 3 < argc) { set_at = atoi(argv[i + 1]); set_prop = argv[i + 2]; set_value = argv[i + 3]; i += 3; }
     }
     if (use_appsrc) {

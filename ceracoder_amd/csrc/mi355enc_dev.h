@@ -239,6 +239,10 @@ int k_launch_jpeg(const int16_t *d_coef, const uint16_t *d_qt, int hs, int vs, i
  * address and stride, by method 1 .. 7 (MI355ENC_ORIENT_*) into NV12 surfaces of stride W and coded size W x H of the oriented picture, margin included.
  * -1: not such a method, or sizes that do not fit each other. */
 int k_launch_orient(int method, const uint8_t *sy, int ssy, const uint8_t *suv, int ssuv, int in_w, int in_h, uint8_t *dy, uint8_t *duv, int W, int H, hipStream_t s);
+/* JPEG stills (k_snapshot.hip; the rule: DESIGN.md section 18): NV12 planes of w x h (even) at any address and stride, reduced by 2^log2s, as the quantised
+ * levels of a 4:2:0 still: 64 int16 per block in jpeg_host_layout's layout (16-byte aligned) and one hint byte per block (the zigzag index of its last non-zero
+ * level), device or pinned host memory; d_tab: the quality's snapshot_tab_t on the device.  -1: sizes or a reduction it does not take. */
+int k_launch_snapshot(const uint8_t *sy, int ys, const uint8_t *suv, int uvs, int w, int h, int log2s, const void *d_tab, int16_t *levels, uint8_t *hint, hipStream_t s);
 void k_launch_quality(const uint8_t *src_y, const uint8_t *src_uv, int src_stride, const uint8_t *rec_y, const uint8_t *rec_uv, int rec_stride,
                       int width, int height, unsigned long long *d_acc, unsigned long long *out, hipStream_t s);
 #endif

@@ -29,7 +29,7 @@ IDEC = np.dtype([("modes4", "u1", (16,)), ("mode16", "u1"), ("cmode", "u1"), ("u
 IMV_DTYPE = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("sad", "<u2"), ("bits", "<u2")])
 SURF_ROWS, SURF_COLS = 35, 36
 DROP_MAX, DROP_SKIP = 12, 255
-STAGE_ME, STAGE_INTER, STAGE_INTRA, STAGE_DEBLOCK, STAGE_SUBPEL, STAGE_CSC_I420, STAGE_CSC_YUY2, STAGE_CSC_UYVY, STAGE_ME_SELECT, STAGE_PMB, STAGE_INTRA_P, STAGE_QUALITY, STAGE_JPEG, STAGE_ORIENT, STAGE_SCALE, STAGE_IMAGE = range(16)
+STAGE_ME, STAGE_INTER, STAGE_INTRA, STAGE_DEBLOCK, STAGE_SUBPEL, STAGE_CSC_I420, STAGE_CSC_YUY2, STAGE_CSC_UYVY, STAGE_ME_SELECT, STAGE_PMB, STAGE_INTRA_P, STAGE_QUALITY, STAGE_JPEG, STAGE_ORIENT, STAGE_SCALE, STAGE_IMAGE, STAGE_SNAPSHOT = range(17)
 # mi355enc_set_orientation: GstVideoOrientationMethod's numbers
 ORIENT_IDENTITY, ORIENT_90R, ORIENT_180, ORIENT_90L, ORIENT_HORIZ, ORIENT_VERT, ORIENT_UL_LR, ORIENT_UR_LL = range(8)
 ORIENT_NAMES = ("identity", "90r", "180", "90l", "horiz", "vert", "ul-lr", "ur-ll")
@@ -52,6 +52,8 @@ EXPORTS = [
     "mi355enc_debug_orient_bytes",
     "mi355enc_set_input_geometry", "mi355enc_get_input_geometry", "mi355enc_set_crop", "mi355enc_geometry_table", "mi355enc_fit_rect", "mi355enc_stage_geometry",
     "mi355enc_geometry_check", "mi355enc_geometry_sar",
+    "mi355enc_request_snapshot", "mi355enc_take_snapshot", "mi355enc_debug_snapshot_bytes", "mi355enc_snapshot_tables", "mi355enc_snapshot_reciprocal",
+    "mi355enc_snapshot_max_bytes", "mi355enc_snapshot_write", "mi355enc_stage_snapshot_blocks", "mi355enc_stage_snapshot_blocks_device", "mi355enc_stage_snapshot",
 ]
 
 
@@ -112,6 +114,20 @@ class Geometry(C.Structure):
                 ("border_y", C.c_int), ("border_cb", C.c_int), ("border_cr", C.c_int), ("flags", C.c_uint)]
 
 
+class SnapshotReq(C.Structure):
+    """mi355enc_snapshot_req_t: what 0 the coded source / 1 the deblocked reconstruction; reduce 1, 2, 4 or 8; quality 1 .. 100"""
+    _fields_ = [("what", C.c_int), ("reduce", C.c_int), ("quality", C.c_int)]
+
+
+class SnapshotInfo(C.Structure):
+    """mi355enc_snapshot_info_t: the picture a still was taken of (index: its position in the stream) and the still's size"""
+    _fields_ = [("pts", C.c_int64), ("index", C.c_uint64), ("width", C.c_int), ("height", C.c_int), ("what", C.c_int), ("quality", C.c_int)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+SNAP_SOURCE, SNAP_DECODED = 0, 1
 IMAGE_LAYERS, IMAGE_MAX_DIM = 4, 4096
 GEOM_KEEP_SAR = 1  # mi355enc_geometry_t.flags: no aspect ratio from the geometry in the SPS
 OVERLAY_MAX_TEXT = 255
@@ -212,6 +228,19 @@ def load():
         L.mi355enc_stage_geometry.argtypes = [vp, C.c_int, vp, vp, vp, vp]
         L.mi355enc_geometry_check.argtypes = [C.POINTER(Geometry), C.c_int, C.c_int]
         L.mi355enc_geometry_sar.argtypes = [C.POINTER(Geometry), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.mi355enc_request_snapshot.argtypes = [vp, C.POINTER(SnapshotReq)]
+        L.mi355enc_take_snapshot.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(SnapshotInfo)]
+        L.mi355enc_debug_snapshot_bytes.restype = C.c_size_t
+        L.mi355enc_debug_snapshot_bytes.argtypes = [vp]
+        L.mi355enc_snapshot_tables.argtypes = [C.c_int, vp]
+        L.mi355enc_snapshot_reciprocal.restype = C.c_uint32
+        L.mi355enc_snapshot_reciprocal.argtypes = [C.c_int]
+        L.mi355enc_snapshot_max_bytes.restype = C.c_size_t
+        L.mi355enc_snapshot_max_bytes.argtypes = [C.c_int, C.c_int]
+        L.mi355enc_snapshot_write.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.mi355enc_stage_snapshot_blocks.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+        L.mi355enc_stage_snapshot_blocks_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+        L.mi355enc_stage_snapshot.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.mi355enc_host_alloc.restype = vp
         L.mi355enc_host_alloc.argtypes = [C.c_size_t]
         L.mi355enc_host_free.restype = None
@@ -428,6 +457,58 @@ def jpeg_entropy_decode(data, coef_cap=None):
         out.append(coef[o:o + bw * bh * 64].reshape(bh, bw, 8, 8))
         o += bw * bh * 64
     return info, out, qt.reshape(3, 8, 8)
+
+
+def snapshot_size(w, h, reduce=1):
+    """(ow, oh) of a still of a w x h picture"""
+    return -(-w // reduce), -(-h // reduce)
+
+
+def snapshot_layout(ow, oh):
+    """[(blocks per row, block rows)] of Y, Cb, Cr of a still of ow x oh: the layout jpeg_entropy_decode returns for a 4:2:0 picture of that size"""
+    mcux, mcuy = -(-ow // 16), -(-oh // 16)
+    return [(2 * mcux, 2 * mcuy), (mcux, mcuy), (mcux, mcuy)]
+
+
+def _snapshot_split(flat, ow, oh):
+    out, o = [], 0
+    for bw, bh in snapshot_layout(ow, oh):
+        out.append(flat[o:o + bw * bh * 64].reshape(bh, bw, 8, 8))
+        o += bw * bh * 64
+    return out
+
+
+def snapshot_tables(quality):
+    """The two quantisation tables of a quality (host only): uint16 (2, 64), natural order."""
+    qt = np.zeros((2, 64), np.uint16)
+    r = load().mi355enc_snapshot_tables(int(quality), _p(qt))
+    if r != 0:
+        raise EncoderError("mi355enc_snapshot_tables: %s (%d)" % (load().mi355enc_strerror(r).decode(), r))
+    return qt
+
+
+def snapshot_reciprocal(q):
+    """The multiplier the device divides by 8 q with (host only)."""
+    return int(load().mi355enc_snapshot_reciprocal(int(q)))
+
+
+def snapshot_max_bytes(ow, oh):
+    return int(load().mi355enc_snapshot_max_bytes(int(ow), int(oh)))
+
+
+def snapshot_write(levels, qt, ow, oh, cap=None, want_len=False):
+    """The file of a still from its levels (host only): levels a list of per-component int16 arrays (block rows, blocks per row, 8, 8) or one flat array,
+    qt uint16 (2, 64).  cap: the room offered (default: snapshot_max_bytes).  want_len: (return code, length) instead of the bytes."""
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(c, np.int16).ravel() for c in levels]) if isinstance(levels, (list, tuple)) else levels, np.int16)
+    q = np.ascontiguousarray(np.asarray(qt, np.uint16).reshape(2, 64))
+    cap = snapshot_max_bytes(ow, oh) if cap is None else int(cap)
+    out, n = np.empty(max(cap, 1), np.uint8), C.c_size_t(0)
+    r = load().mi355enc_snapshot_write(_p(flat), _p(q), int(ow), int(oh), _p(out), cap, C.byref(n))
+    if want_len:
+        return r, int(n.value)
+    if r != 0:
+        raise EncoderError("mi355enc_snapshot_write: %s (%d)" % (load().mi355enc_strerror(r).decode(), r))
+    return bytes(out[:n.value])
 
 
 def overlay_style(**kw):
@@ -823,6 +904,64 @@ class Encoder:
         q = Quality()
         self._chk(self.L.mi355enc_stage_quality_device(self.h, src_y_ptr, src_uv_ptr, int(src_stride), rec_y_ptr, rec_uv_ptr, C.byref(q)), "stage_quality_device")
         return q
+
+    def request_snapshot(self, what=SNAP_SOURCE, reduce=1, quality=75):
+        """Arms the next submitted picture: a JPEG still of its coded source (what 0) or of its deblocked reconstruction (1), reduced by 1, 2, 4 or 8."""
+        req = SnapshotReq(int(what), int(reduce), int(quality))
+        self._chk(self.L.mi355enc_request_snapshot(self.h, C.byref(req)), "request_snapshot")
+
+    def take_snapshot(self, cap=None):
+        """(bytes, info dict) of the still of the last armed picture that has been collected -- Huffman coded here, in this thread -- or None while none is ready.
+        cap: the room offered (default: what the still needs, asked for first); too little raises EncoderError with .need = the bytes needed."""
+        n, info = C.c_size_t(0), SnapshotInfo()
+        if cap is None:  # ask first: a capacity of 0 yields the bytes needed (coding the still twice costs less than a buffer for the worst case of the full size)
+            r = self.L.mi355enc_take_snapshot(self.h, None, 0, C.byref(n), C.byref(info))
+            if r == -6:
+                return None
+            if r != -5:
+                self._chk(r, "take_snapshot")
+            cap = int(n.value)
+        out = np.empty(max(int(cap), 1), np.uint8)
+        r = self.L.mi355enc_take_snapshot(self.h, _p(out), int(cap), C.byref(n), C.byref(info))
+        if r == -6:
+            return None
+        if r == -5:
+            e = EncoderError("mi355enc_take_snapshot: output buffer too small (-5)")
+            e.need = int(n.value)
+            raise e
+        self._chk(r, "take_snapshot")
+        return bytes(out[:n.value]), info.as_dict()
+
+    def snapshot_bytes(self):
+        """memory held for stills (0 until the first armed picture is submitted)"""
+        return int(self.L.mi355enc_debug_snapshot_bytes(self.h))
+
+    def stage_snapshot_blocks(self, y, uv, reduce=1, quality=75):
+        """The still kernel alone: NV12 planes (h, w) and (h / 2, w) of any even size -> ([int16 (block rows, blocks per row, 8, 8)] of Y, Cb, Cr, qt uint16 (2, 64))."""
+        y, uv = _rows(y), _rows(uv)
+        h, w = y.shape
+        ow, oh = snapshot_size(w, h, reduce)
+        flat = np.zeros(sum(bw * bh for bw, bh in snapshot_layout(ow, oh)) * 64, np.int16)
+        qt = np.zeros((2, 64), np.uint16)
+        self._chk(self.L.mi355enc_stage_snapshot_blocks(self.h, _p(y), y.strides[0], _p(uv), uv.strides[0], w, h, int(reduce), int(quality), _p(flat), _p(qt)), "stage_snapshot_blocks")
+        return _snapshot_split(flat, ow, oh), qt
+
+    def stage_snapshot_blocks_device(self, y_ptr, y_stride, uv_ptr, uv_stride, w, h, reduce=1, quality=75):
+        """... on planes in this GPU's memory (addresses as ints, any alignment and stride)"""
+        ow, oh = snapshot_size(w, h, reduce)
+        flat = np.zeros(sum(bw * bh for bw, bh in snapshot_layout(ow, oh)) * 64, np.int16)
+        qt = np.zeros((2, 64), np.uint16)
+        self._chk(self.L.mi355enc_stage_snapshot_blocks_device(self.h, y_ptr, y_stride, uv_ptr, uv_stride, w, h, int(reduce), int(quality), _p(flat), _p(qt)), "stage_snapshot_blocks_device")
+        return _snapshot_split(flat, ow, oh), qt
+
+    def stage_snapshot(self, y, uv, reduce=1, quality=75):
+        """... and the whole file (bytes)"""
+        y, uv = _rows(y), _rows(uv)
+        h, w = y.shape
+        ow, oh = snapshot_size(w, h, reduce)
+        out, n = np.empty(snapshot_max_bytes(ow, oh), np.uint8), C.c_size_t(0)
+        self._chk(self.L.mi355enc_stage_snapshot(self.h, _p(y), y.strides[0], _p(uv), uv.strides[0], w, h, int(reduce), int(quality), _p(out), out.size, C.byref(n)), "stage_snapshot")
+        return bytes(out[:n.value])
 
     def set_overlay_text(self, text):
         """The text drawn into every picture submitted from now on (str or bytes; None or "": off).  Thread-safe, no GPU call."""

@@ -451,6 +451,45 @@ int mi355enc_image_pixel(int matrix, int full_range, int r, int g, int b, uint8_
 /* host only: a Netpbm PAM (P7) file, TUPLTYPE RGB_ALPHA with DEPTH 4 or RGB with DEPTH 3 (alpha 255), MAXVAL 255, sizes 1 .. 4096, as RGBA into
  * rgba (cap bytes of room).  rgba NULL: only *w and *h.  ERR_OVERFLOW: cap is too small; ERR_ARG: anything else.  (PNG would need an inflate: out of scope.) */
 int mi355enc_image_load_pam(const uint8_t *data, size_t len, int *w, int *h, uint8_t *rgba, size_t cap);
+/* ---- JPEG stills of the running stream --------------------------
+ * A still is a baseline JFIF JPEG (SOF0, 8 bit, Y 2x2 + Cb + Cr, one interleaved scan, the typical Huffman tables of T.81 Annex K.3, no restart markers) of
+ * one picture of the stream, taken while the stream runs: one more launch in that picture's pipeline leaves the quantised levels in pinned host memory, and
+ * the Huffman coding runs in the thread that takes the still.  The access units are byte for byte those of the stream without stills.
+ *   what     0: the coded source -- what the coding kernels read for the picture, after conversion, scaling, geometry, orientation, image layers and text;
+ *            1: the deblocked reconstruction -- what a decoder shows.  Only the visible width x height samples are used.
+ *   reduce   s = 1, 2, 4 or 8: the still is ceil(width / s) x ceil(height / s); a sample is the rounded mean of its s x s source samples, coordinates clamped
+ *            to the picture; chroma likewise from the width / 2 x height / 2 planes into ceil(ow / 2) x ceil(oh / 2).
+ *   quality  1 .. 100, libjpeg's scale of the Annex K.1 tables.
+ * The arithmetic is libjpeg's accurate integer path (jfdctint and its quantiser): a grey JPEG libjpeg writes of the same plane holds the same coefficients. */
+typedef struct { int what, reduce, quality; } mi355enc_snapshot_req_t;
+typedef struct { int64_t pts; uint64_t index; int width, height, what, quality; } mi355enc_snapshot_info_t; /* index: the picture's position in the stream */
+/* Arms the NEXT submitted picture; a second request before that replaces the first.  Any thread, any time; no GPU call.  ERR_ARG for values out of range. */
+int mi355enc_request_snapshot(mi355enc_t *h, const mi355enc_snapshot_req_t *req);
+/* The still of the last armed picture that has been collected, coded here, in the caller's thread (any thread).  ERR_STATE while none is ready; ERR_OVERFLOW
+ * with *len = the bytes needed (mi355enc_snapshot_max_bytes bounds them).  A still not taken is replaced by the next one; taking it twice yields the same
+ * bytes.  info may be NULL. */
+int mi355enc_take_snapshot(mi355enc_t *h, uint8_t *out, size_t cap, size_t *len, mi355enc_snapshot_info_t *info);
+/* pinned host and device memory held for stills: 0 until the first armed picture is submitted (with no request nothing is allocated, launched or waited for) */
+size_t mi355enc_debug_snapshot_bytes(const mi355enc_t *h);
+/* host only: the two quantisation tables of a quality (0 luminance, 1 chrominance; natural order); the multiplier the device divides by 8 q with,
+ * ceil(2^32 / (8 q)) (0 outside 1 .. 255); an upper bound of a still's size (0 for sizes outside 1 .. 65535) */
+int mi355enc_snapshot_tables(int quality, uint16_t qt[2][64]);
+uint32_t mi355enc_snapshot_reciprocal(int q);
+size_t mi355enc_snapshot_max_bytes(int ow, int oh);
+/* host only: the file of a still of ow x oh from its levels -- per component (Y, Cb, Cr) the blocks of its MCU-padded plane in raster order, 64 int16 each in
+ * natural order: the layout mi355enc_jpeg_entropy_decode returns for a 4:2:0 picture of that size.  ERR_ARG for a level Huffman coding cannot express
+ * (an AC level beyond +-1023, a DC difference beyond 11 bits); ERR_OVERFLOW with *len = the bytes needed. */
+int mi355enc_snapshot_write(const int16_t *levels, const uint16_t qt[2][64], int ow, int oh, uint8_t *out, size_t cap, size_t *len);
+/* the kernel alone (tests): NV12 host planes of w x h (even, 2 .. 16384; independent of the handle's size) -> the levels of the still reduced by `reduce`
+ * (room for the blocks of a ceil(w / reduce) x ceil(h / reduce) picture) and the tables of `quality` */
+int mi355enc_stage_snapshot_blocks(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t *uv, int uv_stride, int w, int ht, int reduce, int quality,
+                                   int16_t *levels, uint16_t qt[2][64]);
+/* ... on planes in this GPU's memory, any address and stride: no byte outside the visible w x ht is read */
+int mi355enc_stage_snapshot_blocks_device(mi355enc_t *h, const void *d_y, int y_stride, const void *d_uv, int uv_stride, int w, int ht, int reduce, int quality,
+                                          int16_t *levels, uint16_t qt[2][64]);
+/* ... and the whole file */
+int mi355enc_stage_snapshot(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t *uv, int uv_stride, int w, int ht, int reduce, int quality,
+                            uint8_t *out, size_t cap, size_t *len);
 size_t mi355enc_max_au_bytes(const mi355enc_t *h);
 const char *mi355enc_strerror(int code);
 int mi355enc_abi_version(void);
@@ -510,7 +549,8 @@ int mi355enc_stage_deblock(mi355enc_t *h, uint8_t *rec_y, uint8_t *rec_uv, const
  * 12 the JPEG launch for the handle's input size as 4:2:2, on whatever slot 0's coefficient buffer holds,
  * 13 the orientation launch at the handle's size (the handle's method; 90r on a handle without one), on whatever slot 0's raw staging buffer holds,
  * 14 the scale / geometry launch for an NV12 picture of the handle's input size (MI355ENC_ERR_STATE without mi355enc_set_input_size / _geometry), likewise,
- * 15 the blend launch of image layer 0 at its current place into slot 0's source surfaces (MI355ENC_ERR_STATE without an image on layer 0).
+ * 15 the blend launch of image layer 0 at its current place into slot 0's source surfaces (MI355ENC_ERR_STATE without an image on layer 0),
+ * 16 the still launch on slot 0's source surfaces, with the reduction and quality of the last mi355enc_request_snapshot (1 and 75 without one).
  * Uses whatever the handle's surfaces currently hold.  Returns average ms per launch. */
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms);
 
