@@ -149,6 +149,7 @@ struct mi355enc {
     int psrc_cur;         // which of them holds the last coded picture
     unsigned *d_ip_progress; // intra macroblocks of P pictures: one progress word per macroblock row (epoch-tagged, never cleared)
     uint8_t *d_ip_strips;    // ... and the bottom lines they publish for the row below, 32 bytes per macroblock
+    uint32_t ip_epoch = 0;   // ... and the epoch of the last launch that wrote those words (0: none since they were cleared): ip_rows_stamp()
     uint32_t epoch;
     int islice_rows, stage_slice_rows;   // rows per slice of an I picture (cfg.intra_slices; 0: one slice) / what the single-stage entry points use
     int pslice_rows, slice_dbf, stage_slice_dbf; // ... of a P picture (cfg.slices); disable_deblocking_filter_idc of every slice (cfg.slice_deblock: 0 or 2) / of the single-stage entry points
@@ -271,6 +272,7 @@ int run_intra(mi355enc_t *h, int ci, const frame_ctx_t *hc, unsigned *band_done 
 int run_deblock(mi355enc_t *h, int ci, const frame_ctx_t *hc, hipStream_t st, const unsigned *ip_progress, const unsigned *iband_done = nullptr,
                 unsigned *band_done = nullptr, bool after_gated_pmb = false, unsigned row_need = 0, bool fused_ip = false);
 void fill_ctx(mi355enc_t *h, frame_ctx_t *c, int qp, int drop, int idr, int set = 0);
+int ip_rows_stamp(mi355enc_t *h, uint32_t epoch); // in front of every launch of a P picture's intra macroblock rows
 int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_t *src_uv, int src_stride, int64_t pts, int force_idr);
 void entropy_worker(mi355enc_t *h);
 int upload_and_convert(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const planes[3], const int strides[3], hipStream_t up);

@@ -94,6 +94,19 @@ void fill_ctx(mi355enc_t *h, frame_ctx_t *c, int qp, int drop, int idr, int set)
     c->intra_p = h->cfg.intra_in_p ? (h->cfg.i4x4 && h->cfg.intra_in_p > 1 ? 2 : 1) : 0; // 2: Intra_4x4 as well
     c->ir_c0 = 0; c->ir_c1 = 0; c->ir_clean = -1; // (enqueue_picture sets the refresh columns of a picture of an intra-refresh stream)
 }
+// The progress words of a P picture's intra macroblock rows carry 20 bits of the epoch (IP_EPOCH, intra_mb.hpp).  Every launch of the rows rewrites every row's
+// word, so the words are those of the last launch, and a launch's deblocker can take a stale word for its own picture's only when that launch was a multiple of
+// 2^20 epochs ago with no launch of the rows in between: a run of IDR pictures (force_idr, or stage calls, which stamp epochs of their own) of 4 h 51 min at 60
+// pictures/s, then a P picture.  There the words are cleared first (a zero word reports no macroblock final under any tag).  No launch that reads or writes them
+// is in flight then: a picture in flight is at most three epochs old.
+int ip_rows_stamp(mi355enc_t *h, uint32_t epoch) {
+    if (h->ip_epoch && h->ip_epoch != epoch && ((h->ip_epoch ^ epoch) & 0xFFFFFu) == 0) {
+        HIPCHK(hipMemsetAsync(h->d_ip_progress, 0, (size_t)h->mbh * MI355_PROG_STRIDE * sizeof(unsigned), h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream)); // (whichever stream carries the rows and their deblocker: behind this)
+    }
+    h->ip_epoch = epoch;
+    return 0;
+}
 // P picture, front part (front stream): nothing here depends on the coding of the picture before
 static int run_p_front(mi355enc_t *h, const frame_ctx_t *hc, slot_t *s, int prof) {
     hipStream_t st = h->fstream;
@@ -201,6 +214,7 @@ int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_
         c->vis_h = h->cfg.height;
         fill_ctx(h, c, qp, drop, idr, set);
         c->mbi = h->d_mbi_set[set]; c->levels = h->d_levels_set[set];
+        if (!idr && c->intra_p) { int r = ip_rows_stamp(h, c->epoch); if (r) return r; }
         if (ir_j >= 0) {
             const int R = h->ir_R;
             c->ir_c0 = R > 0 ? R - 1 : 0; // (one column of overlap: deblocking left the last columns of column R - 1 dirty in the reference)

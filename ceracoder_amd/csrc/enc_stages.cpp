@@ -146,6 +146,7 @@ int mi355enc_stage_pmb(mi355enc_t *h, const uint8_t *src_y, const uint8_t *src_u
     HIPCHK(hipMemsetAsync(h->d_rec_uv[1], 0, h->csz, h->stream));
     HIPCHK(hipMemsetAsync(h->d_levels, 0, (size_t)h->nmb * MB_LEVELS * 2, h->stream));
     k_launch_pmb(c, h->mbw, 0, h->mbh, refine ? 1 : 0, nullptr, 0, err_word(h), nullptr, h->stream);
+    if (idec && run_intra_p) { r = ip_rows_stamp(h, c->epoch); if (r) return r; }
     if (idec && run_intra_p) k_launch_intra_p(c, h->mbw, h->mbh, h->d_ip_progress, h->d_ip_strips, err_word(h), h->stream);
     HIPCHK(hipGetLastError());
     return download_picture(h, mbinfo_out, rec_y, rec_uv, levels) ? MI355ENC_ERR_HIP : MI355ENC_OK;
@@ -218,6 +219,36 @@ int mi355enc_debug_trip_wait(mi355enc_t *h, unsigned code) {
     HIPCHK(hipMemcpy(h->d_progress, &code, sizeof code, hipMemcpyHostToDevice));
     return MI355ENC_OK;
 }
+int mi355enc_debug_get_counters(mi355enc_t *h, mi355enc_counters_t *out) {
+    if (!h || !out) return MI355ENC_ERR_ARG;
+    *out = {h->epoch, h->pmb_rows_total, h->db_started_total, h->ip_done_total, h->qpc_total, (uint32_t)h->idr_count, (uint32_t)h->frames_since_idr, 0u};
+    return MI355ENC_OK;
+}
+// Host-side value and device-side word of every count move together (the kernels compare one with the other); rec_epoch[], the band-done words, the
+// strips and progress words tagged with an epoch, and the parity of the band parts' counters stay as the last picture left them.
+int mi355enc_debug_set_counters(mi355enc_t *h, const mi355enc_counters_t *in) {
+    if (!h || !in || (!(in->keep & 64u) && in->frames_since_idr > 0x7FFFFFFFu) || (!(in->keep & 32u) && in->idr_count > 0x7FFFFFFFu)) return MI355ENC_ERR_ARG;
+    STAGE_IDLE(h);
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    HIPCHK(hipStreamSynchronize(h->cstream));
+    { int r = sync_compute(h); if (r) return r; }
+    if (!(in->keep & 1u)) h->epoch = in->epoch;
+    if (!(in->keep & 2u)) {
+        uint32_t *rows = (uint32_t *)malloc((size_t)h->mbh * sizeof(uint32_t));
+        if (!rows) return MI355ENC_ERR_NOMEM;
+        for (int r = 0; r < h->mbh; r++) rows[r] = in->pmb_rows_total;
+        const hipError_t e = hipMemcpy2D(h->d_row_done, MI355_PROG_STRIDE * sizeof(unsigned), rows, sizeof(uint32_t), sizeof(uint32_t), (size_t)h->mbh, hipMemcpyHostToDevice);
+        free(rows);
+        HIPCHK(e);
+        h->pmb_rows_total = in->pmb_rows_total;
+    }
+    if (!(in->keep & 4u)) { HIPCHK(hipMemcpy(h->d_progress + 1, &in->db_started_total, sizeof(uint32_t), hipMemcpyHostToDevice)); h->db_started_total = in->db_started_total; }
+    if (!(in->keep & 8u)) { HIPCHK(hipMemcpy(h->d_progress + 2, &in->ip_done_total, sizeof(uint32_t), hipMemcpyHostToDevice)); h->ip_done_total = in->ip_done_total; }
+    if (!(in->keep & 16u)) { HIPCHK(hipMemcpy(h->d_progress + 3, &in->qpc_total, sizeof(uint32_t), hipMemcpyHostToDevice)); h->qpc_total = in->qpc_total; }
+    if (!(in->keep & 32u)) h->idr_count = (int)in->idr_count;
+    if (!(in->keep & 64u)) h->frames_since_idr = (int)in->frames_since_idr;
+    return MI355ENC_OK;
+}
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
     if (!h || !avg_ms || iters < 1 || stage < 0 || stage > 16) return MI355ENC_ERR_ARG;
     if (stage == 14 && !h->d_scale_tab) return MI355ENC_ERR_STATE; // (mi355enc_set_input_size or mi355enc_set_input_geometry first)
@@ -242,6 +273,7 @@ int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
     }
     if (stage == 12) { int r = jpeg_alloc(h, s); if (r) return r; }
     if (stage == 16) { int r = snapshot_time_prepare(h); if (r) return r; } // (the block of the stage entry points)
+    if (stage == 10) { int r = ip_rows_stamp(h, s->h_ctx->epoch); if (r) return r; }
     const scale_plan_t *scale_pl = stage == 14 ? scale_plan_for(h, s, h->stream) : nullptr; // (a stale slot copy of the tables travels here, not inside the timed loop)
     if (stage == 14 && !scale_pl) return MI355ENC_ERR_HIP;
     image_args_t img_a; // stage 15: layer 0's image on the device and prepared here, not inside the timed loop

@@ -395,8 +395,9 @@ __global__ __launch_bounds__(IB_ROWS * 128) void intra_band_kernel(ib_args a) {
     for (int i = threadIdx.x; i < TAB_DWORDS; i += IB_ROWS * 128) tabw[i] = ((const unsigned *)&g_tab)[i];
     if (lane == 0 && role == 0) L->cseq = 0;
     // Between bands the bottom lines travel as 8-byte granules {4 samples, tag}, one sc1 store each, polled directly by the band below
-    // (MI355X_MICROARCH.md hand-off R2): no drain on the producer, no counter.  The tag is the picture's epoch inverted -- the band
-    // deblocker of the same picture uses the same buffer with the plain epoch.
+    // (MI355X_MICROARCH.md hand-off R2): no drain on the producer, no counter.  The tag is the picture's epoch inverted; the buffer (d_ib_gran)
+    // and the band-done words (d_iband_done) hold inverted epochs only -- the band deblocker's strips, tagged with the plain epoch, have a buffer of
+    // their own (d_db_gran), so a plain and an inverted epoch never meet in one word (~e == e + 1 at e = 0x7FFFFFFF).
     const unsigned tag = ~ctx->epoch;
     uint2 *gran_up = a.gran + (size_t)(band > 0 ? band - 1 : 0) * mbw * 8 + 4 * role, *gran_my = a.gran + (size_t)band * mbw * 8 + 4 * role;
     // the lanes that move neighbour samples: luma wave 24..40 (i = -1..15), chroma wave 41..58 (plane c, i = -1..7)

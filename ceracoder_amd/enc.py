@@ -41,7 +41,7 @@ EXPORTS = [
     "mi355enc_max_au_bytes", "mi355enc_fetch", "mi355enc_mb_width", "mi355enc_mb_height", "mi355enc_stage_me",
     "mi355enc_stage_subpel", "mi355enc_stage_inter", "mi355enc_stage_pmb", "mi355enc_stage_intra", "mi355enc_stage_intra_analyse", "mi355enc_stage_csc", "mi355enc_submit_fmt", "mi355enc_host_write_slice_packed", "mi355enc_stage_deblock", "mi355enc_time_stage",
     "mi355enc_host_write_headers", "mi355enc_host_write_slice", "mi355enc_host_set_slice_rows", "mi355enc_host_set_p_slices", "mi355enc_stage_set_slice_rows", "mi355enc_slice_rows", "mi355enc_p_slice_rows", "mi355enc_stage_set_slice_deblock", "mi355enc_rc_init", "mi355enc_rc_set_bitrate",
-    "mi355enc_rc_pick", "mi355enc_rc_update", "mi355enc_host_cavlc_block", "mi355enc_debug_trip_wait", "mi355enc_host_alloc", "mi355enc_host_free",
+    "mi355enc_rc_pick", "mi355enc_rc_update", "mi355enc_host_cavlc_block", "mi355enc_debug_trip_wait", "mi355enc_debug_get_counters", "mi355enc_debug_set_counters", "mi355enc_host_alloc", "mi355enc_host_free",
     "mi355enc_set_input_size", "mi355enc_stage_scale", "mi355enc_scale_table",
     "mi355enc_set_colorimetry", "mi355enc_csc_coefficients", "mi355enc_host_write_headers_vui", "mi355enc_stage_csc_device",
     "mi355enc_set_quality_metrics", "mi355enc_last_quality", "mi355enc_quality_totals", "mi355enc_stage_quality", "mi355enc_stage_quality_device",
@@ -71,6 +71,14 @@ class Stats(C.Structure):
                 ("n_inter", C.c_uint64), ("n_intra", C.c_uint64), ("n_deblock", C.c_uint64), ("ms_entropy", C.c_double),
                 ("ms_wait", C.c_double), ("n_total_gpu", C.c_uint64), ("ms_deblock_idr", C.c_double), ("n_deblock_idr", C.c_uint64), ("cavlc_threads", C.c_uint32), ("last_drop", C.c_uint32), ("ms_select", C.c_double), ("ms_analyse_p", C.c_double), ("ms_intra_p", C.c_double), ("skip_pictures", C.c_uint64), ("ms_open", C.c_double),
                 ("recoveries", C.c_uint32), ("last_error_word", C.c_uint32), ("safe_level", C.c_uint32), ("pinned_inputs", C.c_uint64)]
+
+
+class Counters(C.Structure):
+    """mi355enc_counters_t: the picture epoch, the four counts the kernels compare on the device, the counts behind idr_pic_id and frame_num; keep: bit i set =
+    mi355enc_debug_set_counters leaves field i alone"""
+    _fields_ = [("epoch", C.c_uint32), ("pmb_rows_total", C.c_uint32), ("db_started_total", C.c_uint32), ("ip_done_total", C.c_uint32),
+                ("qpc_total", C.c_uint32), ("idr_count", C.c_uint32), ("frames_since_idr", C.c_uint32), ("keep", C.c_uint32)]
+    NAMES = ("epoch", "pmb_rows_total", "db_started_total", "ip_done_total", "qpc_total", "idr_count", "frames_since_idr")
 
 
 class Quality(C.Structure):
@@ -180,6 +188,8 @@ def load():
         L.mi355enc_submit_fmt.argtypes = [vp, C.c_int, vp, vp, C.c_int64, C.c_int]
         L.mi355enc_stage_csc.argtypes = [vp, C.c_int, vp, vp, vp, vp]
         L.mi355enc_debug_trip_wait.argtypes = [vp, C.c_uint]
+        L.mi355enc_debug_get_counters.argtypes = [vp, C.POINTER(Counters)]
+        L.mi355enc_debug_set_counters.argtypes = [vp, C.POINTER(Counters)]
         L.mi355enc_set_input_size.argtypes = [vp, C.c_int, C.c_int]
         L.mi355enc_stage_scale.argtypes = [vp, C.c_int, vp, vp, vp, vp]
         L.mi355enc_scale_table.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t, C.POINTER(C.c_int)]
@@ -1163,6 +1173,22 @@ class Encoder:
     def debug_trip_wait(self, code):
         """fault injection: as if a bounded device-side wait had just run out (include/mi355enc.h)"""
         self._chk(self.L.mi355enc_debug_trip_wait(self.h, int(code)), "debug_trip_wait")
+
+    def debug_get_counters(self):
+        """Development: the long-run state as a dict (Counters.NAMES): the epoch of the last picture stamped, the four device-side totals, idr_count, frames_since_idr."""
+        c = Counters()
+        self._chk(self.L.mi355enc_debug_get_counters(self.h, C.byref(c)), "debug_get_counters")
+        return {k: int(getattr(c, k)) for k in Counters.NAMES}
+
+    def debug_set_counters(self, **values):
+        """Development: puts the handle where a long run would have put it (include/mi355enc.h): host-side values and the device-side words they are compared
+        with.  Only the fields named are touched; nothing may be pending (EncoderError, code ERR_STATE)."""
+        c = Counters()
+        c.keep = (1 << len(Counters.NAMES)) - 1
+        for k, v in values.items():
+            setattr(c, k, int(v) & 0xFFFFFFFF)
+            c.keep &= ~(1 << Counters.NAMES.index(k))
+        self._chk(self.L.mi355enc_debug_set_counters(self.h, C.byref(c)), "debug_set_counters")
 
     def time_stage(self, stage, iters=20):
         ms = C.c_double(0)

@@ -354,6 +354,18 @@ int mi355enc_collect(mi355enc_t *h, uint8_t *out, size_t out_cap, size_t *out_le
  * collect() through the recovery path: re-encoded in stream order, starting with an IDR picture; stats.recoveries counts it. */
 int mi355enc_debug_trip_wait(mi355enc_t *h, unsigned code);
 
+/* Long-run state (tests; DESIGN.md "State that outlives a picture"): the per-handle picture epoch, the four counts the kernels compare on the device
+ * (macroblocks per row of all gated fused P stages; workgroups of all band-deblocking launches; intra macroblock rows of all fused launches; rows of
+ * all QP_Y chains) and the two counts behind idr_pic_id and frame_num.  mi355enc_debug_set_counters puts a handle where a long run would have put
+ * it: MI355ENC_ERR_STATE unless nothing is pending; it waits for every stream of the handle, then sets the host-side values AND the device-side words
+ * they are compared with to the same numbers.  A field whose bit in `keep` is set (bit i: field i in the order below) is not touched.  The next picture
+ * is stamped epoch + 1 (0 is skipped).  Everything tagged with an epoch -- the strips and progress words on the device, the band-done words and the
+ * epoch the host remembers for each reconstruction buffer -- keeps what the last picture left: exactly a handle that has been running.
+ * Contract: after the call the handle behaves like one whose pictures so far had brought each value to the given number. */
+typedef struct { uint32_t epoch, pmb_rows_total, db_started_total, ip_done_total, qpc_total, idr_count, frames_since_idr, keep; } mi355enc_counters_t;
+int mi355enc_debug_get_counters(mi355enc_t *h, mi355enc_counters_t *out); /* keep: 0 */
+int mi355enc_debug_set_counters(mi355enc_t *h, const mi355enc_counters_t *in);
+
 int mi355enc_get_stats(mi355enc_t *h, mi355enc_stats_t *st);
 void mi355enc_reset_stats(mi355enc_t *h);
 

@@ -93,3 +93,27 @@ def parse_sps(rbsp):
 def sps_of(stream):
     units = nal_units(stream)
     return [parse_sps(r) for t, _, r in units if t == 7]
+
+
+def slice_frame_num(slice_nal):
+    """frame_num of a slice header (7.3.3: first_mb_in_slice, slice_type, pic_parameter_set_id as ue(v), then frame_num in the SPS's 8 bits); slice_nal: the
+    NAL unit's bytes behind its header byte, emulation prevention still in place"""
+    bits = "".join("{:08b}".format(b) for b in slice_nal.replace(b"\x00\x00\x03", b"\x00\x00")[:16])
+    p = 0
+    for _ in range(3):
+        z = bits.index("1", p) - p
+        p += 2 * z + 1
+    return int(bits[p:p + 8], 2)
+
+
+def slice_headers(au):
+    """Per slice NAL unit of an access unit: (nal_unit_type, first_mb_in_slice, frame_num, idr_pic_id or None) -- frame_num in the 8 bits this encoder's
+    SPS gives it, idr_pic_id (ue(v), IDR slices only) directly behind it (frame_mbs_only_flag = 1)"""
+    out = []
+    for t, _, rbsp in nal_units(au):
+        if t in (1, 5):
+            b = Bits(rbsp)
+            first_mb, _, _ = b.ue(), b.ue(), b.ue()
+            fn = b.u(8)
+            out.append((t, first_mb, fn, b.ue() if t == 5 else None))
+    return out

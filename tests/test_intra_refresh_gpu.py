@@ -9,6 +9,7 @@ import pytest
 from ceracoder_amd import enc as E_
 from ceracoder_amd import synth
 from tests import irref
+from tests.spsref import slice_frame_num as _frame_num
 
 pytestmark = pytest.mark.gpu
 
@@ -268,16 +269,6 @@ def test_cbr_under_the_balancer_script_without_idr_bursts(E):
     idr_max = off[key_off].max()
     print("largest AU after picture 0: refresh %d bytes, IDR %d bytes" % (sizes[1:].max(), idr_max))
     assert sizes[1:].max() < 0.5 * idr_max, (sizes[1:].max(), idr_max)
-
-
-def _frame_num(slice_nal):
-    """frame_num of a slice header (7.3.3: first_mb_in_slice, slice_type, pic_parameter_set_id as ue(v), then frame_num in the SPS's 8 bits)"""
-    bits = "".join("{:08b}".format(b) for b in slice_nal.replace(b"\x00\x00\x03", b"\x00\x00")[:16])
-    p = 0
-    for _ in range(3):
-        z = bits.index("1", p) - p
-        p += 2 * z + 1
-    return int(bits[p:p + 8], 2)
 
 
 def test_a_long_stream_keeps_its_cycle_and_frame_num(E, oracle):
