@@ -62,13 +62,11 @@ int mi355enc_stage_csc_device(mi355enc_t *h, int fmt, const void *const d_planes
     const int w = h->cfg.width, ht = h->cfg.height;
     const uint8_t *p[3] = {(const uint8_t *)d_planes[0], (const uint8_t *)d_planes[1], (const uint8_t *)d_planes[2]};
     int st[3] = {strides[0], strides[1], strides[2]};
-    if (fmt == MI355ENC_FMT_YV12) { const uint8_t *t = p[1]; p[1] = p[2]; p[2] = t; const int u = st[1]; st[1] = st[2]; st[2] = u; fmt = MI355ENC_FMT_I420; }
-    // every plane the format reads is there and as wide as the picture: the kernels stay inside rows of these lengths
-    const int nplanes = fmt == MI355ENC_FMT_I420 || fmt == MI355ENC_FMT_Y42B || fmt == MI355ENC_FMT_Y444 ? 3 : fmt == MI355ENC_FMT_NV21 ? 2 : 1;
-    const int row0 = fmt >= MI355ENC_FMT_BGR ? 3 * w : fmt >= MI355ENC_FMT_BGRX ? 4 * w : fmt == MI355ENC_FMT_YUY2 || fmt == MI355ENC_FMT_UYVY ? 2 * w : w;
-    const int row1 = fmt == MI355ENC_FMT_Y444 || fmt == MI355ENC_FMT_NV21 ? w : w / 2;
-    if (fmt <= MI355ENC_FMT_NV12 || fmt > MI355ENC_FMT_RGB || st[0] < row0) return MI355ENC_ERR_ARG;
-    for (int i = 1; i < nplanes; i++) if (!p[i] || st[i] < row1) return MI355ENC_ERR_ARG;
+    fmt = yv12_as_i420(fmt, p, st);
+    // every plane the format reads is there and as wide as the picture: the kernels stay inside rows of these lengths (NV12 is not converted: refused)
+    fmt_plane_t pl[3];
+    const int nplanes = fmt == MI355ENC_FMT_NV12 ? 0 : fmt_planes(fmt, w, ht, pl);
+    if (!nplanes || !planes_fit(nplanes, pl, p, st)) return MI355ENC_ERR_ARG;
     if (fmt >= MI355ENC_FMT_BGRX && !h->csc_ok) return MI355ENC_ERR_ARG;
     HIPCHK(hipSetDevice(h->cfg.device_id));
     int r;

@@ -1,7 +1,8 @@
 // enc_internal.hpp -- what the translation units of the C-ABI shim share (not part of the ABI):
 // the handle, the per-picture slot, and the helpers used by more than one of
 //   enc_handle.cpp    open / close / setters / statistics / fetch
-//   enc_schedule.cpp  the picture pipeline: submit*, the stream schedule of one picture, collect
+//   enc_input.cpp     the input path: submit*, from the caller's picture to the slot's source surfaces (upload, conversion, the sequence around them)
+//   enc_schedule.cpp  the picture pipeline: the stream schedule of one picture, the entropy worker, recovery, collect
 //   enc_overlay.cpp   the text overlay: setters, latch, layout, launch
 //   enc_image.cpp    image layers: setters, latch, upload + prepare, blend launches, retirement
 //   enc_orient.cpp    orientation of the input picture: setter, the slot's pre-orientation picture, launch, its stage entry points
@@ -275,9 +276,11 @@ void fill_ctx(mi355enc_t *h, frame_ctx_t *c, int qp, int drop, int idr, int set 
 int ip_rows_stamp(mi355enc_t *h, uint32_t epoch); // in front of every launch of a P picture's intra macroblock rows
 int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_t *src_uv, int src_stride, int64_t pts, int force_idr);
 void entropy_worker(mi355enc_t *h);
+// enc_input.cpp
 int upload_and_convert(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const planes[3], const int strides[3], hipStream_t up);
 // a picture of the input size tightly into the slot's raw staging buffer (any format); p / st: where its planes lie on the device then
 int upload_raw(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const planes[3], const int strides[3], hipStream_t up, const uint8_t *p[3], int st[3]);
+// enc_scale.cpp
 size_t raw_bytes(const mi355enc_t *h); // size of a slot's raw staging buffer
 // enc_quality.cpp
 int quality_alloc(mi355enc_t *h);   // the accumulator and result blocks (idempotent)
@@ -314,6 +317,21 @@ int input_target(mi355enc_t *h, slot_t *s, in_target_t *t);
 // ... and ends here: with a method, the orientation launch from (src_y, src_uv; null: the slot's pre-orientation picture) into the slot's coded surfaces (nothing with identity)
 int input_finish(mi355enc_t *h, slot_t *s, hipStream_t up, const uint8_t *src_y = nullptr, int y_stride = 0, const uint8_t *src_uv = nullptr, int uv_stride = 0);
 void orient_free(slot_t *s);
+// enc_input.cpp, what the other files share with it (these stay inside the library: the shared object exports what it did)
+#pragma GCC visibility push(hidden)
+// The planes of a w x h picture in `fmt`: how many, and per plane the bytes of a row and the rows.  0: not a format (YV12 is I420 once its planes are exchanged).
+// The one description every upload and every validation of caller-owned planes goes by.
+struct fmt_plane_t { int row, rows; };
+int fmt_planes(int fmt, int w, int h, fmt_plane_t pl[3]);
+bool planes_fit(int n, const fmt_plane_t pl[3], const uint8_t *const planes[3], const int strides[3]); // each of the n planes is there and its stride holds a row
+int yv12_as_i420(int fmt, const uint8_t *p[3], int st[3]); // YV12 is I420 with V before U: exchanges the two planes and answers I420 (the only exchange); any other format as it is
+// the two-launch form: the slot's NV12 picture of the input size (allocated on first use), which a conversion or decode launch writes, and the scale launch from
+// such a picture into the input target with the slot's plan (k_launch_scale's answer)
+struct nv12_pic_t { uint8_t *y, *uv; int stride; };
+int input_nv12(mi355enc_t *h, slot_t *s, nv12_pic_t *c);
+int scale_nv12(const nv12_pic_t *c, const in_target_t *t, const scale_plan_t *pl, hipStream_t up);
+int stage_out(mi355enc_t *h, slot_t *s, uint8_t *out_y, uint8_t *out_uv); // the slot's source surfaces to the host, behind everything on the main stream, waited for
+#pragma GCC visibility pop
 // enc_jpeg.cpp
 int jpeg_alloc(mi355enc_t *h, slot_t *s);  // the slot's coefficient buffers (idempotent)
 void jpeg_free(slot_t *s);

@@ -1,6 +1,6 @@
 // enc_jpeg.cpp -- MJPEG input: a slot's coefficient buffers, the host's entropy decode into them (jpeg_host.c), the
 // transfer and the launch of k_jpeg.hip into the slot's NV12 staging surfaces, and the single-stage entry points.  The submit entry point
-// itself sits beside the other submits in enc_schedule.cpp.
+// itself sits beside the other submits in enc_input.cpp.
 #include "enc_internal.hpp"
 
 #include "jpeg_host.h"
@@ -58,13 +58,13 @@ int jpeg_enqueue(mi355enc_t *h, slot_t *s, const mi355enc_jpeg_info_t *info, hip
     if (r) return r;
     if (!h->scaling) r = k_launch_jpeg(dc, dq, info->hs, info->vs, info->components, t.vw, t.vh, t.y, t.uv, t.W, t.H, s->d_jpeg_planar, up);
     else {
-        const int wi = (h->in_w + 15) & ~15;
-        if (!s->d_csc) HIPCHK(hipMalloc((void **)&s->d_csc, (size_t)wi * h->in_h * 3 / 2 + SURF_PAD));
-        uint8_t *cy = s->d_csc, *cuv = cy + (size_t)wi * h->in_h;
-        r = k_launch_jpeg(dc, dq, info->hs, info->vs, info->components, h->in_w, h->in_h, cy, cuv, wi, h->in_h, s->d_jpeg_planar, up);
+        nv12_pic_t c;
+        r = input_nv12(h, s, &c);
+        if (r) return r;
+        r = k_launch_jpeg(dc, dq, info->hs, info->vs, info->components, h->in_w, h->in_h, c.y, c.uv, c.stride, h->in_h, s->d_jpeg_planar, up);
         const scale_plan_t *pl = scale_plan_for(h, s, up);
         if (!pl) return MI355ENC_ERR_HIP;
-        if (!r) r = k_launch_scale(MI355ENC_FMT_NV12, cy, cuv, nullptr, wi, wi, 0, t.y, t.uv, t.W, t.H, pl, up);
+        if (!r) r = scale_nv12(&c, &t, pl, up);
     }
     if (r) return MI355ENC_ERR_ARG;
     HIPCHK(hipGetLastError());
@@ -78,13 +78,6 @@ int jpeg_time_launch(mi355enc_t *h, slot_t *s) {
     if (r) return r;
     return k_launch_jpeg((const int16_t *)(s->d_jpeg + JPEG_QT_BYTES), (const uint16_t *)s->d_jpeg, 2, 1, 3, t.vw, t.vh, t.y, t.uv, t.W, t.H,
                          s->d_jpeg_planar, h->stream) ? MI355ENC_ERR_ARG : MI355ENC_OK;
-}
-
-static int stage_out(mi355enc_t *h, slot_t *s, uint8_t *out_y, uint8_t *out_uv) {
-    HIPCHK(hipMemcpyAsync(out_y, s->d_src_y, h->ysz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(out_uv, s->d_src_uv, h->csz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MI355ENC_OK;
 }
 
 extern "C" {

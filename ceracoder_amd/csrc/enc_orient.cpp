@@ -87,10 +87,10 @@ int mi355enc_stage_orient(mi355enc_t *h, int method, const uint8_t *y, int y_str
     if (hipMemcpy2DAsync(d, ps, y, y_stride, pw, ph, hipMemcpyHostToDevice, h->stream) == hipSuccess &&
         hipMemcpy2DAsync(d + (size_t)ps * ph, ps, uv, uv_stride, pw, ph / 2, hipMemcpyHostToDevice, h->stream) == hipSuccess) {
         r = k_launch_orient(method, d, ps, d + (size_t)ps * ph, ps, pw, ph, s->d_src_y, s->d_src_uv, h->W, h->H, h->stream) ? MI355ENC_ERR_ARG : MI355ENC_OK;
-        if (!r && (hipGetLastError() != hipSuccess || hipMemcpyAsync(out_y, s->d_src_y, h->ysz, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-                   hipMemcpyAsync(out_uv, s->d_src_uv, h->csz, hipMemcpyDeviceToHost, h->stream) != hipSuccess)) r = MI355ENC_ERR_HIP;
+        if (!r && hipGetLastError() != hipSuccess) r = MI355ENC_ERR_HIP;
+        if (!r) r = stage_out(h, s, out_y, out_uv); // (waits for the stream)
     }
-    if (hipStreamSynchronize(h->stream) != hipSuccess) r = MI355ENC_ERR_HIP;
+    if (r && hipStreamSynchronize(h->stream) != hipSuccess) r = MI355ENC_ERR_HIP; // the temporary is freed behind everything that reads it, on every path
     (void)hipFree(d);
     return r;
 }

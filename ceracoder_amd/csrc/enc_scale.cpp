@@ -281,7 +281,9 @@ static void scale_sar(int in_w, int in_h, int out_w, int out_h, int *sw, int *sh
 
 size_t raw_bytes(const mi355enc_t *h) {
     const int w = h->in_w > h->W ? h->in_w : h->W, ht = h->in_h > h->H ? h->in_h : h->H;
-    return (size_t)(4 * w + 48) * ht + 64; // the largest: four bytes per pixel, or three planes of the picture's size, rows at multiples of 16 bytes
+    // Bounds every layout of fmt_planes() with rows at multiples of 16 bytes: no format has more than four bytes per pixel in all its planes together, plane by
+    // plane at most ht rows each (4:2:0 chroma, with half the rows, counts for less), and at most three planes round a row up, by 15 bytes each: (4 w + 45) ht.
+    return (size_t)(4 * w + 48) * ht + 64;
 }
 
 // The input geometry of a handle: the method, and the input size (in_set: the one mi355enc_set_input_size gave; otherwise it follows the method).  The scaler's
@@ -451,10 +453,7 @@ int mi355enc_stage_scale(mi355enc_t *h, int fmt, const uint8_t *const planes[3],
         r = input_finish(h, s, h->stream);
         if (r) return r;
     }
-    HIPCHK(hipMemcpyAsync(out_y, s->d_src_y, h->ysz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(out_uv, s->d_src_uv, h->csz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MI355ENC_OK;
+    return stage_out(h, s, out_y, out_uv);
 }
 
 } // extern "C"

@@ -1,4 +1,5 @@
-// enc_schedule.cpp -- the picture pipeline of the C-ABI shim.
+// enc_schedule.cpp -- the picture pipeline of the C-ABI shim: the stream schedule of one picture (enqueue_picture), the entropy worker, recovery, collect.
+// What stands in front of the search on the front stream -- the bracketed steps below -- is enqueued by the submit entry points (enc_input.cpp).
 //
 // Per picture:
 //   front stream: [H2D source | conversion | JPEG coefficients + inverse DCT | scale] -> [image layers, if one is set] -> [text overlay, if a text is set] -> P: me_kernel (SAD surfaces + first selection) -> me_select_kernel x ME_ITERS
@@ -63,12 +64,6 @@ int run_deblock(mi355enc_t *h, int ci, const frame_ctx_t *hc, hipStream_t st, co
 // scene-cut recovery: the decision taken with picture k's hand-over lands on picture k + lag, the first one that cannot have been
 // submitted yet (depth 0 behaves as depth 1, so that the stream is the same for both)
 static int sc_lag(const mi355enc_t *h) { return h->cfg.pipeline_depth >= 2 ? h->cfg.pipeline_depth + 1 : 2; }
-static hipStream_t upload_stream(const mi355enc_t *h) { return h->ustream ? h->ustream : h->fstream; }
-// the front stream's kernels read the source: behind the upload, if that went to a stream of its own
-static int upload_done(mi355enc_t *h, slot_t *s) {
-    if (h->ustream) { HIPCHK(hipEventRecord(s->ev_up, h->ustream)); HIPCHK(hipStreamWaitEvent(h->fstream, s->ev_up, 0)); }
-    return 0;
-}
 
 // rate control's ladder below QP 51 (oracle: k_drop_sad): the SAD under which a P macroblock carries no residual / takes the skip vector
 static const uint32_t k_drop_sad[DROP_MAX + 1] = {0, 384, 512, 768, 1024, 1536, 2048, 3072, 4096, 6144, 8192, 12288, 0xFFFFFFFFu};
@@ -332,86 +327,6 @@ int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_
     return MI355ENC_OK;
 }
 
-// Upload the planes of a picture of the input size tightly into the slot's raw staging buffer (rows at multiples of 16 bytes).
-int upload_raw(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const planes[3], const int strides[3], hipStream_t up, const uint8_t *p[3], int st[3]) {
-    const int w = h->in_w, ht = h->in_h;
-    if (fmt < MI355ENC_FMT_NV12 || fmt > MI355ENC_FMT_RGB || !planes || !strides || !planes[0]) return MI355ENC_ERR_ARG;
-    if (!s->d_raw) HIPCHK(hipMalloc((void **)&s->d_raw, raw_bytes(h)));
-    p[1] = p[2] = nullptr; st[1] = st[2] = 0;
-    if (fmt == MI355ENC_FMT_I420) {
-        if (!planes[1] || !planes[2] || strides[0] < w || strides[1] < w / 2 || strides[2] < w / 2) return MI355ENC_ERR_ARG;
-        const int r0 = (w + 15) & ~15, r1 = (w / 2 + 15) & ~15;
-        uint8_t *dy = s->d_raw, *du = dy + (size_t)r0 * ht, *dv = du + (size_t)r1 * (ht / 2);
-        HIPCHK(hipMemcpy2DAsync(dy, r0, planes[0], strides[0], w, ht, hipMemcpyHostToDevice, up));
-        HIPCHK(hipMemcpy2DAsync(du, r1, planes[1], strides[1], w / 2, ht / 2, hipMemcpyHostToDevice, up));
-        HIPCHK(hipMemcpy2DAsync(dv, r1, planes[2], strides[2], w / 2, ht / 2, hipMemcpyHostToDevice, up));
-        p[0] = dy; p[1] = du; p[2] = dv; st[0] = r0; st[1] = st[2] = r1;
-    } else if (fmt == MI355ENC_FMT_Y42B || fmt == MI355ENC_FMT_Y444) { // three planes: chroma of the full height, half or full width
-        const int cw = fmt == MI355ENC_FMT_Y444 ? w : w / 2;
-        if (!planes[1] || !planes[2] || strides[0] < w || strides[1] < cw || strides[2] < cw) return MI355ENC_ERR_ARG;
-        const int r0 = (w + 15) & ~15, r1 = (cw + 15) & ~15;
-        uint8_t *dy = s->d_raw, *du = dy + (size_t)r0 * ht, *dv = du + (size_t)r1 * ht;
-        HIPCHK(hipMemcpy2DAsync(dy, r0, planes[0], strides[0], w, ht, hipMemcpyHostToDevice, up));
-        HIPCHK(hipMemcpy2DAsync(du, r1, planes[1], strides[1], cw, ht, hipMemcpyHostToDevice, up));
-        HIPCHK(hipMemcpy2DAsync(dv, r1, planes[2], strides[2], cw, ht, hipMemcpyHostToDevice, up));
-        p[0] = dy; p[1] = du; p[2] = dv; st[0] = r0; st[1] = st[2] = r1;
-    } else if (fmt >= MI355ENC_FMT_BGRX) { // one packed plane of four or three bytes per pixel
-        const int bpp = fmt >= MI355ENC_FMT_BGR ? 3 : 4;
-        if (strides[0] < bpp * w) return MI355ENC_ERR_ARG;
-        const int r0 = (bpp * w + 15) & ~15;
-        HIPCHK(hipMemcpy2DAsync(s->d_raw, r0, planes[0], strides[0], (size_t)bpp * w, ht, hipMemcpyHostToDevice, up));
-        p[0] = s->d_raw; st[0] = r0;
-    } else if (fmt == MI355ENC_FMT_NV12 || fmt == MI355ENC_FMT_NV21) {
-        if (!planes[1] || strides[0] < w || strides[1] < w) return MI355ENC_ERR_ARG;
-        const int r0 = (w + 15) & ~15;
-        uint8_t *dy = s->d_raw, *duv = dy + (size_t)r0 * ht;
-        HIPCHK(hipMemcpy2DAsync(dy, r0, planes[0], strides[0], w, ht, hipMemcpyHostToDevice, up));
-        HIPCHK(hipMemcpy2DAsync(duv, r0, planes[1], strides[1], w, ht / 2, hipMemcpyHostToDevice, up));
-        p[0] = dy; p[1] = duv; st[0] = st[1] = r0;
-    } else if (fmt == MI355ENC_FMT_YUY2 || fmt == MI355ENC_FMT_UYVY) {
-        if (strides[0] < 2 * w) return MI355ENC_ERR_ARG;
-        const int r0 = (2 * w + 15) & ~15;
-        HIPCHK(hipMemcpy2DAsync(s->d_raw, r0, planes[0], strides[0], 2 * w, ht, hipMemcpyHostToDevice, up));
-        p[0] = s->d_raw; st[0] = r0;
-    } else return MI355ENC_ERR_ARG; // (YV12 arrives here as I420 with its chroma planes exchanged)
-    return MI355ENC_OK;
-}
-// ... and convert (or, with an input size of its own, scale) it into the slot's NV12 staging surfaces.  NV12 only when scaling: unscaled, it is
-// transferred straight into the surfaces (mi355enc_submit).
-int upload_and_convert(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const planes[3], const int strides[3], hipStream_t up) {
-    if (fmt == MI355ENC_FMT_NV12 && !h->scaling) return MI355ENC_ERR_ARG;
-    if (!planes || !strides) return MI355ENC_ERR_ARG;
-    if (fmt == MI355ENC_FMT_YV12) { // I420 with V before U
-        const uint8_t *const pl[3] = {planes[0], planes[2], planes[1]};
-        const int sl[3] = {strides[0], strides[2], strides[1]};
-        return upload_and_convert(h, s, MI355ENC_FMT_I420, pl, sl, up);
-    }
-    if (fmt >= MI355ENC_FMT_BGRX && fmt <= MI355ENC_FMT_RGB && !h->csc_ok) return MI355ENC_ERR_ARG; // (a matrix code RGB cannot be converted with: before anything is uploaded)
-    const uint8_t *p[3];
-    int st[3];
-    int r = upload_raw(h, s, fmt, planes, strides, up, p, st);
-    if (r) return r;
-    in_target_t t; // the coded surfaces, or with an orientation the slot's pre-orientation picture
-    r = input_target(h, s, &t);
-    if (r) return r;
-    const scale_plan_t *pl = h->scaling ? scale_plan_for(h, s, up) : nullptr;
-    if (h->scaling && !pl) return MI355ENC_ERR_HIP;
-    if (fmt >= MI355ENC_FMT_Y42B) { // the formats of k_csc.hip; with an input size of its own: converted at that size, then scaled as NV12
-        if (!h->scaling) r = k_launch_csc2(fmt, p[0], p[1], p[2], st[0], st[1], st[2], t.y, t.uv, t.vw, t.vh, t.W, t.H, h->csc_coef, up);
-        else {
-            const int wi = (h->in_w + 15) & ~15;
-            if (!s->d_csc) HIPCHK(hipMalloc((void **)&s->d_csc, (size_t)wi * h->in_h * 3 / 2 + SURF_PAD));
-            uint8_t *cy = s->d_csc, *cuv = cy + (size_t)wi * h->in_h;
-            r = k_launch_csc2(fmt, p[0], p[1], p[2], st[0], st[1], st[2], cy, cuv, h->in_w, h->in_h, wi, h->in_h, h->csc_coef, up);
-            if (!r) r = k_launch_scale(MI355ENC_FMT_NV12, cy, cuv, nullptr, wi, wi, 0, t.y, t.uv, t.W, t.H, pl, up);
-        }
-    } else if (h->scaling) r = k_launch_scale(fmt, p[0], p[1], p[2], st[0], st[1], st[2], t.y, t.uv, t.W, t.H, pl, up);
-    else r = k_launch_csc(fmt, p[0], p[1], p[2], st[0], st[1], st[2], t.y, t.uv, t.vw, t.vh, t.W, t.H, up);
-    if (r) return MI355ENC_ERR_ARG;
-    HIPCHK(hipGetLastError());
-    return input_finish(h, s, up);
-}
-
 // ---- the entropy-coding worker: one picture at a time, in submission order
 static size_t code_access_unit(mi355enc_t *h, slot_t *s, uint8_t *out, size_t cap) {
     size_t n = 0;
@@ -528,183 +443,7 @@ static int recover(mi355enc_t *h, unsigned code) {
     return MI355ENC_OK;
 }
 
-// one piece of a pageable source picture: into the pinned staging buffer, then on its way to the device
-static int stage_piece(mi355enc_t *h, const mi355enc::stage_job &j, hipStream_t up) {
-    if (j.src_stride == (int)j.dst_stride) memcpy(j.dst, j.src, j.dst_stride * (size_t)(j.rows - 1) + (size_t)j.width);
-    else for (int r = 0; r < j.rows; r++) memcpy(j.dst + (size_t)r * j.dst_stride, j.src + (size_t)r * j.src_stride, (size_t)j.width);
-    return hipMemcpyAsync(j.dev, j.dst, j.dst_stride * (size_t)(j.rows - 1) + (size_t)j.width, hipMemcpyHostToDevice, up) == hipSuccess ? 0 : 1;
-}
-void stage_helper(mi355enc_t *h) {
-    (void)hipSetDevice(h->cfg.device_id);
-    unsigned long long seen = 0;
-    for (;;) {
-        {
-            std::unique_lock<std::mutex> g(h->stg_mu);
-            h->stg_cv.wait(g, [&] { return h->stg_stop || (h->stg_gen != seen && h->stg_next < h->stg_n); });
-            if (h->stg_stop) return;
-        }
-        const hipStream_t up = upload_stream(h);
-        for (;;) {
-            int i;
-            { std::lock_guard<std::mutex> g(h->stg_mu); seen = h->stg_gen; i = h->stg_next < h->stg_n ? h->stg_next++ : -1; }
-            if (i < 0) break;
-            const int e = stage_piece(h, h->stg_job[i], up);
-            bool last;
-            { std::lock_guard<std::mutex> g(h->stg_mu); if (e) h->stg_err = e; last = ++h->stg_done >= h->stg_n; }
-            if (last) h->stg_done_cv.notify_all();
-        }
-    }
-}
 extern "C" {
-
-// Host input.  A picture in memory from mi355enc_host_alloc() is DMA'd from where it lies (the call returns at once; the memory is the
-// caller's again after the matching collect()).  Anything else is pageable as far as HIP knows: a stream-ordered copy from pageable memory
-// blocks the calling thread while the runtime stages it chunk by chunk through its own pinned buffers -- so the picture is copied once, by
-// this thread, into the slot's pinned staging buffer and leaves from there in one asynchronous transfer per plane, on the front stream,
-// beside the kernels of the pictures before it.
-int mi355enc_submit(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t *uv, int uv_stride, int64_t pts, int force_idr) {
-    if (!h || !y || !uv || y_stride < h->in_w || uv_stride < h->in_w) return MI355ENC_ERR_ARG;
-    if (h->pending > h->cfg.pipeline_depth) return MI355ENC_ERR_STATE;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    slot_t *s = &h->slot[h->head];
-    overlay_latch(h, s);
-    { int r = image_latch(h, s); if (r) return r; }
-    const int w = h->in_w, ht = h->in_h;
-    hipStream_t up = upload_stream(h);
-    // where the planes go: the staging surfaces at the coded stride, or -- to be scaled -- the raw staging buffer at the input's
-    // (with an orientation, `the staging surfaces' are the slot's pre-orientation picture at its own stride: input_target)
-    if (h->scaling && !s->d_raw) HIPCHK(hipMalloc((void **)&s->d_raw, raw_bytes(h)));
-    in_target_t t;
-    { int r = input_target(h, s, &t); if (r) return r; }
-    const int ds = h->scaling ? (w + 15) & ~15 : t.W;
-    uint8_t *dev_y = h->scaling ? s->d_raw : t.y, *dev_uv = h->scaling ? s->d_raw + (size_t)ds * ht : t.uv;
-    const bool pinned = host_range_pinned(y, (size_t)y_stride * (ht - 1) + w) && host_range_pinned(uv, (size_t)uv_stride * (ht / 2 - 1) + w);
-    if (pinned || h->cfg.pipeline_depth == 0) {
-        // pinned: transferred in place.  pipeline_depth 0 (the latency mode: collect() follows at once, there is nothing to run beside): the
-        // runtime's own pageable path, which stages and transfers in chunks on its side of the call (measured 0.06 ms less per 1080p picture
-        // than staging here and transferring afterwards)
-        HIPCHK(hipMemcpy2DAsync(dev_y, ds, y, y_stride, w, ht, hipMemcpyHostToDevice, up));
-        HIPCHK(hipMemcpy2DAsync(dev_uv, ds, uv, uv_stride, w, ht / 2, hipMemcpyHostToDevice, up));
-        h->st.pinned_inputs += pinned ? 1 : 0;
-    } else {
-        if (!s->h_src) HIPCHK(hipHostMalloc((void **)&s->h_src, (h->scaling || h->orient) ? (size_t)ds * ht * 3 / 2 : h->ysz + h->csz, hipHostMallocDefault));
-        // rows at the coded stride, so that a range of rows is one contiguous transfer; in pieces (luma thirds or sixths, the chroma plane in one or two), each
-        // sent as soon as it is staged: the transfer of one piece runs beside the staging of the next, and with the helper threads three pieces are
-        // staged side by side (a single thread copies 3.1 MB in 0.15-0.2 ms, as long as the device needs for the whole picture)
-        uint8_t *hy = s->h_src, *huv = s->h_src + (size_t)ds * ht;
-        mi355enc::stage_job jobs[8];
-        int nj = 0;
-        const int ny = h->stg_on ? 6 : 3, nc = h->stg_on ? 2 : 1;
-        for (int k = 0; k < ny; k++) {
-            const int r0 = (ht * k / ny) & ~1, r1 = k == ny - 1 ? ht : (ht * (k + 1) / ny) & ~1;
-            if (r1 > r0) jobs[nj++] = {y + (size_t)r0 * y_stride, hy + (size_t)r0 * ds, dev_y + (size_t)r0 * ds, y_stride, r1 - r0, w, (size_t)ds};
-        }
-        for (int k = 0; k < nc; k++) {
-            const int r0 = (ht / 2) * k / nc, r1 = (ht / 2) * (k + 1) / nc;
-            if (r1 > r0) jobs[nj++] = {uv + (size_t)r0 * uv_stride, huv + (size_t)r0 * ds, dev_uv + (size_t)r0 * ds, uv_stride, r1 - r0, w, (size_t)ds};
-        }
-        if (h->stg_on) {
-            { std::lock_guard<std::mutex> g(h->stg_mu); for (int i = 0; i < nj; i++) h->stg_job[i] = jobs[i]; h->stg_n = nj; h->stg_next = 0; h->stg_done = 0; h->stg_err = 0; h->stg_gen++; }
-            h->stg_cv.notify_all();
-            for (;;) { // the caller takes pieces too
-                int i;
-                { std::lock_guard<std::mutex> g(h->stg_mu); i = h->stg_next < h->stg_n ? h->stg_next++ : -1; }
-                if (i < 0) break;
-                const int e = stage_piece(h, h->stg_job[i], up);
-                { std::lock_guard<std::mutex> g(h->stg_mu); if (e) h->stg_err = e; h->stg_done++; }
-            }
-            { std::unique_lock<std::mutex> g(h->stg_mu); h->stg_done_cv.wait(g, [&] { return h->stg_done >= h->stg_n; }); if (h->stg_err) return MI355ENC_ERR_HIP; }
-        } else
-            for (int i = 0; i < nj; i++) if (stage_piece(h, jobs[i], up)) return MI355ENC_ERR_HIP;
-    }
-    if (h->scaling) {
-        const scale_plan_t *pl = scale_plan_for(h, s, up);
-        if (!pl) return MI355ENC_ERR_HIP;
-        if (k_launch_scale(MI355ENC_FMT_NV12, dev_y, dev_uv, nullptr, ds, ds, 0, t.y, t.uv, t.W, t.H, pl, up)) return MI355ENC_ERR_ARG;
-    }
-    else if (!h->orient && w != h->W) k_launch_pad(s->d_src_y, s->d_src_uv, h->W, w, ht, h->W, h->H, up); // (the orientation launch writes the margin itself)
-    { int r = input_finish(h, s, up); if (r) return r; }
-    { int r = image_draw(h, s, up); if (r) return r; }
-    { int r = overlay_draw(h, s, up); if (r) return r; }
-    { int r = upload_done(h, s); if (r) return r; }
-    return enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
-}
-
-int mi355enc_submit_fmt(mi355enc_t *h, int fmt, const uint8_t *const planes[3], const int strides[3], int64_t pts, int force_idr) {
-    if (!h || !planes || !strides) return MI355ENC_ERR_ARG;
-    if (fmt == MI355ENC_FMT_NV12) return mi355enc_submit(h, planes[0], strides[0], planes[1], strides[1], pts, force_idr);
-    if (h->pending > h->cfg.pipeline_depth) return MI355ENC_ERR_STATE;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    slot_t *s = &h->slot[h->head];
-    overlay_latch(h, s);
-    { int r = image_latch(h, s); if (r) return r; }
-    int r = upload_and_convert(h, s, fmt, planes, strides, upload_stream(h));
-    if (r) return r;
-    r = image_draw(h, s, upload_stream(h)); if (r) return r;
-    r = overlay_draw(h, s, upload_stream(h)); if (r) return r;
-    r = upload_done(h, s); if (r) return r;
-    return enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
-}
-
-// MJPEG input: the host decodes the entropy-coded data into the slot's pinned coefficient buffer first -- a picture that is refused or does not decode has
-// touched nothing else -- then the transfer and the JPEG launch take the place of the conversion launch.
-int mi355enc_submit_jpeg(mi355enc_t *h, const uint8_t *data, size_t len, int64_t pts, int force_idr) {
-    if (!h || !data) return MI355ENC_ERR_ARG;
-    if (h->pending > h->cfg.pipeline_depth) return MI355ENC_ERR_STATE;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    slot_t *s = &h->slot[h->head];
-    mi355enc_jpeg_info_t info;
-    int r = jpeg_decode_host(h, s, data, len, &info);
-    if (r) return r;
-    overlay_latch(h, s);
-    r = image_latch(h, s); if (r) return r;
-    r = jpeg_enqueue(h, s, &info, upload_stream(h)); if (r) return r;
-    r = image_draw(h, s, upload_stream(h)); if (r) return r;
-    r = overlay_draw(h, s, upload_stream(h)); if (r) return r;
-    r = upload_done(h, s); if (r) return r;
-    return enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
-}
-
-int mi355enc_submit_device(mi355enc_t *h, const void *d_y, int y_stride, const void *d_uv, int uv_stride, int64_t pts, int force_idr) {
-    if (!h || !d_y || !d_uv || y_stride < h->in_w || uv_stride < h->in_w) return MI355ENC_ERR_ARG;
-    if (h->pending > h->cfg.pipeline_depth) return MI355ENC_ERR_STATE;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    slot_t *s = &h->slot[h->head];
-    overlay_latch(h, s);
-    { int r = image_latch(h, s); if (r) return r; }
-    if (h->scaling) { // scaled from where the planes lie into the slot's staging surfaces
-        in_target_t t;
-        { int r = input_target(h, s, &t); if (r) return r; }
-        const scale_plan_t *pl = scale_plan_for(h, s, upload_stream(h));
-        if (!pl) return MI355ENC_ERR_HIP;
-        if (k_launch_scale(MI355ENC_FMT_NV12, (const uint8_t *)d_y, (const uint8_t *)d_uv, nullptr, y_stride, uv_stride, 0, t.y, t.uv, t.W, t.H, pl, upload_stream(h))) return MI355ENC_ERR_ARG;
-        HIPCHK(hipGetLastError());
-        { int r = input_finish(h, s, upload_stream(h)); if (r) return r; }
-        { int r = image_draw(h, s, upload_stream(h)); if (r) return r; }
-        { int r = overlay_draw(h, s, upload_stream(h)); if (r) return r; }
-        { int r = upload_done(h, s); if (r) return r; }
-        return enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
-    }
-    hipStream_t up = upload_stream(h);
-    if (h->orient) { // oriented from where the planes lie, at their stride and address, into the slot's staging surfaces: never in place, the caller's planes are only read
-        { int r = input_finish(h, s, up, (const uint8_t *)d_y, y_stride, (const uint8_t *)d_uv, uv_stride); if (r) return r; }
-        { int r = image_draw(h, s, up); if (r) return r; }
-        { int r = overlay_draw(h, s, up); if (r) return r; }
-        { int r = upload_done(h, s); if (r) return r; }
-        return enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
-    }
-    const int w = h->cfg.width, ht = h->cfg.height;
-    // in place -- unless a text is to be drawn or an image blended in: that goes into the encoder's own surfaces, never into the caller's planes
-    const bool direct = !s->ov_len && !image_active(s) && w == h->W && y_stride == uv_stride && (y_stride & 15) == 0 && (((uintptr_t)d_y | (uintptr_t)d_uv) & 15) == 0;
-    if (direct) return enqueue_picture(h, s, (const uint8_t *)d_y, (const uint8_t *)d_uv, y_stride, pts, force_idr);
-    HIPCHK(hipMemcpy2DAsync(s->d_src_y, h->W, d_y, y_stride, w, ht, hipMemcpyDeviceToDevice, up));
-    HIPCHK(hipMemcpy2DAsync(s->d_src_uv, h->W, d_uv, uv_stride, w, ht / 2, hipMemcpyDeviceToDevice, up));
-    if (w != h->W) k_launch_pad(s->d_src_y, s->d_src_uv, h->W, w, ht, h->W, h->H, up);
-    { int r = image_draw(h, s, up); if (r) return r; }
-    { int r = overlay_draw(h, s, up); if (r) return r; }
-    { int r = upload_done(h, s); if (r) return r; }
-    return enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
-}
 
 int mi355enc_collect(mi355enc_t *h, uint8_t *out, size_t out_cap, size_t *out_len, int *is_keyframe, int64_t *pts, int *qp) {
     if (!h || !out || !out_len) return MI355ENC_ERR_ARG;

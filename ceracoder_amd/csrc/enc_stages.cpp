@@ -7,19 +7,6 @@
 
 extern "C" {
 
-int mi355enc_stage_csc(mi355enc_t *h, int fmt, const uint8_t *const planes[3], const int strides[3], uint8_t *out_y, uint8_t *out_uv) {
-    if (!h || !out_y || !out_uv || h->pending) return MI355ENC_ERR_ARG;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    STAGE_IDLE(h);
-    slot_t *s = &h->slot[0];
-    int r = upload_and_convert(h, s, fmt, planes, strides, h->stream);
-    if (r) return r;
-    HIPCHK(hipMemcpyAsync(out_y, s->d_src_y, h->ysz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(out_uv, s->d_src_uv, h->csz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MI355ENC_OK;
-}
-
 // ---------------------------------------------------------------- single-stage entry points
 // A single-stage call overwrites the reconstruction buffers, the previous-source planes and the record sets behind the encoder's back: the
 // next picture submitted through the pipeline must not predict from any of it, so it is coded as an IDR picture and nothing of the
