@@ -134,7 +134,7 @@ int mi355enc_open(const mi355enc_cfg_t *cfg, mi355enc_t **out) {
     h->cur = 0; h->have_ref = 0; h->frames_since_idr = 0; h->idr_count = 0; h->last_collected_rec = 0; h->last_slot = nullptr;
     h->ir_on = 0; h->ir_pos = 0; h->ir_R = 0; h->ir_skip_owed = 0;
     h->in_w = cfg->width; h->in_h = cfg->height; h->sar_w = h->sar_h = 0; h->scaling = false; h->d_scale_tab = nullptr; h->scale_tab_bytes = 0; memset(&h->scale, 0, sizeof h->scale);
-    h->col_full = 0; h->col_prim = h->col_trc = h->col_mat = 2; csc_resolve(h);
+    h->col_full = 0; h->col_prim = h->col_trc = h->col_mat = 2; h->in_col_set = false; csc_resolve(h);
     h->ov_len = 0; h->ov_last_have = 0; h->ov_last_len = 0; mi355enc_overlay_default_style(&h->ov_style);
     for (int l = 0; l < MI355ENC_IMAGE_LAYERS; l++) { h->img_cur[l] = nullptr; h->img_x[l] = h->img_y[l] = 0; h->img_op[l] = 256; h->img_serial[l] = 0; }
     h->img_bufs = nullptr; h->img_dev_bytes = 0; memset(h->img_last, 0, sizeof h->img_last);

@@ -4,7 +4,7 @@
 //   its own argument checks
 //   ingest_begin   the pipeline-full check, the slot, the latches (text, image layers)
 //   fill           its own way of filling the input target: copy | convert | decode | scale, ending in input_finish (the orientation launch)
-//   ingest_end     image layers -> text -> upload event -> enqueue_picture (enc_schedule.cpp) on the slot's own surfaces
+//   ingest_end     colour step -> image layers -> text -> upload event -> enqueue_picture (enc_schedule.cpp) on the slot's own surfaces
 // The one exception is the in-place exit of mi355enc_submit_device.  A new step on the way in goes into ingest_end (one that works on the coded surfaces) or
 // in front of input_finish (one that works on the pre-orientation picture), never into a submit.
 // Also here: what the fills share -- a format's planes, the raw staging upload, the two-launch form, the staging helper threads -- and mi355enc_stage_csc.
@@ -23,6 +23,7 @@ static int ingest_slot(mi355enc_t *h, slot_t **s) {
     if (h->pending > h->cfg.pipeline_depth) return MI355ENC_ERR_STATE;
     HIPCHK(hipSetDevice(h->cfg.device_id));
     *s = &h->slot[h->head];
+    (*s)->yuv_step = h->yuv_on;
     return MI355ENC_OK;
 }
 // what the control thread set last becomes the picture's
@@ -38,7 +39,8 @@ static int ingest_begin(mi355enc_t *h, slot_t **s) {
 }
 // the slot's surfaces hold the oriented picture: everything that is drawn into it, in this order, then the schedule
 static int ingest_end(mi355enc_t *h, slot_t *s, hipStream_t up, int64_t pts, int force_idr) {
-    int r = image_draw(h, s, up);
+    int r = s->yuv_step ? yuv_draw(h, s, up) : MI355ENC_OK; // the colour step first: layers and text are drawn in the output's colours
+    if (!r) r = image_draw(h, s, up);
     if (!r) r = overlay_draw(h, s, up);
     if (!r) r = upload_done(h, s);
     return r ? r : enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
@@ -55,6 +57,10 @@ int fmt_planes(int fmt, int w, int h, fmt_plane_t pl[3]) {
     case MI355ENC_FMT_YUY2: case MI355ENC_FMT_UYVY: pl[0].row = 2 * w; return 1;
     case MI355ENC_FMT_BGRX: case MI355ENC_FMT_RGBX: case MI355ENC_FMT_XRGB: case MI355ENC_FMT_XBGR: pl[0].row = 4 * w; return 1;
     case MI355ENC_FMT_BGR: case MI355ENC_FMT_RGB: pl[0].row = 3 * w; return 1;
+    case MI355ENC_FMT_P010: pl[0].row = 2 * w; pl[1] = {2 * w, h / 2}; return 2;
+    case MI355ENC_FMT_I420_10: pl[0].row = 2 * w; pl[1] = pl[2] = {w, h / 2}; return 3;
+    case MI355ENC_FMT_V210: pl[0].row = (w + 5) / 6 * 16; return 1;
+    case MI355ENC_FMT_GRAY8: return 1;
     default: return 0; // (YV12 too: it arrives here as I420, yv12_as_i420)
     }
 }
@@ -107,7 +113,7 @@ int upload_and_convert(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const p
         int sl[3] = {strides[0], strides[1], strides[2]};
         return upload_and_convert(h, s, yv12_as_i420(fmt, pl, sl), pl, sl, up);
     }
-    if (fmt >= MI355ENC_FMT_BGRX && fmt <= MI355ENC_FMT_RGB && !h->csc_ok) return MI355ENC_ERR_ARG; // (a matrix code RGB cannot be converted with: before anything is uploaded)
+    if (fmt_is_rgb(fmt) && !h->csc_ok) return MI355ENC_ERR_ARG; // (a matrix code RGB cannot be converted with: before anything is uploaded)
     const uint8_t *p[3];
     int st[3];
     int r = upload_raw(h, s, fmt, planes, strides, up, p, st);
@@ -185,7 +191,7 @@ int mi355enc_stage_csc(mi355enc_t *h, int fmt, const uint8_t *const planes[3], c
 // this thread, into the slot's pinned staging buffer and leaves from there in one asynchronous transfer per plane, on the front stream,
 // beside the kernels of the pictures before it.
 int mi355enc_submit(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t *uv, int uv_stride, int64_t pts, int force_idr) {
-    if (!h || !y || !uv || y_stride < h->in_w || uv_stride < h->in_w) return MI355ENC_ERR_ARG;
+    if (!h || !y || !uv || y_stride < h->in_w || uv_stride < h->in_w || h->yuv_bad) return MI355ENC_ERR_ARG; // (yuv_bad: YUV samples that cannot be converted to the output's matrix)
     slot_t *s;
     { int r = ingest_begin(h, &s); if (r) return r; }
     const int w = h->in_w, ht = h->in_h;
@@ -251,8 +257,10 @@ int mi355enc_submit(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t
 int mi355enc_submit_fmt(mi355enc_t *h, int fmt, const uint8_t *const planes[3], const int strides[3], int64_t pts, int force_idr) {
     if (!h || !planes || !strides) return MI355ENC_ERR_ARG;
     if (fmt == MI355ENC_FMT_NV12) return mi355enc_submit(h, planes[0], strides[0], planes[1], strides[1], pts, force_idr);
+    if (!fmt_is_rgb(fmt) && h->yuv_bad) return MI355ENC_ERR_ARG;
     slot_t *s;
     int r = ingest_begin(h, &s);
+    if (!r && fmt_is_rgb(fmt)) s->yuv_step = false; // (RGB is converted straight to the output's matrix and range)
     if (!r) r = upload_and_convert(h, s, fmt, planes, strides, upload_stream(h));
     return r ? r : ingest_end(h, s, upload_stream(h), pts, force_idr);
 }
@@ -260,7 +268,7 @@ int mi355enc_submit_fmt(mi355enc_t *h, int fmt, const uint8_t *const planes[3], 
 // MJPEG input: the host decodes the entropy-coded data into the slot's pinned coefficient buffer first -- a picture that is refused or does not decode has
 // touched nothing else -- then the transfer and the JPEG launch take the place of the conversion launch.
 int mi355enc_submit_jpeg(mi355enc_t *h, const uint8_t *data, size_t len, int64_t pts, int force_idr) {
-    if (!h || !data) return MI355ENC_ERR_ARG;
+    if (!h || !data || h->yuv_bad) return MI355ENC_ERR_ARG;
     slot_t *s;
     int r = ingest_slot(h, &s);
     if (r) return r;
@@ -272,9 +280,9 @@ int mi355enc_submit_jpeg(mi355enc_t *h, const uint8_t *data, size_t len, int64_t
 }
 
 // Device input.  The in-place exit is the one exception to the sequence: the kernels read the caller's planes where they lie, nothing is drawn (with a
-// text or an active layer the exit is not taken) and nothing was uploaded, so enqueue_picture follows the latches directly.
+// colour step, a text or an active layer the exit is not taken) and nothing was uploaded, so enqueue_picture follows the latches directly.
 int mi355enc_submit_device(mi355enc_t *h, const void *d_y, int y_stride, const void *d_uv, int uv_stride, int64_t pts, int force_idr) {
-    if (!h || !d_y || !d_uv || y_stride < h->in_w || uv_stride < h->in_w) return MI355ENC_ERR_ARG;
+    if (!h || !d_y || !d_uv || y_stride < h->in_w || uv_stride < h->in_w || h->yuv_bad) return MI355ENC_ERR_ARG;
     slot_t *s;
     int r = ingest_begin(h, &s);
     if (r) return r;
@@ -292,8 +300,8 @@ int mi355enc_submit_device(mi355enc_t *h, const void *d_y, int y_stride, const v
         r = input_finish(h, s, up, (const uint8_t *)d_y, y_stride, (const uint8_t *)d_uv, uv_stride);
     } else {
         const int w = h->cfg.width, ht = h->cfg.height;
-        // in place -- unless a text is to be drawn or an image blended in: that goes into the encoder's own surfaces, never into the caller's planes
-        const bool direct = !s->ov_len && !image_active(s) && w == h->W && y_stride == uv_stride && (y_stride & 15) == 0 && (((uintptr_t)d_y | (uintptr_t)d_uv) & 15) == 0;
+        // in place -- unless the samples are to be converted, a text drawn or an image blended in: that goes into the encoder's own surfaces, never into the caller's planes
+        const bool direct = !s->yuv_step && !s->ov_len && !image_active(s) && w == h->W && y_stride == uv_stride && (y_stride & 15) == 0 && (((uintptr_t)d_y | (uintptr_t)d_uv) & 15) == 0;
         if (direct) return enqueue_picture(h, s, (const uint8_t *)d_y, (const uint8_t *)d_uv, y_stride, pts, force_idr);
         HIPCHK(hipMemcpy2DAsync(s->d_src_y, h->W, d_y, y_stride, w, ht, hipMemcpyDeviceToDevice, up));
         HIPCHK(hipMemcpy2DAsync(s->d_src_uv, h->W, d_uv, uv_stride, w, ht / 2, hipMemcpyDeviceToDevice, up));

@@ -8,6 +8,7 @@
 //   enc_orient.cpp    orientation of the input picture: setter, the slot's pre-orientation picture, launch, its stage entry points
 //   enc_jpeg.cpp      MJPEG input: coefficient buffers, host decode, transfer + launch, its stage entry points
 //   enc_snapshot.cpp  JPEG stills: request / take, the blocks the levels land in, the launch, its stage entry points
+//   enc_csc.cpp       colorimetry: the setters, the RGB matrix and the YUV -> YUV table, the colour step's launch, their stage entry points
 //   enc_stages.cpp    single-stage entry points (parity tests, probes) and the host-only stages
 #ifndef MI355_ENC_INTERNAL_HPP
 #define MI355_ENC_INTERNAL_HPP
@@ -103,6 +104,8 @@ struct slot_t {
     image_t *img[MI355ENC_IMAGE_LAYERS]; int img_x[MI355ENC_IMAGE_LAYERS], img_y[MI355ENC_IMAGE_LAYERS], img_op[MI355ENC_IMAGE_LAYERS]; uint32_t img_serial[MI355ENC_IMAGE_LAYERS];
     // stills: the block this picture's still lands in, + 1 (0: the picture is not armed), and the request it was armed with; a recovery keeps both
     int snap; mi355enc_snapshot_req_t snap_req;
+    // the colour step: this picture's samples are converted in ingest_end (latched with the slot; an RGB picture, converted straight to the output, clears it)
+    bool yuv_step;
 };
 
 struct mi355enc {
@@ -201,6 +204,11 @@ struct mi355enc {
     // (csc_coef: the ten words of mi355enc_csc_coefficients; csc_ok false: the matrix code is not one RGB input can be converted with)
     int col_full, col_prim, col_trc, col_mat;
     int csc_coef[10]; bool csc_ok;
+    // what submitted YUV samples mean (mi355enc_set_input_colorimetry).  in_col_set: the call was made; yuv_on: the resolved input differs from
+    // the resolved output, so every YUV picture takes the colour step (yuv_coef: the nine words of mi355enc_yuv_coefficients); yuv_bad: the call was made and the
+    // output matrix is not one the step can convert to -- a YUV submit is refused
+    bool in_col_set, yuv_on, yuv_bad;
+    int in_col_full, in_col_mat, yuv_coef[9];
     uint32_t n_recoveries, last_error_word;
     // quality metrics (mi355enc_set_quality_metrics; everything null / 0 while they are off and no stage call has asked for them):
     // per slot, and one more for the single-stage entry points, a block of QUALITY_WORDS accumulator words on the device and of result words in pinned
@@ -348,5 +356,9 @@ int snapshot_time_launch(mi355enc_t *h, slot_t *s);
 void snapshot_init(mi355enc_t *h);
 void snapshot_free(mi355enc_t *h);
 // enc_csc.cpp
-void csc_resolve(mi355enc_t *h); // fills csc_coef / csc_ok from col_mat, col_full and the coded size
+void csc_resolve(mi355enc_t *h); // fills csc_coef / csc_ok from col_mat, col_full and the coded size, and what the colour step follows from them
+static inline bool fmt_is_rgb(int fmt) { return fmt >= MI355ENC_FMT_BGRX && fmt <= MI355ENC_FMT_RGB; }
+// the colour step on the slot's coded surfaces, behind everything enqueued on st so far: the picture part (with a geometry: the oriented destination rectangle) is
+// converted in place, the border keeps its bytes
+int yuv_draw(mi355enc_t *h, slot_t *s, hipStream_t st);
 #endif

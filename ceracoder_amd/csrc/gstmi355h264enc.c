@@ -102,6 +102,7 @@ typedef struct {
      * closes or opens it (s->enc and snap_gen change under it, taken in front of the object lock).  snap_mu / snap_cv: the helper's wake-ups, and snap_count.
      * snap_next: object lock.  snap_gen counts the encoders opened: a new one resets what the helper remembers of the last still it wrote. */
     gchar *snap_location;
+    gchar *out_colorimetry; /* output-colorimetry: what the coded samples are to mean (NULL or "": what the input's mean) */
     guint snap_interval;
     gint snap_quality, snap_reduce, snap_source;
     GstClockTime snap_next;   /* stream time of the next picture to arm (NONE: the next one) */
@@ -125,10 +126,11 @@ enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME
        PROP_OV_TEXT, PROP_OV_HALIGN, PROP_OV_VALIGN, PROP_OV_XPAD, PROP_OV_YPAD, PROP_OV_SCALE, PROP_OV_SHADED, PROP_VIDEO_DIRECTION,
        PROP_CROP_LEFT, PROP_CROP_RIGHT, PROP_CROP_TOP, PROP_CROP_BOTTOM, PROP_ADD_BORDERS, PROP_UPSCALE, PROP_BORDER_COLOR,
        PROP_IMG_LOCATION, PROP_IMG_X, PROP_IMG_Y, PROP_IMG_ALPHA,
-       PROP_SNAP_LOCATION, PROP_SNAP_INTERVAL, PROP_SNAP_QUALITY, PROP_SNAP_REDUCE, PROP_SNAP_SOURCE };
+       PROP_SNAP_LOCATION, PROP_SNAP_INTERVAL, PROP_SNAP_QUALITY, PROP_SNAP_REDUCE, PROP_SNAP_SOURCE,
+       PROP_OUTPUT_COLORIMETRY };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
-    GST_STATIC_CAPS("video/x-raw, format=(string){ NV12, I420, YUY2, UYVY, Y42B, Y444, YV12, NV21, BGRx, RGBx, xRGB, xBGR, BGRA, RGBA, ARGB, ABGR, BGR, RGB }, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]; "
+    GST_STATIC_CAPS("video/x-raw, format=(string){ NV12, I420, YUY2, UYVY, Y42B, Y444, YV12, NV21, BGRx, RGBx, xRGB, xBGR, BGRA, RGBA, ARGB, ABGR, BGR, RGB, P010_10LE, I420_10LE, v210, GRAY8 }, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]; "
                     "image/jpeg, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]"));
 static GstStaticPadTemplate src_tmpl = GST_STATIC_PAD_TEMPLATE("src", GST_PAD_SRC, GST_PAD_ALWAYS,
     GST_STATIC_CAPS("video/x-h264, stream-format=(string)byte-stream, alignment=(string)au, profile=(string){ constrained-baseline, high }, "
@@ -265,6 +267,7 @@ static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *
     case PROP_SNAP_QUALITY: s->snap_quality = g_value_get_int(val); break;
     case PROP_SNAP_REDUCE: { const gint r = g_value_get_int(val); if (r == 1 || r == 2 || r == 4 || r == 8) s->snap_reduce = r; else GST_WARNING_OBJECT(s, "snapshot-reduce %d: not 1, 2, 4 or 8; stays %d", r, s->snap_reduce); break; }
     case PROP_SNAP_SOURCE: s->snap_source = g_value_get_enum(val); break;
+    case PROP_OUTPUT_COLORIMETRY: g_free(s->out_colorimetry); s->out_colorimetry = g_value_dup_string(val); break; /* (read at the next set_format) */
     case PROP_IMG_X: s->img_x = g_value_get_int(val); image_forward(s, FALSE); break;
     case PROP_IMG_Y: s->img_y = g_value_get_int(val); image_forward(s, FALSE); break;
     case PROP_IMG_ALPHA: s->img_alpha = g_value_get_double(val); image_forward(s, FALSE); break;
@@ -323,6 +326,7 @@ static void get_property(GObject *obj, guint id, GValue *val, GParamSpec *ps) {
     case PROP_SNAP_QUALITY: g_value_set_int(val, s->snap_quality); break;
     case PROP_SNAP_REDUCE: g_value_set_int(val, s->snap_reduce); break;
     case PROP_SNAP_SOURCE: g_value_set_enum(val, s->snap_source); break;
+    case PROP_OUTPUT_COLORIMETRY: g_value_set_string(val, s->out_colorimetry ? s->out_colorimetry : ""); break;
     case PROP_IMG_X: g_value_set_int(val, s->img_x); break;
     case PROP_IMG_Y: g_value_set_int(val, s->img_y); break;
     case PROP_IMG_ALPHA: g_value_set_double(val, s->img_alpha); break;
@@ -514,6 +518,10 @@ static int rgb_or_planar_fmt(GstVideoFormat f) {
     case GST_VIDEO_FORMAT_xBGR: case GST_VIDEO_FORMAT_ABGR: return MI355ENC_FMT_XBGR;
     case GST_VIDEO_FORMAT_BGR: return MI355ENC_FMT_BGR;
     case GST_VIDEO_FORMAT_RGB: return MI355ENC_FMT_RGB;
+    case GST_VIDEO_FORMAT_P010_10LE: return MI355ENC_FMT_P010; /* 10-bit and grey */
+    case GST_VIDEO_FORMAT_I420_10LE: return MI355ENC_FMT_I420_10;
+    case GST_VIDEO_FORMAT_v210: return MI355ENC_FMT_V210;
+    case GST_VIDEO_FORMAT_GRAY8: return MI355ENC_FMT_GRAY8;
     default: return -1;
     }
 }
@@ -595,6 +603,18 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
         GST_ELEMENT_ERROR(s, CORE, NEGOTIATION, ("mi355h264enc: image/jpeg caps need width and height"), ("caps without a size"));
         return FALSE;
     }
+    /* output-colorimetry: the coded samples' meaning where it is not to be the input's */
+    GstVideoColorimetry out_col;
+    GST_OBJECT_LOCK(s);
+    gchar *out_str = s->out_colorimetry && *s->out_colorimetry ? g_strdup(s->out_colorimetry) : NULL;
+    GST_OBJECT_UNLOCK(s);
+    const gboolean convert = out_str != NULL;
+    if (out_str && !gst_video_colorimetry_from_string(&out_col, out_str)) {
+        GST_ELEMENT_ERROR(s, LIBRARY, SETTINGS, ("mi355h264enc: output-colorimetry=%s is not a colorimetry", out_str), ("gst_video_colorimetry_from_string failed"));
+        g_free(out_str);
+        return FALSE;
+    }
+    g_free(out_str);
     GST_OBJECT_LOCK(s);
     const int dir = effective_direction(s);
     const gboolean tr = direction_transposes(dir);
@@ -657,7 +677,13 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
             prim = trc = mat = (out_w > 1024 || out_h > 576) ? 1 : 6;
             full = 0;
         } else if (GST_VIDEO_INFO_IS_RGB(vi)) full = 0;
-        r = mi355enc_set_colorimetry(e, full, prim, trc, mat);
+        if (convert) { /* the SPS carries the output's codes; YUV input is converted to them on the device from what the caps say it is, RGB straight to them */
+            const int in_full = full, in_mat = mat;
+            colorimetry_codes(&out_col, &full, &prim, &trc, &mat);
+            if (mat != 1 && mat != 2 && mat != 5 && mat != 6 && mat != 9) r = MI355ENC_ERR_ARG; /* (the library would refuse the first picture) */
+            if (r == MI355ENC_OK && !GST_VIDEO_INFO_IS_RGB(vi)) r = mi355enc_set_input_colorimetry(e, in_full, in_mat); /* (refused: an input matrix outside 1, 5, 6, 9, 2) */
+        }
+        if (r == MI355ENC_OK) r = mi355enc_set_colorimetry(e, full, prim, trc, mat);
     }
     if (r == MI355ENC_OK && dir != 0) r = mi355enc_set_orientation(e, dir); /* (first: the input size is then checked against the pre-orientation target) */
     if (r == MI355ENC_OK && geom) r = mi355enc_set_input_geometry(e, &gm); /* (refused: a ratio above 8 either way, odd sizes) */
@@ -970,6 +996,7 @@ static void finalize(GObject *obj) {
     g_free(GST_MI355H264ENC(obj)->img_location);
     g_free(GST_MI355H264ENC(obj)->img_rgba);
     g_free(GST_MI355H264ENC(obj)->snap_location);
+    g_free(GST_MI355H264ENC(obj)->out_colorimetry);
     g_mutex_clear(&GST_MI355H264ENC(obj)->snap_mu); g_mutex_clear(&GST_MI355H264ENC(obj)->snap_enc_mu); g_cond_clear(&GST_MI355H264ENC(obj)->snap_cv);
     G_OBJECT_CLASS(gst_mi355h264enc_parent_class)->finalize(obj);
 }
@@ -1065,6 +1092,7 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
     g_object_class_install_property(g, PROP_SNAP_QUALITY, g_param_spec_int("snapshot-quality", "Still quality", "libjpeg's quality scale", 1, 100, 75, F));
     g_object_class_install_property(g, PROP_SNAP_REDUCE, g_param_spec_int("snapshot-reduce", "Still reduction", "1, 2, 4 or 8: the still is the picture's size divided by it (rounded up)", 1, 8, 4, F));
     g_object_class_install_property(g, PROP_SNAP_SOURCE, g_param_spec_enum("snapshot-source", "Still source", "source: the picture that is coded, with scaling, orientation, image and text in it; decoded: what a decoder shows", snapshot_source_type(), 0, F));
+    g_object_class_install_property(g, PROP_OUTPUT_COLORIMETRY, g_param_spec_string("output-colorimetry", "Output colorimetry", "what the coded samples are to mean, e.g. bt709 or bt601 (a GstVideoColorimetry string): the SPS says this, and YUV input is converted on the GPU from the range and matrix its caps give; empty: label the stream as the input, convert nothing", "", F));
     g_object_class_override_property(g, PROP_VIDEO_DIRECTION, "video-direction"); /* GstVideoDirection: identity, 90r, 180, 90l, horiz, vert, ul-lr, ur-ll, auto -- as on videoflip */
     g_object_class_install_property(g, PROP_STATS, g_param_spec_boolean("stats", "Print stats", "Print a JSON line with counters when the encoder closes", FALSE, F));
     gst_element_class_add_static_pad_template(e, &sink_tmpl);
@@ -1082,6 +1110,7 @@ static void gst_mi355h264enc_init(GstMi355H264Enc *s) {
     s->img_location = NULL; s->img_rgba = NULL; s->img_w = s->img_h = s->img_x = s->img_y = 0; s->img_alpha = 1.0;
     s->direction = s->tag_direction = s->open_direction = GST_VIDEO_ORIENTATION_IDENTITY;
     s->border_color = 0x108080;
+    s->out_colorimetry = NULL;
     s->snap_location = NULL; s->snap_interval = 1000; s->snap_quality = 75; s->snap_reduce = 4; s->snap_source = 0; s->snap_next = GST_CLOCK_TIME_NONE; s->snap_watch = 0;
     g_mutex_init(&s->snap_mu); g_mutex_init(&s->snap_enc_mu); g_cond_init(&s->snap_cv);
     s->snap_thread = NULL; s->snap_wake = 0; s->snap_stop = FALSE; s->snap_count = 0; s->snap_gen = 0;

@@ -158,10 +158,13 @@ void k_launch_intra_band(const frame_ctx_t *h_ctx, int mbh, uint2 *d_gran, unsig
 void k_launch_intra_rows(const frame_ctx_t *h_ctx, int mbh, uint2 *d_gran, unsigned *d_err, unsigned *d_row_done, hipStream_t s);
 int k_launch_csc(int fmt, const uint8_t *p0, const uint8_t *p1, const uint8_t *p2, int s0, int s1, int s2, uint8_t *dy, uint8_t *duv,
                  int vw, int vh, int W, int H, hipStream_t s);
-/* the formats csc_kernel does not take (k_csc.hip; the rule: DESIGN.md section 11): fmt MI355ENC_FMT_Y42B .. MI355ENC_FMT_RGB except YV12 (k_launch_csc with
+/* the formats csc_kernel does not take (k_csc.hip; the rule: DESIGN.md section 11): fmt MI355ENC_FMT_Y42B .. MI355ENC_FMT_GRAY8 except YV12 (k_launch_csc with
  * the chroma planes exchanged); coef: the ten words of mi355enc_csc_coefficients, RGB formats only.  -1: not one of them */
 int k_launch_csc2(int fmt, const uint8_t *p0, const uint8_t *p1, const uint8_t *p2, int s0, int s1, int s2, uint8_t *dy, uint8_t *duv,
                   int vw, int vh, int W, int H, const int *coef, hipStream_t s);
+/* the colour step (k_csc.hip; the rule: DESIGN.md section 20), in place on NV12 surfaces of W x H at stride W: the samples inside rect (x0, x1, y0, y1; even)
+ * go from one (range, matrix) to another with the nine words of mi355enc_yuv_coefficients; everything outside keeps its bytes.  -1: arguments outside that */
+int k_launch_yuv_convert(uint8_t *y, uint8_t *uv, int W, int H, const int rect[4], const int *coef, hipStream_t s);
 /* Downscaling of the input picture to the coded size (k_scale.hip; the rule: DESIGN.md section 10).  Tables built on the host
  * (enc_scale.cpp), five of them: 0 luma horizontal, 1 luma vertical, 2 chroma horizontal, 3 chroma vertical from 4:2:0 input, 4 chroma
  * vertical from 4:2:2 input.  Entry i of table t: first[t][i] (first source index, not clamped) and q[t][i * taps[t] + k]. */

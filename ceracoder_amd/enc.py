@@ -24,12 +24,13 @@ BAND_ROWS = 4  # MI355_BAND_ROWS: macroblock rows per band of the band deblocker
 ERR_ARG, ERR_STATE = -1, -6
 FMT_NV12, FMT_I420, FMT_YUY2, FMT_UYVY = range(4)
 FMT_Y42B, FMT_Y444, FMT_YV12, FMT_NV21, FMT_BGRX, FMT_RGBX, FMT_XRGB, FMT_XBGR, FMT_BGR, FMT_RGB = range(4, 14)  # converted by k_csc.hip
+FMT_P010, FMT_I420_10, FMT_V210, FMT_GRAY8 = range(14, 18)  # 10-bit and grey input
 SCALE_LUMA, SCALE_CHROMA_V, SCALE_CHROMA_H, SCALE_CHROMA_V422 = range(4)  # kinds of scale_table()
 IDEC = np.dtype([("modes4", "u1", (16,)), ("mode16", "u1"), ("cmode", "u1"), ("use_i4", "u1"), ("pad", "u1"), ("cost", "<u4"), ("cost_luma", "<u4"), ("rsv", "<u4")])
 IMV_DTYPE = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("sad", "<u2"), ("bits", "<u2")])
 SURF_ROWS, SURF_COLS = 35, 36
 DROP_MAX, DROP_SKIP = 12, 255
-STAGE_ME, STAGE_INTER, STAGE_INTRA, STAGE_DEBLOCK, STAGE_SUBPEL, STAGE_CSC_I420, STAGE_CSC_YUY2, STAGE_CSC_UYVY, STAGE_ME_SELECT, STAGE_PMB, STAGE_INTRA_P, STAGE_QUALITY, STAGE_JPEG, STAGE_ORIENT, STAGE_SCALE, STAGE_IMAGE, STAGE_SNAPSHOT = range(17)
+STAGE_ME, STAGE_INTER, STAGE_INTRA, STAGE_DEBLOCK, STAGE_SUBPEL, STAGE_CSC_I420, STAGE_CSC_YUY2, STAGE_CSC_UYVY, STAGE_ME_SELECT, STAGE_PMB, STAGE_INTRA_P, STAGE_QUALITY, STAGE_JPEG, STAGE_ORIENT, STAGE_SCALE, STAGE_IMAGE, STAGE_SNAPSHOT, STAGE_YUV_CONVERT = range(18)
 # mi355enc_set_orientation: GstVideoOrientationMethod's numbers
 ORIENT_IDENTITY, ORIENT_90R, ORIENT_180, ORIENT_90L, ORIENT_HORIZ, ORIENT_VERT, ORIENT_UL_LR, ORIENT_UR_LL = range(8)
 ORIENT_NAMES = ("identity", "90r", "180", "90l", "horiz", "vert", "ul-lr", "ur-ll")
@@ -44,6 +45,7 @@ EXPORTS = [
     "mi355enc_rc_pick", "mi355enc_rc_update", "mi355enc_host_cavlc_block", "mi355enc_debug_trip_wait", "mi355enc_debug_get_counters", "mi355enc_debug_set_counters", "mi355enc_host_alloc", "mi355enc_host_free",
     "mi355enc_set_input_size", "mi355enc_stage_scale", "mi355enc_scale_table",
     "mi355enc_set_colorimetry", "mi355enc_csc_coefficients", "mi355enc_host_write_headers_vui", "mi355enc_stage_csc_device",
+    "mi355enc_set_input_colorimetry", "mi355enc_yuv_coefficients", "mi355enc_stage_yuv_convert",
     "mi355enc_set_quality_metrics", "mi355enc_last_quality", "mi355enc_quality_totals", "mi355enc_stage_quality", "mi355enc_stage_quality_device",
     "mi355enc_overlay_default_style", "mi355enc_set_overlay_style", "mi355enc_set_overlay_text", "mi355enc_last_overlay", "mi355enc_overlay_glyph", "mi355enc_stage_overlay",
     "mi355enc_set_image", "mi355enc_set_image_place", "mi355enc_last_image", "mi355enc_stage_image", "mi355enc_debug_image_bytes", "mi355enc_image_pixel", "mi355enc_image_load_pam",
@@ -197,6 +199,9 @@ def load():
         L.mi355enc_csc_coefficients.argtypes = [C.c_int, C.c_int, vp]
         L.mi355enc_host_write_headers_vui.argtypes = [C.c_int] * 11 + [vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.mi355enc_stage_csc_device.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+        L.mi355enc_set_input_colorimetry.argtypes = [vp, C.c_int, C.c_int]
+        L.mi355enc_yuv_coefficients.argtypes = [C.c_int] * 4 + [vp]
+        L.mi355enc_stage_yuv_convert.argtypes = [vp, vp, vp]
         L.mi355enc_set_quality_metrics.argtypes = [vp, C.c_int]
         L.mi355enc_last_quality.argtypes = [vp, C.POINTER(Quality)]
         L.mi355enc_quality_totals.argtypes = [vp, C.POINTER(Quality)]
@@ -306,6 +311,15 @@ def host_write_headers(width, height, fps_num, fps_den=1, transform8x8=False, co
     if r:
         raise RuntimeError("mi355enc_host_write_headers: %d" % r)
     return bytes(out[: n.value])
+
+
+def yuv_coefficients(in_matrix, in_full, out_matrix, out_full):
+    """The library's integer YUV -> YUV table (host only): int32 (9,) = cyy, cyb, cyr, cbb, cbr, crb, crr in 2^-16 units, the input's and the output's luma offset."""
+    c = np.zeros(9, np.int32)
+    r = load().mi355enc_yuv_coefficients(int(in_matrix), int(in_full), int(out_matrix), int(out_full), c.ctypes.data_as(C.c_void_p))
+    if r:
+        raise EncoderError("mi355enc_yuv_coefficients(%d, %d, %d, %d): %d" % (in_matrix, in_full, out_matrix, out_full, r))
+    return c
 
 
 def csc_coefficients(matrix, full_range):
@@ -651,7 +665,7 @@ class Encoder:
     (bitrate in bits/s as written through `bps`, key-int-max -> gop)."""
 
     def __init__(self, width, height, fps=60, gop=60, bitrate_bps=6_000_000, device_id=0, fixed_qp=-1, me_range=16,
-                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False, input_size=None, colorimetry=None, orientation=None, geometry=None):
+                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False, input_size=None, colorimetry=None, orientation=None, geometry=None, input_colorimetry=None):
         self.L = load()
         cfg = Cfg()
         self.L.mi355enc_default_cfg(C.byref(cfg), width, height, fps, fps_den)
@@ -694,6 +708,8 @@ class Encoder:
             self._chk(self.L.mi355enc_set_intra_refresh(self.h, 1), "set_intra_refresh", close_on_fail=True)
         if colorimetry is not None:  # (full_range, primaries, transfer, matrix): the VUI of every SPS, and the matrix RGB input is converted with
             self._chk(self.L.mi355enc_set_colorimetry(self.h, *[int(v) for v in colorimetry]), "set_colorimetry", close_on_fail=True)
+        if input_colorimetry is not None:  # (full_range, matrix): what submitted YUV samples mean; converted on the device to `colorimetry` where the two differ
+            self._chk(self.L.mi355enc_set_input_colorimetry(self.h, *[int(v) for v in input_colorimetry]), "set_input_colorimetry", close_on_fail=True)
         self.input_size = (width, height)
         self.orientation, self._in_set = ORIENT_IDENTITY, False
         if orientation is not None:  # 0 .. 7 or a name of ORIENT_NAMES: the pictures submitted are turned / mirrored on the device; width x height is the oriented size
@@ -743,6 +759,17 @@ class Encoder:
         """H.264 Table E-3 / E-4 / E-5 code points for the VUI of every SPS from now on (before the first submit); RGB input is converted with them"""
         self._chk(self.L.mi355enc_set_colorimetry(self.h, int(full_range), int(primaries), int(transfer), int(matrix)), "set_colorimetry")
 
+    def set_input_colorimetry(self, full_range, matrix):
+        """what the submitted YUV samples mean (before the first submit): converted on the device to set_colorimetry's range and matrix where they differ"""
+        self._chk(self.L.mi355enc_set_input_colorimetry(self.h, int(full_range), int(matrix)), "set_input_colorimetry")
+
+    def stage_yuv_convert(self, y, uv):
+        """The colour step alone on host planes of the coded size, with the handle's geometry, orientation and colorimetries; returns the converted copies."""
+        y, uv = np.ascontiguousarray(y, np.uint8).copy(), np.ascontiguousarray(uv, np.uint8).copy()
+        assert y.shape == (self.mbh * 16, self.mbw * 16) and uv.shape == (self.mbh * 8, self.mbw * 16)
+        self._chk(self.L.mi355enc_stage_yuv_convert(self.h, _p(y), _p(uv)), "stage_yuv_convert")
+        return y, uv
+
     def encode(self, y, uv, pts=0, force_idr=False):
         y, uv = _rows(y), _rows(uv)
         n, key = C.c_size_t(0), C.c_int(0)
@@ -755,14 +782,16 @@ class Encoder:
         self._chk(self.L.mi355enc_submit(self.h, _p(y), y.strides[0], _p(uv), uv.strides[0], pts, int(force_idr)), "submit")
 
     def _planes(self, planes):
-        arrs = [np.ascontiguousarray(a, np.uint8) for a in planes]
+        arrs = [np.ascontiguousarray(a) for a in planes]  # uint8, or the 16-bit / 32-bit words of FMT_P010 / FMT_I420_10 / FMT_V210 as their bytes
+        arrs = [a if a.dtype == np.uint8 else a.view(np.uint8) if a.dtype.itemsize > 1 and a.dtype.kind == "u" else a.astype(np.uint8) for a in arrs]
         pp = (C.c_void_p * 3)(*([a.ctypes.data for a in arrs] + [None] * (3 - len(arrs))))
         ss = (C.c_int * 3)(*([a.strides[0] for a in arrs] + [0] * (3 - len(arrs))))
         return arrs, pp, ss
 
     def submit_fmt(self, fmt, planes, pts=0, force_idr=False):
         """fmt: FMT_I420 / FMT_YV12 / FMT_Y42B / FMT_Y444 (three planes), FMT_YUY2 / FMT_UYVY (one packed plane, 2 bytes per pixel), FMT_NV12 / FMT_NV21
-        (Y and interleaved chroma), FMT_BGRX .. FMT_XBGR (one plane, 4 bytes per pixel), FMT_BGR / FMT_RGB (3 bytes per pixel).  A contiguous plane is taken where
+        (Y and interleaved chroma), FMT_BGRX .. FMT_XBGR (one plane, 4 bytes per pixel), FMT_BGR / FMT_RGB (3 bytes per pixel), FMT_P010 (two planes of '<u2'), FMT_I420_10 (three of '<u2'), FMT_V210 (one plane of '<u4' words or of bytes), FMT_GRAY8
+        (one plane).  A contiguous plane is taken where
         it lies (so one inside a PinnedBuffer is transferred in place)."""
         arrs, pp, ss = self._planes(planes)
         self._chk(self.L.mi355enc_submit_fmt(self.h, fmt, pp, ss, pts, int(force_idr)), "submit_fmt")

@@ -219,12 +219,18 @@ enum { MI355ENC_FMT_NV12 = 0, MI355ENC_FMT_I420 = 1, MI355ENC_FMT_YUY2 = 2, MI35
  * of 0 .. 255 in four 4-byte orders (the byte X is ignored: BGRA, RGBA, ARGB, ABGR are submitted as these) and two 3-byte orders, plane 0 only, converted
  * to Y'CbCr with the matrix and range of mi355enc_set_colorimetry.  mi355enc_submit_device stays NV12. */
        MI355ENC_FMT_Y42B = 4, MI355ENC_FMT_Y444 = 5, MI355ENC_FMT_YV12 = 6, MI355ENC_FMT_NV21 = 7,
-       MI355ENC_FMT_BGRX = 8, MI355ENC_FMT_RGBX = 9, MI355ENC_FMT_XRGB = 10, MI355ENC_FMT_XBGR = 11, MI355ENC_FMT_BGR = 12, MI355ENC_FMT_RGB = 13 };
+       MI355ENC_FMT_BGRX = 8, MI355ENC_FMT_RGBX = 9, MI355ENC_FMT_XRGB = 10, MI355ENC_FMT_XBGR = 11, MI355ENC_FMT_BGR = 12, MI355ENC_FMT_RGB = 13,
+/* ... and 10-bit and grey input, brought to 8 bits on the way in -- y8 = min(255, (v10 + 2) >> 2), a 4:2:0 chroma sample likewise, a
+ * 4:2:2 one from the sum S of its two rows, min(255, (S + 4) >> 3).  P010 (GStreamer P010_10LE): planes Y and interleaved (Cb, Cr) of little-endian 16-bit
+ * words, rows of 2 w bytes, v10 = word >> 6.  I420_10 (I420_10LE): planes Y, U, V of 16-bit words, v10 = word & 1023.  V210 (v210): plane 0 only, six pixels
+ * in four little-endian 32-bit words of three 10-bit fields (bits 0-9, 10-19, 20-29): Cb0 Y0 Cr0 | Y1 Cb1 Y2 | Cr1 Y3 Cb2 | Y4 Cr2 Y5; a row is read up to
+ * ceil(w / 6) 16 bytes (GStreamer's stride ((w + 47) / 48) 128 holds that).  GRAY8: plane 0 only, every chroma byte becomes 128. */
+       MI355ENC_FMT_P010 = 14, MI355ENC_FMT_I420_10 = 15, MI355ENC_FMT_V210 = 16, MI355ENC_FMT_GRAY8 = 17 };
 /* What the samples mean: written into the VUI of every SPS the handle writes from now on (E.1.1 video_signal_type; each IDR picture, each refresh cycle's
  * start, recovery re-encodes), and -- for RGB input -- the matrix and range the device converts with.  full_range 0 / 1; primaries, transfer, matrix: code
  * points of H.264 Tables E-3 / E-4 / E-5, 0 .. 255 (2: unspecified); MI355ENC_ERR_ARG outside.  Valid only before the first submit (MI355ENC_ERR_STATE
  * after it).  A handle on which this was never called writes no video_signal_type (0, 2, 2, 2: the stream of earlier versions).  YUV input is only
- * labelled, never converted.  RGB input: matrix 1 (BT.709), 5 / 6 (BT.601) or 9 (BT.2020 non-constant) convert with that matrix; 2 converts with 1 when the
+ * labelled, not converted -- unless mi355enc_set_input_colorimetry says that it means something else.  RGB input: matrix 1 (BT.709), 5 / 6 (BT.601) or 9 (BT.2020 non-constant) convert with that matrix; 2 converts with 1 when the
  * coded picture is wider than 1024 or higher than 576, else with 6 (and the SPS still says 2: signal what you convert with); any other code makes the
  * submit of an RGB picture fail with MI355ENC_ERR_ARG.  full_range 0: Y' 16 .. 235, CbCr 16 .. 240; 1: 0 .. 255. */
 int mi355enc_set_colorimetry(mi355enc_t *h, int full_range, int primaries, int transfer, int matrix);
@@ -232,6 +238,23 @@ int mi355enc_set_colorimetry(mi355enc_t *h, int full_range, int primaries, int t
  * of 2^-16; coef[9] the luma offset (16 or 0).  Y' = clip((yr R + yg G + yb B + (off << 16) + 2^15) >> 16); Cb = clip((br S_R + bg S_G + bb S_B + (128 << 19)
  * + 2^18) >> 19) from the eight-weight sums S of the 2 x 2 site, Cr likewise.  matrix: 1, 5, 6 or 9, else MI355ENC_ERR_ARG. */
 int mi355enc_csc_coefficients(int matrix, int full_range, int32_t coef[10]);
+/* What the submitted YUV samples mean, where that differs from what the coded samples are to mean (what a caps filter behind
+ * `videoconvert` does).  mi355enc_set_colorimetry keeps its meaning: the coded samples, the SPS, and what RGB input, image layers, overlay and border colours
+ * are expressed in.  full_range 0 / 1; matrix 1, 5, 6, 9 or 2 (resolved by the coded size as for RGB input; the output's 2 likewise), else MI355ENC_ERR_ARG.
+ * Before the first submit only (MI355ENC_ERR_STATE after it), in either order with mi355enc_set_colorimetry.  When the resolved input (range, matrix) differs
+ * from the resolved output, every YUV picture -- every submit entry point, JPEG included -- is converted on the device, in place on the coded surfaces, behind
+ * decode / conversion / scale / orientation and in front of image layers and text; with a geometry the border keeps its colour.  Pointwise on NV12 (a luma
+ * sample uses the chroma pair of its own 2 x 2 block), 16-bit fixed point, clipped to 0 .. 255.  mi355enc_submit_device then never takes its in-place exit:
+ * the caller's planes are only read.  When the two are equal, or this was never called, nothing is added.  RGB input is never touched by it.  An output
+ * matrix outside 1, 5, 6, 9, 2 makes every YUV submit fail with MI355ENC_ERR_ARG once this has been called. */
+int mi355enc_set_input_colorimetry(mi355enc_t *h, int full_range, int matrix);
+/* The YUV -> YUV table in the device's integer arithmetic (host only): coef[0..2] cyy, cyb, cyr; [3..4] cbb, cbr; [5..6] crb, crr in units of 2^-16; [7] the
+ * input's luma offset oy (16 or 0), [8] the output's oy'.  Y' = clip((cyy (Y - oy) + cyb (Cb - 128) + cyr (Cr - 128) + (oy' << 16) + 2^15) >> 16);
+ * Cb' = clip((cbb (Cb - 128) + cbr (Cr - 128) + (128 << 16) + 2^15) >> 16), Cr' likewise with crb, crr.  Matrices 1, 5, 6 or 9, else MI355ENC_ERR_ARG. */
+int mi355enc_yuv_coefficients(int in_matrix, int in_full, int out_matrix, int out_full, int32_t coef[9]);
+/* the colour step alone (tests): host NV12 planes of the coded size (16*mbw x 16*mbh luma, then interleaved chroma), in and out, like mi355enc_stage_image,
+ * with the handle's geometry, orientation and colorimetries; MI355ENC_ERR_STATE when the handle has no conversion */
+int mi355enc_stage_yuv_convert(mi355enc_t *h, uint8_t *y, uint8_t *uv);
 /* like mi355enc_submit, from host memory in `fmt`; planes[]/strides[]: as many entries as the format has planes */
 int mi355enc_submit_fmt(mi355enc_t *h, int fmt, const uint8_t *const planes[3], const int strides[3], int64_t pts, int force_idr);
 /* conversion stage alone (tests): writes the coded-size NV12 surfaces (16*mbw x 16*mbh luma, then interleaved chroma) */
@@ -562,7 +585,8 @@ int mi355enc_stage_deblock(mi355enc_t *h, uint8_t *rec_y, uint8_t *rec_uv, const
  * 13 the orientation launch at the handle's size (the handle's method; 90r on a handle without one), on whatever slot 0's raw staging buffer holds,
  * 14 the scale / geometry launch for an NV12 picture of the handle's input size (MI355ENC_ERR_STATE without mi355enc_set_input_size / _geometry), likewise,
  * 15 the blend launch of image layer 0 at its current place into slot 0's source surfaces (MI355ENC_ERR_STATE without an image on layer 0),
- * 16 the still launch on slot 0's source surfaces, with the reduction and quality of the last mi355enc_request_snapshot (1 and 75 without one).
+ * 16 the still launch on slot 0's source surfaces, with the reduction and quality of the last mi355enc_request_snapshot (1 and 75 without one),
+ * 17 the colour step on slot 0's source surfaces (MI355ENC_ERR_STATE when the handle has no conversion).
  * Uses whatever the handle's surfaces currently hold.  Returns average ms per launch. */
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms);
 
