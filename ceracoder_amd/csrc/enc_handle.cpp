@@ -153,6 +153,14 @@ int mi355enc_open(const mi355enc_cfg_t *cfg, mi355enc_t **out) {
     HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     h->fip_rows = fip_on(h->nmb);
     h->pgate = pgate_on(h->nmb);
+    {   // Kernels that wait on the device for another kernel hold their compute units while they wait.  A band-deblocking workgroup takes a compute unit to itself, so a
+        // launch with as many of them as the chip has compute units -- 128 bands: a picture of 8192 lines; 65 bands and 257 intra rows in one launch: 4112 lines --
+        // leaves the kernel it waits for nowhere to go, and every wait runs into its bound (error word 11 on the first IDR picture of a 16 x 8192 stream).  Such
+        // pictures are coded in stream order; a quarter of the chip stays free otherwise.  The bound is the MI355X's, not the device's own count: on a partition of
+        // the chip the launches of every size coded so far keep the schedule they have always had there.
+        const int wgs_max = 256 - 256 / 4;
+        for (int idr = 0; idr < 2; idr++) h->wait_room[idr] = k_deblock_launch_wgs(h->mbw, h->mbh, idr, !idr && h->fip_rows) <= wgs_max;
+    }
     for (int i = 0; i < NSET; i++) HIPCHK(hipMalloc((void **)&h->d_ctx2[i], sizeof(frame_ctx_t)));
     h->d_ctx = h->d_ctx2[0];
     if (h->cfg.single_stream) { // one hardware queue per encoder: every stage in order on the main stream

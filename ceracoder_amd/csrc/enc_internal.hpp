@@ -122,6 +122,7 @@ struct mi355enc {
     int16_t *d_levels, *d_levels_set[NSET];
     hipStream_t cstream;                 // hand-over stream (scan + pack into pinned host memory)
     bool pgate;                          // the fused P stage runs beside the previous picture's deblocking launch, gated per band (pgate_on(), latched at open())
+    bool wait_room[2];                   // [0] P, [1] IDR pictures: the picture's deblocking launch leaves a quarter of an MI355X's 256 compute units free, so its workgroups may wait on the device for another kernel (latched at open())
     bool fip_rows;                       // the intra macroblock rows of a P picture ride in its deblocking launch (fip_on(), latched at open())
     uint64_t n_submitted;
     uint64_t sc_sum, sc_force_at; int sc_cnt, sc_prev_skip; // scene-cut recovery: summed cost / number of the P pictures since the last IDR; picture to force

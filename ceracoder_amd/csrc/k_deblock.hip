@@ -989,6 +989,12 @@ void k_launch_deblock_diag(const frame_ctx_t *d_ctx, int mbw, int mbh, int diag,
 #define DB_ROWS MI355_BAND_ROWS /* rows per band: three waves per row, one row per SIMD (5 rows = 15 waves is equal on P pictures, a third slower on I pictures) */
 #endif
 int k_deblock_bands16(int mbh) { return (mbh + DB_ROWS - 1) / DB_ROWS; }
+// The workgroups of one launch over a whole picture: two per band (luma, chroma), four where a P picture's bands are walked in two parts, and one per macroblock row
+// where the intra rows ride in it.  Each is twelve waves at more than 100 VGPRs -- a compute unit holds one, and nothing of the size of an intra row's workgroup beside
+// it -- so a launch whose workgroups wait for another kernel must leave that kernel compute units to be placed on (enc_handle.cpp: wait_room).
+int k_deblock_launch_wgs(int mbw, int mbh, int all_intra, int fused_ip) {
+    return (!all_intra && mbw >= DB_CUT_MIN_MBW ? 4 : 2) * k_deblock_bands16(mbh) + (fused_ip ? mbh : 0);
+}
 size_t k_deblock_gran_bytes(int mbw, int mbh) { return (size_t)k_deblock_bands16(mbh) * mbw * 24 * sizeof(uint2); } // per band boundary and macroblock: 16 luma + 8 chroma granules
 // The band kernel may be launched in several pieces (bands [band0, band1)): a band only ever waits for the band above it.
 // d_ip_progress (may be null): intra_p_kernel of the same picture is still running; the movers follow its per-row progress words.

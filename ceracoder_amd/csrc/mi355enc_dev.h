@@ -129,6 +129,7 @@ void k_launch_intra_analyse(const frame_ctx_t *h_ctx, int mbw, int mbh, int gate
 void k_launch_intra_diag(const frame_ctx_t *d_ctx, int mbw, int mbh, int diag, hipStream_t s);
 void k_launch_deblock_diag(const frame_ctx_t *d_ctx, int mbw, int mbh, int diag, hipStream_t s);
 int k_deblock_bands16(int mbh);
+int k_deblock_launch_wgs(int mbw, int mbh, int all_intra, int fused_ip); // workgroups of a launch over the whole picture, each a compute unit's worth
  // flags: per-band "has work" words of this picture's set
 // d_ip_progress (may be null): intra_p_kernel of the same picture is still running; the band kernel follows its per-row progress words
 // d_iband_done (may be null; all-intra pictures): the intra band kernel of the same picture is still running; a band waits for its flags

@@ -92,7 +92,9 @@ typedef struct {
                                  beside the deblocking of the picture before it and its workgroups wait ON the device for the
                                  bands they read -- a chip full of waiting workgroups.  With another process on the same GPU
                                  such launches can keep each other's kernels off the chip (seen: one of two processes ran into
-                                 the bound of its wait), so it is opt-in.  Same stream either way */
+                                 the bound of its wait), so it is opt-in.  Same stream either way.  No effect on pictures whose
+                                 deblocking launch would by itself take more than three quarters of the compute units (from about
+                                 4000 lines up): there the waiting workgroups would keep the kernel they wait for off the chip */
     int aq_mode;              /* 0 (default): one QP per picture.  1: adaptive quantisation -- a QP offset of -4 .. +4 per macroblock from the luma
                                  variance of its source samples (flat areas finer, busy texture coarser), coded with mb_qp_delta.  The QP_Y of
                                  macroblocks that send no mb_qp_delta is that of the macroblock before them (7.4.5), which the deblocker reads: a

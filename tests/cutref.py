@@ -115,10 +115,16 @@ def window(mbw):
     return mid - w, mid + w, mid - w // 8
 
 
+def _band_edge_bs(records, mbw, mbh, band):
+    """vertical_mb_edge_bs of the band's rows alone (a vertical edge's bS takes nothing from another row): what a picture of 128 bands can afford per band"""
+    rows = band_rows(band, mbh)
+    return vertical_mb_edge_bs(np.asarray(records).reshape(mbh, mbw)[rows.start:rows.stop], mbw, len(rows))
+
+
 def busy_columns(records, mbw, mbh, band):
     """Per plane, (2, mbw) bool: the left macroblock edge of the column has bS > 0 in some row of the band -- luma by its 16 lines' segments,
     chroma by its 8 lines (chroma line k lies in luma segment k // 2)."""
-    bs = vertical_mb_edge_bs(records, mbw, mbh)[list(band_rows(band, mbh))]
+    bs = _band_edge_bs(records, mbw, mbh, band)
     luma = (bs[:, :, [k // 4 for k in range(16)]] > 0).any(axis=(0, 2))
     chroma = (bs[:, :, [k // 2 for k in range(8)]] > 0).any(axis=(0, 2))
     return np.stack([luma, chroma])
@@ -170,7 +176,7 @@ def cut_is_safe(records, mbw, mbh, band, col):
         return True
     if not 0 <= col < mbw:
         return False
-    return not (vertical_mb_edge_bs(records, mbw, mbh)[list(band_rows(band, mbh)), col] > 0).any()
+    return not (_band_edge_bs(records, mbw, mbh, band)[:, col] > 0).any()
 
 
 def never_steps_left(cuts, mbw, mbh, slice_rows=0, idc=0):

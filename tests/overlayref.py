@@ -65,10 +65,13 @@ def masks(text, w, h, **style):
     B[by:by + bh, bx:bx + bw] = True
     # outline: within s samples of a text sample in the 8-neighbourhood sense (Chebyshev distance <= s), not text itself.  T keeps a border of
     # s samples inside B, so the shifts below never wrap a set sample around
-    near = np.zeros_like(T)
+    # (the square neighbourhood is taken one axis after the other: the union over |dx| <= s of the union over |dy| <= s is the union over both)
+    rows = np.zeros_like(T)
     for dy in range(-s, s + 1):
-        for dx in range(-s, s + 1):
-            near |= np.roll(np.roll(T, dy, 0), dx, 1)
+        rows |= np.roll(T, dy, 0)
+    near = np.zeros_like(T)
+    for dx in range(-s, s + 1):
+        near |= np.roll(rows, dx, 1)
     O = near & ~T
     assert not (O & ~B).any()
     return T[:h, :w], O[:h, :w], B[:h, :w]

@@ -10,8 +10,9 @@ from tests.util import db_picture, first_diff, marked_records, random_records
 
 pytestmark = pytest.mark.gpu
 
-# (mbw, mbh): every width of the issue with every mbh % 4; 59 is below DB_CUT_MIN_MBW (bands walked whole)
-SIZES = [(59, 9), (60, 12), (64, 13), (80, 14), (120, 15), (124, 11), (240, 21), (256, 10)]
+# (mbw, mbh): every width of the issue with every mbh % 4; 59 is below DB_CUT_MIN_MBW (bands walked whole); the widest rows the encoder opens for (512, 511) and the
+# first past 256; 512 rows of the shortest row that is cut: 128 bands, all cut
+SIZES = [(59, 9), (60, 12), (64, 13), (80, 14), (120, 15), (124, 11), (240, 21), (256, 10), (512, 5), (511, 8), (257, 4), (60, 512)]
 SETTINGS = [(0, 0), (2, 4), (2, 8), (2, 20)]  # (disable_deblocking_filter_idc, slice rows)
 
 

@@ -476,7 +476,8 @@ def test_adaptive_quantisation_equals_oracle(E, oracle, w, h, n, depth):
 
 @pytest.mark.parametrize("w,h", [(16, 16), (32, 16), (16, 48), (18, 18), (4096, 32)])
 def test_degenerate_geometries(E, oracle, w, h):
-    """Single macroblock, single row/column, non-multiple-of-16, and the widest row the caps allow."""
+    """Single macroblock, single row/column, non-multiple-of-16, and a row of 256 macroblocks (the widest and tallest the caps allow, 8192, are in
+    tests/test_size_range_gpu.py)."""
     e = E.Encoder(w, h, gop=3, fixed_qp=27, exclusive=True)
     oe = oracle.Encoder(w, h, gop=3, threads=4)
     dec = oracle.Decoder()

@@ -1,4 +1,6 @@
 """Shared helpers for the parity tests."""
+import functools
+
 import numpy as np
 
 from ceracoder_amd import synth
@@ -59,8 +61,9 @@ def half_static_clip(w, h, n, static_lines):
 
 # ---- the band deblocker's cut (tests/cutref.py): crafted records, pictures that filter visibly, content that steers the cut
 
+@functools.lru_cache(maxsize=8)
 def db_picture(mbw, mbh, seed):
-    """A pre-filter picture on which the deblocking filter visibly works: a smooth field with steps of 5..30 levels between 4x4 blocks
+    """(Kept per (size, seed), read-only: the crafted-record tests ask for the same few pictures dozens of times, and at 512 rows one costs a second.)  A pre-filter picture on which the deblocking filter visibly works: a smooth field with steps of 5..30 levels between 4x4 blocks
     (luma) and 4x4 blocks of either chroma component -- small enough to stay under alpha at most QPs (uniform noise does not: |p0 - q0|
     >= alpha turns most filters off)."""
     g = np.random.Generator(np.random.PCG64(seed))
@@ -75,6 +78,8 @@ def db_picture(mbw, mbh, seed):
     uv = np.empty((H // 2, W), np.uint8)
     uv[:, 0::2] = field(H // 2, W // 2, 23.0, 4)
     uv[:, 1::2] = field(H // 2, W // 2, 29.0, 4)
+    y.setflags(write=False)
+    uv.setflags(write=False)
     return y, uv
 
 
