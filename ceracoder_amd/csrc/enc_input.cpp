@@ -2,9 +2,10 @@
 //
 // Every submit entry point is four steps ("The input path"):
 //   its own argument checks
-//   ingest_begin   the pipeline-full check, the slot, the latches (text, image layers)
+//   ingest_begin   the pipeline-full check (with frame-rate conversion: the rule's step, which says how many pictures the submit yields), the slot, the latches (text, image layers)
 //   fill           its own way of filling the input target: copy | convert | decode | scale, ending in input_finish (the orientation launch)
-//   ingest_end     colour step -> image layers -> text -> upload event -> enqueue_picture (enc_schedule.cpp) on the slot's own surfaces
+//   ingest_end     colour step -> [frame-rate conversion: mix / keep / repeat, per output picture] -> image layers -> text -> upload event -> enqueue_picture
+//                  (enc_schedule.cpp) on the slot's own surfaces
 // The one exception is the in-place exit of mi355enc_submit_device.  A new step on the way in goes into ingest_end (one that works on the coded surfaces) or
 // in front of input_finish (one that works on the pre-orientation picture), never into a submit.
 // Also here: what the fills share -- a format's planes, the raw staging upload, the two-launch form, the staging helper threads -- and mi355enc_stage_csc.
@@ -18,33 +19,74 @@ static int upload_done(mi355enc_t *h, slot_t *s) {
 }
 
 // ---- the sequence around every fill
-// the slot the next picture goes into; ERR_STATE with the pipeline full
-static int ingest_slot(mi355enc_t *h, slot_t **s) {
-    if (h->pending > h->cfg.pipeline_depth) return MI355ENC_ERR_STATE;
+// the slot the next picture goes into; ERR_STATE with the pipeline full.  With frame-rate conversion the rule is asked first: a submit that
+// yields n pictures needs n free slots, its input goes into the last of them (the repeats / earlier mixes are enqueued in front of it, from the queue's head
+// on), and one that yields none and transfers nothing answers INGEST_DROP
+static int ingest_slot(mi355enc_t *h, slot_t **s, int64_t pts, int force_idr) {
+    int ahead = 0;
+    if (h->rate.mode) { int r = rate_begin(h, pts, force_idr, &ahead); if (r) return r; }
+    else if (h->pending > h->cfg.pipeline_depth) return MI355ENC_ERR_STATE;
     HIPCHK(hipSetDevice(h->cfg.device_id));
-    *s = &h->slot[h->head];
+    *s = &h->slot[(h->head + ahead) % NSLOT];
     (*s)->yuv_step = h->yuv_on;
     return MI355ENC_OK;
 }
-// what the control thread set last becomes the picture's
+// what the control thread set last becomes the picture's -- every picture's that the submit yields: layers and text are drawn afresh into each
 static int ingest_latch(mi355enc_t *h, slot_t *s) {
+    for (int i = 0; h->rate.mode && i < h->rate_n - 1; i++) {
+        slot_t *t = &h->slot[(h->head + i) % NSLOT];
+        overlay_latch(h, t);
+        int r = image_latch(h, t);
+        if (r) return r;
+    }
     overlay_latch(h, s);
     return image_latch(h, s);
 }
 // (apart only for mi355enc_submit_jpeg, which decodes into the slot between the two: after the state check -- with the pipeline full the slot's buffers
 // belong to a picture in flight -- and before anything is latched)
-static int ingest_begin(mi355enc_t *h, slot_t **s) {
-    int r = ingest_slot(h, s);
+static int ingest_begin(mi355enc_t *h, slot_t **s, int64_t pts, int force_idr) {
+    int r = ingest_slot(h, s, pts, force_idr);
     return r ? r : ingest_latch(h, *s);
 }
-// the slot's surfaces hold the oriented picture: everything that is drawn into it, in this order, then the schedule
-static int ingest_end(mi355enc_t *h, slot_t *s, hipStream_t up, int64_t pts, int force_idr) {
-    int r = s->yuv_step ? yuv_draw(h, s, up) : MI355ENC_OK; // the colour step first: layers and text are drawn in the output's colours
-    if (!r) r = image_draw(h, s, up);
+// everything that is drawn into a picture on top of its samples, in this order, then the schedule
+static int draw_and_enqueue(mi355enc_t *h, slot_t *s, hipStream_t up, int64_t pts, int force_idr) {
+    int r = image_draw(h, s, up);
     if (!r) r = overlay_draw(h, s, up);
     if (!r) r = upload_done(h, s);
     return r ? r : enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
 }
+// frame-rate conversion: the slot's surfaces hold the input after the colour step; the pictures the plan's step yields, in tick order (s is the last one's slot)
+static int ingest_end_rate(mi355enc_t *h, slot_t *s, hipStream_t up, int force_idr) {
+    const int n = h->rate_n, idr = force_idr || h->rate_idr_owed;
+    if (n == 0) { // blend: the input is the next pair's `a` and nothing is coded.  The slot (and a pinned staging buffer or the caller's pinned picture behind it) is free
+        int r = rate_keep(h, s, up); // again when this returns, so the transfer is waited for here
+        if (r) return r;
+        HIPCHK(hipStreamSynchronize(up));
+        rate_commit(h, force_idr);
+        return MI355ENC_OK;
+    }
+    for (int i = 0; i < n - 1; i++) { // the ticks in front of the input's own: hold -- the previous output picture again; blend -- mixes of the same pair, b read where it lies
+        slot_t *t = &h->slot[h->head];
+        int r = h->rate.mode == 1 ? rate_repeat(h, t, up) : rate_mix(h, s, t, h->rate_w[i], false, up);
+        if (!r) r = draw_and_enqueue(h, t, up, h->rate_pts[i], i == 0 ? idr : 0);
+        if (r) return r;
+    }
+    int r = h->rate.mode == 1 ? rate_keep(h, s, up) : rate_mix(h, s, s, h->rate_w[n - 1], true, up); // (hold: kept before layers and text, and only with max_fill > 0)
+    if (!r) r = draw_and_enqueue(h, s, up, h->rate_pts[n - 1], n == 1 ? idr : 0);
+    if (!r) rate_commit(h, force_idr);
+    return r;
+}
+// the slot's surfaces hold the oriented picture: everything that is drawn into it, in this order, then the schedule
+static int ingest_end(mi355enc_t *h, slot_t *s, hipStream_t up, int64_t pts, int force_idr) {
+    int r = s->yuv_step ? yuv_draw(h, s, up) : MI355ENC_OK; // the colour step first: layers and text are drawn in the output's colours
+    if (r) return r;
+    if (h->rate.mode) return ingest_end_rate(h, s, up, force_idr); // (the mix sits here: between the colour step and the layers)
+    r = draw_and_enqueue(h, s, up, pts, force_idr);
+    if (!r) h->last_count = 1;
+    return r;
+}
+// a submit's answer to ingest_begin's: a dropped input is a successful submit
+static inline int begin_answer(int r) { return r == INGEST_DROP ? MI355ENC_OK : r; }
 
 // ---- a format's planes
 int fmt_planes(int fmt, int w, int h, fmt_plane_t pl[3]) {
@@ -193,7 +235,7 @@ int mi355enc_stage_csc(mi355enc_t *h, int fmt, const uint8_t *const planes[3], c
 int mi355enc_submit(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t *uv, int uv_stride, int64_t pts, int force_idr) {
     if (!h || !y || !uv || y_stride < h->in_w || uv_stride < h->in_w || h->yuv_bad) return MI355ENC_ERR_ARG; // (yuv_bad: YUV samples that cannot be converted to the output's matrix)
     slot_t *s;
-    { int r = ingest_begin(h, &s); if (r) return r; }
+    { int r = ingest_begin(h, &s, pts, force_idr); if (r) return begin_answer(r); }
     const int w = h->in_w, ht = h->in_h;
     hipStream_t up = upload_stream(h);
     // where the planes go: the staging surfaces at the coded stride, or -- to be scaled -- the raw staging buffer at the input's
@@ -259,9 +301,10 @@ int mi355enc_submit_fmt(mi355enc_t *h, int fmt, const uint8_t *const planes[3], 
     if (fmt == MI355ENC_FMT_NV12) return mi355enc_submit(h, planes[0], strides[0], planes[1], strides[1], pts, force_idr);
     if (!fmt_is_rgb(fmt) && h->yuv_bad) return MI355ENC_ERR_ARG;
     slot_t *s;
-    int r = ingest_begin(h, &s);
-    if (!r && fmt_is_rgb(fmt)) s->yuv_step = false; // (RGB is converted straight to the output's matrix and range)
-    if (!r) r = upload_and_convert(h, s, fmt, planes, strides, upload_stream(h));
+    int r = ingest_begin(h, &s, pts, force_idr);
+    if (r) return begin_answer(r);
+    if (fmt_is_rgb(fmt)) s->yuv_step = false; // (RGB is converted straight to the output's matrix and range)
+    r = upload_and_convert(h, s, fmt, planes, strides, upload_stream(h));
     return r ? r : ingest_end(h, s, upload_stream(h), pts, force_idr);
 }
 
@@ -270,8 +313,8 @@ int mi355enc_submit_fmt(mi355enc_t *h, int fmt, const uint8_t *const planes[3], 
 int mi355enc_submit_jpeg(mi355enc_t *h, const uint8_t *data, size_t len, int64_t pts, int force_idr) {
     if (!h || !data || h->yuv_bad) return MI355ENC_ERR_ARG;
     slot_t *s;
-    int r = ingest_slot(h, &s);
-    if (r) return r;
+    int r = ingest_slot(h, &s, pts, force_idr);
+    if (r) return begin_answer(r); // (a dropped picture is not entropy-decoded)
     mi355enc_jpeg_info_t info;
     r = jpeg_decode_host(h, s, data, len, &info);
     if (!r) r = ingest_latch(h, s);
@@ -284,8 +327,8 @@ int mi355enc_submit_jpeg(mi355enc_t *h, const uint8_t *data, size_t len, int64_t
 int mi355enc_submit_device(mi355enc_t *h, const void *d_y, int y_stride, const void *d_uv, int uv_stride, int64_t pts, int force_idr) {
     if (!h || !d_y || !d_uv || y_stride < h->in_w || uv_stride < h->in_w || h->yuv_bad) return MI355ENC_ERR_ARG;
     slot_t *s;
-    int r = ingest_begin(h, &s);
-    if (r) return r;
+    int r = ingest_begin(h, &s, pts, force_idr);
+    if (r) return begin_answer(r);
     hipStream_t up = upload_stream(h);
     if (h->scaling) { // scaled from where the planes lie into the slot's staging surfaces
         in_target_t t;
@@ -300,8 +343,8 @@ int mi355enc_submit_device(mi355enc_t *h, const void *d_y, int y_stride, const v
         r = input_finish(h, s, up, (const uint8_t *)d_y, y_stride, (const uint8_t *)d_uv, uv_stride);
     } else {
         const int w = h->cfg.width, ht = h->cfg.height;
-        // in place -- unless the samples are to be converted, a text drawn or an image blended in: that goes into the encoder's own surfaces, never into the caller's planes
-        const bool direct = !s->yuv_step && !s->ov_len && !image_active(s) && w == h->W && y_stride == uv_stride && (y_stride & 15) == 0 && (((uintptr_t)d_y | (uintptr_t)d_uv) & 15) == 0;
+        // in place -- unless the frame rate is converted (the picture may be kept, repeated or mixed), the samples are to be converted, a text drawn or an image blended in: that goes into the encoder's own surfaces, never into the caller's planes
+        const bool direct = !h->rate.mode && !s->yuv_step && !s->ov_len && !image_active(s) && w == h->W && y_stride == uv_stride && (y_stride & 15) == 0 && (((uintptr_t)d_y | (uintptr_t)d_uv) & 15) == 0;
         if (direct) return enqueue_picture(h, s, (const uint8_t *)d_y, (const uint8_t *)d_uv, y_stride, pts, force_idr);
         HIPCHK(hipMemcpy2DAsync(s->d_src_y, h->W, d_y, y_stride, w, ht, hipMemcpyDeviceToDevice, up));
         HIPCHK(hipMemcpy2DAsync(s->d_src_uv, h->W, d_uv, uv_stride, w, ht / 2, hipMemcpyDeviceToDevice, up));

@@ -9,6 +9,7 @@
 //   enc_jpeg.cpp      MJPEG input: coefficient buffers, host decode, transfer + launch, its stage entry points
 //   enc_snapshot.cpp  JPEG stills: request / take, the blocks the levels land in, the launch, its stage entry points
 //   enc_csc.cpp       colorimetry: the setters, the RGB matrix and the YUV -> YUV table, the colour step's launch, their stage entry points
+//   enc_rate.cpp      frame-rate conversion: setter, the plan's step and commit per submit, keep buffer, mix / keep / repeat launches, its stage entry point
 //   enc_stages.cpp    single-stage entry points (parity tests, probes) and the host-only stages
 #ifndef MI355_ENC_INTERNAL_HPP
 #define MI355_ENC_INTERNAL_HPP
@@ -210,6 +211,18 @@ struct mi355enc {
     // output matrix is not one the step can convert to -- a YUV submit is refused
     bool in_col_set, yuv_on, yuv_bad;
     int in_col_full, in_col_mat, yuv_coef[9];
+    // frame-rate conversion (mi355enc_set_rate_conversion).  rate.mode 0: off, and nothing below is used but last_count.  rate.max_fill is
+    // clamped to pipeline_depth.  rate_plan: the rule's state; ingest_begin steps a copy of it (rate_next, with what the step yields: rate_n pictures, their pts
+    // and weights) and ingest_end commits it once the pictures are enqueued -- a submit that fails in between has not advanced the plan.  d_keep: one NV12
+    // picture of the coded size (luma, then chroma at ysz): blend -- the previous input after the colour step; hold with max_fill > 0 -- the previous output
+    // picture before layers and text.  rate_idr_owed: the force_idr of submits that yielded no picture.  last_count: pictures the last successful submit enqueued.
+    mi355enc_rate_t rate = {};
+    mi355enc_rate_plan_t rate_plan = {}, rate_next = {};
+    int rate_n = 0, rate_resync = 0, rate_w[MI355ENC_RATE_MAX_OUT] = {};
+    int64_t rate_pts[MI355ENC_RATE_MAX_OUT] = {};
+    int rate_idr_owed = 0, last_count = 0;
+    uint8_t *d_keep = nullptr;
+    mi355enc_rate_stats_t rate_st = {};
     uint32_t n_recoveries, last_error_word;
     // quality metrics (mi355enc_set_quality_metrics; everything null / 0 while they are off and no stage call has asked for them):
     // per slot, and one more for the single-stage entry points, a block of QUALITY_WORDS accumulator words on the device and of result words in pinned
@@ -362,4 +375,16 @@ static inline bool fmt_is_rgb(int fmt) { return fmt >= MI355ENC_FMT_BGRX && fmt 
 // the colour step on the slot's coded surfaces, behind everything enqueued on st so far: the picture part (with a geometry: the oriented destination rectangle) is
 // converted in place, the border keeps its bytes
 int yuv_draw(mi355enc_t *h, slot_t *s, hipStream_t st);
+// enc_rate.cpp (frame-rate conversion; every one of them is called with conversion on only)
+#pragma GCC visibility push(hidden)
+#define INGEST_DROP 1 /* ingest_begin's answer for a submit that yields no picture and needs no transfer (hold mode): the submit returns MI355ENC_OK at once */
+// ingest_begin: steps a copy of the plan for an input at pts.  ERR_STATE with fewer free slots than the step needs (nothing has changed); INGEST_DROP: the input
+// is dropped and booked; otherwise *ahead = pictures in front of the input's own (their slots follow the queue's head, the input goes into the slot behind them)
+int rate_begin(mi355enc_t *h, int64_t pts, int force_idr, int *ahead);
+int rate_keep(mi355enc_t *h, slot_t *s, hipStream_t st);                       // the slot's surfaces -> the keep buffer (nothing without one)
+int rate_repeat(mi355enc_t *h, slot_t *t, hipStream_t st);                     // the keep buffer -> the slot's surfaces
+int rate_mix(mi355enc_t *h, slot_t *b, slot_t *out, int w256, bool keep, hipStream_t st); // keep buffer x slot b -> slot out; keep: b replaces the keep buffer (out == b)
+void rate_commit(mi355enc_t *h, int force_idr);                                // ingest_end: the step's pictures are enqueued (or it yields none): plan and statistics advance
+void rate_free(mi355enc_t *h);
+#pragma GCC visibility pop
 #endif

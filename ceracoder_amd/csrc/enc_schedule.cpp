@@ -539,7 +539,7 @@ int mi355enc_collect(mi355enc_t *h, uint8_t *out, size_t out_cap, size_t *out_le
 int mi355enc_encode(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t *uv, int uv_stride, int64_t pts, int force_idr,
                     uint8_t *out, size_t out_cap, size_t *out_len, int *is_keyframe) {
     if (!h) return MI355ENC_ERR_ARG;
-    if (h->pending) return MI355ENC_ERR_STATE;
+    if (h->pending || h->rate.mode) return MI355ENC_ERR_STATE; // (frame-rate conversion: a submit yields any number of pictures, this call returns one)
     int r = mi355enc_submit(h, y, y_stride, uv, uv_stride, pts, force_idr);
     if (r) return r;
     return mi355enc_collect(h, out, out_cap, out_len, is_keyframe, nullptr, nullptr);

@@ -237,8 +237,9 @@ int mi355enc_debug_set_counters(mi355enc_t *h, const mi355enc_counters_t *in) {
     return MI355ENC_OK;
 }
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
-    if (!h || !avg_ms || iters < 1 || stage < 0 || stage > 17) return MI355ENC_ERR_ARG;
+    if (!h || !avg_ms || iters < 1 || stage < 0 || stage > 18) return MI355ENC_ERR_ARG;
     if (stage == 17 && !h->yuv_on) return MI355ENC_ERR_STATE; // (the handle has no conversion)
+    if (stage == 18 && !h->d_keep) return MI355ENC_ERR_STATE; // (frame-rate conversion off, or hold mode without a keep buffer: there is no mix)
     if (stage == 14 && !h->d_scale_tab) return MI355ENC_ERR_STATE; // (mi355enc_set_input_size or mi355enc_set_input_geometry first)
     if (h->pending) return MI355ENC_ERR_STATE;
     HIPCHK(hipSetDevice(h->cfg.device_id));
@@ -293,6 +294,7 @@ int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
             else if (stage == 15) k_launch_image_blend(&img_a, h->stream);
             else if (stage == 16) { int r = snapshot_time_launch(h, s); if (r) return r; }
             else if (stage == 17) { int r = yuv_draw(h, s, h->stream); if (r) return r; } // the colour step, in place on slot 0's surfaces (whatever they hold)
+            else if (stage == 18) { int r = rate_mix(h, s, s, 128, true, h->stream); if (r) return r; } // the mix of the keep buffer and slot 0's surfaces, in place as the encoder runs it
             else if (stage == 10) k_launch_intra_p(h->slot[0].h_ctx, h->mbw, h->mbh, h->d_ip_progress, h->d_ip_strips, err_word(h), h->stream);
             else if (stage >= 5) {
                 const int w = h->cfg.width, ht = h->cfg.height, r0 = stage == 5 ? (w + 15) & ~15 : (2 * w + 15) & ~15, r1 = (w / 2 + 15) & ~15;

@@ -102,6 +102,13 @@ typedef struct {
      * closes or opens it (s->enc and snap_gen change under it, taken in front of the object lock).  snap_mu / snap_cv: the helper's wake-ups, and snap_count.
      * snap_next: object lock.  snap_gen counts the encoders opened: a new one resets what the helper remembers of the last still it wrote. */
     gchar *snap_location;
+    /* frame-rate conversion: the properties (read at the next set_format), what the encoder was opened with, and per submitted frame that
+     * yielded pictures their number -- a FIFO in submission order, so that collected access units meet their GstVideoCodecFrame: a frame's pictures but the last
+     * are pushed as buffers of their own, the last one finishes the frame */
+    gint rate_mode, out_fps_n, out_fps_d, max_fill;
+    gint open_rate;           /* 0: conversion off */
+    GstClockTime tick;        /* duration of an output picture */
+    guint8 rate_q[8]; guint rate_qh, rate_qn;
     gchar *out_colorimetry; /* output-colorimetry: what the coded samples are to mean (NULL or "": what the input's mean) */
     guint snap_interval;
     gint snap_quality, snap_reduce, snap_source;
@@ -127,7 +134,7 @@ enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME
        PROP_CROP_LEFT, PROP_CROP_RIGHT, PROP_CROP_TOP, PROP_CROP_BOTTOM, PROP_ADD_BORDERS, PROP_UPSCALE, PROP_BORDER_COLOR,
        PROP_IMG_LOCATION, PROP_IMG_X, PROP_IMG_Y, PROP_IMG_ALPHA,
        PROP_SNAP_LOCATION, PROP_SNAP_INTERVAL, PROP_SNAP_QUALITY, PROP_SNAP_REDUCE, PROP_SNAP_SOURCE,
-       PROP_OUTPUT_COLORIMETRY };
+       PROP_OUTPUT_COLORIMETRY, PROP_RATE_CONVERSION, PROP_OUTPUT_FRAMERATE, PROP_MAX_FILL };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
     GST_STATIC_CAPS("video/x-raw, format=(string){ NV12, I420, YUY2, UYVY, Y42B, Y444, YV12, NV21, BGRx, RGBx, xRGB, xBGR, BGRA, RGBA, ARGB, ABGR, BGR, RGB, P010_10LE, I420_10LE, v210, GRAY8 }, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]; "
@@ -136,6 +143,13 @@ static GstStaticPadTemplate src_tmpl = GST_STATIC_PAD_TEMPLATE("src", GST_PAD_SR
     GST_STATIC_CAPS("video/x-h264, stream-format=(string)byte-stream, alignment=(string)au, profile=(string){ constrained-baseline, high }, "
                     "width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]"));
 
+static GType rate_conversion_type(void) {
+    static GType t = 0;
+    static const GEnumValue v[] = {{0, "Off: every input picture is coded", "off"}, {1, "Drop or repeat pictures to the output ticks", "hold"},
+                                   {2, "Blend neighbouring pictures at the output ticks' instants", "blend"}, {0, NULL, NULL}};
+    if (!t) t = g_enum_register_static("GstMi355H264EncRateConversion", v);
+    return t;
+}
 static GType snapshot_source_type(void) {
     static GType t = 0;
     static const GEnumValue v[] = {{0, "The coded source", "source"}, {1, "The decoded picture", "decoded"}, {0, NULL, NULL}};
@@ -267,6 +281,9 @@ static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *
     case PROP_SNAP_QUALITY: s->snap_quality = g_value_get_int(val); break;
     case PROP_SNAP_REDUCE: { const gint r = g_value_get_int(val); if (r == 1 || r == 2 || r == 4 || r == 8) s->snap_reduce = r; else GST_WARNING_OBJECT(s, "snapshot-reduce %d: not 1, 2, 4 or 8; stays %d", r, s->snap_reduce); break; }
     case PROP_SNAP_SOURCE: s->snap_source = g_value_get_enum(val); break;
+    case PROP_RATE_CONVERSION: s->rate_mode = g_value_get_enum(val); break; /* (these three are read at the next set_format) */
+    case PROP_OUTPUT_FRAMERATE: s->out_fps_n = gst_value_get_fraction_numerator(val); s->out_fps_d = gst_value_get_fraction_denominator(val); break;
+    case PROP_MAX_FILL: s->max_fill = g_value_get_int(val); break;
     case PROP_OUTPUT_COLORIMETRY: g_free(s->out_colorimetry); s->out_colorimetry = g_value_dup_string(val); break; /* (read at the next set_format) */
     case PROP_IMG_X: s->img_x = g_value_get_int(val); image_forward(s, FALSE); break;
     case PROP_IMG_Y: s->img_y = g_value_get_int(val); image_forward(s, FALSE); break;
@@ -326,6 +343,9 @@ static void get_property(GObject *obj, guint id, GValue *val, GParamSpec *ps) {
     case PROP_SNAP_QUALITY: g_value_set_int(val, s->snap_quality); break;
     case PROP_SNAP_REDUCE: g_value_set_int(val, s->snap_reduce); break;
     case PROP_SNAP_SOURCE: g_value_set_enum(val, s->snap_source); break;
+    case PROP_RATE_CONVERSION: g_value_set_enum(val, s->rate_mode); break;
+    case PROP_OUTPUT_FRAMERATE: gst_value_set_fraction(val, s->out_fps_n, s->out_fps_d > 0 ? s->out_fps_d : 1); break;
+    case PROP_MAX_FILL: g_value_set_int(val, s->max_fill); break;
     case PROP_OUTPUT_COLORIMETRY: g_value_set_string(val, s->out_colorimetry ? s->out_colorimetry : ""); break;
     case PROP_IMG_X: g_value_set_int(val, s->img_x); break;
     case PROP_IMG_Y: g_value_set_int(val, s->img_y); break;
@@ -664,6 +684,8 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
         if (t.slice_deblock >= 0) cfg.slice_deblock = t.slice_deblock;
     }
     const gboolean intra_refresh = s->intra_refresh, quality_stats = s->quality_stats;
+    const int rate_mode = s->rate_mode, max_fill = s->max_fill;
+    if (rate_mode && s->out_fps_n > 0 && s->out_fps_d > 0) { cfg.fps_num = fn = s->out_fps_n; cfg.fps_den = fd = s->out_fps_d; } /* the encoder runs at the output rate: rate control and the VUI follow the ticks */
     if (intra_refresh) { cfg.partitions = 0; if (!cfg.intra_in_p) cfg.intra_in_p = 1; } /* (the refresh columns are intra macroblocks of P pictures; no partitions) */
     GST_OBJECT_UNLOCK(s);
     int r = mi355enc_open(&cfg, &e);
@@ -689,6 +711,7 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     if (r == MI355ENC_OK && geom) r = mi355enc_set_input_geometry(e, &gm); /* (refused: a ratio above 8 either way, odd sizes) */
     else if (r == MI355ENC_OK && (in_w != pre_w || in_h != pre_h)) r = mi355enc_set_input_size(e, in_w, in_h); /* (refused: upscaling, a ratio above 8, odd sizes) */
     if (r == MI355ENC_OK && quality_stats) r = mi355enc_set_quality_metrics(e, 1);
+    if (r == MI355ENC_OK && rate_mode) { const mi355enc_rate_t rt = {rate_mode, GST_SECOND, max_fill}; r = mi355enc_set_rate_conversion(e, &rt); }
     if (r != MI355ENC_OK) {
         if (e) mi355enc_close(e);
         GST_ELEMENT_ERROR(s, LIBRARY, INIT, ("mi355h264enc: cannot open the MI355X encoder: %s", mi355enc_strerror(r)),
@@ -700,6 +723,7 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     s->enc = e;
     s->snap_gen++; s->snap_next = GST_CLOCK_TIME_NONE; s->snap_watch = 0; /* stills start over with the new encoder */
     s->open_depth = cfg.pipeline_depth;
+    s->open_rate = rate_mode; s->tick = gst_util_uint64_scale(GST_SECOND, (guint64)fd, (guint64)fn); s->rate_qh = s->rate_qn = 0;
     s->open_direction = dir;
     s->open_geom = geom;
     memcpy(s->open_crop, crop, sizeof crop);
@@ -732,6 +756,7 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
         else gst_util_fraction_multiply(GST_VIDEO_INFO_PAR_N(vi), GST_VIDEO_INFO_PAR_D(vi), in_w * pre_h, in_h * pre_w, &pn, &pd);
         out->info.par_n = tr ? pd : pn; out->info.par_d = tr ? pn : pd;
     }
+    if (rate_mode) { out->info.fps_n = fn; out->info.fps_d = fd; } /* the source caps carry the output rate */
     gst_video_codec_state_unref(out);
     if (cfg.pipeline_depth > 0) {
         GstClockTime d = gst_util_uint64_scale(GST_SECOND, (guint64)fd * cfg.pipeline_depth, fn);
@@ -748,7 +773,8 @@ static GstFlowReturn collect_into(GstMi355H264Enc *s, GstVideoCodecFrame *frame)
     size_t len = 0;
     int key = 0, qp = 0;
     const gint64 t0 = g_get_monotonic_time();
-    int r = mi355enc_collect(s->enc, s->au_buf, s->max_au, &len, &key, NULL, &qp);
+    int64_t tick_pts = 0;
+    int r = mi355enc_collect(s->enc, s->au_buf, s->max_au, &len, &key, &tick_pts, &qp);
     const gint64 t1 = g_get_monotonic_time();
     s->us_collect += t1 - t0;
     if (r != MI355ENC_OK) {
@@ -757,6 +783,26 @@ static GstFlowReturn collect_into(GstMi355H264Enc *s, GstVideoCodecFrame *frame)
         return GST_FLOW_ERROR;
     }
     if (s->snap_watch > 0) { s->snap_watch--; snapshot_wake(s); } /* an armed picture may just have been collected: the helper looks */
+    if (s->open_rate && s->rate_qn && s->rate_q[s->rate_qh] > 1) {
+        /* frame-rate conversion: a picture in front of the frame's own (a repeat, or an earlier mix of the same pair) leaves as a buffer of its own, with its
+         * tick's PTS; the frame stays the oldest one */
+        s->rate_q[s->rate_qh]--;
+        GstBuffer *b = gst_buffer_new_allocate(NULL, len, NULL);
+        if (!b) { gst_video_codec_frame_unref(frame); return GST_FLOW_ERROR; }
+        gst_buffer_fill(b, 0, s->au_buf, len);
+        GstClockTime t = (GstClockTime)tick_pts;
+        if (GST_CLOCK_TIME_IS_VALID(s->last_pts) && t < s->last_pts) t = s->last_pts;
+        s->last_pts = t;
+        GST_BUFFER_PTS(b) = GST_BUFFER_DTS(b) = t;
+        GST_BUFFER_DURATION(b) = s->tick;
+        if (!key) GST_BUFFER_FLAG_SET(b, GST_BUFFER_FLAG_DELTA_UNIT);
+        gst_video_codec_frame_unref(frame); /* (get_oldest_frame's reference) */
+        return gst_pad_push(GST_VIDEO_ENCODER_SRC_PAD(ve), b);
+    }
+    if (s->open_rate) { /* the frame's own picture: it carries its tick's PTS, not the input's */
+        if (s->rate_qn) { s->rate_qh = (s->rate_qh + 1) % G_N_ELEMENTS(s->rate_q); s->rate_qn--; }
+        frame->pts = (GstClockTime)tick_pts; frame->duration = s->tick;
+    }
     GstFlowReturn fr = gst_video_encoder_allocate_output_frame(ve, frame, len);
     if (fr != GST_FLOW_OK) { gst_video_encoder_finish_frame(ve, frame); return fr; }
     gst_buffer_fill(frame->output_buffer, 0, s->au_buf, len);
@@ -776,6 +822,38 @@ static GstFlowReturn collect_into(GstMi355H264Enc *s, GstVideoCodecFrame *frame)
     return fr;
 }
 
+/* frame-rate conversion, in front of a submit: the pictures it will yield need as many free slots (blend: at least one) -- collected here */
+static GstFlowReturn rate_make_room(GstMi355H264Enc *s, GstClockTime pts) {
+    GstVideoEncoder *ve = GST_VIDEO_ENCODER(s);
+    int need = mi355enc_rate_peek(s->enc, (int64_t)pts);
+    if (need < 1 && s->open_rate == 2) need = 1;
+    GstFlowReturn fr = GST_FLOW_OK;
+    while (fr == GST_FLOW_OK && mi355enc_pending(s->enc) + need > s->open_depth + 1) {
+        GstVideoCodecFrame *old = gst_video_encoder_get_oldest_frame(ve);
+        if (!old) break;
+        fr = collect_into(s, old);
+    }
+    return fr;
+}
+/* ... and behind it: the frame's count goes into the FIFO; a frame that yields no picture is finished without a buffer (TRUE: done) */
+static gboolean rate_submitted(GstMi355H264Enc *s, GstVideoCodecFrame *frame, GstFlowReturn *fr) {
+    const int n = mi355enc_last_submit_count(s->enc);
+    if (n <= 0) { *fr = gst_video_encoder_finish_frame(GST_VIDEO_ENCODER(s), frame); return TRUE; }
+    s->rate_q[(s->rate_qh + s->rate_qn++) % G_N_ELEMENTS(s->rate_q)] = (guint8)n;
+    return FALSE;
+}
+/* after a submit: as many collects as keep no more than pipeline-depth pictures in flight (one, without conversion) */
+static GstFlowReturn collect_down(GstMi355H264Enc *s) {
+    GstVideoEncoder *ve = GST_VIDEO_ENCODER(s);
+    GstFlowReturn fr = GST_FLOW_OK;
+    while (fr == GST_FLOW_OK && mi355enc_pending(s->enc) > s->open_depth) {
+        GstVideoCodecFrame *old = gst_video_encoder_get_oldest_frame(ve);
+        if (!old) break;
+        fr = collect_into(s, old); /* finish_frame() consumes the reference */
+        if (!s->open_rate) break;
+    }
+    return fr;
+}
 static GstFlowReturn enc_handle_frame(GstVideoEncoder *ve, GstVideoCodecFrame *frame) {
     GstMi355H264Enc *s = GST_MI355H264ENC(ve);
     GstVideoFrame vf;
@@ -809,6 +887,7 @@ static GstFlowReturn enc_handle_frame(GstVideoEncoder *ve, GstVideoCodecFrame *f
         return gst_video_encoder_finish_frame(ve, frame);
     }
     snapshot_maybe_arm(s, frame);
+    if (s->open_rate) { const GstFlowReturn fr = rate_make_room(s, frame->pts); if (fr != GST_FLOW_OK) { gst_video_encoder_finish_frame(ve, frame); return fr; } }
     const gint64 t0 = g_get_monotonic_time();
     if (s->jpeg) { /* a picture the encoder refuses (not baseline, another size, corrupt data) is dropped; ten in a row: this is not a stream it can take */
         GstMapInfo mi;
@@ -834,10 +913,8 @@ static GstFlowReturn enc_handle_frame(GstVideoEncoder *ve, GstVideoCodecFrame *f
         }
         s->jpeg_refused = 0;
         GstFlowReturn fr = GST_FLOW_OK;
-        if (mi355enc_pending(s->enc) > s->open_depth) {
-            GstVideoCodecFrame *old = gst_video_encoder_get_oldest_frame(ve);
-            if (old) fr = collect_into(s, old);
-        }
+        if (s->open_rate && rate_submitted(s, frame, &fr)) return fr;
+        fr = collect_down(s);
         gst_video_codec_frame_unref(frame);
         return fr;
     }
@@ -871,10 +948,8 @@ static GstFlowReturn enc_handle_frame(GstVideoEncoder *ve, GstVideoCodecFrame *f
         return GST_FLOW_ERROR;
     }
     GstFlowReturn fr = GST_FLOW_OK;
-    if (mi355enc_pending(s->enc) > s->open_depth) {
-        GstVideoCodecFrame *old = gst_video_encoder_get_oldest_frame(ve);
-        if (old) fr = collect_into(s, old); /* finish_frame() consumes the reference */
-    }
+    if (s->open_rate && rate_submitted(s, frame, &fr)) return fr;
+    fr = collect_down(s);
     gst_video_codec_frame_unref(frame);
     return fr;
 }
@@ -888,6 +963,8 @@ static GstFlowReturn drain(GstMi355H264Enc *s, gboolean push) {
         else {
             size_t n = 0;
             mi355enc_collect(s->enc, s->au_buf, s->max_au, &n, NULL, NULL, NULL);
+            if (s->open_rate && s->rate_qn && s->rate_q[s->rate_qh] > 1) { s->rate_q[s->rate_qh]--; gst_video_codec_frame_unref(old); continue; } /* (not the frame's last picture yet) */
+            if (s->open_rate && s->rate_qn) { s->rate_qh = (s->rate_qh + 1) % G_N_ELEMENTS(s->rate_q); s->rate_qn--; }
             gst_video_encoder_finish_frame(ve, old); /* no output buffer: dropped */
         }
         if (fr != GST_FLOW_OK) break;
@@ -920,7 +997,8 @@ static void gst_mi355_pin_allocator_init(GstMi355PinAllocator *a) { GST_OBJECT_F
 static GstCaps *enc_getcaps(GstVideoEncoder *ve, GstCaps *filter) {
     GstMi355H264Enc *s = GST_MI355H264ENC(ve);
     GST_OBJECT_LOCK(s);
-    const gboolean scaled = s->out_w > 0 || s->out_h > 0 || s->direction != GST_VIDEO_ORIENTATION_IDENTITY; /* (a direction may exchange the size: the pads' sizes are decoupled as well) */
+    const gboolean scaled = s->out_w > 0 || s->out_h > 0 || s->direction != GST_VIDEO_ORIENTATION_IDENTITY || /* (a direction may exchange the size: the pads' sizes are decoupled as well) */
+                            s->rate_mode != 0; /* (frame-rate conversion: the pads' frame rates are decoupled likewise) */
     GST_OBJECT_UNLOCK(s);
     if (!scaled) return gst_video_encoder_proxy_getcaps(ve, NULL, filter);
     GstCaps *t = gst_pad_get_pad_template_caps(GST_VIDEO_ENCODER_SINK_PAD(ve));
@@ -1093,6 +1171,9 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
     g_object_class_install_property(g, PROP_SNAP_REDUCE, g_param_spec_int("snapshot-reduce", "Still reduction", "1, 2, 4 or 8: the still is the picture's size divided by it (rounded up)", 1, 8, 4, F));
     g_object_class_install_property(g, PROP_SNAP_SOURCE, g_param_spec_enum("snapshot-source", "Still source", "source: the picture that is coded, with scaling, orientation, image and text in it; decoded: what a decoder shows", snapshot_source_type(), 0, F));
     g_object_class_install_property(g, PROP_OUTPUT_COLORIMETRY, g_param_spec_string("output-colorimetry", "Output colorimetry", "what the coded samples are to mean, e.g. bt709 or bt601 (a GstVideoColorimetry string): the SPS says this, and YUV input is converted on the GPU from the range and matrix its caps give; empty: label the stream as the input, convert nothing", "", F));
+    g_object_class_install_property(g, PROP_RATE_CONVERSION, g_param_spec_enum("rate-conversion", "Frame-rate conversion", "convert the frame rate on the GPU in place of a videorate in front: hold drops or repeats pictures to the output ticks, blend mixes neighbouring pictures at the ticks' instants", rate_conversion_type(), 0, F));
+    g_object_class_install_property(g, PROP_OUTPUT_FRAMERATE, gst_param_spec_fraction("output-framerate", "Output frame rate", "with rate-conversion: the frame rate of the stream and of the source caps; 0/1: the sink caps' rate", 0, 1, G_MAXINT, 1, 0, 1, F));
+    g_object_class_install_property(g, PROP_MAX_FILL, g_param_spec_int("max-fill", "Most repeats", "with rate-conversion: the most pictures one input may be preceded by (a longer hole in the timestamps re-anchors the ticks); at most pipeline-depth take effect", 0, 15, 2, F));
     g_object_class_override_property(g, PROP_VIDEO_DIRECTION, "video-direction"); /* GstVideoDirection: identity, 90r, 180, 90l, horiz, vert, ul-lr, ur-ll, auto -- as on videoflip */
     g_object_class_install_property(g, PROP_STATS, g_param_spec_boolean("stats", "Print stats", "Print a JSON line with counters when the encoder closes", FALSE, F));
     gst_element_class_add_static_pad_template(e, &sink_tmpl);
@@ -1111,6 +1192,7 @@ static void gst_mi355h264enc_init(GstMi355H264Enc *s) {
     s->direction = s->tag_direction = s->open_direction = GST_VIDEO_ORIENTATION_IDENTITY;
     s->border_color = 0x108080;
     s->out_colorimetry = NULL;
+    s->rate_mode = 0; s->out_fps_n = 0; s->out_fps_d = 1; s->max_fill = 2; s->open_rate = 0; s->tick = GST_CLOCK_TIME_NONE; s->rate_qh = s->rate_qn = 0;
     s->snap_location = NULL; s->snap_interval = 1000; s->snap_quality = 75; s->snap_reduce = 4; s->snap_source = 0; s->snap_next = GST_CLOCK_TIME_NONE; s->snap_watch = 0;
     g_mutex_init(&s->snap_mu); g_mutex_init(&s->snap_enc_mu); g_cond_init(&s->snap_cv);
     s->snap_thread = NULL; s->snap_wake = 0; s->snap_stop = FALSE; s->snap_count = 0; s->snap_gen = 0;

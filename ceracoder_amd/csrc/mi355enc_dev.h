@@ -247,6 +247,11 @@ int k_launch_orient(int method, const uint8_t *sy, int ssy, const uint8_t *suv, 
  * levels of a 4:2:0 still: 64 int16 per block in jpeg_host_layout's layout (16-byte aligned) and one hint byte per block (the zigzag index of its last non-zero
  * level), device or pinned host memory; d_tab: the quality's snapshot_tab_t on the device.  -1: sizes or a reduction it does not take. */
 int k_launch_snapshot(const uint8_t *sy, int ys, const uint8_t *suv, int uvs, int w, int h, int log2s, const void *d_tab, int16_t *levels, uint8_t *hint, hipStream_t s);
+/* Frame-rate conversion (k_rate.hip; the rule: DESIGN.md section 21): out = (a (256 - w256) + b w256 + 128) >> 8 per byte over NV12 surfaces of W x H at stride W
+ * (multiples of 16, every pointer 16-byte aligned), margins included; k_y / k_uv (both or neither): b is stored there as well.  Works in place index for index
+ * (a == k, b == out).  -1: arguments outside that. */
+int k_launch_rate_mix(const uint8_t *a_y, const uint8_t *a_uv, const uint8_t *b_y, const uint8_t *b_uv, uint8_t *o_y, uint8_t *o_uv, uint8_t *k_y, uint8_t *k_uv,
+                      int W, int H, int w256, hipStream_t s);
 void k_launch_quality(const uint8_t *src_y, const uint8_t *src_uv, int src_stride, const uint8_t *rec_y, const uint8_t *rec_uv, int rec_stride,
                       int width, int height, unsigned long long *d_acc, unsigned long long *out, hipStream_t s);
 #endif

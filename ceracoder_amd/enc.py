@@ -30,7 +30,7 @@ IDEC = np.dtype([("modes4", "u1", (16,)), ("mode16", "u1"), ("cmode", "u1"), ("u
 IMV_DTYPE = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("sad", "<u2"), ("bits", "<u2")])
 SURF_ROWS, SURF_COLS = 35, 36
 DROP_MAX, DROP_SKIP = 12, 255
-STAGE_ME, STAGE_INTER, STAGE_INTRA, STAGE_DEBLOCK, STAGE_SUBPEL, STAGE_CSC_I420, STAGE_CSC_YUY2, STAGE_CSC_UYVY, STAGE_ME_SELECT, STAGE_PMB, STAGE_INTRA_P, STAGE_QUALITY, STAGE_JPEG, STAGE_ORIENT, STAGE_SCALE, STAGE_IMAGE, STAGE_SNAPSHOT, STAGE_YUV_CONVERT = range(18)
+STAGE_ME, STAGE_INTER, STAGE_INTRA, STAGE_DEBLOCK, STAGE_SUBPEL, STAGE_CSC_I420, STAGE_CSC_YUY2, STAGE_CSC_UYVY, STAGE_ME_SELECT, STAGE_PMB, STAGE_INTRA_P, STAGE_QUALITY, STAGE_JPEG, STAGE_ORIENT, STAGE_SCALE, STAGE_IMAGE, STAGE_SNAPSHOT, STAGE_YUV_CONVERT, STAGE_RATE = range(19)
 # mi355enc_set_orientation: GstVideoOrientationMethod's numbers
 ORIENT_IDENTITY, ORIENT_90R, ORIENT_180, ORIENT_90L, ORIENT_HORIZ, ORIENT_VERT, ORIENT_UL_LR, ORIENT_UR_LL = range(8)
 ORIENT_NAMES = ("identity", "90r", "180", "90l", "horiz", "vert", "ul-lr", "ur-ll")
@@ -56,6 +56,8 @@ EXPORTS = [
     "mi355enc_geometry_check", "mi355enc_geometry_sar",
     "mi355enc_request_snapshot", "mi355enc_take_snapshot", "mi355enc_debug_snapshot_bytes", "mi355enc_snapshot_tables", "mi355enc_snapshot_reciprocal",
     "mi355enc_snapshot_max_bytes", "mi355enc_snapshot_write", "mi355enc_stage_snapshot_blocks", "mi355enc_stage_snapshot_blocks_device", "mi355enc_stage_snapshot",
+    "mi355enc_rate_check", "mi355enc_set_rate_conversion", "mi355enc_rate_peek", "mi355enc_last_submit_count", "mi355enc_rate_stats", "mi355enc_debug_rate_bytes",
+    "mi355enc_rate_plan_init", "mi355enc_rate_plan_step", "mi355enc_stage_rate",
 ]
 
 
@@ -137,6 +139,27 @@ class SnapshotInfo(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class Rate(C.Structure):
+    """mi355enc_rate_t: mode 0 off / 1 hold / 2 blend; the pts units per second; the most repeats one submit may yield"""
+    _fields_ = [("mode", C.c_int), ("pts_per_second", C.c_int64), ("max_fill", C.c_int)]
+
+
+class RateStats(C.Structure):
+    """mi355enc_rate_stats_t"""
+    _fields_ = [("in_", C.c_uint64), ("out", C.c_uint64), ("dropped", C.c_uint64), ("repeated", C.c_uint64), ("blended", C.c_uint64), ("resyncs", C.c_uint64)]
+
+    def as_dict(self):
+        return {k.rstrip("_"): int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class RatePlanState(C.Structure):
+    """mi355enc_rate_plan_t"""
+    _fields_ = [("mode", C.c_int), ("fps_num", C.c_int), ("fps_den", C.c_int), ("max_fill", C.c_int), ("started", C.c_int),
+                ("pps", C.c_int64), ("t0", C.c_int64), ("k_next", C.c_int64), ("prev_pts", C.c_int64)]
+
+
+RATE_OFF, RATE_HOLD, RATE_BLEND = 0, 1, 2
+RATE_MAX_OUT = 16
 SNAP_SOURCE, SNAP_DECODED = 0, 1
 IMAGE_LAYERS, IMAGE_MAX_DIM = 4, 4096
 GEOM_KEEP_SAR = 1  # mi355enc_geometry_t.flags: no aspect ratio from the geometry in the SPS
@@ -256,6 +279,17 @@ def load():
         L.mi355enc_stage_snapshot_blocks.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
         L.mi355enc_stage_snapshot_blocks_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
         L.mi355enc_stage_snapshot.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.mi355enc_rate_check.argtypes = [C.POINTER(Rate)]
+        L.mi355enc_set_rate_conversion.argtypes = [vp, C.POINTER(Rate)]
+        L.mi355enc_rate_peek.argtypes = [vp, C.c_int64]
+        L.mi355enc_last_submit_count.argtypes = [vp]
+        L.mi355enc_rate_stats.argtypes = [vp, C.POINTER(RateStats)]
+        L.mi355enc_debug_rate_bytes.restype = C.c_size_t
+        L.mi355enc_debug_rate_bytes.argtypes = [vp]
+        L.mi355enc_rate_plan_init.restype = None
+        L.mi355enc_rate_plan_init.argtypes = [C.POINTER(RatePlanState), C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64]
+        L.mi355enc_rate_plan_step.argtypes = [C.POINTER(RatePlanState), C.c_int64, C.POINTER(C.c_int), vp, vp, C.POINTER(C.c_int)]
+        L.mi355enc_stage_rate.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
         L.mi355enc_host_alloc.restype = vp
         L.mi355enc_host_alloc.argtypes = [C.c_size_t]
         L.mi355enc_host_free.restype = None
@@ -599,6 +633,29 @@ def _text_bytes(text):
     return text.encode("latin-1") if isinstance(text, str) else (bytes(text) if text is not None else None)
 
 
+def rate_check(mode, pts_per_second, max_fill):
+    """mi355enc_rate_check: True when mi355enc_set_rate_conversion would take the three values (host only)"""
+    return load().mi355enc_rate_check(C.byref(Rate(int(mode), int(pts_per_second), int(max_fill)))) == 0
+
+
+class RatePlan:
+    """The rule of the frame-rate conversion by itself (host logic; no device): which output pictures an input's pts yields."""
+
+    def __init__(self, mode, pts_per_second, fps_num, fps_den=1, max_fill=2, t0=0, k_next=-1):
+        self.L = load()
+        self.st = RatePlanState()
+        self.L.mi355enc_rate_plan_init(C.byref(self.st), int(mode), int(pts_per_second), int(fps_num), int(fps_den), int(max_fill), int(t0), int(k_next))
+
+    def step(self, pts):
+        """-> (out_pts list, weights list, resync): one entry per picture the input yields (hold: weight 0 a repeat, 256 the input)"""
+        n, rs = C.c_int(0), C.c_int(0)
+        t, w = (C.c_int64 * RATE_MAX_OUT)(), (C.c_int * RATE_MAX_OUT)()
+        r = self.L.mi355enc_rate_plan_step(C.byref(self.st), int(pts), C.byref(n), t, w, C.byref(rs))
+        if r:
+            raise EncoderError("mi355enc_rate_plan_step: %d" % r)
+        return [int(t[i]) for i in range(n.value)], [int(w[i]) for i in range(n.value)], bool(rs.value)
+
+
 RC_BYTES = 512  # include/mi355enc.h MI355ENC_RC_BYTES
 
 
@@ -665,7 +722,7 @@ class Encoder:
     (bitrate in bits/s as written through `bps`, key-int-max -> gop)."""
 
     def __init__(self, width, height, fps=60, gop=60, bitrate_bps=6_000_000, device_id=0, fixed_qp=-1, me_range=16,
-                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False, input_size=None, colorimetry=None, orientation=None, geometry=None, input_colorimetry=None):
+                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False, input_size=None, colorimetry=None, orientation=None, geometry=None, input_colorimetry=None, rate=None):
         self.L = load()
         cfg = Cfg()
         self.L.mi355enc_default_cfg(C.byref(cfg), width, height, fps, fps_den)
@@ -710,6 +767,10 @@ class Encoder:
             self._chk(self.L.mi355enc_set_colorimetry(self.h, *[int(v) for v in colorimetry]), "set_colorimetry", close_on_fail=True)
         if input_colorimetry is not None:  # (full_range, matrix): what submitted YUV samples mean; converted on the device to `colorimetry` where the two differ
             self._chk(self.L.mi355enc_set_input_colorimetry(self.h, *[int(v) for v in input_colorimetry]), "set_input_colorimetry", close_on_fail=True)
+        self.rate_on = False
+        if rate is not None:  # (mode, pts_per_second, max_fill): frame-rate conversion to fps / fps_den; every submit*() then returns the pictures it enqueued
+            self._chk(self.L.mi355enc_set_rate_conversion(self.h, C.byref(Rate(*[int(v) for v in rate]))), "set_rate_conversion", close_on_fail=True)
+            self.rate_on = int(rate[0]) != 0
         self.input_size = (width, height)
         self.orientation, self._in_set = ORIENT_IDENTITY, False
         if orientation is not None:  # 0 .. 7 or a name of ORIENT_NAMES: the pictures submitted are turned / mirrored on the device; width x height is the oriented size
@@ -780,6 +841,7 @@ class Encoder:
     def submit(self, y, uv, pts=0, force_idr=False):
         y, uv = _rows(y), _rows(uv)
         self._chk(self.L.mi355enc_submit(self.h, _p(y), y.strides[0], _p(uv), uv.strides[0], pts, int(force_idr)), "submit")
+        return self._count()
 
     def _planes(self, planes):
         arrs = [np.ascontiguousarray(a) for a in planes]  # uint8, or the 16-bit / 32-bit words of FMT_P010 / FMT_I420_10 / FMT_V210 as their bytes
@@ -795,6 +857,7 @@ class Encoder:
         it lies (so one inside a PinnedBuffer is transferred in place)."""
         arrs, pp, ss = self._planes(planes)
         self._chk(self.L.mi355enc_submit_fmt(self.h, fmt, pp, ss, pts, int(force_idr)), "submit_fmt")
+        return self._count()
 
     def stage_csc(self, fmt, planes):
         arrs, pp, ss = self._planes(planes)
@@ -808,6 +871,7 @@ class Encoder:
         for a picture that is refused or does not decode; nothing is enqueued then."""
         buf = np.frombuffer(bytes(data), np.uint8)
         self._chk(self.L.mi355enc_submit_jpeg(self.h, _p(buf) if buf.size else None, buf.size, pts, int(force_idr)), "submit_jpeg")
+        return self._count()
 
     def _surfaces(self):
         return np.empty((self.mbh * 16, self.mbw * 16), np.uint8), np.empty((self.mbh * 8, self.mbw * 16), np.uint8)
@@ -1057,6 +1121,33 @@ class Encoder:
 
     def submit_device(self, y_ptr, y_stride, uv_ptr, uv_stride, pts=0, force_idr=False):
         self._chk(self.L.mi355enc_submit_device(self.h, y_ptr, y_stride, uv_ptr, uv_stride, pts, int(force_idr)), "submit_device")
+        return self._count()
+
+    def _count(self):
+        """what a submit*() returns: with frame-rate conversion the pictures it enqueued (0 .. max_fill + 1), otherwise None as ever"""
+        return int(self.L.mi355enc_last_submit_count(self.h)) if getattr(self, "rate_on", False) else None
+
+    def rate_peek(self, pts):
+        """pictures a submit with this pts would enqueue now; changes nothing"""
+        return int(self.L.mi355enc_rate_peek(self.h, int(pts)))
+
+    def rate_stats(self):
+        """dict of in / out / dropped / repeated / blended / resyncs; EncoderError with conversion off"""
+        st = RateStats()
+        self._chk(self.L.mi355enc_rate_stats(self.h, C.byref(st)), "rate_stats")
+        return st.as_dict()
+
+    def rate_bytes(self):
+        """development: device memory held for the frame-rate conversion (0 when off, and in hold mode with max_fill 0)"""
+        return int(self.L.mi355enc_debug_rate_bytes(self.h))
+
+    def stage_rate(self, w256, a_y, a_uv, b_y, b_uv):
+        """The mix launch alone on host planes of the coded size: (a (256 - w256) + b w256 + 128) >> 8, as the encoder runs it (in place, b kept where a was); returns (y, uv)."""
+        pl = [np.ascontiguousarray(p, np.uint8) for p in (a_y, a_uv, b_y, b_uv)]
+        assert pl[0].shape == pl[2].shape == (self.mbh * 16, self.mbw * 16) and pl[1].shape == pl[3].shape == (self.mbh * 8, self.mbw * 16)
+        oy, ouv = self._surfaces()
+        self._chk(self.L.mi355enc_stage_rate(self.h, int(w256), _p(pl[0]), _p(pl[1]), _p(pl[2]), _p(pl[3]), _p(oy), _p(ouv)), "stage_rate")
+        return oy, ouv
 
     def collect(self, copy=True):
         n, key, pts, qp = C.c_size_t(0), C.c_int(0), C.c_int64(0), C.c_int(0)

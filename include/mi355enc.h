@@ -527,6 +527,42 @@ int mi355enc_stage_snapshot_blocks_device(mi355enc_t *h, const void *d_y, int y_
 /* ... and the whole file */
 int mi355enc_stage_snapshot(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t *uv, int uv_stride, int w, int ht, int reduce, int quality,
                             uint8_t *out, size_t cap, size_t *len);
+/* ---- frame-rate conversion --------------------------------------
+ * In place of a `videorate ! video/x-raw,framerate=...` in front of the encoder.  On, the pictures a handle codes lie on a regular grid of ticks at the
+ * configured fps_num / fps_den: tick k at T0 + k D / N (D = pts_per_second * fps_den, N = fps_num), its pts T0 + floor(k D / N); the first picture submitted
+ * sets T0 to its pts and is tick 0.  The pts of the submitted pictures decide which of them a tick shows:
+ *   hold   an input at p makes the ticks up to floor((2 N (p - T0) + D) / (2 D)) due (no later than half a tick period after p).  No due tick: the input is
+ *          dropped -- nothing of it is decoded, transferred or latched.  n due ticks: the first n - 1 repeat the previous output picture's source, the last
+ *          one shows the input.  Nothing waits for a later input.
+ *   blend  ticks up to floor((16 N (p - T0) + D) / (16 D)) are due (a sixteenth of a period of tolerance); a due tick is the mix of the previous input (at
+ *          p0) and this one (at p1) with w = clamp(round-half-up(256 (T_k - p0) / (p1 - p0)), 0, 256) from the exact rational T_k, every sample
+ *          (a (256 - w) + b w + 128) >> 8 after the colour step, luma and chroma alike (w = 0 and w = 256 give a and b exactly).  Every input is
+ *          transferred and kept; one with no due tick yields no picture.
+ * An input whose pts lies below the previous input's, or that would make more than max_fill + 1 ticks due, re-anchors: T0 = its pts, one picture, a resync.
+ * max_fill is clamped to cfg.pipeline_depth: a submit that yields n pictures takes n slots.  With fewer free ones the submit returns MI355ENC_ERR_STATE and
+ * has touched nothing -- collect, then submit again (in blend mode a submit that yields no picture still passes through one free slot).  Image layers and
+ * text are drawn afresh into every output picture, repeats included; they are never mixed or kept.  force_idr goes to the first picture a submit yields; a
+ * submit that yields none carries it to the next picture coded.  mi355enc_collect returns every picture with its tick's pts.  mi355enc_submit_device never
+ * takes its in-place exit and mi355enc_encode returns MI355ENC_ERR_STATE with conversion on.  Off (the default): nothing is allocated or launched. */
+typedef struct { int mode; int64_t pts_per_second; int max_fill; } mi355enc_rate_t;            /* mode 0 off, 1 hold, 2 blend */
+typedef struct { uint64_t in, out, dropped, repeated, blended, resyncs; } mi355enc_rate_stats_t; /* blended: pictures with 0 < w < 256 */
+#define MI355ENC_RATE_MAX_OUT 16 /* most pictures one step of a plan yields: max_fill is 0 .. 15 there */
+/* the rule's state (host only): initialise with mi355enc_rate_plan_init, then treat as opaque */
+typedef struct { int mode, fps_num, fps_den, max_fill, started; int64_t pps, t0, k_next, prev_pts; } mi355enc_rate_plan_t;
+int mi355enc_rate_check(const mi355enc_rate_t *r);                           /* host only: ERR_ARG for no r, mode outside 0..2, pts_per_second <= 0, max_fill < 0 */
+int mi355enc_set_rate_conversion(mi355enc_t *h, const mi355enc_rate_t *r);   /* before the first submit only (ERR_STATE after); ERR_ARG as above */
+int mi355enc_rate_peek(const mi355enc_t *h, int64_t pts);                    /* pictures a submit with this pts would enqueue now: 0 .. max_fill + 1 (1 with conversion off); changes nothing */
+int mi355enc_last_submit_count(const mi355enc_t *h);                         /* pictures the last successful submit enqueued */
+int mi355enc_rate_stats(mi355enc_t *h, mi355enc_rate_stats_t *st);           /* ERR_STATE with conversion off */
+size_t mi355enc_debug_rate_bytes(const mi355enc_t *h);                       /* device memory held for it: 0 when off, and in hold mode with max_fill 0 */
+/* host only, no handle: the rule itself.  init: max_fill is clamped to 0 .. 15; k_next < 0 starts an empty plan (the first input anchors it), k_next >= 0 one
+ * anchored at t0 whose ticks below k_next are out.  step: one input; *n pictures (0 .. max_fill + 1) with their pts and weights (hold: 0 a repeat, 256 the
+ * input) in arrays of MI355ENC_RATE_MAX_OUT entries, *resync 1 when it re-anchored.  ERR_ARG for a missing pointer or a plan that was not initialised. */
+void mi355enc_rate_plan_init(mi355enc_rate_plan_t *plan, int mode, int64_t pts_per_second, int fps_num, int fps_den, int max_fill, int64_t t0, int64_t k_next);
+int mi355enc_rate_plan_step(mi355enc_rate_plan_t *plan, int64_t pts, int *n, int64_t out_pts[], int weight[], int *resync);
+/* the launch alone (tests): out = mix of a and b with weight w256 (0 .. 256); host planes of the coded size, stride 16 * mb_width; works with conversion off;
+ * ERR_STATE with pictures pending */
+int mi355enc_stage_rate(mi355enc_t *h, int w256, const uint8_t *a_y, const uint8_t *a_uv, const uint8_t *b_y, const uint8_t *b_uv, uint8_t *out_y, uint8_t *out_uv);
 size_t mi355enc_max_au_bytes(const mi355enc_t *h);
 const char *mi355enc_strerror(int code);
 int mi355enc_abi_version(void);
@@ -588,7 +624,8 @@ int mi355enc_stage_deblock(mi355enc_t *h, uint8_t *rec_y, uint8_t *rec_uv, const
  * 14 the scale / geometry launch for an NV12 picture of the handle's input size (MI355ENC_ERR_STATE without mi355enc_set_input_size / _geometry), likewise,
  * 15 the blend launch of image layer 0 at its current place into slot 0's source surfaces (MI355ENC_ERR_STATE without an image on layer 0),
  * 16 the still launch on slot 0's source surfaces, with the reduction and quality of the last mi355enc_request_snapshot (1 and 75 without one),
- * 17 the colour step on slot 0's source surfaces (MI355ENC_ERR_STATE when the handle has no conversion).
+ * 17 the colour step on slot 0's source surfaces (MI355ENC_ERR_STATE when the handle has no conversion),
+ * 18 the frame-rate conversion's mix launch (w = 128) of the keep buffer and slot 0's source surfaces, in place (MI355ENC_ERR_STATE with conversion off).
  * Uses whatever the handle's surfaces currently hold.  Returns average ms per launch. */
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms);
 
