@@ -118,7 +118,7 @@ int mi355enc_yuv_coefficients(int in_matrix, int in_full, int out_matrix, int ou
 
 int mi355enc_set_input_colorimetry(mi355enc_t *h, int full_range, int matrix) {
     if (!h || (full_range | 1) != 1 || (matrix != 1 && matrix != 2 && matrix != 5 && matrix != 6 && matrix != 9)) return MI355ENC_ERR_ARG;
-    if (h->n_submitted) return MI355ENC_ERR_STATE; // (like the output's: fixed from the stream's first picture on)
+    if (h->n_submitted || h->hdr_on) return MI355ENC_ERR_STATE; // (like the output's: fixed from the stream's first picture on; not beside mi355enc_set_hdr_input)
     h->in_col_set = true; h->in_col_full = full_range; h->in_col_mat = matrix;
     csc_resolve(h);
     return MI355ENC_OK;
@@ -157,12 +157,13 @@ int mi355enc_stage_csc_device(mi355enc_t *h, int fmt, const void *const d_planes
     fmt_plane_t pl[3];
     const int nplanes = fmt == MI355ENC_FMT_NV12 ? 0 : fmt_planes(fmt, w, ht, pl);
     if (!nplanes || !planes_fit(nplanes, pl, p, st)) return MI355ENC_ERR_ARG;
-    if (fmt_is_rgb(fmt) && !h->csc_ok) return MI355ENC_ERR_ARG;
+    if ((fmt_is_rgb(fmt) && !h->csc_ok) || hdr_refuses(h, fmt)) return MI355ENC_ERR_ARG;
     HIPCHK(hipSetDevice(h->cfg.device_id));
     int r;
-    if (fmt <= MI355ENC_FMT_UYVY) r = k_launch_csc(fmt, p[0], p[1], p[2], st[0], st[1], st[2], (uint8_t *)d_out_y, (uint8_t *)d_out_uv, w, ht, h->W, h->H, h->stream);
+    if (h->hdr_on) r = hdr_convert(h, fmt, p, st, (uint8_t *)d_out_y, (uint8_t *)d_out_uv, w, ht, h->W, h->H, h->stream); // (tone-mapped: DESIGN.md section 22)
+    else if (fmt <= MI355ENC_FMT_UYVY) r = k_launch_csc(fmt, p[0], p[1], p[2], st[0], st[1], st[2], (uint8_t *)d_out_y, (uint8_t *)d_out_uv, w, ht, h->W, h->H, h->stream);
     else r = k_launch_csc2(fmt, p[0], p[1], p[2], st[0], st[1], st[2], (uint8_t *)d_out_y, (uint8_t *)d_out_uv, w, ht, h->W, h->H, h->csc_coef, h->stream);
-    if (r) return MI355ENC_ERR_ARG;
+    if (r) return r < -1 ? r : MI355ENC_ERR_ARG;
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
     return MI355ENC_OK;

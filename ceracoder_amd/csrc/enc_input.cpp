@@ -156,6 +156,7 @@ int upload_and_convert(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const p
         return upload_and_convert(h, s, yv12_as_i420(fmt, pl, sl), pl, sl, up);
     }
     if (fmt_is_rgb(fmt) && !h->csc_ok) return MI355ENC_ERR_ARG; // (a matrix code RGB cannot be converted with: before anything is uploaded)
+    if (hdr_refuses(h, fmt)) return MI355ENC_ERR_ARG;           // (a handle that tone-maps takes the three 10-bit formats only)
     const uint8_t *p[3];
     int st[3];
     int r = upload_raw(h, s, fmt, planes, strides, up, p, st);
@@ -166,17 +167,19 @@ int upload_and_convert(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const p
     const scale_plan_t *pl = h->scaling ? scale_plan_for(h, s, up) : nullptr;
     if (h->scaling && !pl) return MI355ENC_ERR_HIP;
     if (fmt >= MI355ENC_FMT_Y42B) { // the formats of k_csc.hip; with an input size of its own: converted at that size, then scaled as NV12
-        if (!h->scaling) r = k_launch_csc2(fmt, p[0], p[1], p[2], st[0], st[1], st[2], t.y, t.uv, t.vw, t.vh, t.W, t.H, h->csc_coef, up);
+        if (h->hdr_on && !h->scaling) r = hdr_convert(h, fmt, p, st, t.y, t.uv, t.vw, t.vh, t.W, t.H, up); // (tone-mapped in the conversion launch: DESIGN.md section 22)
+        else if (!h->scaling) r = k_launch_csc2(fmt, p[0], p[1], p[2], st[0], st[1], st[2], t.y, t.uv, t.vw, t.vh, t.W, t.H, h->csc_coef, up);
         else {
             nv12_pic_t c;
             r = input_nv12(h, s, &c);
             if (r) return r;
-            r = k_launch_csc2(fmt, p[0], p[1], p[2], st[0], st[1], st[2], c.y, c.uv, h->in_w, h->in_h, c.stride, h->in_h, h->csc_coef, up);
+            if (h->hdr_on) r = hdr_convert(h, fmt, p, st, c.y, c.uv, h->in_w, h->in_h, c.stride, h->in_h, up);
+            else r = k_launch_csc2(fmt, p[0], p[1], p[2], st[0], st[1], st[2], c.y, c.uv, h->in_w, h->in_h, c.stride, h->in_h, h->csc_coef, up);
             if (!r) r = scale_nv12(&c, &t, pl, up);
         }
     } else if (h->scaling) r = k_launch_scale(fmt, p[0], p[1], p[2], st[0], st[1], st[2], t.y, t.uv, t.W, t.H, pl, up);
     else r = k_launch_csc(fmt, p[0], p[1], p[2], st[0], st[1], st[2], t.y, t.uv, t.vw, t.vh, t.W, t.H, up);
-    if (r) return MI355ENC_ERR_ARG;
+    if (r) return r < -1 ? r : MI355ENC_ERR_ARG;
     HIPCHK(hipGetLastError());
     return input_finish(h, s, up);
 }
@@ -233,7 +236,7 @@ int mi355enc_stage_csc(mi355enc_t *h, int fmt, const uint8_t *const planes[3], c
 // this thread, into the slot's pinned staging buffer and leaves from there in one asynchronous transfer per plane, on the front stream,
 // beside the kernels of the pictures before it.
 int mi355enc_submit(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t *uv, int uv_stride, int64_t pts, int force_idr) {
-    if (!h || !y || !uv || y_stride < h->in_w || uv_stride < h->in_w || h->yuv_bad) return MI355ENC_ERR_ARG; // (yuv_bad: YUV samples that cannot be converted to the output's matrix)
+    if (!h || !y || !uv || y_stride < h->in_w || uv_stride < h->in_w || h->yuv_bad || hdr_refuses(h, MI355ENC_FMT_NV12)) return MI355ENC_ERR_ARG; // (yuv_bad: YUV samples that cannot be converted to the output's matrix; a handle that tone-maps takes 10-bit input only)
     slot_t *s;
     { int r = ingest_begin(h, &s, pts, force_idr); if (r) return begin_answer(r); }
     const int w = h->in_w, ht = h->in_h;
@@ -299,7 +302,7 @@ int mi355enc_submit(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t
 int mi355enc_submit_fmt(mi355enc_t *h, int fmt, const uint8_t *const planes[3], const int strides[3], int64_t pts, int force_idr) {
     if (!h || !planes || !strides) return MI355ENC_ERR_ARG;
     if (fmt == MI355ENC_FMT_NV12) return mi355enc_submit(h, planes[0], strides[0], planes[1], strides[1], pts, force_idr);
-    if (!fmt_is_rgb(fmt) && h->yuv_bad) return MI355ENC_ERR_ARG;
+    if ((!fmt_is_rgb(fmt) && h->yuv_bad) || hdr_refuses(h, fmt)) return MI355ENC_ERR_ARG;
     slot_t *s;
     int r = ingest_begin(h, &s, pts, force_idr);
     if (r) return begin_answer(r);
@@ -311,7 +314,7 @@ int mi355enc_submit_fmt(mi355enc_t *h, int fmt, const uint8_t *const planes[3], 
 // MJPEG input: the host decodes the entropy-coded data into the slot's pinned coefficient buffer first -- a picture that is refused or does not decode has
 // touched nothing else -- then the transfer and the JPEG launch take the place of the conversion launch.
 int mi355enc_submit_jpeg(mi355enc_t *h, const uint8_t *data, size_t len, int64_t pts, int force_idr) {
-    if (!h || !data || h->yuv_bad) return MI355ENC_ERR_ARG;
+    if (!h || !data || h->yuv_bad || hdr_refuses(h, -1)) return MI355ENC_ERR_ARG;
     slot_t *s;
     int r = ingest_slot(h, &s, pts, force_idr);
     if (r) return begin_answer(r); // (a dropped picture is not entropy-decoded)
@@ -325,7 +328,7 @@ int mi355enc_submit_jpeg(mi355enc_t *h, const uint8_t *data, size_t len, int64_t
 // Device input.  The in-place exit is the one exception to the sequence: the kernels read the caller's planes where they lie, nothing is drawn (with a
 // colour step, a text or an active layer the exit is not taken) and nothing was uploaded, so enqueue_picture follows the latches directly.
 int mi355enc_submit_device(mi355enc_t *h, const void *d_y, int y_stride, const void *d_uv, int uv_stride, int64_t pts, int force_idr) {
-    if (!h || !d_y || !d_uv || y_stride < h->in_w || uv_stride < h->in_w || h->yuv_bad) return MI355ENC_ERR_ARG;
+    if (!h || !d_y || !d_uv || y_stride < h->in_w || uv_stride < h->in_w || h->yuv_bad || hdr_refuses(h, -1)) return MI355ENC_ERR_ARG;
     slot_t *s;
     int r = ingest_begin(h, &s, pts, force_idr);
     if (r) return begin_answer(r);

@@ -30,6 +30,7 @@
 #include "h264_host.h"
 #include "mi355enc_dev.h"
 #include "snapshot_host.h"
+#include "hdr_host.h"
 
 #define HIPCHK(expr)                                                                                 \
     do {                                                                                             \
@@ -211,6 +212,14 @@ struct mi355enc {
     // output matrix is not one the step can convert to -- a YUV submit is refused
     bool in_col_set, yuv_on, yuv_bad;
     int in_col_full, in_col_mat, yuv_coef[9];
+    // HDR input (mi355enc_set_hdr_input).  hdr_on: the call was made -- P010, I420_10 and V210 pictures are tone-mapped in their conversion
+    // launch, every other input is refused.  h_hdr / d_hdr: the parameter block (HDR_WORDS words of mi355enc_hdr_tables) as built for the output (matrix, range)
+    // hdr_key names, on the host and on the device; built and uploaded in front of the first conversion, on its stream (hdr_stream), and again only if the
+    // output's colorimetry was changed since (before the first submit).  Nothing of this is allocated on a handle that never made the call.
+    bool hdr_on = false, hdr_arrived = false; // hdr_arrived: a stream other than hdr_stream has waited for the upload, no later launch needs to
+    int hdr_transfer = 0, hdr_full = 0, hdr_peak = 0, hdr_target = 0, hdr_key = -1;
+    int32_t *h_hdr = nullptr, *d_hdr = nullptr;
+    hipStream_t hdr_stream = nullptr;
     // frame-rate conversion (mi355enc_set_rate_conversion).  rate.mode 0: off, and nothing below is used but last_count.  rate.max_fill is
     // clamped to pipeline_depth.  rate_plan: the rule's state; ingest_begin steps a copy of it (rate_next, with what the step yields: rate_n pictures, their pts
     // and weights) and ingest_end commits it once the pictures are enqueued -- a submit that fails in between has not advanced the plan.  d_keep: one NV12
@@ -375,6 +384,13 @@ static inline bool fmt_is_rgb(int fmt) { return fmt >= MI355ENC_FMT_BGRX && fmt 
 // the colour step on the slot's coded surfaces, behind everything enqueued on st so far: the picture part (with a geometry: the oriented destination rectangle) is
 // converted in place, the border keeps its bytes
 int yuv_draw(mi355enc_t *h, slot_t *s, hipStream_t st);
+// enc_hdr.cpp (HDR input)
+// true: the handle tone-maps and this input is not one it takes (a format other than the three 10-bit ones -- fmt -1: an entry point that takes none of them --
+// or an output matrix outside 1, 5, 6, 2): the submit fails with MI355ENC_ERR_ARG before anything is latched
+bool hdr_refuses(const mi355enc_t *h, int fmt);
+// the conversion launch of a 10-bit picture on a handle with hdr_on, in the place of k_launch_csc2 (same arguments); the block travels in front of the first one
+int hdr_convert(mi355enc_t *h, int fmt, const uint8_t *const p[3], const int st[3], uint8_t *dy, uint8_t *duv, int vw, int vh, int W, int H, hipStream_t s);
+void hdr_free(mi355enc_t *h);
 // enc_rate.cpp (frame-rate conversion; every one of them is called with conversion on only)
 #pragma GCC visibility push(hidden)
 #define INGEST_DROP 1 /* ingest_begin's answer for a submit that yields no picture and needs no transfer (hold mode): the submit returns MI355ENC_OK at once */

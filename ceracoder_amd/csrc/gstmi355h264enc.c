@@ -106,6 +106,7 @@ typedef struct {
      * yielded pictures their number -- a FIFO in submission order, so that collected access units meet their GstVideoCodecFrame: a frame's pictures but the last
      * are pushed as buffers of their own, the last one finishes the frame */
     gint rate_mode, out_fps_n, out_fps_d, max_fill;
+    gint hdr_input, hdr_peak, hdr_target; /* hdr-input (0 off, 16 pq, 18 hlg), hdr-peak-nits, hdr-target-nits: read at the next set_format */
     gint open_rate;           /* 0: conversion off */
     GstClockTime tick;        /* duration of an output picture */
     guint8 rate_q[8]; guint rate_qh, rate_qn;
@@ -134,7 +135,7 @@ enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME
        PROP_CROP_LEFT, PROP_CROP_RIGHT, PROP_CROP_TOP, PROP_CROP_BOTTOM, PROP_ADD_BORDERS, PROP_UPSCALE, PROP_BORDER_COLOR,
        PROP_IMG_LOCATION, PROP_IMG_X, PROP_IMG_Y, PROP_IMG_ALPHA,
        PROP_SNAP_LOCATION, PROP_SNAP_INTERVAL, PROP_SNAP_QUALITY, PROP_SNAP_REDUCE, PROP_SNAP_SOURCE,
-       PROP_OUTPUT_COLORIMETRY, PROP_RATE_CONVERSION, PROP_OUTPUT_FRAMERATE, PROP_MAX_FILL };
+       PROP_OUTPUT_COLORIMETRY, PROP_RATE_CONVERSION, PROP_OUTPUT_FRAMERATE, PROP_MAX_FILL, PROP_HDR_INPUT, PROP_HDR_PEAK_NITS, PROP_HDR_TARGET_NITS };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
     GST_STATIC_CAPS("video/x-raw, format=(string){ NV12, I420, YUY2, UYVY, Y42B, Y444, YV12, NV21, BGRx, RGBx, xRGB, xBGR, BGRA, RGBA, ARGB, ABGR, BGR, RGB, P010_10LE, I420_10LE, v210, GRAY8 }, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]; "
@@ -148,6 +149,13 @@ static GType rate_conversion_type(void) {
     static const GEnumValue v[] = {{0, "Off: every input picture is coded", "off"}, {1, "Drop or repeat pictures to the output ticks", "hold"},
                                    {2, "Blend neighbouring pictures at the output ticks' instants", "blend"}, {0, NULL, NULL}};
     if (!t) t = g_enum_register_static("GstMi355H264EncRateConversion", v);
+    return t;
+}
+static GType hdr_input_type(void) { /* (the values are the transfer's H.264 Table E-4 code points: what mi355enc_set_hdr_input takes) */
+    static GType t = 0;
+    static const GEnumValue v[] = {{0, "Off: 10-bit input is rounded to 8 bits", "off"}, {16, "PQ (SMPTE ST 2084), BT.2020: tone-mapped to SDR", "pq"},
+                                   {18, "HLG (BT.2100), BT.2020: tone-mapped to SDR", "hlg"}, {0, NULL, NULL}};
+    if (!t) t = g_enum_register_static("GstMi355H264EncHdrInput", v);
     return t;
 }
 static GType snapshot_source_type(void) {
@@ -284,6 +292,9 @@ static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *
     case PROP_RATE_CONVERSION: s->rate_mode = g_value_get_enum(val); break; /* (these three are read at the next set_format) */
     case PROP_OUTPUT_FRAMERATE: s->out_fps_n = gst_value_get_fraction_numerator(val); s->out_fps_d = gst_value_get_fraction_denominator(val); break;
     case PROP_MAX_FILL: s->max_fill = g_value_get_int(val); break;
+    case PROP_HDR_INPUT: s->hdr_input = g_value_get_enum(val); break; /* (these three are read at the next set_format) */
+    case PROP_HDR_PEAK_NITS: s->hdr_peak = g_value_get_int(val); break;
+    case PROP_HDR_TARGET_NITS: s->hdr_target = g_value_get_int(val); break;
     case PROP_OUTPUT_COLORIMETRY: g_free(s->out_colorimetry); s->out_colorimetry = g_value_dup_string(val); break; /* (read at the next set_format) */
     case PROP_IMG_X: s->img_x = g_value_get_int(val); image_forward(s, FALSE); break;
     case PROP_IMG_Y: s->img_y = g_value_get_int(val); image_forward(s, FALSE); break;
@@ -346,6 +357,9 @@ static void get_property(GObject *obj, guint id, GValue *val, GParamSpec *ps) {
     case PROP_RATE_CONVERSION: g_value_set_enum(val, s->rate_mode); break;
     case PROP_OUTPUT_FRAMERATE: gst_value_set_fraction(val, s->out_fps_n, s->out_fps_d > 0 ? s->out_fps_d : 1); break;
     case PROP_MAX_FILL: g_value_set_int(val, s->max_fill); break;
+    case PROP_HDR_INPUT: g_value_set_enum(val, s->hdr_input); break;
+    case PROP_HDR_PEAK_NITS: g_value_set_int(val, s->hdr_peak); break;
+    case PROP_HDR_TARGET_NITS: g_value_set_int(val, s->hdr_target); break;
     case PROP_OUTPUT_COLORIMETRY: g_value_set_string(val, s->out_colorimetry ? s->out_colorimetry : ""); break;
     case PROP_IMG_X: g_value_set_int(val, s->img_x); break;
     case PROP_IMG_Y: g_value_set_int(val, s->img_y); break;
@@ -685,9 +699,18 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     }
     const gboolean intra_refresh = s->intra_refresh, quality_stats = s->quality_stats;
     const int rate_mode = s->rate_mode, max_fill = s->max_fill;
+    const int hdr_input = s->hdr_input, hdr_peak = s->hdr_peak, hdr_target = s->hdr_target;
     if (rate_mode && s->out_fps_n > 0 && s->out_fps_d > 0) { cfg.fps_num = fn = s->out_fps_n; cfg.fps_den = fd = s->out_fps_d; } /* the encoder runs at the output rate: rate control and the VUI follow the ticks */
     if (intra_refresh) { cfg.partitions = 0; if (!cfg.intra_in_p) cfg.intra_in_p = 1; } /* (the refresh columns are intra macroblocks of P pictures; no partitions) */
     GST_OBJECT_UNLOCK(s);
+    /* hdr-input: GStreamer 1.14's caps cannot say PQ or HLG, so the property does; only the three 10-bit formats can be HDR here */
+    if (hdr_input) {
+        const GstVideoFormat f = jpeg ? GST_VIDEO_FORMAT_UNKNOWN : GST_VIDEO_INFO_FORMAT(vi);
+        if (f != GST_VIDEO_FORMAT_P010_10LE && f != GST_VIDEO_FORMAT_I420_10LE && f != GST_VIDEO_FORMAT_v210) {
+            GST_ELEMENT_ERROR(s, CORE, NEGOTIATION, ("mi355h264enc: hdr-input needs P010_10LE, I420_10LE or v210 input"), ("caps %s", jpeg ? "image/jpeg" : gst_video_format_to_string(f)));
+            return FALSE;
+        }
+    }
     int r = mi355enc_open(&cfg, &e);
     if (r == MI355ENC_OK && intra_refresh) r = mi355enc_set_intra_refresh(e, 1); /* (refused with key-int-max < 2) */
     if (r == MI355ENC_OK) { /* what the samples mean goes into the SPS (x264enc copies its input caps' colorimetry likewise); YUV input is only labelled */
@@ -699,7 +722,15 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
             prim = trc = mat = (out_w > 1024 || out_h > 576) ? 1 : 6;
             full = 0;
         } else if (GST_VIDEO_INFO_IS_RGB(vi)) full = 0;
-        if (convert) { /* the SPS carries the output's codes; YUV input is converted to them on the device from what the caps say it is, RGB straight to them */
+        if (hdr_input) { /* tone-mapped to SDR: the caps give the input's range only; the SPS says output-colorimetry, else BT.709 limited -- never the caps' bt2020 label */
+            const int in_full = full;
+            full = 0; prim = trc = mat = 1;
+            if (convert) {
+                colorimetry_codes(&out_col, &full, &prim, &trc, &mat);
+                if (mat != 1 && mat != 2 && mat != 5 && mat != 6) r = MI355ENC_ERR_ARG; /* (the library would refuse the first picture) */
+            }
+            if (r == MI355ENC_OK) r = mi355enc_set_hdr_input(e, hdr_input, in_full, hdr_peak, hdr_target); /* (refused: a peak or target outside the setter's range) */
+        } else if (convert) { /* the SPS carries the output's codes; YUV input is converted to them on the device from what the caps say it is, RGB straight to them */
             const int in_full = full, in_mat = mat;
             colorimetry_codes(&out_col, &full, &prim, &trc, &mat);
             if (mat != 1 && mat != 2 && mat != 5 && mat != 6 && mat != 9) r = MI355ENC_ERR_ARG; /* (the library would refuse the first picture) */
@@ -1174,6 +1205,9 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
     g_object_class_install_property(g, PROP_RATE_CONVERSION, g_param_spec_enum("rate-conversion", "Frame-rate conversion", "convert the frame rate on the GPU in place of a videorate in front: hold drops or repeats pictures to the output ticks, blend mixes neighbouring pictures at the ticks' instants", rate_conversion_type(), 0, F));
     g_object_class_install_property(g, PROP_OUTPUT_FRAMERATE, gst_param_spec_fraction("output-framerate", "Output frame rate", "with rate-conversion: the frame rate of the stream and of the source caps; 0/1: the sink caps' rate", 0, 1, G_MAXINT, 1, 0, 1, F));
     g_object_class_install_property(g, PROP_MAX_FILL, g_param_spec_int("max-fill", "Most repeats", "with rate-conversion: the most pictures one input may be preceded by (a longer hole in the timestamps re-anchors the ticks); at most pipeline-depth take effect", 0, 15, 2, F));
+    g_object_class_install_property(g, PROP_HDR_INPUT, g_param_spec_enum("hdr-input", "HDR input", "the 10-bit input (P010_10LE, I420_10LE, v210) is PQ or HLG with BT.2020 primaries and matrix: tone-mapped on the GPU to SDR BT.709 (or to output-colorimetry) in the conversion launch; the caps give the range; other caps are an error", hdr_input_type(), 0, F));
+    g_object_class_install_property(g, PROP_HDR_PEAK_NITS, g_param_spec_int("hdr-peak-nits", "HDR source peak", "with hdr-input: the source's peak luminance in cd/m^2 (HLG: the nominal peak Lw), 400 .. 10000 (hlg: .. 2000); 0: 1000", 0, 10000, 0, F));
+    g_object_class_install_property(g, PROP_HDR_TARGET_NITS, g_param_spec_int("hdr-target-nits", "SDR target peak", "with hdr-input: the luminance the SDR peak stands for in cd/m^2, 100 .. 400; 0: 203 (BT.2408's reference white)", 0, 400, 0, F));
     g_object_class_override_property(g, PROP_VIDEO_DIRECTION, "video-direction"); /* GstVideoDirection: identity, 90r, 180, 90l, horiz, vert, ul-lr, ur-ll, auto -- as on videoflip */
     g_object_class_install_property(g, PROP_STATS, g_param_spec_boolean("stats", "Print stats", "Print a JSON line with counters when the encoder closes", FALSE, F));
     gst_element_class_add_static_pad_template(e, &sink_tmpl);
@@ -1192,6 +1226,7 @@ static void gst_mi355h264enc_init(GstMi355H264Enc *s) {
     s->direction = s->tag_direction = s->open_direction = GST_VIDEO_ORIENTATION_IDENTITY;
     s->border_color = 0x108080;
     s->out_colorimetry = NULL;
+    s->hdr_input = 0; s->hdr_peak = 0; s->hdr_target = 0;
     s->rate_mode = 0; s->out_fps_n = 0; s->out_fps_d = 1; s->max_fill = 2; s->open_rate = 0; s->tick = GST_CLOCK_TIME_NONE; s->rate_qh = s->rate_qn = 0;
     s->snap_location = NULL; s->snap_interval = 1000; s->snap_quality = 75; s->snap_reduce = 4; s->snap_source = 0; s->snap_next = GST_CLOCK_TIME_NONE; s->snap_watch = 0;
     g_mutex_init(&s->snap_mu); g_mutex_init(&s->snap_enc_mu); g_cond_init(&s->snap_cv);

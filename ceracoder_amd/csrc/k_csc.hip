@@ -14,16 +14,6 @@ struct csc2_args {
     int yr, yg, yb, br, bg, bb, rr, rg, rb, off; // RGB: the matrix in 2^-16 units and the luma offset (mi355enc_csc_coefficients)
 };
 
-// Four values (each fits 16 bits) -> clipped bytes of one word through the packed 16-bit forms and v_perm, not `clip255(a) | clip255(b) << 8 | ...`:
-// for that hipcc selects gfx950's v_ashr_pk_u8_i32, whose upper half is not cleared on this hardware (tests/test_abi_cpu.py).
-typedef short csc_s2 __attribute__((ext_vector_type(2)));
-DEV unsigned csc_pack4(int a, int b, int c, int d) {
-    const csc_s2 lo = __builtin_bit_cast(csc_s2, __builtin_amdgcn_perm((unsigned)b, (unsigned)a, 0x05040100u));
-    const csc_s2 hi = __builtin_bit_cast(csc_s2, __builtin_amdgcn_perm((unsigned)d, (unsigned)c, 0x05040100u));
-    const csc_s2 l = __builtin_elementwise_min(__builtin_elementwise_max(lo, (csc_s2)(0)), (csc_s2)(255));
-    const csc_s2 h = __builtin_elementwise_min(__builtin_elementwise_max(hi, (csc_s2)(0)), (csc_s2)(255));
-    return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, h), __builtin_bit_cast(unsigned, l), 0x06040200u);
-}
 DEV void csc_store(const csc2_args &a, int ry, int x0, const uint2 *yrow, const unsigned *uvw) {
     stg64(a.dy + (size_t)(2 * ry) * a.W + x0, yrow[0]);
     stg64(a.dy + (size_t)(2 * ry + 1) * a.W + x0, yrow[1]);
@@ -203,16 +193,6 @@ __global__ __launch_bounds__(256) void csc_rgb_kernel(csc2_args a) {
 // fills whole 8-byte words, so every store of the fast path stays an aligned 8-byte one; the coded width is a multiple of 16, not of 24, so the last patch of a
 // row may keep only its first one or two 8-sample pieces.  Margin rows read the picture's last rows on the same path.  A patch that reaches past the visible
 // width, and planes that are not 16-byte (I420_10's chroma: 8-byte) aligned, go sample by sample with clamped source coordinates and byte loads.
-DEV int deep_word(const uint8_t *p) { return (int)(ldg8(p) | (ldg8(p + 1) << 8)); } // a 16-bit word, byte by byte
-DEV unsigned v210_field(const uint8_t *row, int wi, int sh) { // field of word wi of the row, byte by byte
-    const uint8_t *p = row + 4 * wi;
-    return ((ldg8(p) | (ldg8(p + 1) << 8) | (ldg8(p + 2) << 16) | (ldg8(p + 3) << 24)) >> sh) & 1023u;
-}
-// where the samples of a v210 group lie: word and shift per luma sample 0..5 / per chroma sample (Cb0 Cr0 Cb1 Cr1 Cb2 Cr2)
-DEV int v210_yw(int k) { return (0x332110 >> (4 * k)) & 3; }
-DEV int v210_ys(int k) { return 10 * ((0x201201 >> (4 * k)) & 3); }
-DEV int v210_cw(int k) { return (0x322100 >> (4 * k)) & 3; }
-DEV int v210_cs(int k) { return 10 * ((0x120120 >> (4 * k)) & 3); }
 DEV int deep8(int v10) { const int v = (v10 + 2) >> 2; return v > 255 ? 255 : v; }
 // luma sample (sx, sy) as the byte it becomes
 template <int FMT> DEV int deep_luma(const csc2_args &a, int sx, int sy) {
@@ -234,7 +214,6 @@ template <int FMT> DEV int deep_chroma(const csc2_args &a, int c, int base, int 
     }
     return 128;
 }
-DEV int v210_get(const uint4 &q, int w, int sh) { return (int)(((w == 0 ? q.x : w == 1 ? q.y : w == 2 ? q.z : q.w) >> sh) & 1023u); }
 template <int FMT>
 __global__ __launch_bounds__(256) void csc_deep_kernel(csc2_args a) {
     constexpr int PW = FMT == 16 ? 24 : 8;

@@ -282,6 +282,28 @@ DEV void store_levels(int16_t *dst, const int *lev) { // 16 int16 = two 16-byte 
 }
 DEV unsigned pack4(int a, int b, int c, int d) { return (unsigned)a | ((unsigned)b << 8) | ((unsigned)c << 16) | ((unsigned)d << 24); }
 DEV int byte_of(unsigned w, int i) { return (int)((w >> (8 * i)) & 255); }
+// Four values (each fits 16 bits) -> clipped bytes of one word through the packed 16-bit forms and v_perm, not `clip255(a) | clip255(b) << 8 | ...`:
+// for that hipcc selects gfx950's v_ashr_pk_u8_i32, whose upper half is not cleared on this hardware (tests/test_abi_cpu.py).
+typedef short csc_s2 __attribute__((ext_vector_type(2)));
+DEV unsigned csc_pack4(int a, int b, int c, int d) {
+    const csc_s2 lo = __builtin_bit_cast(csc_s2, __builtin_amdgcn_perm((unsigned)b, (unsigned)a, 0x05040100u));
+    const csc_s2 hi = __builtin_bit_cast(csc_s2, __builtin_amdgcn_perm((unsigned)d, (unsigned)c, 0x05040100u));
+    const csc_s2 l = __builtin_elementwise_min(__builtin_elementwise_max(lo, (csc_s2)(0)), (csc_s2)(255));
+    const csc_s2 h = __builtin_elementwise_min(__builtin_elementwise_max(hi, (csc_s2)(0)), (csc_s2)(255));
+    return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, h), __builtin_bit_cast(unsigned, l), 0x06040200u);
+}
+// the 10-bit formats' words (k_csc.hip, k_hdr.hip)
+DEV int deep_word(const uint8_t *p) { return (int)(ldg8(p) | (ldg8(p + 1) << 8)); } // a 16-bit word, byte by byte
+DEV unsigned v210_field(const uint8_t *row, int wi, int sh) { // field of word wi of the row, byte by byte
+    const uint8_t *p = row + 4 * wi;
+    return ((ldg8(p) | (ldg8(p + 1) << 8) | (ldg8(p + 2) << 16) | (ldg8(p + 3) << 24)) >> sh) & 1023u;
+}
+// where the samples of a v210 group lie: word and shift per luma sample 0..5 / per chroma sample (Cb0 Cr0 Cb1 Cr1 Cb2 Cr2)
+DEV int v210_yw(int k) { return (0x332110 >> (4 * k)) & 3; }
+DEV int v210_ys(int k) { return 10 * ((0x201201 >> (4 * k)) & 3); }
+DEV int v210_cw(int k) { return (0x322100 >> (4 * k)) & 3; }
+DEV int v210_cs(int k) { return 10 * ((0x120120 >> (4 * k)) & 3); }
+DEV int v210_get(const uint4 &q, int w, int sh) { return (int)(((w == 0 ? q.x : w == 1 ? q.y : w == 2 ? q.z : q.w) >> sh) & 1023u); }
 
 // Chroma of one macroblock, run by 8 consecutive lanes (cl = 0..7: plane c = cl>>2, block b = cl&3).
 // value of lane (l ^ K) of this lane's quad, K = 1..3 (DPP quad_perm)

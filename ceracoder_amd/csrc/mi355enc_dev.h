@@ -163,6 +163,9 @@ int k_launch_csc(int fmt, const uint8_t *p0, const uint8_t *p1, const uint8_t *p
  * the chroma planes exchanged); coef: the ten words of mi355enc_csc_coefficients, RGB formats only.  -1: not one of them */
 int k_launch_csc2(int fmt, const uint8_t *p0, const uint8_t *p1, const uint8_t *p2, int s0, int s1, int s2, uint8_t *dy, uint8_t *duv,
                   int vw, int vh, int W, int H, const int *coef, hipStream_t s);
+/* HDR input tone-mapped to SDR NV12 (k_hdr.hip; the model and the rule: DESIGN.md section 22): fmt MI355ENC_FMT_P010, _I420_10 or _V210, planes and strides
+ * as k_launch_csc2's, d_tables the words of mi355enc_hdr_tables on the device, hlg whether their transfer is 18 (the kernel with the OOTF step) and not 16.  -1: another format, or arguments outside what the kernel's addressing holds for */
+int k_launch_hdr(int fmt, int hlg, const uint8_t *const planes[3], const int strides[3], uint8_t *dy, uint8_t *duv, int vw, int vh, int W, int H, const int *d_tables, hipStream_t s);
 /* the colour step (k_csc.hip; the rule: DESIGN.md section 20), in place on NV12 surfaces of W x H at stride W: the samples inside rect (x0, x1, y0, y1; even)
  * go from one (range, matrix) to another with the nine words of mi355enc_yuv_coefficients; everything outside keeps its bytes.  -1: arguments outside that */
 int k_launch_yuv_convert(uint8_t *y, uint8_t *uv, int W, int H, const int rect[4], const int *coef, hipStream_t s);

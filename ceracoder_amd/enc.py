@@ -22,6 +22,7 @@ FETCH_SCALE_TABLES = 6  # the device's copy of the scale tables (Encoder.scale_t
 FETCH_BAND_CUTS, FETCH_ERROR_WORD = 102, 103  # development: Encoder.band_cuts(), Encoder.error_word()
 BAND_ROWS = 4  # MI355_BAND_ROWS: macroblock rows per band of the band deblocker
 ERR_ARG, ERR_STATE = -1, -6
+ERR_OVERFLOW = -5
 FMT_NV12, FMT_I420, FMT_YUY2, FMT_UYVY = range(4)
 FMT_Y42B, FMT_Y444, FMT_YV12, FMT_NV21, FMT_BGRX, FMT_RGBX, FMT_XRGB, FMT_XBGR, FMT_BGR, FMT_RGB = range(4, 14)  # converted by k_csc.hip
 FMT_P010, FMT_I420_10, FMT_V210, FMT_GRAY8 = range(14, 18)  # 10-bit and grey input
@@ -31,6 +32,8 @@ IMV_DTYPE = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("sad", "<u2"), ("bits", "
 SURF_ROWS, SURF_COLS = 35, 36
 DROP_MAX, DROP_SKIP = 12, 255
 STAGE_ME, STAGE_INTER, STAGE_INTRA, STAGE_DEBLOCK, STAGE_SUBPEL, STAGE_CSC_I420, STAGE_CSC_YUY2, STAGE_CSC_UYVY, STAGE_ME_SELECT, STAGE_PMB, STAGE_INTRA_P, STAGE_QUALITY, STAGE_JPEG, STAGE_ORIENT, STAGE_SCALE, STAGE_IMAGE, STAGE_SNAPSHOT, STAGE_YUV_CONVERT, STAGE_RATE = range(19)
+STAGE_HDR_P010, STAGE_HDR_I420_10, STAGE_HDR_V210, STAGE_DEEP_P010 = 19, 20, 21, 22  # the tone-mapping launch per format, and the plain P010 launch beside it
+HDR_PQ, HDR_HLG = 16, 18  # mi355enc_set_hdr_input: the transfer's H.264 Table E-4 code point
 # mi355enc_set_orientation: GstVideoOrientationMethod's numbers
 ORIENT_IDENTITY, ORIENT_90R, ORIENT_180, ORIENT_90L, ORIENT_HORIZ, ORIENT_VERT, ORIENT_UL_LR, ORIENT_UR_LL = range(8)
 ORIENT_NAMES = ("identity", "90r", "180", "90l", "horiz", "vert", "ul-lr", "ur-ll")
@@ -58,6 +61,7 @@ EXPORTS = [
     "mi355enc_snapshot_max_bytes", "mi355enc_snapshot_write", "mi355enc_stage_snapshot_blocks", "mi355enc_stage_snapshot_blocks_device", "mi355enc_stage_snapshot",
     "mi355enc_rate_check", "mi355enc_set_rate_conversion", "mi355enc_rate_peek", "mi355enc_last_submit_count", "mi355enc_rate_stats", "mi355enc_debug_rate_bytes",
     "mi355enc_rate_plan_init", "mi355enc_rate_plan_step", "mi355enc_stage_rate",
+    "mi355enc_set_hdr_input", "mi355enc_hdr_tables",
 ]
 
 
@@ -224,6 +228,8 @@ def load():
         L.mi355enc_stage_csc_device.argtypes = [vp, C.c_int, vp, vp, vp, vp]
         L.mi355enc_set_input_colorimetry.argtypes = [vp, C.c_int, C.c_int]
         L.mi355enc_yuv_coefficients.argtypes = [C.c_int] * 4 + [vp]
+        L.mi355enc_set_hdr_input.argtypes = [vp] + [C.c_int] * 4
+        L.mi355enc_hdr_tables.argtypes = [C.c_int] * 6 + [vp, C.c_size_t, vp]
         L.mi355enc_stage_yuv_convert.argtypes = [vp, vp, vp]
         L.mi355enc_set_quality_metrics.argtypes = [vp, C.c_int]
         L.mi355enc_last_quality.argtypes = [vp, C.POINTER(Quality)]
@@ -354,6 +360,20 @@ def yuv_coefficients(in_matrix, in_full, out_matrix, out_full):
     if r:
         raise EncoderError("mi355enc_yuv_coefficients(%d, %d, %d, %d): %d" % (in_matrix, in_full, out_matrix, out_full, r))
     return c
+
+
+def hdr_tables(transfer, full_range=0, peak_nits=0, target_nits=0, out_matrix=1, out_full=0):
+    """The parameter block of the HDR tone map in the device's integer arithmetic (host only; include/mi355enc.h has the layout): int32 (7726,)."""
+    L, n = load(), C.c_size_t(0)
+    args = [int(v) for v in (transfer, full_range, peak_nits, target_nits, out_matrix, out_full)]
+    r = L.mi355enc_hdr_tables(*args, None, 0, C.byref(n))
+    if r:
+        raise EncoderError("mi355enc_hdr_tables%r: %d" % (tuple(args), r))
+    out = np.zeros(n.value, np.int32)
+    r = L.mi355enc_hdr_tables(*args, out.ctypes.data_as(C.c_void_p), out.size, C.byref(n))
+    if r:
+        raise EncoderError("mi355enc_hdr_tables%r: %d" % (tuple(args), r))
+    return out
 
 
 def csc_coefficients(matrix, full_range):
@@ -722,7 +742,7 @@ class Encoder:
     (bitrate in bits/s as written through `bps`, key-int-max -> gop)."""
 
     def __init__(self, width, height, fps=60, gop=60, bitrate_bps=6_000_000, device_id=0, fixed_qp=-1, me_range=16,
-                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False, input_size=None, colorimetry=None, orientation=None, geometry=None, input_colorimetry=None, rate=None):
+                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False, input_size=None, colorimetry=None, orientation=None, geometry=None, input_colorimetry=None, rate=None, hdr_input=None):
         self.L = load()
         cfg = Cfg()
         self.L.mi355enc_default_cfg(C.byref(cfg), width, height, fps, fps_den)
@@ -767,6 +787,8 @@ class Encoder:
             self._chk(self.L.mi355enc_set_colorimetry(self.h, *[int(v) for v in colorimetry]), "set_colorimetry", close_on_fail=True)
         if input_colorimetry is not None:  # (full_range, matrix): what submitted YUV samples mean; converted on the device to `colorimetry` where the two differ
             self._chk(self.L.mi355enc_set_input_colorimetry(self.h, *[int(v) for v in input_colorimetry]), "set_input_colorimetry", close_on_fail=True)
+        if hdr_input is not None:  # (transfer, full_range, peak_nits, target_nits): the 10-bit pictures submitted are PQ / HLG BT.2020 and are tone-mapped on the device to SDR in `colorimetry`
+            self._chk(self.L.mi355enc_set_hdr_input(self.h, *[int(v) for v in hdr_input]), "set_hdr_input", close_on_fail=True)
         self.rate_on = False
         if rate is not None:  # (mode, pts_per_second, max_fill): frame-rate conversion to fps / fps_den; every submit*() then returns the pictures it enqueued
             self._chk(self.L.mi355enc_set_rate_conversion(self.h, C.byref(Rate(*[int(v) for v in rate]))), "set_rate_conversion", close_on_fail=True)
@@ -823,6 +845,11 @@ class Encoder:
     def set_input_colorimetry(self, full_range, matrix):
         """what the submitted YUV samples mean (before the first submit): converted on the device to set_colorimetry's range and matrix where they differ"""
         self._chk(self.L.mi355enc_set_input_colorimetry(self.h, int(full_range), int(matrix)), "set_input_colorimetry")
+
+    def set_hdr_input(self, transfer, full_range=0, peak_nits=0, target_nits=0):
+        """the submitted 10-bit pictures (FMT_P010, FMT_I420_10, FMT_V210) are HDR (transfer HDR_PQ / HDR_HLG, BT.2020): tone-mapped to SDR BT.709 in their conversion
+        launch (before the first submit; not beside set_input_colorimetry); every other input is refused from then on"""
+        self._chk(self.L.mi355enc_set_hdr_input(self.h, int(transfer), int(full_range), int(peak_nits), int(target_nits)), "set_hdr_input")
 
     def stage_yuv_convert(self, y, uv):
         """The colour step alone on host planes of the coded size, with the handle's geometry, orientation and colorimetries; returns the converted copies."""

@@ -254,6 +254,35 @@ int mi355enc_set_input_colorimetry(mi355enc_t *h, int full_range, int matrix);
  * input's luma offset oy (16 or 0), [8] the output's oy'.  Y' = clip((cyy (Y - oy) + cyb (Cb - 128) + cyr (Cr - 128) + (oy' << 16) + 2^15) >> 16);
  * Cb' = clip((cbb (Cb - 128) + cbr (Cr - 128) + (128 << 16) + 2^15) >> 16), Cr' likewise with crb, crr.  Matrices 1, 5, 6 or 9, else MI355ENC_ERR_ARG. */
 int mi355enc_yuv_coefficients(int in_matrix, int in_full, int out_matrix, int out_full, int32_t coef[9]);
+/* HDR input: the submitted 10-bit pictures (MI355ENC_FMT_P010, _I420_10, _V210) are PQ (transfer 16, SMPTE ST 2084) or HLG (18,
+ * BT.2100) Y'CbCr with the BT.2020 non-constant-luminance matrix, limited range (full_range 0: Y - 64 over 876, C - 512 over 896) or full; they are tone-mapped to
+ * SDR BT.709 in their conversion launch and land in the coded surfaces as 8-bit Y'CbCr of mi355enc_set_colorimetry's matrix and range.  The model: linear
+ * display light (PQ: the EOTF, clipped to peak_nits; HLG: the inverse OETF and the OOTF with Lw = peak_nits), the BT.2390 section 5.4.1 EETF from peak_nits to
+ * target_nits on max(R, G, B) as a gain on all three, BT.2020 -> BT.709 primaries, over target_nits, clipped, the BT.709 OETF, then the output matrix; a 4:2:0
+ * chroma pair from the mean R'G'B' of its four samples; a luma sample uses the chroma pair of its own 2 x 2 block; v210's chroma is first averaged over the two
+ * rows, (a + b + 1) >> 1.  The device follows it in integers and table look-ups (mi355enc_hdr_tables) to within one output code.
+ * transfer 16 or 18; peak_nits 0 (1000) or 400 .. 10000 (HLG: .. 2000); target_nits 0 (203, BT.2408's reference white) or 100 .. 400; else MI355ENC_ERR_ARG.
+ * Before the first submit only, and not on a handle on which mi355enc_set_input_colorimetry was called (nor that call after this one): MI355ENC_ERR_STATE.
+ * Once set, every entry point that takes the three formats tone-maps them (mi355enc_submit_fmt, mi355enc_stage_csc, mi355enc_stage_csc_device, the two-launch
+ * form under an input size or geometry); every other input -- 8-bit YUV, RGB, GRAY8, JPEG, mi355enc_submit_device -- and an output matrix outside 1, 5, 6, 2
+ * (2: resolved by the coded size as for RGB input) fail with MI355ENC_ERR_ARG before anything is latched.  Never called: nothing is allocated, uploaded or
+ * launched, and every stream is byte for byte what it was. */
+int mi355enc_set_hdr_input(mi355enc_t *h, int transfer, int full_range, int peak_nits, int target_nits);
+/* The parameter block of the tone map in the device's integer arithmetic (host only, no device needed): *n = the block's size in words (7726); out (cap words)
+ * receives it; out null: the size alone; cap too small: MI355ENC_ERR_OVERFLOW.  out_matrix 1, 5 or 6; other arguments as mi355enc_set_hdr_input's.  Words:
+ * 0 layout version (1), 1 transfer, 2 full_range, 3 peak, 4 target (resolved), 5 out_matrix, 6 out_full, 7 words in all; 8 oy, 9 cy, 10 rv, 11 gu, 12 gv, 13 bu
+ * (the input matrix, 2^-28 per code); 14-16 the HLG luminance weights (2^-16); 17-25 BT.2020 -> BT.709 by rows (2^-20); 26-28 yr yg yb, 29-31 br bg bb, 32-34
+ * rr rg rb (2^-14 of a code per unit); 35 oy'; 36-39 zero; 40 LIN[4097] (linear light over the non-linear code in 2^-12 steps, 2^-28 of peak / of scene 1.0);
+ * 4137 GA[1282] (HLG OOTF gain Ys^(g - 1), 2^-30); 5419 GB[1282] (tone gain EETF(n) / n peak / target, 2^-24); 6701 OE[1025] (BT.709 OETF over 2^-10 steps,
+ * 2^-16).  GA, GB by octaves: entry 64 o + m stands for s = (64 + m) << (o + 2), entry 1280 for 2^28, 1281 repeats it.  The rule, with y = Y - oy, u = Cb - 512,
+ * v = Cr - 512:  t = cy y + {rv v | gu u + gv v | bu u};  x = clip((t + 8) >> 4, 0, 2^24), k = min(x >> 12, 4095), f = x - (k << 12),
+ * l = LIN[k] + (((LIN[k + 1] - LIN[k]) f + 2^11) >> 12);  HLG only: ys = (lr lR + lg lG + lb lB + 2^15) >> 16, l = (l gain(GA, ys) + 2^29) >> 30;
+ * w = (l gain(GB, max l) + 2^23) >> 24;  u_i = clip((sum_j M_ij w_j + 2^19) >> 20, 0, 2^28), k = min(u >> 18, 1023), f = u - (k << 18),
+ * E = OE[k] + (((OE[k + 1] - OE[k]) f + 2^17) >> 18);  Y' = clip255((yr R + yg G + yb B + (oy' << 30) + 2^29) >> 30);  with S the sums of E over a pair's
+ * four samples, Cb = clip255((br SR + bg SG + bb SB + (128 << 32) + 2^31) >> 32), Cr likewise.  gain(T, s): s = max(min(s, 2^28), 256), e = floor(log2 s),
+ * sh = e - 6, q = s >> sh, i = 64 (e - 8) + q - 64, f = s - (q << sh), T[i] + (((T[i + 1] - T[i]) f + (1 << (sh - 1))) >> sh).  Products wider than 32 bits
+ * are taken in 64. */
+int mi355enc_hdr_tables(int transfer, int full_range, int peak_nits, int target_nits, int out_matrix, int out_full, int32_t *out, size_t cap, size_t *n);
 /* the colour step alone (tests): host NV12 planes of the coded size (16*mbw x 16*mbh luma, then interleaved chroma), in and out, like mi355enc_stage_image,
  * with the handle's geometry, orientation and colorimetries; MI355ENC_ERR_STATE when the handle has no conversion */
 int mi355enc_stage_yuv_convert(mi355enc_t *h, uint8_t *y, uint8_t *uv);
@@ -625,7 +654,9 @@ int mi355enc_stage_deblock(mi355enc_t *h, uint8_t *rec_y, uint8_t *rec_uv, const
  * 15 the blend launch of image layer 0 at its current place into slot 0's source surfaces (MI355ENC_ERR_STATE without an image on layer 0),
  * 16 the still launch on slot 0's source surfaces, with the reduction and quality of the last mi355enc_request_snapshot (1 and 75 without one),
  * 17 the colour step on slot 0's source surfaces (MI355ENC_ERR_STATE when the handle has no conversion),
- * 18 the frame-rate conversion's mix launch (w = 128) of the keep buffer and slot 0's source surfaces, in place (MI355ENC_ERR_STATE with conversion off).
+ * 18 the frame-rate conversion's mix launch (w = 128) of the keep buffer and slot 0's source surfaces, in place (MI355ENC_ERR_STATE with conversion off),
+ * 19 / 20 / 21 the tone-mapping conversion launch of a P010 / I420_10 / V210 picture in slot 0's raw staging buffer (whatever the last conversion left there;
+ * MI355ENC_ERR_STATE without mi355enc_set_hdr_input), 22 the plain P010 conversion launch from the same buffer.
  * Uses whatever the handle's surfaces currently hold.  Returns average ms per launch. */
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms);
 
