@@ -3,6 +3,7 @@
 //   enc_handle.cpp    open / close / setters / statistics / fetch
 //   enc_input.cpp     the input path: submit*, from the caller's picture to the slot's source surfaces (upload, conversion, the sequence around them)
 //   enc_schedule.cpp  the picture pipeline: the stream schedule of one picture, the entropy worker, recovery, collect
+//   enc_plan.hpp      ... and that schedule's decisions as a value: plan_picture(), plain C++ (included here)
 //   enc_overlay.cpp   the text overlay: setters, latch, layout, launch
 //   enc_image.cpp    image layers: setters, latch, upload + prepare, blend launches, retirement
 //   enc_orient.cpp    orientation of the input picture: setter, the slot's pre-orientation picture, launch, its stage entry points
@@ -31,6 +32,7 @@
 #include "mi355enc_dev.h"
 #include "snapshot_host.h"
 #include "hdr_host.h"
+#include "enc_plan.hpp"
 
 #define HIPCHK(expr)                                                                                 \
     do {                                                                                             \
@@ -88,7 +90,7 @@ struct slot_t {
     hipEvent_t done, gpu_done, ev[12];
     hipEvent_t ev_up;          // the source has arrived (upload stream; only when that is a stream of its own)
     hipEvent_t ev_front;       // the front stream's part of the picture is done (source in place, search + selection + analysis)
-    int prof, fused;
+    int prof;
     int all_skip;              // the picture is one run of P_Skip macroblocks: written by the host alone, no device work
     uint64_t index;            // position of the picture in the stream
     int is_idr, qp, drop, frame_num, idr_pic_id, rec_index, set;
@@ -301,8 +303,7 @@ int sync_compute(mi355enc_t *h);
 bool host_range_pinned(const void *p, size_t bytes); // inside memory handed out by mi355enc_host_alloc()
 // enc_schedule.cpp
 int run_intra(mi355enc_t *h, int ci, const frame_ctx_t *hc, unsigned *band_done = nullptr);
-int run_deblock(mi355enc_t *h, int ci, const frame_ctx_t *hc, hipStream_t st, const unsigned *ip_progress, const unsigned *iband_done = nullptr,
-                unsigned *band_done = nullptr, bool after_gated_pmb = false, unsigned row_need = 0, bool fused_ip = false);
+int run_deblock(mi355enc_t *h, int ci, const frame_ctx_t *hc, const pic_plan_t &plan = pic_plan_t(), int rec = -1); // (the defaults: in order on the main stream, no band-done words)
 void fill_ctx(mi355enc_t *h, frame_ctx_t *c, int qp, int drop, int idr, int set = 0);
 int ip_rows_stamp(mi355enc_t *h, uint32_t epoch); // in front of every launch of a P picture's intra macroblock rows
 int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_t *src_uv, int src_stride, int64_t pts, int force_idr);

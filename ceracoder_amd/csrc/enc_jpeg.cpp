@@ -17,6 +17,7 @@ int jpeg_alloc(mi355enc_t *h, slot_t *s) {
     memset(s->h_jpeg, 0, bytes);
     HIPCHK(hipMalloc((void **)&s->d_jpeg, bytes));
     HIPCHK(hipMemset(s->d_jpeg, 0, bytes)); // (mi355enc_time_stage runs the launch on whatever the buffer holds)
+    HIPCHK(hipStreamSynchronize(nullptr));  // the fill runs on the null stream, which the handle's streams do not wait for: through before the first transfer into the buffer is enqueued
     HIPCHK(hipMalloc((void **)&s->d_jpeg_planar, 3 * (size_t)((h->in_w + 15) & ~15) * h->in_h + SURF_PAD));
     return MI355ENC_OK;
 }

@@ -9,6 +9,8 @@
 //   hand-over stream, from the moment records and levels are final: scan + pack into pinned host memory -> event
 //   host, when the event has fired: CAVLC slice coding (h264_host.c).
 // With pipeline_depth = 1 the host codes picture n while the device works on n+1; with 2 a third picture is in flight.
+// Which of these run beside each other, on which stream, waiting for what on the device, is the picture's plan (enc_plan.hpp; the table of its flags:
+// DESIGN.md section 5, "The plan of a picture"): enqueue_picture() decides, plans, then enqueues from the plan.
 #include "enc_internal.hpp"
 
 static void worker_push(mi355enc_t *h, int slot_index);
@@ -44,13 +46,17 @@ int run_intra(mi355enc_t *h, int ci, const frame_ctx_t *hc, unsigned *band_done)
     } else launch_intra_all(h, ci);
     return 0;
 }
-// whole picture on the main stream; hc: host copy of the context (by-value kernels), ci: which device copy holds the same (graph kernels)
-int run_deblock(mi355enc_t *h, int ci, const frame_ctx_t *hc, hipStream_t st, const unsigned *ip_progress, const unsigned *iband_done, unsigned *band_done, bool after_gated_pmb, unsigned row_need, bool fused_ip) {
+static hipStream_t plan_stream(const mi355enc_t *h, plan_stream_t which) { return which == PS_MAIN ? h->stream : which == PS_FRONT ? h->fstream : which == PS_INTRA ? h->istream : h->cstream; }
+// whole picture; hc: host copy of the context (by-value kernels), ci: which device copy holds the same (graph kernels); p: the picture's plan -- the stream and what the
+// launch waits for on the device (the stage entry points: the in-order plan); rec: the reconstruction buffer whose band-done words the launch publishes (-1: none)
+int run_deblock(mi355enc_t *h, int ci, const frame_ctx_t *hc, const pic_plan_t &p, int rec) {
     if (h->cfg.deblock_mode == 0) { // the persistent band kernel (its prologue derives the boundary strengths from the records)
-        const int wgs = k_launch_deblock_bands(hc, h->mbh, 0, k_deblock_bands16(h->mbh), err_word(h), h->d_db_gran, h->d_db_par, ip_progress, iband_done, h->cfg.intra_mode == 2 ? k_intra_band_rows() : 1, band_done, h->d_progress + 1, after_gated_pmb ? h->d_row_done : nullptr, row_need ? row_need : h->pmb_rows_total,
-                                               fused_ip ? h->d_ip_strips : nullptr, fused_ip ? h->d_progress + 2 : nullptr, h->d_progress + 3, h->qpc_total, h->d_db_part, st);
+        unsigned *band_done = rec >= 0 ? h->d_db_done + (size_t)rec * (k_deblock_done_bytes() / sizeof(unsigned)) : nullptr; // (that many words per reconstruction buffer)
+        const int wgs = k_launch_deblock_bands(hc, h->mbh, 0, k_deblock_bands16(h->mbh), err_word(h), h->d_db_gran, h->d_db_par, p.db_follows_ip ? h->d_ip_progress : nullptr, p.isplit ? h->d_iband_done + (size_t)rec * h->mbh : nullptr,
+                                               h->cfg.intra_mode == 2 ? k_intra_band_rows() : 1, band_done, h->d_progress + 1, p.db_rows ? h->d_row_done : nullptr, h->pmb_rows_total,
+                                               p.fip ? h->d_ip_strips : nullptr, p.fip ? h->d_progress + 2 : nullptr, h->d_progress + 3, h->qpc_total, h->d_db_part, plan_stream(h, p.deblock));
         if (hc->qp_off) h->qpc_total += (uint32_t)h->mbh; // the QP_Y chain rides in the launch and counts the rows it has resolved
-        if (fused_ip) h->ip_done_total += (uint32_t)h->mbh;
+        if (p.fip) h->ip_done_total += (uint32_t)h->mbh;
         h->db_started_total += (unsigned)wgs; // (two per band, or four where every band is walked as two parts)
         HIPCHK(hipGetLastError());
         return 0;
@@ -115,40 +121,36 @@ static int run_p_front(mi355enc_t *h, const frame_ctx_t *hc, slot_t *s, int prof
     HIPCHK(hipGetLastError());
     return 0;
 }
-// ... and back part (back stream): needs the deblocked picture before it
-// gate: the reference picture's band-done words (the fused stage then runs on the intra stream, beside that picture's deblocking)
-// rows: the picture's deblocking launch will sit directly behind the previous one and wait on the device for this stage's rows (no event)
-static int run_p_back(mi355enc_t *h, const frame_ctx_t *hc, slot_t *s, int prof, int split, const unsigned *gate, unsigned ref_epoch, int rows, bool defer_ip = false) {
-    hipStream_t st = gate ? h->istream : h->stream;
+// ... and back part (the plan's back stream): needs the deblocked picture before it
+// p.pgate: gated on the reference picture's band-done words (the fused stage then runs on the intra stream, beside that picture's deblocking)
+// p.prows: the picture's deblocking launch will sit directly behind the previous one and wait on the device for this stage's rows (no event)
+static int run_p_back(mi355enc_t *h, const frame_ctx_t *hc, slot_t *s, int prof, const pic_plan_t &p) {
+    hipStream_t st = plan_stream(h, p.back);
+    const unsigned *gate = p.pgate ? h->d_db_done + (size_t)h->cur * (k_deblock_done_bytes() / sizeof(unsigned)) : nullptr;
     if (prof) HIPCHK(hipEventRecord(s->ev[8], st));
-    if (false) { // (the two-kernel form of the High-profile path: absolute-vector refinement, 8x8 transform, no skip / intra logic -- kept for reference, reached through the stage entry points only)
-        k_launch_imv_to_mbi(hc, h->mbw, 0, h->mbh, st);
-        if (h->cfg.subpel) k_launch_subpel(hc, h->mbw, 0, h->mbh, st);
-        if (prof) HIPCHK(hipEventRecord(s->ev[5], st));
-        k_launch_inter(hc, h->mbw, 0, h->mbh, st);
-    } else {
-        if (gate) k_launch_wait_started(h->d_progress + 1, h->db_started_total, err_word(h), st); // not before the reference's deblocking launch is on the chip
-        k_launch_pmb(hc, h->mbw, 0, h->mbh, h->cfg.subpel, gate, ref_epoch, err_word(h), rows ? h->d_row_done : nullptr, st);
-        if (prof) HIPCHK(hipEventRecord(s->ev[5], st));
-        if (gate) { // the main stream carries nothing but deblocking launches, back to back: this picture's bands wait on the device for the fused
-            if (rows) h->pmb_rows_total += (uint32_t)h->mbw; // stage's rows (row counts, no event between the streams), and its movers follow intra_p_kernel
-            else { HIPCHK(hipEventRecord(h->ev_pmb, st)); HIPCHK(hipStreamWaitEvent(h->stream, h->ev_pmb, 0)); } // (fewer than three pictures in flight: by event)
-            if (hc->intra_p && !defer_ip) k_launch_intra_p(hc, h->mbw, h->mbh, h->d_ip_progress, h->d_ip_strips, err_word(h), st); // (defer_ip: the caller enqueues the deblocking launch that carries them)
-        } else if (split) { // intra_p_kernel leaves the chain: prep + the band deblocker follow the fused stage directly and overtake it row by row
-            HIPCHK(hipEventRecord(h->ev_pmb, st));
-            HIPCHK(hipStreamWaitEvent(h->istream, h->ev_pmb, 0));
-            k_launch_intra_p(hc, h->mbw, h->mbh, h->d_ip_progress, h->d_ip_strips, err_word(h), h->istream);
-        } else if (hc->intra_p) k_launch_intra_p(hc, h->mbw, h->mbh, h->d_ip_progress, h->d_ip_strips, err_word(h), st);
-    }
+    if (gate) k_launch_wait_started(h->d_progress + 1, h->db_started_total, err_word(h), st); // not before the reference's deblocking launch is on the chip
+    k_launch_pmb(hc, h->mbw, 0, h->mbh, h->cfg.subpel, gate, h->rec_epoch[h->cur], err_word(h), p.prows ? h->d_row_done : nullptr, st);
+    if (prof) HIPCHK(hipEventRecord(s->ev[5], st));
+    if (gate) { // the main stream carries nothing but deblocking launches, back to back: this picture's bands wait on the device for the fused
+        if (p.prows) h->pmb_rows_total += (uint32_t)h->mbw; // stage's rows (row counts, no event between the streams), and its movers follow intra_p_kernel
+        else { HIPCHK(hipEventRecord(h->ev_pmb, st)); HIPCHK(hipStreamWaitEvent(h->stream, h->ev_pmb, 0)); } // (fewer than three pictures in flight: by event)
+        if (hc->intra_p && !p.fip) k_launch_intra_p(hc, h->mbw, h->mbh, h->d_ip_progress, h->d_ip_strips, err_word(h), st); // (fip: the deblocking launch carries the rows)
+    } else if (p.split) { // intra_p_kernel leaves the chain: prep + the band deblocker follow the fused stage directly and overtake it row by row
+        HIPCHK(hipEventRecord(h->ev_pmb, st));
+        HIPCHK(hipStreamWaitEvent(h->istream, h->ev_pmb, 0));
+        k_launch_intra_p(hc, h->mbw, h->mbh, h->d_ip_progress, h->d_ip_strips, err_word(h), h->istream);
+    } else if (hc->intra_p) k_launch_intra_p(hc, h->mbw, h->mbh, h->d_ip_progress, h->d_ip_strips, err_word(h), st);
     if (prof) HIPCHK(hipEventRecord(s->ev[11], st));
     HIPCHK(hipGetLastError());
     return 0;
 }
 
-// Enqueue every device step of one picture whose source is described by (src_y, src_uv, src_stride).  Anything the caller
-// uploaded for this picture was enqueued on the same stream.
-int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_t *src_uv, int src_stride, int64_t pts, int force_idr) {
-    if (!h->recovering) snapshot_latch(h, s); // stills: an armed request becomes this picture's (a picture recover() enqueues again keeps what it had)
+// ---- one picture: decide (host state) -> plan (enc_plan.hpp) -> enqueue from the plan -> book.  No decision is taken behind the picture's first launch.
+// what decide_picture() settles about a picture on the host
+struct pic_t { const uint8_t *src_y, *src_uv; int src_stride, idr, qp, drop, ir_j, all_skip, nxt, set, prof; }; // nxt: the reconstruction buffer it writes; set: its device set and context copy
+
+// Decide: IDR or P, rate control's pick, the position in the intra-refresh cycle, all-skip, buffers and device set, whether the stage timers are sampled
+static pic_t decide_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_t *src_uv, int src_stride, int force_idr) {
     const int idr = force_idr || !h->have_ref || (!h->ir_on && h->frames_since_idr >= h->cfg.gop) || // (intra refresh: no periodic IDR picture)
                     (h->n_submitted == h->sc_force_at && h->frames_since_idr >= sc_lag(h)); // scene-cut recovery, see collect(): not when an IDR picture came in between
     if (idr) { h->frames_since_idr = 0; h->ir_pos = 0; h->ir_R = 0; h->ir_skip_owed = 0; }
@@ -171,159 +173,162 @@ int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_
         else if (h->ir_skip_owed && !last) { drop = DROP_SKIP; h->ir_skip_owed = 0; }
     }
     const int all_skip = !idr && drop == DROP_SKIP;
-    const int nxt = all_skip ? h->cur : (h->cur ^ 1); // an all-skip picture IS its reference: nothing is written
-    const int set = (int)(h->n_submitted % NSET), ci = set;
-    frame_ctx_t *c = s->h_ctx, *dctx = h->d_ctx2[ci];
     // stage timers: an event record costs ~5 us of queue time, so profile_events = k samples every k-th picture (IDR pictures always)
     // (a sampled picture runs its stages strictly in order; IDR pictures: every other one, or at the P pictures' cadence in an all-intra stream)
     const int prof = !all_skip && h->cfg.profile_events > 0 &&
                      ((idr && h->cfg.gop > 1) ? (h->idr_count & 1) == 0 : h->n_submitted % (uint64_t)h->cfg.profile_events == 0);
-    const bool fused = true; // (r03: the High-profile stream goes through the fused stage too; the two-kernel form remains behind the single-stage entry points)
-    if (all_skip) {
-        // one run of P_Skip macroblocks with the zero vector (8.4.1.1 infers it: every neighbour's vector is zero): the host
-        // writes the records itself; no source sample is read, no kernel runs, the reference stays where it is
-        memset(s->h_mbi, 0, (size_t)h->nmb * sizeof(mb_info_t));
-        for (int i = 0; i < h->nmb; i++) { s->h_mbi[i].mb_type = 1; s->h_mbi[i].qp = (uint8_t)qp; }
-        s->h_hdr[0] = 0; s->h_hdr[1] = 0;
-        for (int r = 0; r < h->mbh; r++) s->h_hdr[2 + r] = 0;
-        s->h_hdr[2 + h->mbh] = s->h_hdr[3 + h->mbh] = 0;
-        if (h->d_pre_y) {
-            HIPCHK(hipMemcpyAsync(h->d_pre_y, h->d_rec_y[nxt], h->ysz, hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->d_pre_uv, h->d_rec_uv[nxt], h->csz, hipMemcpyDeviceToDevice, h->stream));
-        }
-        if (h->q_on) { // quality metrics: the picture repeats its reference, so that is what the source is measured against -- on the main stream, behind the reference's
-            // deblocking (an IDR picture's may have run on the intra stream) and behind the source's arrival on the front stream, which nothing else of this picture waits for
-            HIPCHK(hipEventRecord(s->ev_front, h->fstream));
-            HIPCHK(hipStreamWaitEvent(h->stream, s->ev_front, 0));
-            if (h->dbI_busy[nxt]) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_dbI[nxt], 0)); h->dbI_busy[nxt] = 0; }
-            int r = quality_enqueue(h, s, src_y, src_uv, src_stride, nxt, h->stream); if (r) return r;
-        }
-        if (s->snap && s->snap_req.what == 1) { // a still of what a decoder shows: the reference the picture repeats, behind that picture's deblocking
-            if (h->dbI_busy[nxt]) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_dbI[nxt], 0)); h->dbI_busy[nxt] = 0; }
-            int r = snapshot_enqueue(h, s, h->d_rec_y[nxt], h->d_rec_uv[nxt], h->W, h->stream); if (r) return r;
-        }
-    } else {
-        c->src_y = src_y; c->src_uv = src_uv; c->src_stride = src_stride;
-        c->ref_y = h->d_rec_y[h->cur]; c->ref_uv = h->d_rec_uv[h->cur];
-        c->rec_y = h->d_rec_y[nxt]; c->rec_uv = h->d_rec_uv[nxt];
-        c->vis_h = h->cfg.height;
-        fill_ctx(h, c, qp, drop, idr, set);
-        c->mbi = h->d_mbi_set[set]; c->levels = h->d_levels_set[set];
-        if (!idr && c->intra_p) { int r = ip_rows_stamp(h, c->epoch); if (r) return r; }
-        if (ir_j >= 0) {
-            const int R = h->ir_R;
-            c->ir_c0 = R > 0 ? R - 1 : 0; // (one column of overlap: deblocking left the last columns of column R - 1 dirty in the reference)
-            c->ir_c1 = (int)((long long)(ir_j + 1) * h->mbw / h->cfg.gop);
-            c->ir_clean = R > 0 ? 16 * R - 4 : -1;
-            h->ir_R = c->ir_c1;
-        }
-        // Every kernel of the default path takes the context by value; only the kernels replayed from a hipGraph
-        // (intra_mode 1, deblock_mode 1) read the device copy, so only those pictures pay for an upload.
-        if ((idr && h->cfg.intra_mode == 1) || h->cfg.deblock_mode != 0) HIPCHK(hipMemcpyAsync(dctx, c, sizeof *c, hipMemcpyHostToDevice, h->stream));
-        // front stream: the source is in place (upload / conversion were enqueued there); P pictures: search, selection, gated intra
-        // analysis; I pictures: only the padded source copy the next picture's search will run against
-        if (c->qp_off) k_launch_aq(c, h->d_qp_off[set], h->fstream); // adaptive quantisation: the offsets of this picture's macroblocks
-        // (r04 tried the IDR picture's open-loop analysis on the front stream as well -- it needs nothing but the source: all-intra 3 469 -> 3 463 frames/s, the flat analysis
-        // launch beside the previous picture's rows kernel slows that kernel by what it saves; not kept.)
-        if (idr) k_launch_copy_luma(c, h->fstream);
-        else { int r = run_p_front(h, c, s, prof); if (r) return r; }
-        HIPCHK(hipEventRecord(s->ev_front, h->fstream));
-        h->psrc_cur ^= 1;
-        // P picture with intra macroblocks: intra_p_kernel (a chain along rows, 10..80 us) and the band deblocker (a chain along
-        // x + y) overlap -- intra_p_kernel runs on a stream of its own and the deblocker's movers follow its per-row progress words
-        // (GATED, k_deblock.hip); the chain pmb -> prep -> deblocker -> next pmb stays on one stream (a cross-stream event on the
-        // chain costs 10-17 us).  Not on pictures whose stage timers are sampled (a gated launch's duration includes its waiting).
-        // Every kernel-waits-for-kernel overlap below is opt-in (cfg.exclusive_device): next to another process's kernels on the same GPU a
-        // kernel that waits on the device for a kernel that has not been placed yet can run into the bound of its wait.
-        const bool may_wait = overlap_allowed(h) && exclusive_device(h) && h->wait_room[idr ? 1 : 0] && h->cfg.deblock_mode == 0 && !h->d_pre_y && !(prof && (idr || !h->cfg.profile_overlap)) && !(h->cfg.aq_mode && h->cfg.intra_in_p == 2); // (adaptive quantisation: the QP_Y chain
-                                                                                                                                                    // over the whole picture sits between a picture's records and its deblocking)
-        const int split = !idr && fused && c->intra_p && may_wait;
-        // IDR picture: the band deblocker runs on the intra stream BESIDE the intra wavefront, each of its bands waiting for the intra bands
-        // of the same rows (flags + acquire); in an all-intra stream the next picture's wavefront then starts while this one is still
-        // being deblocked.  What has to wait for such a deblocking: a P picture (it reads the whole reference), and whoever writes
-        // the reconstruction buffer it works on (the picture after next).
-        // P picture whose reference is still being deblocked: the fused stage leaves the chain too.  It runs on the intra stream, each of
-        // its waves waiting for the reference's bands it reads (pmb_kernel<GATED>), so it is all but done when that deblocking ends.
-        const size_t nbd = k_deblock_done_bytes() / sizeof(unsigned); // words per reconstruction buffer
-        const int pgate = !idr && fused && may_wait && h->rec_epoch[h->cur] != 0 && h->pgate;
-        HIPCHK(hipStreamWaitEvent(pgate ? h->istream : h->stream, s->ev_front, 0));
-        // ... and with three pictures in flight (the next picture's front stages are done long before this launch ends) the deblocking launches go back
-        // to back, each waiting on the device for its picture's rows; with fewer the host sits on the chain and a launch waiting on the chip only
-        // gets in the way (1080p depth 1: 4465 -> 3980 frames/s, 2160p: 2050 -> 1615)
-        const int prows = pgate && h->cfg.pipeline_depth >= 2;
-        const int isplit = idr && h->cfg.intra_mode != 1 && may_wait;
-        // (Round 3 also built consecutive pictures' deblocking launches on two streams, the next picture's upper bands beside this one's lower
-        // ones: +2 % at 1080p, slower at 2160p, and a bounded wait that ran out in two of four runs without a cause found -- removed in round 4;
-        // what shortens the chain instead is slices with slice-local deblocking)
-        hipStream_t mst = h->stream;
-        bool fip = false;
-        for (int b = 0; b < 2; b++)
-            if (h->dbI_busy[b] && (!idr || b == nxt)) { HIPCHK(hipStreamWaitEvent(mst, h->ev_dbI[b], 0)); h->dbI_busy[b] = 0; }
-        if (idr) {
-            if (isplit) { HIPCHK(hipEventRecord(h->ev_pmb, h->stream)); HIPCHK(hipStreamWaitEvent(h->istream, h->ev_pmb, 0)); } // behind everything enqueued so far (a P picture's deblocker, its tables)
-            if (prof) HIPCHK(hipEventRecord(s->ev[0], h->stream));
-            int r = run_intra(h, ci, c, isplit ? h->d_iband_done + (size_t)nxt * h->mbh : nullptr); if (r) return r;
-            if (prof) HIPCHK(hipEventRecord(s->ev[1], h->stream));
-        } else {
-            // One launch in flight, the intra macroblock rows inside it: the rows no longer queue behind the END of pmb_kernel (stream order) -- each starts when pmb_kernel
-            // has completed its row and the row above, so the upper bands find them done when the launch starts.  Behind pmb_kernel in host order: nothing here waits for a
-            // kernel that is not on the chip or in front of it in its own stream.  Not on sampled pictures (the timers bracket the launches in stream order).
-            fip = prows && !c->qp_off && c->intra_p && !prof && h->fip_rows;
-            int r = run_p_back(h, c, s, prof, split, pgate ? h->d_db_done + (size_t)h->cur * nbd : nullptr, h->rec_epoch[h->cur], prows, fip); if (r) return r;
-            if (fip) {
-                r = run_deblock(h, ci, c, mst, h->d_ip_progress, nullptr, h->d_db_done + (size_t)nxt * nbd, true, h->pmb_rows_total, true); if (r) return r;
-                k_launch_wait_started(h->d_progress + 2, h->ip_done_total, err_word(h), h->istream); // records and levels are final once the rows have all counted themselves
-            }
-        }
-        if (prof) HIPCHK(hipEventRecord(s->ev[2], h->stream));
-        HIPCHK(hipGetLastError());
-        if (c->qp_off && h->cfg.deblock_mode != 0) k_launch_qp_chain(h->d_mbi_set[set], h->nmb, qp, c->slice_rows * h->mbw, h->stream); // 7.4.5: QP_Y of the macroblocks without mb_qp_delta, for the deblocker (everything runs on the main stream here)
-        HIPCHK(hipEventRecord(s->gpu_done, (split || pgate) ? h->istream : h->stream)); // records and levels are final here; they do not depend on deblocking
-        if (h->d_pre_y) {
-            HIPCHK(hipMemcpyAsync(h->d_pre_y, h->d_rec_y[nxt], h->ysz, hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->d_pre_uv, h->d_rec_uv[nxt], h->csz, hipMemcpyDeviceToDevice, h->stream));
-            if (prof) HIPCHK(hipEventRecord(s->ev[2], h->stream));
-        }
-        if (isplit) {
-            int r = run_deblock(h, ci, c, h->istream, nullptr, h->d_iband_done + (size_t)nxt * h->mbh, h->d_db_done + (size_t)nxt * nbd); if (r) return r;
-            if (h->q_on) { r = quality_enqueue(h, s, src_y, src_uv, src_stride, nxt, h->istream); if (r) return r; } // in front of the event the buffer's next writer waits for
-            if (s->snap && s->snap_req.what == 1) { r = snapshot_enqueue(h, s, h->d_rec_y[nxt], h->d_rec_uv[nxt], h->W, h->istream); if (r) return r; } // likewise
-            HIPCHK(hipEventRecord(h->ev_dbI[nxt], h->istream));
-            h->dbI_busy[nxt] = 1;
-        } else if (!fip) { int r = run_deblock(h, ci, c, mst, (split || (pgate && c->intra_p)) ? h->d_ip_progress : nullptr, nullptr, h->d_db_done + (size_t)nxt * nbd, prows != 0); if (r) return r; }
-        h->rec_epoch[nxt] = h->cfg.deblock_mode == 0 ? c->epoch : 0;
-        if (prof) { HIPCHK(hipEventRecord(s->ev[3], h->stream)); HIPCHK(hipEventRecord(s->ev[4], h->stream)); }
-        // Quality metrics: directly behind the picture's deblocking launch, on its stream.  Whatever writes this reconstruction buffer next (the picture after next) is
-        // either behind it in the main stream's order, or a gated fused P stage on the intra stream, which starts only when the deblocking launch of the picture
-        // between the two is on the chip -- a launch that sits behind this one in the main stream.
-        if (h->q_on && !isplit) { int r = quality_enqueue(h, s, src_y, src_uv, src_stride, nxt, mst); if (r) return r; }
-        // A still of the reconstruction sits in the same place, for the same reason; with metrics on, both launches sit there.
-        if (s->snap && s->snap_req.what == 1 && !isplit) { int r = snapshot_enqueue(h, s, h->d_rec_y[nxt], h->d_rec_uv[nxt], h->W, mst); if (r) return r; }
-        // Hand-over, enqueued after the deblocking launches so that it cannot be dispatched ahead of them: the device packs the non-zero
-        // blocks straight into the pinned host buffer while the band deblocker runs.
-        hipStream_t pst = h->cstream;
-        HIPCHK(hipStreamWaitEvent(h->cstream, s->gpu_done, 0));
-        k_launch_pack(h->d_mbi_set[set], h->d_levels_set[set], h->nmb, h->mbw, h->d_off, s->h_mbi, s->h_levels, s->h_hdr, err_word(h), pst);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(s->done, pst));
+    return {src_y, src_uv, src_stride, idr, qp, drop, ir_j, all_skip, all_skip ? h->cur : (h->cur ^ 1) /* an all-skip picture IS its reference: nothing is written */, (int)(h->n_submitted % NSET), prof};
+}
+// Plan: what plan_picture() is asked with
+static plan_in_t plan_inputs(const mi355enc_t *h, const pic_t &p) {
+    plan_in_t in;
+    in.idr = p.idr != 0; in.all_skip = p.all_skip != 0; in.prof = p.prof != 0;
+    in.pipeline_depth = h->cfg.pipeline_depth; in.intra_mode = h->cfg.intra_mode; in.deblock_mode = h->cfg.deblock_mode; in.aq_mode = h->cfg.aq_mode;
+    in.intra_in_p = h->cfg.intra_in_p; in.i4x4 = h->cfg.i4x4; in.profile_overlap = h->cfg.profile_overlap;
+    in.overlap_allowed = overlap_allowed(h); in.exclusive_device = exclusive_device(h); in.wait_room[0] = h->wait_room[0]; in.wait_room[1] = h->wait_room[1];
+    in.keep_prefilter = h->d_pre_y != nullptr; in.ref_flags = h->rec_epoch[h->cur] != 0; in.pgate = h->pgate; in.fip_rows = h->fip_rows;
+    return in;
+}
+// Enqueue, all-skip: one run of P_Skip macroblocks with the zero vector (8.4.1.1 infers it: every neighbour's vector is zero): the host
+// writes the records itself; no source sample is read, no kernel runs, the reference stays where it is
+static int enqueue_all_skip(mi355enc_t *h, slot_t *s, const pic_t &p) {
+    memset(s->h_mbi, 0, (size_t)h->nmb * sizeof(mb_info_t));
+    for (int i = 0; i < h->nmb; i++) { s->h_mbi[i].mb_type = 1; s->h_mbi[i].qp = (uint8_t)p.qp; }
+    s->h_hdr[0] = 0; s->h_hdr[1] = 0;
+    for (int r = 0; r < h->mbh; r++) s->h_hdr[2 + r] = 0;
+    s->h_hdr[2 + h->mbh] = s->h_hdr[3 + h->mbh] = 0;
+    if (h->d_pre_y) {
+        HIPCHK(hipMemcpyAsync(h->d_pre_y, h->d_rec_y[p.nxt], h->ysz, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->d_pre_uv, h->d_rec_uv[p.nxt], h->csz, hipMemcpyDeviceToDevice, h->stream));
     }
-    // A still of the coded source: on the front stream, where the source is in place, behind everything of this picture that runs there (it delays none of it);
-    // the source stays valid until the picture's collect() returns, and collect() waits for the still.
-    if (s->snap && s->snap_req.what == 0) { int r = snapshot_enqueue(h, s, src_y, src_uv, src_stride, h->fstream); if (r) return r; }
+    // The readers of the reconstruction (below) read the reference the picture repeats -- that is what the source is measured against, and what a decoder shows: on the main
+    // stream, behind the reference's deblocking (an IDR picture's may have run on the intra stream); the metrics also behind the source's arrival on the front stream, which
+    // nothing else of this picture waits for
+    if (h->q_on) { HIPCHK(hipEventRecord(s->ev_front, h->fstream)); HIPCHK(hipStreamWaitEvent(h->stream, s->ev_front, 0)); }
+    if ((h->q_on || (s->snap && s->snap_req.what == 1)) && h->dbI_busy[p.nxt]) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_dbI[p.nxt], 0)); h->dbI_busy[p.nxt] = 0; }
+    return 0;
+}
+// the picture's context: the host copy every kernel of the default path takes by value
+static int picture_ctx(mi355enc_t *h, frame_ctx_t *c, const pic_t &p) {
+    c->src_y = p.src_y; c->src_uv = p.src_uv; c->src_stride = p.src_stride;
+    c->ref_y = h->d_rec_y[h->cur]; c->ref_uv = h->d_rec_uv[h->cur];
+    c->rec_y = h->d_rec_y[p.nxt]; c->rec_uv = h->d_rec_uv[p.nxt];
+    c->vis_h = h->cfg.height;
+    fill_ctx(h, c, p.qp, p.drop, p.idr, p.set);
+    c->mbi = h->d_mbi_set[p.set]; c->levels = h->d_levels_set[p.set];
+    if (!p.idr && c->intra_p) { int r = ip_rows_stamp(h, c->epoch); if (r) return r; }
+    if (p.ir_j >= 0) {
+        const int R = h->ir_R;
+        c->ir_c0 = R > 0 ? R - 1 : 0; // (one column of overlap: deblocking left the last columns of column R - 1 dirty in the reference)
+        c->ir_c1 = (int)((long long)(p.ir_j + 1) * h->mbw / h->cfg.gop);
+        c->ir_clean = R > 0 ? 16 * R - 4 : -1;
+        h->ir_R = c->ir_c1;
+    }
+    return 0;
+}
+// Enqueue, front stream: the source is in place (upload / conversion were enqueued there); P pictures: search, selection, gated intra
+// analysis; I pictures: only the padded source copy the next picture's search will run against.  Then what the back stage has to wait for.
+static int enqueue_front(mi355enc_t *h, slot_t *s, const pic_t &p, const pic_plan_t &plan) {
+    frame_ctx_t *c = s->h_ctx;
+    { int r = picture_ctx(h, c, p); if (r) return r; }
+    if (plan.upload_ctx) HIPCHK(hipMemcpyAsync(h->d_ctx2[p.set], c, sizeof *c, hipMemcpyHostToDevice, h->stream));
+    if (c->qp_off) k_launch_aq(c, h->d_qp_off[p.set], h->fstream); // adaptive quantisation: the offsets of this picture's macroblocks
+    if (p.idr) k_launch_copy_luma(c, h->fstream);
+    else { int r = run_p_front(h, c, s, p.prof); if (r) return r; }
+    HIPCHK(hipEventRecord(s->ev_front, h->fstream));
+    h->psrc_cur ^= 1;
+    HIPCHK(hipStreamWaitEvent(plan_stream(h, plan.back), s->ev_front, 0));
+    for (int b = 0; b < 2; b++) // an IDR picture's deblocking on the intra stream: a P picture reads the whole reference, and whoever writes the buffer it works on waits too
+        if (h->dbI_busy[b] && (!p.idr || b == p.nxt)) { HIPCHK(hipStreamWaitEvent(h->stream, h->ev_dbI[b], 0)); h->dbI_busy[b] = 0; }
+    return 0;
+}
+// Enqueue, back stage of an IDR picture: the intra wavefront on the main stream (isplit: its bands publish their flags for the deblocker beside it)
+static int enqueue_idr(mi355enc_t *h, slot_t *s, const pic_t &p, const pic_plan_t &plan) {
+    if (plan.isplit) { HIPCHK(hipEventRecord(h->ev_pmb, h->stream)); HIPCHK(hipStreamWaitEvent(h->istream, h->ev_pmb, 0)); } // behind everything enqueued so far (a P picture's deblocker, its tables)
+    if (p.prof) HIPCHK(hipEventRecord(s->ev[0], h->stream));
+    int r = run_intra(h, p.set, s->h_ctx, plan.isplit ? h->d_iband_done + (size_t)p.nxt * h->mbh : nullptr); if (r) return r;
+    if (p.prof) HIPCHK(hipEventRecord(s->ev[1], h->stream));
+    return 0;
+}
+// ... of a P picture: the fused stage; fip: the deblocking launch follows at once, the intra macroblock rows inside it
+static int enqueue_p(mi355enc_t *h, slot_t *s, const pic_t &p, const pic_plan_t &plan) {
+    int r = run_p_back(h, s->h_ctx, s, p.prof, plan); if (r) return r;
+    if (plan.fip) {
+        r = run_deblock(h, p.set, s->h_ctx, plan, p.nxt); if (r) return r;
+        k_launch_wait_started(h->d_progress + 2, h->ip_done_total, err_word(h), h->istream); // records and levels are final once the rows have all counted themselves
+    }
+    return 0;
+}
+// Enqueue, behind the back stage: "records and levels are final", then the deblocking launch (unless the P stage carried it)
+static int enqueue_deblock(mi355enc_t *h, slot_t *s, const pic_t &p, const pic_plan_t &plan) {
+    const frame_ctx_t *c = s->h_ctx;
+    if (p.prof) HIPCHK(hipEventRecord(s->ev[2], h->stream));
+    HIPCHK(hipGetLastError());
+    if (c->qp_off && h->cfg.deblock_mode != 0) k_launch_qp_chain(h->d_mbi_set[p.set], h->nmb, p.qp, c->slice_rows * h->mbw, h->stream); // 7.4.5: QP_Y of the macroblocks without mb_qp_delta, for the deblocker (everything runs on the main stream here)
+    HIPCHK(hipEventRecord(s->gpu_done, plan_stream(h, plan.gpu_done))); // records and levels are final here; they do not depend on deblocking
+    if (h->d_pre_y) {
+        HIPCHK(hipMemcpyAsync(h->d_pre_y, h->d_rec_y[p.nxt], h->ysz, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->d_pre_uv, h->d_rec_uv[p.nxt], h->csz, hipMemcpyDeviceToDevice, h->stream));
+        if (p.prof) HIPCHK(hipEventRecord(s->ev[2], h->stream));
+    }
+    if (!plan.fip) { int r = run_deblock(h, p.set, c, plan, p.nxt); if (r) return r; }
+    if (p.prof) { HIPCHK(hipEventRecord(s->ev[3], h->stream)); HIPCHK(hipEventRecord(s->ev[4], h->stream)); } // (never an isplit picture: a sampled IDR picture may not wait)
+    return 0;
+}
+// Readers of the reconstruction: quality metrics and a still of what a decoder shows (DESIGN.md sections 12, 18), directly behind the picture's deblocking launch, on its
+// stream.  Whatever writes this reconstruction buffer next (the picture after next) is either behind them in the main stream's order, or a gated fused P stage on the intra
+// stream, which starts only when the deblocking launch of the picture between the two is on the chip -- a launch that sits behind this one in the main stream.  An isplit
+// picture's deblocking runs on the intra stream: the event the buffer's next writer waits for is recorded here, behind the readers.
+static int enqueue_rec_readers(mi355enc_t *h, slot_t *s, const pic_t &p, const pic_plan_t &plan) {
+    hipStream_t st = plan_stream(h, plan.deblock);
+    if (h->q_on) { int r = quality_enqueue(h, s, p.src_y, p.src_uv, p.src_stride, p.nxt, st); if (r) return r; }
+    if (s->snap && s->snap_req.what == 1) { int r = snapshot_enqueue(h, s, h->d_rec_y[p.nxt], h->d_rec_uv[p.nxt], h->W, st); if (r) return r; }
+    if (plan.isplit) { HIPCHK(hipEventRecord(h->ev_dbI[p.nxt], st)); h->dbI_busy[p.nxt] = 1; }
+    return 0;
+}
+// Hand-over, enqueued after the deblocking launches so that it cannot be dispatched ahead of them: the device packs the non-zero
+// blocks straight into the pinned host buffer while the band deblocker runs.
+static int enqueue_handover(mi355enc_t *h, slot_t *s, const pic_t &p) {
+    HIPCHK(hipStreamWaitEvent(h->cstream, s->gpu_done, 0));
+    k_launch_pack(h->d_mbi_set[p.set], h->d_levels_set[p.set], h->nmb, h->mbw, h->d_off, s->h_mbi, s->h_levels, s->h_hdr, err_word(h), h->cstream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(s->done, h->cstream));
+    return 0;
+}
+// Book: the picture on its slot, the handle moved on to the next one
+static void book_picture(mi355enc_t *h, slot_t *s, const pic_t &p, int64_t pts, int force_idr) {
+    if (!p.all_skip) h->rec_epoch[p.nxt] = h->cfg.deblock_mode == 0 ? s->h_ctx->epoch : 0; // the epoch the buffer's band-done words carry once its deblocking is through
     h->n_submitted++;
-    s->is_idr = idr; s->qp = qp; s->drop = drop; s->frame_num = h->frames_since_idr; s->idr_pic_id = h->idr_count & 0xFFFF; s->ir_start = ir_j == 0;
-    s->src_y = src_y; s->src_uv = src_uv; s->src_stride = src_stride; s->force_idr = force_idr;
-    s->pts = pts; s->rec_index = nxt; s->set = set; s->prof = prof; s->fused = fused && !idr; s->index = h->n_submitted - 1; s->all_skip = all_skip;
-    if (idr) h->idr_count++;
+    s->is_idr = p.idr; s->qp = p.qp; s->drop = p.drop; s->frame_num = h->frames_since_idr; s->idr_pic_id = h->idr_count & 0xFFFF; s->ir_start = p.ir_j == 0;
+    s->src_y = p.src_y; s->src_uv = p.src_uv; s->src_stride = p.src_stride; s->force_idr = force_idr;
+    s->pts = pts; s->rec_index = p.nxt; s->set = p.set; s->prof = p.prof; s->index = h->n_submitted - 1; s->all_skip = p.all_skip;
+    if (p.idr) h->idr_count++;
     h->frames_since_idr++;
-    if (ir_j >= 0) h->ir_pos = ir_j + 1 < h->cfg.gop ? ir_j + 1 : 0;
+    if (p.ir_j >= 0) h->ir_pos = p.ir_j + 1 < h->cfg.gop ? p.ir_j + 1 : 0;
     // intra refresh: no periodic IDR picture resets the count, so it is kept bounded; frame_num is sent modulo MaxFrameNum = 256 (h264_host.c), and the
     // count stays >= 256, past the scene-cut rule's sc_lag()
     if (h->ir_on && h->frames_since_idr >= 512) h->frames_since_idr -= 256;
-    h->cur = nxt; h->have_ref = 1; h->prev_slot = s;
-    const int slot_index = (int)(s - h->slot);
+    h->cur = p.nxt; h->have_ref = 1; h->prev_slot = s;
     h->head = (h->head + 1) % NSLOT; h->pending++;
-    if (h->wk_on) worker_push(h, slot_index);
+    if (h->wk_on) worker_push(h, (int)(s - h->slot));
+}
+
+// Enqueue every device step of one picture whose source is described by (src_y, src_uv, src_stride).  Anything the caller
+// uploaded for this picture was enqueued on the same stream.
+int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_t *src_uv, int src_stride, int64_t pts, int force_idr) {
+    if (!h->recovering) snapshot_latch(h, s); // stills: an armed request becomes this picture's (a picture recover() enqueues again keeps what it had)
+    const pic_t p = decide_picture(h, s, src_y, src_uv, src_stride, force_idr);
+    const pic_plan_t plan = plan_picture(plan_inputs(h, p)); // streams and device-side waits: all of them, before the first launch
+    int r = p.all_skip ? enqueue_all_skip(h, s, p) : enqueue_front(h, s, p, plan);
+    if (!r && !p.all_skip) r = p.idr ? enqueue_idr(h, s, p, plan) : enqueue_p(h, s, p, plan);
+    if (!r && !p.all_skip) r = enqueue_deblock(h, s, p, plan);
+    if (!r) r = enqueue_rec_readers(h, s, p, plan);
+    if (!r && !p.all_skip) r = enqueue_handover(h, s, p);
+    // A still of the coded source: on the front stream, where the source is in place, behind everything of this picture that runs there (it delays none of it);
+    // the source stays valid until the picture's collect() returns, and collect() waits for the still.
+    if (!r && s->snap && s->snap_req.what == 0) r = snapshot_enqueue(h, s, src_y, src_uv, src_stride, h->fstream);
+    if (r) return r;
+    book_picture(h, s, p, pts, force_idr);
     return MI355ENC_OK;
 }
 
@@ -443,6 +448,31 @@ static int recover(mi355enc_t *h, unsigned code) {
     return MI355ENC_OK;
 }
 
+// a sampled picture's stage timers into the statistics
+static int book_stage_timers(mi355enc_t *h, slot_t *s) {
+    float a = 0, b = 0, c = 0, tot = 0, sel = 0, an = 0, ip = 0;
+    HIPCHK(hipEventSynchronize(s->ev[4])); // the access unit is ready before deblocking ends; the stage timers are not
+    if (s->is_idr) { (void)hipEventElapsedTime(&a, s->ev[0], s->ev[1]); (void)hipEventElapsedTime(&tot, s->ev[0], s->ev[4]); }
+    else { // front-stream stages and back-stream stages are timed on their own streams; the picture's total is their sum
+        float fe = 0, be = 0;
+        (void)hipEventElapsedTime(&a, s->ev[0], s->ev[6]);
+        (void)hipEventElapsedTime(&sel, s->ev[6], s->ev[1]);
+        (void)hipEventElapsedTime(&an, s->ev[1], s->ev[7]);
+        (void)hipEventElapsedTime(&fe, s->ev[0], s->ev[7]);
+        (void)hipEventElapsedTime(&be, s->ev[8], s->ev[4]);
+        tot = fe + be;
+        (void)hipEventElapsedTime(&b, s->ev[8], s->ev[11]); b += an; (void)hipEventElapsedTime(&ip, s->ev[5], s->ev[11]); // analysis + fused stage + intra macroblocks, booked as inter
+        h->st.ms_select += sel; h->st.ms_analyse_p += an; h->st.ms_intra_p += ip;
+    }
+    (void)hipEventElapsedTime(&c, s->ev[2], s->ev[3]);
+    if (s->is_idr) { h->st.ms_intra += a; h->st.n_intra++; }
+    else { h->st.ms_me += a; h->st.n_me++; h->st.ms_inter += b; h->st.n_inter++; } // (ms_subpel stays 0: the refinement is part of the fused stage)
+    h->st.ms_deblock += c; h->st.n_deblock++;
+    if (s->is_idr) { h->st.ms_deblock_idr += c; h->st.n_deblock_idr++; }
+    h->st.ms_total_gpu += tot; h->st.n_total_gpu++;
+    return 0;
+}
+
 extern "C" {
 
 int mi355enc_collect(mi355enc_t *h, uint8_t *out, size_t out_cap, size_t *out_len, int *is_keyframe, int64_t *pts, int *qp) {
@@ -451,7 +481,7 @@ int mi355enc_collect(mi355enc_t *h, uint8_t *out, size_t out_cap, size_t *out_le
     HIPCHK(hipSetDevice(h->cfg.device_id));
     slot_t *s = &h->slot[h->tail];
     double t0 = now_ms();
-    size_t n = 0, m = 0;
+    size_t m = 0;
     if (h->wk_on) { // the worker codes the access unit; here it is only copied out
         for (int attempt = 0;; attempt++) {
             { std::unique_lock<std::mutex> g(h->wk_mu); h->wk_done_cv.wait(g, [&] { return s->au_state >= 2; }); }
@@ -484,11 +514,11 @@ int mi355enc_collect(mi355enc_t *h, uint8_t *out, size_t out_cap, size_t *out_le
     }
     if (h->q_on) { int r = quality_collect(h, s); if (r) return r; } // (a picture that came back through recover(): the re-encode's)
     if (s->snap) { int r = snapshot_collect(h, s); if (r) return r; } // an armed picture: its still becomes the one mi355enc_take_snapshot codes
-    *out_len = n + m;
+    *out_len = m;
     if (is_keyframe) *is_keyframe = s->is_idr || s->ir_start; // (intra refresh: a cycle's first picture is a recovery point)
     if (pts) *pts = s->pts;
     if (qp) *qp = s->qp;
-    if (s->rc_picked) rc_update(&h->rc, s->is_idr, s->qp, s->drop, n + m); // picks and updates stay paired: a picture coded at a fixed QP booked nothing
+    if (s->rc_picked) rc_update(&h->rc, s->is_idr, s->qp, s->drop, m); // picks and updates stay paired: a picture coded at a fixed QP booked nothing
     // Scene-cut recovery (cfg.scenecut; the oracle's orc_enc_frame applies the same rule): the summed cost of the picture's
     // macroblocks came with the hand-over.  The decision lands on picture index + 2, the first one not submitted yet whatever
     // the pipeline depth, and is skipped there if picture index + 1 turned out to be an IDR: the stream does not depend on
@@ -501,34 +531,9 @@ int mi355enc_collect(mi355enc_t *h, uint8_t *out, size_t out_cap, size_t *out_le
         h->sc_sum += cost; h->sc_cnt++;
     }
     h->sc_prev_skip = s->all_skip;
-    if (s->prof) {
-        float a = 0, b = 0, c = 0, tot = 0, sp = 0;
-        {
-            HIPCHK(hipEventSynchronize(s->ev[4])); // the access unit is ready before deblocking ends; the stage timers are not
-            float sel = 0, an = 0, ip = 0;
-            if (s->is_idr) { (void)hipEventElapsedTime(&a, s->ev[0], s->ev[1]); (void)hipEventElapsedTime(&tot, s->ev[0], s->ev[4]); }
-            else { // front-stream stages and back-stream stages are timed on their own streams; the picture's total is their sum
-                float fe = 0, be = 0;
-                (void)hipEventElapsedTime(&a, s->ev[0], s->ev[6]);
-                (void)hipEventElapsedTime(&sel, s->ev[6], s->ev[1]);
-                (void)hipEventElapsedTime(&an, s->ev[1], s->ev[7]);
-                (void)hipEventElapsedTime(&fe, s->ev[0], s->ev[7]);
-                (void)hipEventElapsedTime(&be, s->ev[8], s->ev[4]);
-                tot = fe + be;
-                if (s->fused) { (void)hipEventElapsedTime(&b, s->ev[8], s->ev[11]); b += an; (void)hipEventElapsedTime(&ip, s->ev[5], s->ev[11]); } // analysis + fused stage + intra macroblocks, booked as inter
-                else { (void)hipEventElapsedTime(&sp, s->ev[8], s->ev[5]); (void)hipEventElapsedTime(&b, s->ev[5], s->ev[11]); }
-                h->st.ms_select += sel; h->st.ms_analyse_p += an; h->st.ms_intra_p += ip;
-            }
-            (void)hipEventElapsedTime(&c, s->ev[2], s->ev[3]);
-        }
-        if (s->is_idr) { h->st.ms_intra += a; h->st.n_intra++; }
-        else { h->st.ms_me += a; h->st.n_me++; h->st.ms_inter += b; h->st.n_inter++; h->st.ms_subpel += sp; }
-        h->st.ms_deblock += c; h->st.n_deblock++;
-        if (s->is_idr) { h->st.ms_deblock_idr += c; h->st.n_deblock_idr++; }
-        h->st.ms_total_gpu += tot; h->st.n_total_gpu++;
-    }
-    h->st.frames++; h->st.idr_frames += s->is_idr; h->st.bytes += n + m;
-    h->st.last_qp = (uint32_t)s->qp; h->st.last_drop = (uint32_t)s->drop; h->n_skip_pictures += s->all_skip; h->st.last_bytes = (uint32_t)(n + m); h->st.target_bps = h->want_bps.load();
+    if (s->prof) { int r = book_stage_timers(h, s); if (r) return r; }
+    h->st.frames++; h->st.idr_frames += s->is_idr; h->st.bytes += m;
+    h->st.last_qp = (uint32_t)s->qp; h->st.last_drop = (uint32_t)s->drop; h->n_skip_pictures += s->all_skip; h->st.last_bytes = (uint32_t)m; h->st.target_bps = h->want_bps.load();
     h->last_slot = s; h->last_collected_rec = s->rec_index;
     h->ov_last_have = 1; h->ov_last_len = s->ov_len; if (s->ov_len) memcpy(h->ov_last, s->ov_text, (size_t)s->ov_len);
     image_collected(h, s);
