@@ -142,7 +142,7 @@ int mi355enc_open(const mi355enc_cfg_t *cfg, mi355enc_t **out) {
     h->q_on = false; h->q_have = false; h->d_qacc = nullptr; h->h_qres = nullptr; for (int i = 0; i < NSLOT; i++) h->ev_q[i] = nullptr; memset(&h->q_last, 0, sizeof h->q_last); memset(&h->q_tot, 0, sizeof h->q_tot);
     for (int i = 0; i < NSET; i++) { h->g_intra[i] = h->g_deblock[i] = nullptr; h->d_ctx2[i] = nullptr; h->d_surf[i] = nullptr; h->d_idec2[i] = nullptr; h->d_mbi_set[i] = nullptr; h->d_levels_set[i] = nullptr; h->d_qp_off[i] = nullptr; }
     h->prev_slot = nullptr;
-    h->d_ctx = nullptr; h->d_pre_y = h->d_pre_uv = nullptr; memset(h->d_imv, 0, sizeof h->d_imv); h->d_psrc[0] = h->d_psrc[1] = nullptr; h->psrc_cur = 0; h->fstream = nullptr; h->ustream = nullptr; h->d_ip_progress = nullptr; h->d_ip_strips = nullptr; h->epoch = 0; h->istream = nullptr; h->ev_pmb = nullptr; h->d_db_gran = nullptr; h->d_db_done = nullptr; h->rec_epoch[0] = h->rec_epoch[1] = 0; h->db_started_total = 0; h->ip_done_total = 0; h->d_row_done = nullptr; h->pmb_rows_total = 0; h->d_db_par = nullptr; h->d_db_part = nullptr; h->d_ib_gran = nullptr; h->d_iband_done = nullptr; h->ev_dbI[0] = h->ev_dbI[1] = nullptr; h->dbI_busy[0] = h->dbI_busy[1] = 0; h->d_progress = nullptr; h->d_off = nullptr; h->d_isad = nullptr; h->d_dbrec = nullptr; h->d_idec = nullptr;
+    h->d_ctx = nullptr; h->d_pre_y = h->d_pre_uv = nullptr; memset(h->d_imv, 0, sizeof h->d_imv); h->d_psrc[0] = h->d_psrc[1] = nullptr; h->psrc_cur = 0; h->fstream = nullptr; h->ustream = nullptr; h->d_ip_strips = nullptr; h->epoch = 0; h->istream = nullptr; h->ev_pmb = nullptr; h->d_db_gran = nullptr; h->d_db_par = nullptr; h->d_ib_gran = nullptr; h->ev_dbI[0] = h->ev_dbI[1] = nullptr; h->dbI_busy[0] = h->dbI_busy[1] = 0; h->d_off = nullptr; h->d_isad = nullptr; h->d_dbrec = nullptr; h->d_idec = nullptr;
     h->cstream = nullptr; h->d_mbi = nullptr; h->d_levels = nullptr;
     memset(&h->st, 0, sizeof h->st);
     h->want_bps.store(cfg->bitrate_bps ? cfg->bitrate_bps : 2048000);
@@ -159,7 +159,7 @@ int mi355enc_open(const mi355enc_cfg_t *cfg, mi355enc_t **out) {
         // pictures are coded in stream order; a quarter of the chip stays free otherwise.  The bound is the MI355X's, not the device's own count: on a partition of
         // the chip the launches of every size coded so far keep the schedule they have always had there.
         const int wgs_max = 256 - 256 / 4;
-        for (int idr = 0; idr < 2; idr++) h->wait_room[idr] = k_deblock_launch_wgs(h->mbw, h->mbh, idr, !idr && h->fip_rows) <= wgs_max;
+        for (int idr = 0; idr < 2; idr++) h->wait_room[idr] = wait_room_wgs(h->mbw, h->mbh, idr != 0, h->fip_rows) <= wgs_max;
     }
     for (int i = 0; i < NSET; i++) HIPCHK(hipMalloc((void **)&h->d_ctx2[i], sizeof(frame_ctx_t)));
     h->d_ctx = h->d_ctx2[0];
@@ -211,22 +211,11 @@ int mi355enc_open(const mi355enc_cfg_t *cfg, mi355enc_t **out) {
     HIPCHK(hipMalloc((void **)&h->d_dbrec, (size_t)h->nmb * 64));
     HIPCHK(hipMalloc((void **)&h->d_idec, (size_t)h->nmb * IDEC_BYTES + 16));
     h->d_idec2[0] = h->d_idec;
-    HIPCHK(hipMalloc((void **)&h->d_progress, 4 * sizeof(unsigned)));
-    HIPCHK(hipMemsetAsync(h->d_progress, 0, 4 * sizeof(unsigned), h->stream)); // the error word is sticky: only cleared here
+    { int r = h->words.alloc(h->mbh, h->stream); if (r) return r; }
     HIPCHK(hipMalloc((void **)&h->d_db_par, k_deblock_partab_bytes(h->mbw, h->mbh)));
-    if (!getenv("MI355ENC_NO_SPLIT")) { // (A/B switch, read once per encoder)
-        HIPCHK(hipMalloc((void **)&h->d_db_part, 6 * (size_t)k_deblock_bands16(h->mbh) * sizeof(unsigned))); // two counters and two {cut, epoch} granules per band
-        HIPCHK(hipMemsetAsync(h->d_db_part, 0, 6 * (size_t)k_deblock_bands16(h->mbh) * sizeof(unsigned), h->stream));
-    }
     HIPCHK(hipMalloc((void **)&h->d_ib_gran, (size_t)h->mbh * h->mbw * 8 * sizeof(uint2)));
     HIPCHK(hipMemsetAsync(h->d_ib_gran, 0, (size_t)h->mbh * h->mbw * 8 * sizeof(uint2), h->stream));
-    HIPCHK(hipMalloc((void **)&h->d_iband_done, 2 * (size_t)h->mbh * sizeof(unsigned))); // one word per macroblock row (intra_mode 2: per band), one set per reconstruction buffer: the next picture's wavefront runs beside this one's deblocking
-    HIPCHK(hipMemsetAsync(h->d_iband_done, 0, 2 * (size_t)h->mbh * sizeof(unsigned), h->stream));
     for (int i = 0; i < 2; i++) HIPCHK(hipEventCreateWithFlags(&h->ev_dbI[i], hipEventDisableTiming));
-    HIPCHK(hipMalloc((void **)&h->d_row_done, (size_t)h->mbh * MI355_PROG_STRIDE * sizeof(unsigned)));
-    HIPCHK(hipMemsetAsync(h->d_row_done, 0, (size_t)h->mbh * MI355_PROG_STRIDE * sizeof(unsigned), h->stream));
-    HIPCHK(hipMalloc((void **)&h->d_db_done, 2 * k_deblock_done_bytes()));
-    HIPCHK(hipMemsetAsync(h->d_db_done, 0, 2 * k_deblock_done_bytes(), h->stream)); // epoch 0 is never used
     HIPCHK(hipMalloc((void **)&h->d_db_gran, k_deblock_gran_bytes(h->mbw, h->mbh)));
     HIPCHK(hipMemsetAsync(h->d_db_gran, 0, k_deblock_gran_bytes(h->mbw, h->mbh), h->stream)); // epoch 0 is never used
     HIPCHK(hipMalloc((void **)&h->d_off, (size_t)h->nmb * sizeof(unsigned)));
@@ -240,8 +229,6 @@ int mi355enc_open(const mi355enc_cfg_t *cfg, mi355enc_t **out) {
         HIPCHK(hipMalloc((void **)&h->d_psrc[k], h->ysz + SURF_PAD));
         HIPCHK(hipMemsetAsync(h->d_psrc[k], 0, h->ysz + SURF_PAD, h->stream));
     }
-    HIPCHK(hipMalloc((void **)&h->d_ip_progress, (size_t)h->mbh * MI355_PROG_STRIDE * sizeof(unsigned)));
-    HIPCHK(hipMemsetAsync(h->d_ip_progress, 0, (size_t)h->mbh * MI355_PROG_STRIDE * sizeof(unsigned), h->stream)); // epoch-tagged: the epoch starts at 1
     HIPCHK(hipMalloc((void **)&h->d_ip_strips, (size_t)h->nmb * IP_STRIP_BYTES));
     HIPCHK(hipMemsetAsync(h->d_ip_strips, 0, (size_t)h->nmb * IP_STRIP_BYTES, h->stream)); // epoch-tagged granules: the epoch starts at 1
     if (cfg->keep_prefilter) {
@@ -345,14 +332,10 @@ void mi355enc_close(mi355enc_t *h) {
     if (h->d_isad) (void)hipFree(h->d_isad);
     if (h->d_dbrec) (void)hipFree(h->d_dbrec);
     if (h->d_idec) (void)hipFree(h->d_idec);
-    if (h->d_progress) (void)hipFree(h->d_progress);
+    h->words.release();
     if (h->d_db_gran) (void)hipFree(h->d_db_gran);
-    if (h->d_db_done) (void)hipFree(h->d_db_done);
-    if (h->d_row_done) (void)hipFree(h->d_row_done);
     if (h->d_db_par) (void)hipFree(h->d_db_par);
-    if (h->d_db_part) (void)hipFree(h->d_db_part);
     if (h->d_ib_gran) (void)hipFree(h->d_ib_gran);
-    if (h->d_iband_done) (void)hipFree(h->d_iband_done);
     for (int i = 0; i < 2; i++) if (h->ev_dbI[i]) (void)hipEventDestroy(h->ev_dbI[i]);
     if (h->d_off) (void)hipFree(h->d_off);
     scale_free(h);
@@ -368,7 +351,6 @@ void mi355enc_close(mi355enc_t *h) {
         if (h->d_qp_off[k]) (void)hipFree(h->d_qp_off[k]);
     }
     for (int k = 0; k < 2; k++) if (h->d_psrc[k]) (void)hipFree(h->d_psrc[k]);
-    if (h->d_ip_progress) (void)hipFree(h->d_ip_progress);
     if (h->d_ip_strips) (void)hipFree(h->d_ip_strips);
     for (int i = 0; i < NSET; i++) if (h->d_ctx2[i]) (void)hipFree(h->d_ctx2[i]);
     for (int i = 0; i < NSET; i++) { if (h->d_mbi_set[i]) (void)hipFree(h->d_mbi_set[i]); if (h->d_levels_set[i]) (void)hipFree(h->d_levels_set[i]); }
@@ -431,8 +413,14 @@ int mi355enc_fetch(mi355enc_t *h, int what, void *dst, size_t n) {
     case MI355ENC_FETCH_MBINFO: src = h->last_slot ? h->last_slot->h_mbi : nullptr; need = (size_t)h->nmb * sizeof(mb_info_t); host = true; break;
     case MI355ENC_FETCH_SCALE_TABLES: src = h->d_scale_tab; need = h->scale_tab_bytes; break;
     case MI355ENC_FETCH_LEVELS: src = h->last_slot ? h->d_levels_set[h->last_slot->set] : nullptr; need = (size_t)h->nmb * MB_LEVELS * 2; break; // dense, from HBM
-    case 102: src = h->d_db_part; need = h->d_db_part ? 6 * (size_t)k_deblock_bands16(h->mbh) * sizeof(unsigned) : 0; break; /* development: per band and plane the parts' counter, then {cut column, epoch} of the last launch */
-    case 103: src = h->d_progress; need = sizeof(unsigned); break; /* development: the sticky error word of bounded device-side waits (0: none ran out) */
+    /* development, the wait words (enc_sync.hpp), read with the compute streams idle: 102 per band and plane the parts' counter, then {cut column, epoch} of the last
+       launch; 103 the sticky error word of bounded device-side waits (0: none ran out); 104 the started, ip_done and qpc words, then every row's row_done word */
+    case 102: case 103: case 104: {
+        if (!h->words.fetch_bytes(what)) return MI355ENC_ERR_STATE;
+        if (n < h->words.fetch_bytes(what)) return MI355ENC_ERR_OVERFLOW;
+        int r = sync_compute(h);
+        return r ? r : h->words.fetch(what, dst);
+    }
     case 100: src = h->d_dbrec; need = (size_t)h->nmb * 64; break; /* development: deblocking records (cycle counters in -DD3_PROF builds) */
     case 101: src = h->d_isad; need = 1024; break;                 /* development: cycle counters of -DIB_PROF builds */
     default: return MI355ENC_ERR_ARG;

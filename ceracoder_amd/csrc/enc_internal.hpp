@@ -3,7 +3,8 @@
 //   enc_handle.cpp    open / close / setters / statistics / fetch
 //   enc_input.cpp     the input path: submit*, from the caller's picture to the slot's source surfaces (upload, conversion, the sequence around them)
 //   enc_schedule.cpp  the picture pipeline: the stream schedule of one picture, the entropy worker, recovery, collect
-//   enc_plan.hpp      ... and that schedule's decisions as a value: plan_picture(), plain C++ (included here)
+//   enc_plan.hpp      ... and that schedule's decisions as a value: plan_picture(), and the launches that follow from a plan: plan_launches(); plain C++ (included here)
+//   enc_sync.*        the words kernels wait on and the host's totals of them, under one owner: dev_words_t (mi355enc::words)
 //   enc_overlay.cpp   the text overlay: setters, latch, layout, launch
 //   enc_image.cpp    image layers: setters, latch, upload + prepare, blend launches, retirement
 //   enc_orient.cpp    orientation of the input picture: setter, the slot's pre-orientation picture, launch, its stage entry points
@@ -33,6 +34,7 @@
 #include "snapshot_host.h"
 #include "hdr_host.h"
 #include "enc_plan.hpp"
+#include "enc_sync.hpp"
 
 #define HIPCHK(expr)                                                                                 \
     do {                                                                                             \
@@ -135,20 +137,11 @@ struct mi355enc {
     uint8_t *d_idec;      // intra decisions, IDEC_BYTES per macroblock
     uint16_t *d_isad;     // intra analysis SADs, ISAD_PER_MB u16 per macroblock
     uint2 *d_ib_gran;     // the intra band kernel's bottom lines between bands (tagged granules)
-    unsigned *d_iband_done; // ... and its per-band completion flags (the band deblocker's gate on IDR pictures)
     hipEvent_t ev_dbI[2];  // [reconstruction buffer]: the deblocking of an IDR picture that ran beside its intra wavefront on the intra stream has finished
     int dbI_busy[2];
     unsigned *d_db_par;   // the band deblocker's table of per-edge parameter words (written by its prologue, read by its movers)
-    unsigned *d_db_part;  // ... and, per band and plane, the count of band parts that have finished (P pictures walk every band as two workgroups: k_deblock.hip, "the cut"); null: bands are walked whole (MI355ENC_NO_SPLIT)
-    unsigned *d_db_done;  // per reconstruction buffer: one word per band and plane, = the epoch of the picture whose deblocking of that band is complete
-    unsigned *d_row_done;      // per macroblock row: macroblocks the gated P-stage launches have completed so far (the picture's deblocking launch waits for its rows)
-    uint32_t pmb_rows_total;   // ... and what each of those counts reaches with the last gated launch enqueued
-    uint32_t db_started_total; // workgroups of all band-deblocking launches so far (the device counts them as they are placed: d_progress[1])
-    uint32_t qpc_total;        // macroblock rows whose QP_Y chain the deblocking launches have resolved so far (adaptive quantisation; the device counts them: d_progress[3])
-    uint32_t ip_done_total;    // intra macroblock rows of all fused launches so far (the device counts them as they complete: d_progress[2])
-    uint32_t rec_epoch[2]; // ... and the epoch those words carry once the buffer's picture is done (0: no flags for it)
+    dev_words_t words;    // every word a kernel waits on, with the host's totals (enc_sync.hpp; the table: DESIGN.md section 5, "The wait words")
     uint2 *d_db_gran;     // strips between deblocking bands, as epoch-tagged granules (never cleared)
-    unsigned *d_progress; // [0] the sticky error word of the persistent kernels (bounded spins report here), [1] workgroups of band-deblocking launches placed
     unsigned *d_off;      // per-macroblock block offsets of the packed stream (scan kernel -> pack kernel)
     uint16_t *d_surf[NSET]; // SAD surfaces of the motion search, SURF_U16 per macroblock; one set per picture in flight: the front stages of picture n+1 (n+2) run beside the back stages of n
     imv_t *d_imv[NSET][3];   // whole-sample vector fields (search result / selection iterations alternate), per set
@@ -156,9 +149,7 @@ struct mi355enc {
     int8_t *d_qp_off[NSET];  // adaptive quantisation: QP offset per macroblock, per set (null unless cfg.aq_mode)
     uint8_t *d_psrc[2];   // padded source luma of the last two coded pictures: the search runs source against source
     int psrc_cur;         // which of them holds the last coded picture
-    unsigned *d_ip_progress; // intra macroblocks of P pictures: one progress word per macroblock row (epoch-tagged, never cleared)
-    uint8_t *d_ip_strips;    // ... and the bottom lines they publish for the row below, 32 bytes per macroblock
-    uint32_t ip_epoch = 0;   // ... and the epoch of the last launch that wrote those words (0: none since they were cleared): ip_rows_stamp()
+    uint8_t *d_ip_strips;    // intra macroblocks of P pictures: the bottom lines they publish for the row below, IP_STRIP_BYTES per macroblock
     uint32_t epoch;
     int islice_rows, stage_slice_rows;   // rows per slice of an I picture (cfg.intra_slices; 0: one slice) / what the single-stage entry points use
     int pslice_rows, slice_dbf, stage_slice_dbf; // ... of a P picture (cfg.slices); disable_deblocking_filter_idc of every slice (cfg.slice_deblock: 0 or 2) / of the single-stage entry points
@@ -291,7 +282,6 @@ static inline double now_ms() {
     using namespace std::chrono;
     return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
-static inline unsigned *err_word(const mi355enc_t *h) { return h->d_progress; }
 
 // enc_handle.cpp
 extern std::atomic<int> g_open_encoders;
@@ -303,9 +293,9 @@ int sync_compute(mi355enc_t *h);
 bool host_range_pinned(const void *p, size_t bytes); // inside memory handed out by mi355enc_host_alloc()
 // enc_schedule.cpp
 int run_intra(mi355enc_t *h, int ci, const frame_ctx_t *hc, unsigned *band_done = nullptr);
+int run_pmb(mi355enc_t *h, const frame_ctx_t *hc, int refine, const pic_plan_t &plan, hipStream_t st); // the fused P stage as the plan gates it, booked (the default plan: in order)
 int run_deblock(mi355enc_t *h, int ci, const frame_ctx_t *hc, const pic_plan_t &plan = pic_plan_t(), int rec = -1); // (the defaults: in order on the main stream, no band-done words)
 void fill_ctx(mi355enc_t *h, frame_ctx_t *c, int qp, int drop, int idr, int set = 0);
-int ip_rows_stamp(mi355enc_t *h, uint32_t epoch); // in front of every launch of a P picture's intra macroblock rows
 int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_t *src_uv, int src_stride, int64_t pts, int force_idr);
 void entropy_worker(mi355enc_t *h);
 // enc_input.cpp

@@ -3,6 +3,7 @@
 // plan_driver.cpp and holds the result against tests/planref.py.  The flags as a table: DESIGN.md section 5, "The plan of a picture".
 #ifndef MI355_ENC_PLAN_HPP
 #define MI355_ENC_PLAN_HPP
+#include "mi355enc_dev.h" // (its plain C part: db_variant_t, pmb_gate_t, db_launch_wgs(), DB_CUT_MIN_MBW)
 
 enum plan_stream_t { PS_MAIN, PS_FRONT, PS_INTRA, PS_HANDOVER }; // mi355enc::stream / fstream / istream / cstream
 
@@ -72,5 +73,35 @@ inline pic_plan_t plan_picture(const plan_in_t &in) {
     p.db_follows_ip = p.split || (p.pgate && intra_p);
     p.db_rows = p.prows;
     return p;
+}
+
+// ---- the picture's two launches that wait on the device, as they follow from its plan: which kernel, how many workgroups, and what the launches add to the
+// counts that device and host keep in step (enc_sync.hpp: dev_words_t::book).  run_p_back() and run_deblock() fill pmb_launch_t / db_launch_t from here.
+struct launch_counts_t { uint32_t rows = 0, started = 0, ip_done = 0, qpc = 0; }; // per row of row_done; the started, ip_done and qpc words
+struct launch_shape_t {
+    db_variant_t db; bool parts, qpc; // the deblocking launch: db_launch_t's variant, parts and qpc
+    pmb_gate_t gate;                  // the fused P stage's gate (P pictures)
+    int grid;                         // workgroups of the deblocking launch
+    launch_counts_t inc;
+};
+// idr: frame_ctx_t::all_intra; qp_off: frame_ctx_t::qp_off is present; part_words: the handle has the parts' words (k_deblock_part_bytes(), MI355ENC_NO_SPLIT)
+inline launch_shape_t plan_launches(const pic_plan_t &p, bool idr, bool qp_off, bool part_words, int mbw, int mbh) {
+    launch_shape_t l;
+    l.db = idr ? DB_ALL_INTRA : p.fip ? DB_P_FUSED_IP : p.db_follows_ip ? DB_P_FOLLOWS_IP : DB_P;
+    l.parts = !idr && mbw >= DB_CUT_MIN_MBW && part_words; // P pictures walk every band as two workgroups (k_deblock.hip: the cut)
+    l.qpc = qp_off;                                        // the QP_Y chain rides in the launch and counts the rows it has resolved
+    l.gate = p.prows ? PMB_GATED_ROWS : p.pgate ? PMB_GATED : PMB_IN_ORDER;
+    const db_wgs_t w = db_launch_wgs(mbh, l.db, l.parts, l.qpc);
+    l.grid = w.grid;
+    l.inc.rows = p.prows ? (uint32_t)mbw : 0u; // the picture's deblocking launch waits for its rows
+    l.inc.started = (uint32_t)w.counted;
+    l.inc.ip_done = p.fip ? (uint32_t)mbh : 0u;
+    l.inc.qpc = qp_off ? (uint32_t)mbh : 0u;
+    return l;
+}
+// open()'s wait_room: the workgroups of a picture's deblocking launch at its largest -- a P picture's bands in two parts wherever rows are long enough (whether
+// the handle has the parts' words or not), its intra rows inside wherever fip_rows allows; the QP_Y chain's one small workgroup is not counted
+inline int wait_room_wgs(int mbw, int mbh, bool idr, bool fip_rows) {
+    return db_launch_wgs(mbh, idr ? DB_ALL_INTRA : fip_rows ? DB_P_FUSED_IP : DB_P, !idr && mbw >= DB_CUT_MIN_MBW, 0).grid;
 }
 #endif

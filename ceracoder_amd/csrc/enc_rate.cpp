@@ -73,6 +73,7 @@ int mi355enc_set_rate_conversion(mi355enc_t *h, const mi355enc_rate_t *r) {
     if (h->rate.mode == 2 || (h->rate.mode == 1 && h->rate.max_fill > 0)) {
         HIPCHK(hipMalloc((void **)&h->d_keep, h->ysz + h->csz));
         HIPCHK(hipMemset(h->d_keep, 0, h->ysz + h->csz)); // (the first picture's mix has w = 256: whatever a holds does not show, but it is read)
+        HIPCHK(hipStreamSynchronize(nullptr));            // the fill runs on the null stream, which the handle's streams do not wait for: through before the first launch that touches the buffer is enqueued
     }
     return MI355ENC_OK;
 }

@@ -35,8 +35,8 @@ static int build_graph(mi355enc_t *h, int which, int ci, hipGraphExec_t *out) {
 int run_intra(mi355enc_t *h, int ci, const frame_ctx_t *hc, unsigned *band_done) {
     k_launch_intra_analyse(hc, h->mbw, h->mbh, 0, h->stream); // open-loop mode analysis + decisions: one flat launch
     if (h->cfg.intra_mode == 0 || h->cfg.intra_mode == 2) { // one persistent launch: dataflow per macroblock row (0) / the lock-step band kernel (2, kept for A/B)
-        if (h->cfg.intra_mode == 0) k_launch_intra_rows(hc, h->mbh, h->d_ib_gran, err_word(h), band_done, h->stream);
-        else k_launch_intra_band(hc, h->mbh, h->d_ib_gran, err_word(h), band_done, h->stream);
+        if (h->cfg.intra_mode == 0) k_launch_intra_rows(hc, h->mbh, h->d_ib_gran, h->words.err(), band_done, h->stream);
+        else k_launch_intra_band(hc, h->mbh, h->d_ib_gran, h->words.err(), band_done, h->stream);
         HIPCHK(hipGetLastError());
         return 0;
     }
@@ -51,13 +51,18 @@ static hipStream_t plan_stream(const mi355enc_t *h, plan_stream_t which) { retur
 // launch waits for on the device (the stage entry points: the in-order plan); rec: the reconstruction buffer whose band-done words the launch publishes (-1: none)
 int run_deblock(mi355enc_t *h, int ci, const frame_ctx_t *hc, const pic_plan_t &p, int rec) {
     if (h->cfg.deblock_mode == 0) { // the persistent band kernel (its prologue derives the boundary strengths from the records)
-        unsigned *band_done = rec >= 0 ? h->d_db_done + (size_t)rec * (k_deblock_done_bytes() / sizeof(unsigned)) : nullptr; // (that many words per reconstruction buffer)
-        const int wgs = k_launch_deblock_bands(hc, h->mbh, 0, k_deblock_bands16(h->mbh), err_word(h), h->d_db_gran, h->d_db_par, p.db_follows_ip ? h->d_ip_progress : nullptr, p.isplit ? h->d_iband_done + (size_t)rec * h->mbh : nullptr,
-                                               h->cfg.intra_mode == 2 ? k_intra_band_rows() : 1, band_done, h->d_progress + 1, p.db_rows ? h->d_row_done : nullptr, h->pmb_rows_total,
-                                               p.fip ? h->d_ip_strips : nullptr, p.fip ? h->d_progress + 2 : nullptr, h->d_progress + 3, h->qpc_total, h->d_db_part, plan_stream(h, p.deblock));
-        if (hc->qp_off) h->qpc_total += (uint32_t)h->mbh; // the QP_Y chain rides in the launch and counts the rows it has resolved
-        if (p.fip) h->ip_done_total += (uint32_t)h->mbh;
-        h->db_started_total += (unsigned)wgs; // (two per band, or four where every band is walked as two parts)
+        const dev_words_t &w = h->words;
+        const launch_shape_t shape = plan_launches(p, hc->all_intra != 0, hc->qp_off != nullptr, w.part_cnt() != nullptr, h->mbw, h->mbh);
+        db_launch_t l;
+        l.variant = shape.db; l.parts = shape.parts; l.qpc = shape.qpc; l.ib_rows = h->cfg.intra_mode == 2 ? k_intra_band_rows() : 1;
+        l.err = w.err(); l.gran = h->d_db_gran; l.partab = h->d_db_par;
+        l.band_done = rec >= 0 ? w.band_done(rec) : nullptr; l.started = w.started().word;
+        l.iband_done = p.isplit ? w.iband_done(rec) : nullptr;
+        l.row_done = p.db_rows ? w.row_done().word : nullptr; l.row_need = w.row_done().total;
+        l.ip_progress = w.ip_progress(); l.ip_strips = h->d_ip_strips; l.ip_done = w.ip_done().word;
+        l.qpc_word = w.qpc().word; l.qpc_base = w.qpc().total; l.part_cnt = w.part_cnt();
+        if (k_launch_deblock_bands(hc, &l, plan_stream(h, p.deblock))) return MI355ENC_ERR_ARG;
+        h->words.book({0, shape.inc.started, shape.inc.ip_done, shape.inc.qpc}); // (the rows were booked with the fused P stage: run_pmb)
         HIPCHK(hipGetLastError());
         return 0;
     }
@@ -95,26 +100,27 @@ void fill_ctx(mi355enc_t *h, frame_ctx_t *c, int qp, int drop, int idr, int set)
     c->intra_p = h->cfg.intra_in_p ? (h->cfg.i4x4 && h->cfg.intra_in_p > 1 ? 2 : 1) : 0; // 2: Intra_4x4 as well
     c->ir_c0 = 0; c->ir_c1 = 0; c->ir_clean = -1; // (enqueue_picture sets the refresh columns of a picture of an intra-refresh stream)
 }
-// The progress words of a P picture's intra macroblock rows carry 20 bits of the epoch (IP_EPOCH, intra_mb.hpp).  Every launch of the rows rewrites every row's
-// word, so the words are those of the last launch, and a launch's deblocker can take a stale word for its own picture's only when that launch was a multiple of
-// 2^20 epochs ago with no launch of the rows in between: a run of IDR pictures (force_idr, or stage calls, which stamp epochs of their own) of 4 h 51 min at 60
-// pictures/s, then a P picture.  There the words are cleared first (a zero word reports no macroblock final under any tag).  No launch that reads or writes them
-// is in flight then: a picture in flight is at most three epochs old.
-int ip_rows_stamp(mi355enc_t *h, uint32_t epoch) {
-    if (h->ip_epoch && h->ip_epoch != epoch && ((h->ip_epoch ^ epoch) & 0xFFFFFu) == 0) {
-        HIPCHK(hipMemsetAsync(h->d_ip_progress, 0, (size_t)h->mbh * MI355_PROG_STRIDE * sizeof(unsigned), h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream)); // (whichever stream carries the rows and their deblocker: behind this)
-    }
-    h->ip_epoch = epoch;
+// The fused P stage as the plan gates it: gated on the reference picture's band-done words, behind wait_started_kernel (not before the reference's deblocking
+// launch is on the chip); with rows, every macroblock counted for the picture's own deblocking launch
+int run_pmb(mi355enc_t *h, const frame_ctx_t *hc, int refine, const pic_plan_t &p, hipStream_t st) {
+    const dev_words_t &w = h->words;
+    const launch_shape_t shape = plan_launches(p, false, hc->qp_off != nullptr, w.part_cnt() != nullptr, h->mbw, h->mbh);
+    pmb_launch_t l;
+    l.gate = shape.gate; l.refine = refine; l.err = w.err();
+    l.gate_done = shape.gate != PMB_IN_ORDER ? w.band_done(h->cur) : nullptr; l.ref_epoch = w.rec_epoch(h->cur);
+    l.row_done = shape.gate == PMB_GATED_ROWS ? w.row_done().word : nullptr;
+    if (shape.gate != PMB_IN_ORDER) k_launch_wait_started(w.started().word, w.started().total, w.err(), st);
+    if (k_launch_pmb(hc, h->mbw, &l, st)) return MI355ENC_ERR_ARG;
+    h->words.book({shape.inc.rows, 0, 0, 0});
     return 0;
 }
 // P picture, front part (front stream): nothing here depends on the coding of the picture before
 static int run_p_front(mi355enc_t *h, const frame_ctx_t *hc, slot_t *s, int prof) {
     hipStream_t st = h->fstream;
     if (prof) HIPCHK(hipEventRecord(s->ev[0], st));
-    k_launch_me(hc, h->mbw, 0, h->mbh, st);
+    k_launch_me(hc, h->mbw, st);
     if (prof) HIPCHK(hipEventRecord(s->ev[6], st));
-    k_launch_me_select_all(hc, h->mbw, 0, h->mbh, st);
+    k_launch_me_select_all(hc, h->mbw, st);
     if (prof) HIPCHK(hipEventRecord(s->ev[1], st));
     if (hc->intra_p) k_launch_intra_analyse(hc, h->mbw, h->mbh, 1, st);
     if (prof) HIPCHK(hipEventRecord(s->ev[7], st));
@@ -126,20 +132,19 @@ static int run_p_front(mi355enc_t *h, const frame_ctx_t *hc, slot_t *s, int prof
 // p.prows: the picture's deblocking launch will sit directly behind the previous one and wait on the device for this stage's rows (no event)
 static int run_p_back(mi355enc_t *h, const frame_ctx_t *hc, slot_t *s, int prof, const pic_plan_t &p) {
     hipStream_t st = plan_stream(h, p.back);
-    const unsigned *gate = p.pgate ? h->d_db_done + (size_t)h->cur * (k_deblock_done_bytes() / sizeof(unsigned)) : nullptr;
+    unsigned *const ip_progress = h->words.ip_progress();
     if (prof) HIPCHK(hipEventRecord(s->ev[8], st));
-    if (gate) k_launch_wait_started(h->d_progress + 1, h->db_started_total, err_word(h), st); // not before the reference's deblocking launch is on the chip
-    k_launch_pmb(hc, h->mbw, 0, h->mbh, h->cfg.subpel, gate, h->rec_epoch[h->cur], err_word(h), p.prows ? h->d_row_done : nullptr, st);
+    { int r = run_pmb(h, hc, h->cfg.subpel, p, st); if (r) return r; }
     if (prof) HIPCHK(hipEventRecord(s->ev[5], st));
-    if (gate) { // the main stream carries nothing but deblocking launches, back to back: this picture's bands wait on the device for the fused
-        if (p.prows) h->pmb_rows_total += (uint32_t)h->mbw; // stage's rows (row counts, no event between the streams), and its movers follow intra_p_kernel
-        else { HIPCHK(hipEventRecord(h->ev_pmb, st)); HIPCHK(hipStreamWaitEvent(h->stream, h->ev_pmb, 0)); } // (fewer than three pictures in flight: by event)
-        if (hc->intra_p && !p.fip) k_launch_intra_p(hc, h->mbw, h->mbh, h->d_ip_progress, h->d_ip_strips, err_word(h), st); // (fip: the deblocking launch carries the rows)
+    if (p.pgate) { // the main stream carries nothing but deblocking launches, back to back: with prows this picture's bands wait on the device for the fused
+        // stage's rows (row counts, no event between the streams), and its movers follow intra_p_kernel
+        if (!p.prows) { HIPCHK(hipEventRecord(h->ev_pmb, st)); HIPCHK(hipStreamWaitEvent(h->stream, h->ev_pmb, 0)); } // (fewer than three pictures in flight: by event)
+        if (hc->intra_p && !p.fip) k_launch_intra_p(hc, h->mbw, h->mbh, ip_progress, h->d_ip_strips, h->words.err(), st); // (fip: the deblocking launch carries the rows)
     } else if (p.split) { // intra_p_kernel leaves the chain: prep + the band deblocker follow the fused stage directly and overtake it row by row
         HIPCHK(hipEventRecord(h->ev_pmb, st));
         HIPCHK(hipStreamWaitEvent(h->istream, h->ev_pmb, 0));
-        k_launch_intra_p(hc, h->mbw, h->mbh, h->d_ip_progress, h->d_ip_strips, err_word(h), h->istream);
-    } else if (hc->intra_p) k_launch_intra_p(hc, h->mbw, h->mbh, h->d_ip_progress, h->d_ip_strips, err_word(h), st);
+        k_launch_intra_p(hc, h->mbw, h->mbh, ip_progress, h->d_ip_strips, h->words.err(), h->istream);
+    } else if (hc->intra_p) k_launch_intra_p(hc, h->mbw, h->mbh, ip_progress, h->d_ip_strips, h->words.err(), st);
     if (prof) HIPCHK(hipEventRecord(s->ev[11], st));
     HIPCHK(hipGetLastError());
     return 0;
@@ -186,7 +191,7 @@ static plan_in_t plan_inputs(const mi355enc_t *h, const pic_t &p) {
     in.pipeline_depth = h->cfg.pipeline_depth; in.intra_mode = h->cfg.intra_mode; in.deblock_mode = h->cfg.deblock_mode; in.aq_mode = h->cfg.aq_mode;
     in.intra_in_p = h->cfg.intra_in_p; in.i4x4 = h->cfg.i4x4; in.profile_overlap = h->cfg.profile_overlap;
     in.overlap_allowed = overlap_allowed(h); in.exclusive_device = exclusive_device(h); in.wait_room[0] = h->wait_room[0]; in.wait_room[1] = h->wait_room[1];
-    in.keep_prefilter = h->d_pre_y != nullptr; in.ref_flags = h->rec_epoch[h->cur] != 0; in.pgate = h->pgate; in.fip_rows = h->fip_rows;
+    in.keep_prefilter = h->d_pre_y != nullptr; in.ref_flags = h->words.rec_epoch(h->cur) != 0; in.pgate = h->pgate; in.fip_rows = h->fip_rows;
     return in;
 }
 // Enqueue, all-skip: one run of P_Skip macroblocks with the zero vector (8.4.1.1 infers it: every neighbour's vector is zero): the host
@@ -216,7 +221,7 @@ static int picture_ctx(mi355enc_t *h, frame_ctx_t *c, const pic_t &p) {
     c->vis_h = h->cfg.height;
     fill_ctx(h, c, p.qp, p.drop, p.idr, p.set);
     c->mbi = h->d_mbi_set[p.set]; c->levels = h->d_levels_set[p.set];
-    if (!p.idr && c->intra_p) { int r = ip_rows_stamp(h, c->epoch); if (r) return r; }
+    if (!p.idr && c->intra_p) { int r = h->words.ip_rows_stamp(c->epoch, h->stream); if (r) return r; }
     if (p.ir_j >= 0) {
         const int R = h->ir_R;
         c->ir_c0 = R > 0 ? R - 1 : 0; // (one column of overlap: deblocking left the last columns of column R - 1 dirty in the reference)
@@ -246,7 +251,7 @@ static int enqueue_front(mi355enc_t *h, slot_t *s, const pic_t &p, const pic_pla
 static int enqueue_idr(mi355enc_t *h, slot_t *s, const pic_t &p, const pic_plan_t &plan) {
     if (plan.isplit) { HIPCHK(hipEventRecord(h->ev_pmb, h->stream)); HIPCHK(hipStreamWaitEvent(h->istream, h->ev_pmb, 0)); } // behind everything enqueued so far (a P picture's deblocker, its tables)
     if (p.prof) HIPCHK(hipEventRecord(s->ev[0], h->stream));
-    int r = run_intra(h, p.set, s->h_ctx, plan.isplit ? h->d_iband_done + (size_t)p.nxt * h->mbh : nullptr); if (r) return r;
+    int r = run_intra(h, p.set, s->h_ctx, plan.isplit ? h->words.iband_done(p.nxt) : nullptr); if (r) return r;
     if (p.prof) HIPCHK(hipEventRecord(s->ev[1], h->stream));
     return 0;
 }
@@ -255,7 +260,7 @@ static int enqueue_p(mi355enc_t *h, slot_t *s, const pic_t &p, const pic_plan_t 
     int r = run_p_back(h, s->h_ctx, s, p.prof, plan); if (r) return r;
     if (plan.fip) {
         r = run_deblock(h, p.set, s->h_ctx, plan, p.nxt); if (r) return r;
-        k_launch_wait_started(h->d_progress + 2, h->ip_done_total, err_word(h), h->istream); // records and levels are final once the rows have all counted themselves
+        k_launch_wait_started(h->words.ip_done().word, h->words.ip_done().total, h->words.err(), h->istream); // records and levels are final once the rows have all counted themselves
     }
     return 0;
 }
@@ -290,14 +295,14 @@ static int enqueue_rec_readers(mi355enc_t *h, slot_t *s, const pic_t &p, const p
 // blocks straight into the pinned host buffer while the band deblocker runs.
 static int enqueue_handover(mi355enc_t *h, slot_t *s, const pic_t &p) {
     HIPCHK(hipStreamWaitEvent(h->cstream, s->gpu_done, 0));
-    k_launch_pack(h->d_mbi_set[p.set], h->d_levels_set[p.set], h->nmb, h->mbw, h->d_off, s->h_mbi, s->h_levels, s->h_hdr, err_word(h), h->cstream);
+    k_launch_pack(h->d_mbi_set[p.set], h->d_levels_set[p.set], h->nmb, h->mbw, h->d_off, s->h_mbi, s->h_levels, s->h_hdr, h->words.err(), h->cstream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->done, h->cstream));
     return 0;
 }
 // Book: the picture on its slot, the handle moved on to the next one
 static void book_picture(mi355enc_t *h, slot_t *s, const pic_t &p, int64_t pts, int force_idr) {
-    if (!p.all_skip) h->rec_epoch[p.nxt] = h->cfg.deblock_mode == 0 ? s->h_ctx->epoch : 0; // the epoch the buffer's band-done words carry once its deblocking is through
+    if (!p.all_skip) h->words.stamp_rec(p.nxt, h->cfg.deblock_mode == 0 ? s->h_ctx->epoch : 0); // the epoch the buffer's band-done words carry once its deblocking is through
     h->n_submitted++;
     s->is_idr = p.idr; s->qp = p.qp; s->drop = p.drop; s->frame_num = h->frames_since_idr; s->idr_pic_id = h->idr_count & 0xFFFF; s->ir_start = p.ir_j == 0;
     s->src_y = p.src_y; s->src_uv = p.src_uv; s->src_stride = p.src_stride; s->force_idr = force_idr;
@@ -400,7 +405,7 @@ static const char *wait_name(unsigned code) {
     default: return "injected / unknown";
     }
 }
-// A bounded wait on the device ran out (the kernels report it in the sticky word d_progress[0], which the hand-over copies into h_hdr[1]; once
+// A bounded wait on the device ran out (the kernels report it in the sticky error word, which the hand-over copies into h_hdr[1]; once
 // it is set nobody waits any more, so everything in flight completes, possibly from data that was not final).  Nothing that was produced since
 // can be trusted, but nothing needs to be lost either: the sources of the pictures in flight are still where submit() put them (the slots'
 // staging surfaces, or the caller's device memory, which stays valid until the matching collect()).  So: drain, clear the device-side words,
@@ -416,14 +421,10 @@ static int recover(mi355enc_t *h, unsigned code) {
     if (h->wk_on) worker_drain(h); // (the pictures behind the failing one are coded and thrown away: they are enqueued again below)
     HIPCHK(hipStreamSynchronize(h->cstream));
     { int r = sync_compute(h); if (r) return r; }
-    HIPCHK(hipMemsetAsync(h->d_progress, 0, 4 * sizeof(unsigned), h->stream));
-    HIPCHK(hipMemsetAsync(h->d_row_done, 0, (size_t)h->mbh * MI355_PROG_STRIDE * sizeof(unsigned), h->stream));
-    if (h->d_db_part) HIPCHK(hipMemsetAsync(h->d_db_part, 0, 6 * (size_t)k_deblock_bands16(h->mbh) * sizeof(unsigned), h->stream));
-    HIPCHK(hipMemsetAsync(h->d_db_done, 0, 2 * k_deblock_done_bytes(), h->stream));
-    HIPCHK(hipMemsetAsync(h->d_iband_done, 0, 2 * (size_t)h->mbh * sizeof(unsigned), h->stream));
+    { int r = h->words.clear(h->stream); if (r) return r; }
     if (h->d_qacc) HIPCHK(hipMemsetAsync(h->d_qacc, 0, (size_t)(NSLOT + 1) * QUALITY_ACC_WORDS * sizeof(unsigned long long), h->stream)); // (every launch has completed and left its block clear; kept with the other device-side words)
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->pmb_rows_total = 0; h->db_started_total = 0; h->ip_done_total = 0; h->qpc_total = 0; h->rec_epoch[0] = h->rec_epoch[1] = 0; h->dbI_busy[0] = h->dbI_busy[1] = 0;
+    h->dbI_busy[0] = h->dbI_busy[1] = 0;
     if (h->safe_level == 2) { h->cfg.deblock_mode = 1; h->cfg.intra_mode = 1; }
     const int n = h->pending;
     struct { const uint8_t *y, *uv; int stride, force_idr; int64_t pts; int fixed_qp, fixed_drop; } again[NSLOT];

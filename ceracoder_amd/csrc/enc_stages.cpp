@@ -11,7 +11,7 @@ extern "C" {
 // A single-stage call overwrites the reconstruction buffers, the previous-source planes and the record sets behind the encoder's back: the
 // next picture submitted through the pipeline must not predict from any of it, so it is coded as an IDR picture and nothing of the
 // previous picture's on-device progress words is trusted.
-static void stage_touched(mi355enc_t *h) { h->have_ref = 0; h->rec_epoch[0] = h->rec_epoch[1] = 0; h->dbI_busy[0] = h->dbI_busy[1] = 0; }
+static void stage_touched(mi355enc_t *h) { h->have_ref = 0; h->words.forget(); h->dbI_busy[0] = h->dbI_busy[1] = 0; }
 static int stage_ctx(mi355enc_t *h, int qp, bool src_is_staging, int drop = 0, int idr = 0) {
     if (h->pending) return MI355ENC_ERR_STATE;
     // slice-local deblocking: a band of the deblocker never spans two slices (mi355enc_dev.h); the two settings are made separately, so the pair is checked here
@@ -43,7 +43,7 @@ int mi355enc_stage_me(mi355enc_t *h, const uint8_t *cur_y, const uint8_t *ref_y,
     HIPCHK(hipMemcpyAsync(h->slot[0].d_src_y, cur_y, h->ysz, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_psrc[h->psrc_cur], ref_y, h->ysz, hipMemcpyHostToDevice, h->stream)); // what the search runs against (in the encoder: the previous source)
     int r = stage_ctx(h, qp, true); if (r) return r;
-    k_launch_me(h->slot[0].h_ctx, h->mbw, 0, h->mbh, h->stream);
+    k_launch_me(h->slot[0].h_ctx, h->mbw, h->stream);
     HIPCHK(hipMemcpyAsync(imv_out, h->d_imv[0][0], (size_t)h->nmb * sizeof(imv_t), hipMemcpyDeviceToHost, h->stream));
     if (surf_out) HIPCHK(hipMemcpyAsync(surf_out, h->d_surf[0], (size_t)h->nmb * SURF_U16 * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -56,7 +56,7 @@ int mi355enc_stage_me_select(mi355enc_t *h, const uint16_t *surf, const void *im
     int r = stage_ctx(h, qp, true); if (r) return r;
     HIPCHK(hipMemcpyAsync(h->d_surf[0], surf, (size_t)h->nmb * SURF_U16 * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_imv[0][0], imv_in, (size_t)h->nmb * sizeof(imv_t), hipMemcpyHostToDevice, h->stream));
-    k_launch_me_select(h->slot[0].h_ctx, h->mbw, 0, h->mbh, h->d_imv[0][0], h->d_imv[0][1], nullptr, 0, h->stream);
+    k_launch_me_select(h->slot[0].h_ctx, h->mbw, h->d_imv[0][0], h->d_imv[0][1], nullptr, 0, h->stream);
     HIPCHK(hipMemcpyAsync(imv_out, h->d_imv[0][1], (size_t)h->nmb * sizeof(imv_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return MI355ENC_OK;
@@ -71,7 +71,7 @@ int mi355enc_stage_me_select_next(mi355enc_t *h, const uint16_t *surf, const voi
     HIPCHK(hipMemcpyAsync(h->d_surf[0], surf, (size_t)h->nmb * SURF_U16 * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_imv[0][0], imv_in, (size_t)h->nmb * sizeof(imv_t), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_imv[0][2], imv_prev, (size_t)h->nmb * sizeof(imv_t), hipMemcpyHostToDevice, h->stream));
-    k_launch_me_select(h->slot[0].h_ctx, h->mbw, 0, h->mbh, h->d_imv[0][0], h->d_imv[0][1], h->d_imv[0][2], 2, h->stream);
+    k_launch_me_select(h->slot[0].h_ctx, h->mbw, h->d_imv[0][0], h->d_imv[0][1], h->d_imv[0][2], 2, h->stream);
     HIPCHK(hipMemcpyAsync(imv_out, h->d_imv[0][1], (size_t)h->nmb * sizeof(imv_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return MI355ENC_OK;
@@ -83,7 +83,7 @@ int mi355enc_stage_subpel(mi355enc_t *h, const uint8_t *cur_y, const uint8_t *re
     int r = upload_luma_pair(h, cur_y, ref_y); if (r) return r;
     HIPCHK(hipMemcpyAsync(h->d_mbi, mbinfo_inout, (size_t)h->nmb * sizeof(mb_info_t), hipMemcpyHostToDevice, h->stream));
     r = stage_ctx(h, qp, true); if (r) return r;
-    k_launch_subpel(h->slot[0].h_ctx, h->mbw, 0, h->mbh, h->stream);
+    k_launch_subpel(h->slot[0].h_ctx, h->mbw, h->stream);
     HIPCHK(hipMemcpyAsync(mbinfo_inout, h->d_mbi, (size_t)h->nmb * sizeof(mb_info_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return MI355ENC_OK;
@@ -112,7 +112,7 @@ int mi355enc_stage_inter(mi355enc_t *h, const uint8_t *src_y, const uint8_t *src
     int r = upload_planes4(h, src_y, src_uv, ref_y, ref_uv); if (r) return r;
     HIPCHK(hipMemcpyAsync(h->d_mbi, mbinfo_inout, (size_t)h->nmb * sizeof(mb_info_t), hipMemcpyHostToDevice, h->stream));
     r = stage_ctx(h, qp, true); if (r) return r;
-    k_launch_inter(h->slot[0].h_ctx, h->mbw, 0, h->mbh, h->stream);
+    k_launch_inter(h->slot[0].h_ctx, h->mbw, h->stream);
     return download_picture(h, mbinfo_inout, rec_y, rec_uv, levels) ? MI355ENC_ERR_HIP : MI355ENC_OK;
 }
 int mi355enc_stage_pmb(mi355enc_t *h, const uint8_t *src_y, const uint8_t *src_uv, const uint8_t *ref_y, const uint8_t *ref_uv,
@@ -132,9 +132,9 @@ int mi355enc_stage_pmb(mi355enc_t *h, const uint8_t *src_y, const uint8_t *src_u
     HIPCHK(hipMemsetAsync(h->d_rec_y[1], 0, h->ysz, h->stream)); // macroblocks decided intra stay untouched unless run_intra_p
     HIPCHK(hipMemsetAsync(h->d_rec_uv[1], 0, h->csz, h->stream));
     HIPCHK(hipMemsetAsync(h->d_levels, 0, (size_t)h->nmb * MB_LEVELS * 2, h->stream));
-    k_launch_pmb(c, h->mbw, 0, h->mbh, refine ? 1 : 0, nullptr, 0, err_word(h), nullptr, h->stream);
-    if (idec && run_intra_p) { r = ip_rows_stamp(h, c->epoch); if (r) return r; }
-    if (idec && run_intra_p) k_launch_intra_p(c, h->mbw, h->mbh, h->d_ip_progress, h->d_ip_strips, err_word(h), h->stream);
+    r = run_pmb(h, c, refine ? 1 : 0, pic_plan_t(), h->stream); if (r) return r;
+    if (idec && run_intra_p) { r = h->words.ip_rows_stamp(c->epoch, h->stream); if (r) return r; }
+    if (idec && run_intra_p) k_launch_intra_p(c, h->mbw, h->mbh, h->words.ip_progress(), h->d_ip_strips, h->words.err(), h->stream);
     HIPCHK(hipGetLastError());
     return download_picture(h, mbinfo_out, rec_y, rec_uv, levels) ? MI355ENC_ERR_HIP : MI355ENC_OK;
 }
@@ -203,16 +203,16 @@ int mi355enc_debug_trip_wait(mi355enc_t *h, unsigned code) {
     HIPCHK(hipSetDevice(h->cfg.device_id));
     HIPCHK(hipStreamSynchronize(h->cstream));
     { int r = sync_compute(h); if (r) return r; }
-    HIPCHK(hipMemcpy(h->d_progress, &code, sizeof code, hipMemcpyHostToDevice));
-    return MI355ENC_OK;
+    return h->words.trip(code);
 }
 int mi355enc_debug_get_counters(mi355enc_t *h, mi355enc_counters_t *out) {
     if (!h || !out) return MI355ENC_ERR_ARG;
-    *out = {h->epoch, h->pmb_rows_total, h->db_started_total, h->ip_done_total, h->qpc_total, (uint32_t)h->idr_count, (uint32_t)h->frames_since_idr, 0u};
+    *out = {h->epoch, 0u, 0u, 0u, 0u, (uint32_t)h->idr_count, (uint32_t)h->frames_since_idr, 0u};
+    h->words.get(out);
     return MI355ENC_OK;
 }
-// Host-side value and device-side word of every count move together (the kernels compare one with the other); rec_epoch[], the band-done words, the
-// strips and progress words tagged with an epoch, and the parity of the band parts' counters stay as the last picture left them.
+// The four counts go through their owner (dev_words_t::set: word and total together); the band-done words and their epochs, the strips and progress words
+// tagged with an epoch, and the parity of the band parts' counters stay as the last picture left them.
 int mi355enc_debug_set_counters(mi355enc_t *h, const mi355enc_counters_t *in) {
     if (!h || !in || (!(in->keep & 64u) && in->frames_since_idr > 0x7FFFFFFFu) || (!(in->keep & 32u) && in->idr_count > 0x7FFFFFFFu)) return MI355ENC_ERR_ARG;
     STAGE_IDLE(h);
@@ -220,18 +220,7 @@ int mi355enc_debug_set_counters(mi355enc_t *h, const mi355enc_counters_t *in) {
     HIPCHK(hipStreamSynchronize(h->cstream));
     { int r = sync_compute(h); if (r) return r; }
     if (!(in->keep & 1u)) h->epoch = in->epoch;
-    if (!(in->keep & 2u)) {
-        uint32_t *rows = (uint32_t *)malloc((size_t)h->mbh * sizeof(uint32_t));
-        if (!rows) return MI355ENC_ERR_NOMEM;
-        for (int r = 0; r < h->mbh; r++) rows[r] = in->pmb_rows_total;
-        const hipError_t e = hipMemcpy2D(h->d_row_done, MI355_PROG_STRIDE * sizeof(unsigned), rows, sizeof(uint32_t), sizeof(uint32_t), (size_t)h->mbh, hipMemcpyHostToDevice);
-        free(rows);
-        HIPCHK(e);
-        h->pmb_rows_total = in->pmb_rows_total;
-    }
-    if (!(in->keep & 4u)) { HIPCHK(hipMemcpy(h->d_progress + 1, &in->db_started_total, sizeof(uint32_t), hipMemcpyHostToDevice)); h->db_started_total = in->db_started_total; }
-    if (!(in->keep & 8u)) { HIPCHK(hipMemcpy(h->d_progress + 2, &in->ip_done_total, sizeof(uint32_t), hipMemcpyHostToDevice)); h->ip_done_total = in->ip_done_total; }
-    if (!(in->keep & 16u)) { HIPCHK(hipMemcpy(h->d_progress + 3, &in->qpc_total, sizeof(uint32_t), hipMemcpyHostToDevice)); h->qpc_total = in->qpc_total; }
+    { int r = h->words.set(in); if (r) return r; }
     if (!(in->keep & 32u)) h->idr_count = (int)in->idr_count;
     if (!(in->keep & 64u)) h->frames_since_idr = (int)in->frames_since_idr;
     return MI355ENC_OK;
@@ -263,7 +252,7 @@ int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
     }
     if (stage == 12) { int r = jpeg_alloc(h, s); if (r) return r; }
     if (stage == 16) { int r = snapshot_time_prepare(h); if (r) return r; } // (the block of the stage entry points)
-    if (stage == 10) { int r = ip_rows_stamp(h, s->h_ctx->epoch); if (r) return r; }
+    if (stage == 10) { int r = h->words.ip_rows_stamp(s->h_ctx->epoch, h->stream); if (r) return r; }
     const scale_plan_t *scale_pl = stage == 14 ? scale_plan_for(h, s, h->stream) : nullptr; // (a stale slot copy of the tables travels here, not inside the timed loop)
     if (stage == 14 && !scale_pl) return MI355ENC_ERR_HIP;
     image_args_t img_a; // stage 15: layer 0's image on the device and prepared here, not inside the timed loop
@@ -271,12 +260,12 @@ int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
     for (int warm = 0; warm < 2; warm++) {
         if (warm) HIPCHK(hipEventRecord(s->ev[0], h->stream));
         for (int i = 0; i < (warm ? iters : 1); i++) {
-            if (stage == 0) k_launch_me(h->slot[0].h_ctx, h->mbw, 0, h->mbh, h->stream);
-            else if (stage == 1) k_launch_inter(h->slot[0].h_ctx, h->mbw, 0, h->mbh, h->stream);
+            if (stage == 0) k_launch_me(h->slot[0].h_ctx, h->mbw, h->stream);
+            else if (stage == 1) k_launch_inter(h->slot[0].h_ctx, h->mbw, h->stream);
             else if (stage == 2) { if (++h->epoch == 0) h->epoch = 1; h->slot[0].h_ctx->epoch = h->epoch; int r = run_intra(h, 0, h->slot[0].h_ctx); if (r) return r; } // a fresh stamp per launch: the lines between bands are epoch-tagged
-            else if (stage == 4) k_launch_subpel(h->slot[0].h_ctx, h->mbw, 0, h->mbh, h->stream);
-            else if (stage == 8) k_launch_me_select(h->slot[0].h_ctx, h->mbw, 0, h->mbh, h->d_imv[0][0], h->d_imv[0][1], nullptr, 0, h->stream);
-            else if (stage == 9) k_launch_pmb(h->slot[0].h_ctx, h->mbw, 0, h->mbh, 1, nullptr, 0, err_word(h), nullptr, h->stream);
+            else if (stage == 4) k_launch_subpel(h->slot[0].h_ctx, h->mbw, h->stream);
+            else if (stage == 8) k_launch_me_select(h->slot[0].h_ctx, h->mbw, h->d_imv[0][0], h->d_imv[0][1], nullptr, 0, h->stream);
+            else if (stage == 9) { int r = run_pmb(h, h->slot[0].h_ctx, 1, pic_plan_t(), h->stream); if (r) return r; }
             else if (stage == 11) k_launch_quality(s->d_src_y, s->d_src_uv, h->W, h->d_rec_y[1], h->d_rec_uv[1], h->W, h->cfg.width, h->cfg.height, h->d_qacc + (size_t)NSLOT * QUALITY_ACC_WORDS,
                                                    h->h_qres + (size_t)NSLOT * QUALITY_WORDS, h->stream);
             else if (stage == 12) { int r = jpeg_time_launch(h, s); if (r) return r; }
@@ -308,7 +297,7 @@ int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
                                     : hdr_convert(h, fmt, p, st, s->d_src_y, s->d_src_uv, w, ht, h->W, h->H, h->stream);
                 if (r) return r < -1 ? r : MI355ENC_ERR_ARG;
             }
-            else if (stage == 10) k_launch_intra_p(h->slot[0].h_ctx, h->mbw, h->mbh, h->d_ip_progress, h->d_ip_strips, err_word(h), h->stream);
+            else if (stage == 10) k_launch_intra_p(h->slot[0].h_ctx, h->mbw, h->mbh, h->words.ip_progress(), h->d_ip_strips, h->words.err(), h->stream);
             else if (stage >= 5) {
                 const int w = h->cfg.width, ht = h->cfg.height, r0 = stage == 5 ? (w + 15) & ~15 : (2 * w + 15) & ~15, r1 = (w / 2 + 15) & ~15;
                 const uint8_t *p0 = s->d_raw, *p1 = p0 + (size_t)r0 * ht, *p2 = p1 + (size_t)r1 * (ht / 2);

@@ -982,30 +982,11 @@ void k_launch_deblock_diag(const frame_ctx_t *d_ctx, int mbw, int mbh, int diag,
     if (y_hi < y_lo) return;
     hipLaunchKernelGGL(deblock_kernel, dim3(y_hi - y_lo + 1), dim3(64), 0, s, d_ctx, diag);
 }
-#ifndef DB_CUT_MIN_MBW
-#define DB_CUT_MIN_MBW 60 /* rows at least this long are walked in two parts (A/B, alternating processes: 2160p +6...9 %, 1080p +2 %, 720p +5 %, 640 x 368 -3 %: two workgroups' prologues cost more than twenty columns save) */
-#endif
 #ifndef DB_ROWS
 #define DB_ROWS MI355_BAND_ROWS /* rows per band: three waves per row, one row per SIMD (5 rows = 15 waves is equal on P pictures, a third slower on I pictures) */
 #endif
 int k_deblock_bands16(int mbh) { return (mbh + DB_ROWS - 1) / DB_ROWS; }
-// The workgroups of one launch over a whole picture: two per band (luma, chroma), four where a P picture's bands are walked in two parts, and one per macroblock row
-// where the intra rows ride in it.  Each is twelve waves at more than 100 VGPRs -- a compute unit holds one, and nothing of the size of an intra row's workgroup beside
-// it -- so a launch whose workgroups wait for another kernel must leave that kernel compute units to be placed on (enc_handle.cpp: wait_room).
-int k_deblock_launch_wgs(int mbw, int mbh, int all_intra, int fused_ip) {
-    return (!all_intra && mbw >= DB_CUT_MIN_MBW ? 4 : 2) * k_deblock_bands16(mbh) + (fused_ip ? mbh : 0);
-}
 size_t k_deblock_gran_bytes(int mbw, int mbh) { return (size_t)k_deblock_bands16(mbh) * mbw * 24 * sizeof(uint2); } // per band boundary and macroblock: 16 luma + 8 chroma granules
-// The band kernel may be launched in several pieces (bands [band0, band1)): a band only ever waits for the band above it.
-// d_ip_progress (may be null): intra_p_kernel of the same picture is still running; the movers follow its per-row progress words.
-template <typename K>
-static int launch_bands(K kernel, const db_args &a, int nbands, int mbw, hipStream_t s) {
-    constexpr size_t lds = (size_t)DB_ROWS * sizeof(dbt_luma) + 16 + 4 * DB_ROWS + 8; // the rows' tile rings + three work flags (and the parts' hand-shake word) + the rows' first intra macroblocks + the cut's column mask: ~12.5 KB
-    static_assert(lds <= 48 * 1024, "above 48 KB of dynamic LDS every instantiation launched here would need hipFuncAttributeMaxDynamicSharedMemorySize");
-    const int wgs = (a.part_cnt ? 4 : 2) * nbands;
-    hipLaunchKernelGGL(kernel, dim3(wgs + (a.nip > 0 ? a.nip : 0) + (a.qpc && a.nip <= 0 ? 1 : 0)), dim3(192 * DB_ROWS), lds, s, a);
-    return wgs; // the workgroups that count themselves in a.started
-}
 // One wave that ends once `count` workgroups of band-deblocking launches have been placed since the encoder was opened (the count only
 // grows; the comparison is wrap-safe).  On a stream in front of a kernel whose workgroups wait for the deblocker's flags, it keeps
 // them from filling the chip before the deblocker is on it.
@@ -1021,23 +1002,35 @@ __global__ __launch_bounds__(64) void wait_started_kernel(const unsigned *starte
 void k_launch_wait_started(const unsigned *d_started, unsigned count, unsigned *d_err, hipStream_t s) { hipLaunchKernelGGL(wait_started_kernel, dim3(1), dim3(64), 0, s, d_started, count, d_err); }
 size_t k_deblock_done_bytes(void) { return (size_t)DB_DONE_COPIES * DB_DONE_STRIDE * sizeof(unsigned); } // 2 words per band: up to 512 bands
 size_t k_deblock_partab_bytes(int mbw, int mbh) { return (size_t)k_deblock_bands16(mbh) * DB_ROWS * mbw * 48 * sizeof(unsigned); } // 32 luma + 16 chroma words per macroblock
-int k_launch_deblock_bands(const frame_ctx_t *h_ctx, int mbh, int band0, int band1, unsigned *d_err, uint2 *d_gran, unsigned *d_partab, const unsigned *d_ip_progress,
-                           const unsigned *d_iband_done, int ib_rows, unsigned *d_band_done, unsigned *d_started, const unsigned *d_row_done, unsigned row_need,
-                           uint8_t *d_ip_strips, unsigned *d_ip_done, unsigned *d_qpc, unsigned qpc_base, unsigned *d_part_cnt, hipStream_t s) {
-    db_args a;
-    a.part_cnt = nullptr;
-    a.ctx = *h_ctx; a.err = d_err; a.band0 = band0; a.nb_total = k_deblock_bands16(mbh); a.gran = d_gran; a.ip_progress = d_ip_progress; a.partab = d_partab; a.iband_done = d_iband_done; a.ib_rows = ib_rows > 0 ? ib_rows : DB_ROWS; a.band_done = d_band_done; a.started = d_started; a.row_done = d_row_done; a.row_need = row_need;
-    a.nip = 0; a.ip_progress_w = nullptr; a.ip_strips = nullptr; a.ip_done = nullptr;
-    a.qpc = (h_ctx->qp_off && band0 == 0) ? d_qpc : nullptr; a.qpc_base = qpc_base; // (a launch of all the picture's bands)
-    if (band1 <= band0) return 0;
-    if (h_ctx->all_intra) return launch_bands(deblock_rows3_kernel<DB_ROWS, true, false, false>, a, band1 - band0, h_ctx->mbw, s); // IDR pictures: every edge has work
-#ifndef DBG_DELAY_BAND /* (the adversarial-schedule build delays a band's last columns by their position in the whole row) */
-    if (band0 == 0 && band1 == a.nb_total && h_ctx->mbw >= DB_CUT_MIN_MBW) a.part_cnt = d_part_cnt; // P pictures, the whole picture in one launch: every band as two workgroups (rows3_body: the cut)
+// The parts' words (db_launch_t::part_cnt).  The adversarial-schedule build delays a band's last columns by their position in the whole row: it has no such words,
+// so no launch of it is asked for parts.
+size_t k_deblock_part_bytes(int mbh) {
+#ifdef DBG_DELAY_BAND
+    (void)mbh; return 0;
+#else
+    return 6 * (size_t)k_deblock_bands16(mbh) * sizeof(unsigned);
 #endif
-    if (d_ip_progress && d_ip_done && d_row_done && band0 == 0) { // the picture's intra macroblock rows lead the launch (pmb_kernel<GATED, ROWS> of the same picture still runs)
-        a.nip = mbh; a.ip_progress_w = const_cast<unsigned *>(d_ip_progress); a.ip_strips = d_ip_strips; a.ip_done = d_ip_done;
-        return launch_bands(deblock_rows3_kernel<DB_ROWS, false, true, true>, a, band1 - band0, h_ctx->mbw, s);
+}
+int k_launch_deblock_bands(const frame_ctx_t *h_ctx, const db_launch_t *l, hipStream_t s) {
+    static_assert(DB_ROWS == MI355_BAND_ROWS, "db_launch_wgs() and pmb_kernel's gate count bands of MI355_BAND_ROWS rows");
+    constexpr size_t lds = (size_t)DB_ROWS * sizeof(dbt_luma) + 16 + 4 * DB_ROWS + 8; // the rows' tile rings + three work flags (and the parts' hand-shake word) + the rows' first intra macroblocks + the cut's column mask: ~12.5 KB
+    static_assert(lds <= 48 * 1024, "above 48 KB of dynamic LDS every instantiation launched here would need hipFuncAttributeMaxDynamicSharedMemorySize");
+    const bool follows = l->variant == DB_P_FOLLOWS_IP || l->variant == DB_P_FUSED_IP, fused = l->variant == DB_P_FUSED_IP;
+    if (!l->err || !l->gran || !l->partab || (follows && !l->ip_progress) || (fused && (!l->ip_strips || !l->ip_done || !l->row_done)) ||
+        (l->parts && (!l->part_cnt || l->variant == DB_ALL_INTRA)) || (l->qpc && !l->qpc_word)) return -1;
+    const int mbh = h_ctx->mbh;
+    db_args a;
+    a.ctx = *h_ctx; a.err = l->err; a.band0 = 0; a.nb_total = k_deblock_bands16(mbh); a.gran = (uint2 *)l->gran; a.ip_progress = follows ? l->ip_progress : nullptr; a.partab = l->partab; a.iband_done = l->iband_done; a.ib_rows = l->ib_rows > 0 ? l->ib_rows : DB_ROWS; a.band_done = l->band_done; a.started = l->started; a.row_done = l->row_done; a.row_need = l->row_need;
+    a.nip = fused ? mbh : 0; a.ip_progress_w = fused ? l->ip_progress : nullptr; a.ip_strips = fused ? l->ip_strips : nullptr; a.ip_done = fused ? l->ip_done : nullptr; // (the picture's intra macroblock rows lead the launch: pmb_kernel<GATED, ROWS> of the same picture still runs)
+    a.qpc = l->qpc ? l->qpc_word : nullptr; a.qpc_base = l->qpc_base;
+    a.part_cnt = l->parts ? l->part_cnt : nullptr; // every band as two workgroups (rows3_body: the cut)
+    const dim3 grid(db_launch_wgs(mbh, l->variant, l->parts, l->qpc).grid), block(192 * DB_ROWS);
+    switch (l->variant) {
+    case DB_ALL_INTRA: hipLaunchKernelGGL((deblock_rows3_kernel<DB_ROWS, true, false, false>), grid, block, lds, s, a); break; // IDR pictures: every edge has work
+    case DB_P: hipLaunchKernelGGL((deblock_rows3_kernel<DB_ROWS, false, false, false>), grid, block, lds, s, a); break;
+    case DB_P_FOLLOWS_IP: hipLaunchKernelGGL((deblock_rows3_kernel<DB_ROWS, false, true, false>), grid, block, lds, s, a); break; // beside intra_p_kernel
+    case DB_P_FUSED_IP: hipLaunchKernelGGL((deblock_rows3_kernel<DB_ROWS, false, true, true>), grid, block, lds, s, a); break;
+    default: return -1;
     }
-    if (d_ip_progress) return launch_bands(deblock_rows3_kernel<DB_ROWS, false, true, false>, a, band1 - band0, h_ctx->mbw, s); // beside intra_p_kernel
-    return launch_bands(deblock_rows3_kernel<DB_ROWS, false, false, false>, a, band1 - band0, h_ctx->mbw, s);
+    return 0;
 }

@@ -290,7 +290,7 @@ __global__ __launch_bounds__(256) void inter_kernel(const frame_ctx_t cv, int mb
 
 // sum over each row of 16 lanes, result in every lane: four DPP adds (no LDS crossbar round trips)
 // =================================================================== launcher
-void k_launch_inter(const frame_ctx_t *h_ctx, int mbw, int row0, int row1, hipStream_t s) {
-    int pairs = (mbw * (row1 - row0) + 1) / 2;
-    if (row1 > row0) hipLaunchKernelGGL(inter_kernel, dim3((pairs + 3) / 4), dim3(256), 0, s, *h_ctx, row0 * mbw, row1 * mbw);
+void k_launch_inter(const frame_ctx_t *h_ctx, int mbw, hipStream_t s) {
+    const int n = mbw * h_ctx->mbh, pairs = (n + 1) / 2;
+    if (n > 0) hipLaunchKernelGGL(inter_kernel, dim3((pairs + 3) / 4), dim3(256), 0, s, *h_ctx, 0, n);
 }

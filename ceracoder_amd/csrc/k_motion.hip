@@ -1147,11 +1147,7 @@ __global__ __launch_bounds__(256) void pmb_kernel(const frame_ctx_t cv, int mb0,
             r_hi = r_hi < mbh ? r_hi : mbh - 1;
             const uint2 *flags = (const uint2 *)(gate_done + DB_DONE_STRIDE * (blockIdx.x & (DB_DONE_COPIES - 1)));
             const int b_hi = r_hi / MI355_BAND_ROWS;
-#ifdef DBG_OLD_GATE /* what round 2 first shipped: the lowest band alone (tests/test_adversarial_gpu.py was checked to FAIL with this and the ADVBAND delay) */
-            int spins = 0, b = b_hi;
-#else
             int spins = 0, b = r_lo / MI355_BAND_ROWS;
-#endif
             for (;;) {
                 const uint2 f = ld64_sc1(flags + b);
                 if (f.x == ref_epoch && f.y == ref_epoch) { if (++b > b_hi) break; continue; }
@@ -1192,6 +1188,8 @@ void k_launch_copy_luma(const frame_ctx_t *h_ctx, hipStream_t s) {
 }
 
 // whole-sample field -> records for the two-kernel (8x8-transform) path: subpel_kernel compares absolute-vector costs
+// (No launcher: nothing calls it any more.  It stays in this file until a change that may alter device code: without this caller of mvq_bits() the compiler
+// selects other instructions for that function inside me_kernel, both selection kernels and subpel_kernel -- profiles/sync_words.md, section 1.)
 __global__ __launch_bounds__(256) void imv_to_mbi_kernel(const frame_ctx_t cv, int mb0, int mb1) {
     const frame_ctx_t *__restrict__ ctx = &cv;
     const int i = mb0 + blockIdx.x * 256 + threadIdx.x;
@@ -1203,67 +1201,41 @@ __global__ __launch_bounds__(256) void imv_to_mbi_kernel(const frame_ctx_t cv, i
 }
 
 // =================================================================== launchers
-// The P-picture kernels take a macroblock-row range [row0, row1).
-void k_launch_me(const frame_ctx_t *h_ctx, int mbw, int row0, int row1, hipStream_t s) {
+// The P-picture launchers cover the whole picture (the kernels keep their macroblock range [mb0, mb1)).
+void k_launch_me(const frame_ctx_t *h_ctx, int mbw, hipStream_t s) {
     int strips = (mbw + ME_MBS - 1) / ME_MBS;
-    if (row1 > row0) hipLaunchKernelGGL(me_kernel, dim3(strips * (row1 - row0)), dim3(64 * ME_MBS), 0, s, *h_ctx, row0);
+    if (h_ctx->mbh > 0) hipLaunchKernelGGL(me_kernel, dim3(strips * h_ctx->mbh), dim3(64 * ME_MBS), 0, s, *h_ctx, 0);
 }
-void k_launch_me_select(const frame_ctx_t *h_ctx, int mbw, int row0, int row1, const imv_t *in, imv_t *out, const imv_t *prev, int mode, hipStream_t s) {
-    int n = mbw * (row1 - row0);
+void k_launch_me_select(const frame_ctx_t *h_ctx, int mbw, const imv_t *in, imv_t *out, const imv_t *prev, int mode, hipStream_t s) {
+    int n = mbw * h_ctx->mbh;
     if (n <= 0) return;
-#ifdef NO_SPARSE_SELECT /* A/B build (tools/build_variant.sh): the dense kernel for every pass */
-    if (false) hipLaunchKernelGGL(me_select_sparse_kernel,
-#else
-    if (mode == 2) hipLaunchKernelGGL(me_select_sparse_kernel,
-#endif
-  dim3((n + 4 * SEL_SPW - 1) / (4 * SEL_SPW)), dim3(256), 0, s, *h_ctx, row0 * mbw, row1 * mbw, in, out, prev); // later passes: mostly copies
-    else hipLaunchKernelGGL(me_select_kernel, dim3((n + 3) / 4), dim3(256), 0, s, *h_ctx, row0 * mbw, row1 * mbw, in, out, prev, mode);
+    if (mode == 2) hipLaunchKernelGGL(me_select_sparse_kernel, dim3((n + 4 * SEL_SPW - 1) / (4 * SEL_SPW)), dim3(256), 0, s, *h_ctx, 0, n, in, out, prev); // later passes: mostly copies
+    else hipLaunchKernelGGL(me_select_kernel, dim3((n + 3) / 4), dim3(256), 0, s, *h_ctx, 0, n, in, out, prev, mode);
 }
 // The ME_ITERS iterations walk a -> b -> c -> a ...: iteration k reads field k % 3, writes (k + 1) % 3 and compares with what iteration k - 1 read.
-void k_launch_me_select_all(const frame_ctx_t *h_ctx, int mbw, int row0, int row1, hipStream_t s) {
+void k_launch_me_select_all(const frame_ctx_t *h_ctx, int mbw, hipStream_t s) {
     imv_t *const f[3] = {h_ctx->imv_a, h_ctx->imv_b, h_ctx->imv_c};
-    for (int it = 0; it < ME_ITERS; it++) k_launch_me_select(h_ctx, mbw, row0, row1, f[it % 3], f[(it + 1) % 3], it ? f[(it - 1) % 3] : nullptr, it ? 2 : 1, s);
+    for (int it = 0; it < ME_ITERS; it++) k_launch_me_select(h_ctx, mbw, f[it % 3], f[(it + 1) % 3], it ? f[(it - 1) % 3] : nullptr, it ? 2 : 1, s);
 }
 const imv_t *k_final_imv(const frame_ctx_t *h_ctx) { return ME_ITERS % 3 == 0 ? h_ctx->imv_a : ME_ITERS % 3 == 1 ? h_ctx->imv_b : h_ctx->imv_c; }
-void k_launch_imv_to_mbi(const frame_ctx_t *h_ctx, int mbw, int row0, int row1, hipStream_t s) {
-    int n = mbw * (row1 - row0);
-    if (n > 0) hipLaunchKernelGGL(imv_to_mbi_kernel, dim3((n + 255) / 256), dim3(256), 0, s, *h_ctx, row0 * mbw, row1 * mbw);
+void k_launch_subpel(const frame_ctx_t *h_ctx, int mbw, hipStream_t s) {
+    const int n = mbw * h_ctx->mbh;
+    if (n > 0) hipLaunchKernelGGL(subpel_kernel, dim3((n + 3) / 4), dim3(256), 0, s, *h_ctx, 0, n);
 }
-void k_launch_subpel(const frame_ctx_t *h_ctx, int mbw, int row0, int row1, hipStream_t s) {
-    if (row1 > row0) hipLaunchKernelGGL(subpel_kernel, dim3((mbw * (row1 - row0) + 3) / 4), dim3(256), 0, s, *h_ctx, row0 * mbw, row1 * mbw);
-}
-void k_launch_pmb(const frame_ctx_t *h_ctx, int mbw, int row0, int row1, int refine, const unsigned *gate_done, unsigned ref_epoch, unsigned *d_err, unsigned *d_row_done, hipStream_t s) {
-    const int n = mbw * (row1 - row0), g = (n + 3) / 4;
-    if (n <= 0) return;
-#define PMB_LAUNCH(G, R, P, T) hipLaunchKernelGGL((pmb_kernel<G, R, P, T>), dim3(g), dim3(256), 0, s, *h_ctx, row0 * mbw, row1 * mbw, refine, gate_done, ref_epoch, d_err, d_row_done)
-#define PMB_LAUNCH_IR(G, R, T) hipLaunchKernelGGL((pmb_kernel<G, R, false, T, true>), dim3(g), dim3(256), 0, s, *h_ctx, row0 * mbw, row1 * mbw, refine, gate_done, ref_epoch, d_err, d_row_done)
-    if (h_ctx->ir_c1 > 0) { // periodic intra refresh (never with partitions: mi355enc_set_intra_refresh refuses them); a picture without refresh columns has no clean bound either
-        if (h_ctx->t8 == 2) {
-            if (gate_done && d_row_done) PMB_LAUNCH_IR(true, true, 2);
-            else if (gate_done) PMB_LAUNCH_IR(true, false, 2);
-            else PMB_LAUNCH_IR(false, false, 2);
-        } else if (h_ctx->t8) {
-            if (gate_done && d_row_done) PMB_LAUNCH_IR(true, true, 1);
-            else if (gate_done) PMB_LAUNCH_IR(true, false, 1);
-            else PMB_LAUNCH_IR(false, false, 1);
-        } else if (gate_done && d_row_done) PMB_LAUNCH_IR(true, true, 0);
-        else if (gate_done) PMB_LAUNCH_IR(true, false, 0);
-        else PMB_LAUNCH_IR(false, false, 0);
-    } else if (h_ctx->t8 == 2) { // High profile, 4x4 or 8x8 transform chosen per inter macroblock
-        if (gate_done && d_row_done) PMB_LAUNCH(true, true, false, 2);
-        else if (gate_done) PMB_LAUNCH(true, false, false, 2);
-        else PMB_LAUNCH(false, false, false, 2);
-    } else if (h_ctx->t8) { // High profile: 8x8 transform for the inter macroblocks' luma (no partitions on this path)
-        if (gate_done && d_row_done) PMB_LAUNCH(true, true, false, 1);
-        else if (gate_done) PMB_LAUNCH(true, false, false, 1);
-        else PMB_LAUNCH(false, false, false, 1);
-    } else if (h_ctx->partitions) {
-        if (gate_done && d_row_done) PMB_LAUNCH(true, true, true, 0);
-        else if (gate_done) PMB_LAUNCH(true, false, true, 0);
-        else PMB_LAUNCH(false, false, true, 0);
-    } else if (gate_done && d_row_done) PMB_LAUNCH(true, true, false, 0);
-    else if (gate_done) PMB_LAUNCH(true, false, false, 0);
-    else PMB_LAUNCH(false, false, false, 0);
-#undef PMB_LAUNCH
-#undef PMB_LAUNCH_IR
+// The fused P stage's instantiations: [intra refresh][body: plain, partitions, 8x8 transform (t8 1), transform chosen per macroblock (t8 2)][pmb_gate_t].
+// (Intra refresh never comes with partitions: mi355enc_set_intra_refresh refuses them.)
+typedef void (*pmb_fn_t)(const frame_ctx_t, int, int, int, const unsigned *, unsigned, unsigned *, unsigned *);
+#define PMB_GATES(P, T, IR) {pmb_kernel<false, false, P, T, IR>, pmb_kernel<true, false, P, T, IR>, pmb_kernel<true, true, P, T, IR>}
+static const pmb_fn_t k_pmb_table[2][4][3] = {
+    {PMB_GATES(false, 0, false), PMB_GATES(true, 0, false), PMB_GATES(false, 1, false), PMB_GATES(false, 2, false)},
+    {PMB_GATES(false, 0, true), {nullptr, nullptr, nullptr}, PMB_GATES(false, 1, true), PMB_GATES(false, 2, true)}};
+#undef PMB_GATES
+int k_launch_pmb(const frame_ctx_t *h_ctx, int mbw, const pmb_launch_t *l, hipStream_t s) {
+    const int n = mbw * h_ctx->mbh;
+    if (n <= 0) return 0;
+    if ((l->gate != PMB_IN_ORDER && !l->gate_done) || (l->gate == PMB_GATED_ROWS && !l->row_done) || l->gate < PMB_IN_ORDER || l->gate > PMB_GATED_ROWS) return -1;
+    const int ir = h_ctx->ir_c1 > 0; // periodic intra refresh; a picture without refresh columns has no clean bound either
+    const int body = h_ctx->t8 == 2 ? 3 : h_ctx->t8 ? 2 : (!ir && h_ctx->partitions) ? 1 : 0; // (High profile: no partitions on that path)
+    hipLaunchKernelGGL(k_pmb_table[ir][body][l->gate], dim3((n + 3) / 4), dim3(256), 0, s, *h_ctx, 0, n, l->refine, l->gate_done, l->ref_epoch, l->err, l->row_done);
+    return 0;
 }

@@ -37,6 +37,9 @@ typedef struct {
 #ifndef MI355_BAND_ROWS
 #define MI355_BAND_ROWS 4 /* macroblock rows per band of the band deblocker (the intra band kernel has bands of its own height, k_intra_band_rows()) */
 #endif
+#ifndef DB_CUT_MIN_MBW
+#define DB_CUT_MIN_MBW 60 /* rows at least this long are walked in two parts (A/B, alternating processes: 2160p +6...9 %, 1080p +2 %, 720p +5 %, 640 x 368 -3 %: two workgroups' prologues cost more than twenty columns save) */
+#endif
 /* Words that one workgroup publishes and others poll (pmb_kernel's row counts, intra_p_kernel's progress words) lie this many words apart: one
  * per 4 KB, i.e. on different memory channels -- dozens of waves polling neighbouring words of one cache line make its channel a hot spot. */
 #ifndef MI355_PROG_STRIDE
@@ -104,6 +107,55 @@ typedef struct {
     int32_t ir_clean;
 } frame_ctx_t;
 
+/* ---- the two launches that wait on the device for other kernels, described by value (the decisions: plan_launches(), enc_plan.hpp) */
+/* the band deblocker's kernel: an IDR picture (every edge has work) | a P picture | ... whose movers follow the intra macroblock rows' progress words
+ * (intra_p_kernel beside it) | ... whose intra macroblock rows lead the launch itself, one workgroup per row */
+typedef enum { DB_ALL_INTRA, DB_P, DB_P_FOLLOWS_IP, DB_P_FUSED_IP } db_variant_t;
+/* the fused P stage: in stream order | each workgroup waits for the reference's band-done words | ... and counts every macroblock for its row */
+typedef enum { PMB_IN_ORDER, PMB_GATED, PMB_GATED_ROWS } pmb_gate_t;
+/* The workgroups of one deblocking launch over a whole picture.  counted: two per band (luma, chroma), four where every band is walked as two parts (the cut) --
+ * twelve waves at more than 100 VGPRs each, a compute unit's worth, and each counts itself in the `started` word as it is placed.  grid: those behind what leads
+ * the launch -- the picture's intra macroblock rows (DB_P_FUSED_IP: one workgroup per row), or the QP_Y chain's workgroup.  The launcher's grid, what a launch
+ * adds to the host's `started` total and open()'s wait_room all come from here. */
+typedef struct { int counted, grid; } db_wgs_t;
+static inline db_wgs_t db_launch_wgs(int mbh, db_variant_t v, int parts, int qpc) {
+    db_wgs_t w;
+    w.counted = (parts ? 4 : 2) * ((mbh + MI355_BAND_ROWS - 1) / MI355_BAND_ROWS);
+    w.grid = w.counted + (v == DB_P_FUSED_IP ? mbh : qpc ? 1 : 0);
+    return w;
+}
+/* One deblocking launch.  The launcher chooses its kernel by `variant` and nothing else; a pointer marked "may be null" switches one wait or one publication off,
+ * every other one the variant names must be there. */
+typedef struct {
+    db_variant_t variant;
+    int parts;                    /* P pictures: every band as two workgroups, cut at a column where the filter does nothing (part_cnt) */
+    int qpc;                      /* adaptive quantisation: the launch's first workgroup resolves the QP_Y chain and counts the rows in *qpc_word from qpc_base */
+    int ib_rows;                  /* rows per intra band (iband_done's granularity; 0: the deblocker's own bands) */
+    unsigned *err;                /* the sticky error word */
+    void *gran;                   /* uint2: the strips between bands, epoch-tagged granules */
+    unsigned *partab;             /* per-edge parameter words (prologue -> movers) */
+    unsigned *band_done;          /* may be null: DB_DONE_COPIES x {luma, chroma} per band = the picture's epoch once the band is final in memory */
+    unsigned *started;            /* may be null: counts the workgroups placed */
+    const unsigned *iband_done;   /* may be null (DB_ALL_INTRA): the picture's intra wavefront is still running; a band waits for its flags */
+    const unsigned *row_done;     /* may be null unless DB_P_FUSED_IP: pmb_kernel<GATED, ROWS> of this picture is still running; per macroblock row, it counts up to row_need */
+    unsigned row_need;
+    unsigned *ip_progress;        /* DB_P_FOLLOWS_IP, DB_P_FUSED_IP: the intra macroblock rows' progress words */
+    uint8_t *ip_strips;           /* DB_P_FUSED_IP: ... the bottom lines they publish */
+    unsigned *ip_done;            /* DB_P_FUSED_IP: ... and each row counts itself here when its records and levels are in memory */
+    unsigned *qpc_word; unsigned qpc_base;
+    unsigned *part_cnt;           /* parts: k_deblock_part_bytes() of words, zeroed once -- 2 counters per band ({luma, chroma}: each part adds one when its lines are in
+                                     memory; the counts only grow), then 2 uint2 granules {cut column, picture epoch} per band that the band below reads
+                                     (cut 0: an idle band, mbw: walked whole) */
+} db_launch_t;
+/* One launch of the fused P stage */
+typedef struct {
+    pmb_gate_t gate;
+    int refine;
+    const unsigned *gate_done; unsigned ref_epoch; /* PMB_GATED*: the reference's band-done words; a wave waits until the bands it reads carry ref_epoch */
+    unsigned *row_done;                            /* PMB_GATED_ROWS: one count per macroblock row, + mbw per launch */
+    unsigned *err;
+} pmb_launch_t;
+
 #ifdef __cplusplus
 }
 #endif
@@ -112,40 +164,23 @@ typedef struct {
 #include <hip/hip_runtime.h>
 /* launchers (k_*.hip); all asynchronous on `s`.  h_ctx: HOST copy of the context, passed to the kernel by value
  * (kernarg segment); d_ctx: device copy, for the kernels that are replayed from a hipGraph. */
-void k_launch_me(const frame_ctx_t *h_ctx, int mbw, int row0, int row1, hipStream_t s);
+/* (the P-picture launchers cover the whole picture: mbw x h_ctx->mbh macroblocks) */
+void k_launch_me(const frame_ctx_t *h_ctx, int mbw, hipStream_t s);
 void k_launch_copy_luma(const frame_ctx_t *h_ctx, hipStream_t s); /* I pictures: source luma -> psrc_out (rows beyond the visible picture repeat its last row) */
-void k_launch_me_select(const frame_ctx_t *h_ctx, int mbw, int row0, int row1, const imv_t *in, imv_t *out, const imv_t *prev, int mode, hipStream_t s); /* mode 0: recompute all; 1 / 2: copy where the predictors equal zeros / those of `prev` */
-void k_launch_me_select_all(const frame_ctx_t *h_ctx, int mbw, int row0, int row1, hipStream_t s); /* the ME_ITERS iterations */
+void k_launch_me_select(const frame_ctx_t *h_ctx, int mbw, const imv_t *in, imv_t *out, const imv_t *prev, int mode, hipStream_t s); /* mode 0: recompute all; 1 / 2: copy where the predictors equal zeros / those of `prev` */
+void k_launch_me_select_all(const frame_ctx_t *h_ctx, int mbw, hipStream_t s); /* the ME_ITERS iterations */
 void k_launch_intra_p(const frame_ctx_t *h_ctx, int mbw, int mbh, unsigned *d_progress /* one word per macroblock row */, uint8_t *d_strips /* 32 bytes per macroblock */,
                       unsigned *d_err, hipStream_t s);
 const imv_t *k_final_imv(const frame_ctx_t *h_ctx); /* where the last selection iteration leaves the field */
-void k_launch_imv_to_mbi(const frame_ctx_t *h_ctx, int mbw, int row0, int row1, hipStream_t s); // whole-sample field -> records, for the two-kernel (8x8 transform) path
-void k_launch_subpel(const frame_ctx_t *h_ctx, int mbw, int row0, int row1, hipStream_t s);
-// gate_done (may be null): the reference picture's band deblocker may still be running; a wave waits until the band that holds macroblock row r + 2 carries ref_epoch
-void k_launch_pmb(const frame_ctx_t *h_ctx, int mbw, int row0, int row1, int refine, const unsigned *gate_done, unsigned ref_epoch, unsigned *d_err,
-                  unsigned *d_row_done /* gated launches: one count per macroblock row, + mbw per launch */, hipStream_t s); // fused refinement + inter (4x4 transform)
-void k_launch_inter(const frame_ctx_t *h_ctx, int mbw, int row0, int row1, hipStream_t s);
+void k_launch_subpel(const frame_ctx_t *h_ctx, int mbw, hipStream_t s);
+int k_launch_pmb(const frame_ctx_t *h_ctx, int mbw, const pmb_launch_t *l, hipStream_t s); // fused refinement + inter; -1: a word the gate needs is missing (nothing is launched)
+void k_launch_inter(const frame_ctx_t *h_ctx, int mbw, hipStream_t s);
 void k_launch_intra_analyse(const frame_ctx_t *h_ctx, int mbw, int mbh, int gate_p, hipStream_t s); /* gate_p: P picture -- only macroblocks whose search cost reaches INTRA_GATE */
 void k_launch_intra_diag(const frame_ctx_t *d_ctx, int mbw, int mbh, int diag, hipStream_t s);
 void k_launch_deblock_diag(const frame_ctx_t *d_ctx, int mbw, int mbh, int diag, hipStream_t s);
 int k_deblock_bands16(int mbh);
-int k_deblock_launch_wgs(int mbw, int mbh, int all_intra, int fused_ip); // workgroups of a launch over the whole picture, each a compute unit's worth
- // flags: per-band "has work" words of this picture's set
-// d_ip_progress (may be null): intra_p_kernel of the same picture is still running; the band kernel follows its per-row progress words
-// d_iband_done (may be null; all-intra pictures): the intra band kernel of the same picture is still running; a band waits for its flags
-/* returns the number of workgroups that will count themselves in *d_started */
-int k_launch_deblock_bands(const frame_ctx_t *h_ctx, int mbh, int band0, int band1, unsigned *d_err, uint2 *d_gran, unsigned *d_partab, const unsigned *d_ip_progress,
-                            const unsigned *d_iband_done, int ib_rows /* rows per intra band */,
-                            unsigned *d_band_done /* may be null: DB_DONE_COPIES x {luma, chroma} per band = the picture's epoch once the band is final in memory */,
-                            unsigned *d_started /* may be null: counts the workgroups placed */,
-                            const unsigned *d_row_done /* may be null: pmb_kernel<GATED> of this picture is still running; per macroblock row, it counts up to row_need */, unsigned row_need,
-                            uint8_t *d_ip_strips, unsigned *d_ip_done /* both non-null (with d_ip_progress and d_row_done): the picture's intra macroblock rows run as the launch's
-                                                                            leading workgroups; each counts itself in d_ip_done when its records and levels are in memory */,
-                            unsigned *d_qpc, unsigned qpc_base /* adaptive quantisation (h_ctx->qp_off): the launch's first workgroup resolves the QP_Y chain and counts the rows in *d_qpc from qpc_base */,
-                            unsigned *d_part_cnt /* may be null; 6 words per band, zeroed once: P pictures walk every band as two workgroups, cut at a column where the filter does nothing.
-                                                    Words 0 .. 2*nb-1 (nb bands): the parts' counters, {luma, chroma} per band -- each part adds one when its lines are in
-                                                    memory (the counts only grow: two per band, plane and launch); then 2*nb uint2 granules {cut column, picture epoch},
-                                                    {luma, chroma} per band, that the band below reads (0: an idle band, mbw: walked whole) */, hipStream_t s);
+int k_launch_deblock_bands(const frame_ctx_t *h_ctx, const db_launch_t *l, hipStream_t s); /* all the picture's bands in one launch; -1: a word the variant needs is missing (nothing is launched) */
+size_t k_deblock_part_bytes(int mbh); /* db_launch_t::part_cnt: 6 words per band (0: this build walks every band whole) */
 int k_intra_band_rows(void);
 size_t k_deblock_partab_bytes(int mbw, int mbh); // scratch of the band kernel: one parameter word per (edge, segment) of every macroblock
 size_t k_deblock_gran_bytes(int mbw, int mbh);

@@ -19,7 +19,7 @@ MBINFO_DTYPE = np.dtype(
 
 FETCH_RECON_Y, FETCH_RECON_UV, FETCH_PREFILTER_Y, FETCH_PREFILTER_UV, FETCH_MBINFO, FETCH_LEVELS = range(6)
 FETCH_SCALE_TABLES = 6  # the device's copy of the scale tables (Encoder.scale_tables_device())
-FETCH_BAND_CUTS, FETCH_ERROR_WORD = 102, 103  # development: Encoder.band_cuts(), Encoder.error_word()
+FETCH_BAND_CUTS, FETCH_ERROR_WORD, FETCH_SYNC_WORDS = 102, 103, 104  # development: Encoder.band_cuts(), Encoder.error_word(), Encoder.sync_words()
 BAND_ROWS = 4  # MI355_BAND_ROWS: macroblock rows per band of the band deblocker
 ERR_ARG, ERR_STATE = -1, -6
 ERR_OVERFLOW = -5
@@ -1232,6 +1232,13 @@ class Encoder:
         a = np.zeros(1, np.uint32)
         self._chk(self.L.mi355enc_fetch(self.h, FETCH_ERROR_WORD, _p(a), a.nbytes), "fetch")
         return int(a[0])
+
+    def sync_words(self):
+        """Development: the device's side of debug_get_counters()'s four totals, read with the compute streams idle -- "db_started_total", "ip_done_total",
+        "qpc_total": the three counting words; "row_done": every macroblock row's count (each equals pmb_rows_total once its launches are through)."""
+        a = np.zeros(3 + self.mbh, np.uint32)
+        self._chk(self.L.mi355enc_fetch(self.h, FETCH_SYNC_WORDS, _p(a), a.nbytes), "fetch")
+        return {"db_started_total": int(a[0]), "ip_done_total": int(a[1]), "qpc_total": int(a[2]), "row_done": a[3:].copy()}
 
     # ---- single-stage entry points (coded-size host planes)
     def stage_me(self, cur_y, ref_y, qp):

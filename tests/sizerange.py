@@ -41,7 +41,7 @@ WAIT_WGS_MAX = 192   # an MI355X has 256 compute units; a quarter stays free of 
 
 
 def wait_wgs(mbw, mbh):
-    """workgroups of a P picture's band-deblocking launch with three pictures in flight (k_deblock.hip, k_deblock_launch_wgs): two per band of four rows, four where
+    """workgroups of a P picture's band-deblocking launch with three pictures in flight (mi355enc_dev.h, db_launch_wgs): two per band of four rows, four where
     the bands are walked in two parts (mbw >= 60), and one per macroblock row where the intra rows ride in the launch (up to 3600 macroblocks)"""
     return (4 if mbw >= 60 else 2) * ((mbh + 3) // 4) + (mbh if mbw * mbh <= 3600 else 0)
 
