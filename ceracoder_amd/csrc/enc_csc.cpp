@@ -68,7 +68,7 @@ void csc_resolve(mi355enc_t *h) {
 
 // the part of the coded surfaces that is picture: everything, or with a geometry the destination rectangle mapped through the orientation -- up to the surfaces'
 // edge where it reaches the visible picture's (a margin sample is what its clamped visible source is)
-static void yuv_rect(const mi355enc_t *h, int rect[4]) {
+void yuv_rect(const mi355enc_t *h, int rect[4]) {
     rect[0] = 0; rect[1] = h->W; rect[2] = 0; rect[3] = h->H;
     if (!h->geom_on) return;
     const int m = h->orient;
@@ -106,6 +106,7 @@ int mi355enc_set_colorimetry(mi355enc_t *h, int full_range, int primaries, int t
     if (h->n_submitted) return MI355ENC_ERR_STATE; // (what the samples mean is fixed from the stream's first picture on)
     h->col_full = full_range; h->col_prim = primaries; h->col_trc = transfer; h->col_mat = matrix;
     csc_resolve(h);
+    adjust_retable(h); // (black level and scale of the picture controls are the output range's)
     return MI355ENC_OK;
 }
 

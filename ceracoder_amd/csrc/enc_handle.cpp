@@ -344,6 +344,7 @@ void mi355enc_close(mi355enc_t *h) {
     image_free(h);
     rate_free(h);
     hdr_free(h);
+    adjust_free(h);
     for (int k = 0; k < NSET; k++) {
         if (h->d_surf[k]) (void)hipFree(h->d_surf[k]);
         for (int i = 0; i < 3; i++) if (h->d_imv[k][i]) (void)hipFree(h->d_imv[k][i]);
@@ -411,6 +412,8 @@ int mi355enc_fetch(mi355enc_t *h, int what, void *dst, size_t n) {
     case MI355ENC_FETCH_PREFILTER_Y: src = h->d_pre_y; need = h->ysz; break;
     case MI355ENC_FETCH_PREFILTER_UV: src = h->d_pre_uv; need = h->csz; break;
     case MI355ENC_FETCH_MBINFO: src = h->last_slot ? h->last_slot->h_mbi : nullptr; need = (size_t)h->nmb * sizeof(mb_info_t); host = true; break;
+    case MI355ENC_FETCH_SOURCE_Y: src = h->last_slot && h->last_slot->src_y == h->last_slot->d_src_y ? h->last_slot->d_src_y : nullptr; need = h->ysz; break;
+    case MI355ENC_FETCH_SOURCE_UV: src = h->last_slot && h->last_slot->src_y == h->last_slot->d_src_y ? h->last_slot->d_src_uv : nullptr; need = h->csz; break;
     case MI355ENC_FETCH_SCALE_TABLES: src = h->d_scale_tab; need = h->scale_tab_bytes; break;
     case MI355ENC_FETCH_LEVELS: src = h->last_slot ? h->d_levels_set[h->last_slot->set] : nullptr; need = (size_t)h->nmb * MB_LEVELS * 2; break; // dense, from HBM
     /* development, the wait words (enc_sync.hpp), read with the compute streams idle: 102 per band and plane the parts' counter, then {cut column, epoch} of the last

@@ -11,6 +11,7 @@
 //   enc_jpeg.cpp      MJPEG input: coefficient buffers, host decode, transfer + launch, its stage entry points
 //   enc_snapshot.cpp  JPEG stills: request / take, the blocks the levels land in, the launch, its stage entry points
 //   enc_csc.cpp       colorimetry: the setters, the RGB matrix and the YUV -> YUV table, the colour step's launch, their stage entry points
+//   enc_adjust.cpp    picture controls: setter, latch, the two launch forms and the scratch plane, its stage entry point
 //   enc_rate.cpp      frame-rate conversion: setter, the plan's step and commit per submit, keep buffer, mix / keep / repeat launches, its stage entry point
 //   enc_stages.cpp    single-stage entry points (parity tests, probes) and the host-only stages
 #ifndef MI355_ENC_INTERNAL_HPP
@@ -33,6 +34,7 @@
 #include "mi355enc_dev.h"
 #include "snapshot_host.h"
 #include "hdr_host.h"
+#include "adjust_host.h"
 #include "enc_plan.hpp"
 #include "enc_sync.hpp"
 
@@ -77,6 +79,10 @@ struct snap_block_t {
     mi355enc_snapshot_info_t info;
 };
 
+// Picture controls (mi355enc_set_adjust): a checked parameter set with what follows from it -- which parts are not neutral (ADJUST_*; 0: off),
+// the luma table and the chroma rotation as built for the handle's output range by the thread that set it.
+struct adjust_set_t { mi355enc_adjust_t a; int parts; uint8_t luma[256]; int32_t chroma[2]; };
+
 struct slot_t {
     frame_ctx_t *h_ctx;   // pinned
     mb_info_t *h_mbi;     // pinned
@@ -112,6 +118,8 @@ struct slot_t {
     int snap; mi355enc_snapshot_req_t snap_req;
     // the colour step: this picture's samples are converted in ingest_end (latched with the slot; an RGB picture, converted straight to the output, clears it)
     bool yuv_step;
+    // picture controls: what submit latched for this picture (adj.parts 0: nothing); applied once, to the input's own slot, in ingest_end
+    adjust_set_t adj;
 };
 
 struct mi355enc {
@@ -213,6 +221,14 @@ struct mi355enc {
     int hdr_transfer = 0, hdr_full = 0, hdr_peak = 0, hdr_target = 0, hdr_key = -1;
     int32_t *h_hdr = nullptr, *d_hdr = nullptr;
     hipStream_t hdr_stream = nullptr;
+    // picture controls (mi355enc_set_adjust): what the control thread set last (under adj_mu; submit latches it per input picture), what the
+    // last collected picture carried, and the scratch luma plane of the stencil form (W x H bytes, allocated by the first sharpened picture; adj_bytes: its size), which
+    // changes places with a slot's luma surface whenever the stencil has written all of it
+    std::mutex adj_mu;
+    adjust_set_t adj_cur = {}, adj_last = {};
+    bool adj_last_have = false;
+    uint8_t *d_adj = nullptr;
+    size_t adj_bytes = 0;
     // frame-rate conversion (mi355enc_set_rate_conversion).  rate.mode 0: off, and nothing below is used but last_count.  rate.max_fill is
     // clamped to pipeline_depth.  rate_plan: the rule's state; ingest_begin steps a copy of it (rate_next, with what the step yields: rate_n pictures, their pts
     // and weights) and ingest_end commits it once the pictures are enqueued -- a submit that fails in between has not advanced the plan.  d_keep: one NV12
@@ -375,6 +391,15 @@ static inline bool fmt_is_rgb(int fmt) { return fmt >= MI355ENC_FMT_BGRX && fmt 
 // the colour step on the slot's coded surfaces, behind everything enqueued on st so far: the picture part (with a geometry: the oriented destination rectangle) is
 // converted in place, the border keeps its bytes
 int yuv_draw(mi355enc_t *h, slot_t *s, hipStream_t st);
+void yuv_rect(const mi355enc_t *h, int rect[4]); // that picture part: x0, x1, y0, y1 in the coded surfaces (reaching their edge where it reaches the visible picture's)
+// enc_adjust.cpp (picture controls)
+void adjust_latch(mi355enc_t *h, slot_t *s);                 // the value set last becomes the slot's (beside overlay_latch)
+void adjust_retable(mi355enc_t *h);                          // mi355enc_set_colorimetry: the current value's tables again, for the new output range
+int adjust_draw(mi355enc_t *h, slot_t *s, hipStream_t st);   // the slot's adjustment on its coded surfaces, behind everything enqueued on st so far; nothing with none
+void adjust_collected(mi355enc_t *h, slot_t *s);             // collect(): books what the picture carried as the last picture's
+void adjust_free(mi355enc_t *h);
+bool adjust_time_ready(mi355enc_t *h, bool stencil);         // mi355enc_time_stage 23 / 24: the value set last is active and of that form
+int adjust_time_launch(mi355enc_t *h, slot_t *s);            // ... and its launches on the main stream
 // enc_hdr.cpp (HDR input)
 // true: the handle tone-maps and this input is not one it takes (a format other than the three 10-bit ones -- fmt -1: an entry point that takes none of them --
 // or an output matrix outside 1, 5, 6, 2): the submit fails with MI355ENC_ERR_ARG before anything is latched

@@ -226,9 +226,10 @@ int mi355enc_debug_set_counters(mi355enc_t *h, const mi355enc_counters_t *in) {
     return MI355ENC_OK;
 }
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
-    if (!h || !avg_ms || iters < 1 || stage < 0 || stage > 22) return MI355ENC_ERR_ARG;
+    if (!h || !avg_ms || iters < 1 || stage < 0 || stage > 24) return MI355ENC_ERR_ARG;
     if (stage == 17 && !h->yuv_on) return MI355ENC_ERR_STATE; // (the handle has no conversion)
     if (stage >= 19 && stage <= 21 && (!h->hdr_on || hdr_refuses(h, MI355ENC_FMT_P010))) return MI355ENC_ERR_STATE; // (mi355enc_set_hdr_input first, and an output matrix it converts to)
+    if (stage >= 23 && !adjust_time_ready(h, stage == 24)) return MI355ENC_ERR_STATE; // (mi355enc_set_adjust first: 23 with sharpen 0, 24 with sharpen set)
     if (stage == 18 && !h->d_keep) return MI355ENC_ERR_STATE; // (frame-rate conversion off, or hold mode without a keep buffer: there is no mix)
     if (stage == 14 && !h->d_scale_tab) return MI355ENC_ERR_STATE; // (mi355enc_set_input_size or mi355enc_set_input_geometry first)
     if (h->pending) return MI355ENC_ERR_STATE;
@@ -246,7 +247,7 @@ int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
         stage_touched(h);
     }
     if (stage == 11) { int r = quality_alloc(h); if (r) return r; } // (the block of the stage entry points)
-    if (((stage >= 5 && stage <= 7) || stage == 13 || stage == 14 || stage >= 19) && !s->d_raw) { // input conversion (5 I420, 6 YUY2, 7 UYVY), orientation (13), scale / geometry (14): any bytes will do as a source
+    if (((stage >= 5 && stage <= 7) || stage == 13 || stage == 14 || (stage >= 19 && stage <= 22)) && !s->d_raw) { // input conversion (5 I420, 6 YUY2, 7 UYVY), orientation (13), scale / geometry (14): any bytes will do as a source
         HIPCHK(hipMalloc((void **)&s->d_raw, raw_bytes(h)));
         HIPCHK(hipMemsetAsync(s->d_raw, 0x55, raw_bytes(h), h->stream));
     }
@@ -285,6 +286,7 @@ int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
             else if (stage == 16) { int r = snapshot_time_launch(h, s); if (r) return r; }
             else if (stage == 17) { int r = yuv_draw(h, s, h->stream); if (r) return r; } // the colour step, in place on slot 0's surfaces (whatever they hold)
             else if (stage == 18) { int r = rate_mix(h, s, s, 128, true, h->stream); if (r) return r; } // the mix of the keep buffer and slot 0's surfaces, in place as the encoder runs it
+            else if (stage >= 23) { int r = adjust_time_launch(h, s); if (r) return r; } // the picture controls set last, in place on slot 0's surfaces: 23 the pointwise form, 24 the stencil form with the hand-back of its scratch plane
             else if (stage >= 19) { // the conversion launch of a 10-bit picture in the raw staging buffer: 19 P010, 20 I420_10, 21 V210 tone-mapped; 22 P010 plain (section 20)
                 const int fmt = stage == 22 ? MI355ENC_FMT_P010 : MI355ENC_FMT_P010 + stage - 19, w = h->cfg.width, ht = h->cfg.height;
                 fmt_plane_t pl[3];

@@ -106,6 +106,10 @@ typedef struct {
      * yielded pictures their number -- a FIFO in submission order, so that collected access units meet their GstVideoCodecFrame: a frame's pictures but the last
      * are pushed as buffers of their own, the last one finishes the frame */
     gint rate_mode, out_fps_n, out_fps_d, max_fill;
+    /* picture controls on the device (mi355enc_set_adjust): brightness, contrast, hue, saturation with videobalance's names, ranges and
+     * defaults, gamma, sharpen, sharpen-threshold; stored in the library's integers (the doubles as thousandths, lround) under the object lock and forwarded like
+     * the overlay's text -- any thread, at any time */
+    mi355enc_adjust_t adj;
     gint hdr_input, hdr_peak, hdr_target; /* hdr-input (0 off, 16 pq, 18 hlg), hdr-peak-nits, hdr-target-nits: read at the next set_format */
     gint open_rate;           /* 0: conversion off */
     GstClockTime tick;        /* duration of an output picture */
@@ -135,7 +139,8 @@ enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME
        PROP_CROP_LEFT, PROP_CROP_RIGHT, PROP_CROP_TOP, PROP_CROP_BOTTOM, PROP_ADD_BORDERS, PROP_UPSCALE, PROP_BORDER_COLOR,
        PROP_IMG_LOCATION, PROP_IMG_X, PROP_IMG_Y, PROP_IMG_ALPHA,
        PROP_SNAP_LOCATION, PROP_SNAP_INTERVAL, PROP_SNAP_QUALITY, PROP_SNAP_REDUCE, PROP_SNAP_SOURCE,
-       PROP_OUTPUT_COLORIMETRY, PROP_RATE_CONVERSION, PROP_OUTPUT_FRAMERATE, PROP_MAX_FILL, PROP_HDR_INPUT, PROP_HDR_PEAK_NITS, PROP_HDR_TARGET_NITS };
+       PROP_OUTPUT_COLORIMETRY, PROP_RATE_CONVERSION, PROP_OUTPUT_FRAMERATE, PROP_MAX_FILL, PROP_HDR_INPUT, PROP_HDR_PEAK_NITS, PROP_HDR_TARGET_NITS,
+       PROP_ADJ_BRIGHTNESS, PROP_ADJ_CONTRAST, PROP_ADJ_HUE, PROP_ADJ_SATURATION, PROP_ADJ_GAMMA, PROP_ADJ_SHARPEN, PROP_ADJ_SHARPEN_THRESHOLD };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
     GST_STATIC_CAPS("video/x-raw, format=(string){ NV12, I420, YUY2, UYVY, Y42B, Y444, YV12, NV21, BGRx, RGBx, xRGB, xBGR, BGRA, RGBA, ARGB, ABGR, BGR, RGB, P010_10LE, I420_10LE, v210, GRAY8 }, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]; "
@@ -232,6 +237,10 @@ static void overlay_forward(GstMi355H264Enc *s) {
     if (mi355enc_set_overlay_style(s->enc, &s->ov_style) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the overlay style: it keeps its previous one");
     if (mi355enc_set_overlay_text(s->enc, s->ov_text) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the overlay text");
 }
+/* stored picture controls -> the encoder, if one is open (object lock held; the library builds two small tables and stores: no GPU call, any thread) */
+static void adjust_forward(GstMi355H264Enc *s) {
+    if (s->enc && mi355enc_set_adjust(s->enc, &s->adj) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the picture controls: it keeps its previous ones");
+}
 static void overlay_store_text(GstMi355H264Enc *s, const gchar *t) { g_strlcpy(s->ov_text, t ? t : "", sizeof s->ov_text); }
 
 /* stored image, place and alpha -> layer 0 of the encoder, if one is open (object lock held; the library only copies and stores: no GPU call, any thread).
@@ -295,6 +304,13 @@ static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *
     case PROP_HDR_INPUT: s->hdr_input = g_value_get_enum(val); break; /* (these three are read at the next set_format) */
     case PROP_HDR_PEAK_NITS: s->hdr_peak = g_value_get_int(val); break;
     case PROP_HDR_TARGET_NITS: s->hdr_target = g_value_get_int(val); break;
+    case PROP_ADJ_BRIGHTNESS: s->adj.brightness = (int)lround(1000.0 * g_value_get_double(val)); adjust_forward(s); break;
+    case PROP_ADJ_CONTRAST: s->adj.contrast = (int)lround(1000.0 * g_value_get_double(val)); adjust_forward(s); break;
+    case PROP_ADJ_HUE: s->adj.hue = (int)lround(1000.0 * g_value_get_double(val)); adjust_forward(s); break;
+    case PROP_ADJ_SATURATION: s->adj.saturation = (int)lround(1000.0 * g_value_get_double(val)); adjust_forward(s); break;
+    case PROP_ADJ_GAMMA: s->adj.gamma = (int)lround(1000.0 * g_value_get_double(val)); adjust_forward(s); break;
+    case PROP_ADJ_SHARPEN: s->adj.sharpen = g_value_get_int(val); adjust_forward(s); break;
+    case PROP_ADJ_SHARPEN_THRESHOLD: s->adj.sharpen_threshold = g_value_get_int(val); adjust_forward(s); break;
     case PROP_OUTPUT_COLORIMETRY: g_free(s->out_colorimetry); s->out_colorimetry = g_value_dup_string(val); break; /* (read at the next set_format) */
     case PROP_IMG_X: s->img_x = g_value_get_int(val); image_forward(s, FALSE); break;
     case PROP_IMG_Y: s->img_y = g_value_get_int(val); image_forward(s, FALSE); break;
@@ -360,6 +376,13 @@ static void get_property(GObject *obj, guint id, GValue *val, GParamSpec *ps) {
     case PROP_HDR_INPUT: g_value_set_enum(val, s->hdr_input); break;
     case PROP_HDR_PEAK_NITS: g_value_set_int(val, s->hdr_peak); break;
     case PROP_HDR_TARGET_NITS: g_value_set_int(val, s->hdr_target); break;
+    case PROP_ADJ_BRIGHTNESS: g_value_set_double(val, s->adj.brightness / 1000.0); break;
+    case PROP_ADJ_CONTRAST: g_value_set_double(val, s->adj.contrast / 1000.0); break;
+    case PROP_ADJ_HUE: g_value_set_double(val, s->adj.hue / 1000.0); break;
+    case PROP_ADJ_SATURATION: g_value_set_double(val, s->adj.saturation / 1000.0); break;
+    case PROP_ADJ_GAMMA: g_value_set_double(val, s->adj.gamma / 1000.0); break;
+    case PROP_ADJ_SHARPEN: g_value_set_int(val, s->adj.sharpen); break;
+    case PROP_ADJ_SHARPEN_THRESHOLD: g_value_set_int(val, s->adj.sharpen_threshold); break;
     case PROP_OUTPUT_COLORIMETRY: g_value_set_string(val, s->out_colorimetry ? s->out_colorimetry : ""); break;
     case PROP_IMG_X: g_value_set_int(val, s->img_x); break;
     case PROP_IMG_Y: g_value_set_int(val, s->img_y); break;
@@ -762,6 +785,7 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     mi355enc_set_bitrate(e, target_bps(s)); /* a write that raced with open() must not be lost */
     overlay_forward(s);                     /* ... nor the overlay's text and style, set before the device was opened */
     image_forward(s, TRUE);                 /* ... nor the image layer */
+    adjust_forward(s);                      /* ... nor the picture controls */
     GST_OBJECT_UNLOCK(s);
     g_mutex_unlock(&s->snap_enc_mu);
     s->max_au = mi355enc_max_au_bytes(e);
@@ -1208,6 +1232,13 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
     g_object_class_install_property(g, PROP_HDR_INPUT, g_param_spec_enum("hdr-input", "HDR input", "the 10-bit input (P010_10LE, I420_10LE, v210) is PQ or HLG with BT.2020 primaries and matrix: tone-mapped on the GPU to SDR BT.709 (or to output-colorimetry) in the conversion launch; the caps give the range; other caps are an error", hdr_input_type(), 0, F));
     g_object_class_install_property(g, PROP_HDR_PEAK_NITS, g_param_spec_int("hdr-peak-nits", "HDR source peak", "with hdr-input: the source's peak luminance in cd/m^2 (HLG: the nominal peak Lw), 400 .. 10000 (hlg: .. 2000); 0: 1000", 0, 10000, 0, F));
     g_object_class_install_property(g, PROP_HDR_TARGET_NITS, g_param_spec_int("hdr-target-nits", "SDR target peak", "with hdr-input: the luminance the SDR peak stands for in cd/m^2, 100 .. 400; 0: 203 (BT.2408's reference white)", 0, 400, 0, F));
+    g_object_class_install_property(g, PROP_ADJ_BRIGHTNESS, g_param_spec_double("brightness", "Brightness", "picture controls on the GPU (videobalance's property): added to the luma, in units of the luma scale", -1.0, 1.0, 0.0, F));
+    g_object_class_install_property(g, PROP_ADJ_CONTRAST, g_param_spec_double("contrast", "Contrast", "picture controls on the GPU (videobalance's property): luma gain about black", 0.0, 2.0, 1.0, F));
+    g_object_class_install_property(g, PROP_ADJ_HUE, g_param_spec_double("hue", "Hue", "picture controls on the GPU (videobalance's property): chroma rotation in units of pi", -1.0, 1.0, 0.0, F));
+    g_object_class_install_property(g, PROP_ADJ_SATURATION, g_param_spec_double("saturation", "Saturation", "picture controls on the GPU (videobalance's property): chroma gain", 0.0, 2.0, 1.0, F));
+    g_object_class_install_property(g, PROP_ADJ_GAMMA, g_param_spec_double("gamma", "Gamma", "picture controls on the GPU (the gamma element's property): t -> t^(1 / gamma) on the luma between black and white", 0.1, 10.0, 1.0, F));
+    g_object_class_install_property(g, PROP_ADJ_SHARPEN, g_param_spec_int("sharpen", "Sharpen", "picture controls on the GPU: 3 x 3 unsharp mask on the luma in sixteenths of its amount (16: original + detail); negative softens (-16: the binomial blur); 0: off", -16, 64, 0, F));
+    g_object_class_install_property(g, PROP_ADJ_SHARPEN_THRESHOLD, g_param_spec_int("sharpen-threshold", "Sharpen threshold", "with sharpen > 0: detail of at most this many codes is left alone (coring)", 0, 32, 0, F));
     g_object_class_override_property(g, PROP_VIDEO_DIRECTION, "video-direction"); /* GstVideoDirection: identity, 90r, 180, 90l, horiz, vert, ul-lr, ur-ll, auto -- as on videoflip */
     g_object_class_install_property(g, PROP_STATS, g_param_spec_boolean("stats", "Print stats", "Print a JSON line with counters when the encoder closes", FALSE, F));
     gst_element_class_add_static_pad_template(e, &sink_tmpl);
@@ -1227,6 +1258,7 @@ static void gst_mi355h264enc_init(GstMi355H264Enc *s) {
     s->border_color = 0x108080;
     s->out_colorimetry = NULL;
     s->hdr_input = 0; s->hdr_peak = 0; s->hdr_target = 0;
+    mi355enc_adjust_default(&s->adj);
     s->rate_mode = 0; s->out_fps_n = 0; s->out_fps_d = 1; s->max_fill = 2; s->open_rate = 0; s->tick = GST_CLOCK_TIME_NONE; s->rate_qh = s->rate_qn = 0;
     s->snap_location = NULL; s->snap_interval = 1000; s->snap_quality = 75; s->snap_reduce = 4; s->snap_source = 0; s->snap_next = GST_CLOCK_TIME_NONE; s->snap_watch = 0;
     g_mutex_init(&s->snap_mu); g_mutex_init(&s->snap_enc_mu); g_cond_init(&s->snap_cv);

@@ -204,6 +204,14 @@ int k_launch_hdr(int fmt, int hlg, const uint8_t *const planes[3], const int str
 /* the colour step (k_csc.hip; the rule: DESIGN.md section 20), in place on NV12 surfaces of W x H at stride W: the samples inside rect (x0, x1, y0, y1; even)
  * go from one (range, matrix) to another with the nine words of mi355enc_yuv_coefficients; everything outside keeps its bytes.  -1: arguments outside that */
 int k_launch_yuv_convert(uint8_t *y, uint8_t *uv, int W, int H, const int rect[4], const int *coef, hipStream_t s);
+/* picture controls (k_adjust.hip; the rule: DESIGN.md section 23), pointwise form, in place on NV12 surfaces of W x H at stride W: the samples inside rect (as
+ * k_launch_yuv_convert's) go through the luma table (256 bytes; null: the luma plane is not touched) and the chroma rotation {cu, su} (null: the chroma plane
+ * is not touched); everything outside keeps its bytes.  -1: arguments outside that, or both null */
+int k_launch_adjust(uint8_t *y, uint8_t *uv, int W, int H, const int rect[4], const uint8_t *luma, const int *chroma, hipStream_t s);
+/* ... stencil form, luma only, from y into another plane `out` of the same layout (W, H multiples of 16; vw x vh the visible size, less than 16 short of them):
+ * table (null: neutral, none), then the 3 x 3 unsharp mask with amount (-16 .. 64, not 0) and threshold thr (0 .. 32), neighbours clamped to the visible part of rect, a margin sample
+ * the result of its clamped visible position.  Writes rect's samples of `out` and at most two bytes beside its left and right edge.  -1: arguments outside that */
+int k_launch_adjust_sharpen(const uint8_t *y, uint8_t *out, int W, int H, int vw, int vh, const int rect[4], const uint8_t *luma, int amount, int thr, hipStream_t s);
 /* Downscaling of the input picture to the coded size (k_scale.hip; the rule: DESIGN.md section 10).  Tables built on the host
  * (enc_scale.cpp), five of them: 0 luma horizontal, 1 luma vertical, 2 chroma horizontal, 3 chroma vertical from 4:2:0 input, 4 chroma
  * vertical from 4:2:2 input.  Entry i of table t: first[t][i] (first source index, not clamped) and q[t][i * taps[t] + k]. */

@@ -19,6 +19,7 @@ MBINFO_DTYPE = np.dtype(
 
 FETCH_RECON_Y, FETCH_RECON_UV, FETCH_PREFILTER_Y, FETCH_PREFILTER_UV, FETCH_MBINFO, FETCH_LEVELS = range(6)
 FETCH_SCALE_TABLES = 6  # the device's copy of the scale tables (Encoder.scale_tables_device())
+FETCH_SOURCE_Y, FETCH_SOURCE_UV = 7, 8  # the last collected picture's coded source surfaces, valid until the next submit
 FETCH_BAND_CUTS, FETCH_ERROR_WORD, FETCH_SYNC_WORDS = 102, 103, 104  # development: Encoder.band_cuts(), Encoder.error_word(), Encoder.sync_words()
 BAND_ROWS = 4  # MI355_BAND_ROWS: macroblock rows per band of the band deblocker
 ERR_ARG, ERR_STATE = -1, -6
@@ -32,6 +33,7 @@ IMV_DTYPE = np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("sad", "<u2"), ("bits", "
 SURF_ROWS, SURF_COLS = 35, 36
 DROP_MAX, DROP_SKIP = 12, 255
 STAGE_ME, STAGE_INTER, STAGE_INTRA, STAGE_DEBLOCK, STAGE_SUBPEL, STAGE_CSC_I420, STAGE_CSC_YUY2, STAGE_CSC_UYVY, STAGE_ME_SELECT, STAGE_PMB, STAGE_INTRA_P, STAGE_QUALITY, STAGE_JPEG, STAGE_ORIENT, STAGE_SCALE, STAGE_IMAGE, STAGE_SNAPSHOT, STAGE_YUV_CONVERT, STAGE_RATE = range(19)
+STAGE_ADJUST_POINT, STAGE_ADJUST_SHARPEN = 23, 24  # the picture controls set last on slot 0's surfaces: pointwise form, stencil form
 STAGE_HDR_P010, STAGE_HDR_I420_10, STAGE_HDR_V210, STAGE_DEEP_P010 = 19, 20, 21, 22  # the tone-mapping launch per format, and the plain P010 launch beside it
 HDR_PQ, HDR_HLG = 16, 18  # mi355enc_set_hdr_input: the transfer's H.264 Table E-4 code point
 # mi355enc_set_orientation: GstVideoOrientationMethod's numbers
@@ -62,6 +64,8 @@ EXPORTS = [
     "mi355enc_rate_check", "mi355enc_set_rate_conversion", "mi355enc_rate_peek", "mi355enc_last_submit_count", "mi355enc_rate_stats", "mi355enc_debug_rate_bytes",
     "mi355enc_rate_plan_init", "mi355enc_rate_plan_step", "mi355enc_stage_rate",
     "mi355enc_set_hdr_input", "mi355enc_hdr_tables",
+    "mi355enc_adjust_default", "mi355enc_adjust_check", "mi355enc_adjust_tables", "mi355enc_set_adjust", "mi355enc_get_adjust", "mi355enc_last_adjust", "mi355enc_stage_adjust",
+    "mi355enc_debug_adjust_bytes",
 ]
 
 
@@ -107,6 +111,15 @@ class JpegInfo(C.Structure):
 class OverlayStyle(C.Structure):
     """mi355enc_overlay_style_t: halign / valign 0 left / top, 1 centre, 2 right / bottom; pads in luma samples; scale 0 = auto, 1 .. 8"""
     _fields_ = [("halign", C.c_int), ("valign", C.c_int), ("xpad", C.c_int), ("ypad", C.c_int), ("scale", C.c_int), ("shaded_background", C.c_int)]
+
+
+class Adjust(C.Structure):
+    """mi355enc_adjust_t: picture controls in integers -- brightness, contrast, saturation, hue, gamma in thousandths, sharpen in sixteenths, the coring threshold"""
+    _fields_ = [("brightness", C.c_int), ("contrast", C.c_int), ("saturation", C.c_int), ("hue", C.c_int), ("gamma", C.c_int), ("sharpen", C.c_int), ("sharpen_threshold", C.c_int)]
+    NAMES = ("brightness", "contrast", "saturation", "hue", "gamma", "sharpen", "sharpen_threshold")
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n in self.NAMES}
 
 
 class ImageLayer(C.Structure):
@@ -231,6 +244,16 @@ def load():
         L.mi355enc_set_hdr_input.argtypes = [vp] + [C.c_int] * 4
         L.mi355enc_hdr_tables.argtypes = [C.c_int] * 6 + [vp, C.c_size_t, vp]
         L.mi355enc_stage_yuv_convert.argtypes = [vp, vp, vp]
+        L.mi355enc_adjust_default.restype = None
+        L.mi355enc_adjust_default.argtypes = [C.POINTER(Adjust)]
+        L.mi355enc_adjust_check.argtypes = [C.POINTER(Adjust)]
+        L.mi355enc_adjust_tables.argtypes = [C.POINTER(Adjust), C.c_int, vp, vp]
+        L.mi355enc_set_adjust.argtypes = [vp, C.POINTER(Adjust)]
+        L.mi355enc_get_adjust.argtypes = [vp, C.POINTER(Adjust)]
+        L.mi355enc_last_adjust.argtypes = [vp, C.POINTER(Adjust)]
+        L.mi355enc_stage_adjust.argtypes = [vp, C.POINTER(Adjust), vp, vp]
+        L.mi355enc_debug_adjust_bytes.restype = C.c_size_t
+        L.mi355enc_debug_adjust_bytes.argtypes = [vp]
         L.mi355enc_set_quality_metrics.argtypes = [vp, C.c_int]
         L.mi355enc_last_quality.argtypes = [vp, C.POINTER(Quality)]
         L.mi355enc_quality_totals.argtypes = [vp, C.POINTER(Quality)]
@@ -360,6 +383,34 @@ def yuv_coefficients(in_matrix, in_full, out_matrix, out_full):
     if r:
         raise EncoderError("mi355enc_yuv_coefficients(%d, %d, %d, %d): %d" % (in_matrix, in_full, out_matrix, out_full, r))
     return c
+
+
+def adjust(a=None, **kw):
+    """An Adjust: the neutral values (mi355enc_adjust_default), then a's (an Adjust or a dict) and the keywords' on top.  Not checked here."""
+    st = Adjust()
+    load().mi355enc_adjust_default(C.byref(st))
+    src = a.as_dict() if isinstance(a, Adjust) else dict(a or {})
+    src.update(kw)
+    for k, v in src.items():
+        if k not in Adjust.NAMES:
+            raise TypeError("adjust: no parameter %r" % (k,))
+        setattr(st, k, int(v))
+    return st
+
+
+def adjust_check(a=None, **kw):
+    """mi355enc_adjust_check (host only): 0, or the error code for a value outside its range"""
+    return load().mi355enc_adjust_check(C.byref(adjust(a, **kw)))
+
+
+def adjust_tables(a, full_range=0):
+    """The picture controls' luma table and chroma rotation for an output range (host only): (uint8 (256,), int32 (2,) = cu, su)."""
+    st = adjust(a)
+    luma, chroma = np.zeros(256, np.uint8), np.zeros(2, np.int32)
+    r = load().mi355enc_adjust_tables(C.byref(st), int(full_range), luma.ctypes.data_as(C.c_void_p), chroma.ctypes.data_as(C.c_void_p))
+    if r:
+        raise EncoderError("mi355enc_adjust_tables(%r, %d): %d" % (st.as_dict(), full_range, r))
+    return luma, chroma
 
 
 def hdr_tables(transfer, full_range=0, peak_nits=0, target_nits=0, out_matrix=1, out_full=0):
@@ -742,7 +793,7 @@ class Encoder:
     (bitrate in bits/s as written through `bps`, key-int-max -> gop)."""
 
     def __init__(self, width, height, fps=60, gop=60, bitrate_bps=6_000_000, device_id=0, fixed_qp=-1, me_range=16,
-                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False, input_size=None, colorimetry=None, orientation=None, geometry=None, input_colorimetry=None, rate=None, hdr_input=None):
+                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False, input_size=None, colorimetry=None, orientation=None, geometry=None, input_colorimetry=None, rate=None, hdr_input=None, adjust=None):
         self.L = load()
         cfg = Cfg()
         self.L.mi355enc_default_cfg(C.byref(cfg), width, height, fps, fps_den)
@@ -789,6 +840,12 @@ class Encoder:
             self._chk(self.L.mi355enc_set_input_colorimetry(self.h, *[int(v) for v in input_colorimetry]), "set_input_colorimetry", close_on_fail=True)
         if hdr_input is not None:  # (transfer, full_range, peak_nits, target_nits): the 10-bit pictures submitted are PQ / HLG BT.2020 and are tone-mapped on the device to SDR in `colorimetry`
             self._chk(self.L.mi355enc_set_hdr_input(self.h, *[int(v) for v in hdr_input]), "set_hdr_input", close_on_fail=True)
+        if adjust is not None:  # a dict of picture controls (brightness=..., sharpen=...): applied on the device to every picture from the first one on
+            try:
+                self.set_adjust(adjust)
+            except EncoderError:
+                self.close()
+                raise
         self.rate_on = False
         if rate is not None:  # (mode, pts_per_second, max_fill): frame-rate conversion to fps / fps_den; every submit*() then returns the pictures it enqueued
             self._chk(self.L.mi355enc_set_rate_conversion(self.h, C.byref(Rate(*[int(v) for v in rate]))), "set_rate_conversion", close_on_fail=True)
@@ -850,6 +907,32 @@ class Encoder:
         """the submitted 10-bit pictures (FMT_P010, FMT_I420_10, FMT_V210) are HDR (transfer HDR_PQ / HDR_HLG, BT.2020): tone-mapped to SDR BT.709 in their conversion
         launch (before the first submit; not beside set_input_colorimetry); every other input is refused from then on"""
         self._chk(self.L.mi355enc_set_hdr_input(self.h, int(transfer), int(full_range), int(peak_nits), int(target_nits)), "set_hdr_input")
+
+    def set_adjust(self, a=None, **kw):
+        """picture controls from the next submitted picture on (any time, any thread): brightness, contrast, saturation, hue, gamma in thousandths, sharpen in
+        sixteenths, sharpen_threshold; unnamed ones are neutral, none at all (or all neutral) switches the step off"""
+        self._chk(self.L.mi355enc_set_adjust(self.h, C.byref(adjust(a, **kw))), "set_adjust")
+
+    def get_adjust(self):
+        st = Adjust()
+        self._chk(self.L.mi355enc_get_adjust(self.h, C.byref(st)), "get_adjust")
+        return st.as_dict()
+
+    def last_adjust(self):
+        """the picture controls the last collected picture was submitted under (a dict); EncoderError before the first collect"""
+        st = Adjust()
+        self._chk(self.L.mi355enc_last_adjust(self.h, C.byref(st)), "last_adjust")
+        return st.as_dict()
+
+    def stage_adjust(self, a, y, uv):
+        """The picture controls alone on host planes of the coded size, with the handle's geometry, orientation and output range; returns the adjusted copies."""
+        y, uv = np.ascontiguousarray(y, np.uint8).copy(), np.ascontiguousarray(uv, np.uint8).copy()
+        assert y.shape == (self.mbh * 16, self.mbw * 16) and uv.shape == (self.mbh * 8, self.mbw * 16)
+        self._chk(self.L.mi355enc_stage_adjust(self.h, C.byref(adjust(a)), _p(y), _p(uv)), "stage_adjust")
+        return y, uv
+
+    def debug_adjust_bytes(self):
+        return int(self.L.mi355enc_debug_adjust_bytes(self.h))
 
     def stage_yuv_convert(self, y, uv):
         """The colour step alone on host planes of the coded size, with the handle's geometry, orientation and colorimetries; returns the converted copies."""
@@ -1202,9 +1285,9 @@ class Encoder:
 
     def fetch(self, what):
         H, W, n = self.mbh * 16, self.mbw * 16, self.mbw * self.mbh
-        if what in (FETCH_RECON_Y, FETCH_PREFILTER_Y):
+        if what in (FETCH_RECON_Y, FETCH_PREFILTER_Y, FETCH_SOURCE_Y):
             a = np.empty((H, W), np.uint8)
-        elif what in (FETCH_RECON_UV, FETCH_PREFILTER_UV):
+        elif what in (FETCH_RECON_UV, FETCH_PREFILTER_UV, FETCH_SOURCE_UV):
             a = np.empty((H // 2, W), np.uint8)
         elif what == FETCH_MBINFO:
             a = np.empty(n, MBINFO_DTYPE)

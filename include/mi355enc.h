@@ -286,6 +286,36 @@ int mi355enc_hdr_tables(int transfer, int full_range, int peak_nits, int target_
 /* the colour step alone (tests): host NV12 planes of the coded size (16*mbw x 16*mbh luma, then interleaved chroma), in and out, like mi355enc_stage_image,
  * with the handle's geometry, orientation and colorimetries; MI355ENC_ERR_STATE when the handle has no conversion */
 int mi355enc_stage_yuv_convert(mi355enc_t *h, uint8_t *y, uint8_t *uv);
+/* Picture controls on the way in: colour balance, gamma and sharpening of the picture part of the coded surfaces, behind the colour
+ * step and in front of frame-rate conversion, image layers and text.  All integers: brightness -1000 .. 1000 (thousandths of the luma scale S, added; neutral
+ * 0), contrast 0 .. 2000 (thousandths, gain about black; 1000), saturation 0 .. 2000 (thousandths, chroma gain; 1000), hue -1000 .. 1000 (thousandths of pi,
+ * chroma rotation with videobalance's sign; 0), gamma 100 .. 10000 (thousandths, t -> t^(1000 / gamma) on [0, 1]; 1000), sharpen -16 .. 64 (sixteenths of the
+ * unsharp amount, negative softens; 0), sharpen_threshold 0 .. 32 (coring, for sharpen > 0 only; 0).  Black level B and scale S are the output range's
+ * (mi355enc_set_colorimetry's full_range): 16 and 219, or 0 and 255.
+ *   luma     Y' = L[Y]; gamma 1000: L[v] = clip255(B + floor((2 ((v - B) contrast + brightness S) + 1000) / 2000)); otherwise in double: t = (v - B) / S, inside
+ *            [0, 1] t^(1000 / gamma), outside as it is, y = B + S (t contrast / 1000 + brightness / 1000), L[v] = clip255(floor(y + 0.5)).  Non-decreasing.
+ *   chroma   cu = round(4096 sat / 1000 cos(pi hue / 1000)), su likewise with sin; a = Cb - 128, b = Cr - 128:
+ *            Cb' = clip255(128 + ((cu a + su b + 2048) >> 12)), Cr' = clip255(128 + ((-su a + cu b + 2048) >> 12))
+ *   sharpen  on the luma behind the table, weights 1 2 1 / 2 4 2 / 1 2 1: d = 16 Y - sum; sharpen > 0 and |d| <= 16 threshold: Y stays; otherwise
+ *            Y' = clip255(Y + ((sharpen d + 128) >> 8)).  Neighbours are clamped to the visible part of the picture rectangle; a margin sample of the coded
+ *            surface is the result of its clamped visible position; a letterbox border keeps its bytes. */
+typedef struct {
+    int brightness, contrast, saturation, hue, gamma, sharpen, sharpen_threshold;
+} mi355enc_adjust_t;
+void mi355enc_adjust_default(mi355enc_adjust_t *a);     /* the neutral values */
+int mi355enc_adjust_check(const mi355enc_adjust_t *a); /* host only: MI355ENC_OK, or MI355ENC_ERR_ARG for a value outside its range */
+/* host only, no device needed: the luma table L and {cu, su} of a parameter set for an output range */
+int mi355enc_adjust_tables(const mi355enc_adjust_t *a, int full_range, uint8_t luma[256], int32_t chroma[2]);
+/* At any time and from any thread, no GPU call (the tables are built here); latched once per input picture at its submit.  NULL or all neutral: off.  Off (the
+ * default): nothing is allocated, uploaded or launched, and every stream is byte for byte what it was.  With an active adjustment mi355enc_submit_device
+ * never encodes in place: the caller's planes are only read. */
+int mi355enc_set_adjust(mi355enc_t *h, const mi355enc_adjust_t *a);
+int mi355enc_get_adjust(const mi355enc_t *h, mi355enc_adjust_t *a);
+int mi355enc_last_adjust(mi355enc_t *h, mi355enc_adjust_t *a); /* of the last collected picture; MI355ENC_ERR_STATE before the first collect */
+/* the step alone (tests): host NV12 planes of the coded size, in and out, like mi355enc_stage_yuv_convert, with the handle's geometry, orientation and
+ * output range; a: the parameters (the handle's own setting is not touched) */
+int mi355enc_stage_adjust(mi355enc_t *h, const mi355enc_adjust_t *a, uint8_t *y, uint8_t *uv);
+size_t mi355enc_debug_adjust_bytes(const mi355enc_t *h); /* device bytes the step holds: 0 until the first sharpened picture, then 16 mb_width x 16 mb_height */
 /* like mi355enc_submit, from host memory in `fmt`; planes[]/strides[]: as many entries as the format has planes */
 int mi355enc_submit_fmt(mi355enc_t *h, int fmt, const uint8_t *const planes[3], const int strides[3], int64_t pts, int force_idr);
 /* conversion stage alone (tests): writes the coded-size NV12 surfaces (16*mbw x 16*mbh luma, then interleaved chroma) */
@@ -605,8 +635,12 @@ int mi355enc_abi_version(void);
 /* MI355ENC_FETCH_SCALE_TABLES: the device's copy of the scale tables (after mi355enc_set_input_size): the luma horizontal, luma vertical,
  * chroma horizontal, chroma vertical 4:2:0 and chroma vertical 4:2:2 tables in this order, each as int32 first[n] then int16 coef[n][taps]
  * (mi355enc_scale_table's), padded to a multiple of 16 bytes. */
+/* MI355ENC_FETCH_SOURCE_Y / _UV: the coded source surfaces of the last collected picture as its kernels read them -- behind the colour step, picture controls,
+ * frame-rate conversion, image layers and text.  They are its slot's: valid until the next submit (which may reuse the slot); MI355ENC_ERR_STATE before the
+ * first collect and for a picture mi355enc_submit_device encoded in place. */
 enum { MI355ENC_FETCH_RECON_Y = 0, MI355ENC_FETCH_RECON_UV = 1, MI355ENC_FETCH_PREFILTER_Y = 2,
-       MI355ENC_FETCH_PREFILTER_UV = 3, MI355ENC_FETCH_MBINFO = 4, MI355ENC_FETCH_LEVELS = 5, MI355ENC_FETCH_SCALE_TABLES = 6 };
+       MI355ENC_FETCH_PREFILTER_UV = 3, MI355ENC_FETCH_MBINFO = 4, MI355ENC_FETCH_LEVELS = 5, MI355ENC_FETCH_SCALE_TABLES = 6,
+       MI355ENC_FETCH_SOURCE_Y = 7, MI355ENC_FETCH_SOURCE_UV = 8 };
 int mi355enc_fetch(mi355enc_t *h, int what, void *dst, size_t dst_bytes);
 int mi355enc_mb_width(const mi355enc_t *h);
 int mi355enc_mb_height(const mi355enc_t *h);
@@ -656,7 +690,9 @@ int mi355enc_stage_deblock(mi355enc_t *h, uint8_t *rec_y, uint8_t *rec_uv, const
  * 17 the colour step on slot 0's source surfaces (MI355ENC_ERR_STATE when the handle has no conversion),
  * 18 the frame-rate conversion's mix launch (w = 128) of the keep buffer and slot 0's source surfaces, in place (MI355ENC_ERR_STATE with conversion off),
  * 19 / 20 / 21 the tone-mapping conversion launch of a P010 / I420_10 / V210 picture in slot 0's raw staging buffer (whatever the last conversion left there;
- * MI355ENC_ERR_STATE without mi355enc_set_hdr_input), 22 the plain P010 conversion launch from the same buffer.
+ * MI355ENC_ERR_STATE without mi355enc_set_hdr_input), 22 the plain P010 conversion launch from the same buffer,
+ * 23 / 24 the picture controls set last (mi355enc_set_adjust) in place on slot 0's source surfaces: 23 the pointwise form, 24 the stencil form with the hand-back
+ * of its scratch plane (MI355ENC_ERR_STATE when the value set last is off or of the other form).
  * Uses whatever the handle's surfaces currently hold.  Returns average ms per launch. */
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms);
 
