@@ -1,0 +1,15 @@
+/* denoise_host.h -- the rule of the temporal noise filter, host only.  The entry points are the ABI's (include/mi355enc.h:
+ * mi355enc_denoise_default, _check, _tables); this is what the shim shares with them. */
+#ifndef MI355_DENOISE_HOST_H
+#define MI355_DENOISE_HOST_H
+#include "../../include/mi355enc.h"
+#ifdef __cplusplus
+extern "C" {
+#endif
+/* which planes of a checked parameter set are filtered; 0: off */
+enum { DENOISE_LUMA = 1, DENOISE_CHROMA = 2 };
+__attribute__((visibility("hidden"))) int denoise_parts(const mi355enc_denoise_t *d);
+#ifdef __cplusplus
+}
+#endif
+#endif

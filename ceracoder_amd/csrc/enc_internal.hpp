@@ -12,6 +12,7 @@
 //   enc_snapshot.cpp  JPEG stills: request / take, the blocks the levels land in, the launch, its stage entry points
 //   enc_csc.cpp       colorimetry: the setters, the RGB matrix and the YUV -> YUV table, the colour step's launch, their stage entry points
 //   enc_adjust.cpp    picture controls: setter, latch, the two launch forms and the scratch plane, its stage entry point
+//   enc_denoise.cpp   temporal noise reduction: setter, latch, the launch and the handle's history, its stage entry point
 //   enc_rate.cpp      frame-rate conversion: setter, the plan's step and commit per submit, keep buffer, mix / keep / repeat launches, its stage entry point
 //   enc_stages.cpp    single-stage entry points (parity tests, probes) and the host-only stages
 #ifndef MI355_ENC_INTERNAL_HPP
@@ -35,6 +36,7 @@
 #include "snapshot_host.h"
 #include "hdr_host.h"
 #include "adjust_host.h"
+#include "denoise_host.h"
 #include "enc_plan.hpp"
 #include "enc_sync.hpp"
 
@@ -83,6 +85,10 @@ struct snap_block_t {
 // the luma table and the chroma rotation as built for the handle's output range by the thread that set it.
 struct adjust_set_t { mi355enc_adjust_t a; int parts; uint8_t luma[256]; int32_t chroma[2]; };
 
+// Temporal noise reduction (mi355enc_set_denoise): a checked parameter set with what follows from it -- which planes are filtered (DENOISE_*;
+// 0: off) and the three tables (B, the luma's P, the chroma's P) as built by the thread that set it.
+struct denoise_set_t { mi355enc_denoise_t d; int parts; uint8_t tabs[768]; };
+
 struct slot_t {
     frame_ctx_t *h_ctx;   // pinned
     mb_info_t *h_mbi;     // pinned
@@ -120,6 +126,8 @@ struct slot_t {
     bool yuv_step;
     // picture controls: what submit latched for this picture (adj.parts 0: nothing); applied once, to the input's own slot, in ingest_end
     adjust_set_t adj;
+    // temporal noise reduction: what submit latched for this picture (dn.parts 0: nothing); applied once, to the input's own slot, in ingest_end
+    denoise_set_t dn;
 };
 
 struct mi355enc {
@@ -229,6 +237,16 @@ struct mi355enc {
     bool adj_last_have = false;
     uint8_t *d_adj = nullptr;
     size_t adj_bytes = 0;
+    // temporal noise reduction (mi355enc_set_denoise): what the control thread set last (under dn_mu; submit latches it per input picture), what
+    // the last collected picture carried, and the history -- one uint16 per luma / chroma sample of the coded surfaces, allocated by the first filtered picture
+    // (dn_bytes: both sizes), written only by the step's launches, which follow one another on the upload stream.  dn_prev: the strengths of the previous picture
+    // that went through the step ({0, 0}: none, or it was off) -- a plane whose strength was 0 there primes.  recover() touches none of this.
+    std::mutex dn_mu;
+    denoise_set_t dn_cur = {}, dn_last = {};
+    bool dn_last_have = false;
+    uint16_t *d_dn_y = nullptr, *d_dn_uv = nullptr;
+    size_t dn_bytes = 0;
+    mi355enc_denoise_t dn_prev = {0, 0};
     // frame-rate conversion (mi355enc_set_rate_conversion).  rate.mode 0: off, and nothing below is used but last_count.  rate.max_fill is
     // clamped to pipeline_depth.  rate_plan: the rule's state; ingest_begin steps a copy of it (rate_next, with what the step yields: rate_n pictures, their pts
     // and weights) and ingest_end commits it once the pictures are enqueued -- a submit that fails in between has not advanced the plan.  d_keep: one NV12
@@ -400,6 +418,14 @@ void adjust_collected(mi355enc_t *h, slot_t *s);             // collect(): books
 void adjust_free(mi355enc_t *h);
 bool adjust_time_ready(mi355enc_t *h, bool stencil);         // mi355enc_time_stage 23 / 24: the value set last is active and of that form
 int adjust_time_launch(mi355enc_t *h, slot_t *s);            // ... and its launches on the main stream
+// enc_denoise.cpp (temporal noise reduction)
+void denoise_latch(mi355enc_t *h, slot_t *s, bool tables);   // the value set last becomes the slot's (beside adjust_latch); tables: with its tables (the slot the step runs on)
+int denoise_draw(mi355enc_t *h, slot_t *s, hipStream_t st);  // the slot's filter on its coded surfaces and the handle's history, behind everything enqueued on st so far; nothing with none
+void denoise_collected(mi355enc_t *h, slot_t *s);            // collect(): books what the picture carried as the last picture's
+void denoise_free(mi355enc_t *h);
+bool denoise_time_ready(mi355enc_t *h);                      // mi355enc_time_stage 25 / 26: the value set last is active
+int denoise_time_launch(mi355enc_t *h, slot_t *s, bool prime); // ... and its launch on the main stream: filtering (priming where the history is not valid) or priming
+void denoise_time_done(mi355enc_t *h);                       // ... behind the timed launches: the history they left is no stream's, the next picture primes
 // enc_hdr.cpp (HDR input)
 // true: the handle tone-maps and this input is not one it takes (a format other than the three 10-bit ones -- fmt -1: an entry point that takes none of them --
 // or an output matrix outside 1, 5, 6, 2): the submit fails with MI355ENC_ERR_ARG before anything is latched

@@ -110,6 +110,8 @@ typedef struct {
      * defaults, gamma, sharpen, sharpen-threshold; stored in the library's integers (the doubles as thousandths, lround) under the object lock and forwarded like
      * the overlay's text -- any thread, at any time */
     mi355enc_adjust_t adj;
+    /* temporal noise reduction on the device (mi355enc_set_denoise): denoise-luma, denoise-chroma; stored and forwarded like the picture controls */
+    mi355enc_denoise_t dn;
     gint hdr_input, hdr_peak, hdr_target; /* hdr-input (0 off, 16 pq, 18 hlg), hdr-peak-nits, hdr-target-nits: read at the next set_format */
     gint open_rate;           /* 0: conversion off */
     GstClockTime tick;        /* duration of an output picture */
@@ -140,7 +142,8 @@ enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME
        PROP_IMG_LOCATION, PROP_IMG_X, PROP_IMG_Y, PROP_IMG_ALPHA,
        PROP_SNAP_LOCATION, PROP_SNAP_INTERVAL, PROP_SNAP_QUALITY, PROP_SNAP_REDUCE, PROP_SNAP_SOURCE,
        PROP_OUTPUT_COLORIMETRY, PROP_RATE_CONVERSION, PROP_OUTPUT_FRAMERATE, PROP_MAX_FILL, PROP_HDR_INPUT, PROP_HDR_PEAK_NITS, PROP_HDR_TARGET_NITS,
-       PROP_ADJ_BRIGHTNESS, PROP_ADJ_CONTRAST, PROP_ADJ_HUE, PROP_ADJ_SATURATION, PROP_ADJ_GAMMA, PROP_ADJ_SHARPEN, PROP_ADJ_SHARPEN_THRESHOLD };
+       PROP_ADJ_BRIGHTNESS, PROP_ADJ_CONTRAST, PROP_ADJ_HUE, PROP_ADJ_SATURATION, PROP_ADJ_GAMMA, PROP_ADJ_SHARPEN, PROP_ADJ_SHARPEN_THRESHOLD,
+       PROP_DENOISE_LUMA, PROP_DENOISE_CHROMA };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
     GST_STATIC_CAPS("video/x-raw, format=(string){ NV12, I420, YUY2, UYVY, Y42B, Y444, YV12, NV21, BGRx, RGBx, xRGB, xBGR, BGRA, RGBA, ARGB, ABGR, BGR, RGB, P010_10LE, I420_10LE, v210, GRAY8 }, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]; "
@@ -241,6 +244,10 @@ static void overlay_forward(GstMi355H264Enc *s) {
 static void adjust_forward(GstMi355H264Enc *s) {
     if (s->enc && mi355enc_set_adjust(s->enc, &s->adj) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the picture controls: it keeps its previous ones");
 }
+/* stored noise filter strengths -> the encoder, if one is open (object lock held; the library builds three small tables and stores: no GPU call, any thread) */
+static void denoise_forward(GstMi355H264Enc *s) {
+    if (s->enc && mi355enc_set_denoise(s->enc, &s->dn) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the noise filter's strengths: it keeps its previous ones");
+}
 static void overlay_store_text(GstMi355H264Enc *s, const gchar *t) { g_strlcpy(s->ov_text, t ? t : "", sizeof s->ov_text); }
 
 /* stored image, place and alpha -> layer 0 of the encoder, if one is open (object lock held; the library only copies and stores: no GPU call, any thread).
@@ -311,6 +318,8 @@ static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *
     case PROP_ADJ_GAMMA: s->adj.gamma = (int)lround(1000.0 * g_value_get_double(val)); adjust_forward(s); break;
     case PROP_ADJ_SHARPEN: s->adj.sharpen = g_value_get_int(val); adjust_forward(s); break;
     case PROP_ADJ_SHARPEN_THRESHOLD: s->adj.sharpen_threshold = g_value_get_int(val); adjust_forward(s); break;
+    case PROP_DENOISE_LUMA: s->dn.luma = g_value_get_int(val); denoise_forward(s); break;
+    case PROP_DENOISE_CHROMA: s->dn.chroma = g_value_get_int(val); denoise_forward(s); break;
     case PROP_OUTPUT_COLORIMETRY: g_free(s->out_colorimetry); s->out_colorimetry = g_value_dup_string(val); break; /* (read at the next set_format) */
     case PROP_IMG_X: s->img_x = g_value_get_int(val); image_forward(s, FALSE); break;
     case PROP_IMG_Y: s->img_y = g_value_get_int(val); image_forward(s, FALSE); break;
@@ -383,6 +392,8 @@ static void get_property(GObject *obj, guint id, GValue *val, GParamSpec *ps) {
     case PROP_ADJ_GAMMA: g_value_set_double(val, s->adj.gamma / 1000.0); break;
     case PROP_ADJ_SHARPEN: g_value_set_int(val, s->adj.sharpen); break;
     case PROP_ADJ_SHARPEN_THRESHOLD: g_value_set_int(val, s->adj.sharpen_threshold); break;
+    case PROP_DENOISE_LUMA: g_value_set_int(val, s->dn.luma); break;
+    case PROP_DENOISE_CHROMA: g_value_set_int(val, s->dn.chroma); break;
     case PROP_OUTPUT_COLORIMETRY: g_value_set_string(val, s->out_colorimetry ? s->out_colorimetry : ""); break;
     case PROP_IMG_X: g_value_set_int(val, s->img_x); break;
     case PROP_IMG_Y: g_value_set_int(val, s->img_y); break;
@@ -786,6 +797,7 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     overlay_forward(s);                     /* ... nor the overlay's text and style, set before the device was opened */
     image_forward(s, TRUE);                 /* ... nor the image layer */
     adjust_forward(s);                      /* ... nor the picture controls */
+    denoise_forward(s);                     /* ... nor the noise filter */
     GST_OBJECT_UNLOCK(s);
     g_mutex_unlock(&s->snap_enc_mu);
     s->max_au = mi355enc_max_au_bytes(e);
@@ -1239,6 +1251,8 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
     g_object_class_install_property(g, PROP_ADJ_GAMMA, g_param_spec_double("gamma", "Gamma", "picture controls on the GPU (the gamma element's property): t -> t^(1 / gamma) on the luma between black and white", 0.1, 10.0, 1.0, F));
     g_object_class_install_property(g, PROP_ADJ_SHARPEN, g_param_spec_int("sharpen", "Sharpen", "picture controls on the GPU: 3 x 3 unsharp mask on the luma in sixteenths of its amount (16: original + detail); negative softens (-16: the binomial blur); 0: off", -16, 64, 0, F));
     g_object_class_install_property(g, PROP_ADJ_SHARPEN_THRESHOLD, g_param_spec_int("sharpen-threshold", "Sharpen threshold", "with sharpen > 0: detail of at most this many codes is left alone (coring)", 0, 32, 0, F));
+    g_object_class_install_property(g, PROP_DENOISE_LUMA, g_param_spec_int("denoise-luma", "Denoise luma", "temporal noise reduction on the GPU, motion-adaptive, in front of the picture controls: the luma noise amplitude in codes that is filtered fully; 0: off", 0, MI355ENC_DENOISE_MAX, 0, F));
+    g_object_class_install_property(g, PROP_DENOISE_CHROMA, g_param_spec_int("denoise-chroma", "Denoise chroma", "temporal noise reduction on the GPU: the chroma noise amplitude in codes that is filtered fully; 0: off", 0, MI355ENC_DENOISE_MAX, 0, F));
     g_object_class_override_property(g, PROP_VIDEO_DIRECTION, "video-direction"); /* GstVideoDirection: identity, 90r, 180, 90l, horiz, vert, ul-lr, ur-ll, auto -- as on videoflip */
     g_object_class_install_property(g, PROP_STATS, g_param_spec_boolean("stats", "Print stats", "Print a JSON line with counters when the encoder closes", FALSE, F));
     gst_element_class_add_static_pad_template(e, &sink_tmpl);
@@ -1259,6 +1273,7 @@ static void gst_mi355h264enc_init(GstMi355H264Enc *s) {
     s->out_colorimetry = NULL;
     s->hdr_input = 0; s->hdr_peak = 0; s->hdr_target = 0;
     mi355enc_adjust_default(&s->adj);
+    mi355enc_denoise_default(&s->dn);
     s->rate_mode = 0; s->out_fps_n = 0; s->out_fps_d = 1; s->max_fill = 2; s->open_rate = 0; s->tick = GST_CLOCK_TIME_NONE; s->rate_qh = s->rate_qn = 0;
     s->snap_location = NULL; s->snap_interval = 1000; s->snap_quality = 75; s->snap_reduce = 4; s->snap_source = 0; s->snap_next = GST_CLOCK_TIME_NONE; s->snap_watch = 0;
     g_mutex_init(&s->snap_mu); g_mutex_init(&s->snap_enc_mu); g_cond_init(&s->snap_cv);

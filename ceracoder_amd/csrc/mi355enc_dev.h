@@ -212,6 +212,11 @@ int k_launch_adjust(uint8_t *y, uint8_t *uv, int W, int H, const int rect[4], co
  * table (null: neutral, none), then the 3 x 3 unsharp mask with amount (-16 .. 64, not 0) and threshold thr (0 .. 32), neighbours clamped to the visible part of rect, a margin sample
  * the result of its clamped visible position.  Writes rect's samples of `out` and at most two bytes beside its left and right edge.  -1: arguments outside that */
 int k_launch_adjust_sharpen(const uint8_t *y, uint8_t *out, int W, int H, int vw, int vh, const int rect[4], const uint8_t *luma, int amount, int thr, hipStream_t s);
+/* temporal noise reduction (k_denoise.hip; the rule: DESIGN.md section 24), in place on NV12 surfaces of W x H (multiples of 16) at stride W and on their
+ * histories hy, huv (uint16 per sample, the same layout, 16-byte aligned; huv null with cmode 0); vw x vh the visible size (even, less than 16 short of W x H).
+ * lmode 1: the luma is filtered, 0: it primes / follows (H' = 16 c, the luma surface is not written); cmode 2: the chroma is filtered, 1: it primes, 0: neither
+ * read nor written.  tabs: 768 bytes -- B, the luma's P, the chroma's P (mi355enc_denoise_tables) --, needed when anything is filtered.  -1: arguments outside that */
+int k_launch_denoise(uint8_t *y, uint8_t *uv, uint16_t *hy, uint16_t *huv, int W, int H, int vw, int vh, int lmode, int cmode, const uint8_t *tabs, hipStream_t s);
 /* Downscaling of the input picture to the coded size (k_scale.hip; the rule: DESIGN.md section 10).  Tables built on the host
  * (enc_scale.cpp), five of them: 0 luma horizontal, 1 luma vertical, 2 chroma horizontal, 3 chroma vertical from 4:2:0 input, 4 chroma
  * vertical from 4:2:2 input.  Entry i of table t: first[t][i] (first source index, not clamped) and q[t][i * taps[t] + k]. */

@@ -34,6 +34,7 @@ SURF_ROWS, SURF_COLS = 35, 36
 DROP_MAX, DROP_SKIP = 12, 255
 STAGE_ME, STAGE_INTER, STAGE_INTRA, STAGE_DEBLOCK, STAGE_SUBPEL, STAGE_CSC_I420, STAGE_CSC_YUY2, STAGE_CSC_UYVY, STAGE_ME_SELECT, STAGE_PMB, STAGE_INTRA_P, STAGE_QUALITY, STAGE_JPEG, STAGE_ORIENT, STAGE_SCALE, STAGE_IMAGE, STAGE_SNAPSHOT, STAGE_YUV_CONVERT, STAGE_RATE = range(19)
 STAGE_ADJUST_POINT, STAGE_ADJUST_SHARPEN = 23, 24  # the picture controls set last on slot 0's surfaces: pointwise form, stencil form
+STAGE_DENOISE, STAGE_DENOISE_PRIME = 25, 26  # the temporal noise filter set last on slot 0's surfaces and the handle's history: filtering, priming
 STAGE_HDR_P010, STAGE_HDR_I420_10, STAGE_HDR_V210, STAGE_DEEP_P010 = 19, 20, 21, 22  # the tone-mapping launch per format, and the plain P010 launch beside it
 HDR_PQ, HDR_HLG = 16, 18  # mi355enc_set_hdr_input: the transfer's H.264 Table E-4 code point
 # mi355enc_set_orientation: GstVideoOrientationMethod's numbers
@@ -66,6 +67,8 @@ EXPORTS = [
     "mi355enc_set_hdr_input", "mi355enc_hdr_tables",
     "mi355enc_adjust_default", "mi355enc_adjust_check", "mi355enc_adjust_tables", "mi355enc_set_adjust", "mi355enc_get_adjust", "mi355enc_last_adjust", "mi355enc_stage_adjust",
     "mi355enc_debug_adjust_bytes",
+    "mi355enc_denoise_default", "mi355enc_denoise_check", "mi355enc_denoise_tables", "mi355enc_set_denoise", "mi355enc_get_denoise", "mi355enc_last_denoise", "mi355enc_stage_denoise",
+    "mi355enc_debug_denoise_bytes",
 ]
 
 
@@ -120,6 +123,14 @@ class Adjust(C.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n in self.NAMES}
+
+
+class Denoise(C.Structure):
+    """mi355enc_denoise_t: the temporal noise filter's strengths, 0 .. 32 codes each, 0: that plane is not filtered"""
+    _fields_ = [("luma", C.c_int), ("chroma", C.c_int)]
+
+    def as_dict(self):
+        return dict(luma=int(self.luma), chroma=int(self.chroma))
 
 
 class ImageLayer(C.Structure):
@@ -254,6 +265,16 @@ def load():
         L.mi355enc_stage_adjust.argtypes = [vp, C.POINTER(Adjust), vp, vp]
         L.mi355enc_debug_adjust_bytes.restype = C.c_size_t
         L.mi355enc_debug_adjust_bytes.argtypes = [vp]
+        L.mi355enc_denoise_default.restype = None
+        L.mi355enc_denoise_default.argtypes = [C.POINTER(Denoise)]
+        L.mi355enc_denoise_check.argtypes = [C.POINTER(Denoise)]
+        L.mi355enc_denoise_tables.argtypes = [C.POINTER(Denoise), vp, vp, vp]
+        L.mi355enc_set_denoise.argtypes = [vp, C.POINTER(Denoise)]
+        L.mi355enc_get_denoise.argtypes = [vp, C.POINTER(Denoise)]
+        L.mi355enc_last_denoise.argtypes = [vp, C.POINTER(Denoise)]
+        L.mi355enc_stage_denoise.argtypes = [vp, C.POINTER(Denoise)] + [vp] * 6
+        L.mi355enc_debug_denoise_bytes.restype = C.c_size_t
+        L.mi355enc_debug_denoise_bytes.argtypes = [vp]
         L.mi355enc_set_quality_metrics.argtypes = [vp, C.c_int]
         L.mi355enc_last_quality.argtypes = [vp, C.POINTER(Quality)]
         L.mi355enc_quality_totals.argtypes = [vp, C.POINTER(Quality)]
@@ -411,6 +432,30 @@ def adjust_tables(a, full_range=0):
     if r:
         raise EncoderError("mi355enc_adjust_tables(%r, %d): %d" % (st.as_dict(), full_range, r))
     return luma, chroma
+
+
+def denoise(d=None, **kw):
+    """A Denoise: off, then d's (a Denoise or a dict) and the keywords' luma / chroma on top.  Not checked here."""
+    src = d.as_dict() if isinstance(d, Denoise) else dict(d or {})
+    src.update(kw)
+    if set(src) - {"luma", "chroma"}:
+        raise TypeError("denoise: no parameter %r" % (sorted(set(src) - {"luma", "chroma"}),))
+    return Denoise(int(src.get("luma", 0)), int(src.get("chroma", 0)))
+
+
+def denoise_check(d=None, **kw):
+    """mi355enc_denoise_check (host only): 0, or the error code for a strength outside 0 .. 32"""
+    return load().mi355enc_denoise_check(C.byref(denoise(d, **kw)))
+
+
+def denoise_tables(d=None, **kw):
+    """The temporal noise filter's tables (host only): (B, the luma's P, the chroma's P), uint8 (256,) each."""
+    st = denoise(d, **kw)
+    t = [np.zeros(256, np.uint8) for _ in range(3)]
+    r = load().mi355enc_denoise_tables(C.byref(st), *[a.ctypes.data_as(C.c_void_p) for a in t])
+    if r:
+        raise EncoderError("mi355enc_denoise_tables(%r): %d" % (st.as_dict(), r))
+    return tuple(t)
 
 
 def hdr_tables(transfer, full_range=0, peak_nits=0, target_nits=0, out_matrix=1, out_full=0):
@@ -793,7 +838,7 @@ class Encoder:
     (bitrate in bits/s as written through `bps`, key-int-max -> gop)."""
 
     def __init__(self, width, height, fps=60, gop=60, bitrate_bps=6_000_000, device_id=0, fixed_qp=-1, me_range=16,
-                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False, input_size=None, colorimetry=None, orientation=None, geometry=None, input_colorimetry=None, rate=None, hdr_input=None, adjust=None):
+                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False, input_size=None, colorimetry=None, orientation=None, geometry=None, input_colorimetry=None, rate=None, hdr_input=None, adjust=None, denoise=None):
         self.L = load()
         cfg = Cfg()
         self.L.mi355enc_default_cfg(C.byref(cfg), width, height, fps, fps_den)
@@ -843,6 +888,12 @@ class Encoder:
         if adjust is not None:  # a dict of picture controls (brightness=..., sharpen=...): applied on the device to every picture from the first one on
             try:
                 self.set_adjust(adjust)
+            except EncoderError:
+                self.close()
+                raise
+        if denoise is not None:  # dict(luma=, chroma=): the temporal noise filter's strengths, from the first picture on
+            try:
+                self.set_denoise(denoise)
             except EncoderError:
                 self.close()
                 raise
@@ -933,6 +984,38 @@ class Encoder:
 
     def debug_adjust_bytes(self):
         return int(self.L.mi355enc_debug_adjust_bytes(self.h))
+
+    def set_denoise(self, d=None, **kw):
+        """the temporal noise filter from the next submitted picture on (any time, any thread): luma, chroma = 0 .. 32 codes; none (or both 0) switches it off"""
+        self._chk(self.L.mi355enc_set_denoise(self.h, C.byref(denoise(d, **kw))), "set_denoise")
+
+    def get_denoise(self):
+        st = Denoise()
+        self._chk(self.L.mi355enc_get_denoise(self.h, C.byref(st)), "get_denoise")
+        return st.as_dict()
+
+    def last_denoise(self):
+        """the strengths the last collected picture was submitted under (a dict); EncoderError before the first collect"""
+        st = Denoise()
+        self._chk(self.L.mi355enc_last_denoise(self.h, C.byref(st)), "last_denoise")
+        return st.as_dict()
+
+    def stage_denoise(self, d, y, uv, hist_y=None, hist_uv=None):
+        """The temporal noise filter alone on host planes of the coded size and their histories (uint16, the planes' shapes; None: that plane primes), with the
+        handle's visible size.  Returns (y, uv, hist_y, hist_uv): the filtered copies and the new histories (None for a plane that keeps none)."""
+        st = denoise(d)
+        y, uv = np.ascontiguousarray(y, np.uint8).copy(), np.ascontiguousarray(uv, np.uint8).copy()
+        assert y.shape == (self.mbh * 16, self.mbw * 16) and uv.shape == (self.mbh * 8, self.mbw * 16)
+        hin = [None if a is None else np.ascontiguousarray(a, np.uint16) for a in (hist_y, hist_uv)]
+        assert all(a is None or a.shape == p.shape for a, p in zip(hin, (y, uv)))
+        hy = np.zeros(y.shape, np.uint16) if st.luma or st.chroma else None
+        huv = np.zeros(uv.shape, np.uint16) if st.chroma else None
+        ptr = lambda a: None if a is None else _p(a)
+        self._chk(self.L.mi355enc_stage_denoise(self.h, C.byref(st), ptr(hin[0]), ptr(hin[1]), _p(y), _p(uv), ptr(hy), ptr(huv)), "stage_denoise")
+        return y, uv, hy, huv
+
+    def debug_denoise_bytes(self):
+        return int(self.L.mi355enc_debug_denoise_bytes(self.h))
 
     def stage_yuv_convert(self, y, uv):
         """The colour step alone on host planes of the coded size, with the handle's geometry, orientation and colorimetries; returns the converted copies."""

@@ -316,6 +316,41 @@ int mi355enc_last_adjust(mi355enc_t *h, mi355enc_adjust_t *a); /* of the last co
  * output range; a: the parameters (the handle's own setting is not touched) */
 int mi355enc_stage_adjust(mi355enc_t *h, const mi355enc_adjust_t *a, uint8_t *y, uint8_t *uv);
 size_t mi355enc_debug_adjust_bytes(const mi355enc_t *h); /* device bytes the step holds: 0 until the first sharpened picture, then 16 mb_width x 16 mb_height */
+/* Temporal noise reduction on the way in: a motion-adaptive recursive filter on the coded surfaces, behind the colour step and in front
+ * of the picture controls, so that everything later -- controls, frame-rate conversion, image layers, text, metrics, stills, the encoder -- sees the filtered
+ * picture, and layers and text are never filtered.  luma, chroma: 0 .. MI355ENC_DENOISE_MAX, the noise amplitude in codes that is filtered fully; 0 leaves that
+ * plane's samples as they are.  All integers.  The handle keeps a history H per sample in sixteenths of a code (uint16, 0 .. 4080; the chroma's interleaved like
+ * NV12); "the previous picture" is the previous one that went through the step (one that frame-rate conversion drops before transfer never does).
+ *   tables   for a strength s > 0, floor of the exact quotient, then clipped:
+ *            P_s[a] = clip(0, 224, floor(224 (3 s - a) / (2 s))), one for luma and one for chroma; B[i] = clip(0, 255, floor(255 (6 s - i) / (4 s))) with the
+ *            luma strength, or the chroma strength when luma is 0
+ *   block    per aligned 8 x 8 luma block: M = sum |c - ((H + 8) >> 4)| over its 64 luma samples, b = B[min(255, M >> 4)]; its 4 x 4 chroma pairs use the same b.
+ *            (With luma 0 and chroma > 0 the luma samples are not changed, and their history follows them, H' = 16 c: M then measures against the previous picture.)
+ *   sample   c the input code: d = |c - ((H + 8) >> 4)|, k = (b P[d] + 128) >> 8, H' = 16 c + ((k (H - 16 c) + 128) >> 8) (floor), out = (H' + 8) >> 4
+ *   priming  a plane without a valid history -- the first picture, a strength that was 0 for the previous picture -- gets out = c, H' = 16 c
+ *   margins  the step runs over the whole coded surface (a letterbox border is constant: the rule is the identity there); an 8 x 8 block without a visible
+ *            sample takes out and H' of its clamped visible position, a partly visible one is computed as it lies (the input path makes the margins it reads
+ *            replicas before the step; mi355enc_stage_denoise takes its surfaces as given).
+ * A change between two strengths > 0 keeps the history; a scene cut needs nothing (b = 0: out = c, H' = 16 c). */
+#define MI355ENC_DENOISE_MAX 32
+typedef struct {
+    int luma, chroma;
+} mi355enc_denoise_t;
+void mi355enc_denoise_default(mi355enc_denoise_t *d);     /* off: {0, 0} */
+int mi355enc_denoise_check(const mi355enc_denoise_t *d); /* host only: MI355ENC_OK, or MI355ENC_ERR_ARG for a value outside 0 .. 32 */
+/* host only, no device needed: B, the luma's P and the chroma's P (all zeros for a plane with strength 0) */
+int mi355enc_denoise_tables(const mi355enc_denoise_t *d, uint8_t block[256], uint8_t luma[256], uint8_t chroma[256]);
+/* At any time and from any thread, no GPU call; latched once per input picture at its submit.  NULL or {0, 0}: off.  Off (the default): nothing is allocated or
+ * launched, and every stream is byte for byte what it was.  With an active filter mi355enc_submit_device never encodes in place: the caller's planes are only read. */
+int mi355enc_set_denoise(mi355enc_t *h, const mi355enc_denoise_t *d);
+int mi355enc_get_denoise(const mi355enc_t *h, mi355enc_denoise_t *d);
+int mi355enc_last_denoise(mi355enc_t *h, mi355enc_denoise_t *d); /* of the last collected picture; MI355ENC_ERR_STATE before the first collect */
+/* the step alone (tests): host NV12 planes of the coded size and their histories (uint16, the planes' shapes), in and out in place on the host arrays, with the
+ * handle's visible size; hist_y / hist_uv NULL: that plane primes (hist_y is needed whenever anything is filtered: the block measure reads it).  hist_y_out is
+ * written whenever d is not off, hist_uv_out when d->chroma > 0; either may be NULL.  The handle's own setting and history are not touched. */
+int mi355enc_stage_denoise(mi355enc_t *h, const mi355enc_denoise_t *d, const uint16_t *hist_y, const uint16_t *hist_uv, uint8_t *y, uint8_t *uv,
+                           uint16_t *hist_y_out, uint16_t *hist_uv_out);
+size_t mi355enc_debug_denoise_bytes(const mi355enc_t *h); /* device bytes of the handle's history: 0 until the first filtered picture, then 2 per luma and per chroma sample kept */
 /* like mi355enc_submit, from host memory in `fmt`; planes[]/strides[]: as many entries as the format has planes */
 int mi355enc_submit_fmt(mi355enc_t *h, int fmt, const uint8_t *const planes[3], const int strides[3], int64_t pts, int force_idr);
 /* conversion stage alone (tests): writes the coded-size NV12 surfaces (16*mbw x 16*mbh luma, then interleaved chroma) */
@@ -692,7 +727,10 @@ int mi355enc_stage_deblock(mi355enc_t *h, uint8_t *rec_y, uint8_t *rec_uv, const
  * 19 / 20 / 21 the tone-mapping conversion launch of a P010 / I420_10 / V210 picture in slot 0's raw staging buffer (whatever the last conversion left there;
  * MI355ENC_ERR_STATE without mi355enc_set_hdr_input), 22 the plain P010 conversion launch from the same buffer,
  * 23 / 24 the picture controls set last (mi355enc_set_adjust) in place on slot 0's source surfaces: 23 the pointwise form, 24 the stencil form with the hand-back
- * of its scratch plane (MI355ENC_ERR_STATE when the value set last is off or of the other form).
+ * of its scratch plane (MI355ENC_ERR_STATE when the value set last is off or of the other form),
+ * 25 / 26 the temporal noise filter set last (mi355enc_set_denoise) in place on slot 0's source surfaces and the handle's history: 25 filtering (the history
+ * primed by the launch in front of the timed ones, if it was not valid), 26 priming (MI355ENC_ERR_STATE when the value set last is off).  Both leave the
+ * history invalid: the next picture submitted primes.
  * Uses whatever the handle's surfaces currently hold.  Returns average ms per launch. */
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms);
 
