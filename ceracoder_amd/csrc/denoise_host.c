@@ -38,3 +38,15 @@ int mi355enc_denoise_tables(const mi355enc_denoise_t *d, uint8_t block[256], uin
     for (int i = 0; s > 0 && i < 256; i++) block[i] = (uint8_t)clip(0, 255, floor_div(255L * (6 * s - i), 4L * s));
     return MI355ENC_OK;
 }
+
+/* ---- motion compensation: how the search ranks a candidate (dx, dy) of cost `cost`; tests/denoisemcref.py restates it */
+int denoise_motion_lambda(int s) { return 4 * s; }
+
+uint32_t mi355enc_denoise_motion_key(int cost, int dx, int dy, int s) {
+    if (cost < 0 || cost > 64 * 255 || dx < -MI355ENC_DENOISE_MOTION_MAX || dx > MI355ENC_DENOISE_MOTION_MAX || dy < -MI355ENC_DENOISE_MOTION_MAX ||
+        dy > MI355ENC_DENOISE_MOTION_MAX || s < 0 || s > MI355ENC_DENOISE_MAX)
+        return 0xFFFFFFFFu;
+    const int n = (dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy);
+    /* the penalised cost stays below 2^15 (16320 + 128 * 32), the rank below 2^16 (32 * 1089 + 32 * 33 + 32): unique per vector, shorter first, then by dy, then by dx */
+    return ((uint32_t)(cost + denoise_motion_lambda(s) * n) << 16) | (uint32_t)(n * 1089 + (dy + 16) * 33 + (dx + 16));
+}

@@ -86,8 +86,9 @@ struct snap_block_t {
 struct adjust_set_t { mi355enc_adjust_t a; int parts; uint8_t luma[256]; int32_t chroma[2]; };
 
 // Temporal noise reduction (mi355enc_set_denoise): a checked parameter set with what follows from it -- which planes are filtered (DENOISE_*;
-// 0: off) and the three tables (B, the luma's P, the chroma's P) as built by the thread that set it.
-struct denoise_set_t { mi355enc_denoise_t d; int parts; uint8_t tabs[768]; };
+// 0: off) and the three tables (B, the luma's P, the chroma's P) as built by the thread that set it; range: the search range of the motion compensation
+// (mi355enc_set_denoise_motion; section 25), 0: none.
+struct denoise_set_t { mi355enc_denoise_t d; int parts; uint8_t tabs[768]; int range; };
 
 struct slot_t {
     frame_ctx_t *h_ctx;   // pinned
@@ -241,10 +242,13 @@ struct mi355enc {
     // the last collected picture carried, and the history -- one uint16 per luma / chroma sample of the coded surfaces, allocated by the first filtered picture
     // (dn_bytes: both sizes), written only by the step's launches, which follow one another on the upload stream.  dn_prev: the strengths of the previous picture
     // that went through the step ({0, 0}: none, or it was off) -- a plane whose strength was 0 there primes.  recover() touches none of this.
+    // Motion compensation (section 25): d_dn_y / d_dn_uv are the current histories; a compensated launch reads them, writes d_dn_y_alt / d_dn_uv_alt and swaps
+    // the pointers.  Those and d_dn_vec (a word per 8 x 8 block: the search's result) are allocated by the first picture that is filtered with a range above 0.
     std::mutex dn_mu;
     denoise_set_t dn_cur = {}, dn_last = {};
     bool dn_last_have = false;
-    uint16_t *d_dn_y = nullptr, *d_dn_uv = nullptr;
+    uint16_t *d_dn_y = nullptr, *d_dn_uv = nullptr, *d_dn_y_alt = nullptr, *d_dn_uv_alt = nullptr;
+    unsigned *d_dn_vec = nullptr;
     size_t dn_bytes = 0;
     mi355enc_denoise_t dn_prev = {0, 0};
     // frame-rate conversion (mi355enc_set_rate_conversion).  rate.mode 0: off, and nothing below is used but last_count.  rate.max_fill is
@@ -423,8 +427,8 @@ void denoise_latch(mi355enc_t *h, slot_t *s, bool tables);   // the value set la
 int denoise_draw(mi355enc_t *h, slot_t *s, hipStream_t st);  // the slot's filter on its coded surfaces and the handle's history, behind everything enqueued on st so far; nothing with none
 void denoise_collected(mi355enc_t *h, slot_t *s);            // collect(): books what the picture carried as the last picture's
 void denoise_free(mi355enc_t *h);
-bool denoise_time_ready(mi355enc_t *h);                      // mi355enc_time_stage 25 / 26: the value set last is active
-int denoise_time_launch(mi355enc_t *h, slot_t *s, bool prime); // ... and its launch on the main stream: filtering (priming where the history is not valid) or priming
+bool denoise_time_ready(mi355enc_t *h, int stage);           // mi355enc_time_stage 25 .. 28: the value set last is active (27 / 28: with a range above 0)
+int denoise_time_launch(mi355enc_t *h, slot_t *s, int stage); // ... and its launch on the main stream: 25 filtering in place (priming where the history is not valid), 26 priming, 27 the search alone, 28 search and compensated filter
 void denoise_time_done(mi355enc_t *h);                       // ... behind the timed launches: the history they left is no stream's, the next picture primes
 // enc_hdr.cpp (HDR input)
 // true: the handle tone-maps and this input is not one it takes (a format other than the three 10-bit ones -- fmt -1: an entry point that takes none of them --

@@ -226,10 +226,10 @@ int mi355enc_debug_set_counters(mi355enc_t *h, const mi355enc_counters_t *in) {
     return MI355ENC_OK;
 }
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
-    if (!h || !avg_ms || iters < 1 || stage < 0 || stage > 26) return MI355ENC_ERR_ARG;
+    if (!h || !avg_ms || iters < 1 || stage < 0 || stage > 28) return MI355ENC_ERR_ARG;
     if (stage == 17 && !h->yuv_on) return MI355ENC_ERR_STATE; // (the handle has no conversion)
     if (stage >= 19 && stage <= 21 && (!h->hdr_on || hdr_refuses(h, MI355ENC_FMT_P010))) return MI355ENC_ERR_STATE; // (mi355enc_set_hdr_input first, and an output matrix it converts to)
-    if (stage >= 25 && !denoise_time_ready(h)) return MI355ENC_ERR_STATE; // (mi355enc_set_denoise first)
+    if (stage >= 25 && !denoise_time_ready(h, stage)) return MI355ENC_ERR_STATE; // (mi355enc_set_denoise first; 27 / 28: and mi355enc_set_denoise_motion)
     if (stage >= 23 && stage <= 24 && !adjust_time_ready(h, stage == 24)) return MI355ENC_ERR_STATE; // (mi355enc_set_adjust first: 23 with sharpen 0, 24 with sharpen set)
     if (stage == 18 && !h->d_keep) return MI355ENC_ERR_STATE; // (frame-rate conversion off, or hold mode without a keep buffer: there is no mix)
     if (stage == 14 && !h->d_scale_tab) return MI355ENC_ERR_STATE; // (mi355enc_set_input_size or mi355enc_set_input_geometry first)
@@ -287,7 +287,7 @@ int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
             else if (stage == 16) { int r = snapshot_time_launch(h, s); if (r) return r; }
             else if (stage == 17) { int r = yuv_draw(h, s, h->stream); if (r) return r; } // the colour step, in place on slot 0's surfaces (whatever they hold)
             else if (stage == 18) { int r = rate_mix(h, s, s, 128, true, h->stream); if (r) return r; } // the mix of the keep buffer and slot 0's surfaces, in place as the encoder runs it
-            else if (stage >= 25) { int r = denoise_time_launch(h, s, stage == 26); if (r) return r; } // the noise filter set last, in place on slot 0's surfaces and the handle's history: 25 filtering, 26 priming
+            else if (stage >= 25) { int r = denoise_time_launch(h, s, stage); if (r) return r; } // the noise filter set last, in place on slot 0's surfaces and the handle's history: 25 filtering, 26 priming, 27 the search alone, 28 search and compensated filter
             else if (stage >= 23) { int r = adjust_time_launch(h, s); if (r) return r; } // the picture controls set last, in place on slot 0's surfaces: 23 the pointwise form, 24 the stencil form with the hand-back of its scratch plane
             else if (stage >= 19) { // the conversion launch of a 10-bit picture in the raw staging buffer: 19 P010, 20 I420_10, 21 V210 tone-mapped; 22 P010 plain (section 20)
                 const int fmt = stage == 22 ? MI355ENC_FMT_P010 : MI355ENC_FMT_P010 + stage - 19, w = h->cfg.width, ht = h->cfg.height;

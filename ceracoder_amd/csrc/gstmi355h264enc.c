@@ -112,6 +112,7 @@ typedef struct {
     mi355enc_adjust_t adj;
     /* temporal noise reduction on the device (mi355enc_set_denoise): denoise-luma, denoise-chroma; stored and forwarded like the picture controls */
     mi355enc_denoise_t dn;
+    gint dn_motion; /* denoise-motion: the search range of its motion compensation (mi355enc_set_denoise_motion; section 25), 0: none */
     gint hdr_input, hdr_peak, hdr_target; /* hdr-input (0 off, 16 pq, 18 hlg), hdr-peak-nits, hdr-target-nits: read at the next set_format */
     gint open_rate;           /* 0: conversion off */
     GstClockTime tick;        /* duration of an output picture */
@@ -143,7 +144,7 @@ enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME
        PROP_SNAP_LOCATION, PROP_SNAP_INTERVAL, PROP_SNAP_QUALITY, PROP_SNAP_REDUCE, PROP_SNAP_SOURCE,
        PROP_OUTPUT_COLORIMETRY, PROP_RATE_CONVERSION, PROP_OUTPUT_FRAMERATE, PROP_MAX_FILL, PROP_HDR_INPUT, PROP_HDR_PEAK_NITS, PROP_HDR_TARGET_NITS,
        PROP_ADJ_BRIGHTNESS, PROP_ADJ_CONTRAST, PROP_ADJ_HUE, PROP_ADJ_SATURATION, PROP_ADJ_GAMMA, PROP_ADJ_SHARPEN, PROP_ADJ_SHARPEN_THRESHOLD,
-       PROP_DENOISE_LUMA, PROP_DENOISE_CHROMA };
+       PROP_DENOISE_LUMA, PROP_DENOISE_CHROMA, PROP_DENOISE_MOTION };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
     GST_STATIC_CAPS("video/x-raw, format=(string){ NV12, I420, YUY2, UYVY, Y42B, Y444, YV12, NV21, BGRx, RGBx, xRGB, xBGR, BGRA, RGBA, ARGB, ABGR, BGR, RGB, P010_10LE, I420_10LE, v210, GRAY8 }, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]; "
@@ -247,6 +248,7 @@ static void adjust_forward(GstMi355H264Enc *s) {
 /* stored noise filter strengths -> the encoder, if one is open (object lock held; the library builds three small tables and stores: no GPU call, any thread) */
 static void denoise_forward(GstMi355H264Enc *s) {
     if (s->enc && mi355enc_set_denoise(s->enc, &s->dn) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the noise filter's strengths: it keeps its previous ones");
+    if (s->enc && mi355enc_set_denoise_motion(s->enc, s->dn_motion) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the noise filter's search range: it keeps its previous one");
 }
 static void overlay_store_text(GstMi355H264Enc *s, const gchar *t) { g_strlcpy(s->ov_text, t ? t : "", sizeof s->ov_text); }
 
@@ -320,6 +322,7 @@ static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *
     case PROP_ADJ_SHARPEN_THRESHOLD: s->adj.sharpen_threshold = g_value_get_int(val); adjust_forward(s); break;
     case PROP_DENOISE_LUMA: s->dn.luma = g_value_get_int(val); denoise_forward(s); break;
     case PROP_DENOISE_CHROMA: s->dn.chroma = g_value_get_int(val); denoise_forward(s); break;
+    case PROP_DENOISE_MOTION: s->dn_motion = g_value_get_int(val); denoise_forward(s); break;
     case PROP_OUTPUT_COLORIMETRY: g_free(s->out_colorimetry); s->out_colorimetry = g_value_dup_string(val); break; /* (read at the next set_format) */
     case PROP_IMG_X: s->img_x = g_value_get_int(val); image_forward(s, FALSE); break;
     case PROP_IMG_Y: s->img_y = g_value_get_int(val); image_forward(s, FALSE); break;
@@ -394,6 +397,7 @@ static void get_property(GObject *obj, guint id, GValue *val, GParamSpec *ps) {
     case PROP_ADJ_SHARPEN_THRESHOLD: g_value_set_int(val, s->adj.sharpen_threshold); break;
     case PROP_DENOISE_LUMA: g_value_set_int(val, s->dn.luma); break;
     case PROP_DENOISE_CHROMA: g_value_set_int(val, s->dn.chroma); break;
+    case PROP_DENOISE_MOTION: g_value_set_int(val, s->dn_motion); break;
     case PROP_OUTPUT_COLORIMETRY: g_value_set_string(val, s->out_colorimetry ? s->out_colorimetry : ""); break;
     case PROP_IMG_X: g_value_set_int(val, s->img_x); break;
     case PROP_IMG_Y: g_value_set_int(val, s->img_y); break;
@@ -1253,6 +1257,7 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
     g_object_class_install_property(g, PROP_ADJ_SHARPEN_THRESHOLD, g_param_spec_int("sharpen-threshold", "Sharpen threshold", "with sharpen > 0: detail of at most this many codes is left alone (coring)", 0, 32, 0, F));
     g_object_class_install_property(g, PROP_DENOISE_LUMA, g_param_spec_int("denoise-luma", "Denoise luma", "temporal noise reduction on the GPU, motion-adaptive, in front of the picture controls: the luma noise amplitude in codes that is filtered fully; 0: off", 0, MI355ENC_DENOISE_MAX, 0, F));
     g_object_class_install_property(g, PROP_DENOISE_CHROMA, g_param_spec_int("denoise-chroma", "Denoise chroma", "temporal noise reduction on the GPU: the chroma noise amplitude in codes that is filtered fully; 0: off", 0, MI355ENC_DENOISE_MAX, 0, F));
+    g_object_class_install_property(g, PROP_DENOISE_MOTION, g_param_spec_int("denoise-motion", "Denoise motion", "motion compensation of the temporal noise reduction: per 8 x 8 block the history is searched within this many luma samples; 0: none (the filter lets go where the picture moves)", 0, MI355ENC_DENOISE_MOTION_MAX, 0, F));
     g_object_class_override_property(g, PROP_VIDEO_DIRECTION, "video-direction"); /* GstVideoDirection: identity, 90r, 180, 90l, horiz, vert, ul-lr, ur-ll, auto -- as on videoflip */
     g_object_class_install_property(g, PROP_STATS, g_param_spec_boolean("stats", "Print stats", "Print a JSON line with counters when the encoder closes", FALSE, F));
     gst_element_class_add_static_pad_template(e, &sink_tmpl);
@@ -1274,6 +1279,7 @@ static void gst_mi355h264enc_init(GstMi355H264Enc *s) {
     s->hdr_input = 0; s->hdr_peak = 0; s->hdr_target = 0;
     mi355enc_adjust_default(&s->adj);
     mi355enc_denoise_default(&s->dn);
+    s->dn_motion = 0;
     s->rate_mode = 0; s->out_fps_n = 0; s->out_fps_d = 1; s->max_fill = 2; s->open_rate = 0; s->tick = GST_CLOCK_TIME_NONE; s->rate_qh = s->rate_qn = 0;
     s->snap_location = NULL; s->snap_interval = 1000; s->snap_quality = 75; s->snap_reduce = 4; s->snap_source = 0; s->snap_next = GST_CLOCK_TIME_NONE; s->snap_watch = 0;
     g_mutex_init(&s->snap_mu); g_mutex_init(&s->snap_enc_mu); g_cond_init(&s->snap_cv);

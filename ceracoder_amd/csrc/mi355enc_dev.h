@@ -217,6 +217,13 @@ int k_launch_adjust_sharpen(const uint8_t *y, uint8_t *out, int W, int H, int vw
  * lmode 1: the luma is filtered, 0: it primes / follows (H' = 16 c, the luma surface is not written); cmode 2: the chroma is filtered, 1: it primes, 0: neither
  * read nor written.  tabs: 768 bytes -- B, the luma's P, the chroma's P (mi355enc_denoise_tables) --, needed when anything is filtered.  -1: arguments outside that */
 int k_launch_denoise(uint8_t *y, uint8_t *uv, uint16_t *hy, uint16_t *huv, int W, int H, int vw, int vh, int lmode, int cmode, const uint8_t *tabs, hipStream_t s);
+/* ... with motion compensation.  The search: per aligned 8 x 8 luma block with a visible sample the vector into the history hy within
+ * `range` (1 .. 16) whose key is smallest, lambda (0 .. 128) the penalty per sample of vector length; vec: (W / 8) (H / 8) words in raster order -- dx in byte 0,
+ * dy in byte 1 (int8), the vector's cost M in the high half; zero for a block without a visible sample.  The compensated filter: k_launch_denoise with the
+ * histories read (hy, huv) and written (ny, nuv: other buffers) apart, the history read at the block's vector; something is filtered (lmode 1 or cmode 2). */
+int k_launch_denoise_search(const uint8_t *y, const uint16_t *hy, unsigned *vec, int W, int H, int vw, int vh, int range, int lambda, hipStream_t s);
+int k_launch_denoise_mc(uint8_t *y, uint8_t *uv, const uint16_t *hy, const uint16_t *huv, uint16_t *ny, uint16_t *nuv, const unsigned *vec, int W, int H, int vw, int vh,
+                        int lmode, int cmode, const uint8_t *tabs, hipStream_t s);
 /* Downscaling of the input picture to the coded size (k_scale.hip; the rule: DESIGN.md section 10).  Tables built on the host
  * (enc_scale.cpp), five of them: 0 luma horizontal, 1 luma vertical, 2 chroma horizontal, 3 chroma vertical from 4:2:0 input, 4 chroma
  * vertical from 4:2:2 input.  Entry i of table t: first[t][i] (first source index, not clamped) and q[t][i * taps[t] + k]. */

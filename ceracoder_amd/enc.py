@@ -34,6 +34,8 @@ SURF_ROWS, SURF_COLS = 35, 36
 DROP_MAX, DROP_SKIP = 12, 255
 STAGE_ME, STAGE_INTER, STAGE_INTRA, STAGE_DEBLOCK, STAGE_SUBPEL, STAGE_CSC_I420, STAGE_CSC_YUY2, STAGE_CSC_UYVY, STAGE_ME_SELECT, STAGE_PMB, STAGE_INTRA_P, STAGE_QUALITY, STAGE_JPEG, STAGE_ORIENT, STAGE_SCALE, STAGE_IMAGE, STAGE_SNAPSHOT, STAGE_YUV_CONVERT, STAGE_RATE = range(19)
 STAGE_ADJUST_POINT, STAGE_ADJUST_SHARPEN = 23, 24  # the picture controls set last on slot 0's surfaces: pointwise form, stencil form
+STAGE_DENOISE_SEARCH, STAGE_DENOISE_MC = 27, 28  # ... with motion compensation: the search alone, the search and the compensated filter
+DENOISE_MOTION_MAX = 16
 STAGE_DENOISE, STAGE_DENOISE_PRIME = 25, 26  # the temporal noise filter set last on slot 0's surfaces and the handle's history: filtering, priming
 STAGE_HDR_P010, STAGE_HDR_I420_10, STAGE_HDR_V210, STAGE_DEEP_P010 = 19, 20, 21, 22  # the tone-mapping launch per format, and the plain P010 launch beside it
 HDR_PQ, HDR_HLG = 16, 18  # mi355enc_set_hdr_input: the transfer's H.264 Table E-4 code point
@@ -69,6 +71,7 @@ EXPORTS = [
     "mi355enc_debug_adjust_bytes",
     "mi355enc_denoise_default", "mi355enc_denoise_check", "mi355enc_denoise_tables", "mi355enc_set_denoise", "mi355enc_get_denoise", "mi355enc_last_denoise", "mi355enc_stage_denoise",
     "mi355enc_debug_denoise_bytes",
+    "mi355enc_set_denoise_motion", "mi355enc_get_denoise_motion", "mi355enc_last_denoise_motion", "mi355enc_denoise_motion_key", "mi355enc_stage_denoise_search", "mi355enc_stage_denoise_mc",
 ]
 
 
@@ -275,6 +278,13 @@ def load():
         L.mi355enc_stage_denoise.argtypes = [vp, C.POINTER(Denoise)] + [vp] * 6
         L.mi355enc_debug_denoise_bytes.restype = C.c_size_t
         L.mi355enc_debug_denoise_bytes.argtypes = [vp]
+        L.mi355enc_set_denoise_motion.argtypes = [vp, C.c_int]
+        L.mi355enc_get_denoise_motion.argtypes = [vp, C.POINTER(C.c_int)]
+        L.mi355enc_last_denoise_motion.argtypes = [vp, C.POINTER(C.c_int)]
+        L.mi355enc_denoise_motion_key.restype = C.c_uint32
+        L.mi355enc_denoise_motion_key.argtypes = [C.c_int] * 4
+        L.mi355enc_stage_denoise_search.argtypes = [vp, C.POINTER(Denoise), C.c_int, vp, vp, vp]
+        L.mi355enc_stage_denoise_mc.argtypes = [vp, C.POINTER(Denoise), C.c_int] + [vp] * 7
         L.mi355enc_set_quality_metrics.argtypes = [vp, C.c_int]
         L.mi355enc_last_quality.argtypes = [vp, C.POINTER(Quality)]
         L.mi355enc_quality_totals.argtypes = [vp, C.POINTER(Quality)]
@@ -456,6 +466,16 @@ def denoise_tables(d=None, **kw):
     if r:
         raise EncoderError("mi355enc_denoise_tables(%r): %d" % (st.as_dict(), r))
     return tuple(t)
+
+
+def denoise_motion_key(cost, dx, dy, s):
+    """mi355enc_denoise_motion_key (host only): the word the motion search ranks a candidate by; 0xFFFFFFFF for arguments outside its ranges"""
+    return int(load().mi355enc_denoise_motion_key(int(cost), int(dx), int(dy), int(s)))
+
+
+def _denoise_vectors(words):
+    """the search's words per block -> (vec (.., 2) int8 as (dx, dy), M uint16)"""
+    return np.stack([(words & 255).astype(np.uint8).view(np.int8), ((words >> 8) & 255).astype(np.uint8).view(np.int8)], axis=-1), (words >> 16).astype(np.uint16)
 
 
 def hdr_tables(transfer, full_range=0, peak_nits=0, target_nits=0, out_matrix=1, out_full=0):
@@ -891,8 +911,10 @@ class Encoder:
             except EncoderError:
                 self.close()
                 raise
-        if denoise is not None:  # dict(luma=, chroma=): the temporal noise filter's strengths, from the first picture on
+        if denoise is not None:  # dict(luma=, chroma=, motion=): the temporal noise filter's strengths and its search range (default 0: no motion compensation), from the first picture on
             try:
+                denoise = denoise.as_dict() if isinstance(denoise, Denoise) else dict(denoise)
+                self.set_denoise_motion(denoise.pop("motion", 0))
                 self.set_denoise(denoise)
             except EncoderError:
                 self.close()
@@ -1016,6 +1038,46 @@ class Encoder:
 
     def debug_denoise_bytes(self):
         return int(self.L.mi355enc_debug_denoise_bytes(self.h))
+
+    def set_denoise_motion(self, rng):
+        """the noise filter's motion compensation from the next submitted picture on (any time, any thread): the search range, 0 .. 16 luma samples; 0: none"""
+        self._chk(self.L.mi355enc_set_denoise_motion(self.h, int(rng)), "set_denoise_motion")
+
+    def get_denoise_motion(self):
+        v = C.c_int(0)
+        self._chk(self.L.mi355enc_get_denoise_motion(self.h, C.byref(v)), "get_denoise_motion")
+        return v.value
+
+    def last_denoise_motion(self):
+        """the range the last collected picture was submitted under; EncoderError before the first collect"""
+        v = C.c_int(0)
+        self._chk(self.L.mi355enc_last_denoise_motion(self.h, C.byref(v)), "last_denoise_motion")
+        return v.value
+
+    def stage_denoise_search(self, d, rng, y, hist_y):
+        """The motion search alone: a luma plane of the coded size against a luma history (uint16, its shape), with the handle's visible size.  Returns (vec, M):
+        per 8 x 8 block (dx, dy) as int8 (rows, columns, 2) and the vector's cost (uint16); zeros for a block without a visible sample."""
+        st = denoise(d)
+        y, hist_y = np.ascontiguousarray(y, np.uint8), np.ascontiguousarray(hist_y, np.uint16)
+        assert y.shape == (self.mbh * 16, self.mbw * 16) and hist_y.shape == y.shape
+        words = np.zeros((self.mbh * 2, self.mbw * 2), np.uint32)
+        self._chk(self.L.mi355enc_stage_denoise_search(self.h, C.byref(st), int(rng), _p(y), _p(hist_y), _p(words)), "stage_denoise_search")
+        return _denoise_vectors(words)
+
+    def stage_denoise_mc(self, d, rng, y, uv, hist_y=None, hist_uv=None):
+        """stage_denoise with a search range (0: that call itself).  Returns (y, uv, hist_y, hist_uv, vec, M): behind stage_denoise's four the search's result as
+        stage_denoise_search returns it (zeros where no search ran)."""
+        st = denoise(d)
+        y, uv = np.ascontiguousarray(y, np.uint8).copy(), np.ascontiguousarray(uv, np.uint8).copy()
+        assert y.shape == (self.mbh * 16, self.mbw * 16) and uv.shape == (self.mbh * 8, self.mbw * 16)
+        hin = [None if a is None else np.ascontiguousarray(a, np.uint16) for a in (hist_y, hist_uv)]
+        assert all(a is None or a.shape == p.shape for a, p in zip(hin, (y, uv)))
+        hy = np.zeros(y.shape, np.uint16) if st.luma or st.chroma else None
+        huv = np.zeros(uv.shape, np.uint16) if st.chroma else None
+        words = np.zeros((self.mbh * 2, self.mbw * 2), np.uint32)
+        ptr = lambda a: None if a is None else _p(a)
+        self._chk(self.L.mi355enc_stage_denoise_mc(self.h, C.byref(st), int(rng), ptr(hin[0]), ptr(hin[1]), _p(y), _p(uv), ptr(hy), ptr(huv), _p(words)), "stage_denoise_mc")
+        return (y, uv, hy, huv) + _denoise_vectors(words)
 
     def stage_yuv_convert(self, y, uv):
         """The colour step alone on host planes of the coded size, with the handle's geometry, orientation and colorimetries; returns the converted copies."""

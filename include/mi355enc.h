@@ -350,7 +350,31 @@ int mi355enc_last_denoise(mi355enc_t *h, mi355enc_denoise_t *d); /* of the last 
  * written whenever d is not off, hist_uv_out when d->chroma > 0; either may be NULL.  The handle's own setting and history are not touched. */
 int mi355enc_stage_denoise(mi355enc_t *h, const mi355enc_denoise_t *d, const uint16_t *hist_y, const uint16_t *hist_uv, uint8_t *y, uint8_t *uv,
                            uint16_t *hist_y_out, uint16_t *hist_uv_out);
-size_t mi355enc_debug_denoise_bytes(const mi355enc_t *h); /* device bytes of the handle's history: 0 until the first filtered picture, then 2 per luma and per chroma sample kept */
+size_t mi355enc_debug_denoise_bytes(const mi355enc_t *h); /* device bytes of the handle's history: 0 until the first filtered picture, then 2 per luma and per chroma sample kept (with motion compensation: twice that and 4 per 8 x 8 block) */
+/* Motion compensation of the filter: per aligned 8 x 8 luma block with a visible sample, a whole-sample vector (dx, dy) into the history.
+ *   search   Q = (H_luma + 8) >> 4; the candidates are all (dx, dy) with |dx|, |dy| <= range whose displaced block lies inside the coded surface (margins
+ *            included); cost = sum |c(x, y) - Q(x + dx, y + dy)| over the block; key = ((cost + 4 s (|dx| + |dy|)) << 16) | rank with s the strength that builds
+ *            B and rank = (|dx| + |dy|) * 1089 + (dy + 16) * 33 + (dx + 16); the block's vector is the candidate with the smallest key.  It runs whenever the
+ *            block measure runs (a plane is filtered, not priming), and M is its cost.
+ *   luma     the sample rule with H(x + dx, y + dy); H' and out are written at (x, y)
+ *   chroma   H.264's chroma prediction for a whole-sample luma vector, on the history, per byte of the pair: the pair at (dx >> 1, dy >> 1), the rounded mean
+ *            of two along an odd axis, (a + b + c + d + 2) >> 2 of four with both odd
+ * Everything else is the filter's as described above; a change of range between pictures, 0 included, keeps the history.  range: 0 .. 16 luma samples, 0 (the
+ * default): none, exactly the filter above.  Callable at any time from any thread, no GPU call; latched per input picture beside the strengths.  With both
+ * strengths 0 the range has no effect.  The history is double-buffered from the first picture that is filtered with a range above 0. */
+#define MI355ENC_DENOISE_MOTION_MAX 16
+int mi355enc_set_denoise_motion(mi355enc_t *h, int range); /* MI355ENC_ERR_ARG outside 0 .. 16 */
+int mi355enc_get_denoise_motion(const mi355enc_t *h, int *range);
+int mi355enc_last_denoise_motion(mi355enc_t *h, int *range); /* of the last collected picture; MI355ENC_ERR_STATE before the first collect */
+/* host only: the key of a candidate; 0xFFFFFFFF for arguments outside cost 0 .. 16320, |dx|, |dy| <= 16, s 0 .. 32 */
+uint32_t mi355enc_denoise_motion_key(int cost, int dx, int dy, int s);
+/* the search alone (tests): a luma surface of the coded size and a luma history on host arrays; vec_out: (coded width / 8) x (coded height / 8) words in raster
+ * order -- dx in byte 0, dy in byte 1 (int8), the vector's cost M in the high half; zero for a block without a visible sample.  d not off, range 1 .. 16 */
+int mi355enc_stage_denoise_search(mi355enc_t *h, const mi355enc_denoise_t *d, int range, const uint8_t *y, const uint16_t *hist_y, uint32_t *vec_out);
+/* mi355enc_stage_denoise with a range (0: that call itself), on histories of its own; vec_out (may be NULL): the search's words as above, zeros where no search
+ * ran (range 0, or nothing is filtered) */
+int mi355enc_stage_denoise_mc(mi355enc_t *h, const mi355enc_denoise_t *d, int range, const uint16_t *hist_y, const uint16_t *hist_uv, uint8_t *y, uint8_t *uv,
+                              uint16_t *hist_y_out, uint16_t *hist_uv_out, uint32_t *vec_out);
 /* like mi355enc_submit, from host memory in `fmt`; planes[]/strides[]: as many entries as the format has planes */
 int mi355enc_submit_fmt(mi355enc_t *h, int fmt, const uint8_t *const planes[3], const int strides[3], int64_t pts, int force_idr);
 /* conversion stage alone (tests): writes the coded-size NV12 surfaces (16*mbw x 16*mbh luma, then interleaved chroma) */
@@ -731,6 +755,8 @@ int mi355enc_stage_deblock(mi355enc_t *h, uint8_t *rec_y, uint8_t *rec_uv, const
  * 25 / 26 the temporal noise filter set last (mi355enc_set_denoise) in place on slot 0's source surfaces and the handle's history: 25 filtering (the history
  * primed by the launch in front of the timed ones, if it was not valid), 26 priming (MI355ENC_ERR_STATE when the value set last is off).  Both leave the
  * history invalid: the next picture submitted primes.
+ * 27 / 28 its motion-compensated form with the range set last (mi355enc_set_denoise_motion; MI355ENC_ERR_STATE when that is 0 or the filter is off): 27 the
+ * search alone, 28 the search and the compensated filter.  They leave the history invalid likewise.
  * Uses whatever the handle's surfaces currently hold.  Returns average ms per launch. */
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms);
 

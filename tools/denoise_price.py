@@ -7,7 +7,10 @@ decoder reproduces: tests/test_denoise_gpu.py) against the CLEAN clip, not the n
 on a tripod the filter is for; the benchmark's clip pans, and a filter without motion compensation has little to work with there.  Prints two markdown tables.
 
 --fps STRENGTH: frames/s of the benchmark's 1080p IPPP configuration (60 pictures/s, GOP 60, 6 Mbit/s, three pictures in flight, pictures from device memory)
-with the filter at STRENGTH (0: off) in this process; one JSON line.  Run it in alternating processes to compare."""
+with the filter at STRENGTH (0: off) in this process; one JSON line.  Run it in alternating processes to compare.
+
+--motion R [R ...]: the motion-compensated form -- the pan's table alone, with the filter off, at strength 8, and at strength 8 with each
+search range R; with --fps, the one range the filter runs with."""
 import argparse
 import json
 import os
@@ -32,14 +35,15 @@ def clips(n, still, seed=2400):
     return clean, noisy
 
 
-def price(n, still):
+def price(n, still, cases=((0, 0), (4, 0), (8, 0))):
+    """cases: (strength, search range) per row"""
     clean, noisy = clips(n, still)
     print("%s, %d pictures, Gaussian noise sigma %g:\n" % ("The clip's first picture held still (a camera on a tripod)" if still else "The benchmark's clip (a pan with moving objects)", n, SIGMA))
     print("| QP | filter | bytes / P picture | macroblocks without residual | PSNR-Y against the clean clip (dB) | PSNR-Y of the source against the clean clip (dB) |")
     print("|---|---|---|---|---|---|")
     for qp in (26, 32, 38):
-        for s in (0, 4, 8):
-            e = E.Encoder(W, H, fps=60, gop=n, fixed_qp=qp, denoise=dict(luma=s, chroma=s))
+        for s, r in cases:
+            e = E.Encoder(W, H, fps=60, gop=n, fixed_qp=qp, denoise=dict(luma=s, chroma=s, motion=r))
             size, bare, psnr, src = [], [], [], []
             for i in range(n):
                 au = e.encode(*noisy[i], pts=i)[0]
@@ -51,10 +55,10 @@ def price(n, still):
                 psnr.append(synth.psnr(e.fetch(E.FETCH_RECON_Y)[:H, :W], clean[i][0]))
                 src.append(synth.psnr(e.fetch(E.FETCH_SOURCE_Y)[:H, :W], clean[i][0]))
             e.close()
-            print("| %d | %s | %d | %.1f %% | %.2f | %.2f |" % (qp, s or "off", round(np.mean(size)), 100 * np.mean(bare), np.mean(psnr), np.mean(src)), flush=True)
+            print("| %d | %s | %d | %.1f %% | %.2f | %.2f |" % (qp, ("%d, range %d" % (s, r) if r else s) if s else "off", round(np.mean(size)), 100 * np.mean(bare), np.mean(psnr), np.mean(src)), flush=True)
 
 
-def fps(strength, steps, warmup, unique=32):
+def fps(strength, steps, warmup, unique=32, motion=0):
     import torch
     frames = np.empty((unique, H * 3 // 2, W), np.uint8)
     rng = np.random.default_rng(2400)
@@ -63,7 +67,7 @@ def fps(strength, steps, warmup, unique=32):
     frames = np.clip(np.rint(frames + SIGMA * rng.standard_normal(frames.shape, dtype=np.float32)), 0, 255).astype(np.uint8)
     dev = torch.from_numpy(frames).cuda()
     base, fbytes = dev.data_ptr(), dev.stride(0)
-    e = E.Encoder(W, H, fps=60, gop=60, bitrate_bps=6_000_000, pipeline_depth=2, exclusive=True, denoise=dict(luma=strength, chroma=strength))
+    e = E.Encoder(W, H, fps=60, gop=60, bitrate_bps=6_000_000, pipeline_depth=2, exclusive=True, denoise=dict(luma=strength, chroma=strength, motion=motion))
 
     def run(n, first):
         for i in range(first, first + n):
@@ -80,7 +84,7 @@ def fps(strength, steps, warmup, unique=32):
     run(steps, warmup)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    print(json.dumps(dict(denoise=strength, steps=steps, frames_per_s=round(steps / dt, 2), history_bytes=e.debug_denoise_bytes())), flush=True)
+    print(json.dumps(dict(denoise=strength, motion=motion, steps=steps, frames_per_s=round(steps / dt, 2), history_bytes=e.debug_denoise_bytes())), flush=True)
     e.close()
 
 
@@ -90,10 +94,13 @@ if __name__ == "__main__":
     ap.add_argument("--pictures", type=int, default=16)
     ap.add_argument("--steps", type=int, default=1200)
     ap.add_argument("--warmup", type=int, default=120)
+    ap.add_argument("--motion", type=int, nargs="+", default=None, metavar="R")
     a = ap.parse_args()
-    if a.fps is None:
+    if a.fps is not None:
+        fps(a.fps, a.steps, a.warmup, motion=a.motion[0] if a.motion else 0)
+    elif a.motion:
+        price(a.pictures, False, [(0, 0), (8, 0)] + [(8, r) for r in a.motion])
+    else:
         price(a.pictures, False)
         print()
         price(a.pictures, True)
-    else:
-        fps(a.fps, a.steps, a.warmup)
