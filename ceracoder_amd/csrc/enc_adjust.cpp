@@ -54,11 +54,11 @@ void adjust_collected(mi355enc_t *h, slot_t *s) {
     h->adj_last.a = s->adj.a; h->adj_last.parts = s->adj.parts;
 }
 
-bool adjust_time_ready(mi355enc_t *h, bool stencil) {
+bool adjust_time_ready(mi355enc_t *h, int stage) {
     std::lock_guard<std::mutex> g(h->adj_mu);
-    return h->adj_cur.parts && !(h->adj_cur.parts & ADJUST_SHARPEN) == !stencil;
+    return h->adj_cur.parts && !(h->adj_cur.parts & ADJUST_SHARPEN) == (stage != 24);
 }
-int adjust_time_launch(mi355enc_t *h, slot_t *s) {
+int adjust_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *) {
     adjust_set_t set;
     { std::lock_guard<std::mutex> g(h->adj_mu); set = h->adj_cur; }
     return adjust_run(h, s, &set, h->stream);
@@ -101,15 +101,12 @@ int mi355enc_last_adjust(mi355enc_t *h, mi355enc_adjust_t *a) {
 
 int mi355enc_stage_adjust(mi355enc_t *h, const mi355enc_adjust_t *a, uint8_t *y, uint8_t *uv) {
     if (!h || !y || !uv || mi355enc_adjust_check(a)) return MI355ENC_ERR_ARG;
-    if (h->pending) return MI355ENC_ERR_STATE;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    { int r = sync_compute(h); if (r) return r; }
     adjust_set_t set;
     adjust_make(h, a, &set);
     slot_t *s = &h->slot[0];
-    HIPCHK(hipMemcpyAsync(s->d_src_y, y, h->ysz, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(s->d_src_uv, uv, h->csz, hipMemcpyHostToDevice, h->stream));
-    int r = adjust_run(h, s, &set, h->stream);
+    int r = stage_enter(h);
+    if (!r) r = stage_in(h, s, y, uv);
+    if (!r) r = adjust_run(h, s, &set, h->stream);
     return r ? r : stage_out(h, s, y, uv);
 }
 

@@ -127,13 +127,11 @@ int mi355enc_set_input_colorimetry(mi355enc_t *h, int full_range, int matrix) {
 
 int mi355enc_stage_yuv_convert(mi355enc_t *h, uint8_t *y, uint8_t *uv) {
     if (!h || !y || !uv) return MI355ENC_ERR_ARG;
-    if (h->pending || !h->yuv_on) return MI355ENC_ERR_STATE;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    { int r = sync_compute(h); if (r) return r; }
+    if (!h->yuv_on) return MI355ENC_ERR_STATE;
     slot_t *s = &h->slot[0];
-    HIPCHK(hipMemcpyAsync(s->d_src_y, y, h->ysz, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(s->d_src_uv, uv, h->csz, hipMemcpyHostToDevice, h->stream));
-    int r = yuv_draw(h, s, h->stream);
+    int r = stage_enter(h);
+    if (!r) r = stage_in(h, s, y, uv);
+    if (!r) r = yuv_draw(h, s, h->stream);
     return r ? r : stage_out(h, s, y, uv);
 }
 
@@ -149,7 +147,7 @@ int mi355enc_host_write_headers_vui(int width, int height, int fps_num, int fps_
 
 int mi355enc_stage_csc_device(mi355enc_t *h, int fmt, const void *const d_planes[3], const int strides[3], void *d_out_y, void *d_out_uv) {
     if (!h || !d_planes || !strides || !d_planes[0] || !d_out_y || !d_out_uv || (((uintptr_t)d_out_y | (uintptr_t)d_out_uv) & 7)) return MI355ENC_ERR_ARG;
-    if (h->pending) return MI355ENC_ERR_STATE;
+    { int r = stage_enter(h); if (r) return r; }
     const int w = h->cfg.width, ht = h->cfg.height;
     const uint8_t *p[3] = {(const uint8_t *)d_planes[0], (const uint8_t *)d_planes[1], (const uint8_t *)d_planes[2]};
     int st[3] = {strides[0], strides[1], strides[2]};
@@ -159,7 +157,6 @@ int mi355enc_stage_csc_device(mi355enc_t *h, int fmt, const void *const d_planes
     const int nplanes = fmt == MI355ENC_FMT_NV12 ? 0 : fmt_planes(fmt, w, ht, pl);
     if (!nplanes || !planes_fit(nplanes, pl, p, st)) return MI355ENC_ERR_ARG;
     if ((fmt_is_rgb(fmt) && !h->csc_ok) || hdr_refuses(h, fmt)) return MI355ENC_ERR_ARG;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
     int r;
     if (h->hdr_on) r = hdr_convert(h, fmt, p, st, (uint8_t *)d_out_y, (uint8_t *)d_out_uv, w, ht, h->W, h->H, h->stream); // (tone-mapped: DESIGN.md section 22)
     else if (fmt <= MI355ENC_FMT_UYVY) r = k_launch_csc(fmt, p[0], p[1], p[2], st[0], st[1], st[2], (uint8_t *)d_out_y, (uint8_t *)d_out_uv, w, ht, h->W, h->H, h->stream);

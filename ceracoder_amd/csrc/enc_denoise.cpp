@@ -99,7 +99,8 @@ bool denoise_time_ready(mi355enc_t *h, int stage) {
     std::lock_guard<std::mutex> g(h->dn_mu);
     return h->dn_cur.parts != 0 && (stage < 27 || h->dn_cur.range > 0);
 }
-int denoise_time_launch(mi355enc_t *h, slot_t *s, int stage) {
+int denoise_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x) {
+    const int stage = x->stage;
     denoise_set_t set;
     { std::lock_guard<std::mutex> g(h->dn_mu); set = h->dn_cur; }
     if (stage < 27) set.range = 0; // (the in-place forms)
@@ -176,43 +177,34 @@ int mi355enc_stage_denoise_mc(mi355enc_t *h, const mi355enc_denoise_t *d, int ra
                               uint16_t *hist_y_out, uint16_t *hist_uv_out, uint32_t *vec_out) {
     if (!h || !y || !uv || mi355enc_denoise_check(d) || (hist_uv && !hist_y)) return MI355ENC_ERR_ARG; // (a chroma history is filtered by a measure, which reads the luma's)
     if (range < 0 || range > MI355ENC_DENOISE_MOTION_MAX) return MI355ENC_ERR_ARG;
-    if (h->pending) return MI355ENC_ERR_STATE;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    { int r = sync_compute(h); if (r) return r; }
+    { int r = stage_enter(h); if (r) return r; }
     denoise_set_t set;
     denoise_make(d, &set);
     set.range = range;
     slot_t *s = &h->slot[0];
     const size_t vb = denoise_vec_bytes(h);
     if (vec_out) memset(vec_out, 0, vb);
-    HIPCHK(hipMemcpyAsync(s->d_src_y, y, h->ysz, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(s->d_src_uv, uv, h->csz, hipMemcpyHostToDevice, h->stream));
+    { int r = stage_in(h, s, y, uv); if (r) return r; }
     if (!set.parts) return stage_out(h, s, y, uv);
     // what the previous picture must have had for these histories to be valid: the luma's was filtered (d->luma > 0) or followed (the chroma's was filtered)
     const mi355enc_denoise_t prev = {hist_y && d->luma > 0 ? d->luma : 0, hist_uv ? d->chroma : 0};
     const denoise_form_t f = denoise_form(&set, &prev);
     // histories of the call's own: the handle's are its stream's.  The compensated form writes second ones
-    uint16_t *hy = nullptr, *huv = nullptr, *ny = nullptr, *nuv = nullptr;
-    unsigned *vec = nullptr;
-    int r = MI355ENC_OK;
-    if (hipMalloc((void **)&hy, 2 * h->ysz) != hipSuccess || (d->chroma > 0 && hipMalloc((void **)&huv, 2 * h->csz) != hipSuccess)) r = MI355ENC_ERR_HIP;
-    if (!r && f.mc && (hipMalloc((void **)&ny, 2 * h->ysz) != hipSuccess || hipMalloc((void **)&vec, vb) != hipSuccess)) r = MI355ENC_ERR_HIP;
-    if (!r && f.mc && d->chroma > 0 && hipMalloc((void **)&nuv, 2 * h->csz) != hipSuccess) r = MI355ENC_ERR_HIP;
-    if (!r && hist_y && hipMemcpyAsync(hy, hist_y, 2 * h->ysz, hipMemcpyHostToDevice, h->stream) != hipSuccess) r = MI355ENC_ERR_HIP;
-    if (!r && hist_uv && huv && hipMemcpyAsync(huv, hist_uv, 2 * h->csz, hipMemcpyHostToDevice, h->stream) != hipSuccess) r = MI355ENC_ERR_HIP;
-    if (!r) r = f.mc ? denoise_run_mc(h, s->d_src_y, s->d_src_uv, hy, huv, ny, nuv, vec, &set, f, h->stream) : denoise_run(h, s->d_src_y, s->d_src_uv, hy, huv, &set, f, h->stream);
+    stage_tmp_t thy(h->stream), thuv(h->stream), tny(h->stream), tnuv(h->stream), tvec(h->stream);
+    if (thy.alloc(2 * h->ysz) || (d->chroma > 0 && thuv.alloc(2 * h->csz))) return MI355ENC_ERR_HIP;
+    if (f.mc && (tny.alloc(2 * h->ysz) || tvec.alloc(vb) || (d->chroma > 0 && tnuv.alloc(2 * h->csz)))) return MI355ENC_ERR_HIP;
+    uint16_t *hy = thy.as<uint16_t>(), *huv = thuv.as<uint16_t>(), *ny = tny.as<uint16_t>(), *nuv = tnuv.as<uint16_t>();
+    unsigned *vec = tvec.as<unsigned>();
+    if (hist_y) HIPCHK(hipMemcpyAsync(hy, hist_y, 2 * h->ysz, hipMemcpyHostToDevice, h->stream));
+    if (hist_uv && huv) HIPCHK(hipMemcpyAsync(huv, hist_uv, 2 * h->csz, hipMemcpyHostToDevice, h->stream));
+    int r = f.mc ? denoise_run_mc(h, s->d_src_y, s->d_src_uv, hy, huv, ny, nuv, vec, &set, f, h->stream) : denoise_run(h, s->d_src_y, s->d_src_uv, hy, huv, &set, f, h->stream);
     if (!r) r = stage_out(h, s, y, uv); // (waits for the main stream)
+    if (r) return r;
     const uint16_t *oy = f.mc ? ny : hy, *ouv = f.mc ? nuv : huv;
-    if (!r && hist_y_out && hipMemcpy(hist_y_out, oy, 2 * h->ysz, hipMemcpyDeviceToHost) != hipSuccess) r = MI355ENC_ERR_HIP;
-    if (!r && hist_uv_out && ouv && hipMemcpy(hist_uv_out, ouv, 2 * h->csz, hipMemcpyDeviceToHost) != hipSuccess) r = MI355ENC_ERR_HIP;
-    if (!r && vec_out && vec && hipMemcpy(vec_out, vec, vb, hipMemcpyDeviceToHost) != hipSuccess) r = MI355ENC_ERR_HIP;
-    if (r) (void)hipStreamSynchronize(h->stream);
-    if (hy) (void)hipFree(hy);
-    if (huv) (void)hipFree(huv);
-    if (ny) (void)hipFree(ny);
-    if (nuv) (void)hipFree(nuv);
-    if (vec) (void)hipFree(vec);
-    return r;
+    if (hist_y_out) HIPCHK(hipMemcpy(hist_y_out, oy, 2 * h->ysz, hipMemcpyDeviceToHost));
+    if (hist_uv_out && ouv) HIPCHK(hipMemcpy(hist_uv_out, ouv, 2 * h->csz, hipMemcpyDeviceToHost));
+    if (vec_out && vec) HIPCHK(hipMemcpy(vec_out, vec, vb, hipMemcpyDeviceToHost));
+    return MI355ENC_OK;
 }
 
 int mi355enc_stage_denoise(mi355enc_t *h, const mi355enc_denoise_t *d, const uint16_t *hist_y, const uint16_t *hist_uv, uint8_t *y, uint8_t *uv,
@@ -222,26 +214,21 @@ int mi355enc_stage_denoise(mi355enc_t *h, const mi355enc_denoise_t *d, const uin
 
 int mi355enc_stage_denoise_search(mi355enc_t *h, const mi355enc_denoise_t *d, int range, const uint8_t *y, const uint16_t *hist_y, uint32_t *vec_out) {
     if (!h || !y || !hist_y || !vec_out || mi355enc_denoise_check(d) || !denoise_parts(d) || range < 1 || range > MI355ENC_DENOISE_MOTION_MAX) return MI355ENC_ERR_ARG;
-    if (h->pending) return MI355ENC_ERR_STATE;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    { int r = sync_compute(h); if (r) return r; }
+    { int r = stage_enter(h); if (r) return r; }
     denoise_set_t set;
     denoise_make(d, &set);
     set.range = range;
     slot_t *s = &h->slot[0];
     HIPCHK(hipMemcpyAsync(s->d_src_y, y, h->ysz, hipMemcpyHostToDevice, h->stream));
     const size_t vb = denoise_vec_bytes(h);
-    uint16_t *hy = nullptr;
-    unsigned *vec = nullptr;
-    int r = MI355ENC_OK;
-    if (hipMalloc((void **)&hy, 2 * h->ysz) != hipSuccess || hipMalloc((void **)&vec, vb) != hipSuccess) r = MI355ENC_ERR_HIP;
-    if (!r && hipMemcpyAsync(hy, hist_y, 2 * h->ysz, hipMemcpyHostToDevice, h->stream) != hipSuccess) r = MI355ENC_ERR_HIP;
-    if (!r) r = denoise_run_search(h, s->d_src_y, hy, vec, &set, h->stream);
-    if (!r && hipMemcpyAsync(vec_out, vec, vb, hipMemcpyDeviceToHost, h->stream) != hipSuccess) r = MI355ENC_ERR_HIP;
-    if (hipStreamSynchronize(h->stream) != hipSuccess && !r) r = MI355ENC_ERR_HIP;
-    if (hy) (void)hipFree(hy);
-    if (vec) (void)hipFree(vec);
-    return r;
+    stage_tmp_t thy(h->stream), tvec(h->stream);
+    if (thy.alloc(2 * h->ysz) || tvec.alloc(vb)) return MI355ENC_ERR_HIP;
+    HIPCHK(hipMemcpyAsync(thy.p, hist_y, 2 * h->ysz, hipMemcpyHostToDevice, h->stream));
+    int r = denoise_run_search(h, s->d_src_y, thy.as<uint16_t>(), tvec.as<unsigned>(), &set, h->stream);
+    if (r) return r;
+    HIPCHK(hipMemcpyAsync(vec_out, tvec.p, vb, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MI355ENC_OK;
 }
 
 size_t mi355enc_debug_denoise_bytes(const mi355enc_t *h) { return h ? h->dn_bytes : 0; }

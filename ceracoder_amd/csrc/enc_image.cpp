@@ -190,23 +190,18 @@ int mi355enc_image_pixel(int matrix, int full_range, int r, int g, int b, uint8_
 int mi355enc_stage_image(mi355enc_t *h, const mi355enc_image_layer_t *layers, int n, uint8_t *y, uint8_t *uv) {
     if (!h || !y || !uv || n < 0 || n > MI355ENC_IMAGE_LAYERS || (n && !layers)) return MI355ENC_ERR_ARG;
     for (int l = 0; l < n; l++) if (layers[l].pixels && !layer_ok(&layers[l])) return MI355ENC_ERR_ARG;
-    if (h->pending) return MI355ENC_ERR_STATE;
+    { int r = stage_enter(h); if (r) return r; } // (its wait for every stream: the pool's buffers may have been read on the upload stream last)
     if (!h->csc_ok) return MI355ENC_ERR_ARG;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    { int r = sync_compute(h); if (r) return r; } // (the pool's buffers may have been read on the upload stream last)
     slot_t *s = &h->slot[0];
-    HIPCHK(hipMemcpyAsync(s->d_src_y, y, h->ysz, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(s->d_src_uv, uv, h->csz, hipMemcpyHostToDevice, h->stream));
     image_t *made[MI355ENC_IMAGE_LAYERS] = {nullptr, nullptr, nullptr, nullptr};
-    int r = MI355ENC_OK;
+    int r = stage_in(h, s, y, uv);
     for (int l = 0; l < n && !r; l++) {
         if (!layers[l].pixels) continue;
         made[l] = image_new(&layers[l]);
         r = made[l] ? image_blend(h, s, made[l], layers[l].x, layers[l].y, layers[l].opacity, h->stream) : MI355ENC_ERR_NOMEM;
     }
-    if (!r && (hipMemcpyAsync(y, s->d_src_y, h->ysz, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-               hipMemcpyAsync(uv, s->d_src_uv, h->csz, hipMemcpyDeviceToHost, h->stream) != hipSuccess)) r = MI355ENC_ERR_HIP;
-    if (hipStreamSynchronize(h->stream) != hipSuccess) r = MI355ENC_ERR_HIP;
+    if (!r) r = stage_out(h, s, y, uv);
+    if (r && hipStreamSynchronize(h->stream) != hipSuccess) r = MI355ENC_ERR_HIP;
     { std::lock_guard<std::mutex> lk(h->img_mu); for (int l = 0; l < n; l++) image_unref(made[l]); } // (everything that read them has completed)
     return r;
 }
@@ -214,8 +209,8 @@ int mi355enc_stage_image(mi355enc_t *h, const mi355enc_image_layer_t *layers, in
 } // extern "C"
 
 // mi355enc_time_stage 15: layer 0's image on the device (outside the timed loop), and the launch's arguments at its current place into slot 0's surfaces
-int image_time_prepare(mi355enc_t *h, image_args_t *a) {
-    slot_t *s = &h->slot[0];
+int image_time_prepare(mi355enc_t *h, slot_t *s, ts_ctx_t *ctx) {
+    image_args_t *a = &ctx->img;
     image_t *g;
     int x, y, op;
     {

@@ -123,20 +123,21 @@ int yv12_as_i420(int fmt, const uint8_t *p[3], int st[3]) {
     return MI355ENC_FMT_I420;
 }
 
-// Upload the planes of a picture of the input size tightly into the slot's raw staging buffer (rows at multiples of 16 bytes).
+// A picture's planes tightly in a raw staging buffer (rows at multiples of 16 bytes), one behind the other from d on.
+int raw_layout(int fmt, int w, int h, const uint8_t *d, const uint8_t *p[3], int st[3], fmt_plane_t pl[3]) {
+    const int n = fmt_planes(fmt, w, h, pl);
+    p[0] = p[1] = p[2] = nullptr; st[0] = st[1] = st[2] = 0;
+    for (int i = 0; i < n; i++) { st[i] = (pl[i].row + 15) & ~15; p[i] = d; d += (size_t)st[i] * pl[i].rows; }
+    return n;
+}
+// Upload the planes of a picture of the input size into the slot's raw staging buffer, laid out so.
 int upload_raw(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const planes[3], const int strides[3], hipStream_t up, const uint8_t *p[3], int st[3]) {
     fmt_plane_t pl[3];
     const int n = fmt_planes(fmt, h->in_w, h->in_h, pl);
     if (!planes || !strides || !n || !planes_fit(n, pl, planes, strides)) return MI355ENC_ERR_ARG; // (nothing is allocated for or transferred of a picture that is refused)
     if (!s->d_raw) HIPCHK(hipMalloc((void **)&s->d_raw, raw_bytes(h)));
-    p[1] = p[2] = nullptr; st[1] = st[2] = 0;
-    uint8_t *d = s->d_raw;
-    for (int i = 0; i < n; i++) {
-        const int row = (pl[i].row + 15) & ~15;
-        HIPCHK(hipMemcpy2DAsync(d, row, planes[i], strides[i], pl[i].row, pl[i].rows, hipMemcpyHostToDevice, up));
-        p[i] = d; st[i] = row;
-        d += (size_t)row * pl[i].rows;
-    }
+    raw_layout(fmt, h->in_w, h->in_h, s->d_raw, p, st, pl);
+    for (int i = 0; i < n; i++) HIPCHK(hipMemcpy2DAsync((void *)p[i], st[i], planes[i], strides[i], pl[i].row, pl[i].rows, hipMemcpyHostToDevice, up));
     return MI355ENC_OK;
 }
 
@@ -190,14 +191,6 @@ int upload_and_convert(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const p
     return input_finish(h, s, up);
 }
 
-// what the stage entry points of the input path return: the slot's source surfaces, once everything enqueued on the main stream is done
-int stage_out(mi355enc_t *h, slot_t *s, uint8_t *out_y, uint8_t *out_uv) {
-    HIPCHK(hipMemcpyAsync(out_y, s->d_src_y, h->ysz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(out_uv, s->d_src_uv, h->csz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MI355ENC_OK;
-}
-
 // one piece of a pageable source picture: into the pinned staging buffer, then on its way to the device
 static int stage_piece(mi355enc_t *h, const mi355enc::stage_job &j, hipStream_t up) {
     if (j.src_stride == (int)j.dst_stride) memcpy(j.dst, j.src, j.dst_stride * (size_t)(j.rows - 1) + (size_t)j.width);
@@ -229,8 +222,8 @@ void stage_helper(mi355enc_t *h) {
 extern "C" {
 
 int mi355enc_stage_csc(mi355enc_t *h, int fmt, const uint8_t *const planes[3], const int strides[3], uint8_t *out_y, uint8_t *out_uv) {
-    if (!h || !out_y || !out_uv || h->pending) return MI355ENC_ERR_ARG; // (with pictures in flight too: ERR_ARG, not the other stages' ERR_STATE)
-    HIPCHK(hipSetDevice(h->cfg.device_id));
+    if (!h || !out_y || !out_uv) return MI355ENC_ERR_ARG;
+    { int r = stage_enter(h); if (r) return r == MI355ENC_ERR_STATE ? MI355ENC_ERR_ARG : r; } // (with pictures in flight too: ERR_ARG, not the other stages' ERR_STATE)
     slot_t *s = &h->slot[0];
     int r = upload_and_convert(h, s, fmt, planes, strides, h->stream);
     return r ? r : stage_out(h, s, out_y, out_uv);

@@ -14,7 +14,11 @@
 //   enc_adjust.cpp    picture controls: setter, latch, the two launch forms and the scratch plane, its stage entry point
 //   enc_denoise.cpp   temporal noise reduction: setter, latch, the launch and the handle's history, its stage entry point
 //   enc_rate.cpp      frame-rate conversion: setter, the plan's step and commit per submit, keep buffer, mix / keep / repeat launches, its stage entry point
-//   enc_stages.cpp    single-stage entry points (parity tests, probes) and the host-only stages
+//   enc_hdr.cpp       HDR input: setter, the parameter block on the host and on the device, the tone-mapping conversion launch
+//   enc_quality.cpp   quality metrics: setter, the accumulator and result blocks, enqueue / collect, the stage launch
+//   enc_scale.cpp     input size and geometry: the one place both are decided, tables, the slots' plans, their stage entry points
+//   enc_stage.hpp     the frame of every single-stage entry point: stage_enter, stage_in / stage_out, a call's own device buffers (included at the end)
+//   enc_stages.cpp    single-stage entry points (parity tests, probes), mi355enc_time_stage and its table of stages, and the host-only stages
 #ifndef MI355_ENC_INTERNAL_HPP
 #define MI355_ENC_INTERNAL_HPP
 #include "../../include/mi355enc.h"
@@ -315,6 +319,8 @@ struct mi355enc {
     bool stg_stop, stg_on;
 };
 void stage_helper(mi355enc_t *h);
+// mi355enc_time_stage (enc_stages.cpp): what a stage's preparation hands to its launches (14: the scale plan, 15: the image arguments); the features' *_time_* hooks have the signatures of its table's rows
+struct ts_ctx_t { int stage; const scale_plan_t *scale; image_args_t img; };
 
 static inline double now_ms() {
     using namespace std::chrono;
@@ -359,7 +365,7 @@ static inline bool image_active(const slot_t *s) { for (int l = 0; l < MI355ENC_
 int image_draw(mi355enc_t *h, slot_t *s, hipStream_t st);   // the slot's layers into its source surfaces in index order, behind everything enqueued on st so far (an image not yet on the device goes there first); nothing with no layer
 void image_collected(mi355enc_t *h, slot_t *s);             // collect(): books what the picture carried as the last picture's and lets go of the slot's images
 void image_free(mi355enc_t *h);                             // close(): everything
-int image_time_prepare(mi355enc_t *h, image_args_t *a);     // mi355enc_time_stage 15: layer 0's image on the device, the launch's arguments at its current place; ERR_STATE without one
+int image_time_prepare(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // mi355enc_time_stage 15: layer 0's image on the device, the launch's arguments (x->img) at its current place; ERR_STATE without one
 // enc_scale.cpp
 // the one place the input geometry of a handle is decided (both setters end here): validates, then rebuilds tables, sizes, SAR and staging buffers; ERR_ARG leaves the handle as it was
 int geometry_apply(mi355enc_t *h, int orient, bool in_set, int in_w, int in_h, const mi355enc_geometry_t *geom = nullptr); // geom: the geometry in place of an input size
@@ -390,21 +396,22 @@ int yv12_as_i420(int fmt, const uint8_t *p[3], int st[3]); // YV12 is I420 with 
 struct nv12_pic_t { uint8_t *y, *uv; int stride; };
 int input_nv12(mi355enc_t *h, slot_t *s, nv12_pic_t *c);
 int scale_nv12(const nv12_pic_t *c, const in_target_t *t, const scale_plan_t *pl, hipStream_t up);
-int stage_out(mi355enc_t *h, slot_t *s, uint8_t *out_y, uint8_t *out_uv); // the slot's source surfaces to the host, behind everything on the main stream, waited for
+// the planes' layout at rows of 16 n bytes, one behind the other from d on (a slot's raw staging buffer): where each lies and its stride -> the number of planes
+int raw_layout(int fmt, int w, int h, const uint8_t *d, const uint8_t *p[3], int st[3], fmt_plane_t pl[3]);
 #pragma GCC visibility pop
 // enc_jpeg.cpp
 int jpeg_alloc(mi355enc_t *h, slot_t *s);  // the slot's coefficient buffers (idempotent)
 void jpeg_free(slot_t *s);
 int jpeg_decode_host(mi355enc_t *h, slot_t *s, const uint8_t *data, size_t len, mi355enc_jpeg_info_t *info); // parse, check the size, entropy decode into the slot's pinned buffer
 int jpeg_enqueue(mi355enc_t *h, slot_t *s, const mi355enc_jpeg_info_t *info, hipStream_t up);               // transfer + launch (+ scale) into the slot's staging surfaces
-int jpeg_time_launch(mi355enc_t *h, slot_t *s);
+int jpeg_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x);
 // enc_snapshot.cpp
 void snapshot_latch(mi355enc_t *h, slot_t *s);  // enqueue_picture of a newly submitted picture: an armed request becomes the slot's, with a block to land in
 // the slot's still from NV12 planes (the source, or the reconstruction) behind everything enqueued on st so far; records the slot's event
 int snapshot_enqueue(mi355enc_t *h, slot_t *s, const uint8_t *y, const uint8_t *uv, int stride, hipStream_t st);
 int snapshot_collect(mi355enc_t *h, slot_t *s); // waits for the slot's still and makes it the ready one
-int snapshot_time_prepare(mi355enc_t *h);       // mi355enc_time_stage 16: the stage block and its tables
-int snapshot_time_launch(mi355enc_t *h, slot_t *s);
+int snapshot_time_prepare(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // mi355enc_time_stage 16: the stage block and its tables
+int snapshot_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x);
 void snapshot_init(mi355enc_t *h);
 void snapshot_free(mi355enc_t *h);
 // enc_csc.cpp
@@ -420,15 +427,15 @@ void adjust_retable(mi355enc_t *h);                          // mi355enc_set_col
 int adjust_draw(mi355enc_t *h, slot_t *s, hipStream_t st);   // the slot's adjustment on its coded surfaces, behind everything enqueued on st so far; nothing with none
 void adjust_collected(mi355enc_t *h, slot_t *s);             // collect(): books what the picture carried as the last picture's
 void adjust_free(mi355enc_t *h);
-bool adjust_time_ready(mi355enc_t *h, bool stencil);         // mi355enc_time_stage 23 / 24: the value set last is active and of that form
-int adjust_time_launch(mi355enc_t *h, slot_t *s);            // ... and its launches on the main stream
+bool adjust_time_ready(mi355enc_t *h, int stage);            // mi355enc_time_stage 23 / 24: the value set last is active and of that form (24: the stencil form)
+int adjust_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // ... and its launches on the main stream
 // enc_denoise.cpp (temporal noise reduction)
 void denoise_latch(mi355enc_t *h, slot_t *s, bool tables);   // the value set last becomes the slot's (beside adjust_latch); tables: with its tables (the slot the step runs on)
 int denoise_draw(mi355enc_t *h, slot_t *s, hipStream_t st);  // the slot's filter on its coded surfaces and the handle's history, behind everything enqueued on st so far; nothing with none
 void denoise_collected(mi355enc_t *h, slot_t *s);            // collect(): books what the picture carried as the last picture's
 void denoise_free(mi355enc_t *h);
 bool denoise_time_ready(mi355enc_t *h, int stage);           // mi355enc_time_stage 25 .. 28: the value set last is active (27 / 28: with a range above 0)
-int denoise_time_launch(mi355enc_t *h, slot_t *s, int stage); // ... and its launch on the main stream: 25 filtering in place (priming where the history is not valid), 26 priming, 27 the search alone, 28 search and compensated filter
+int denoise_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // ... and its launch on the main stream: 25 filtering in place (priming where the history is not valid), 26 priming, 27 the search alone, 28 search and compensated filter
 void denoise_time_done(mi355enc_t *h);                       // ... behind the timed launches: the history they left is no stream's, the next picture primes
 // enc_hdr.cpp (HDR input)
 // true: the handle tone-maps and this input is not one it takes (a format other than the three 10-bit ones -- fmt -1: an entry point that takes none of them --
@@ -449,4 +456,5 @@ int rate_mix(mi355enc_t *h, slot_t *b, slot_t *out, int w256, bool keep, hipStre
 void rate_commit(mi355enc_t *h, int force_idr);                                // ingest_end: the step's pictures are enqueued (or it yields none): plan and statistics advance
 void rate_free(mi355enc_t *h);
 #pragma GCC visibility pop
+#include "enc_stage.hpp"
 #endif

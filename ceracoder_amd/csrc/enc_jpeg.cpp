@@ -73,7 +73,7 @@ int jpeg_enqueue(mi355enc_t *h, slot_t *s, const mi355enc_jpeg_info_t *info, hip
 }
 
 // the launch alone for mi355enc_time_stage: the coded size as 4:2:2, on whatever slot 0's coefficient buffer holds
-int jpeg_time_launch(mi355enc_t *h, slot_t *s) {
+int jpeg_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *) {
     in_target_t t;
     int r = input_target(h, s, &t);
     if (r) return r;
@@ -85,8 +85,7 @@ extern "C" {
 
 int mi355enc_stage_jpeg(mi355enc_t *h, const uint8_t *data, size_t len, uint8_t *out_y, uint8_t *out_uv) {
     if (!h || !data || !out_y || !out_uv) return MI355ENC_ERR_ARG;
-    if (h->pending) return MI355ENC_ERR_STATE;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
+    { int r = stage_enter(h); if (r) return r; }
     slot_t *s = &h->slot[0];
     mi355enc_jpeg_info_t info;
     int r = jpeg_decode_host(h, s, data, len, &info);
@@ -97,8 +96,7 @@ int mi355enc_stage_jpeg(mi355enc_t *h, const uint8_t *data, size_t len, uint8_t 
 int mi355enc_stage_jpeg_blocks(mi355enc_t *h, int hs, int vs, int components, const int16_t *coef, const uint16_t qt[3][64], uint8_t *out_y, uint8_t *out_uv) {
     if (!h || !coef || !qt || !out_y || !out_uv) return MI355ENC_ERR_ARG;
     if (!((components == 1 && hs == 1 && vs == 1) || (components == 3 && (hs == 1 || hs == 2) && (vs == 1 || (vs == 2 && hs == 2))))) return MI355ENC_ERR_ARG;
-    if (h->pending) return MI355ENC_ERR_STATE;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
+    { int r = stage_enter(h); if (r) return r; }
     slot_t *s = &h->slot[0];
     const mi355enc_jpeg_info_t info = {h->in_w, h->in_h, components, hs, vs, 0, 0};
     int r = jpeg_check(h, &info);

@@ -77,29 +77,23 @@ static int stage_sizes(const mi355enc_t *h, int method, int *pw, int *ph) {
 int mi355enc_stage_orient(mi355enc_t *h, int method, const uint8_t *y, int y_stride, const uint8_t *uv, int uv_stride, uint8_t *out_y, uint8_t *out_uv) {
     int pw, ph;
     if (!h || !y || !uv || !out_y || !out_uv || stage_sizes(h, method, &pw, &ph) || y_stride < pw || uv_stride < pw) return MI355ENC_ERR_ARG;
-    if (h->pending) return MI355ENC_ERR_STATE;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
+    { int r = stage_enter(h); if (r) return r; }
     slot_t *s = &h->slot[0];
     const int ps = (pw + 15) & ~15;
-    uint8_t *d = nullptr; // (a buffer of its own: the handle's pre-orientation picture has the size of the handle's method)
-    HIPCHK(hipMalloc((void **)&d, (size_t)ps * ph * 3 / 2 + SURF_PAD));
-    int r = MI355ENC_ERR_HIP;
-    if (hipMemcpy2DAsync(d, ps, y, y_stride, pw, ph, hipMemcpyHostToDevice, h->stream) == hipSuccess &&
-        hipMemcpy2DAsync(d + (size_t)ps * ph, ps, uv, uv_stride, pw, ph / 2, hipMemcpyHostToDevice, h->stream) == hipSuccess) {
-        r = k_launch_orient(method, d, ps, d + (size_t)ps * ph, ps, pw, ph, s->d_src_y, s->d_src_uv, h->W, h->H, h->stream) ? MI355ENC_ERR_ARG : MI355ENC_OK;
-        if (!r && hipGetLastError() != hipSuccess) r = MI355ENC_ERR_HIP;
-        if (!r) r = stage_out(h, s, out_y, out_uv); // (waits for the stream)
-    }
-    if (r && hipStreamSynchronize(h->stream) != hipSuccess) r = MI355ENC_ERR_HIP; // the temporary is freed behind everything that reads it, on every path
-    (void)hipFree(d);
-    return r;
+    stage_tmp_t tmp(h->stream); // (a buffer of its own: the handle's pre-orientation picture has the size of the handle's method)
+    if (tmp.alloc((size_t)ps * ph * 3 / 2 + SURF_PAD)) return MI355ENC_ERR_HIP;
+    uint8_t *d = tmp.as<uint8_t>();
+    HIPCHK(hipMemcpy2DAsync(d, ps, y, y_stride, pw, ph, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpy2DAsync(d + (size_t)ps * ph, ps, uv, uv_stride, pw, ph / 2, hipMemcpyHostToDevice, h->stream));
+    if (k_launch_orient(method, d, ps, d + (size_t)ps * ph, ps, pw, ph, s->d_src_y, s->d_src_uv, h->W, h->H, h->stream)) return MI355ENC_ERR_ARG;
+    HIPCHK(hipGetLastError());
+    return stage_out(h, s, out_y, out_uv);
 }
 
 int mi355enc_stage_orient_device(mi355enc_t *h, int method, const void *d_y, int y_stride, const void *d_uv, int uv_stride, void *d_out_y, void *d_out_uv) {
     int pw, ph;
     if (!h || !d_y || !d_uv || !d_out_y || !d_out_uv || stage_sizes(h, method, &pw, &ph) || y_stride < pw || uv_stride < pw) return MI355ENC_ERR_ARG;
-    if (h->pending) return MI355ENC_ERR_STATE;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
+    { int r = stage_enter(h); if (r) return r; }
     if (k_launch_orient(method, (const uint8_t *)d_y, y_stride, (const uint8_t *)d_uv, uv_stride, pw, ph, (uint8_t *)d_out_y, (uint8_t *)d_out_uv, h->W, h->H, h->stream)) return MI355ENC_ERR_ARG;
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));

@@ -43,15 +43,16 @@ void overlay_latch(mi355enc_t *h, slot_t *s) {
     if (h->ov_len) { memcpy(s->ov_text, h->ov_text, (size_t)h->ov_len); s->ov_style = h->ov_style; }
 }
 
-int overlay_draw(mi355enc_t *h, slot_t *s, hipStream_t st) {
-    if (!s->ov_len) return MI355ENC_OK;
+// layout and launch: `len` bytes of text into the slot's source surfaces; nothing with no text, or with none of its box visible
+static int overlay_run(mi355enc_t *h, slot_t *s, const char *text, int len, const mi355enc_overlay_style_t &sty, hipStream_t st) {
     overlay_args_t a;
-    if (!overlay_layout(s->ov_text, s->ov_len, s->ov_style, h->cfg.width, h->cfg.height, h->W, h->H, &a)) return MI355ENC_OK;
+    if (!len || !overlay_layout(text, len, sty, h->cfg.width, h->cfg.height, h->W, h->H, &a)) return MI355ENC_OK;
     a.y = s->d_src_y; a.uv = s->d_src_uv; a.stride = h->W;
     k_launch_overlay(&a, st);
     HIPCHK(hipGetLastError());
     return MI355ENC_OK;
 }
+int overlay_draw(mi355enc_t *h, slot_t *s, hipStream_t st) { return overlay_run(h, s, s->ov_text, s->ov_len, s->ov_style, st); }
 
 extern "C" {
 
@@ -98,22 +99,11 @@ int mi355enc_stage_overlay(mi355enc_t *h, const char *text, const mi355enc_overl
     mi355enc_overlay_style_t sty;
     mi355enc_overlay_default_style(&sty);
     if (st) { if (!style_ok(st)) return MI355ENC_ERR_ARG; sty = *st; }
-    if (h->pending) return MI355ENC_ERR_STATE;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
     slot_t *s = &h->slot[0];
-    HIPCHK(hipMemcpyAsync(s->d_src_y, y, h->ysz, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(s->d_src_uv, uv, h->csz, hipMemcpyHostToDevice, h->stream));
-    const int len = text ? (int)strnlen(text, MI355ENC_OVERLAY_MAX_TEXT) : 0;
-    overlay_args_t a;
-    if (len && overlay_layout(text, len, sty, h->cfg.width, h->cfg.height, h->W, h->H, &a)) {
-        a.y = s->d_src_y; a.uv = s->d_src_uv; a.stride = h->W;
-        k_launch_overlay(&a, h->stream);
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipMemcpyAsync(y, s->d_src_y, h->ysz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(uv, s->d_src_uv, h->csz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MI355ENC_OK;
+    int r = stage_enter(h);
+    if (!r) r = stage_in(h, s, y, uv);
+    if (!r) r = overlay_run(h, s, text, text ? (int)strnlen(text, MI355ENC_OVERLAY_MAX_TEXT) : 0, sty, h->stream);
+    return r ? r : stage_out(h, s, y, uv);
 }
 
 } // extern "C"

@@ -103,14 +103,11 @@ size_t mi355enc_debug_rate_bytes(const mi355enc_t *h) { return h && h->d_keep ? 
 // slot 1 while b goes where a was.
 int mi355enc_stage_rate(mi355enc_t *h, int w256, const uint8_t *a_y, const uint8_t *a_uv, const uint8_t *b_y, const uint8_t *b_uv, uint8_t *out_y, uint8_t *out_uv) {
     if (!h || !a_y || !a_uv || !b_y || !b_uv || !out_y || !out_uv || w256 < 0 || w256 > 256) return MI355ENC_ERR_ARG;
-    if (h->pending) return MI355ENC_ERR_STATE;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    { int r = sync_compute(h); if (r) return r; }
     slot_t *sa = &h->slot[0], *sb = &h->slot[1];
-    HIPCHK(hipMemcpyAsync(sa->d_src_y, a_y, h->ysz, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(sa->d_src_uv, a_uv, h->csz, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(sb->d_src_y, b_y, h->ysz, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(sb->d_src_uv, b_uv, h->csz, hipMemcpyHostToDevice, h->stream));
+    int r = stage_enter(h);
+    if (!r) r = stage_in(h, sa, a_y, a_uv);
+    if (!r) r = stage_in(h, sb, b_y, b_uv);
+    if (r) return r;
     if (k_launch_rate_mix(sa->d_src_y, sa->d_src_uv, sb->d_src_y, sb->d_src_uv, sb->d_src_y, sb->d_src_uv, sa->d_src_y, sa->d_src_uv, h->W, h->H, w256, h->stream))
         return MI355ENC_ERR_ARG;
     HIPCHK(hipGetLastError());

@@ -431,9 +431,8 @@ int mi355enc_stage_geometry(mi355enc_t *h, int fmt, const uint8_t *const planes[
 
 int mi355enc_stage_scale(mi355enc_t *h, int fmt, const uint8_t *const planes[3], const int strides[3], uint8_t *out_y, uint8_t *out_uv) {
     if (!h || !out_y || !out_uv) return MI355ENC_ERR_ARG;
-    if (h->pending) return MI355ENC_ERR_STATE;
+    { int r = stage_enter(h); if (r) return r; }
     if (!h->d_scale_tab) return MI355ENC_ERR_STATE; // (mi355enc_set_input_size first)
-    HIPCHK(hipSetDevice(h->cfg.device_id));
     slot_t *s = &h->slot[0];
     const uint8_t *p[3];
     int st[3];

@@ -103,13 +103,13 @@ int snapshot_collect(mi355enc_t *h, slot_t *s) {
 }
 
 // (the table travels here, once, not inside the timed loop: stage 16 times the kernel alone, like the stages beside it)
-int snapshot_time_prepare(mi355enc_t *h) {
+int snapshot_time_prepare(mi355enc_t *h, slot_t *, ts_ctx_t *) {
     snap_block_t *b = &h->snap_blk[SNAP_BLOCKS - 1];
     int r = block_prepare(h, b, h->cfg.width, h->cfg.height, h->snap_last_req.reduce, h->snap_last_req.quality, 1, 1);
     if (!r) r = block_table(b, h->stream);
     return r;
 }
-int snapshot_time_launch(mi355enc_t *h, slot_t *s) {
+int snapshot_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *) {
     return block_launch(&h->snap_blk[SNAP_BLOCKS - 1], s->d_src_y, h->W, s->d_src_uv, h->W, h->cfg.width, h->cfg.height, h->snap_last_req.reduce, h->stream);
 }
 
@@ -127,14 +127,12 @@ static int stage_run(mi355enc_t *h, const uint8_t *d_y, int ys, const uint8_t *d
 static bool stage_args_ok(const void *y, int ys, const void *uv, int uvs, int w, int ht, int reduce, int quality) {
     return y && uv && w >= 2 && ht >= 2 && !((w | ht) & 1) && w <= 16384 && ht <= 16384 && ys >= w && uvs >= w && log2_reduce(reduce) >= 0 && quality >= 1 && quality <= 100;
 }
-// host planes -> temporary device planes of stride (w + 15) & ~15
-static int stage_upload(mi355enc_t *h, const uint8_t *y, int ys, const uint8_t *uv, int uvs, int w, int ht, uint8_t **d_out, int *stride) {
-    const int st = (w + 15) & ~15;
-    uint8_t *d = nullptr;
-    HIPCHK(hipMalloc((void **)&d, (size_t)st * ht * 3 / 2));
-    *d_out = d; *stride = st;
-    HIPCHK(hipMemcpy2DAsync(d, st, y, ys, w, ht, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpy2DAsync(d + (size_t)st * ht, st, uv, uvs, w, ht / 2, hipMemcpyHostToDevice, h->stream));
+// host planes -> the call's own device planes of stride (w + 15) & ~15: luma, the chroma behind it
+static int stage_upload(mi355enc_t *h, const uint8_t *y, int ys, const uint8_t *uv, int uvs, int w, int ht, stage_tmp_t *tmp, int *stride) {
+    const int st = *stride = (w + 15) & ~15;
+    if (tmp->alloc((size_t)st * ht * 3 / 2)) return MI355ENC_ERR_HIP;
+    HIPCHK(hipMemcpy2DAsync(tmp->p, st, y, ys, w, ht, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpy2DAsync(tmp->as<uint8_t>() + (size_t)st * ht, st, uv, uvs, w, ht / 2, hipMemcpyHostToDevice, h->stream));
     return MI355ENC_OK;
 }
 
@@ -184,26 +182,24 @@ int mi355enc_stage_snapshot_blocks(mi355enc_t *h, const uint8_t *y, int y_stride
                                    int16_t *levels, uint16_t qt[2][64]) {
     if (!h || !levels || !qt || !stage_args_ok(y, y_stride, uv, uv_stride, w, ht, reduce, quality)) return MI355ENC_ERR_ARG;
     HIPCHK(hipSetDevice(h->cfg.device_id));
-    uint8_t *d = nullptr;
+    stage_tmp_t tmp(h->stream);
     int st = 0;
-    int r = stage_upload(h, y, y_stride, uv, uv_stride, w, ht, &d, &st);
-    if (!r) r = mi355enc_stage_snapshot_blocks_device(h, d, st, d + (size_t)st * ht, st, w, ht, reduce, quality, levels, qt);
-    if (d) { (void)hipStreamSynchronize(h->stream); (void)hipFree(d); }
-    return r;
+    int r = stage_upload(h, y, y_stride, uv, uv_stride, w, ht, &tmp, &st);
+    const uint8_t *d = tmp.as<uint8_t>();
+    return r ? r : mi355enc_stage_snapshot_blocks_device(h, d, st, d + (size_t)st * ht, st, w, ht, reduce, quality, levels, qt);
 }
 
 int mi355enc_stage_snapshot(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t *uv, int uv_stride, int w, int ht, int reduce, int quality,
                             uint8_t *out, size_t cap, size_t *len) {
     if (!h || !len || (!out && cap) || !stage_args_ok(y, y_stride, uv, uv_stride, w, ht, reduce, quality)) return MI355ENC_ERR_ARG;
     HIPCHK(hipSetDevice(h->cfg.device_id));
-    uint8_t *d = nullptr;
+    stage_tmp_t tmp(h->stream);
     int st = 0;
     snap_block_t *b = nullptr;
-    int r = stage_upload(h, y, y_stride, uv, uv_stride, w, ht, &d, &st);
+    int r = stage_upload(h, y, y_stride, uv, uv_stride, w, ht, &tmp, &st);
+    const uint8_t *d = tmp.as<uint8_t>();
     if (!r) r = stage_run(h, d, st, d + (size_t)st * ht, st, w, ht, reduce, quality, &b);
-    if (d) { (void)hipStreamSynchronize(h->stream); (void)hipFree(d); }
-    if (r) return r;
-    return snapshot_host_write(blk_levels(b), blk_hint(b), b->qt, b->ow, b->oh, out, cap, len);
+    return r ? r : snapshot_host_write(blk_levels(b), blk_hint(b), b->qt, b->ow, b->oh, out, cap, len);
 }
 
 } // extern "C"

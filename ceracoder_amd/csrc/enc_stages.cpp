@@ -1,27 +1,23 @@
 // enc_stages.cpp -- single-stage entry points of the C ABI (the same kernels the encoder launches, one stage at a time: parity
-// tests and probes) and the host-only stages (parameter sets, slice writer, rate-control model: no device needed).
+// tests and probes), mi355enc_time_stage and its table of stages, and the host-only stages (parameter sets, slice writer, rate-control model: no device needed).
+// Every device entry point runs in the frame of enc_stage.hpp.
 #include "enc_internal.hpp"
 
-// A single-stage call made with pictures in flight would overwrite what they use: refused BEFORE anything is uploaded (the caller collects first).
-#define STAGE_IDLE(h) do { if ((h)->pending) return MI355ENC_ERR_STATE; } while (0)
-
-extern "C" {
+#include <utility>
 
 // ---------------------------------------------------------------- single-stage entry points
 // A single-stage call overwrites the reconstruction buffers, the previous-source planes and the record sets behind the encoder's back: the
 // next picture submitted through the pipeline must not predict from any of it, so it is coded as an IDR picture and nothing of the
 // previous picture's on-device progress words is trusted.
 static void stage_touched(mi355enc_t *h) { h->have_ref = 0; h->words.forget(); h->dbI_busy[0] = h->dbI_busy[1] = 0; }
+// slot 0's context for a single-stage call, on the host and on the device (behind stage_enter)
 static int stage_ctx(mi355enc_t *h, int qp, bool src_is_staging, int drop = 0, int idr = 0) {
-    if (h->pending) return MI355ENC_ERR_STATE;
     // slice-local deblocking: a band of the deblocker never spans two slices (mi355enc_dev.h); the two settings are made separately, so the pair is checked here
     if (h->stage_slice_dbf == 2 && h->stage_slice_rows % MI355_BAND_ROWS != 0) return MI355ENC_ERR_ARG;
     slot_t *s = &h->slot[0];
     frame_ctx_t *c = s->h_ctx;
     c->src_y = src_is_staging ? s->d_src_y : nullptr; c->src_uv = src_is_staging ? s->d_src_uv : nullptr; c->src_stride = h->W;
     c->ref_y = h->d_rec_y[0]; c->ref_uv = h->d_rec_uv[0]; c->rec_y = h->d_rec_y[1]; c->rec_uv = h->d_rec_uv[1];
-    HIPCHK(hipStreamSynchronize(h->cstream));
-    { int r = sync_compute(h); if (r) return r; }
     c->vis_h = h->H;
     fill_ctx(h, c, qp, drop, idr);
     c->slice_rows = h->stage_slice_rows; c->slice_dbf = h->stage_slice_dbf;
@@ -31,68 +27,10 @@ static int stage_ctx(mi355enc_t *h, int qp, bool src_is_staging, int drop = 0, i
     stage_touched(h);
     return 0;
 }
-static int upload_luma_pair(mi355enc_t *h, const uint8_t *cur_y, const uint8_t *ref_y) {
-    HIPCHK(hipMemcpyAsync(h->slot[0].d_src_y, cur_y, h->ysz, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_rec_y[0], ref_y, h->ysz, hipMemcpyHostToDevice, h->stream));
-    return 0;
-}
-int mi355enc_stage_me(mi355enc_t *h, const uint8_t *cur_y, const uint8_t *ref_y, int qp, uint16_t *surf_out, void *imv_out) {
-    if (!h || !cur_y || !ref_y || !imv_out || qp < 0 || qp > 51) return MI355ENC_ERR_ARG;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    STAGE_IDLE(h);
-    HIPCHK(hipMemcpyAsync(h->slot[0].d_src_y, cur_y, h->ysz, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_psrc[h->psrc_cur], ref_y, h->ysz, hipMemcpyHostToDevice, h->stream)); // what the search runs against (in the encoder: the previous source)
-    int r = stage_ctx(h, qp, true); if (r) return r;
-    k_launch_me(h->slot[0].h_ctx, h->mbw, h->stream);
-    HIPCHK(hipMemcpyAsync(imv_out, h->d_imv[0][0], (size_t)h->nmb * sizeof(imv_t), hipMemcpyDeviceToHost, h->stream));
-    if (surf_out) HIPCHK(hipMemcpyAsync(surf_out, h->d_surf[0], (size_t)h->nmb * SURF_U16 * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MI355ENC_OK;
-}
-int mi355enc_stage_me_select(mi355enc_t *h, const uint16_t *surf, const void *imv_in, int qp, void *imv_out) {
-    if (!h || !surf || !imv_in || !imv_out || qp < 0 || qp > 51) return MI355ENC_ERR_ARG;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    STAGE_IDLE(h);
-    int r = stage_ctx(h, qp, true); if (r) return r;
-    HIPCHK(hipMemcpyAsync(h->d_surf[0], surf, (size_t)h->nmb * SURF_U16 * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_imv[0][0], imv_in, (size_t)h->nmb * sizeof(imv_t), hipMemcpyHostToDevice, h->stream));
-    k_launch_me_select(h->slot[0].h_ctx, h->mbw, h->d_imv[0][0], h->d_imv[0][1], nullptr, 0, h->stream);
-    HIPCHK(hipMemcpyAsync(imv_out, h->d_imv[0][1], (size_t)h->nmb * sizeof(imv_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MI355ENC_OK;
-}
-// ... and the form the encoder's later iterations use (me_select_sparse_kernel): imv_prev is the field imv_in was selected from -- a macroblock whose predictors are
-// the same in both copies its entry of imv_in.  Must equal mi355enc_stage_me_select(surf, imv_in) whenever imv_in really is the selection over imv_prev.
-int mi355enc_stage_me_select_next(mi355enc_t *h, const uint16_t *surf, const void *imv_in, const void *imv_prev, int qp, void *imv_out) {
-    if (!h || !surf || !imv_in || !imv_prev || !imv_out || qp < 0 || qp > 51) return MI355ENC_ERR_ARG;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    STAGE_IDLE(h);
-    int r = stage_ctx(h, qp, true); if (r) return r;
-    HIPCHK(hipMemcpyAsync(h->d_surf[0], surf, (size_t)h->nmb * SURF_U16 * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_imv[0][0], imv_in, (size_t)h->nmb * sizeof(imv_t), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_imv[0][2], imv_prev, (size_t)h->nmb * sizeof(imv_t), hipMemcpyHostToDevice, h->stream));
-    k_launch_me_select(h->slot[0].h_ctx, h->mbw, h->d_imv[0][0], h->d_imv[0][1], h->d_imv[0][2], 2, h->stream);
-    HIPCHK(hipMemcpyAsync(imv_out, h->d_imv[0][1], (size_t)h->nmb * sizeof(imv_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MI355ENC_OK;
-}
-int mi355enc_stage_subpel(mi355enc_t *h, const uint8_t *cur_y, const uint8_t *ref_y, int qp, void *mbinfo_inout) {
-    if (!h || !cur_y || !ref_y || !mbinfo_inout || qp < 0 || qp > 51) return MI355ENC_ERR_ARG;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    STAGE_IDLE(h);
-    int r = upload_luma_pair(h, cur_y, ref_y); if (r) return r;
-    HIPCHK(hipMemcpyAsync(h->d_mbi, mbinfo_inout, (size_t)h->nmb * sizeof(mb_info_t), hipMemcpyHostToDevice, h->stream));
-    r = stage_ctx(h, qp, true); if (r) return r;
-    k_launch_subpel(h->slot[0].h_ctx, h->mbw, h->stream);
-    HIPCHK(hipMemcpyAsync(mbinfo_inout, h->d_mbi, (size_t)h->nmb * sizeof(mb_info_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MI355ENC_OK;
-}
-static int upload_planes4(mi355enc_t *h, const uint8_t *src_y, const uint8_t *src_uv, const uint8_t *ref_y, const uint8_t *ref_uv) {
-    HIPCHK(hipMemcpyAsync(h->slot[0].d_src_y, src_y, h->ysz, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->slot[0].d_src_uv, src_uv, h->csz, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_rec_y[0], ref_y, h->ysz, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_rec_uv[0], ref_uv, h->csz, hipMemcpyHostToDevice, h->stream));
+// host planes of the coded size -> a reconstruction buffer (0: what a P stage predicts from, 1: what a stage reconstructs into)
+static int upload_rec(mi355enc_t *h, int i, const uint8_t *y, const uint8_t *uv) {
+    HIPCHK(hipMemcpyAsync(h->d_rec_y[i], y, h->ysz, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_rec_uv[i], uv, h->csz, hipMemcpyHostToDevice, h->stream));
     return 0;
 }
 static int download_picture(mi355enc_t *h, void *mbinfo, uint8_t *rec_y, uint8_t *rec_uv, int16_t *levels) {
@@ -103,13 +41,160 @@ static int download_picture(mi355enc_t *h, void *mbinfo, uint8_t *rec_y, uint8_t
     HIPCHK(hipStreamSynchronize(h->stream));
     return 0;
 }
+
+// ---------------------------------------------------------------- the timed stages: one row per stage of mi355enc_time_stage (the numbers are the ABI's)
+enum {
+    TS_ME = 0, TS_INTER, TS_INTRA, TS_DEBLOCK, TS_SUBPEL, TS_CSC_I420, TS_CSC_YUY2, TS_CSC_UYVY, TS_ME_SELECT, TS_PMB, TS_INTRA_P, TS_QUALITY, TS_JPEG, TS_ORIENT, TS_SCALE,
+    TS_IMAGE, TS_SNAPSHOT, TS_YUV_CONVERT, TS_RATE, TS_HDR_P010, TS_HDR_I420_10, TS_HDR_V210, TS_DEEP_P010, TS_ADJUST_POINT, TS_ADJUST_SHARPEN, TS_DENOISE,
+    TS_DENOISE_PRIME, TS_DENOISE_SEARCH, TS_DENOISE_MC, TS_COUNT
+};
+// ready: the precondition (false: MI355ENC_ERR_STATE); prepare: once, outside the timed loop; launch: the body of the loop; done: behind the timed loop;
+// needs_raw: slot 0's raw staging buffer must exist (any bytes will do as a source: 0x55).  Null: nothing.
+struct ts_row_t {
+    int stage;
+    bool (*ready)(mi355enc_t *h, int stage);
+    int (*prepare)(mi355enc_t *h, slot_t *s, ts_ctx_t *x);
+    int (*launch)(mi355enc_t *h, slot_t *s, ts_ctx_t *x);
+    void (*done)(mi355enc_t *h);
+    bool needs_raw;
+};
+static bool ts_has_scale(mi355enc_t *h, int) { return h->d_scale_tab != nullptr; } // (mi355enc_set_input_size or mi355enc_set_input_geometry first)
+static bool ts_has_yuv(mi355enc_t *h, int) { return h->yuv_on; }                   // (the handle has no conversion)
+static bool ts_has_keep(mi355enc_t *h, int) { return h->d_keep != nullptr; }       // (frame-rate conversion off, or hold mode without a keep buffer: there is no mix)
+static bool ts_has_hdr(mi355enc_t *h, int) { return h->hdr_on && !hdr_refuses(h, MI355ENC_FMT_P010); } // (mi355enc_set_hdr_input first, and an output matrix it converts to)
+static int ts_me(mi355enc_t *h, slot_t *s, ts_ctx_t *) { k_launch_me(s->h_ctx, h->mbw, h->stream); return 0; }
+static int ts_inter(mi355enc_t *h, slot_t *s, ts_ctx_t *) { k_launch_inter(s->h_ctx, h->mbw, h->stream); return 0; }
+static int ts_subpel(mi355enc_t *h, slot_t *s, ts_ctx_t *) { k_launch_subpel(s->h_ctx, h->mbw, h->stream); return 0; }
+static int ts_me_select(mi355enc_t *h, slot_t *s, ts_ctx_t *) { k_launch_me_select(s->h_ctx, h->mbw, h->d_imv[0][0], h->d_imv[0][1], nullptr, 0, h->stream); return 0; }
+static int ts_pmb(mi355enc_t *h, slot_t *s, ts_ctx_t *) { return run_pmb(h, s->h_ctx, 1, pic_plan_t(), h->stream); }
+// a fresh stamp per launch: the lines / strips between bands are epoch-tagged
+static void ts_stamp(mi355enc_t *h, slot_t *s) { if (++h->epoch == 0) h->epoch = 1; s->h_ctx->epoch = h->epoch; }
+static int ts_intra(mi355enc_t *h, slot_t *s, ts_ctx_t *) { ts_stamp(h, s); return run_intra(h, 0, s->h_ctx); }
+static int ts_deblock(mi355enc_t *h, slot_t *s, ts_ctx_t *) { ts_stamp(h, s); return run_deblock(h, 0, s->h_ctx); }
+static int ts_intra_p_prepare(mi355enc_t *h, slot_t *s, ts_ctx_t *) { return h->words.ip_rows_stamp(s->h_ctx->epoch, h->stream); }
+static int ts_intra_p(mi355enc_t *h, slot_t *s, ts_ctx_t *) { k_launch_intra_p(s->h_ctx, h->mbw, h->mbh, h->words.ip_progress(), h->d_ip_strips, h->words.err(), h->stream); return 0; }
+static int ts_quality_prepare(mi355enc_t *h, slot_t *, ts_ctx_t *) { return quality_alloc(h); } // (the block of the stage entry points)
+static int ts_quality(mi355enc_t *h, slot_t *s, ts_ctx_t *) {
+    unsigned long long *acc = h->d_qacc + (size_t)NSLOT * QUALITY_ACC_WORDS, *res = h->h_qres + (size_t)NSLOT * QUALITY_WORDS;
+    k_launch_quality(s->d_src_y, s->d_src_uv, h->W, h->d_rec_y[1], h->d_rec_uv[1], h->W, h->cfg.width, h->cfg.height, acc, res, h->stream); return 0;
+}
+static int ts_jpeg_prepare(mi355enc_t *h, slot_t *s, ts_ctx_t *) { return jpeg_alloc(h, s); }
+// the conversion launch of a picture of the coded visible size in the raw staging buffer: 5 I420, 6 YUY2, 7 UYVY; 19 P010, 20 I420_10, 21 V210 tone-mapped
+// (DESIGN.md section 22); 22 P010 plain (section 20)
+static int ts_convert(mi355enc_t *h, slot_t *s, ts_ctx_t *x) {
+    const int t = x->stage, fmt = t <= TS_CSC_UYVY ? MI355ENC_FMT_I420 + t - TS_CSC_I420 : t == TS_DEEP_P010 ? MI355ENC_FMT_P010 : MI355ENC_FMT_P010 + t - TS_HDR_P010;
+    const int w = h->cfg.width, ht = h->cfg.height;
+    fmt_plane_t pl[3];
+    const uint8_t *p[3];
+    int st[3];
+    raw_layout(fmt, w, ht, s->d_raw, p, st, pl);
+    const int r = t <= TS_CSC_UYVY ? k_launch_csc(fmt, p[0], p[1], p[2], st[0], st[1], st[2], s->d_src_y, s->d_src_uv, w, ht, h->W, h->H, h->stream)
+                : t == TS_DEEP_P010 ? k_launch_csc2(fmt, p[0], p[1], p[2], st[0], st[1], st[2], s->d_src_y, s->d_src_uv, w, ht, h->W, h->H, h->csc_coef, h->stream)
+                                    : hdr_convert(h, fmt, p, st, s->d_src_y, s->d_src_uv, w, ht, h->W, h->H, h->stream);
+    return !r ? 0 : r < -1 ? r : MI355ENC_ERR_ARG;
+}
+// orientation: an NV12 picture of the pre-orientation size in the raw staging buffer -> the coded surfaces
+static int ts_orient(mi355enc_t *h, slot_t *s, ts_ctx_t *) {
+    const int m = h->orient ? h->orient : MI355ENC_ORIENT_90R, pw = orient_transposes(m) ? h->cfg.height : h->cfg.width, ph = orient_transposes(m) ? h->cfg.width : h->cfg.height;
+    const int ps = (pw + 15) & ~15;
+    return k_launch_orient(m, s->d_raw, ps, s->d_raw + (size_t)ps * ph, ps, pw, ph, s->d_src_y, s->d_src_uv, h->W, h->H, h->stream) ? MI355ENC_ERR_ARG : 0;
+}
+// the scale / geometry launch: an NV12 picture of the input size in the raw staging buffer -> the input target (a stale slot copy of the tables travels in prepare)
+static int ts_scale_prepare(mi355enc_t *h, slot_t *s, ts_ctx_t *x) { return (x->scale = scale_plan_for(h, s, h->stream)) ? 0 : MI355ENC_ERR_HIP; }
+static int ts_scale(mi355enc_t *h, slot_t *s, ts_ctx_t *x) {
+    const int ds = (h->in_w + 15) & ~15;
+    in_target_t t;
+    { int r = input_target(h, s, &t); if (r) return r; }
+    return k_launch_scale(MI355ENC_FMT_NV12, s->d_raw, s->d_raw + (size_t)ds * h->in_h, nullptr, ds, ds, 0, t.y, t.uv, t.W, t.H, x->scale, h->stream) ? MI355ENC_ERR_ARG : 0;
+}
+static int ts_image(mi355enc_t *h, slot_t *, ts_ctx_t *x) { k_launch_image_blend(&x->img, h->stream); return 0; }
+static int ts_yuv(mi355enc_t *h, slot_t *s, ts_ctx_t *) { return yuv_draw(h, s, h->stream); }            // the colour step, in place on slot 0's surfaces (whatever they hold)
+static int ts_rate(mi355enc_t *h, slot_t *s, ts_ctx_t *) { return rate_mix(h, s, s, 128, true, h->stream); } // the mix of the keep buffer and slot 0's surfaces, in place as the encoder runs it
+static constexpr ts_row_t k_ts[] = {
+    // stage                ready               prepare                 launch                 done               needs_raw
+    {TS_ME,             nullptr,            nullptr,                ts_me,                 nullptr,           false},
+    {TS_INTER,          nullptr,            nullptr,                ts_inter,              nullptr,           false},
+    {TS_INTRA,          nullptr,            nullptr,                ts_intra,              nullptr,           false},
+    {TS_DEBLOCK,        nullptr,            nullptr,                ts_deblock,            nullptr,           false},
+    {TS_SUBPEL,         nullptr,            nullptr,                ts_subpel,             nullptr,           false},
+    {TS_CSC_I420,       nullptr,            nullptr,                ts_convert,            nullptr,           true},
+    {TS_CSC_YUY2,       nullptr,            nullptr,                ts_convert,            nullptr,           true},
+    {TS_CSC_UYVY,       nullptr,            nullptr,                ts_convert,            nullptr,           true},
+    {TS_ME_SELECT,      nullptr,            nullptr,                ts_me_select,          nullptr,           false},
+    {TS_PMB,            nullptr,            nullptr,                ts_pmb,                nullptr,           false},
+    {TS_INTRA_P,        nullptr,            ts_intra_p_prepare,     ts_intra_p,            nullptr,           false},
+    {TS_QUALITY,        nullptr,            ts_quality_prepare,     ts_quality,            nullptr,           false},
+    {TS_JPEG,           nullptr,            ts_jpeg_prepare,        jpeg_time_launch,      nullptr,           false},
+    {TS_ORIENT,         nullptr,            nullptr,                ts_orient,             nullptr,           true},
+    {TS_SCALE,          ts_has_scale,       ts_scale_prepare,       ts_scale,              nullptr,           true},
+    {TS_IMAGE,          nullptr,            image_time_prepare,     ts_image,              nullptr,           false}, // (prepare: ERR_STATE without an image on layer 0)
+    {TS_SNAPSHOT,       nullptr,            snapshot_time_prepare,  snapshot_time_launch,  nullptr,           false},
+    {TS_YUV_CONVERT,    ts_has_yuv,         nullptr,                ts_yuv,                nullptr,           false},
+    {TS_RATE,           ts_has_keep,        nullptr,                ts_rate,               nullptr,           false},
+    {TS_HDR_P010,       ts_has_hdr,         nullptr,                ts_convert,            nullptr,           true},
+    {TS_HDR_I420_10,    ts_has_hdr,         nullptr,                ts_convert,            nullptr,           true},
+    {TS_HDR_V210,       ts_has_hdr,         nullptr,                ts_convert,            nullptr,           true},
+    {TS_DEEP_P010,      nullptr,            nullptr,                ts_convert,            nullptr,           true},
+    {TS_ADJUST_POINT,   adjust_time_ready,  nullptr,                adjust_time_launch,    nullptr,           false}, // (mi355enc_set_adjust first: 23 with sharpen 0, 24 with sharpen set)
+    {TS_ADJUST_SHARPEN, adjust_time_ready,  nullptr,                adjust_time_launch,    nullptr,           false},
+    {TS_DENOISE,        denoise_time_ready, nullptr,                denoise_time_launch,   denoise_time_done, false}, // (mi355enc_set_denoise first; 27 / 28: and mi355enc_set_denoise_motion)
+    {TS_DENOISE_PRIME,  denoise_time_ready, nullptr,                denoise_time_launch,   denoise_time_done, false},
+    {TS_DENOISE_SEARCH, denoise_time_ready, nullptr,                denoise_time_launch,   denoise_time_done, false},
+    {TS_DENOISE_MC,     denoise_time_ready, nullptr,                denoise_time_launch,   denoise_time_done, false},
+};
+static_assert(sizeof k_ts / sizeof k_ts[0] == 29 && TS_COUNT == 29, "one row per stage 0 .. 28");
+template <size_t... I> static constexpr bool ts_rows_in_order(std::index_sequence<I...>) { return ((k_ts[I].stage == (int)I) && ...); }
+static_assert(ts_rows_in_order(std::make_index_sequence<TS_COUNT>()), "row i describes stage i");
+
+extern "C" {
+
+int mi355enc_stage_me(mi355enc_t *h, const uint8_t *cur_y, const uint8_t *ref_y, int qp, uint16_t *surf_out, void *imv_out) {
+    if (!h || !cur_y || !ref_y || !imv_out || qp < 0 || qp > 51) return MI355ENC_ERR_ARG;
+    int r = stage_enter(h); if (r) return r;
+    HIPCHK(hipMemcpyAsync(h->slot[0].d_src_y, cur_y, h->ysz, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_psrc[h->psrc_cur], ref_y, h->ysz, hipMemcpyHostToDevice, h->stream)); // what the search runs against (in the encoder: the previous source)
+    r = stage_ctx(h, qp, true); if (r) return r;
+    k_launch_me(h->slot[0].h_ctx, h->mbw, h->stream);
+    HIPCHK(hipMemcpyAsync(imv_out, h->d_imv[0][0], (size_t)h->nmb * sizeof(imv_t), hipMemcpyDeviceToHost, h->stream));
+    if (surf_out) HIPCHK(hipMemcpyAsync(surf_out, h->d_surf[0], (size_t)h->nmb * SURF_U16 * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MI355ENC_OK;
+}
+// imv_prev null: the first selection.  Otherwise the form the encoder's later iterations use (me_select_sparse_kernel): imv_prev is the field imv_in was selected
+// from -- a macroblock whose predictors are the same in both copies its entry of imv_in.  Must equal the first form whenever imv_in really is the selection over imv_prev.
+static int me_select(mi355enc_t *h, const uint16_t *surf, const void *imv_in, const void *imv_prev, int qp, void *imv_out) {
+    if (!h || !surf || !imv_in || !imv_out || qp < 0 || qp > 51) return MI355ENC_ERR_ARG;
+    int r = stage_enter(h); if (r) return r;
+    r = stage_ctx(h, qp, true); if (r) return r;
+    HIPCHK(hipMemcpyAsync(h->d_surf[0], surf, (size_t)h->nmb * SURF_U16 * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_imv[0][0], imv_in, (size_t)h->nmb * sizeof(imv_t), hipMemcpyHostToDevice, h->stream));
+    if (imv_prev) HIPCHK(hipMemcpyAsync(h->d_imv[0][2], imv_prev, (size_t)h->nmb * sizeof(imv_t), hipMemcpyHostToDevice, h->stream));
+    k_launch_me_select(h->slot[0].h_ctx, h->mbw, h->d_imv[0][0], h->d_imv[0][1], imv_prev ? h->d_imv[0][2] : nullptr, imv_prev ? 2 : 0, h->stream);
+    HIPCHK(hipMemcpyAsync(imv_out, h->d_imv[0][1], (size_t)h->nmb * sizeof(imv_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MI355ENC_OK;
+}
+int mi355enc_stage_me_select(mi355enc_t *h, const uint16_t *surf, const void *imv_in, int qp, void *imv_out) { return me_select(h, surf, imv_in, nullptr, qp, imv_out); }
+int mi355enc_stage_me_select_next(mi355enc_t *h, const uint16_t *surf, const void *imv_in, const void *imv_prev, int qp, void *imv_out) { return imv_prev ? me_select(h, surf, imv_in, imv_prev, qp, imv_out) : MI355ENC_ERR_ARG; }
+int mi355enc_stage_subpel(mi355enc_t *h, const uint8_t *cur_y, const uint8_t *ref_y, int qp, void *mbinfo_inout) {
+    if (!h || !cur_y || !ref_y || !mbinfo_inout || qp < 0 || qp > 51) return MI355ENC_ERR_ARG;
+    int r = stage_enter(h); if (r) return r;
+    HIPCHK(hipMemcpyAsync(h->slot[0].d_src_y, cur_y, h->ysz, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_rec_y[0], ref_y, h->ysz, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_mbi, mbinfo_inout, (size_t)h->nmb * sizeof(mb_info_t), hipMemcpyHostToDevice, h->stream));
+    r = stage_ctx(h, qp, true); if (r) return r;
+    k_launch_subpel(h->slot[0].h_ctx, h->mbw, h->stream);
+    HIPCHK(hipMemcpyAsync(mbinfo_inout, h->d_mbi, (size_t)h->nmb * sizeof(mb_info_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MI355ENC_OK;
+}
 int mi355enc_stage_inter(mi355enc_t *h, const uint8_t *src_y, const uint8_t *src_uv, const uint8_t *ref_y, const uint8_t *ref_uv,
                          int qp, void *mbinfo_inout, uint8_t *rec_y, uint8_t *rec_uv, int16_t *levels) {
     if (!h || !src_y || !src_uv || !ref_y || !ref_uv || !mbinfo_inout || !rec_y || !rec_uv || !levels || qp < 0 || qp > 51) return MI355ENC_ERR_ARG;
     if (h->cfg.transform8x8 == 2) return MI355ENC_ERR_ARG; // the two-kernel form has no per-macroblock transform choice (the fused stage has: mi355enc_stage_pmb)
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    STAGE_IDLE(h);
-    int r = upload_planes4(h, src_y, src_uv, ref_y, ref_uv); if (r) return r;
+    int r = stage_enter(h); if (r) return r;
+    r = stage_in(h, &h->slot[0], src_y, src_uv); if (r) return r;
+    r = upload_rec(h, 0, ref_y, ref_uv); if (r) return r;
     HIPCHK(hipMemcpyAsync(h->d_mbi, mbinfo_inout, (size_t)h->nmb * sizeof(mb_info_t), hipMemcpyHostToDevice, h->stream));
     r = stage_ctx(h, qp, true); if (r) return r;
     k_launch_inter(h->slot[0].h_ctx, h->mbw, h->stream);
@@ -120,9 +205,9 @@ int mi355enc_stage_pmb(mi355enc_t *h, const uint8_t *src_y, const uint8_t *src_u
                        void *mbinfo_out, uint8_t *rec_y, uint8_t *rec_uv, int16_t *levels) {
     if (!h || !src_y || !src_uv || !ref_y || !ref_uv || !imv || !surf || !mbinfo_out || !rec_y || !rec_uv || !levels || qp < 0 || qp > 51 || drop < 0 || drop > DROP_MAX)
         return MI355ENC_ERR_ARG;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    STAGE_IDLE(h);
-    int r = upload_planes4(h, src_y, src_uv, ref_y, ref_uv); if (r) return r;
+    int r = stage_enter(h); if (r) return r;
+    r = stage_in(h, &h->slot[0], src_y, src_uv); if (r) return r;
+    r = upload_rec(h, 0, ref_y, ref_uv); if (r) return r;
     r = stage_ctx(h, qp, true, drop); if (r) return r;
     frame_ctx_t *c = h->slot[0].h_ctx;
     c->intra_p = idec ? 1 : 0;
@@ -141,21 +226,17 @@ int mi355enc_stage_pmb(mi355enc_t *h, const uint8_t *src_y, const uint8_t *src_u
 int mi355enc_stage_intra(mi355enc_t *h, const uint8_t *src_y, const uint8_t *src_uv, int qp, int drop, void *mbinfo_out, uint8_t *rec_y,
                          uint8_t *rec_uv, int16_t *levels) {
     if (!h || !src_y || !src_uv || !mbinfo_out || !rec_y || !rec_uv || !levels || qp < 0 || qp > 51 || drop < 0 || drop > DROP_MAX) return MI355ENC_ERR_ARG;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    STAGE_IDLE(h);
-    HIPCHK(hipMemcpyAsync(h->slot[0].d_src_y, src_y, h->ysz, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->slot[0].d_src_uv, src_uv, h->csz, hipMemcpyHostToDevice, h->stream));
-    int r = stage_ctx(h, qp, true, drop, 1); if (r) return r;
+    int r = stage_enter(h); if (r) return r;
+    r = stage_in(h, &h->slot[0], src_y, src_uv); if (r) return r;
+    r = stage_ctx(h, qp, true, drop, 1); if (r) return r;
     r = run_intra(h, 0, h->slot[0].h_ctx); if (r) return r;
     return download_picture(h, mbinfo_out, rec_y, rec_uv, levels) ? MI355ENC_ERR_HIP : MI355ENC_OK;
 }
 int mi355enc_stage_intra_analyse(mi355enc_t *h, const uint8_t *src_y, const uint8_t *src_uv, int qp, uint16_t *isad_out, void *idec_out) {
     if (!h || !src_y || !src_uv || !isad_out || qp < 0 || qp > 51) return MI355ENC_ERR_ARG;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    STAGE_IDLE(h);
-    HIPCHK(hipMemcpyAsync(h->slot[0].d_src_y, src_y, h->ysz, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->slot[0].d_src_uv, src_uv, h->csz, hipMemcpyHostToDevice, h->stream));
-    int r = stage_ctx(h, qp, true); if (r) return r;
+    int r = stage_enter(h); if (r) return r;
+    r = stage_in(h, &h->slot[0], src_y, src_uv); if (r) return r;
+    r = stage_ctx(h, qp, true); if (r) return r;
     k_launch_intra_analyse(h->slot[0].h_ctx, h->mbw, h->mbh, 0, h->stream);
     HIPCHK(hipMemcpyAsync(isad_out, h->d_isad, (size_t)h->nmb * ISAD_PER_MB * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
     if (idec_out) HIPCHK(hipMemcpyAsync(idec_out, h->d_idec, (size_t)h->nmb * IDEC_BYTES, hipMemcpyDeviceToHost, h->stream));
@@ -164,12 +245,10 @@ int mi355enc_stage_intra_analyse(mi355enc_t *h, const uint8_t *src_y, const uint
 }
 int mi355enc_stage_deblock(mi355enc_t *h, uint8_t *rec_y, uint8_t *rec_uv, const void *mbinfo) {
     if (!h || !rec_y || !rec_uv || !mbinfo) return MI355ENC_ERR_ARG;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    STAGE_IDLE(h);
-    HIPCHK(hipMemcpyAsync(h->d_rec_y[1], rec_y, h->ysz, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_rec_uv[1], rec_uv, h->csz, hipMemcpyHostToDevice, h->stream));
+    int r = stage_enter(h); if (r) return r;
+    r = upload_rec(h, 1, rec_y, rec_uv); if (r) return r;
     HIPCHK(hipMemcpyAsync(h->d_mbi, mbinfo, (size_t)h->nmb * sizeof(mb_info_t), hipMemcpyHostToDevice, h->stream));
-    int r = stage_ctx(h, 26, false); if (r) return r;
+    r = stage_ctx(h, 26, false); if (r) return r;
     r = run_deblock(h, 0, h->slot[0].h_ctx); if (r) return r;
     HIPCHK(hipMemcpyAsync(rec_y, h->d_rec_y[1], h->ysz, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(rec_uv, h->d_rec_uv[1], h->csz, hipMemcpyDeviceToHost, h->stream));
@@ -179,29 +258,22 @@ int mi355enc_stage_deblock(mi355enc_t *h, uint8_t *rec_y, uint8_t *rec_uv, const
 // quality metrics, the kernel alone: host planes of the coded size through the encoder's own surfaces ...
 int mi355enc_stage_quality(mi355enc_t *h, const uint8_t *src_y, const uint8_t *src_uv, const uint8_t *rec_y, const uint8_t *rec_uv, mi355enc_quality_t *q) {
     if (!h || !src_y || !src_uv || !rec_y || !rec_uv || !q) return MI355ENC_ERR_ARG;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    STAGE_IDLE(h);
-    HIPCHK(hipStreamSynchronize(h->cstream));
-    { int r = sync_compute(h); if (r) return r; }
     slot_t *s = &h->slot[0];
-    HIPCHK(hipMemcpyAsync(s->d_src_y, src_y, h->ysz, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(s->d_src_uv, src_uv, h->csz, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_rec_y[1], rec_y, h->ysz, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_rec_uv[1], rec_uv, h->csz, hipMemcpyHostToDevice, h->stream));
+    int r = stage_enter(h); if (r) return r;
+    r = stage_in(h, s, src_y, src_uv); if (r) return r;
+    r = upload_rec(h, 1, rec_y, rec_uv); if (r) return r;
     stage_touched(h);
     return quality_run(h, s->d_src_y, s->d_src_uv, h->W, h->d_rec_y[1], h->d_rec_uv[1], q);
 }
 // ... and planes that lie on the device, where they lie
 int mi355enc_stage_quality_device(mi355enc_t *h, const void *d_src_y, const void *d_src_uv, int src_stride, const void *d_rec_y, const void *d_rec_uv, mi355enc_quality_t *q) {
     if (!h || !d_src_y || !d_src_uv || !d_rec_y || !d_rec_uv || !q || src_stride < h->cfg.width) return MI355ENC_ERR_ARG;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    STAGE_IDLE(h);
+    int r = stage_enter(h); if (r) return r;
     return quality_run(h, (const uint8_t *)d_src_y, (const uint8_t *)d_src_uv, src_stride, (const uint8_t *)d_rec_y, (const uint8_t *)d_rec_uv, q);
 }
 int mi355enc_debug_trip_wait(mi355enc_t *h, unsigned code) {
     if (!h || !code) return MI355ENC_ERR_ARG;
     HIPCHK(hipSetDevice(h->cfg.device_id));
-    HIPCHK(hipStreamSynchronize(h->cstream));
     { int r = sync_compute(h); if (r) return r; }
     return h->words.trip(code);
 }
@@ -215,10 +287,7 @@ int mi355enc_debug_get_counters(mi355enc_t *h, mi355enc_counters_t *out) {
 // tagged with an epoch, and the parity of the band parts' counters stay as the last picture left them.
 int mi355enc_debug_set_counters(mi355enc_t *h, const mi355enc_counters_t *in) {
     if (!h || !in || (!(in->keep & 64u) && in->frames_since_idr > 0x7FFFFFFFu) || (!(in->keep & 32u) && in->idr_count > 0x7FFFFFFFu)) return MI355ENC_ERR_ARG;
-    STAGE_IDLE(h);
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    HIPCHK(hipStreamSynchronize(h->cstream));
-    { int r = sync_compute(h); if (r) return r; }
+    { int r = stage_enter(h); if (r) return r; }
     if (!(in->keep & 1u)) h->epoch = in->epoch;
     { int r = h->words.set(in); if (r) return r; }
     if (!(in->keep & 32u)) h->idr_count = (int)in->idr_count;
@@ -226,93 +295,33 @@ int mi355enc_debug_set_counters(mi355enc_t *h, const mi355enc_counters_t *in) {
     return MI355ENC_OK;
 }
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms) {
-    if (!h || !avg_ms || iters < 1 || stage < 0 || stage > 28) return MI355ENC_ERR_ARG;
-    if (stage == 17 && !h->yuv_on) return MI355ENC_ERR_STATE; // (the handle has no conversion)
-    if (stage >= 19 && stage <= 21 && (!h->hdr_on || hdr_refuses(h, MI355ENC_FMT_P010))) return MI355ENC_ERR_STATE; // (mi355enc_set_hdr_input first, and an output matrix it converts to)
-    if (stage >= 25 && !denoise_time_ready(h, stage)) return MI355ENC_ERR_STATE; // (mi355enc_set_denoise first; 27 / 28: and mi355enc_set_denoise_motion)
-    if (stage >= 23 && stage <= 24 && !adjust_time_ready(h, stage == 24)) return MI355ENC_ERR_STATE; // (mi355enc_set_adjust first: 23 with sharpen 0, 24 with sharpen set)
-    if (stage == 18 && !h->d_keep) return MI355ENC_ERR_STATE; // (frame-rate conversion off, or hold mode without a keep buffer: there is no mix)
-    if (stage == 14 && !h->d_scale_tab) return MI355ENC_ERR_STATE; // (mi355enc_set_input_size or mi355enc_set_input_geometry first)
-    if (h->pending) return MI355ENC_ERR_STATE;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
+    if (!h || !avg_ms || iters < 1 || stage < 0 || stage >= TS_COUNT) return MI355ENC_ERR_ARG;
+    const ts_row_t &row = k_ts[stage];
+    if (row.ready && !row.ready(h, stage)) return MI355ENC_ERR_STATE;
+    { int r = stage_enter(h); if (r) return r; }
     slot_t *s = &h->slot[0];
     // a valid context in both places: the LAST COLLECTED picture's host copy (the slots rotate: it is slot 0's only one time in three), brought
     // to slot 0 and re-uploaded -- or a fresh stage context.  The stages run on that picture's surfaces in place (stage 3 filters its
     // reconstruction again), so the next picture through the pipeline starts a new GOP.
     if (!h->have_ref || !h->last_slot) { int r = stage_ctx(h, 26, true); if (r) return r; }
     else {
-        { int r = sync_compute(h); if (r) return r; }
-        HIPCHK(hipStreamSynchronize(h->cstream));
         if (h->last_slot != s) *s->h_ctx = *h->last_slot->h_ctx;
         HIPCHK(hipMemcpyAsync(h->d_ctx, s->h_ctx, sizeof(frame_ctx_t), hipMemcpyHostToDevice, h->stream));
         stage_touched(h);
     }
-    if (stage == 11) { int r = quality_alloc(h); if (r) return r; } // (the block of the stage entry points)
-    if (((stage >= 5 && stage <= 7) || stage == 13 || stage == 14 || (stage >= 19 && stage <= 22)) && !s->d_raw) { // input conversion (5 I420, 6 YUY2, 7 UYVY), orientation (13), scale / geometry (14): any bytes will do as a source
+    if (row.needs_raw && !s->d_raw) {
         HIPCHK(hipMalloc((void **)&s->d_raw, raw_bytes(h)));
         HIPCHK(hipMemsetAsync(s->d_raw, 0x55, raw_bytes(h), h->stream));
     }
-    if (stage == 12) { int r = jpeg_alloc(h, s); if (r) return r; }
-    if (stage == 16) { int r = snapshot_time_prepare(h); if (r) return r; } // (the block of the stage entry points)
-    if (stage == 10) { int r = h->words.ip_rows_stamp(s->h_ctx->epoch, h->stream); if (r) return r; }
-    const scale_plan_t *scale_pl = stage == 14 ? scale_plan_for(h, s, h->stream) : nullptr; // (a stale slot copy of the tables travels here, not inside the timed loop)
-    if (stage == 14 && !scale_pl) return MI355ENC_ERR_HIP;
-    image_args_t img_a; // stage 15: layer 0's image on the device and prepared here, not inside the timed loop
-    if (stage == 15) { int r = image_time_prepare(h, &img_a); if (r) return r; }
+    ts_ctx_t x; x.stage = stage; x.scale = nullptr; // what prepare hands to launch
+    if (row.prepare) { int r = row.prepare(h, s, &x); if (r) return r; }
     for (int warm = 0; warm < 2; warm++) {
         if (warm) HIPCHK(hipEventRecord(s->ev[0], h->stream));
-        for (int i = 0; i < (warm ? iters : 1); i++) {
-            if (stage == 0) k_launch_me(h->slot[0].h_ctx, h->mbw, h->stream);
-            else if (stage == 1) k_launch_inter(h->slot[0].h_ctx, h->mbw, h->stream);
-            else if (stage == 2) { if (++h->epoch == 0) h->epoch = 1; h->slot[0].h_ctx->epoch = h->epoch; int r = run_intra(h, 0, h->slot[0].h_ctx); if (r) return r; } // a fresh stamp per launch: the lines between bands are epoch-tagged
-            else if (stage == 4) k_launch_subpel(h->slot[0].h_ctx, h->mbw, h->stream);
-            else if (stage == 8) k_launch_me_select(h->slot[0].h_ctx, h->mbw, h->d_imv[0][0], h->d_imv[0][1], nullptr, 0, h->stream);
-            else if (stage == 9) { int r = run_pmb(h, h->slot[0].h_ctx, 1, pic_plan_t(), h->stream); if (r) return r; }
-            else if (stage == 11) k_launch_quality(s->d_src_y, s->d_src_uv, h->W, h->d_rec_y[1], h->d_rec_uv[1], h->W, h->cfg.width, h->cfg.height, h->d_qacc + (size_t)NSLOT * QUALITY_ACC_WORDS,
-                                                   h->h_qres + (size_t)NSLOT * QUALITY_WORDS, h->stream);
-            else if (stage == 12) { int r = jpeg_time_launch(h, s); if (r) return r; }
-            else if (stage == 13) { // an NV12 picture of the pre-orientation size in the raw staging buffer -> the coded surfaces
-                const int m = h->orient ? h->orient : MI355ENC_ORIENT_90R, pw = orient_transposes(m) ? h->cfg.height : h->cfg.width, ph = orient_transposes(m) ? h->cfg.width : h->cfg.height;
-                const int ps = (pw + 15) & ~15;
-                if (k_launch_orient(m, s->d_raw, ps, s->d_raw + (size_t)ps * ph, ps, pw, ph, s->d_src_y, s->d_src_uv, h->W, h->H, h->stream)) return MI355ENC_ERR_ARG;
-            }
-            else if (stage == 14) { // the scale / geometry launch: an NV12 picture of the input size in the raw staging buffer -> the input target
-                const int ds = (h->in_w + 15) & ~15;
-                in_target_t t;
-                int r = input_target(h, s, &t);
-                if (r) return r;
-                if (k_launch_scale(MI355ENC_FMT_NV12, s->d_raw, s->d_raw + (size_t)ds * h->in_h, nullptr, ds, ds, 0, t.y, t.uv, t.W, t.H, scale_pl, h->stream)) return MI355ENC_ERR_ARG;
-            }
-            else if (stage == 15) k_launch_image_blend(&img_a, h->stream);
-            else if (stage == 16) { int r = snapshot_time_launch(h, s); if (r) return r; }
-            else if (stage == 17) { int r = yuv_draw(h, s, h->stream); if (r) return r; } // the colour step, in place on slot 0's surfaces (whatever they hold)
-            else if (stage == 18) { int r = rate_mix(h, s, s, 128, true, h->stream); if (r) return r; } // the mix of the keep buffer and slot 0's surfaces, in place as the encoder runs it
-            else if (stage >= 25) { int r = denoise_time_launch(h, s, stage); if (r) return r; } // the noise filter set last, in place on slot 0's surfaces and the handle's history: 25 filtering, 26 priming, 27 the search alone, 28 search and compensated filter
-            else if (stage >= 23) { int r = adjust_time_launch(h, s); if (r) return r; } // the picture controls set last, in place on slot 0's surfaces: 23 the pointwise form, 24 the stencil form with the hand-back of its scratch plane
-            else if (stage >= 19) { // the conversion launch of a 10-bit picture in the raw staging buffer: 19 P010, 20 I420_10, 21 V210 tone-mapped; 22 P010 plain (section 20)
-                const int fmt = stage == 22 ? MI355ENC_FMT_P010 : MI355ENC_FMT_P010 + stage - 19, w = h->cfg.width, ht = h->cfg.height;
-                fmt_plane_t pl[3];
-                const int n = fmt_planes(fmt, w, ht, pl);
-                const uint8_t *p[3] = {nullptr, nullptr, nullptr};
-                int st[3] = {0, 0, 0};
-                const uint8_t *d = s->d_raw;
-                for (int k = 0; k < n; k++) { st[k] = (pl[k].row + 15) & ~15; p[k] = d; d += (size_t)st[k] * pl[k].rows; }
-                int r = stage == 22 ? k_launch_csc2(fmt, p[0], p[1], p[2], st[0], st[1], st[2], s->d_src_y, s->d_src_uv, w, ht, h->W, h->H, h->csc_coef, h->stream)
-                                    : hdr_convert(h, fmt, p, st, s->d_src_y, s->d_src_uv, w, ht, h->W, h->H, h->stream);
-                if (r) return r < -1 ? r : MI355ENC_ERR_ARG;
-            }
-            else if (stage == 10) k_launch_intra_p(h->slot[0].h_ctx, h->mbw, h->mbh, h->words.ip_progress(), h->d_ip_strips, h->words.err(), h->stream);
-            else if (stage >= 5) {
-                const int w = h->cfg.width, ht = h->cfg.height, r0 = stage == 5 ? (w + 15) & ~15 : (2 * w + 15) & ~15, r1 = (w / 2 + 15) & ~15;
-                const uint8_t *p0 = s->d_raw, *p1 = p0 + (size_t)r0 * ht, *p2 = p1 + (size_t)r1 * (ht / 2);
-                k_launch_csc(stage - 4, p0, p1, p2, r0, r1, r1, s->d_src_y, s->d_src_uv, w, ht, h->W, h->H, h->stream);
-            }
-            else { if (++h->epoch == 0) h->epoch = 1; h->slot[0].h_ctx->epoch = h->epoch; int r = run_deblock(h, 0, h->slot[0].h_ctx); if (r) return r; } // a fresh stamp per launch: the strips between bands are epoch-tagged
-        }
+        for (int i = 0; i < (warm ? iters : 1); i++) { int r = row.launch(h, s, &x); if (r) return r; }
         if (warm) HIPCHK(hipEventRecord(s->ev[1], h->stream));
     }
     HIPCHK(hipEventSynchronize(s->ev[1]));
-    if (stage >= 25) denoise_time_done(h); // (a stream that follows primes: it does not filter against what the probe left)
+    if (row.done) row.done(h); // (the noise filter: a stream that follows primes, it does not filter against what the probe left)
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
     *avg_ms = (double)ms / iters;
