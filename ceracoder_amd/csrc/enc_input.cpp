@@ -38,12 +38,14 @@ static int ingest_latch(mi355enc_t *h, slot_t *s) {
         overlay_latch(h, t);
         adjust_latch(h, t); // (what the tick's picture reports; the adjustment itself is applied to the input, once)
         denoise_latch(h, t, false); // (likewise; only the input's own slot launches and needs the tables)
+        (void)stab_latch(h, t, false); // (likewise: the shake is measured on the input, once)
         int r = image_latch(h, t);
         if (r) return r;
     }
     overlay_latch(h, s);
     adjust_latch(h, s);
     denoise_latch(h, s, true);
+    { int r = stab_latch(h, s, true); if (r) return r; }
     return image_latch(h, s);
 }
 // (apart only for mi355enc_submit_jpeg, which decodes into the slot between the two: after the state check -- with the pipeline full the slot's buffers
@@ -148,8 +150,8 @@ int input_nv12(mi355enc_t *h, slot_t *s, nv12_pic_t *c) {
     c->y = s->d_csc; c->uv = c->y + (size_t)c->stride * h->in_h;
     return MI355ENC_OK;
 }
-int scale_nv12(const nv12_pic_t *c, const in_target_t *t, const scale_plan_t *pl, hipStream_t up) {
-    return k_launch_scale(MI355ENC_FMT_NV12, c->y, c->uv, nullptr, c->stride, c->stride, 0, t->y, t->uv, t->W, t->H, pl, up);
+int scale_nv12(mi355enc_t *h, slot_t *s, const nv12_pic_t *c, const in_target_t *t, const scale_plan_t *pl, hipStream_t up) {
+    return input_scale(h, s, MI355ENC_FMT_NV12, c->y, c->uv, nullptr, c->stride, c->stride, 0, t, pl, up);
 }
 
 // ... and convert (or, with an input size of its own, scale) it into the slot's NV12 staging surfaces.  NV12 only when scaling: unscaled, it is
@@ -182,9 +184,9 @@ int upload_and_convert(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *const p
             if (r) return r;
             if (h->hdr_on) r = hdr_convert(h, fmt, p, st, c.y, c.uv, h->in_w, h->in_h, c.stride, h->in_h, up);
             else r = k_launch_csc2(fmt, p[0], p[1], p[2], st[0], st[1], st[2], c.y, c.uv, h->in_w, h->in_h, c.stride, h->in_h, h->csc_coef, up);
-            if (!r) r = scale_nv12(&c, &t, pl, up);
+            if (!r) r = scale_nv12(h, s, &c, &t, pl, up);
         }
-    } else if (h->scaling) r = k_launch_scale(fmt, p[0], p[1], p[2], st[0], st[1], st[2], t.y, t.uv, t.W, t.H, pl, up);
+    } else if (h->scaling) r = input_scale(h, s, fmt, p[0], p[1], p[2], st[0], st[1], st[2], &t, pl, up);
     else r = k_launch_csc(fmt, p[0], p[1], p[2], st[0], st[1], st[2], t.y, t.uv, t.vw, t.vh, t.W, t.H, up);
     if (r) return r < -1 ? r : MI355ENC_ERR_ARG;
     HIPCHK(hipGetLastError());
@@ -290,7 +292,7 @@ int mi355enc_submit(mi355enc_t *h, const uint8_t *y, int y_stride, const uint8_t
         const scale_plan_t *pl = scale_plan_for(h, s, up);
         if (!pl) return MI355ENC_ERR_HIP;
         const nv12_pic_t raw = {dev_y, dev_uv, ds};
-        if (scale_nv12(&raw, &t, pl, up)) return MI355ENC_ERR_ARG;
+        { int r = scale_nv12(h, s, &raw, &t, pl, up); if (r) return r; }
         HIPCHK(hipGetLastError());
     }
     else if (!h->orient && (w != h->W || (s->dn.parts && (ht & 7)))) k_launch_pad(s->d_src_y, s->d_src_uv, h->W, w, ht, h->W, h->H, up); // (the orientation launch writes the margin itself; the bottom margin alone is padded only for the noise filter, the one step that reads it, and only where a block row is partly visible: its block measure takes such a block as it lies)
@@ -338,7 +340,8 @@ int mi355enc_submit_device(mi355enc_t *h, const void *d_y, int y_stride, const v
         if (r) return r;
         const scale_plan_t *pl = scale_plan_for(h, s, up);
         if (!pl) return MI355ENC_ERR_HIP;
-        if (k_launch_scale(MI355ENC_FMT_NV12, (const uint8_t *)d_y, (const uint8_t *)d_uv, nullptr, y_stride, uv_stride, 0, t.y, t.uv, t.W, t.H, pl, up)) return MI355ENC_ERR_ARG;
+        r = input_scale(h, s, MI355ENC_FMT_NV12, (const uint8_t *)d_y, (const uint8_t *)d_uv, nullptr, y_stride, uv_stride, 0, &t, pl, up); // (stabilised: the whole submitted luma is read, not only the crop)
+        if (r) return r;
         HIPCHK(hipGetLastError());
         r = input_finish(h, s, up);
     } else if (h->orient) { // oriented from where the planes lie, at their stride and address, into the slot's staging surfaces: never in place, the caller's planes are only read

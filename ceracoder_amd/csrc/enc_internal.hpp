@@ -13,6 +13,7 @@
 //   enc_csc.cpp       colorimetry: the setters, the RGB matrix and the YUV -> YUV table, the colour step's launch, their stage entry points
 //   enc_adjust.cpp    picture controls: setter, latch, the two launch forms and the scratch plane, its stage entry point
 //   enc_denoise.cpp   temporal noise reduction: setter, latch, the launch and the handle's history, its stage entry point
+//   enc_stab.cpp      electronic image stabilisation: setter, latch, the estimate in front of every scale launch, its probes and timed stages
 //   enc_rate.cpp      frame-rate conversion: setter, the plan's step and commit per submit, keep buffer, mix / keep / repeat launches, its stage entry point
 //   enc_hdr.cpp       HDR input: setter, the parameter block on the host and on the device, the tone-mapping conversion launch
 //   enc_quality.cpp   quality metrics: setter, the accumulator and result blocks, enqueue / collect, the stage launch
@@ -41,6 +42,7 @@
 #include "hdr_host.h"
 #include "adjust_host.h"
 #include "denoise_host.h"
+#include "stab_host.h"
 #include "enc_plan.hpp"
 #include "enc_sync.hpp"
 
@@ -133,6 +135,9 @@ struct slot_t {
     adjust_set_t adj;
     // temporal noise reduction: what submit latched for this picture (dn.parts 0: nothing); applied once, to the input's own slot, in ingest_end
     denoise_set_t dn;
+    // image stabilisation: what submit latched for this picture (stab.range 0: off), and whether the estimate ran for it (its record then lies in the handle's
+    // pinned block at the slot's index once the picture is collected)
+    mi355enc_stabilize_t stab; bool stab_done;
 };
 
 struct mi355enc {
@@ -255,6 +260,18 @@ struct mi355enc {
     unsigned *d_dn_vec = nullptr;
     size_t dn_bytes = 0;
     mi355enc_denoise_t dn_prev = {0, 0};
+    // electronic image stabilisation (mi355enc_set_stabilize): what the control thread set last (under stab_mu; submit latches it per input
+    // picture) and what the last collected picture carried.  d_stab (one block, allocated by the first stabilised picture for the input size stab_w x stab_h;
+    // stab_bytes: its size): the trajectory {Sx, Sy}, a record of STAB_REC_WORDS words per slot and one for the stage calls, then the two halves of the
+    // projection buffer (4 (in_w + in_h) words each); h_stab: the records' pinned copies.  stab_half: the half the next picture's sums go into (the other one
+    // holds the previous picture's); stab_primed false: the next stabilised picture primes.  Written only by launches that follow one another on the upload stream.
+    std::mutex stab_mu;
+    mi355enc_stabilize_t stab_cur = {0, 16, 0, 0}, stab_last = {0, 16, 0, 0};
+    mi355enc_stabilize_info_t stab_last_info = {};
+    bool stab_last_have = false, stab_primed = false;
+    int *d_stab = nullptr, *h_stab = nullptr;
+    size_t stab_bytes = 0;
+    int stab_half = 0, stab_w = 0, stab_h = 0;
     // frame-rate conversion (mi355enc_set_rate_conversion).  rate.mode 0: off, and nothing below is used but last_count.  rate.max_fill is
     // clamped to pipeline_depth.  rate_plan: the rule's state; ingest_begin steps a copy of it (rate_next, with what the step yields: rate_n pictures, their pts
     // and weights) and ingest_end commits it once the pictures are enqueued -- a submit that fails in between has not advanced the plan.  d_keep: one NV12
@@ -395,7 +412,7 @@ int yv12_as_i420(int fmt, const uint8_t *p[3], int st[3]); // YV12 is I420 with 
 // such a picture into the input target with the slot's plan (k_launch_scale's answer)
 struct nv12_pic_t { uint8_t *y, *uv; int stride; };
 int input_nv12(mi355enc_t *h, slot_t *s, nv12_pic_t *c);
-int scale_nv12(const nv12_pic_t *c, const in_target_t *t, const scale_plan_t *pl, hipStream_t up);
+int scale_nv12(mi355enc_t *h, slot_t *s, const nv12_pic_t *c, const in_target_t *t, const scale_plan_t *pl, hipStream_t up);
 // the planes' layout at rows of 16 n bytes, one behind the other from d on (a slot's raw staging buffer): where each lies and its stride -> the number of planes
 int raw_layout(int fmt, int w, int h, const uint8_t *d, const uint8_t *p[3], int st[3], fmt_plane_t pl[3]);
 #pragma GCC visibility pop
@@ -437,6 +454,18 @@ void denoise_free(mi355enc_t *h);
 bool denoise_time_ready(mi355enc_t *h, int stage);           // mi355enc_time_stage 25 .. 28: the value set last is active (27 / 28: with a range above 0)
 int denoise_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // ... and its launch on the main stream: 25 filtering in place (priming where the history is not valid), 26 priming, 27 the search alone, 28 search and compensated filter
 void denoise_time_done(mi355enc_t *h);                       // ... behind the timed launches: the history they left is no stream's, the next picture primes
+// enc_stab.cpp (electronic image stabilisation)
+int stab_latch(mi355enc_t *h, slot_t *s, bool own);          // the value set last becomes the slot's (beside denoise_latch); own: the slot the input goes into -- checked there: ERR_STATE without a geometry, ERR_ARG for an input below 4 range
+// The one place a scale / geometry launch of a picture is enqueued (every submit path and mi355enc_stage_scale end here): with the slot stabilised, the estimate
+// (clear, projection launch, match launch, the record's copy to pinned memory) in front of it on the same stream, and the launch reads the offset the match
+// launch wrote.  An MI355ENC_* code
+int input_scale(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *p0, const uint8_t *p1, const uint8_t *p2, int s0, int s1, int s2, const in_target_t *t, const scale_plan_t *pl, hipStream_t up);
+void stab_collected(mi355enc_t *h, slot_t *s);               // collect(): books what the picture carried as the last picture's
+void stab_free(mi355enc_t *h);
+bool stab_time_ready(mi355enc_t *h, int stage);              // mi355enc_time_stage 29 / 30: the value set last is on, and the handle has a geometry of a size it takes
+int stab_time_prepare(mi355enc_t *h, slot_t *s, ts_ctx_t *x);
+int stab_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // 29 the clear and the projection launch on the raw staging buffer, 30 the match launch
+void stab_time_done(mi355enc_t *h);                          // ... behind the timed launches: the next picture primes
 // enc_hdr.cpp (HDR input)
 // true: the handle tone-maps and this input is not one it takes (a format other than the three 10-bit ones -- fmt -1: an entry point that takes none of them --
 // or an output matrix outside 1, 5, 6, 2): the submit fails with MI355ENC_ERR_ARG before anything is latched

@@ -65,7 +65,9 @@ int jpeg_enqueue(mi355enc_t *h, slot_t *s, const mi355enc_jpeg_info_t *info, hip
         r = k_launch_jpeg(dc, dq, info->hs, info->vs, info->components, h->in_w, h->in_h, c.y, c.uv, c.stride, h->in_h, s->d_jpeg_planar, up);
         const scale_plan_t *pl = scale_plan_for(h, s, up);
         if (!pl) return MI355ENC_ERR_HIP;
-        if (!r) r = scale_nv12(&c, &t, pl, up);
+        if (r) return MI355ENC_ERR_ARG;
+        r = scale_nv12(h, s, &c, &t, pl, up);
+        if (r) return r;
     }
     if (r) return MI355ENC_ERR_ARG;
     HIPCHK(hipGetLastError());

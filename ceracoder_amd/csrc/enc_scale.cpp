@@ -321,6 +321,7 @@ int geometry_apply(mi355enc_t *h, int orient, bool in_set, int in_w, int in_h, c
     else h->sar_w = h->sar_h = in_set ? 1 : 0;
     if (h->sar_w == h->sar_h) h->sar_w = h->sar_h = 0; // square samples: no aspect_ratio_info in the VUI (the headers of an unscaled stream)
     else if (tr) { const int t = h->sar_w; h->sar_w = h->sar_h; h->sar_h = t; } // the samples are turned with the picture
+    stab_free(h); // (the stabiliser's buffers too)
     for (int i = 0; i < NSLOT; i++) { // staging buffers follow the input size (allocated again on first use)
         slot_t *s = &h->slot[i];
         if (s->d_raw) { (void)hipFree(s->d_raw); s->d_raw = nullptr; }
@@ -447,7 +448,8 @@ int mi355enc_stage_scale(mi355enc_t *h, int fmt, const uint8_t *const planes[3],
         if (r) return r;
         const scale_plan_t *pl = scale_plan_for(h, s, h->stream);
         if (!pl) return MI355ENC_ERR_HIP;
-        if (k_launch_scale(fmt, p[0], p[1], p[2], st[0], st[1], st[2], t.y, t.uv, t.W, t.H, pl, h->stream)) return MI355ENC_ERR_ARG;
+        r = input_scale(h, s, fmt, p[0], p[1], p[2], st[0], st[1], st[2], &t, pl, h->stream);
+        if (r) return r;
         HIPCHK(hipGetLastError());
         r = input_finish(h, s, h->stream);
         if (r) return r;

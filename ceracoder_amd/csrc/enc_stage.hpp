@@ -8,6 +8,7 @@
 static inline int stage_enter(mi355enc_t *h) {
     if (h->pending) return MI355ENC_ERR_STATE;
     HIPCHK(hipSetDevice(h->cfg.device_id));
+    for (int i = 0; i < NSLOT; i++) { h->slot[i].stab.range = 0; h->slot[i].stab_done = false; } // (a stage call is no part of the stream: it runs the geometry as set, unstabilised -- DESIGN.md section 26)
     return sync_compute(h);
 }
 // host planes of the coded size -> the slot's source surfaces, on the main stream

@@ -112,6 +112,9 @@ typedef struct {
     mi355enc_adjust_t adj;
     /* temporal noise reduction on the device (mi355enc_set_denoise): denoise-luma, denoise-chroma; stored and forwarded like the picture controls */
     mi355enc_denoise_t dn;
+    /* stabilize (mi355enc_set_stabilize): the margin in input samples per side (0: off; odd values count as the even value below), added
+     * to each of crop-* when the geometry is built -- so a change while playing is a crop change --, and the estimator's range and leak */
+    gint stab, stab_range, stab_leak;
     gint dn_motion; /* denoise-motion: the search range of its motion compensation (mi355enc_set_denoise_motion; section 25), 0: none */
     gint hdr_input, hdr_peak, hdr_target; /* hdr-input (0 off, 16 pq, 18 hlg), hdr-peak-nits, hdr-target-nits: read at the next set_format */
     gint open_rate;           /* 0: conversion off */
@@ -144,7 +147,7 @@ enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME
        PROP_SNAP_LOCATION, PROP_SNAP_INTERVAL, PROP_SNAP_QUALITY, PROP_SNAP_REDUCE, PROP_SNAP_SOURCE,
        PROP_OUTPUT_COLORIMETRY, PROP_RATE_CONVERSION, PROP_OUTPUT_FRAMERATE, PROP_MAX_FILL, PROP_HDR_INPUT, PROP_HDR_PEAK_NITS, PROP_HDR_TARGET_NITS,
        PROP_ADJ_BRIGHTNESS, PROP_ADJ_CONTRAST, PROP_ADJ_HUE, PROP_ADJ_SATURATION, PROP_ADJ_GAMMA, PROP_ADJ_SHARPEN, PROP_ADJ_SHARPEN_THRESHOLD,
-       PROP_DENOISE_LUMA, PROP_DENOISE_CHROMA, PROP_DENOISE_MOTION };
+       PROP_DENOISE_LUMA, PROP_DENOISE_CHROMA, PROP_DENOISE_MOTION, PROP_STABILIZE, PROP_STABILIZE_RANGE, PROP_STABILIZE_LEAK };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
     GST_STATIC_CAPS("video/x-raw, format=(string){ NV12, I420, YUY2, UYVY, Y42B, Y444, YV12, NV21, BGRx, RGBx, xRGB, xBGR, BGRA, RGBA, ARGB, ABGR, BGR, RGB, P010_10LE, I420_10LE, v210, GRAY8 }, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]; "
@@ -246,6 +249,16 @@ static void adjust_forward(GstMi355H264Enc *s) {
     if (s->enc && mi355enc_set_adjust(s->enc, &s->adj) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the picture controls: it keeps its previous ones");
 }
 /* stored noise filter strengths -> the encoder, if one is open (object lock held; the library builds three small tables and stores: no GPU call, any thread) */
+/* what the crop rectangle is built from: crop-* (even), each with the stabiliser's margin on top.  Called with the object lock held */
+static void effective_crop(const GstMi355H264Enc *s, int crop[4]) {
+    for (int i = 0; i < 4; i++) crop[i] = (s->crop[i] & ~1) + (s->stab & ~1);
+}
+/* the stabiliser's setting to the encoder (object lock held): on with a margin; the margin itself is part of the crop and follows on the crop's path */
+static void stabilize_forward(GstMi355H264Enc *s) {
+    const int m = s->stab & ~1;
+    const mi355enc_stabilize_t st = {m ? s->stab_range : 0, s->stab_leak, m, m};
+    if (s->enc && mi355enc_set_stabilize(s->enc, &st) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the stabiliser's setting: it keeps its previous one");
+}
 static void denoise_forward(GstMi355H264Enc *s) {
     if (s->enc && mi355enc_set_denoise(s->enc, &s->dn) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the noise filter's strengths: it keeps its previous ones");
     if (s->enc && mi355enc_set_denoise_motion(s->enc, s->dn_motion) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the noise filter's search range: it keeps its previous one");
@@ -323,6 +336,9 @@ static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *
     case PROP_DENOISE_LUMA: s->dn.luma = g_value_get_int(val); denoise_forward(s); break;
     case PROP_DENOISE_CHROMA: s->dn.chroma = g_value_get_int(val); denoise_forward(s); break;
     case PROP_DENOISE_MOTION: s->dn_motion = g_value_get_int(val); denoise_forward(s); break;
+    case PROP_STABILIZE: s->stab = g_value_get_int(val); break; /* (a crop change: latched in front of the next picture, the setting with it) */
+    case PROP_STABILIZE_RANGE: s->stab_range = g_value_get_int(val); stabilize_forward(s); break;
+    case PROP_STABILIZE_LEAK: s->stab_leak = g_value_get_int(val); stabilize_forward(s); break;
     case PROP_OUTPUT_COLORIMETRY: g_free(s->out_colorimetry); s->out_colorimetry = g_value_dup_string(val); break; /* (read at the next set_format) */
     case PROP_IMG_X: s->img_x = g_value_get_int(val); image_forward(s, FALSE); break;
     case PROP_IMG_Y: s->img_y = g_value_get_int(val); image_forward(s, FALSE); break;
@@ -398,6 +414,9 @@ static void get_property(GObject *obj, guint id, GValue *val, GParamSpec *ps) {
     case PROP_DENOISE_LUMA: g_value_set_int(val, s->dn.luma); break;
     case PROP_DENOISE_CHROMA: g_value_set_int(val, s->dn.chroma); break;
     case PROP_DENOISE_MOTION: g_value_set_int(val, s->dn_motion); break;
+    case PROP_STABILIZE: g_value_set_int(val, s->stab); break;
+    case PROP_STABILIZE_RANGE: g_value_set_int(val, s->stab_range); break;
+    case PROP_STABILIZE_LEAK: g_value_set_int(val, s->stab_leak); break;
     case PROP_OUTPUT_COLORIMETRY: g_value_set_string(val, s->out_colorimetry ? s->out_colorimetry : ""); break;
     case PROP_IMG_X: g_value_set_int(val, s->img_x); break;
     case PROP_IMG_Y: g_value_set_int(val, s->img_y); break;
@@ -692,7 +711,7 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     const gboolean tr = direction_transposes(dir);
     /* the crop rectangle (section 16): all four at 0 is the whole input */
     int crop[4];
-    for (int i = 0; i < 4; i++) crop[i] = s->crop[i] & ~1;
+    effective_crop(s, crop); /* (with the stabiliser's margin: the crop leaves that much room around it) */
     const int crop_w = in_w - crop[0] - crop[1], crop_h = in_h - crop[2] - crop[3];
     const gboolean add_borders = s->add_borders, upscale = s->upscale;
     const guint border = s->border_color;
@@ -802,6 +821,7 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     image_forward(s, TRUE);                 /* ... nor the image layer */
     adjust_forward(s);                      /* ... nor the picture controls */
     denoise_forward(s);                     /* ... nor the noise filter */
+    stabilize_forward(s);                   /* ... nor the stabiliser */
     GST_OBJECT_UNLOCK(s);
     g_mutex_unlock(&s->snap_enc_mu);
     s->max_au = mi355enc_max_au_bytes(e);
@@ -932,7 +952,7 @@ static GstFlowReturn enc_handle_frame(GstVideoEncoder *ve, GstVideoCodecFrame *f
     GST_OBJECT_LOCK(s);
     gboolean turn = effective_direction(s) != s->open_direction;
     int crop[4];
-    for (int i = 0; i < 4; i++) crop[i] = s->crop[i] & ~1;
+    effective_crop(s, crop);
     const gboolean recrop = memcmp(crop, s->open_crop, sizeof crop) != 0;
     const gboolean same_size = s->out_w > 0 && s->out_h > 0; /* (width / height at 0 follow the crop: the coded size changes with it) */
     GST_OBJECT_UNLOCK(s);
@@ -942,6 +962,7 @@ static GstFlowReturn enc_handle_frame(GstVideoEncoder *ve, GstVideoCodecFrame *f
         if (s->open_geom && same_size && mi355enc_set_crop(s->enc, crop[0], crop[2], in_w - crop[0] - crop[1], in_h - crop[2] - crop[3]) == MI355ENC_OK) {
             GST_OBJECT_LOCK(s);
             memcpy(s->open_crop, crop, sizeof crop);
+            stabilize_forward(s); /* (a margin that changed with the crop) */
             GST_OBJECT_UNLOCK(s);
         } else turn = TRUE;
     }
@@ -1257,6 +1278,9 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
     g_object_class_install_property(g, PROP_ADJ_SHARPEN_THRESHOLD, g_param_spec_int("sharpen-threshold", "Sharpen threshold", "with sharpen > 0: detail of at most this many codes is left alone (coring)", 0, 32, 0, F));
     g_object_class_install_property(g, PROP_DENOISE_LUMA, g_param_spec_int("denoise-luma", "Denoise luma", "temporal noise reduction on the GPU, motion-adaptive, in front of the picture controls: the luma noise amplitude in codes that is filtered fully; 0: off", 0, MI355ENC_DENOISE_MAX, 0, F));
     g_object_class_install_property(g, PROP_DENOISE_CHROMA, g_param_spec_int("denoise-chroma", "Denoise chroma", "temporal noise reduction on the GPU: the chroma noise amplitude in codes that is filtered fully; 0: off", 0, MI355ENC_DENOISE_MAX, 0, F));
+    g_object_class_install_property(g, PROP_STABILIZE, g_param_spec_int("stabilize", "Stabilize", "electronic image stabilisation on the GPU: the margin in input samples per side that the crop may move by to follow the camera's shake (added to each of crop-*; odd values count as the even value below); 0: off", 0, MI355ENC_STABILIZE_MARGIN_MAX, 0, F));
+    g_object_class_install_property(g, PROP_STABILIZE_RANGE, g_param_spec_int("stabilize-range", "Stabilize range", "the largest motion between two pictures the stabiliser measures, in input luma samples (the input must be at least four times that in both directions)", 1, MI355ENC_STABILIZE_RANGE_MAX, 16, F));
+    g_object_class_install_property(g, PROP_STABILIZE_LEAK, g_param_spec_int("stabilize-leak", "Stabilize leak", "how fast the stabilised crop returns to its place, in 1/256 per picture; 0: never (a knob, not a tuned value)", 0, 255, 16, F));
     g_object_class_install_property(g, PROP_DENOISE_MOTION, g_param_spec_int("denoise-motion", "Denoise motion", "motion compensation of the temporal noise reduction: per 8 x 8 block the history is searched within this many luma samples; 0: none (the filter lets go where the picture moves)", 0, MI355ENC_DENOISE_MOTION_MAX, 0, F));
     g_object_class_override_property(g, PROP_VIDEO_DIRECTION, "video-direction"); /* GstVideoDirection: identity, 90r, 180, 90l, horiz, vert, ul-lr, ur-ll, auto -- as on videoflip */
     g_object_class_install_property(g, PROP_STATS, g_param_spec_boolean("stats", "Print stats", "Print a JSON line with counters when the encoder closes", FALSE, F));
@@ -1280,6 +1304,7 @@ static void gst_mi355h264enc_init(GstMi355H264Enc *s) {
     mi355enc_adjust_default(&s->adj);
     mi355enc_denoise_default(&s->dn);
     s->dn_motion = 0;
+    s->stab = 0; s->stab_range = 16; s->stab_leak = 16;
     s->rate_mode = 0; s->out_fps_n = 0; s->out_fps_d = 1; s->max_fill = 2; s->open_rate = 0; s->tick = GST_CLOCK_TIME_NONE; s->rate_qh = s->rate_qn = 0;
     s->snap_location = NULL; s->snap_interval = 1000; s->snap_quality = 75; s->snap_reduce = 4; s->snap_source = 0; s->snap_next = GST_CLOCK_TIME_NONE; s->snap_watch = 0;
     g_mutex_init(&s->snap_mu); g_mutex_init(&s->snap_enc_mu); g_cond_init(&s->snap_cv);

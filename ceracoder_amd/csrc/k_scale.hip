@@ -16,6 +16,8 @@
 // clamped into the crop rectangle [lo, hi] of its table, and no byte outside the crop rectangle is fetched (the dwords that straddle its left or right
 // edge go byte by byte).  A target position outside the destination rectangle takes the border colour, in the same full-width store; a tile that
 // lies wholly outside it skips both passes.  Without GEOM the kernel is the downscale as it was, instruction for instruction.
+// GEOM with a.stab (section 26): every table index and the clamp rectangle are displaced by the offset read there -- luma by (ox, oy), chroma columns by ox / 2,
+// chroma rows by oy / 2 (4:2:2 input: oy); weights, reach and LDS room are those of the crop as set, since indices and bounds move together.
 #define DEV_HOST_SCALE static __host__ __device__ __forceinline__
 struct scale_args {
     const uint8_t *p0, *p1, *p2; // NV12: Y, UV; I420: Y, U, V; packed formats: p0 only
@@ -27,6 +29,7 @@ struct scale_args {
     int hmax;                    // intermediate rows the LDS holds
     int tmax_h, tmax_v;          // LDS room for coefficients per output column / row
     scale_plan_t p;
+    const int *stab;             // GEOM: the stabiliser's {ox, oy} for this picture on the device; null: none
 };
 
 // one contiguous byte range of a source row, fetched into LDS
@@ -60,8 +63,10 @@ __global__ __launch_bounds__(256) void scale_kernel(const scale_args a) {
     auto col_of = [&](int e) { const int c = luma ? tx * SCALE_TILE_W + e : tx * (SCALE_TILE_W / 2) + (e >> 1); return c < nout_x ? c : nout_x - 1; };
     auto row_of = [&](int o) { const int r = ty * SCALE_TILE_H + o; return r < nout_y ? r : nout_y - 1; };
     // clamp bounds of the source indices (the crop rectangle), and the destination rectangle in this plane's samples
-    const int xlo = GEOM ? a.p.lo[th] : 0, xhi = GEOM ? a.p.hi[th] : nin_x - 1;
-    const int ylo = GEOM ? a.p.lo[tv] : 0, yhi = GEOM ? a.p.hi[tv] : nin_y - 1;
+    int ofx = 0, ofy = 0; // the stabiliser's displacement in this plane's samples (even luma offsets: the halves are exact)
+    if (GEOM && a.stab) { ofx = luma ? a.stab[0] : a.stab[0] / 2; ofy = luma || FMT >= 2 ? a.stab[1] : a.stab[1] / 2; }
+    const int xlo = GEOM ? a.p.lo[th] + ofx : 0, xhi = GEOM ? a.p.hi[th] + ofx : nin_x - 1;
+    const int ylo = GEOM ? a.p.lo[tv] + ofy : 0, yhi = GEOM ? a.p.hi[tv] + ofy : nin_y - 1;
     const int ddx = !GEOM ? 0 : luma ? a.p.dx : a.p.dx >> 1, ddy = !GEOM ? 0 : luma ? a.p.dy : a.p.dy >> 1;
     const int ndx = !GEOM ? nout_x : luma ? a.p.dw : a.p.dw >> 1, ndy = !GEOM ? nout_y : luma ? a.p.dh : a.p.dh >> 1;
     auto clamp3 = [](int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; };
@@ -80,9 +85,9 @@ __global__ __launch_bounds__(256) void scale_kernel(const scale_args a) {
     uint8_t *raw = (uint8_t *)(hbuf + (size_t)a.hmax * SCALE_TILE_W);
 
     // rows and columns of the source this tile reads
-    const int ya = clamp3(fv[trow(0)], ylo, yhi), yb = clamp3(fv[trow(SCALE_TILE_H - 1)] + ntv - 1, ylo, yhi);
+    const int ya = clamp3(fv[trow(0)] + ofy, ylo, yhi), yb = clamp3(fv[trow(SCALE_TILE_H - 1)] + ofy + ntv - 1, ylo, yhi);
     const int nh = yb - ya + 1;
-    const int xa = clamp3(fh[tcol(0)], xlo, xhi), xb = clamp3(fh[tcol(SCALE_TILE_W - 1)] + nth - 1, xlo, xhi);
+    const int xa = clamp3(fh[tcol(0)] + ofx, xlo, xhi), xb = clamp3(fh[tcol(SCALE_TILE_W - 1)] + ofx + nth - 1, xlo, xhi);
     if (nh > a.hmax) return; // (cannot happen: the host sized the LDS for the largest tile; wave-uniform)
     if (GEOM && (nth > a.tmax_h || ntv > a.tmax_v)) return; // (nor this: mi355enc_set_crop refuses a crop whose tables outgrow the room fixed with the geometry)
 
@@ -108,7 +113,7 @@ __global__ __launch_bounds__(256) void scale_kernel(const scale_args a) {
     // the tile's coefficients into LDS
     for (int i = tid; i < SCALE_TILE_W * nth; i += 256) { const int e = i / nth, k = i - e * nth; cq_h[e * a.tmax_h + k] = qh[(size_t)tcol(e) * nth + k]; }
     for (int i = tid; i < SCALE_TILE_H * ntv; i += 256) { const int o = i / ntv, k = i - o * ntv; cq_v[o * a.tmax_v + k] = qv[(size_t)trow(o) * ntv + k]; }
-    if (tid < SCALE_TILE_W) cf_h[tid] = fh[tcol(tid)];
+    if (tid < SCALE_TILE_W) cf_h[tid] = fh[tcol(tid)] + ofx;
     __syncthreads();
 
     // ---- pass 1: horizontal, SCALE_CHUNK source rows at a time
@@ -150,7 +155,7 @@ __global__ __launch_bounds__(256) void scale_kernel(const scale_args a) {
     const int orow = ty * SCALE_TILE_H + o;
     const int xbyte = tx * SCALE_TILE_W + e4;
     if (orow >= rows_here || xbyte >= a.W) return; // (W is a multiple of 16: a dword is all inside or all outside)
-    const int fo = fv[trow(o)];
+    const int fo = fv[trow(o)] + ofy;
     const int16_t *vq = cq_v + o * a.tmax_v;
     int acc[4] = {0, 0, 0, 0};
     for (int k = 0; k < (any ? ntv : 0); k++) {
@@ -191,10 +196,10 @@ static size_t scale_lds_bytes(int fmt, const scale_plan_t *p, int *rawb, int *hm
 }
 
 int k_launch_scale(int fmt, const uint8_t *p0, const uint8_t *p1, const uint8_t *p2, int s0, int s1, int s2, uint8_t *dy, uint8_t *duv,
-                   int W, int H, const scale_plan_t *plan, hipStream_t s) {
+                   int W, int H, const scale_plan_t *plan, hipStream_t s, const int *stab) {
     if (fmt < 0 || fmt > 3 || !plan) return -1;
     scale_args a;
-    a.p0 = p0; a.p1 = p1; a.p2 = p2; a.s0 = s0; a.s1 = s1; a.s2 = s2; a.dy = dy; a.duv = duv; a.W = W; a.H = H; a.p = *plan;
+    a.p0 = p0; a.p1 = p1; a.p2 = p2; a.s0 = s0; a.s1 = s1; a.s2 = s2; a.dy = dy; a.duv = duv; a.W = W; a.H = H; a.p = *plan; a.stab = stab;
     a.ltiles_x = (W + SCALE_TILE_W - 1) / SCALE_TILE_W;
     a.ltiles = a.ltiles_x * ((H + SCALE_TILE_H - 1) / SCALE_TILE_H);
     const int ctiles = a.ltiles_x * ((H / 2 + SCALE_TILE_H - 1) / SCALE_TILE_H);

@@ -246,7 +246,14 @@ typedef struct {
     int cap_taps[SCALE_TABLES];             /* LDS room for coefficients, fixed when the geometry was set (taps[] changes with the crop) */
 } scale_plan_t;
 int k_launch_scale(int fmt, const uint8_t *p0, const uint8_t *p1, const uint8_t *p2, int s0, int s1, int s2, uint8_t *dy, uint8_t *duv,
-                   int W, int H, const scale_plan_t *plan, hipStream_t s);
+                   int W, int H, const scale_plan_t *plan, hipStream_t s, const int *stab = nullptr); /* stab: with a geometry, {ox, oy} on the device (section 26); null: none */
+/* Electronic image stabilisation (k_stab.hip; the rule: DESIGN.md section 26, stab_host.h).  The projection launch: the luma samples of a w x h picture (first
+ * one at `luma`, `step` = 1 or 2 bytes apart, any address and stride) -> sums: C_0 .. C_3 (w words each), then R_0 .. R_3 (h each); added with atomics, so the
+ * 4 (w + h) words are cleared on the same stream in front of it.  The match launch: votes of the eight projections `cur` against `prev` (range 1 .. 32,
+ * w, h >= 4 range), medians and the trajectory step under bounds {lo_x, hi_x, lo_y, hi_y}; state {Sx, Sy} is read and written, rec gets the record's eight
+ * words (mx, my, votes_x, votes_y, ox, oy, Sx, Sy).  prime: no vote is taken, state and record are zero.  -1: arguments outside that */
+int k_launch_stab_project(const uint8_t *luma, int stride, int step, int w, int h, unsigned *sums, hipStream_t s);
+int k_launch_stab_match(const unsigned *prev, const unsigned *cur, int w, int h, int range, int leak, int prime, const int bounds[4], int *state, int *rec, hipStream_t s);
 void k_launch_pack(const mb_info_t *d_mbi, const int16_t *d_levels, int nmb, int mbw, unsigned *d_off, mb_info_t *h_mbi, int16_t *h_packed,
                    unsigned *h_hdr, const unsigned *d_err, hipStream_t s);
 int k_deblock_diags(int mbw, int mbh);

@@ -36,6 +36,8 @@ STAGE_ME, STAGE_INTER, STAGE_INTRA, STAGE_DEBLOCK, STAGE_SUBPEL, STAGE_CSC_I420,
 STAGE_ADJUST_POINT, STAGE_ADJUST_SHARPEN = 23, 24  # the picture controls set last on slot 0's surfaces: pointwise form, stencil form
 STAGE_DENOISE_SEARCH, STAGE_DENOISE_MC = 27, 28  # ... with motion compensation: the search alone, the search and the compensated filter
 DENOISE_MOTION_MAX = 16
+STAGE_STABILIZE_PROJECT, STAGE_STABILIZE_MATCH = 29, 30  # the stabiliser's launches: clear + projection at the input size, match
+STABILIZE_RANGE_MAX, STABILIZE_MARGIN_MAX = 32, 1024
 STAGE_DENOISE, STAGE_DENOISE_PRIME = 25, 26  # the temporal noise filter set last on slot 0's surfaces and the handle's history: filtering, priming
 STAGE_HDR_P010, STAGE_HDR_I420_10, STAGE_HDR_V210, STAGE_DEEP_P010 = 19, 20, 21, 22  # the tone-mapping launch per format, and the plain P010 launch beside it
 HDR_PQ, HDR_HLG = 16, 18  # mi355enc_set_hdr_input: the transfer's H.264 Table E-4 code point
@@ -72,6 +74,8 @@ EXPORTS = [
     "mi355enc_denoise_default", "mi355enc_denoise_check", "mi355enc_denoise_tables", "mi355enc_set_denoise", "mi355enc_get_denoise", "mi355enc_last_denoise", "mi355enc_stage_denoise",
     "mi355enc_debug_denoise_bytes",
     "mi355enc_set_denoise_motion", "mi355enc_get_denoise_motion", "mi355enc_last_denoise_motion", "mi355enc_denoise_motion_key", "mi355enc_stage_denoise_search", "mi355enc_stage_denoise_mc",
+    "mi355enc_stabilize_default", "mi355enc_stabilize_check", "mi355enc_set_stabilize", "mi355enc_get_stabilize", "mi355enc_last_stabilize", "mi355enc_debug_stabilize_bytes",
+    "mi355enc_stabilize_project", "mi355enc_stabilize_vote", "mi355enc_stabilize_motion", "mi355enc_stabilize_step", "mi355enc_stabilize_probe_project", "mi355enc_stabilize_probe_match",
 ]
 
 
@@ -134,6 +138,22 @@ class Denoise(C.Structure):
 
     def as_dict(self):
         return dict(luma=int(self.luma), chroma=int(self.chroma))
+
+
+class Stabilize(C.Structure):
+    """mi355enc_stabilize_t: search range 0 .. 32 input luma samples (0: off), leak 0 .. 255, how far the crop may move per side (even, 0 .. 1024)"""
+    _fields_ = [("range", C.c_int), ("leak", C.c_int), ("margin_x", C.c_int), ("margin_y", C.c_int)]
+
+    def as_dict(self):
+        return dict(range=int(self.range), leak=int(self.leak), margin_x=int(self.margin_x), margin_y=int(self.margin_y))
+
+
+class StabilizeInfo(C.Structure):
+    """mi355enc_stabilize_info_t: a picture's record -- measured motion, valid votes per axis, the crop's displacement, the trajectory's state (1/256 sample)"""
+    _fields_ = [(n, C.c_int) for n in ("mx", "my", "votes_x", "votes_y", "ox", "oy", "sx", "sy")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
 class ImageLayer(C.Structure):
@@ -285,6 +305,20 @@ def load():
         L.mi355enc_denoise_motion_key.argtypes = [C.c_int] * 4
         L.mi355enc_stage_denoise_search.argtypes = [vp, C.POINTER(Denoise), C.c_int, vp, vp, vp]
         L.mi355enc_stage_denoise_mc.argtypes = [vp, C.POINTER(Denoise), C.c_int] + [vp] * 7
+        L.mi355enc_stabilize_default.restype = None
+        L.mi355enc_stabilize_default.argtypes = [C.POINTER(Stabilize)]
+        L.mi355enc_stabilize_check.argtypes = [C.POINTER(Stabilize)]
+        L.mi355enc_set_stabilize.argtypes = [vp, C.POINTER(Stabilize)]
+        L.mi355enc_get_stabilize.argtypes = [vp, C.POINTER(Stabilize)]
+        L.mi355enc_last_stabilize.argtypes = [vp, C.POINTER(Stabilize), C.POINTER(StabilizeInfo)]
+        L.mi355enc_debug_stabilize_bytes.restype = C.c_size_t
+        L.mi355enc_debug_stabilize_bytes.argtypes = [vp]
+        L.mi355enc_stabilize_project.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+        L.mi355enc_stabilize_vote.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        L.mi355enc_stabilize_motion.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
+        L.mi355enc_stabilize_step.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_int)] * 2
+        L.mi355enc_stabilize_probe_project.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+        L.mi355enc_stabilize_probe_match.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(Stabilize), C.POINTER(C.c_int * 4), C.POINTER(C.c_int * 2), C.c_int, C.POINTER(StabilizeInfo)]
         L.mi355enc_set_quality_metrics.argtypes = [vp, C.c_int]
         L.mi355enc_last_quality.argtypes = [vp, C.POINTER(Quality)]
         L.mi355enc_quality_totals.argtypes = [vp, C.POINTER(Quality)]
@@ -451,6 +485,71 @@ def denoise(d=None, **kw):
     if set(src) - {"luma", "chroma"}:
         raise TypeError("denoise: no parameter %r" % (sorted(set(src) - {"luma", "chroma"}),))
     return Denoise(int(src.get("luma", 0)), int(src.get("chroma", 0)))
+
+
+def stabilize(s=None, **kw):
+    """A Stabilize: off with leak 16, then s's (a Stabilize or a dict) and the keywords' range / leak / margin_x / margin_y on top; margin=m or margin=(mx, my) sets
+    both margins.  stabilize(range=16, margin=32) is the usual way to turn it on.  Not checked here."""
+    src = s.as_dict() if isinstance(s, Stabilize) else dict(s or {})
+    src.update(kw)
+    if "margin" in src:
+        m = src.pop("margin")
+        src["margin_x"], src["margin_y"] = (m, m) if np.isscalar(m) else m
+    if set(src) - {"range", "leak", "margin_x", "margin_y"}:
+        raise TypeError("stabilize: no parameter %r" % (sorted(set(src) - {"range", "leak", "margin_x", "margin_y"}),))
+    return Stabilize(int(src.get("range", 0)), int(src.get("leak", 16)), int(src.get("margin_x", 0)), int(src.get("margin_y", 0)))
+
+
+def stabilize_check(s=None, **kw):
+    """mi355enc_stabilize_check (host only): 0, or the error code"""
+    return load().mi355enc_stabilize_check(C.byref(stabilize(s, **kw)))
+
+
+def _luma_view(luma, step):
+    """(address, stride, w, h) of a 2-D uint8 view whose samples lie `step` bytes apart in their rows"""
+    if luma.dtype != np.uint8 or luma.ndim != 2 or luma.strides[1] != step:
+        raise ValueError("a 2-D uint8 view with samples %d bytes apart" % step)
+    return luma.ctypes.data, int(luma.strides[0]), int(luma.shape[1]), int(luma.shape[0])
+
+
+def stabilize_project(luma):
+    """mi355enc_stabilize_project (host only): the band sums of a luma plane -- a 2-D uint8 view, samples 1 or 2 bytes apart, any row stride -> (C (4, w), R (4, h)) uint32"""
+    step = int(luma.strides[1])
+    addr, stride, w, h = _luma_view(luma, step)
+    sums = np.zeros(4 * (w + h), np.uint32)
+    r = load().mi355enc_stabilize_project(addr, stride, step, w, h, _p(sums))
+    if r:
+        raise EncoderError("mi355enc_stabilize_project: %d" % r)
+    return sums[:4 * w].reshape(4, w), sums[4 * w:].reshape(4, h)
+
+
+def stabilize_vote(p, q, rng):
+    """mi355enc_stabilize_vote (host only): (valid, d) of projection p against the previous picture's q"""
+    p, q = np.ascontiguousarray(p, np.uint32), np.ascontiguousarray(q, np.uint32)
+    d = C.c_int(0)
+    r = load().mi355enc_stabilize_vote(_p(p), _p(q), int(p.size), int(rng), C.byref(d))
+    if r < 0 or p.size != q.size:
+        raise EncoderError("mi355enc_stabilize_vote: %d" % r)
+    return bool(r), int(d.value)
+
+
+def stabilize_motion(votes):
+    """mi355enc_stabilize_motion (host only): the lower median of the valid votes, 0 with none"""
+    v = (C.c_int * max(1, len(votes)))(*[int(x) for x in votes])
+    m = C.c_int(0)
+    r = load().mi355enc_stabilize_motion(v, len(votes), C.byref(m))
+    if r:
+        raise EncoderError("mi355enc_stabilize_motion: %d" % r)
+    return int(m.value)
+
+
+def stabilize_step(S, m, leak, lo, hi):
+    """mi355enc_stabilize_step (host only): one trajectory step of an axis -> (S, o)"""
+    s_out, o = C.c_int(0), C.c_int(0)
+    r = load().mi355enc_stabilize_step(int(S), int(m), int(leak), int(lo), int(hi), C.byref(s_out), C.byref(o))
+    if r:
+        raise EncoderError("mi355enc_stabilize_step(%d, %d, %d, %d, %d): %d" % (S, m, leak, lo, hi, r))
+    return int(s_out.value), int(o.value)
 
 
 def denoise_check(d=None, **kw):
@@ -858,7 +957,7 @@ class Encoder:
     (bitrate in bits/s as written through `bps`, key-int-max -> gop)."""
 
     def __init__(self, width, height, fps=60, gop=60, bitrate_bps=6_000_000, device_id=0, fixed_qp=-1, me_range=16,
-                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False, input_size=None, colorimetry=None, orientation=None, geometry=None, input_colorimetry=None, rate=None, hdr_input=None, adjust=None, denoise=None):
+                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False, input_size=None, colorimetry=None, orientation=None, geometry=None, input_colorimetry=None, rate=None, hdr_input=None, adjust=None, denoise=None, stabilize=None):
         self.L = load()
         cfg = Cfg()
         self.L.mi355enc_default_cfg(C.byref(cfg), width, height, fps, fps_den)
@@ -916,6 +1015,12 @@ class Encoder:
                 denoise = denoise.as_dict() if isinstance(denoise, Denoise) else dict(denoise)
                 self.set_denoise_motion(denoise.pop("motion", 0))
                 self.set_denoise(denoise)
+            except EncoderError:
+                self.close()
+                raise
+        if stabilize is not None:  # dict(range=, leak=, margin=) or a Stabilize: the crop of `geometry` follows the camera's shake from the first picture on
+            try:
+                self.set_stabilize(stabilize)
             except EncoderError:
                 self.close()
                 raise
@@ -1035,6 +1140,44 @@ class Encoder:
         ptr = lambda a: None if a is None else _p(a)
         self._chk(self.L.mi355enc_stage_denoise(self.h, C.byref(st), ptr(hin[0]), ptr(hin[1]), _p(y), _p(uv), ptr(hy), ptr(huv)), "stage_denoise")
         return y, uv, hy, huv
+
+    def set_stabilize(self, s=None, **kw):
+        """electronic image stabilisation from the next submitted picture on (None: off); callable at any time from any thread"""
+        self._chk(self.L.mi355enc_set_stabilize(self.h, C.byref(stabilize(s, **kw))), "set_stabilize")
+
+    def get_stabilize(self):
+        st = Stabilize()
+        self._chk(self.L.mi355enc_get_stabilize(self.h, C.byref(st)), "get_stabilize")
+        return st.as_dict()
+
+    def last_stabilize(self):
+        """(setting, record) of the last collected picture, as dicts; an unstabilised picture's record is zeros"""
+        st, info = Stabilize(), StabilizeInfo()
+        self._chk(self.L.mi355enc_last_stabilize(self.h, C.byref(st), C.byref(info)), "last_stabilize")
+        return st.as_dict(), info.as_dict()
+
+    def debug_stabilize_bytes(self):
+        return int(self.L.mi355enc_debug_stabilize_bytes(self.h))
+
+    def stabilize_probe_project(self, luma):
+        """the projection launch alone on a host luma plane (a 2-D uint8 view, samples 1 or 2 bytes apart, any address and row stride) -> (C (4, w), R (4, h))"""
+        step = int(luma.strides[1])
+        addr, stride, w, h = _luma_view(luma, step)
+        sums = np.zeros(4 * (w + h), np.uint32)
+        self._chk(self.L.mi355enc_stabilize_probe_project(self.h, addr, stride, step, w, h, _p(sums)), "stabilize_probe_project")
+        return sums[:4 * w].reshape(4, w), sums[4 * w:].reshape(4, h)
+
+    def stabilize_probe_match(self, prev, cur, s, bounds, state=(0, 0), prime=False):
+        """the match launch alone: prev, cur = (C (4, w), R (4, h)) of the previous and the current picture, s the setting, bounds (lo_x, hi_x, lo_y, hi_y),
+        state (Sx, Sy) going in -> the record as a dict"""
+        w, h = int(cur[0].shape[1]), int(cur[1].shape[1])
+        flat = [np.ascontiguousarray(np.concatenate([np.asarray(c, np.uint32).ravel(), np.asarray(r, np.uint32).ravel()])) for c, r in (prev, cur)]
+        if flat[0].size != 4 * (w + h) or flat[1].size != 4 * (w + h):
+            raise ValueError("sums of one size")
+        info = StabilizeInfo()
+        self._chk(self.L.mi355enc_stabilize_probe_match(self.h, _p(flat[0]), _p(flat[1]), w, h, C.byref(stabilize(s)), C.byref((C.c_int * 4)(*[int(v) for v in bounds])),
+                                                        C.byref((C.c_int * 2)(*[int(v) for v in state])), int(bool(prime)), C.byref(info)), "stabilize_probe_match")
+        return info.as_dict()
 
     def debug_denoise_bytes(self):
         return int(self.L.mi355enc_debug_denoise_bytes(self.h))

@@ -375,6 +375,55 @@ int mi355enc_stage_denoise_search(mi355enc_t *h, const mi355enc_denoise_t *d, in
  * ran (range 0, or nothing is filtered) */
 int mi355enc_stage_denoise_mc(mi355enc_t *h, const mi355enc_denoise_t *d, int range, const uint16_t *hist_y, const uint16_t *hist_uv, uint8_t *y, uint8_t *uv,
                               uint16_t *hist_y_out, uint16_t *hist_uv_out, uint32_t *vec_out);
+/* Electronic image stabilisation: the crop rectangle of the input geometry follows the camera's shake, decided per picture on the
+ * device from the picture itself; off (range 0) by default, and off nothing is allocated or launched.  All integers.
+ *   measured on  the luma of the submitted picture at the input size in_w x in_h (what the geometry launch reads: after conversion / tone map / JPEG decode,
+ *                every second byte of YUY2 / UYVY), the whole picture, not only the crop
+ *   projections  four horizontal bands k: rows [k in_h / 4, (k + 1) in_h / 4) give column sums C_k[x]; four vertical bands likewise give row sums R_k[y]
+ *   vote         of a projection p (length n) against the previous picture's q: cost(d) = sum over x in [range, n - range) of |p[x] - q[x - d]| for
+ *                d in -range .. range; the d of the smallest cost, valid only if that minimum is unique and |d| < range
+ *   motion       mx: the lower median of the valid column-band votes (sorted v[(count - 1) / 2]; 0 with none); my likewise of the row bands
+ *   trajectory   per axis, S in 1/256 sample: S = ((S (256 - leak)) >> 8) + 256 m (floor), S = clip(S, 256 lo, 256 hi), o = clip(2 ((S + 256) >> 9), lo, hi)
+ *                with lo = -min(margin, crop origin), hi = min(margin, input - crop origin - crop size), both even towards zero
+ *   priming      the first picture after off -> on (and after stages 29 / 30 of mi355enc_time_stage): m = 0, S = 0, o = 0
+ *   the offset   the geometry launch uses the tables of the crop as set; every tap index and the clamp rectangle are displaced by (ox, oy) (chroma columns
+ *                ox / 2, 4:2:0 chroma rows oy / 2, 4:2:2 chroma rows oy)
+ * Needs an input geometry (otherwise a submit answers MI355ENC_ERR_STATE) and in_w, in_h >= 4 range (MI355ENC_ERR_ARG).  With it on, mi355enc_submit_device
+ * reads the whole submitted luma plane, not only the crop rectangle.  The setters may be called at any time from any thread and make no GPU call; the value is
+ * latched per input picture.  The single-stage entry points run the geometry as set, unstabilised. */
+#define MI355ENC_STABILIZE_RANGE_MAX 32
+#define MI355ENC_STABILIZE_MARGIN_MAX 1024
+typedef struct {
+    int range;              /* search range in input luma samples, 0 .. 32; 0: off */
+    int leak;               /* 0 .. 255: how fast the trajectory returns to the crop as set (0: never) */
+    int margin_x, margin_y; /* how far the crop may move per side, even, 0 .. 1024 */
+} mi355enc_stabilize_t;
+typedef struct {
+    int mx, my;             /* measured motion against the previous measured picture */
+    int votes_x, votes_y;   /* valid votes per axis, 0 .. 4 */
+    int ox, oy;             /* the crop's displacement in input luma samples (pre-orientation) */
+    int sx, sy;             /* the trajectory's state, 1/256 sample */
+} mi355enc_stabilize_info_t;
+void mi355enc_stabilize_default(mi355enc_stabilize_t *s); /* off: {0, 16, 0, 0} */
+int mi355enc_stabilize_check(const mi355enc_stabilize_t *s); /* host only: MI355ENC_OK or MI355ENC_ERR_ARG */
+int mi355enc_set_stabilize(mi355enc_t *h, const mi355enc_stabilize_t *s); /* NULL: off */
+int mi355enc_get_stabilize(const mi355enc_t *h, mi355enc_stabilize_t *s);
+/* of the last collected picture (either pointer may be NULL); MI355ENC_ERR_STATE before the first collect.  An unstabilised picture reports zeros */
+int mi355enc_last_stabilize(mi355enc_t *h, mi355enc_stabilize_t *s, mi355enc_stabilize_info_t *info);
+size_t mi355enc_debug_stabilize_bytes(const mi355enc_t *h); /* device bytes of the stabiliser: 0 until the first stabilised picture */
+/* host only, the rule piece by piece.  project: a luma plane (first sample at `luma`, samples `step` = 1 or 2 bytes apart) -> sums: C_0 .. C_3 (w each), then
+ * R_0 .. R_3 (h each).  vote: 1 valid / 0 no vote (*d: the first d of the smallest cost either way), n >= 4 range, range >= 1.  motion: the lower median of
+ * `count` (0 .. 4) valid votes.  step: one trajectory step of an axis */
+int mi355enc_stabilize_project(const uint8_t *luma, int stride, int step, int w, int h, uint32_t *sums);
+int mi355enc_stabilize_vote(const uint32_t *p, const uint32_t *q, int n, int range, int *d);
+int mi355enc_stabilize_motion(const int *votes, int count, int *m);
+int mi355enc_stabilize_step(int S, int m, int leak, int lo, int hi, int *S_out, int *o);
+/* the two launches alone (tests), in the frame of the single-stage entry points: MI355ENC_ERR_ARG without a handle, MI355ENC_ERR_STATE with pictures in flight.
+ * probe_project: a host luma plane as above -> the 4 (w + h) sums.  probe_match: previous and current sums of a w x h picture from host arrays, the setting's
+ * range and leak, bounds {lo_x, hi_x, lo_y, hi_y}, the state {Sx, Sy} going in, prime -> the record */
+int mi355enc_stabilize_probe_project(mi355enc_t *h, const uint8_t *luma, int stride, int step, int w, int ht, uint32_t *sums);
+int mi355enc_stabilize_probe_match(mi355enc_t *h, const uint32_t *prev, const uint32_t *cur, int w, int ht, const mi355enc_stabilize_t *s, const int bounds[4],
+                                   const int state[2], int prime, mi355enc_stabilize_info_t *info);
 /* like mi355enc_submit, from host memory in `fmt`; planes[]/strides[]: as many entries as the format has planes */
 int mi355enc_submit_fmt(mi355enc_t *h, int fmt, const uint8_t *const planes[3], const int strides[3], int64_t pts, int force_idr);
 /* conversion stage alone (tests): writes the coded-size NV12 surfaces (16*mbw x 16*mbh luma, then interleaved chroma) */
@@ -757,6 +806,9 @@ int mi355enc_stage_deblock(mi355enc_t *h, uint8_t *rec_y, uint8_t *rec_uv, const
  * history invalid: the next picture submitted primes.
  * 27 / 28 its motion-compensated form with the range set last (mi355enc_set_denoise_motion; MI355ENC_ERR_STATE when that is 0 or the filter is off): 27 the
  * search alone, 28 the search and the compensated filter.  They leave the history invalid likewise.
+ * 29 / 30 the stabiliser's launches (mi355enc_set_stabilize; MI355ENC_ERR_STATE when it is off or the handle has no geometry): 29 the projection launch with
+ * its clear at the handle's input size on slot 0's raw staging buffer, 30 the match launch on whatever the projection buffers hold.  Both leave the
+ * trajectory unprimed: the next picture submitted primes.
  * Uses whatever the handle's surfaces currently hold.  Returns average ms per launch. */
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms);
 
