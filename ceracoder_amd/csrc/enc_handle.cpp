@@ -347,6 +347,7 @@ void mi355enc_close(mi355enc_t *h) {
     adjust_free(h);
     denoise_free(h);
     stab_free(h);
+    warp_close(h);
     for (int k = 0; k < NSET; k++) {
         if (h->d_surf[k]) (void)hipFree(h->d_surf[k]);
         for (int i = 0; i < 3; i++) if (h->d_imv[k][i]) (void)hipFree(h->d_imv[k][i]);

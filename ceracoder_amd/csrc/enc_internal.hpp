@@ -14,6 +14,7 @@
 //   enc_adjust.cpp    picture controls: setter, latch, the two launch forms and the scratch plane, its stage entry point
 //   enc_denoise.cpp   temporal noise reduction: setter, latch, the launch and the handle's history, its stage entry point
 //   enc_stab.cpp      electronic image stabilisation: setter, latch, the estimate in front of every scale launch, its probes and timed stages
+//   enc_warp.cpp      lens, roll and keystone correction: setters, latch, the mesh's way to the device, the launch and the scratch pair, its stage entry point
 //   enc_rate.cpp      frame-rate conversion: setter, the plan's step and commit per submit, keep buffer, mix / keep / repeat launches, its stage entry point
 //   enc_hdr.cpp       HDR input: setter, the parameter block on the host and on the device, the tone-mapping conversion launch
 //   enc_quality.cpp   quality metrics: setter, the accumulator and result blocks, enqueue / collect, the stage launch
@@ -43,6 +44,7 @@
 #include "adjust_host.h"
 #include "denoise_host.h"
 #include "stab_host.h"
+#include "warp_host.h"
 #include "enc_plan.hpp"
 #include "enc_sync.hpp"
 
@@ -138,6 +140,9 @@ struct slot_t {
     // image stabilisation: what submit latched for this picture (stab.range 0: off), and whether the estimate ran for it (its record then lies in the handle's
     // pinned block at the slot's index once the picture is collected)
     mi355enc_stabilize_t stab; bool stab_done;
+    // the warp: what submit latched for this picture (warp_on false: nothing; warp_gen: the count of sets its mesh belongs to); warp_send: the slot's pinned copy
+    // holds that mesh and it travels in front of the launch; applied once, to the input's own slot, first in ingest_end
+    bool warp_on, warp_send; mi355enc_warp_t warp; unsigned warp_gen;
 };
 
 struct mi355enc {
@@ -272,6 +277,21 @@ struct mi355enc {
     int *d_stab = nullptr, *h_stab = nullptr;
     size_t stab_bytes = 0;
     int stab_half = 0, stab_w = 0, stab_h = 0;
+    // lens, roll and keystone correction (mi355enc_set_warp / mi355enc_set_warp_mesh): what the control thread set last (under warp_mu: the
+    // setting, its mesh of the coded visible size on the heap, the count of sets that turned it on; submit latches it per input picture) and what the last
+    // collected picture carried.  Allocated by the first warped picture: the scratch pair d_warp_y / d_warp_uv (the launch writes it, then the slot and the handle
+    // exchange planes), the mesh on the device and one pinned copy per slot (h_warp_mesh); warp_sent: the generation d_warp_mesh holds once the upload stream
+    // has come that far (0: none).  Touched by the submitting thread only, apart from what warp_mu guards.
+    std::mutex warp_mu;
+    bool warp_on = false;
+    mi355enc_warp_t warp_cur = {};
+    int32_t *warp_mesh = nullptr;
+    unsigned warp_gen = 0, warp_sent = 0, warp_last_gen = 0;
+    bool warp_last_have = false;
+    uint8_t *d_warp_y = nullptr, *d_warp_uv = nullptr;
+    int32_t *d_warp_mesh = nullptr, *h_warp_mesh = nullptr;
+    size_t warp_bytes = 0;
+    bool warp_staging = true; // (mi355enc_debug_warp_staging: false -- every workgroup of the launch takes the direct form)
     // frame-rate conversion (mi355enc_set_rate_conversion).  rate.mode 0: off, and nothing below is used but last_count.  rate.max_fill is
     // clamped to pipeline_depth.  rate_plan: the rule's state; ingest_begin steps a copy of it (rate_next, with what the step yields: rate_n pictures, their pts
     // and weights) and ingest_end commits it once the pictures are enqueued -- a submit that fails in between has not advanced the plan.  d_keep: one NV12
@@ -466,6 +486,15 @@ bool stab_time_ready(mi355enc_t *h, int stage);              // mi355enc_time_st
 int stab_time_prepare(mi355enc_t *h, slot_t *s, ts_ctx_t *x);
 int stab_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // 29 the clear and the projection launch on the raw staging buffer, 30 the match launch
 void stab_time_done(mi355enc_t *h);                          // ... behind the timed launches: the next picture primes
+// enc_warp.cpp (lens, roll and keystone correction)
+int warp_latch(mi355enc_t *h, slot_t *s, bool own);          // the value set last becomes the slot's (beside stab_latch); own: the slot the input goes into, which also takes the mesh where it is a new one
+int warp_draw(mi355enc_t *h, slot_t *s, hipStream_t st);     // the slot's warp on its coded surfaces, behind everything enqueued on st so far (a new mesh travels in front of it); nothing with none
+void warp_collected(mi355enc_t *h, slot_t *s);               // collect(): books the generation the picture carried as the last picture's
+void warp_close(mi355enc_t *h);
+bool warp_time_ready(mi355enc_t *h, int stage);              // mi355enc_time_stage 31: the warp is on
+int warp_time_prepare(mi355enc_t *h, slot_t *s, ts_ctx_t *x);
+int warp_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x);
+void warp_time_done(mi355enc_t *h);
 // enc_hdr.cpp (HDR input)
 // true: the handle tone-maps and this input is not one it takes (a format other than the three 10-bit ones -- fmt -1: an entry point that takes none of them --
 // or an output matrix outside 1, 5, 6, 2): the submit fails with MI355ENC_ERR_ARG before anything is latched

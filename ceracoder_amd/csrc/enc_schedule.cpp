@@ -541,6 +541,7 @@ int mi355enc_collect(mi355enc_t *h, uint8_t *out, size_t out_cap, size_t *out_le
     adjust_collected(h, s);
     denoise_collected(h, s);
     stab_collected(h, s);
+    warp_collected(h, s);
     h->tail = (h->tail + 1) % NSLOT; h->pending--;
     return MI355ENC_OK;
 }

@@ -115,6 +115,10 @@ typedef struct {
     /* stabilize (mi355enc_set_stabilize): the margin in input samples per side (0: off; odd values count as the even value below), added
      * to each of crop-* when the geometry is built -- so a change while playing is a crop change --, and the estimator's range and leak */
     gint stab, stab_range, stab_leak;
+    /* lens, roll and keystone correction (mi355enc_set_warp): lens-k1, lens-k2, lens-zoom, roll (degrees), keystone-h, keystone-v as the
+     * doubles they were set to, warp-filter (0 bilinear, 1 bicubic); all neutral: off.  Forwarded like the picture controls; the fill is border-color */
+    gdouble warp_k1, warp_k2, warp_zoom, warp_roll, warp_kh, warp_kv;
+    gint warp_filter;
     gint dn_motion; /* denoise-motion: the search range of its motion compensation (mi355enc_set_denoise_motion; section 25), 0: none */
     gint hdr_input, hdr_peak, hdr_target; /* hdr-input (0 off, 16 pq, 18 hlg), hdr-peak-nits, hdr-target-nits: read at the next set_format */
     gint open_rate;           /* 0: conversion off */
@@ -147,7 +151,8 @@ enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME
        PROP_SNAP_LOCATION, PROP_SNAP_INTERVAL, PROP_SNAP_QUALITY, PROP_SNAP_REDUCE, PROP_SNAP_SOURCE,
        PROP_OUTPUT_COLORIMETRY, PROP_RATE_CONVERSION, PROP_OUTPUT_FRAMERATE, PROP_MAX_FILL, PROP_HDR_INPUT, PROP_HDR_PEAK_NITS, PROP_HDR_TARGET_NITS,
        PROP_ADJ_BRIGHTNESS, PROP_ADJ_CONTRAST, PROP_ADJ_HUE, PROP_ADJ_SATURATION, PROP_ADJ_GAMMA, PROP_ADJ_SHARPEN, PROP_ADJ_SHARPEN_THRESHOLD,
-       PROP_DENOISE_LUMA, PROP_DENOISE_CHROMA, PROP_DENOISE_MOTION, PROP_STABILIZE, PROP_STABILIZE_RANGE, PROP_STABILIZE_LEAK };
+       PROP_DENOISE_LUMA, PROP_DENOISE_CHROMA, PROP_DENOISE_MOTION, PROP_STABILIZE, PROP_STABILIZE_RANGE, PROP_STABILIZE_LEAK,
+       PROP_LENS_K1, PROP_LENS_K2, PROP_LENS_ZOOM, PROP_ROLL, PROP_KEYSTONE_H, PROP_KEYSTONE_V, PROP_WARP_FILTER };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
     GST_STATIC_CAPS("video/x-raw, format=(string){ NV12, I420, YUY2, UYVY, Y42B, Y444, YV12, NV21, BGRx, RGBx, xRGB, xBGR, BGRA, RGBA, ARGB, ABGR, BGR, RGB, P010_10LE, I420_10LE, v210, GRAY8 }, width=(int)[16,8192], height=(int)[16,8192], framerate=(fraction)[0/1,MAX]; "
@@ -161,6 +166,12 @@ static GType rate_conversion_type(void) {
     static const GEnumValue v[] = {{0, "Off: every input picture is coded", "off"}, {1, "Drop or repeat pictures to the output ticks", "hold"},
                                    {2, "Blend neighbouring pictures at the output ticks' instants", "blend"}, {0, NULL, NULL}};
     if (!t) t = g_enum_register_static("GstMi355H264EncRateConversion", v);
+    return t;
+}
+static GType warp_filter_type(void) {
+    static GType t = 0;
+    static const GEnumValue v[] = {{0, "Two taps per axis", "bilinear"}, {1, "Four taps per axis (Catmull-Rom)", "bicubic"}, {0, NULL, NULL}};
+    if (!t) t = g_enum_register_static("GstMi355H264EncWarpFilter", v);
     return t;
 }
 static GType hdr_input_type(void) { /* (the values are the transfer's H.264 Table E-4 code points: what mi355enc_set_hdr_input takes) */
@@ -259,6 +270,18 @@ static void stabilize_forward(GstMi355H264Enc *s) {
     const mi355enc_stabilize_t st = {m ? s->stab_range : 0, s->stab_leak, m, m};
     if (s->enc && mi355enc_set_stabilize(s->enc, &st) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the stabiliser's setting: it keeps its previous one");
 }
+/* the warp's properties to the encoder (object lock held; the library builds a mesh of a few thousand nodes and stores: no GPU call, any thread): doubles to
+ * Q16 by lround, the roll through libm, the fill from border-color; all neutral: off.  Every forward that turns it on is a new mesh in front of the next picture */
+static void warp_forward(GstMi355H264Enc *s) {
+    if (!s->enc) return;
+    const double a = s->warp_roll * G_PI / 180.0;
+    const mi355enc_warp_params_t p = {(int)lround(s->warp_k1 * 65536.0), (int)lround(s->warp_k2 * 65536.0), (int)lround(s->warp_zoom * 65536.0),
+                                      (int)lround(cos(a) * 65536.0), (int)lround(sin(a) * 65536.0), (int)lround(s->warp_kh * 65536.0), (int)lround(s->warp_kv * 65536.0)};
+    const mi355enc_warp_t w = {s->warp_filter, {(uint8_t)(s->border_color >> 16), (uint8_t)(s->border_color >> 8), (uint8_t)s->border_color}};
+    const gboolean neutral = !p.k1 && !p.k2 && p.zoom == 65536 && p.cos == 65536 && !p.sin && !p.kh && !p.kv;
+    if (mi355enc_set_warp(s->enc, neutral ? NULL : &w, neutral ? NULL : &p) != MI355ENC_OK)
+        GST_WARNING_OBJECT(s, "the encoder refused the lens / roll / keystone values (the picture would leave the mesh's range): it keeps its previous ones");
+}
 static void denoise_forward(GstMi355H264Enc *s) {
     if (s->enc && mi355enc_set_denoise(s->enc, &s->dn) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the noise filter's strengths: it keeps its previous ones");
     if (s->enc && mi355enc_set_denoise_motion(s->enc, s->dn_motion) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the noise filter's search range: it keeps its previous one");
@@ -339,6 +362,13 @@ static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *
     case PROP_STABILIZE: s->stab = g_value_get_int(val); break; /* (a crop change: latched in front of the next picture, the setting with it) */
     case PROP_STABILIZE_RANGE: s->stab_range = g_value_get_int(val); stabilize_forward(s); break;
     case PROP_STABILIZE_LEAK: s->stab_leak = g_value_get_int(val); stabilize_forward(s); break;
+    case PROP_LENS_K1: s->warp_k1 = g_value_get_double(val); warp_forward(s); break;
+    case PROP_LENS_K2: s->warp_k2 = g_value_get_double(val); warp_forward(s); break;
+    case PROP_LENS_ZOOM: s->warp_zoom = g_value_get_double(val); warp_forward(s); break;
+    case PROP_ROLL: s->warp_roll = g_value_get_double(val); warp_forward(s); break;
+    case PROP_KEYSTONE_H: s->warp_kh = g_value_get_double(val); warp_forward(s); break;
+    case PROP_KEYSTONE_V: s->warp_kv = g_value_get_double(val); warp_forward(s); break;
+    case PROP_WARP_FILTER: s->warp_filter = g_value_get_enum(val); warp_forward(s); break;
     case PROP_OUTPUT_COLORIMETRY: g_free(s->out_colorimetry); s->out_colorimetry = g_value_dup_string(val); break; /* (read at the next set_format) */
     case PROP_IMG_X: s->img_x = g_value_get_int(val); image_forward(s, FALSE); break;
     case PROP_IMG_Y: s->img_y = g_value_get_int(val); image_forward(s, FALSE); break;
@@ -417,6 +447,13 @@ static void get_property(GObject *obj, guint id, GValue *val, GParamSpec *ps) {
     case PROP_STABILIZE: g_value_set_int(val, s->stab); break;
     case PROP_STABILIZE_RANGE: g_value_set_int(val, s->stab_range); break;
     case PROP_STABILIZE_LEAK: g_value_set_int(val, s->stab_leak); break;
+    case PROP_LENS_K1: g_value_set_double(val, s->warp_k1); break;
+    case PROP_LENS_K2: g_value_set_double(val, s->warp_k2); break;
+    case PROP_LENS_ZOOM: g_value_set_double(val, s->warp_zoom); break;
+    case PROP_ROLL: g_value_set_double(val, s->warp_roll); break;
+    case PROP_KEYSTONE_H: g_value_set_double(val, s->warp_kh); break;
+    case PROP_KEYSTONE_V: g_value_set_double(val, s->warp_kv); break;
+    case PROP_WARP_FILTER: g_value_set_enum(val, s->warp_filter); break;
     case PROP_OUTPUT_COLORIMETRY: g_value_set_string(val, s->out_colorimetry ? s->out_colorimetry : ""); break;
     case PROP_IMG_X: g_value_set_int(val, s->img_x); break;
     case PROP_IMG_Y: g_value_set_int(val, s->img_y); break;
@@ -822,6 +859,7 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     adjust_forward(s);                      /* ... nor the picture controls */
     denoise_forward(s);                     /* ... nor the noise filter */
     stabilize_forward(s);                   /* ... nor the stabiliser */
+    warp_forward(s);                        /* ... nor the warp */
     GST_OBJECT_UNLOCK(s);
     g_mutex_unlock(&s->snap_enc_mu);
     s->max_au = mi355enc_max_au_bytes(e);
@@ -1280,6 +1318,13 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
     g_object_class_install_property(g, PROP_DENOISE_CHROMA, g_param_spec_int("denoise-chroma", "Denoise chroma", "temporal noise reduction on the GPU: the chroma noise amplitude in codes that is filtered fully; 0: off", 0, MI355ENC_DENOISE_MAX, 0, F));
     g_object_class_install_property(g, PROP_STABILIZE, g_param_spec_int("stabilize", "Stabilize", "electronic image stabilisation on the GPU: the margin in input samples per side that the crop may move by to follow the camera's shake (added to each of crop-*; odd values count as the even value below); 0: off", 0, MI355ENC_STABILIZE_MARGIN_MAX, 0, F));
     g_object_class_install_property(g, PROP_STABILIZE_RANGE, g_param_spec_int("stabilize-range", "Stabilize range", "the largest motion between two pictures the stabiliser measures, in input luma samples (the input must be at least four times that in both directions)", 1, MI355ENC_STABILIZE_RANGE_MAX, 16, F));
+    g_object_class_install_property(g, PROP_LENS_K1, g_param_spec_double("lens-k1", "Lens k1", "lens correction on the GPU (DESIGN.md section 27): the radial term in r^2, r = 1 at the picture's corner; negative straightens a barrel", -1.0, 1.0, 0.0, F));
+    g_object_class_install_property(g, PROP_LENS_K2, g_param_spec_double("lens-k2", "Lens k2", "lens correction on the GPU: the radial term in r^4", -1.0, 1.0, 0.0, F));
+    g_object_class_install_property(g, PROP_LENS_ZOOM, g_param_spec_double("lens-zoom", "Lens zoom", "how far out the corrected picture reads its source: below 1 magnifies (and hides the fill), above 1 shrinks", 0.25, 4.0, 1.0, F));
+    g_object_class_install_property(g, PROP_ROLL, g_param_spec_double("roll", "Roll", "rotation about the picture's centre in degrees, on the GPU (a horizon that is off)", -180.0, 180.0, 0.0, F));
+    g_object_class_install_property(g, PROP_KEYSTONE_H, g_param_spec_double("keystone-h", "Keystone horizontal", "perspective correction on the GPU: how much the picture's scale changes from its left to its right edge", -0.5, 0.5, 0.0, F));
+    g_object_class_install_property(g, PROP_KEYSTONE_V, g_param_spec_double("keystone-v", "Keystone vertical", "perspective correction on the GPU: converging verticals", -0.5, 0.5, 0.0, F));
+    g_object_class_install_property(g, PROP_WARP_FILTER, g_param_spec_enum("warp-filter", "Warp filter", "the resampling filter of lens-*, roll and keystone-*; samples whose source lies outside the picture take border-color", warp_filter_type(), 1, F));
     g_object_class_install_property(g, PROP_STABILIZE_LEAK, g_param_spec_int("stabilize-leak", "Stabilize leak", "how fast the stabilised crop returns to its place, in 1/256 per picture; 0: never (a knob, not a tuned value)", 0, 255, 16, F));
     g_object_class_install_property(g, PROP_DENOISE_MOTION, g_param_spec_int("denoise-motion", "Denoise motion", "motion compensation of the temporal noise reduction: per 8 x 8 block the history is searched within this many luma samples; 0: none (the filter lets go where the picture moves)", 0, MI355ENC_DENOISE_MOTION_MAX, 0, F));
     g_object_class_override_property(g, PROP_VIDEO_DIRECTION, "video-direction"); /* GstVideoDirection: identity, 90r, 180, 90l, horiz, vert, ul-lr, ur-ll, auto -- as on videoflip */
@@ -1305,6 +1350,7 @@ static void gst_mi355h264enc_init(GstMi355H264Enc *s) {
     mi355enc_denoise_default(&s->dn);
     s->dn_motion = 0;
     s->stab = 0; s->stab_range = 16; s->stab_leak = 16;
+    s->warp_k1 = s->warp_k2 = s->warp_roll = s->warp_kh = s->warp_kv = 0.0; s->warp_zoom = 1.0; s->warp_filter = 1;
     s->rate_mode = 0; s->out_fps_n = 0; s->out_fps_d = 1; s->max_fill = 2; s->open_rate = 0; s->tick = GST_CLOCK_TIME_NONE; s->rate_qh = s->rate_qn = 0;
     s->snap_location = NULL; s->snap_interval = 1000; s->snap_quality = 75; s->snap_reduce = 4; s->snap_source = 0; s->snap_next = GST_CLOCK_TIME_NONE; s->snap_watch = 0;
     g_mutex_init(&s->snap_mu); g_mutex_init(&s->snap_enc_mu); g_cond_init(&s->snap_cv);

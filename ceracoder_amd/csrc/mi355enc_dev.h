@@ -252,6 +252,10 @@ int k_launch_scale(int fmt, const uint8_t *p0, const uint8_t *p1, const uint8_t 
  * 4 (w + h) words are cleared on the same stream in front of it.  The match launch: votes of the eight projections `cur` against `prev` (range 1 .. 32,
  * w, h >= 4 range), medians and the trajectory step under bounds {lo_x, hi_x, lo_y, hi_y}; state {Sx, Sy} is read and written, rec gets the record's eight
  * words (mx, my, votes_x, votes_y, ox, oy, Sx, Sy).  prime: no vote is taken, state and record are zero.  -1: arguments outside that */
+/* Lens, roll and keystone correction (k_warp.hip; the rule: DESIGN.md section 27, warp_host.h): the coded NV12 surfaces (stride W, visible w x h, even) resampled
+ * through the mesh (warp_nodes(w) x warp_nodes(h) valid nodes, on the device) into another pair of surfaces, margin up to W x H included: every byte of both
+ * is written.  kind 0 bilinear, 1 bicubic; fill: Y, Cb, Cr of the samples outside; staging 0: no workgroup stages its source window in LDS (measurements).  -1: arguments outside that */
+int k_launch_warp(const uint8_t *sy, const uint8_t *suv, uint8_t *dy, uint8_t *duv, int w, int h, int W, int H, const int32_t *mesh, int kind, const uint8_t fill[3], hipStream_t s, int staging = 1);
 int k_launch_stab_project(const uint8_t *luma, int stride, int step, int w, int h, unsigned *sums, hipStream_t s);
 int k_launch_stab_match(const unsigned *prev, const unsigned *cur, int w, int h, int range, int leak, int prime, const int bounds[4], int *state, int *rec, hipStream_t s);
 void k_launch_pack(const mb_info_t *d_mbi, const int16_t *d_levels, int nmb, int mbw, unsigned *d_off, mb_info_t *h_mbi, int16_t *h_packed,

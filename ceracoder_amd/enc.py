@@ -38,6 +38,9 @@ STAGE_DENOISE_SEARCH, STAGE_DENOISE_MC = 27, 28  # ... with motion compensation 
 DENOISE_MOTION_MAX = 16
 STAGE_STABILIZE_PROJECT, STAGE_STABILIZE_MATCH = 29, 30  # the stabiliser's launches: clear + projection at the input size, match
 STABILIZE_RANGE_MAX, STABILIZE_MARGIN_MAX = 32, 1024
+STAGE_WARP = 31  # the warp set last on slot 0's surfaces
+WARP_BILINEAR, WARP_BICUBIC = 0, 1
+WARP_NODE_MIN, WARP_NODE_MAX = -2048 * 256, 10240 * 256
 STAGE_DENOISE, STAGE_DENOISE_PRIME = 25, 26  # the temporal noise filter set last on slot 0's surfaces and the handle's history: filtering, priming
 STAGE_HDR_P010, STAGE_HDR_I420_10, STAGE_HDR_V210, STAGE_DEEP_P010 = 19, 20, 21, 22  # the tone-mapping launch per format, and the plain P010 launch beside it
 HDR_PQ, HDR_HLG = 16, 18  # mi355enc_set_hdr_input: the transfer's H.264 Table E-4 code point
@@ -76,6 +79,8 @@ EXPORTS = [
     "mi355enc_set_denoise_motion", "mi355enc_get_denoise_motion", "mi355enc_last_denoise_motion", "mi355enc_denoise_motion_key", "mi355enc_stage_denoise_search", "mi355enc_stage_denoise_mc",
     "mi355enc_stabilize_default", "mi355enc_stabilize_check", "mi355enc_set_stabilize", "mi355enc_get_stabilize", "mi355enc_last_stabilize", "mi355enc_debug_stabilize_bytes",
     "mi355enc_stabilize_project", "mi355enc_stabilize_vote", "mi355enc_stabilize_motion", "mi355enc_stabilize_step", "mi355enc_stabilize_probe_project", "mi355enc_stabilize_probe_match",
+    "mi355enc_warp_params_default", "mi355enc_warp_coeff", "mi355enc_warp_mesh_size", "mi355enc_warp_mesh_check", "mi355enc_warp_build", "mi355enc_warp_apply_host",
+    "mi355enc_set_warp", "mi355enc_set_warp_mesh", "mi355enc_get_warp", "mi355enc_last_warp", "mi355enc_debug_warp_bytes", "mi355enc_warp_probe", "mi355enc_warp_plan", "mi355enc_debug_warp_staging",
 ]
 
 
@@ -151,6 +156,22 @@ class Stabilize(C.Structure):
 class StabilizeInfo(C.Structure):
     """mi355enc_stabilize_info_t: a picture's record -- measured motion, valid votes per axis, the crop's displacement, the trajectory's state (1/256 sample)"""
     _fields_ = [(n, C.c_int) for n in ("mx", "my", "votes_x", "votes_y", "ox", "oy", "sx", "sy")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class Warp(C.Structure):
+    """mi355enc_warp_t: the filter (0 bilinear, 1 bicubic) and the Y, Cb, Cr of the samples whose source lies outside the picture"""
+    _fields_ = [("kind", C.c_int), ("fill", C.c_uint8 * 3)]
+
+    def as_dict(self):
+        return dict(kind=int(self.kind), fill=tuple(int(v) for v in self.fill))
+
+
+class WarpParams(C.Structure):
+    """mi355enc_warp_params_t, Q16: radial terms, zoom, the roll's cos / sin, keystone"""
+    _fields_ = [(n, C.c_int) for n in ("k1", "k2", "zoom", "cos", "sin", "kh", "kv")]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
@@ -319,6 +340,22 @@ def load():
         L.mi355enc_stabilize_step.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_int)] * 2
         L.mi355enc_stabilize_probe_project.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
         L.mi355enc_stabilize_probe_match.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(Stabilize), C.POINTER(C.c_int * 4), C.POINTER(C.c_int * 2), C.c_int, C.POINTER(StabilizeInfo)]
+        L.mi355enc_warp_params_default.restype = None
+        L.mi355enc_warp_params_default.argtypes = [C.POINTER(WarpParams)]
+        L.mi355enc_warp_coeff.argtypes = [C.c_int, C.c_int, vp]
+        L.mi355enc_warp_mesh_size.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.mi355enc_warp_mesh_check.argtypes = [vp, C.c_int, C.c_int]
+        L.mi355enc_warp_build.argtypes = [C.POINTER(WarpParams), C.c_int, C.c_int, vp, C.c_size_t]
+        L.mi355enc_warp_apply_host.argtypes = [C.POINTER(Warp), vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int]
+        L.mi355enc_set_warp.argtypes = [vp, C.POINTER(Warp), C.POINTER(WarpParams)]
+        L.mi355enc_set_warp_mesh.argtypes = [vp, C.POINTER(Warp), vp, C.c_int, C.c_int]
+        L.mi355enc_get_warp.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(Warp)]
+        L.mi355enc_last_warp.argtypes = [vp, C.POINTER(C.c_uint)]
+        L.mi355enc_debug_warp_bytes.restype = C.c_size_t
+        L.mi355enc_debug_warp_bytes.argtypes = [vp]
+        L.mi355enc_warp_probe.argtypes = [vp, C.POINTER(Warp), vp, vp, vp]
+        L.mi355enc_warp_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.mi355enc_debug_warp_staging.argtypes = [vp, C.c_int]
         L.mi355enc_set_quality_metrics.argtypes = [vp, C.c_int]
         L.mi355enc_last_quality.argtypes = [vp, C.POINTER(Quality)]
         L.mi355enc_quality_totals.argtypes = [vp, C.POINTER(Quality)]
@@ -550,6 +587,89 @@ def stabilize_step(S, m, leak, lo, hi):
     if r:
         raise EncoderError("mi355enc_stabilize_step(%d, %d, %d, %d, %d): %d" % (S, m, leak, lo, hi, r))
     return int(s_out.value), int(o.value)
+
+
+def warp(s=None, **kw):
+    """A Warp: bicubic with a black fill (16, 128, 128), then s's (a Warp or a dict) and the keywords' kind / fill on top.  Not checked here."""
+    src = s.as_dict() if isinstance(s, Warp) else dict(s or {})
+    src.update(kw)
+    if set(src) - {"kind", "fill"}:
+        raise TypeError("warp: no parameter %r" % (sorted(set(src) - {"kind", "fill"}),))
+    return Warp(int(src.get("kind", WARP_BICUBIC)), (C.c_uint8 * 3)(*[int(v) for v in src.get("fill", (16, 128, 128))]))
+
+
+def warp_params(p=None, **kw):
+    """A WarpParams: the neutral values, then p's (a WarpParams or a dict) and the keywords' on top, all Q16 integers.  Not checked here."""
+    src = p.as_dict() if isinstance(p, WarpParams) else dict(p or {})
+    src.update(kw)
+    names = [n for n, _ in WarpParams._fields_]
+    if set(src) - set(names):
+        raise TypeError("warp_params: no parameter %r" % (sorted(set(src) - set(names)),))
+    d = WarpParams()
+    load().mi355enc_warp_params_default(C.byref(d))
+    for n in names:
+        setattr(d, n, int(src.get(n, getattr(d, n))))
+    return d
+
+
+def warp_mesh_size(w, h):
+    """mi355enc_warp_mesh_size: (nx, ny) of a w x h picture"""
+    nx, ny = C.c_int(0), C.c_int(0)
+    r = load().mi355enc_warp_mesh_size(int(w), int(h), C.byref(nx), C.byref(ny))
+    if r:
+        raise EncoderError("mi355enc_warp_mesh_size(%d, %d): %d" % (w, h, r))
+    return int(nx.value), int(ny.value)
+
+
+def warp_coeff(kind, f):
+    """mi355enc_warp_coeff (host only): the four taps of fraction f"""
+    c = np.zeros(4, np.int16)
+    r = load().mi355enc_warp_coeff(int(kind), int(f), _p(c))
+    if r:
+        raise EncoderError("mi355enc_warp_coeff(%d, %d): %d" % (kind, f, r))
+    return [int(v) for v in c]
+
+
+def warp_build(w, h, p=None, **kw):
+    """mi355enc_warp_build (host only): the mesh of a parameter set for a w x h picture, int32 (ny, nx, 2) holding {sx, sy}; EncoderError where it is refused"""
+    nx, ny = warp_mesh_size(w, h)
+    mesh = np.zeros((ny, nx, 2), np.int32)
+    r = load().mi355enc_warp_build(C.byref(warp_params(p, **kw)), int(w), int(h), _p(mesh), mesh.size)
+    if r:
+        raise EncoderError("mi355enc_warp_build: %d" % r)
+    return mesh
+
+
+def _mesh(mesh, w, h):
+    nx, ny = warp_mesh_size(w, h)
+    m = np.ascontiguousarray(mesh, np.int32)
+    if m.shape != (ny, nx, 2):
+        raise ValueError("a mesh of shape (%d, %d, 2)" % (ny, nx))
+    return m, nx, ny
+
+
+def warp_plan(mesh, w, h):
+    """mi355enc_warp_plan (host only): (staged, direct) -- how many of the launch's 32 x 32 tiles take which of the kernel's two forms"""
+    m, nx, ny = _mesh(mesh, w, h)
+    st, di = C.c_int(0), C.c_int(0)
+    r = load().mi355enc_warp_plan(_p(m), nx, ny, int(w), int(h), C.byref(st), C.byref(di))
+    if r:
+        raise EncoderError("mi355enc_warp_plan: %d" % r)
+    return int(st.value), int(di.value)
+
+
+def warp_apply_host(s, mesh, y, uv):
+    """mi355enc_warp_apply_host (host only): NV12 planes of the visible size (h, w) and (h / 2, w) warped through the mesh; returns the new planes"""
+    y, uv = np.ascontiguousarray(y, np.uint8), np.ascontiguousarray(uv, np.uint8)
+    h, w = y.shape
+    if uv.shape != (h // 2, w):
+        raise ValueError("NV12 planes of one picture")
+    m, _, _ = _mesh(mesh, w, h)
+    oy, ouv = np.empty_like(y), np.empty_like(uv)
+    r = load().mi355enc_warp_apply_host(C.byref(warp(s)), _p(m), w, h, _p(y), w, _p(uv), w, _p(oy), w, _p(ouv), w)
+    if r:
+        raise EncoderError("mi355enc_warp_apply_host: %d" % r)
+    return oy, ouv
 
 
 def denoise_check(d=None, **kw):
@@ -1178,6 +1298,49 @@ class Encoder:
         self._chk(self.L.mi355enc_stabilize_probe_match(self.h, _p(flat[0]), _p(flat[1]), w, h, C.byref(stabilize(s)), C.byref((C.c_int * 4)(*[int(v) for v in bounds])),
                                                         C.byref((C.c_int * 2)(*[int(v) for v in state])), int(bool(prime)), C.byref(info)), "stabilize_probe_match")
         return info.as_dict()
+
+    def set_warp(self, s=None, p=None, **kw):
+        """lens, roll and keystone correction from the next submitted picture on (any time, any thread): s the filter and fill (a Warp or a dict; None: off), p and
+        the keywords the Q16 parameters of warp_params()"""
+        if s is None and p is None and not kw:
+            self._chk(self.L.mi355enc_set_warp(self.h, None, None), "set_warp")
+        else:
+            self._chk(self.L.mi355enc_set_warp(self.h, C.byref(warp(s)), C.byref(warp_params(p, **kw))), "set_warp")
+
+    def set_warp_mesh(self, s, mesh):
+        """... through the caller's own mesh, int32 (ny, nx, 2) for the coded visible size (s None: off)"""
+        if s is None:
+            self._chk(self.L.mi355enc_set_warp_mesh(self.h, None, None, 0, 0), "set_warp_mesh")
+            return
+        m, nx, ny = _mesh(mesh, self.width, self.height)
+        self._chk(self.L.mi355enc_set_warp_mesh(self.h, C.byref(warp(s)), _p(m), nx, ny), "set_warp_mesh")
+
+    def get_warp(self):
+        """the setting set last as a dict, None when off"""
+        on, st = C.c_int(0), Warp()
+        self._chk(self.L.mi355enc_get_warp(self.h, C.byref(on), C.byref(st)), "get_warp")
+        return st.as_dict() if on.value else None
+
+    def last_warp(self):
+        """the generation (count of successful sets) whose mesh the last collected picture was warped with, 0 for an unwarped one"""
+        g = C.c_uint(0)
+        self._chk(self.L.mi355enc_last_warp(self.h, C.byref(g)), "last_warp")
+        return int(g.value)
+
+    def debug_warp_bytes(self):
+        return int(self.L.mi355enc_debug_warp_bytes(self.h))
+
+    def debug_warp_staging(self, on):
+        """measurements: False -- every tile of the warp launch takes the direct form (the picture is the same)"""
+        self._chk(self.L.mi355enc_debug_warp_staging(self.h, int(bool(on))), "debug_warp_staging")
+
+    def stage_warp(self, s, mesh, y, uv):
+        """The warp launch alone on host planes of the coded size through `mesh` (of the coded visible size); returns the warped copies, margin included."""
+        y, uv = np.ascontiguousarray(y, np.uint8).copy(), np.ascontiguousarray(uv, np.uint8).copy()
+        assert y.shape == (self.mbh * 16, self.mbw * 16) and uv.shape == (self.mbh * 8, self.mbw * 16)
+        m, _, _ = _mesh(mesh, self.width, self.height)
+        self._chk(self.L.mi355enc_warp_probe(self.h, C.byref(warp(s)), _p(m), _p(y), _p(uv)), "stage_warp")
+        return y, uv
 
     def debug_denoise_bytes(self):
         return int(self.L.mi355enc_debug_denoise_bytes(self.h))

@@ -424,6 +424,62 @@ int mi355enc_stabilize_step(int S, int m, int leak, int lo, int hi, int *S_out, 
 int mi355enc_stabilize_probe_project(mi355enc_t *h, const uint8_t *luma, int stride, int step, int w, int ht, uint32_t *sums);
 int mi355enc_stabilize_probe_match(mi355enc_t *h, const uint32_t *prev, const uint32_t *cur, int w, int ht, const mi355enc_stabilize_t *s, const int bounds[4],
                                    const int state[2], int prime, mi355enc_stabilize_info_t *info);
+/* Lens, roll and keystone correction: the coded picture is resampled through a coarse mesh of source positions, the first step on the
+ * coded surfaces (in front of the colour step, the noise filter, the picture controls, the mix, layers and text; behind the geometry and the stabiliser's
+ * crop); off by default, and off nothing is allocated or launched.  All integers; >> is a floor.
+ *   mesh       for the coded visible size w x h: nx = (w + 15) / 16 + 1 by ny = (h + 15) / 16 + 1 nodes; node (i, j) at int32 index 2 (j nx + i) holds the
+ *              source position {sx, sy} of the output luma sample (16 i, 16 j) in 1/256 luma sample, each inside [-2048 * 256, 10240 * 256]
+ *   position   luma (x, y): i = x >> 4, j = y >> 4, xf = x & 15, yf = y & 15; per coordinate
+ *              P = (16 - yf) ((16 - xf) N[j][i] + xf N[j][i + 1]) + yf ((16 - xf) N[j + 1][i] + xf N[j + 1][i + 1]) (1/65536 sample), p = (P + 1024) >> 11;
+ *              the chroma pair (cx, cy): P at the luma point (2 cx, 2 cy), p = (P + 2048) >> 12 (1/32 chroma sample; siting is ignored).  ix = p >> 5, f = p & 31
+ *   filter     kind 0 bilinear: taps {0, 4 (32 - f), 4 f, 0}; kind 1 Catmull-Rom: c-1 = (-f^3 + 64 f^2 - 1024 f + 256) >> 9,
+ *              c1 = (-3 f^3 + 128 f^2 + 1024 f + 256) >> 9, c2 = (f^3 - 32 f^2 + 256) >> 9, c0 = 128 - c-1 - c1 - c2.
+ *              a = sum_r cy[r] sum_k cx[k] S[clamp(iy - 1 + r)][clamp(ix - 1 + k)], out = clip((a + 8192) >> 14, 0, 255); tap positions clamp to the visible
+ *              plane; Cb and Cr of a pair take the same taps
+ *   outside    ix < -1, ix above the last column, or the same of iy and the rows: the fill value, unfiltered (fill[0] luma, fill[1], fill[2] a chroma pair)
+ *   margin     up to whole macroblocks the last visible column / row (chroma: pair) is repeated, as by every other input launch
+ * The setters may be called at any time from any thread; the value is latched per input picture, and pictures in flight keep the mesh they latched. */
+typedef struct {
+    int kind;        /* 0 bilinear, 1 bicubic (Catmull-Rom) */
+    uint8_t fill[3]; /* Y, Cb, Cr of the samples whose source lies outside the picture */
+} mi355enc_warp_t;
+typedef struct {     /* Q16 */
+    int k1, k2;      /* radial terms, -65536 .. 65536; neutral 0 */
+    int zoom;        /* 16384 .. 262144; neutral 65536 (above: the source is read further out, the picture shrinks) */
+    int cos, sin;    /* roll, -65536 .. 65536 each; neutral 65536, 0 */
+    int kh, kv;      /* keystone, -32768 .. 32768; neutral 0 */
+} mi355enc_warp_params_t;
+void mi355enc_warp_params_default(mi355enc_warp_params_t *p); /* the neutral values: their mesh is the identity (4096 i, 4096 j) */
+/* host only.  coeff: the four taps of fraction f (0 .. 31).  mesh_size: nx, ny of a w x h picture (2 .. 8192 each).  mesh_check: every node inside the range.
+ * build: the mesh of a parameter set into mesh[cap] (cap >= 2 nx ny), in 64-bit arithmetic, for node (i, j):
+ *   u = 32 i - (w - 1), v = 32 j - (h - 1);  U = (zoom (cos u - sin v)) >> 16, V = (zoom (sin u + cos v)) >> 16
+ *   d = 65536 + fdiv(kh U, (w - 1) << 16) + fdiv(kv V, (h - 1) << 16) (fdiv: rounded towards minus infinity; d < 16384: MI355ENC_ERR_ARG)
+ *   U = fdiv(U << 16, d), V likewise;  r2 = ((U >> 8)^2 + (V >> 8)^2) >> 16, q = fdiv(r2 << 16, (w - 1)^2 + (h - 1)^2) (q > 4194304: MI355ENC_ERR_ARG; it keeps U g inside 64 bits)
+ *   g = 65536 + ((k1 q) >> 16) + ((k2 ((q q) >> 16)) >> 16);  sx = ((w - 1) 65536 + ((U g) >> 16) + 256) >> 9, sy likewise with h and V
+ * and MI355ENC_ERR_ARG for a parameter outside its range or a node outside the mesh's.
+ * apply_host: the scalar form of the whole rule on NV12 planes of the visible size w x h (even), no margin */
+int mi355enc_warp_coeff(int kind, int f, int16_t c[4]);
+int mi355enc_warp_mesh_size(int w, int h, int *nx, int *ny);
+int mi355enc_warp_mesh_check(const int32_t *mesh, int nx, int ny);
+int mi355enc_warp_build(const mi355enc_warp_params_t *p, int w, int h, int32_t *mesh, size_t cap);
+/* host only: how many of the launch's 32 x 32 output tiles (of the coded size) take which of the kernel's two forms, by the test the kernel makes -- staged:
+ * the tile's source window, floor(smallest node) - 1 .. floor(largest node) + 2 per axis over the tile's cells, clamped to the picture, fits 64 x 64 luma
+ * samples and 36 x 36 chroma pairs of LDS; direct: it does not, and the taps come from global memory.  Both forms give the same picture */
+int mi355enc_warp_plan(const int32_t *mesh, int nx, int ny, int w, int h, int *staged, int *direct);
+int mi355enc_warp_apply_host(const mi355enc_warp_t *s, const int32_t *mesh, int w, int h, const uint8_t *y, int y_stride, const uint8_t *uv, int uv_stride,
+                             uint8_t *out_y, int out_y_stride, uint8_t *out_uv, int out_uv_stride);
+/* set_warp builds the mesh of `p` for the handle's coded visible size; set_warp_mesh takes the caller's (nx, ny must be that size's, every node valid).  A null
+ * setting: off.  Every successful set that turns the warp on counts one generation up */
+int mi355enc_set_warp(mi355enc_t *h, const mi355enc_warp_t *s, const mi355enc_warp_params_t *p);
+int mi355enc_set_warp_mesh(mi355enc_t *h, const mi355enc_warp_t *s, const int32_t *mesh, int nx, int ny);
+int mi355enc_get_warp(const mi355enc_t *h, int *on, mi355enc_warp_t *s); /* what was set last (s is untouched when off; either pointer may be NULL) */
+/* the generation the last collected picture was warped with, 0 for an unwarped one; MI355ENC_ERR_STATE before the first collect */
+int mi355enc_last_warp(mi355enc_t *h, unsigned *generation);
+size_t mi355enc_debug_warp_bytes(const mi355enc_t *h); /* device bytes of the warp: 0 until the first warped picture is submitted */
+int mi355enc_debug_warp_staging(mi355enc_t *h, int on); /* measurements: 0 -- every tile takes the direct form (the picture is the same); on by default */
+/* the launch alone (tests), in the frame of the single-stage entry points (named as the stabiliser's probes are): y / uv are host planes of the coded size (16 mbw x 16 mbh, chroma interleaved),
+ * warped in place through `mesh` (the handle's coded visible size's nx x ny); the handle's own setting plays no part */
+int mi355enc_warp_probe(mi355enc_t *h, const mi355enc_warp_t *s, const int32_t *mesh, uint8_t *y, uint8_t *uv);
 /* like mi355enc_submit, from host memory in `fmt`; planes[]/strides[]: as many entries as the format has planes */
 int mi355enc_submit_fmt(mi355enc_t *h, int fmt, const uint8_t *const planes[3], const int strides[3], int64_t pts, int force_idr);
 /* conversion stage alone (tests): writes the coded-size NV12 surfaces (16*mbw x 16*mbh luma, then interleaved chroma) */
@@ -809,6 +865,7 @@ int mi355enc_stage_deblock(mi355enc_t *h, uint8_t *rec_y, uint8_t *rec_uv, const
  * 29 / 30 the stabiliser's launches (mi355enc_set_stabilize; MI355ENC_ERR_STATE when it is off or the handle has no geometry): 29 the projection launch with
  * its clear at the handle's input size on slot 0's raw staging buffer, 30 the match launch on whatever the projection buffers hold.  Both leave the
  * trajectory unprimed: the next picture submitted primes.
+ * 31 the warp set last (mi355enc_set_warp / mi355enc_set_warp_mesh; MI355ENC_ERR_STATE when it is off) on slot 0's source surfaces.
  * Uses whatever the handle's surfaces currently hold.  Returns average ms per launch. */
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms);
 
