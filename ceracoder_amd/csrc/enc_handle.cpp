@@ -345,6 +345,7 @@ void mi355enc_close(mi355enc_t *h) {
     rate_free(h);
     hdr_free(h);
     adjust_free(h);
+    autolevel_free(h);
     denoise_free(h);
     stab_free(h);
     warp_close(h);

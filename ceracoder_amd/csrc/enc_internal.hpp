@@ -12,6 +12,7 @@
 //   enc_snapshot.cpp  JPEG stills: request / take, the blocks the levels land in, the launch, its stage entry points
 //   enc_csc.cpp       colorimetry: the setters, the RGB matrix and the YUV -> YUV table, the colour step's launch, their stage entry points
 //   enc_adjust.cpp    picture controls: setter, latch, the two launch forms and the scratch plane, its stage entry point
+//   enc_autolevel.cpp automatic levels and white balance: setter, latch, the three launches and the device block, the probes and the stage entry point
 //   enc_denoise.cpp   temporal noise reduction: setter, latch, the launch and the handle's history, its stage entry point
 //   enc_stab.cpp      electronic image stabilisation: setter, latch, the estimate in front of every scale launch, its probes and timed stages
 //   enc_warp.cpp      lens, roll and keystone correction: setters, latch, the mesh's way to the device, the launch and the scratch pair, its stage entry point
@@ -44,6 +45,7 @@
 #include "adjust_host.h"
 #include "denoise_host.h"
 #include "stab_host.h"
+#include "autolevel_host.h"
 #include "warp_host.h"
 #include "enc_plan.hpp"
 #include "enc_sync.hpp"
@@ -140,6 +142,10 @@ struct slot_t {
     // image stabilisation: what submit latched for this picture (stab.range 0: off), and whether the estimate ran for it (its record then lies in the handle's
     // pinned block at the slot's index once the picture is collected)
     mi355enc_stabilize_t stab; bool stab_done;
+    // automatic levels and white balance: what submit latched for this picture (al_on false: nothing) with the output range it met, and whether the step ran
+    // for it (its record and table then lie in the handle's pinned block at the slot's index once the picture is collected); applied once, to the input's own
+    // slot, in ingest_end
+    mi355enc_autolevel_t al; bool al_on, al_done; int al_full;
     // the warp: what submit latched for this picture (warp_on false: nothing; warp_gen: the count of sets its mesh belongs to); warp_send: the slot's pinned copy
     // holds that mesh and it travels in front of the launch; applied once, to the input's own slot, first in ingest_end
     bool warp_on, warp_send; mi355enc_warp_t warp; unsigned warp_gen;
@@ -277,6 +283,18 @@ struct mi355enc {
     int *d_stab = nullptr, *h_stab = nullptr;
     size_t stab_bytes = 0;
     int stab_half = 0, stab_w = 0, stab_h = 0;
+    // automatic levels and white balance (mi355enc_set_autolevel): what the control thread set last (under al_mu; submit latches it per
+    // input picture) and what the last collected picture carried.  d_al (one block, allocated by the first autolevelled picture; al_bytes: its size): the state
+    // {Lo, Hi, Du, Dv} (and four words of room), AL_SLOT_WORDS words per slot and for the stage calls (record, table), then AL_SLABS_MAX slabs; h_al: the
+    // slots' pinned copies.  al_primed false: the next autolevelled picture primes.  Written only by launches that follow one another on one stream.
+    std::mutex al_mu;
+    mi355enc_autolevel_t al_cur = {0, 0, 16, 50, 50, 2000, 48}, al_last = {0, 0, 16, 50, 50, 2000, 48};
+    mi355enc_autolevel_info_t al_last_info = {};
+    uint8_t al_last_tab[256] = {};
+    bool al_last_have = false, al_primed = false;
+    int *d_al = nullptr, *h_al = nullptr;
+    size_t al_bytes = 0;
+    int al_time_n = 0; // (mi355enc_time_stage 32 .. 34: the slabs its prepare left)
     // lens, roll and keystone correction (mi355enc_set_warp / mi355enc_set_warp_mesh): what the control thread set last (under warp_mu: the
     // setting, its mesh of the coded visible size on the heap, the count of sets that turned it on; submit latches it per input picture) and what the last
     // collected picture carried.  Allocated by the first warped picture: the scratch pair d_warp_y / d_warp_uv (the launch writes it, then the slot and the handle
@@ -486,6 +504,15 @@ bool stab_time_ready(mi355enc_t *h, int stage);              // mi355enc_time_st
 int stab_time_prepare(mi355enc_t *h, slot_t *s, ts_ctx_t *x);
 int stab_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // 29 the clear and the projection launch on the raw staging buffer, 30 the match launch
 void stab_time_done(mi355enc_t *h);                          // ... behind the timed launches: the next picture primes
+// enc_autolevel.cpp (automatic levels and white balance)
+void autolevel_latch(mi355enc_t *h, slot_t *s, bool own);    // the value set last becomes the slot's (beside adjust_latch); own: the slot the input goes into (off there: the next picture it is on for primes)
+int autolevel_draw(mi355enc_t *h, slot_t *s, hipStream_t st); // measure, decide, apply on the slot's coded surfaces and the record's copy to pinned memory, behind everything enqueued on st so far; nothing with none
+void autolevel_collected(mi355enc_t *h, slot_t *s);          // collect(): books what the picture carried as the last picture's
+void autolevel_free(mi355enc_t *h);
+bool autolevel_time_ready(mi355enc_t *h, int stage);         // mi355enc_time_stage 32 .. 34: the value set last is on
+int autolevel_time_prepare(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // the block, and a measure and a (priming) decide launch on slot 0's surfaces
+int autolevel_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // 32 measure, 33 decide, 34 apply
+void autolevel_time_done(mi355enc_t *h);                     // ... behind the timed launches: the next picture primes
 // enc_warp.cpp (lens, roll and keystone correction)
 int warp_latch(mi355enc_t *h, slot_t *s, bool own);          // the value set last becomes the slot's (beside stab_latch); own: the slot the input goes into, which also takes the mesh where it is a new one
 int warp_draw(mi355enc_t *h, slot_t *s, hipStream_t st);     // the slot's warp on its coded surfaces, behind everything enqueued on st so far (a new mesh travels in front of it); nothing with none

@@ -539,6 +539,7 @@ int mi355enc_collect(mi355enc_t *h, uint8_t *out, size_t out_cap, size_t *out_le
     h->ov_last_have = 1; h->ov_last_len = s->ov_len; if (s->ov_len) memcpy(h->ov_last, s->ov_text, (size_t)s->ov_len);
     image_collected(h, s);
     adjust_collected(h, s);
+    autolevel_collected(h, s);
     denoise_collected(h, s);
     stab_collected(h, s);
     warp_collected(h, s);

@@ -112,6 +112,9 @@ typedef struct {
     mi355enc_adjust_t adj;
     /* temporal noise reduction on the device (mi355enc_set_denoise): denoise-luma, denoise-chroma; stored and forwarded like the picture controls */
     mi355enc_denoise_t dn;
+    /* automatic levels and white balance on the device (mi355enc_set_autolevel): auto-levels, auto-balance (doubles 0 .. 1, stored as
+     * thousandths, lround), auto-speed, auto-clip (percent, both clips), auto-max-gain; stored under the object lock and forwarded like the picture controls */
+    mi355enc_autolevel_t al;
     /* stabilize (mi355enc_set_stabilize): the margin in input samples per side (0: off; odd values count as the even value below), added
      * to each of crop-* when the geometry is built -- so a change while playing is a crop change --, and the estimator's range and leak */
     gint stab, stab_range, stab_leak;
@@ -151,7 +154,7 @@ enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME
        PROP_SNAP_LOCATION, PROP_SNAP_INTERVAL, PROP_SNAP_QUALITY, PROP_SNAP_REDUCE, PROP_SNAP_SOURCE,
        PROP_OUTPUT_COLORIMETRY, PROP_RATE_CONVERSION, PROP_OUTPUT_FRAMERATE, PROP_MAX_FILL, PROP_HDR_INPUT, PROP_HDR_PEAK_NITS, PROP_HDR_TARGET_NITS,
        PROP_ADJ_BRIGHTNESS, PROP_ADJ_CONTRAST, PROP_ADJ_HUE, PROP_ADJ_SATURATION, PROP_ADJ_GAMMA, PROP_ADJ_SHARPEN, PROP_ADJ_SHARPEN_THRESHOLD,
-       PROP_DENOISE_LUMA, PROP_DENOISE_CHROMA, PROP_DENOISE_MOTION, PROP_STABILIZE, PROP_STABILIZE_RANGE, PROP_STABILIZE_LEAK,
+       PROP_DENOISE_LUMA, PROP_DENOISE_CHROMA, PROP_DENOISE_MOTION, PROP_STABILIZE, PROP_STABILIZE_RANGE, PROP_STABILIZE_LEAK, PROP_AUTO_LEVELS, PROP_AUTO_BALANCE, PROP_AUTO_SPEED, PROP_AUTO_CLIP, PROP_AUTO_MAX_GAIN,
        PROP_LENS_K1, PROP_LENS_K2, PROP_LENS_ZOOM, PROP_ROLL, PROP_KEYSTONE_H, PROP_KEYSTONE_V, PROP_WARP_FILTER };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
@@ -259,6 +262,10 @@ static void overlay_forward(GstMi355H264Enc *s) {
 static void adjust_forward(GstMi355H264Enc *s) {
     if (s->enc && mi355enc_set_adjust(s->enc, &s->adj) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the picture controls: it keeps its previous ones");
 }
+/* stored automatic levels and white balance -> the encoder, if one is open (object lock held; the library only stores: no GPU call, any thread) */
+static void autolevel_forward(GstMi355H264Enc *s) {
+    if (s->enc && mi355enc_set_autolevel(s->enc, &s->al) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the automatic levels: it keeps its previous setting");
+}
 /* stored noise filter strengths -> the encoder, if one is open (object lock held; the library builds three small tables and stores: no GPU call, any thread) */
 /* what the crop rectangle is built from: crop-* (even), each with the stabiliser's margin on top.  Called with the object lock held */
 static void effective_crop(const GstMi355H264Enc *s, int crop[4]) {
@@ -356,6 +363,11 @@ static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *
     case PROP_ADJ_GAMMA: s->adj.gamma = (int)lround(1000.0 * g_value_get_double(val)); adjust_forward(s); break;
     case PROP_ADJ_SHARPEN: s->adj.sharpen = g_value_get_int(val); adjust_forward(s); break;
     case PROP_ADJ_SHARPEN_THRESHOLD: s->adj.sharpen_threshold = g_value_get_int(val); adjust_forward(s); break;
+    case PROP_AUTO_LEVELS: s->al.levels = (int)lround(1000.0 * g_value_get_double(val)); autolevel_forward(s); break;
+    case PROP_AUTO_BALANCE: s->al.balance = (int)lround(1000.0 * g_value_get_double(val)); autolevel_forward(s); break;
+    case PROP_AUTO_SPEED: s->al.speed = g_value_get_int(val); autolevel_forward(s); break;
+    case PROP_AUTO_CLIP: s->al.clip_low = s->al.clip_high = (int)lround(100.0 * g_value_get_double(val)); autolevel_forward(s); break;
+    case PROP_AUTO_MAX_GAIN: s->al.max_gain = (int)lround(1000.0 * g_value_get_double(val)); autolevel_forward(s); break;
     case PROP_DENOISE_LUMA: s->dn.luma = g_value_get_int(val); denoise_forward(s); break;
     case PROP_DENOISE_CHROMA: s->dn.chroma = g_value_get_int(val); denoise_forward(s); break;
     case PROP_DENOISE_MOTION: s->dn_motion = g_value_get_int(val); denoise_forward(s); break;
@@ -441,6 +453,11 @@ static void get_property(GObject *obj, guint id, GValue *val, GParamSpec *ps) {
     case PROP_ADJ_GAMMA: g_value_set_double(val, s->adj.gamma / 1000.0); break;
     case PROP_ADJ_SHARPEN: g_value_set_int(val, s->adj.sharpen); break;
     case PROP_ADJ_SHARPEN_THRESHOLD: g_value_set_int(val, s->adj.sharpen_threshold); break;
+    case PROP_AUTO_LEVELS: g_value_set_double(val, s->al.levels / 1000.0); break;
+    case PROP_AUTO_BALANCE: g_value_set_double(val, s->al.balance / 1000.0); break;
+    case PROP_AUTO_SPEED: g_value_set_int(val, s->al.speed); break;
+    case PROP_AUTO_CLIP: g_value_set_double(val, s->al.clip_low / 100.0); break;
+    case PROP_AUTO_MAX_GAIN: g_value_set_double(val, s->al.max_gain / 1000.0); break;
     case PROP_DENOISE_LUMA: g_value_set_int(val, s->dn.luma); break;
     case PROP_DENOISE_CHROMA: g_value_set_int(val, s->dn.chroma); break;
     case PROP_DENOISE_MOTION: g_value_set_int(val, s->dn_motion); break;
@@ -857,6 +874,7 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     overlay_forward(s);                     /* ... nor the overlay's text and style, set before the device was opened */
     image_forward(s, TRUE);                 /* ... nor the image layer */
     adjust_forward(s);                      /* ... nor the picture controls */
+    autolevel_forward(s);                   /* ... nor the automatic levels and white balance */
     denoise_forward(s);                     /* ... nor the noise filter */
     stabilize_forward(s);                   /* ... nor the stabiliser */
     warp_forward(s);                        /* ... nor the warp */
@@ -1314,6 +1332,11 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
     g_object_class_install_property(g, PROP_ADJ_GAMMA, g_param_spec_double("gamma", "Gamma", "picture controls on the GPU (the gamma element's property): t -> t^(1 / gamma) on the luma between black and white", 0.1, 10.0, 1.0, F));
     g_object_class_install_property(g, PROP_ADJ_SHARPEN, g_param_spec_int("sharpen", "Sharpen", "picture controls on the GPU: 3 x 3 unsharp mask on the luma in sixteenths of its amount (16: original + detail); negative softens (-16: the binomial blur); 0: off", -16, 64, 0, F));
     g_object_class_install_property(g, PROP_ADJ_SHARPEN_THRESHOLD, g_param_spec_int("sharpen-threshold", "Sharpen threshold", "with sharpen > 0: detail of at most this many codes is left alone (coring)", 0, 32, 0, F));
+    g_object_class_install_property(g, PROP_AUTO_LEVELS, g_param_spec_double("auto-levels", "Automatic levels", "automatic levels on the GPU, measured per picture behind the noise filter and in front of the picture controls: how much of the stretch of the measured black and white point to the range's ends is applied; 0: off", 0.0, 1.0, 0.0, F));
+    g_object_class_install_property(g, PROP_AUTO_BALANCE, g_param_spec_double("auto-balance", "Automatic white balance", "automatic white balance on the GPU (grey world, a constant chroma offset): how much of the measured cast is taken out; 0: off", 0.0, 1.0, 0.0, F));
+    g_object_class_install_property(g, PROP_AUTO_SPEED, g_param_spec_int("auto-speed", "Automatic speed", "how fast the automatic levels and white balance follow the measurement, in 1/256 per picture; 256: at once (a knob, not a tuned value)", 1, 256, 16, F));
+    g_object_class_install_property(g, PROP_AUTO_CLIP, g_param_spec_double("auto-clip", "Automatic clip", "the percentage of the samples that may fall below the black point, and likewise above the white point", 0.0, 20.0, 0.5, F));
+    g_object_class_install_property(g, PROP_AUTO_MAX_GAIN, g_param_spec_double("auto-max-gain", "Automatic maximum gain", "the largest contrast gain the automatic levels apply", 1.0, 8.0, 2.0, F));
     g_object_class_install_property(g, PROP_DENOISE_LUMA, g_param_spec_int("denoise-luma", "Denoise luma", "temporal noise reduction on the GPU, motion-adaptive, in front of the picture controls: the luma noise amplitude in codes that is filtered fully; 0: off", 0, MI355ENC_DENOISE_MAX, 0, F));
     g_object_class_install_property(g, PROP_DENOISE_CHROMA, g_param_spec_int("denoise-chroma", "Denoise chroma", "temporal noise reduction on the GPU: the chroma noise amplitude in codes that is filtered fully; 0: off", 0, MI355ENC_DENOISE_MAX, 0, F));
     g_object_class_install_property(g, PROP_STABILIZE, g_param_spec_int("stabilize", "Stabilize", "electronic image stabilisation on the GPU: the margin in input samples per side that the crop may move by to follow the camera's shake (added to each of crop-*; odd values count as the even value below); 0: off", 0, MI355ENC_STABILIZE_MARGIN_MAX, 0, F));
@@ -1348,6 +1371,7 @@ static void gst_mi355h264enc_init(GstMi355H264Enc *s) {
     s->hdr_input = 0; s->hdr_peak = 0; s->hdr_target = 0;
     mi355enc_adjust_default(&s->adj);
     mi355enc_denoise_default(&s->dn);
+    mi355enc_autolevel_default(&s->al);
     s->dn_motion = 0;
     s->stab = 0; s->stab_range = 16; s->stab_leak = 16;
     s->warp_k1 = s->warp_k2 = s->warp_roll = s->warp_kh = s->warp_kv = 0.0; s->warp_zoom = 1.0; s->warp_filter = 1;

@@ -258,6 +258,14 @@ int k_launch_scale(int fmt, const uint8_t *p0, const uint8_t *p1, const uint8_t 
 int k_launch_warp(const uint8_t *sy, const uint8_t *suv, uint8_t *dy, uint8_t *duv, int w, int h, int W, int H, const int32_t *mesh, int kind, const uint8_t fill[3], hipStream_t s, int staging = 1);
 int k_launch_stab_project(const uint8_t *luma, int stride, int step, int w, int h, unsigned *sums, hipStream_t s);
 int k_launch_stab_match(const unsigned *prev, const unsigned *cur, int w, int h, int range, int leak, int prime, const int bounds[4], int *state, int *rec, hipStream_t s);
+/* Automatic levels and white balance (k_autolevel.hip; the rule: DESIGN.md section 28, autolevel_host.h), three launches on one stream.  measure: the visible
+ * samples of rect on NV12 surfaces of W x H at stride W (visible vw x vh) -> one slab of AL_SLAB_WORDS words per workgroup (plain stores: nothing to clear);
+ * returns their number (1 .. AL_SLABS_MAX).  decide: the slabs, NC visible chroma samples and the setting's seven fields -> the state (4 words, read and
+ * written; prime: only written), the record and the table (AL_SLOT_WORDS words at rec).  apply: the table and offsets at rec onto the samples inside rect, in
+ * place; luma / chroma: the setting's levels / balance are above 0.  -1: arguments outside that */
+int k_launch_autolevel_measure(const uint8_t *y, const uint8_t *uv, int W, int H, const int rect[4], int vw, int vh, int full_range, int reach, unsigned *slabs, hipStream_t s);
+int k_launch_autolevel_decide(const unsigned *slabs, int nslabs, unsigned NC, const int set[7], int full_range, int prime, int *state, int *rec, hipStream_t s);
+int k_launch_autolevel_apply(uint8_t *y, uint8_t *uv, int W, int H, const int rect[4], int luma, int chroma, const int *rec, hipStream_t s);
 void k_launch_pack(const mb_info_t *d_mbi, const int16_t *d_levels, int nmb, int mbw, unsigned *d_off, mb_info_t *h_mbi, int16_t *h_packed,
                    unsigned *h_hdr, const unsigned *d_err, hipStream_t s);
 int k_deblock_diags(int mbw, int mbh);

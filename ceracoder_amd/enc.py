@@ -39,6 +39,7 @@ DENOISE_MOTION_MAX = 16
 STAGE_STABILIZE_PROJECT, STAGE_STABILIZE_MATCH = 29, 30  # the stabiliser's launches: clear + projection at the input size, match
 STABILIZE_RANGE_MAX, STABILIZE_MARGIN_MAX = 32, 1024
 STAGE_WARP = 31  # the warp set last on slot 0's surfaces
+STAGE_AUTOLEVEL_MEASURE, STAGE_AUTOLEVEL_DECIDE, STAGE_AUTOLEVEL_APPLY = 32, 33, 34  # the launches of automatic levels and white balance
 WARP_BILINEAR, WARP_BICUBIC = 0, 1
 WARP_NODE_MIN, WARP_NODE_MAX = -2048 * 256, 10240 * 256
 STAGE_DENOISE, STAGE_DENOISE_PRIME = 25, 26  # the temporal noise filter set last on slot 0's surfaces and the handle's history: filtering, priming
@@ -79,6 +80,8 @@ EXPORTS = [
     "mi355enc_set_denoise_motion", "mi355enc_get_denoise_motion", "mi355enc_last_denoise_motion", "mi355enc_denoise_motion_key", "mi355enc_stage_denoise_search", "mi355enc_stage_denoise_mc",
     "mi355enc_stabilize_default", "mi355enc_stabilize_check", "mi355enc_set_stabilize", "mi355enc_get_stabilize", "mi355enc_last_stabilize", "mi355enc_debug_stabilize_bytes",
     "mi355enc_stabilize_project", "mi355enc_stabilize_vote", "mi355enc_stabilize_motion", "mi355enc_stabilize_step", "mi355enc_stabilize_probe_project", "mi355enc_stabilize_probe_match",
+    "mi355enc_autolevel_default", "mi355enc_autolevel_check", "mi355enc_autolevel_decide", "mi355enc_set_autolevel", "mi355enc_get_autolevel", "mi355enc_last_autolevel",
+    "mi355enc_debug_autolevel_bytes", "mi355enc_autolevel_probe_stage", "mi355enc_autolevel_probe_measure", "mi355enc_autolevel_probe_decide",
     "mi355enc_warp_params_default", "mi355enc_warp_coeff", "mi355enc_warp_mesh_size", "mi355enc_warp_mesh_check", "mi355enc_warp_build", "mi355enc_warp_apply_host",
     "mi355enc_set_warp", "mi355enc_set_warp_mesh", "mi355enc_get_warp", "mi355enc_last_warp", "mi355enc_debug_warp_bytes", "mi355enc_warp_probe", "mi355enc_warp_plan", "mi355enc_debug_warp_staging",
 ]
@@ -156,6 +159,31 @@ class Stabilize(C.Structure):
 class StabilizeInfo(C.Structure):
     """mi355enc_stabilize_info_t: a picture's record -- measured motion, valid votes per axis, the crop's displacement, the trajectory's state (1/256 sample)"""
     _fields_ = [(n, C.c_int) for n in ("mx", "my", "votes_x", "votes_y", "ox", "oy", "sx", "sy")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class Autolevel(C.Structure):
+    """mi355enc_autolevel_t: levels / balance in thousandths (both 0: off), speed 1 .. 256, the clips in ten-thousandths, max_gain in thousandths, the vote's reach"""
+    NAMES = ("levels", "balance", "speed", "clip_low", "clip_high", "max_gain", "reach")
+    _fields_ = [(n, C.c_int) for n in NAMES]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n in self.NAMES}
+
+
+class AutolevelMeas(C.Structure):
+    """mi355enc_autolevel_meas_t: the luma histogram, the chroma voters, the visible chroma samples, the voters' sums of Cb and Cr"""
+    _fields_ = [("hist", C.c_uint32 * 256), ("voters", C.c_uint32), ("chroma", C.c_uint32), ("su", C.c_uint64), ("sv", C.c_uint64)]
+
+    def as_dict(self):
+        return dict(hist=np.array(self.hist, np.int64), voters=int(self.voters), chroma=int(self.chroma), su=int(self.su), sv=int(self.sv))
+
+
+class AutolevelInfo(C.Structure):
+    """mi355enc_autolevel_info_t: a picture's record -- its measurement, the state behind it (1/256 code), the chroma offsets, whether the chroma vote was valid"""
+    _fields_ = [(n, C.c_int) for n in ("lo", "hi", "voters", "du", "dv", "s_lo", "s_hi", "s_du", "s_dv", "off_u", "off_v", "valid")]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
@@ -326,6 +354,18 @@ def load():
         L.mi355enc_denoise_motion_key.argtypes = [C.c_int] * 4
         L.mi355enc_stage_denoise_search.argtypes = [vp, C.POINTER(Denoise), C.c_int, vp, vp, vp]
         L.mi355enc_stage_denoise_mc.argtypes = [vp, C.POINTER(Denoise), C.c_int] + [vp] * 7
+        L.mi355enc_autolevel_default.restype = None
+        L.mi355enc_autolevel_default.argtypes = [C.POINTER(Autolevel)]
+        L.mi355enc_autolevel_check.argtypes = [C.POINTER(Autolevel)]
+        L.mi355enc_autolevel_decide.argtypes = [C.POINTER(AutolevelMeas), C.POINTER(Autolevel), C.c_int, C.c_int, C.POINTER(C.c_int32 * 4), C.POINTER(AutolevelInfo), vp]
+        L.mi355enc_set_autolevel.argtypes = [vp, C.POINTER(Autolevel)]
+        L.mi355enc_get_autolevel.argtypes = [vp, C.POINTER(Autolevel)]
+        L.mi355enc_last_autolevel.argtypes = [vp, C.POINTER(Autolevel), C.POINTER(AutolevelInfo), vp]
+        L.mi355enc_debug_autolevel_bytes.restype = C.c_size_t
+        L.mi355enc_debug_autolevel_bytes.argtypes = [vp]
+        L.mi355enc_autolevel_probe_stage.argtypes = [vp, C.POINTER(Autolevel), vp, vp, C.POINTER(AutolevelInfo), vp]
+        L.mi355enc_autolevel_probe_measure.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(C.c_int * 4), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(AutolevelMeas)]
+        L.mi355enc_autolevel_probe_decide.argtypes = [vp, C.POINTER(AutolevelMeas), C.POINTER(Autolevel), C.c_int, C.c_int, C.POINTER(C.c_int32 * 4), C.POINTER(AutolevelInfo), vp]
         L.mi355enc_stabilize_default.restype = None
         L.mi355enc_stabilize_default.argtypes = [C.POINTER(Stabilize)]
         L.mi355enc_stabilize_check.argtypes = [C.POINTER(Stabilize)]
@@ -587,6 +627,51 @@ def stabilize_step(S, m, leak, lo, hi):
     if r:
         raise EncoderError("mi355enc_stabilize_step(%d, %d, %d, %d, %d): %d" % (S, m, leak, lo, hi, r))
     return int(s_out.value), int(o.value)
+
+
+def autolevel(a=None, **kw):
+    """An Autolevel: the defaults (off: mi355enc_autolevel_default), then a's (an Autolevel or a dict) and the keywords' on top; clip=c sets both clips.
+    autolevel(levels=1000, balance=1000) is the usual way to turn it on.  Not checked here."""
+    st = Autolevel()
+    load().mi355enc_autolevel_default(C.byref(st))
+    src = a.as_dict() if isinstance(a, Autolevel) else dict(a or {})
+    src.update(kw)
+    if "clip" in src:
+        src["clip_low"] = src["clip_high"] = src.pop("clip")
+    for k, v in src.items():
+        if k not in Autolevel.NAMES:
+            raise TypeError("autolevel: no parameter %r" % (k,))
+        setattr(st, k, int(v))
+    return st
+
+
+def autolevel_check(a=None, **kw):
+    """mi355enc_autolevel_check (host only): 0, or the error code for a value outside its range"""
+    return load().mi355enc_autolevel_check(C.byref(autolevel(a, **kw)))
+
+
+def autolevel_meas(hist, voters, su, sv, chroma):
+    """An AutolevelMeas from the histogram (256 counts), n, su, sv and NC"""
+    m = AutolevelMeas()
+    m.hist[:] = [int(v) for v in hist]
+    m.voters, m.chroma, m.su, m.sv = int(voters), int(chroma), int(su), int(sv)
+    return m
+
+
+def _autolevel_decide(fn, what, m, a, full_range, state, prime):
+    st = (C.c_int32 * 4)(*[int(v) for v in (state if state is not None else (0, 0, 0, 0))])
+    info, table = AutolevelInfo(), np.zeros(256, np.uint8)
+    m = m if isinstance(m, AutolevelMeas) else autolevel_meas(**m)
+    r = fn(C.byref(m), C.byref(autolevel(a)), int(full_range), int(bool(prime)), C.byref(st), C.byref(info), _p(table))
+    if r:
+        raise EncoderError("%s: failed (%d)" % (what, r))
+    return info.as_dict(), table, tuple(int(v) for v in st)
+
+
+def autolevel_decide(m, a, full_range=0, state=None, prime=False):
+    """mi355enc_autolevel_decide (host only): a picture's decision from its measurement (an AutolevelMeas or dict(hist=, voters=, su=, sv=, chroma=)), a
+    setting, the output range and the state {Lo, Hi, Du, Dv} going in -> (record, table, state coming out)"""
+    return _autolevel_decide(load().mi355enc_autolevel_decide, "autolevel_decide", m, a, full_range, state, prime)
 
 
 def warp(s=None, **kw):
@@ -1077,7 +1162,7 @@ class Encoder:
     (bitrate in bits/s as written through `bps`, key-int-max -> gop)."""
 
     def __init__(self, width, height, fps=60, gop=60, bitrate_bps=6_000_000, device_id=0, fixed_qp=-1, me_range=16,
-                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False, input_size=None, colorimetry=None, orientation=None, geometry=None, input_colorimetry=None, rate=None, hdr_input=None, adjust=None, denoise=None, stabilize=None):
+                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False, input_size=None, colorimetry=None, orientation=None, geometry=None, input_colorimetry=None, rate=None, hdr_input=None, adjust=None, denoise=None, stabilize=None, autolevel=None):
         self.L = load()
         cfg = Cfg()
         self.L.mi355enc_default_cfg(C.byref(cfg), width, height, fps, fps_den)
@@ -1141,6 +1226,12 @@ class Encoder:
         if stabilize is not None:  # dict(range=, leak=, margin=) or a Stabilize: the crop of `geometry` follows the camera's shake from the first picture on
             try:
                 self.set_stabilize(stabilize)
+            except EncoderError:
+                self.close()
+                raise
+        if autolevel is not None:  # dict(levels=, balance=, ...) or an Autolevel: automatic levels and white balance from the first picture on
+            try:
+                self.set_autolevel(autolevel)
             except EncoderError:
                 self.close()
                 raise
@@ -1260,6 +1351,48 @@ class Encoder:
         ptr = lambda a: None if a is None else _p(a)
         self._chk(self.L.mi355enc_stage_denoise(self.h, C.byref(st), ptr(hin[0]), ptr(hin[1]), _p(y), _p(uv), ptr(hy), ptr(huv)), "stage_denoise")
         return y, uv, hy, huv
+
+    def set_autolevel(self, a=None, **kw):
+        """Automatic levels and white balance from the next picture submitted on (any time, any thread, no GPU call); None or both strengths 0: off."""
+        self._chk(self.L.mi355enc_set_autolevel(self.h, C.byref(autolevel(a, **kw))), "set_autolevel")
+
+    def get_autolevel(self):
+        st = Autolevel()
+        self._chk(self.L.mi355enc_get_autolevel(self.h, C.byref(st)), "get_autolevel")
+        return st.as_dict()
+
+    def last_autolevel(self):
+        """(the setting, the record, the table) of the last collected picture; zeros for a picture the step did not run on"""
+        st, info, table = Autolevel(), AutolevelInfo(), np.zeros(256, np.uint8)
+        self._chk(self.L.mi355enc_last_autolevel(self.h, C.byref(st), C.byref(info), _p(table)), "last_autolevel")
+        return st.as_dict(), info.as_dict(), table
+
+    def debug_autolevel_bytes(self):
+        return int(self.L.mi355enc_debug_autolevel_bytes(self.h))
+
+    def stage_autolevel(self, a, y, uv):
+        """The three launches alone on host planes of the coded size, primed by that picture -> (y, uv, record, table)."""
+        y, uv = np.array(y, np.uint8, order="C"), np.array(uv, np.uint8, order="C")
+        assert y.shape == (16 * self.mbh, 16 * self.mbw) and uv.shape == (8 * self.mbh, 16 * self.mbw)
+        info, table = AutolevelInfo(), np.zeros(256, np.uint8)
+        self._chk(self.L.mi355enc_autolevel_probe_stage(self.h, C.byref(autolevel(a)), _p(y), _p(uv), C.byref(info), _p(table)), "stage_autolevel")
+        return y, uv, info.as_dict(), table
+
+    def autolevel_probe_measure(self, y, uv, rect, visible, full_range=0, reach=48):
+        """The measure launch alone: NV12 surfaces y (H x W) / uv (H / 2 x W), rect (x0, x1, y0, y1), visible (w, h) -> dict(hist, voters, chroma, su, sv)"""
+        y, uv = np.ascontiguousarray(y, np.uint8), np.ascontiguousarray(uv, np.uint8)
+        H, W = y.shape
+        assert uv.shape == (H // 2, W)
+        m = AutolevelMeas()
+        self._chk(self.L.mi355enc_autolevel_probe_measure(self.h, _p(y), _p(uv), W, H, C.byref((C.c_int * 4)(*[int(v) for v in rect])), int(visible[0]), int(visible[1]),
+                                                          int(full_range), int(reach), C.byref(m)), "autolevel_probe_measure")
+        return m.as_dict()
+
+    def autolevel_probe_decide(self, m, a, full_range=0, state=None, prime=False):
+        """The decide launch alone: autolevel_decide's arguments and answer"""
+        def fn(*args):
+            return self.L.mi355enc_autolevel_probe_decide(self.h, *args)
+        return _autolevel_decide(fn, "autolevel_probe_decide", m, a, full_range, state, prime)
 
     def set_stabilize(self, s=None, **kw):
         """electronic image stabilisation from the next submitted picture on (None: off); callable at any time from any thread"""

@@ -424,6 +424,65 @@ int mi355enc_stabilize_step(int S, int m, int leak, int lo, int hi, int *S_out, 
 int mi355enc_stabilize_probe_project(mi355enc_t *h, const uint8_t *luma, int stride, int step, int w, int ht, uint32_t *sums);
 int mi355enc_stabilize_probe_match(mi355enc_t *h, const uint32_t *prev, const uint32_t *cur, int w, int ht, const mi355enc_stabilize_t *s, const int bounds[4],
                                    const int state[2], int prime, mi355enc_stabilize_info_t *info);
+/* Automatic levels and white balance: per picture, a black point, a white point and a chroma offset are measured on the picture's coded
+ * surfaces, smoothed over time and applied to the same picture (feed-forward), all on the device: behind the noise filter and in front of the picture controls,
+ * so the manual controls trim on top of it and mix, layers and text are never touched.  Off by default, and off nothing is allocated or launched.  All integers;
+ * B and S are the output range's black level and scale (16 / 219 or 0 / 255).
+ *   setting      levels, balance 0 .. 1000 (thousandths of the full stretch / chroma correction; both 0: off), speed 1 .. 256 (256 follows at once), clip_low,
+ *                clip_high 0 .. 2000 (ten-thousandths of the samples that may fall outside the black / white point), max_gain 1000 .. 8000 (thousandths),
+ *                reach 0 .. 127 (how far from 128 a chroma sample may lie and still vote)
+ *   measured on  the visible samples of the picture rectangle (margins of the coded surface and a letterbox border never count): H[256] the count per luma
+ *                code, N their sum; the chroma sample (cx, cy) votes if its co-sited luma y = Y(2 cx, 2 cy) has B + (S >> 3) <= y <= B + S - (S >> 3) and
+ *                |Cb - 128|, |Cr - 128| <= reach; n voters, su / sv the sums of their Cb / Cr, NC the visible chroma samples
+ *   points       lo = the smallest v with 10000 cum(v) > clip_low N (cum: inclusive prefix sum; none: 255), hi = the largest v with
+ *                10000 (N - cum(v - 1)) > clip_high N (none: 0), both clipped into [B, B + S]; in 64 bits
+ *   chroma       valid iff n > 0 and 16 n >= NC; then du = (256 su) / n - 32768, dv likewise (1/256 code)
+ *   state        {Lo, Hi, Du, Dv} in 1/256 code: X = X + (((256 m - X) speed) >> 8) (floor); Du / Dv take du / dv as their 256 m and stay as they are with an
+ *                invalid measurement; then Lo, Hi are clipped into [256 B, 256 (B + S)] (a no-op unless the output range changed).  Priming -- the first
+ *                picture after off -> on, and the stage entry points -- sets Lo = 256 lo, Hi = 256 hi, Du = du, Dv = dv (0 when invalid)
+ *   strength     L = 256 B + ((Lo - 256 B) levels) / 1000, T = 256 (B + S) - ((256 (B + S) - Hi) levels) / 1000
+ *   gain limit   span = T - L, smin = ceil(256000 S / max_gain); span < smin: L = ((L + T) >> 1) - (smin >> 1), T = L + smin, then shifted into
+ *                [256 B, 256 (B + S)], span = smin
+ *   table        t = clip(256 v - L, 0, span), A[v] = B + (2 t S + span) / (2 span); not applied with levels 0
+ *   offsets      off_u = floor((Du balance + 128000) / 256000), off_v likewise; Cb' = clip255(Cb - off_u), Cr' = clip255(Cr - off_v)
+ * Applied in place over the whole picture rectangle, margins included; a border keeps its bytes. */
+typedef struct {
+    int levels, balance, speed, clip_low, clip_high, max_gain, reach;
+} mi355enc_autolevel_t;
+typedef struct {
+    uint32_t hist[256]; /* H */
+    uint32_t voters;    /* n */
+    uint32_t chroma;    /* NC */
+    uint64_t su, sv;
+} mi355enc_autolevel_meas_t;
+typedef struct {
+    int lo, hi, voters, du, dv; /* the picture's measurement */
+    int s_lo, s_hi, s_du, s_dv; /* the state behind it: Lo, Hi, Du, Dv */
+    int off_u, off_v, valid;
+} mi355enc_autolevel_info_t;
+void mi355enc_autolevel_default(mi355enc_autolevel_t *a); /* off: {0, 0, 16, 50, 50, 2000, 48} */
+int mi355enc_autolevel_check(const mi355enc_autolevel_t *a); /* host only: MI355ENC_OK or MI355ENC_ERR_ARG */
+/* host only: the decision of a picture.  state: {Lo, Hi, Du, Dv} going in (Lo, Hi in 0 .. 65280, Du, Dv in -32768 .. 32767; ignored with prime) and coming
+ * out; m: su, sv <= 255 voters, voters <= chroma <= 2^24, the sum of hist <= 2^26.  table: 256 bytes (also written with levels 0, where it is not applied) */
+int mi355enc_autolevel_decide(const mi355enc_autolevel_meas_t *m, const mi355enc_autolevel_t *a, int full_range, int prime, int32_t state[4],
+                              mi355enc_autolevel_info_t *info, uint8_t table[256]);
+/* At any time and from any thread, no GPU call; latched once per input picture at its submit.  NULL or both strengths 0: off.  With an active setting
+ * mi355enc_submit_device never encodes in place: the caller's planes are only read. */
+int mi355enc_set_autolevel(mi355enc_t *h, const mi355enc_autolevel_t *a);
+int mi355enc_get_autolevel(const mi355enc_t *h, mi355enc_autolevel_t *a);
+/* of the last collected picture (any pointer may be NULL); MI355ENC_ERR_STATE before the first collect.  A picture the step did not run on reports zeros */
+int mi355enc_last_autolevel(mi355enc_t *h, mi355enc_autolevel_t *a, mi355enc_autolevel_info_t *info, uint8_t table[256]);
+size_t mi355enc_debug_autolevel_bytes(const mi355enc_t *h); /* device bytes of the step: 0 until the first autolevelled picture */
+/* the step alone (tests): host NV12 planes of the coded size, in and out, like mi355enc_stage_adjust; the three launches on that picture, primed by it.  The
+ * handle's own setting is not touched; a stream that follows primes.  info, table may be NULL */
+int mi355enc_autolevel_probe_stage(mi355enc_t *h, const mi355enc_autolevel_t *a, uint8_t *y, uint8_t *uv, mi355enc_autolevel_info_t *info, uint8_t table[256]);
+/* the first two launches alone (tests), in the frame of the single-stage entry points.  probe_measure: host NV12 surfaces of W x H (W a multiple of 16 up to
+ * 8192, H even up to 8192) at stride W, rect {x0, x1, y0, y1} (even, inside the surfaces) and the visible size vw x vh (the rectangle's visible part not
+ * empty) -> the measurement summed over the workgroups' slabs.  probe_decide: mi355enc_autolevel_decide on the device */
+int mi355enc_autolevel_probe_measure(mi355enc_t *h, const uint8_t *y, const uint8_t *uv, int W, int H, const int rect[4], int vw, int vh, int full_range, int reach,
+                                     mi355enc_autolevel_meas_t *m);
+int mi355enc_autolevel_probe_decide(mi355enc_t *h, const mi355enc_autolevel_meas_t *m, const mi355enc_autolevel_t *a, int full_range, int prime, int32_t state[4],
+                                    mi355enc_autolevel_info_t *info, uint8_t table[256]);
 /* Lens, roll and keystone correction: the coded picture is resampled through a coarse mesh of source positions, the first step on the
  * coded surfaces (in front of the colour step, the noise filter, the picture controls, the mix, layers and text; behind the geometry and the stabiliser's
  * crop); off by default, and off nothing is allocated or launched.  All integers; >> is a floor.
@@ -866,6 +925,9 @@ int mi355enc_stage_deblock(mi355enc_t *h, uint8_t *rec_y, uint8_t *rec_uv, const
  * its clear at the handle's input size on slot 0's raw staging buffer, 30 the match launch on whatever the projection buffers hold.  Both leave the
  * trajectory unprimed: the next picture submitted primes.
  * 31 the warp set last (mi355enc_set_warp / mi355enc_set_warp_mesh; MI355ENC_ERR_STATE when it is off) on slot 0's source surfaces.
+ * 32 / 33 / 34 the launches of automatic levels and white balance with the value set last (mi355enc_set_autolevel; MI355ENC_ERR_STATE when it is off) on slot
+ * 0's source surfaces: 32 measure, 33 decide (on the slabs of a measure launch in front of the timed ones), 34 apply (with that decision's table and
+ * offsets, so the surfaces change with every launch).  They leave the state unprimed: the next picture submitted primes.
  * Uses whatever the handle's surfaces currently hold.  Returns average ms per launch. */
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms);
 
