@@ -13,6 +13,7 @@
 //   enc_csc.cpp       colorimetry: the setters, the RGB matrix and the YUV -> YUV table, the colour step's launch, their stage entry points
 //   enc_adjust.cpp    picture controls: setter, latch, the two launch forms and the scratch plane, its stage entry point
 //   enc_autolevel.cpp automatic levels and white balance: setter, latch, the three launches and the device block, the probes and the stage entry point
+//   enc_lut3d.cpp     3D colour LUT: setter, latch, the table's way to the device, the launch, its probe and timed stage
 //   enc_denoise.cpp   temporal noise reduction: setter, latch, the launch and the handle's history, its stage entry point
 //   enc_stab.cpp      electronic image stabilisation: setter, latch, the estimate in front of every scale launch, its probes and timed stages
 //   enc_warp.cpp      lens, roll and keystone correction: setters, latch, the mesh's way to the device, the launch and the scratch pair, its stage entry point
@@ -47,6 +48,7 @@
 #include "stab_host.h"
 #include "autolevel_host.h"
 #include "warp_host.h"
+#include "lut3d_host.h"
 #include "enc_plan.hpp"
 #include "enc_sync.hpp"
 
@@ -149,6 +151,10 @@ struct slot_t {
     // the warp: what submit latched for this picture (warp_on false: nothing; warp_gen: the count of sets its mesh belongs to); warp_send: the slot's pinned copy
     // holds that mesh and it travels in front of the launch; applied once, to the input's own slot, first in ingest_end
     bool warp_on, warp_send; mi355enc_warp_t warp; unsigned warp_gen;
+    // the 3D LUT: what submit latched for this picture (lut_on false: nothing; lut_gen: the count of sets its table belongs to) with the coefficients of the
+    // output matrix and range it met; lut_send: the slot's pinned copy holds that table and it travels in front of the launch; applied once, to the input's own
+    // slot, in ingest_end
+    bool lut_on, lut_send; mi355enc_lut3d_t lut; unsigned lut_gen; int32_t lut_coef[LUT3D_COEF_WORDS];
 };
 
 struct mi355enc {
@@ -309,6 +315,19 @@ struct mi355enc {
     uint8_t *d_warp_y = nullptr, *d_warp_uv = nullptr;
     int32_t *d_warp_mesh = nullptr, *h_warp_mesh = nullptr;
     size_t warp_bytes = 0;
+    // the 3D colour LUT (mi355enc_set_lut3d): what the control thread set last (under lut_mu: the setting, its table on the heap, the count of
+    // sets that turned it on; submit latches it per input picture) and what the last collected picture carried.  Allocated by the first graded picture, for 65^3
+    // nodes whatever the size set: d_lut (the table the launches read; lut_sent: the generation it holds, or will hold by the order of the upload stream) and h_lut
+    // (pinned: one table per slot).  lut_bytes: the device bytes.
+    std::mutex lut_mu;
+    bool lut_on = false;
+    mi355enc_lut3d_t lut_cur = {0, 0}, lut_last = {0, 0};
+    uint32_t *lut_nodes = nullptr;
+    unsigned lut_gen = 0, lut_sent = 0, lut_last_gen = 0;
+    bool lut_last_have = false;
+    uint32_t *d_lut = nullptr, *h_lut = nullptr;
+    size_t lut_bytes = 0;
+    int lut_form = -1; // (mi355enc_debug_lut3d_form: the launch form of the handle's own launches; -1: the plan's)
     bool warp_staging = true; // (mi355enc_debug_warp_staging: false -- every workgroup of the launch takes the direct form)
     // frame-rate conversion (mi355enc_set_rate_conversion).  rate.mode 0: off, and nothing below is used but last_count.  rate.max_fill is
     // clamped to pipeline_depth.  rate_plan: the rule's state; ingest_begin steps a copy of it (rate_next, with what the step yields: rate_n pictures, their pts
@@ -513,6 +532,16 @@ bool autolevel_time_ready(mi355enc_t *h, int stage);         // mi355enc_time_st
 int autolevel_time_prepare(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // the block, and a measure and a (priming) decide launch on slot 0's surfaces
 int autolevel_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // 32 measure, 33 decide, 34 apply
 void autolevel_time_done(mi355enc_t *h);                     // ... behind the timed launches: the next picture primes
+// enc_lut3d.cpp (3D colour LUT)
+int lut3d_latch(mi355enc_t *h, slot_t *s, bool own);         // the value set last becomes the slot's (beside autolevel_latch); own: the slot the input goes into, which also takes the table where it is a new one
+int lut3d_draw(mi355enc_t *h, slot_t *s, hipStream_t st);    // the slot's LUT on its coded surfaces, behind everything enqueued on st so far (a new table travels in front of it); nothing with none
+void lut3d_collected(mi355enc_t *h, slot_t *s);              // collect(): books what the picture carried as the last picture's
+void lut3d_free(mi355enc_t *h);
+void lut3d_close(mi355enc_t *h);
+bool lut3d_time_ready(mi355enc_t *h, int stage);             // mi355enc_time_stage 35: the value set last is on
+int lut3d_time_prepare(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // the table set last onto the device
+int lut3d_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x);
+void lut3d_time_done(mi355enc_t *h);                         // ... behind the timed launches: the next graded picture sends its table again
 // enc_warp.cpp (lens, roll and keystone correction)
 int warp_latch(mi355enc_t *h, slot_t *s, bool own);          // the value set last becomes the slot's (beside stab_latch); own: the slot the input goes into, which also takes the mesh where it is a new one
 int warp_draw(mi355enc_t *h, slot_t *s, hipStream_t st);     // the slot's warp on its coded surfaces, behind everything enqueued on st so far (a new mesh travels in front of it); nothing with none

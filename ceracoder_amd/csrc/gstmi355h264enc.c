@@ -115,6 +115,9 @@ typedef struct {
     /* automatic levels and white balance on the device (mi355enc_set_autolevel): auto-levels, auto-balance (doubles 0 .. 1, stored as
      * thousandths, lround), auto-speed, auto-clip (percent, both clips), auto-max-gain; stored under the object lock and forwarded like the picture controls */
     mi355enc_autolevel_t al;
+    /* a 3D colour LUT on the device (mi355enc_set_lut3d): lut3d-location, the path of a .cube file, read and parsed in the setter (""
+     * or NULL: off; lut_nodes: its lut_size^3 nodes, NULL: none), and lut3d-strength, a double 0 .. 1 stored as round(256 x); under the object lock */
+    gchar *lut_location; guint32 *lut_nodes; gint lut_size, lut_strength;
     /* stabilize (mi355enc_set_stabilize): the margin in input samples per side (0: off; odd values count as the even value below), added
      * to each of crop-* when the geometry is built -- so a change while playing is a crop change --, and the estimator's range and leak */
     gint stab, stab_range, stab_leak;
@@ -154,7 +157,7 @@ enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME
        PROP_SNAP_LOCATION, PROP_SNAP_INTERVAL, PROP_SNAP_QUALITY, PROP_SNAP_REDUCE, PROP_SNAP_SOURCE,
        PROP_OUTPUT_COLORIMETRY, PROP_RATE_CONVERSION, PROP_OUTPUT_FRAMERATE, PROP_MAX_FILL, PROP_HDR_INPUT, PROP_HDR_PEAK_NITS, PROP_HDR_TARGET_NITS,
        PROP_ADJ_BRIGHTNESS, PROP_ADJ_CONTRAST, PROP_ADJ_HUE, PROP_ADJ_SATURATION, PROP_ADJ_GAMMA, PROP_ADJ_SHARPEN, PROP_ADJ_SHARPEN_THRESHOLD,
-       PROP_DENOISE_LUMA, PROP_DENOISE_CHROMA, PROP_DENOISE_MOTION, PROP_STABILIZE, PROP_STABILIZE_RANGE, PROP_STABILIZE_LEAK, PROP_AUTO_LEVELS, PROP_AUTO_BALANCE, PROP_AUTO_SPEED, PROP_AUTO_CLIP, PROP_AUTO_MAX_GAIN,
+       PROP_DENOISE_LUMA, PROP_DENOISE_CHROMA, PROP_DENOISE_MOTION, PROP_STABILIZE, PROP_STABILIZE_RANGE, PROP_STABILIZE_LEAK, PROP_AUTO_LEVELS, PROP_AUTO_BALANCE, PROP_AUTO_SPEED, PROP_AUTO_CLIP, PROP_AUTO_MAX_GAIN, PROP_LUT3D_LOCATION, PROP_LUT3D_STRENGTH,
        PROP_LENS_K1, PROP_LENS_K2, PROP_LENS_ZOOM, PROP_ROLL, PROP_KEYSTONE_H, PROP_KEYSTONE_V, PROP_WARP_FILTER };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
@@ -340,9 +343,48 @@ static void image_set_location(GstMi355H264Enc *s, const gchar *path) {
     GST_OBJECT_UNLOCK(s);
 }
 
+/* stored table and strength -> the encoder, if one is open (object lock held; the library checks, copies and stores: no GPU call, any thread) */
+static void lut3d_forward(GstMi355H264Enc *s) {
+    if (!s->enc) return;
+    const mi355enc_lut3d_t set = {s->lut_size, s->lut_strength};
+    if (mi355enc_set_lut3d(s->enc, s->lut_nodes ? &set : NULL, s->lut_nodes) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the 3D LUT: it keeps its previous one");
+}
+/* lut3d-location: the file is read and parsed here, in the setter, outside the object lock (the warning goes to the bus).  "" or NULL: off.  A file that cannot
+ * be read or that the parser refuses leaves the step as it was */
+static void lut3d_set_location(GstMi355H264Enc *s, const gchar *path) {
+    guint32 *nodes = NULL;
+    int n = 0;
+    if (path && *path) {
+        gchar *data = NULL;
+        gsize len = 0;
+        GError *err = NULL;
+        if (!g_file_get_contents(path, &data, &len, &err)) {
+            GST_ELEMENT_WARNING(s, RESOURCE, OPEN_READ, ("mi355h264enc: cannot read lut3d-location \"%s\": the 3D LUT stays as it was", path), ("%s", err ? err->message : "?"));
+            g_clear_error(&err);
+            return;
+        }
+        const gsize cap = 65 * 65 * 65;
+        nodes = g_malloc(cap * sizeof *nodes);
+        const int r = mi355enc_lut3d_parse_cube(data, len, nodes, cap, &n);
+        g_free(data);
+        if (r != MI355ENC_OK) {
+            g_free(nodes);
+            GST_ELEMENT_WARNING(s, STREAM, FORMAT, ("mi355h264enc: lut3d-location \"%s\" is not a .cube file this element takes (LUT_3D_SIZE 2 .. 65, unit input range): "
+                                                    "the 3D LUT stays as it was", path), ("mi355enc_lut3d_parse_cube returned %d", r));
+            return;
+        }
+    }
+    GST_OBJECT_LOCK(s);
+    g_free(s->lut_location); s->lut_location = g_strdup(path ? path : "");
+    g_free(s->lut_nodes); s->lut_nodes = nodes; s->lut_size = n;
+    lut3d_forward(s);
+    GST_OBJECT_UNLOCK(s);
+}
+
 static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *ps) {
     GstMi355H264Enc *s = GST_MI355H264ENC(obj);
     if (id == PROP_IMG_LOCATION) { image_set_location(s, g_value_get_string(val)); return; }
+    if (id == PROP_LUT3D_LOCATION) { lut3d_set_location(s, g_value_get_string(val)); return; }
     GST_OBJECT_LOCK(s);
     switch (id) {
     case PROP_SNAP_LOCATION: g_free(s->snap_location); s->snap_location = g_value_dup_string(val); s->snap_next = GST_CLOCK_TIME_NONE; break;
@@ -368,6 +410,7 @@ static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *
     case PROP_AUTO_SPEED: s->al.speed = g_value_get_int(val); autolevel_forward(s); break;
     case PROP_AUTO_CLIP: s->al.clip_low = s->al.clip_high = (int)lround(100.0 * g_value_get_double(val)); autolevel_forward(s); break;
     case PROP_AUTO_MAX_GAIN: s->al.max_gain = (int)lround(1000.0 * g_value_get_double(val)); autolevel_forward(s); break;
+    case PROP_LUT3D_STRENGTH: s->lut_strength = (int)lround(256.0 * g_value_get_double(val)); lut3d_forward(s); break;
     case PROP_DENOISE_LUMA: s->dn.luma = g_value_get_int(val); denoise_forward(s); break;
     case PROP_DENOISE_CHROMA: s->dn.chroma = g_value_get_int(val); denoise_forward(s); break;
     case PROP_DENOISE_MOTION: s->dn_motion = g_value_get_int(val); denoise_forward(s); break;
@@ -458,6 +501,8 @@ static void get_property(GObject *obj, guint id, GValue *val, GParamSpec *ps) {
     case PROP_AUTO_SPEED: g_value_set_int(val, s->al.speed); break;
     case PROP_AUTO_CLIP: g_value_set_double(val, s->al.clip_low / 100.0); break;
     case PROP_AUTO_MAX_GAIN: g_value_set_double(val, s->al.max_gain / 1000.0); break;
+    case PROP_LUT3D_LOCATION: g_value_set_string(val, s->lut_location ? s->lut_location : ""); break;
+    case PROP_LUT3D_STRENGTH: g_value_set_double(val, s->lut_strength / 256.0); break;
     case PROP_DENOISE_LUMA: g_value_set_int(val, s->dn.luma); break;
     case PROP_DENOISE_CHROMA: g_value_set_int(val, s->dn.chroma); break;
     case PROP_DENOISE_MOTION: g_value_set_int(val, s->dn_motion); break;
@@ -875,6 +920,7 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     image_forward(s, TRUE);                 /* ... nor the image layer */
     adjust_forward(s);                      /* ... nor the picture controls */
     autolevel_forward(s);                   /* ... nor the automatic levels and white balance */
+    lut3d_forward(s);                       /* ... nor the 3D LUT */
     denoise_forward(s);                     /* ... nor the noise filter */
     stabilize_forward(s);                   /* ... nor the stabiliser */
     warp_forward(s);                        /* ... nor the warp */
@@ -1222,6 +1268,8 @@ static void finalize(GObject *obj) {
     g_free(GST_MI355H264ENC(obj)->img_location);
     g_free(GST_MI355H264ENC(obj)->img_rgba);
     g_free(GST_MI355H264ENC(obj)->snap_location);
+    g_free(GST_MI355H264ENC(obj)->lut_location);
+    g_free(GST_MI355H264ENC(obj)->lut_nodes);
     g_free(GST_MI355H264ENC(obj)->out_colorimetry);
     g_mutex_clear(&GST_MI355H264ENC(obj)->snap_mu); g_mutex_clear(&GST_MI355H264ENC(obj)->snap_enc_mu); g_cond_clear(&GST_MI355H264ENC(obj)->snap_cv);
     G_OBJECT_CLASS(gst_mi355h264enc_parent_class)->finalize(obj);
@@ -1337,6 +1385,9 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
     g_object_class_install_property(g, PROP_AUTO_SPEED, g_param_spec_int("auto-speed", "Automatic speed", "how fast the automatic levels and white balance follow the measurement, in 1/256 per picture; 256: at once (a knob, not a tuned value)", 1, 256, 16, F));
     g_object_class_install_property(g, PROP_AUTO_CLIP, g_param_spec_double("auto-clip", "Automatic clip", "the percentage of the samples that may fall below the black point, and likewise above the white point", 0.0, 20.0, 0.5, F));
     g_object_class_install_property(g, PROP_AUTO_MAX_GAIN, g_param_spec_double("auto-max-gain", "Automatic maximum gain", "the largest contrast gain the automatic levels apply", 1.0, 8.0, 2.0, F));
+    g_object_class_install_property(g, PROP_LUT3D_LOCATION, g_param_spec_string("lut3d-location", "3D LUT location",
+        "a 3D colour LUT on the GPU, behind the noise filter and in front of automatic levels and the picture controls: the path of a .cube file (LUT_3D_SIZE 2 .. 65, tetrahedral interpolation), read when the property is set, at any time; empty: off.  A file that cannot be read or parsed posts a warning and leaves the step as it was", "", F));
+    g_object_class_install_property(g, PROP_LUT3D_STRENGTH, g_param_spec_double("lut3d-strength", "3D LUT strength", "how much of the 3D LUT's grade is applied, per sample between the input and the graded value; 0: off", 0.0, 1.0, 1.0, F));
     g_object_class_install_property(g, PROP_DENOISE_LUMA, g_param_spec_int("denoise-luma", "Denoise luma", "temporal noise reduction on the GPU, motion-adaptive, in front of the picture controls: the luma noise amplitude in codes that is filtered fully; 0: off", 0, MI355ENC_DENOISE_MAX, 0, F));
     g_object_class_install_property(g, PROP_DENOISE_CHROMA, g_param_spec_int("denoise-chroma", "Denoise chroma", "temporal noise reduction on the GPU: the chroma noise amplitude in codes that is filtered fully; 0: off", 0, MI355ENC_DENOISE_MAX, 0, F));
     g_object_class_install_property(g, PROP_STABILIZE, g_param_spec_int("stabilize", "Stabilize", "electronic image stabilisation on the GPU: the margin in input samples per side that the crop may move by to follow the camera's shake (added to each of crop-*; odd values count as the even value below); 0: off", 0, MI355ENC_STABILIZE_MARGIN_MAX, 0, F));
@@ -1372,6 +1423,7 @@ static void gst_mi355h264enc_init(GstMi355H264Enc *s) {
     mi355enc_adjust_default(&s->adj);
     mi355enc_denoise_default(&s->dn);
     mi355enc_autolevel_default(&s->al);
+    s->lut_location = NULL; s->lut_nodes = NULL; s->lut_size = 0; s->lut_strength = 256;
     s->dn_motion = 0;
     s->stab = 0; s->stab_range = 16; s->stab_leak = 16;
     s->warp_k1 = s->warp_k2 = s->warp_roll = s->warp_kh = s->warp_kv = 0.0; s->warp_zoom = 1.0; s->warp_filter = 1;

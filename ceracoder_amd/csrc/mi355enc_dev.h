@@ -266,6 +266,10 @@ int k_launch_stab_match(const unsigned *prev, const unsigned *cur, int w, int h,
 int k_launch_autolevel_measure(const uint8_t *y, const uint8_t *uv, int W, int H, const int rect[4], int vw, int vh, int full_range, int reach, unsigned *slabs, hipStream_t s);
 int k_launch_autolevel_decide(const unsigned *slabs, int nslabs, unsigned NC, const int set[7], int full_range, int prime, int *state, int *rec, hipStream_t s);
 int k_launch_autolevel_apply(uint8_t *y, uint8_t *uv, int W, int H, const int rect[4], int luma, int chroma, const int *rec, hipStream_t s);
+/* A 3D colour LUT (k_lut3d.hip; the rule: DESIGN.md section 29, lut3d_host.h) on NV12 surfaces of W x H at stride W inside rect, in place: nodes N^3 checked
+ * words on the device, strength 1 .. 256, coef mi355enc_lut3d_coefficients', form 0 direct (nodes from global memory) or 1 staged (the table in LDS: N up to
+ * LUT3D_STAGED_FIT, nodes 16-byte aligned).  -1: arguments outside that, and nothing is launched */
+int k_launch_lut3d(uint8_t *y, uint8_t *uv, int W, int H, const int rect[4], const uint32_t *nodes, int N, int strength, const int32_t coef[19], int form, hipStream_t s);
 void k_launch_pack(const mb_info_t *d_mbi, const int16_t *d_levels, int nmb, int mbw, unsigned *d_off, mb_info_t *h_mbi, int16_t *h_packed,
                    unsigned *h_hdr, const unsigned *d_err, hipStream_t s);
 int k_deblock_diags(int mbw, int mbh);

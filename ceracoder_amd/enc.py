@@ -41,6 +41,9 @@ STABILIZE_RANGE_MAX, STABILIZE_MARGIN_MAX = 32, 1024
 STAGE_WARP = 31  # the warp set last on slot 0's surfaces
 STAGE_AUTOLEVEL_MEASURE, STAGE_AUTOLEVEL_DECIDE, STAGE_AUTOLEVEL_APPLY = 32, 33, 34  # the launches of automatic levels and white balance
 WARP_BILINEAR, WARP_BICUBIC = 0, 1
+STAGE_LUT3D = 35  # the 3D colour LUT set last on slot 0's surfaces
+LUT3D_N_MIN, LUT3D_N_MAX = 2, 65
+LUT3D_DIRECT, LUT3D_STAGED = 0, 1  # the launch forms (lut3d_plan, lut3d_probe)
 WARP_NODE_MIN, WARP_NODE_MAX = -2048 * 256, 10240 * 256
 STAGE_DENOISE, STAGE_DENOISE_PRIME = 25, 26  # the temporal noise filter set last on slot 0's surfaces and the handle's history: filtering, priming
 STAGE_HDR_P010, STAGE_HDR_I420_10, STAGE_HDR_V210, STAGE_DEEP_P010 = 19, 20, 21, 22  # the tone-mapping launch per format, and the plain P010 launch beside it
@@ -84,6 +87,8 @@ EXPORTS = [
     "mi355enc_debug_autolevel_bytes", "mi355enc_autolevel_probe_stage", "mi355enc_autolevel_probe_measure", "mi355enc_autolevel_probe_decide",
     "mi355enc_warp_params_default", "mi355enc_warp_coeff", "mi355enc_warp_mesh_size", "mi355enc_warp_mesh_check", "mi355enc_warp_build", "mi355enc_warp_apply_host",
     "mi355enc_set_warp", "mi355enc_set_warp_mesh", "mi355enc_get_warp", "mi355enc_last_warp", "mi355enc_debug_warp_bytes", "mi355enc_warp_probe", "mi355enc_warp_plan", "mi355enc_debug_warp_staging",
+    "mi355enc_lut3d_coefficients", "mi355enc_lut3d_check", "mi355enc_lut3d_identity", "mi355enc_lut3d_parse_cube", "mi355enc_lut3d_apply_host", "mi355enc_lut3d_plan",
+    "mi355enc_set_lut3d", "mi355enc_get_lut3d", "mi355enc_last_lut3d", "mi355enc_debug_lut3d_bytes", "mi355enc_lut3d_probe", "mi355enc_debug_lut3d_form",
 ]
 
 
@@ -187,6 +192,14 @@ class AutolevelInfo(C.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class Lut3d(C.Structure):
+    """mi355enc_lut3d_t: the nodes per axis and the strength 0 .. 256"""
+    _fields_ = [("size", C.c_int), ("strength", C.c_int)]
+
+    def as_dict(self):
+        return dict(size=int(self.size), strength=int(self.strength))
 
 
 class Warp(C.Structure):
@@ -396,6 +409,19 @@ def load():
         L.mi355enc_warp_probe.argtypes = [vp, C.POINTER(Warp), vp, vp, vp]
         L.mi355enc_warp_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.mi355enc_debug_warp_staging.argtypes = [vp, C.c_int]
+        L.mi355enc_lut3d_coefficients.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int32 * 19)]
+        L.mi355enc_lut3d_check.argtypes = [vp, C.c_int]
+        L.mi355enc_lut3d_identity.argtypes = [C.c_int, vp]
+        L.mi355enc_lut3d_parse_cube.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_int)]
+        L.mi355enc_lut3d_apply_host.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.POINTER(C.c_int * 4)]
+        L.mi355enc_lut3d_plan.argtypes = [C.c_int]
+        L.mi355enc_set_lut3d.argtypes = [vp, C.POINTER(Lut3d), vp]
+        L.mi355enc_get_lut3d.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(Lut3d)]
+        L.mi355enc_last_lut3d.argtypes = [vp, C.POINTER(Lut3d), C.POINTER(C.c_uint)]
+        L.mi355enc_debug_lut3d_bytes.restype = C.c_size_t
+        L.mi355enc_debug_lut3d_bytes.argtypes = [vp]
+        L.mi355enc_lut3d_probe.argtypes = [vp, C.POINTER(Lut3d), vp, vp, vp, C.c_int]
+        L.mi355enc_debug_lut3d_form.argtypes = [vp, C.c_int]
         L.mi355enc_set_quality_metrics.argtypes = [vp, C.c_int]
         L.mi355enc_last_quality.argtypes = [vp, C.POINTER(Quality)]
         L.mi355enc_quality_totals.argtypes = [vp, C.POINTER(Quality)]
@@ -672,6 +698,71 @@ def autolevel_decide(m, a, full_range=0, state=None, prime=False):
     """mi355enc_autolevel_decide (host only): a picture's decision from its measurement (an AutolevelMeas or dict(hist=, voters=, su=, sv=, chroma=)), a
     setting, the output range and the state {Lo, Hi, Du, Dv} going in -> (record, table, state coming out)"""
     return _autolevel_decide(load().mi355enc_autolevel_decide, "autolevel_decide", m, a, full_range, state, prime)
+
+
+def _lut3d_nodes(nodes):
+    """(nodes as a contiguous uint32 array, N); ValueError unless their number is a cube"""
+    n = np.ascontiguousarray(nodes, np.uint32).reshape(-1)
+    N = int(round(n.size ** (1.0 / 3.0)))
+    if N ** 3 != n.size:
+        raise ValueError("lut3d: %d nodes are no cube" % n.size)
+    return n, N
+
+
+def lut3d_coefficients(matrix, full_range):
+    """mi355enc_lut3d_coefficients (host only): the 19 words -- Minv, Mf, yoff -- of a matrix code (1, 5, 6, 9) and a range"""
+    out = (C.c_int32 * 19)()
+    r = load().mi355enc_lut3d_coefficients(int(matrix), int(full_range), C.byref(out))
+    if r:
+        raise EncoderError("lut3d_coefficients: failed (%d)" % r)
+    return [int(v) for v in out]
+
+
+def lut3d_check(nodes, N):
+    """mi355enc_lut3d_check (host only): 0, or the error code for N outside 2 .. 65 or a node with a top bit set"""
+    return load().mi355enc_lut3d_check(_p(np.ascontiguousarray(nodes, np.uint32)), int(N))
+
+
+def lut3d_identity(N):
+    """mi355enc_lut3d_identity (host only): the identity table of N nodes per axis"""
+    if not LUT3D_N_MIN <= N <= LUT3D_N_MAX:
+        raise EncoderError("lut3d_identity: N outside %d .. %d" % (LUT3D_N_MIN, LUT3D_N_MAX))
+    nodes = np.zeros(N ** 3, np.uint32)
+    r = load().mi355enc_lut3d_identity(int(N), _p(nodes))
+    if r:
+        raise EncoderError("lut3d_identity: failed (%d)" % r)
+    return nodes
+
+
+def parse_cube(text, cap=LUT3D_N_MAX ** 3):
+    """mi355enc_lut3d_parse_cube (host only, no locale): a .cube text (str or bytes) -> (nodes, N); EncoderError where the file is refused"""
+    data = text.encode("latin-1", "replace") if isinstance(text, str) else bytes(text)
+    nodes, N = np.zeros(max(int(cap), 1), np.uint32), C.c_int(0)
+    r = load().mi355enc_lut3d_parse_cube(data, len(data), _p(nodes), int(cap), C.byref(N))
+    if r:
+        raise EncoderError("parse_cube: refused (%d)" % r)
+    return nodes[:N.value ** 3].copy(), int(N.value)
+
+
+def lut3d_apply_host(nodes, strength, matrix, full_range, y, uv, rect=None):
+    """mi355enc_lut3d_apply_host (host only): the rule on NV12 planes y (H x W) / uv (H / 2 x W) inside rect (x0, x1, y0, y1; all of it without) -> new (y, uv)"""
+    n, N = _lut3d_nodes(nodes)
+    y, uv = np.array(y, np.uint8, order="C"), np.array(uv, np.uint8, order="C")
+    H, W = y.shape
+    assert uv.shape == (H // 2, W)
+    r4 = (C.c_int * 4)(*[int(v) for v in (rect if rect is not None else (0, W, 0, H))])
+    r = load().mi355enc_lut3d_apply_host(_p(n), N, int(strength), int(matrix), int(full_range), _p(y), _p(uv), W, H, C.byref(r4))
+    if r:
+        raise EncoderError("lut3d_apply_host: failed (%d)" % r)
+    return y, uv
+
+
+def lut3d_plan(N):
+    """mi355enc_lut3d_plan (host only): LUT3D_DIRECT or LUT3D_STAGED, the launch form that serves N"""
+    r = load().mi355enc_lut3d_plan(int(N))
+    if r < 0:
+        raise EncoderError("lut3d_plan: failed (%d)" % r)
+    return r
 
 
 def warp(s=None, **kw):
@@ -1439,6 +1530,45 @@ class Encoder:
             self._chk(self.L.mi355enc_set_warp(self.h, None, None), "set_warp")
         else:
             self._chk(self.L.mi355enc_set_warp(self.h, C.byref(warp(s)), C.byref(warp_params(p, **kw))), "set_warp")
+
+    def set_lut3d(self, nodes_or_cube_text=None, strength=256):
+        """A 3D colour LUT from the next picture submitted on (any time, any thread, no GPU call): N^3 packed nodes, or the text of a .cube file (str or
+        bytes), with a strength 0 .. 256; None: off.  The size may change while the stream runs; pictures in flight keep the table they were submitted with."""
+        if nodes_or_cube_text is None:
+            self._chk(self.L.mi355enc_set_lut3d(self.h, None, None), "set_lut3d")
+            return
+        if isinstance(nodes_or_cube_text, (str, bytes)):
+            n, N = parse_cube(nodes_or_cube_text)
+        else:
+            n, N = _lut3d_nodes(nodes_or_cube_text)
+        self._chk(self.L.mi355enc_set_lut3d(self.h, C.byref(Lut3d(N, int(strength))), _p(n)), "set_lut3d")
+
+    def get_lut3d(self):
+        """the setting set last as a dict(size=, strength=), None when off"""
+        on, st = C.c_int(0), Lut3d()
+        self._chk(self.L.mi355enc_get_lut3d(self.h, C.byref(on), C.byref(st)), "get_lut3d")
+        return st.as_dict() if on.value else None
+
+    def last_lut3d(self):
+        """(the setting, the generation of the table) the last collected picture was graded with; zeros for an ungraded one"""
+        st, g = Lut3d(), C.c_uint(0)
+        self._chk(self.L.mi355enc_last_lut3d(self.h, C.byref(st), C.byref(g)), "last_lut3d")
+        return st.as_dict(), int(g.value)
+
+    def debug_lut3d_bytes(self):
+        return int(self.L.mi355enc_debug_lut3d_bytes(self.h))
+
+    def debug_lut3d_form(self, form):
+        """measurements: the launch form of the handle's own LUT launches -- -1 the plan's, LUT3D_DIRECT, LUT3D_STAGED (the picture is the same)"""
+        self._chk(self.L.mi355enc_debug_lut3d_form(self.h, int(form)), "debug_lut3d_form")
+
+    def lut3d_probe(self, nodes, y, uv, strength=256, form=-1):
+        """The LUT launch alone on host planes of the coded size; form -1: the plan's, LUT3D_DIRECT / LUT3D_STAGED: that one.  Returns the graded copies."""
+        n, N = _lut3d_nodes(nodes)
+        y, uv = np.ascontiguousarray(y, np.uint8).copy(), np.ascontiguousarray(uv, np.uint8).copy()
+        assert y.shape == (self.mbh * 16, self.mbw * 16) and uv.shape == (self.mbh * 8, self.mbw * 16)
+        self._chk(self.L.mi355enc_lut3d_probe(self.h, C.byref(Lut3d(N, int(strength))), _p(n), _p(y), _p(uv), int(form)), "lut3d_probe")
+        return y, uv
 
     def set_warp_mesh(self, s, mesh):
         """... through the caller's own mesh, int32 (ny, nx, 2) for the coded visible size (s None: off)"""

@@ -539,6 +539,57 @@ int mi355enc_debug_warp_staging(mi355enc_t *h, int on); /* measurements: 0 -- ev
 /* the launch alone (tests), in the frame of the single-stage entry points (named as the stabiliser's probes are): y / uv are host planes of the coded size (16 mbw x 16 mbh, chroma interleaved),
  * warped in place through `mesh` (the handle's coded visible size's nx x ny); the handle's own setting plays no part */
 int mi355enc_warp_probe(mi355enc_t *h, const mi355enc_warp_t *s, const int32_t *mesh, uint8_t *y, uint8_t *uv);
+/* A 3D colour LUT: a camera-log-to-Rec.709 transform, a house grade or a film emulation, as shipped in a .cube file, applied to the
+ * picture part of the coded surfaces in place -- behind the noise filter (whose history stays in the camera's domain), in front of automatic levels (which
+ * measure the graded picture) and the picture controls; mix, layers and text are never touched.  Off by default, and off nothing is allocated, uploaded or
+ * launched.  All integers; >> is a floor.
+ *   table     N nodes per axis, 2 <= N <= 65; N^3 words R | G << 10 | B << 20, each field 0 .. 1023 (1023 is 1.0); node (r, g, b) is word r + N (g + N b)
+ *   per 2 x 2 luma quad and its chroma pair, with the output's matrix (1, 5, 6, 9; unspecified resolved by the picture's size) and range:
+ *   1  v = (Y - yoff, Cb - 128, Cr - 128) with the quad's own chroma pair for all four samples; c = clamp((Minv . v + 2^13) >> 14, 0, 4096), Q12,
+ *      Minv = floor(M^-1 4096 2^14 + 0.5), M^-1 the inverse from Kr / Kb and the range's scales (219 / 224 with yoff 16, 255 / 255 with yoff 0)
+ *   2  per channel p = c (N - 1), i = min(p >> 12, N - 2), f = p - (i << 12) in 0 .. 4096
+ *   3  tetrahedral: the fractions in descending order f0 >= f1 >= f2 (ties in the order R, G, B), nodes n0 .. n3 walking from node i one step at a time along
+ *      the axes in that order; per channel g = (n0 (4096 - f0) + n1 (f0 - f1) + n2 (f1 - f2) + n3 f2 + 2048) >> 12, ten bits
+ *   4  Mf = floor(M / 1023 2^20 + 0.5); Y' = clamp((Mf[0] . g + (yoff << 20) + 2^19) >> 20, 0, 255) per sample; Cb' = clamp((the sum of the four samples'
+ *      Mf[1] . g + (128 << 22) + 2^21) >> 22, 0, 255), Cr' likewise
+ *   5  out = in + (((graded - in) strength + 128) >> 8) per luma and per chroma sample, strength 0 .. 256 (0: the step is off for that picture)
+ * Host only, no device: */
+typedef struct {
+    int size;     /* N */
+    int strength; /* 0 .. 256 */
+} mi355enc_lut3d_t;
+/* the 18 coefficients and yoff, from exact rationals: Minv row-major (R', G', B' from v), then Mf row-major (Y, Cb, Cr from g), then yoff.  matrix 1, 5, 6, 9 */
+int mi355enc_lut3d_coefficients(int matrix, int full_range, int32_t out[19]);
+int mi355enc_lut3d_check(const uint32_t *nodes, int N);  /* MI355ENC_ERR_ARG: N outside 2 .. 65, or a node with one of its top two bits set */
+int mi355enc_lut3d_identity(int N, uint32_t *nodes);     /* field i of a node: round(i 1023 / (N - 1)) */
+/* A .cube text of `len` bytes -> N^3 nodes (cap: the room at nodes in words) and N.  Accepted: TITLE, # comments, blank lines, CR LF line ends, LUT_3D_SIZE,
+ * DOMAIN_MIN / DOMAIN_MAX (three numbers: the lo / hi per channel that the rows' values are normalised with; 0 / 1 without), LUT_3D_INPUT_RANGE lo hi.  The
+ * rule has no pre-scale of its input, so an input range other than 0 1 is refused rather than folded in.  Refused (MI355ENC_ERR_ARG): LUT_1D_SIZE and any
+ * other keyword, a keyword behind the first row, a size outside 2 .. 65 or beyond cap, too few or too many rows, a row that is not three numbers,
+ * |value| >= 10^6, hi <= lo.  Numbers are decimals with optional sign, fraction and exponent, read without the C library (no locale) into 64-bit integers in
+ * units of 10^-9, further digits truncated; a node's field is clamp(((v - lo) 2046 + (hi - lo)) / (2 (hi - lo)), 0, 1023), the division a floor of
+ * non-negative operands (a negative numerator gives 0) */
+int mi355enc_lut3d_parse_cube(const char *text, size_t len, uint32_t *nodes, size_t cap, int *N);
+/* the rule on host NV12 planes at `stride` (even) with `height` (even) rows of luma, inside rect {x0, x1, y0, y1} (even, inside the planes), in place */
+int mi355enc_lut3d_apply_host(const uint32_t *nodes, int N, int strength, int matrix, int full_range, uint8_t *y, uint8_t *uv, int stride, int height, const int rect[4]);
+/* which of the kernel's two forms serves N: 0 direct (the nodes gathered from global memory), 1 staged (the table copied into LDS once per workgroup by a grid
+ * of persistent workgroups); MI355ENC_ERR_ARG for N outside 2 .. 65.  Both forms give the same picture; decided by measurement (profiles/lut3d_price.md) */
+int mi355enc_lut3d_plan(int N);
+/* On a handle.  set: at any time and from any thread, no GPU call; the nodes (set->size^3 words, checked) are copied; latched once per input picture at its
+ * submit, so pictures in flight keep the table they were submitted with, and the size may change while the stream runs.  NULL: off.  Every successful set
+ * that turns it on counts one generation up.  With the step on mi355enc_submit_device never encodes in place: the caller's planes are only read */
+int mi355enc_set_lut3d(mi355enc_t *h, const mi355enc_lut3d_t *set, const uint32_t *nodes);
+int mi355enc_get_lut3d(const mi355enc_t *h, int *on, mi355enc_lut3d_t *set); /* what was set last (set is untouched when off; either pointer may be NULL) */
+/* of the last collected picture: its setting and the generation of its table (zeros for an ungraded one); MI355ENC_ERR_STATE before the first collect */
+int mi355enc_last_lut3d(mi355enc_t *h, mi355enc_lut3d_t *set, unsigned *generation);
+size_t mi355enc_debug_lut3d_bytes(const mi355enc_t *h); /* device bytes of the step: 0 until the first graded picture is submitted */
+/* measurements: the form of the handle's own launches -- -1 the plan's (the default), 0 direct, 1 staged, with which a picture whose table the staged form
+ * cannot hold fails its submit (the picture is the same in both forms) */
+int mi355enc_debug_lut3d_form(mi355enc_t *h, int form);
+/* the launch alone (tests, measurements), in the frame of the single-stage entry points: y / uv are host planes of the coded size (16 mbw x 16 mbh, chroma
+ * interleaved), graded in place inside the handle's picture rectangle with the handle's output matrix and range; form -1: the plan's, 0 / 1: that form
+ * (MI355ENC_ERR_ARG, and nothing launched, for the staged form with an N it cannot hold).  The handle's own setting plays no part */
+int mi355enc_lut3d_probe(mi355enc_t *h, const mi355enc_lut3d_t *set, const uint32_t *nodes, uint8_t *y, uint8_t *uv, int form);
 /* like mi355enc_submit, from host memory in `fmt`; planes[]/strides[]: as many entries as the format has planes */
 int mi355enc_submit_fmt(mi355enc_t *h, int fmt, const uint8_t *const planes[3], const int strides[3], int64_t pts, int force_idr);
 /* conversion stage alone (tests): writes the coded-size NV12 surfaces (16*mbw x 16*mbh luma, then interleaved chroma) */
@@ -928,6 +979,7 @@ int mi355enc_stage_deblock(mi355enc_t *h, uint8_t *rec_y, uint8_t *rec_uv, const
  * 32 / 33 / 34 the launches of automatic levels and white balance with the value set last (mi355enc_set_autolevel; MI355ENC_ERR_STATE when it is off) on slot
  * 0's source surfaces: 32 measure, 33 decide (on the slabs of a measure launch in front of the timed ones), 34 apply (with that decision's table and
  * offsets, so the surfaces change with every launch).  They leave the state unprimed: the next picture submitted primes.
+ * 35 the 3D LUT set last (mi355enc_set_lut3d; MI355ENC_ERR_STATE when it is off) on slot 0's source surfaces, in the form mi355enc_lut3d_plan names.
  * Uses whatever the handle's surfaces currently hold.  Returns average ms per launch. */
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms);
 
