@@ -346,6 +346,7 @@ void mi355enc_close(mi355enc_t *h) {
     hdr_free(h);
     adjust_free(h);
     autolevel_free(h);
+    dspatial_free(h);
     lut3d_close(h);
     denoise_free(h);
     stab_free(h);

@@ -4,7 +4,7 @@
 //   its own argument checks
 //   ingest_begin   the pipeline-full check (with frame-rate conversion: the rule's step, which says how many pictures the submit yields), the slot, the latches (text, image layers)
 //   fill           its own way of filling the input target: copy | convert | decode | scale, ending in input_finish (the orientation launch)
-//   ingest_end     warp -> colour step -> noise filter -> 3D LUT -> automatic levels -> picture controls -> [frame-rate conversion: mix / keep / repeat, per output picture] -> image layers -> text -> upload event -> enqueue_picture
+//   ingest_end     warp -> colour step -> spatial noise filter -> noise filter -> 3D LUT -> automatic levels -> picture controls -> [frame-rate conversion: mix / keep / repeat, per output picture] -> image layers -> text -> upload event -> enqueue_picture
 //                  (enc_schedule.cpp) on the slot's own surfaces
 // The one exception is the in-place exit of mi355enc_submit_device.  A new step on the way in goes into ingest_end (one that works on the coded surfaces) or
 // in front of input_finish (one that works on the pre-orientation picture), never into a submit.
@@ -39,6 +39,7 @@ static int ingest_latch(mi355enc_t *h, slot_t *s) {
         adjust_latch(h, t); // (what the tick's picture reports; the adjustment itself is applied to the input, once)
         autolevel_latch(h, t, false); // (likewise: the input is measured and corrected, once)
         (void)lut3d_latch(h, t, false); // (likewise: the input is graded, once)
+        dspatial_latch(h, t, false); // (likewise: the input is measured and filtered, once)
         denoise_latch(h, t, false); // (likewise; only the input's own slot launches and needs the tables)
         (void)stab_latch(h, t, false); // (likewise: the shake is measured on the input, once)
         (void)warp_latch(h, t, false); // (likewise: the input is warped, once)
@@ -49,6 +50,7 @@ static int ingest_latch(mi355enc_t *h, slot_t *s) {
     adjust_latch(h, s);
     autolevel_latch(h, s, true);
     { int r = lut3d_latch(h, s, true); if (r) return r; }
+    dspatial_latch(h, s, true);
     denoise_latch(h, s, true);
     { int r = stab_latch(h, s, true); if (r) return r; }
     { int r = warp_latch(h, s, true); if (r) return r; }
@@ -92,6 +94,7 @@ static int ingest_end_rate(mi355enc_t *h, slot_t *s, hipStream_t up, int force_i
 static int ingest_end(mi355enc_t *h, slot_t *s, hipStream_t up, int64_t pts, int force_idr) {
     int r = warp_draw(h, s, up); // geometry first: colours, filter, controls, mix, layers and text follow, so layers and text stay straight
     if (!r && s->yuv_step) r = yuv_draw(h, s, up); // the colour step: layers and text are drawn in the output's colours
+    if (!r) r = dspatial_draw(h, s, up); // the spatial noise filter and its estimate: measured on the camera's picture, filtered in front of the temporal filter, whose block measure then sees less noise
     if (!r) r = denoise_draw(h, s, up); // the temporal noise filter: in front of the picture controls, so that sharpening never amplifies noise
     if (!r) r = lut3d_draw(h, s, up); // the 3D LUT: behind the noise filter, whose history stays in the camera's domain; automatic levels measure the graded picture
     if (!r) r = autolevel_draw(h, s, up); // automatic levels and white balance: measured on the filtered picture, and the manual controls trim on top of it
@@ -358,7 +361,7 @@ int mi355enc_submit_device(mi355enc_t *h, const void *d_y, int y_stride, const v
     } else {
         const int w = h->cfg.width, ht = h->cfg.height;
         // in place -- unless the frame rate is converted (the picture may be kept, repeated or mixed), the samples are to be warped, converted, filtered, graded or adjusted, a text drawn or an image blended in: that goes into the encoder's own surfaces, never into the caller's planes
-        const bool direct = !h->rate.mode && !s->warp_on && !s->yuv_step && !s->dn.parts && !s->lut_on && !s->al_on && !s->adj.parts && !s->ov_len && !image_active(s) && w == h->W && y_stride == uv_stride && (y_stride & 15) == 0 && (((uintptr_t)d_y | (uintptr_t)d_uv) & 15) == 0;
+        const bool direct = !h->rate.mode && !s->warp_on && !s->yuv_step && !s->ds_on && !s->dn.parts && !s->lut_on && !s->al_on && !s->adj.parts && !s->ov_len && !image_active(s) && w == h->W && y_stride == uv_stride && (y_stride & 15) == 0 && (((uintptr_t)d_y | (uintptr_t)d_uv) & 15) == 0;
         if (direct) return enqueue_picture(h, s, (const uint8_t *)d_y, (const uint8_t *)d_uv, y_stride, pts, force_idr);
         HIPCHK(hipMemcpy2DAsync(s->d_src_y, h->W, d_y, y_stride, w, ht, hipMemcpyDeviceToDevice, up));
         HIPCHK(hipMemcpy2DAsync(s->d_src_uv, h->W, d_uv, uv_stride, w, ht / 2, hipMemcpyDeviceToDevice, up));

@@ -14,6 +14,7 @@
 //   enc_adjust.cpp    picture controls: setter, latch, the two launch forms and the scratch plane, its stage entry point
 //   enc_autolevel.cpp automatic levels and white balance: setter, latch, the three launches and the device block, the probes and the stage entry point
 //   enc_lut3d.cpp     3D colour LUT: setter, latch, the table's way to the device, the launch, its probe and timed stage
+//   enc_dspatial.cpp  spatial noise reduction: setter, latch, the estimate's two launches, the filter launches and their scratch planes, probes, stage entry point
 //   enc_denoise.cpp   temporal noise reduction: setter, latch, the launch and the handle's history, its stage entry point
 //   enc_stab.cpp      electronic image stabilisation: setter, latch, the estimate in front of every scale launch, its probes and timed stages
 //   enc_warp.cpp      lens, roll and keystone correction: setters, latch, the mesh's way to the device, the launch and the scratch pair, its stage entry point
@@ -47,6 +48,7 @@
 #include "denoise_host.h"
 #include "stab_host.h"
 #include "autolevel_host.h"
+#include "dspatial_host.h"
 #include "warp_host.h"
 #include "lut3d_host.h"
 #include "enc_plan.hpp"
@@ -148,6 +150,9 @@ struct slot_t {
     // for it (its record and table then lie in the handle's pinned block at the slot's index once the picture is collected); applied once, to the input's own
     // slot, in ingest_end
     mi355enc_autolevel_t al; bool al_on, al_done; int al_full;
+    // the spatial noise filter: what submit latched for this picture (ds_on false: nothing) with the output range it met, and whether the estimate ran for it
+    // (its record then lies in the handle's pinned block at the slot's index once the picture is collected); applied once, to the input's own slot, in ingest_end
+    mi355enc_denoise_spatial_t ds; bool ds_on, ds_done; int ds_full;
     // the warp: what submit latched for this picture (warp_on false: nothing; warp_gen: the count of sets its mesh belongs to); warp_send: the slot's pinned copy
     // holds that mesh and it travels in front of the launch; applied once, to the input's own slot, first in ingest_end
     bool warp_on, warp_send; mi355enc_warp_t warp; unsigned warp_gen;
@@ -301,6 +306,18 @@ struct mi355enc {
     int *d_al = nullptr, *h_al = nullptr;
     size_t al_bytes = 0;
     int al_time_n = 0; // (mi355enc_time_stage 32 .. 34: the slabs its prepare left)
+    // the spatial noise filter (mi355enc_set_denoise_spatial): what the control thread set last (under ds_mu; submit latches it per input
+    // picture) and what the last collected picture carried.  d_ds (one block, allocated by the first picture that is measured): the state X (and seven words of
+    // room), DS_REC_WORDS words per slot and for the stage calls, DS_SLABS_MAX slabs, then the 33 tables R_s; h_ds: the slots' pinned records.  d_ds_y / d_ds_uv:
+    // the scratch planes the filter launches write (allocated by the first picture whose plane is filtered), which then change places with the slot's.  ds_bytes:
+    // all of it.  ds_primed false: the next measured picture primes.  Written only by launches that follow one another on one stream.
+    std::mutex ds_mu;
+    mi355enc_denoise_spatial_t ds_cur = {0, 0, 0, 25, 32}, ds_last = {0, 0, 0, 25, 32};
+    mi355enc_denoise_spatial_info_t ds_last_info = {};
+    bool ds_last_have = false, ds_primed = false;
+    int *d_ds = nullptr, *h_ds = nullptr;
+    uint8_t *d_ds_y = nullptr, *d_ds_uv = nullptr;
+    size_t ds_bytes = 0;
     // lens, roll and keystone correction (mi355enc_set_warp / mi355enc_set_warp_mesh): what the control thread set last (under warp_mu: the
     // setting, its mesh of the coded visible size on the heap, the count of sets that turned it on; submit latches it per input picture) and what the last
     // collected picture carried.  Allocated by the first warped picture: the scratch pair d_warp_y / d_warp_uv (the launch writes it, then the slot and the handle
@@ -532,6 +549,14 @@ bool autolevel_time_ready(mi355enc_t *h, int stage);         // mi355enc_time_st
 int autolevel_time_prepare(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // the block, and a measure and a (priming) decide launch on slot 0's surfaces
 int autolevel_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // 32 measure, 33 decide, 34 apply
 void autolevel_time_done(mi355enc_t *h);                     // ... behind the timed launches: the next picture primes
+// enc_dspatial.cpp (the spatial noise filter and its noise estimate)
+void dspatial_latch(mi355enc_t *h, slot_t *s, bool own);     // the value set last becomes the slot's (beside denoise_latch); own: the slot the input goes into (not automatic there: the next measured picture primes)
+int dspatial_draw(mi355enc_t *h, slot_t *s, hipStream_t st); // measure, decide, the filter launches on the slot's coded surfaces and the record's copy to pinned memory, behind everything enqueued on st so far; nothing with none
+void dspatial_collected(mi355enc_t *h, slot_t *s);           // collect(): books what the picture carried as the last picture's
+void dspatial_free(mi355enc_t *h);
+bool dspatial_time_ready(mi355enc_t *h, int stage);          // mi355enc_time_stage 36 / 37: the value set last is on and manual / automatic
+int dspatial_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // 36 the filter launches, 37 measure, decide and the filter launches
+void dspatial_time_done(mi355enc_t *h);                      // ... behind the timed launches: the next picture primes
 // enc_lut3d.cpp (3D colour LUT)
 int lut3d_latch(mi355enc_t *h, slot_t *s, bool own);         // the value set last becomes the slot's (beside autolevel_latch); own: the slot the input goes into, which also takes the table where it is a new one
 int lut3d_draw(mi355enc_t *h, slot_t *s, hipStream_t st);    // the slot's LUT on its coded surfaces, behind everything enqueued on st so far (a new table travels in front of it); nothing with none

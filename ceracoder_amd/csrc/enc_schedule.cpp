@@ -540,6 +540,7 @@ int mi355enc_collect(mi355enc_t *h, uint8_t *out, size_t out_cap, size_t *out_le
     image_collected(h, s);
     adjust_collected(h, s);
     autolevel_collected(h, s);
+    dspatial_collected(h, s);
     lut3d_collected(h, s);
     denoise_collected(h, s);
     stab_collected(h, s);

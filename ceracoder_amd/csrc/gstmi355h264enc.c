@@ -112,6 +112,9 @@ typedef struct {
     mi355enc_adjust_t adj;
     /* temporal noise reduction on the device (mi355enc_set_denoise): denoise-luma, denoise-chroma; stored and forwarded like the picture controls */
     mi355enc_denoise_t dn;
+    /* spatial noise reduction on the device (mi355enc_set_denoise_spatial): denoise-spatial-luma, denoise-spatial-chroma, denoise-auto (a
+     * double 0 .. 8, stored as thousandths, lround; 0: manual), denoise-auto-percentile, denoise-auto-speed; stored and forwarded like the picture controls */
+    mi355enc_denoise_spatial_t ds;
     /* automatic levels and white balance on the device (mi355enc_set_autolevel): auto-levels, auto-balance (doubles 0 .. 1, stored as
      * thousandths, lround), auto-speed, auto-clip (percent, both clips), auto-max-gain; stored under the object lock and forwarded like the picture controls */
     mi355enc_autolevel_t al;
@@ -157,7 +160,7 @@ enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME
        PROP_SNAP_LOCATION, PROP_SNAP_INTERVAL, PROP_SNAP_QUALITY, PROP_SNAP_REDUCE, PROP_SNAP_SOURCE,
        PROP_OUTPUT_COLORIMETRY, PROP_RATE_CONVERSION, PROP_OUTPUT_FRAMERATE, PROP_MAX_FILL, PROP_HDR_INPUT, PROP_HDR_PEAK_NITS, PROP_HDR_TARGET_NITS,
        PROP_ADJ_BRIGHTNESS, PROP_ADJ_CONTRAST, PROP_ADJ_HUE, PROP_ADJ_SATURATION, PROP_ADJ_GAMMA, PROP_ADJ_SHARPEN, PROP_ADJ_SHARPEN_THRESHOLD,
-       PROP_DENOISE_LUMA, PROP_DENOISE_CHROMA, PROP_DENOISE_MOTION, PROP_STABILIZE, PROP_STABILIZE_RANGE, PROP_STABILIZE_LEAK, PROP_AUTO_LEVELS, PROP_AUTO_BALANCE, PROP_AUTO_SPEED, PROP_AUTO_CLIP, PROP_AUTO_MAX_GAIN, PROP_LUT3D_LOCATION, PROP_LUT3D_STRENGTH,
+       PROP_DENOISE_LUMA, PROP_DENOISE_CHROMA, PROP_DENOISE_MOTION, PROP_DS_LUMA, PROP_DS_CHROMA, PROP_DS_AUTO, PROP_DS_PERCENTILE, PROP_DS_SPEED, PROP_STABILIZE, PROP_STABILIZE_RANGE, PROP_STABILIZE_LEAK, PROP_AUTO_LEVELS, PROP_AUTO_BALANCE, PROP_AUTO_SPEED, PROP_AUTO_CLIP, PROP_AUTO_MAX_GAIN, PROP_LUT3D_LOCATION, PROP_LUT3D_STRENGTH,
        PROP_LENS_K1, PROP_LENS_K2, PROP_LENS_ZOOM, PROP_ROLL, PROP_KEYSTONE_H, PROP_KEYSTONE_V, PROP_WARP_FILTER };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
@@ -292,6 +295,10 @@ static void warp_forward(GstMi355H264Enc *s) {
     if (mi355enc_set_warp(s->enc, neutral ? NULL : &w, neutral ? NULL : &p) != MI355ENC_OK)
         GST_WARNING_OBJECT(s, "the encoder refused the lens / roll / keystone values (the picture would leave the mesh's range): it keeps its previous ones");
 }
+/* stored spatial noise filter -> the encoder, if one is open (object lock held; the library only stores: no GPU call, any thread) */
+static void dspatial_forward(GstMi355H264Enc *s) {
+    if (s->enc && mi355enc_set_denoise_spatial(s->enc, &s->ds) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the spatial noise filter: it keeps its previous setting");
+}
 static void denoise_forward(GstMi355H264Enc *s) {
     if (s->enc && mi355enc_set_denoise(s->enc, &s->dn) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the noise filter's strengths: it keeps its previous ones");
     if (s->enc && mi355enc_set_denoise_motion(s->enc, s->dn_motion) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the noise filter's search range: it keeps its previous one");
@@ -414,6 +421,11 @@ static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *
     case PROP_DENOISE_LUMA: s->dn.luma = g_value_get_int(val); denoise_forward(s); break;
     case PROP_DENOISE_CHROMA: s->dn.chroma = g_value_get_int(val); denoise_forward(s); break;
     case PROP_DENOISE_MOTION: s->dn_motion = g_value_get_int(val); denoise_forward(s); break;
+    case PROP_DS_LUMA: s->ds.luma = g_value_get_int(val); dspatial_forward(s); break;
+    case PROP_DS_CHROMA: s->ds.chroma = g_value_get_int(val); dspatial_forward(s); break;
+    case PROP_DS_AUTO: s->ds.auto_gain = (int)lround(1000.0 * g_value_get_double(val)); dspatial_forward(s); break;
+    case PROP_DS_PERCENTILE: s->ds.percentile = g_value_get_int(val); dspatial_forward(s); break;
+    case PROP_DS_SPEED: s->ds.speed = g_value_get_int(val); dspatial_forward(s); break;
     case PROP_STABILIZE: s->stab = g_value_get_int(val); break; /* (a crop change: latched in front of the next picture, the setting with it) */
     case PROP_STABILIZE_RANGE: s->stab_range = g_value_get_int(val); stabilize_forward(s); break;
     case PROP_STABILIZE_LEAK: s->stab_leak = g_value_get_int(val); stabilize_forward(s); break;
@@ -506,6 +518,11 @@ static void get_property(GObject *obj, guint id, GValue *val, GParamSpec *ps) {
     case PROP_DENOISE_LUMA: g_value_set_int(val, s->dn.luma); break;
     case PROP_DENOISE_CHROMA: g_value_set_int(val, s->dn.chroma); break;
     case PROP_DENOISE_MOTION: g_value_set_int(val, s->dn_motion); break;
+    case PROP_DS_LUMA: g_value_set_int(val, s->ds.luma); break;
+    case PROP_DS_CHROMA: g_value_set_int(val, s->ds.chroma); break;
+    case PROP_DS_AUTO: g_value_set_double(val, s->ds.auto_gain / 1000.0); break;
+    case PROP_DS_PERCENTILE: g_value_set_int(val, s->ds.percentile); break;
+    case PROP_DS_SPEED: g_value_set_int(val, s->ds.speed); break;
     case PROP_STABILIZE: g_value_set_int(val, s->stab); break;
     case PROP_STABILIZE_RANGE: g_value_set_int(val, s->stab_range); break;
     case PROP_STABILIZE_LEAK: g_value_set_int(val, s->stab_leak); break;
@@ -922,6 +939,7 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     autolevel_forward(s);                   /* ... nor the automatic levels and white balance */
     lut3d_forward(s);                       /* ... nor the 3D LUT */
     denoise_forward(s);                     /* ... nor the noise filter */
+    dspatial_forward(s);                    /* ... nor the spatial noise filter */
     stabilize_forward(s);                   /* ... nor the stabiliser */
     warp_forward(s);                        /* ... nor the warp */
     GST_OBJECT_UNLOCK(s);
@@ -1388,6 +1406,11 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
     g_object_class_install_property(g, PROP_LUT3D_LOCATION, g_param_spec_string("lut3d-location", "3D LUT location",
         "a 3D colour LUT on the GPU, behind the noise filter and in front of automatic levels and the picture controls: the path of a .cube file (LUT_3D_SIZE 2 .. 65, tetrahedral interpolation), read when the property is set, at any time; empty: off.  A file that cannot be read or parsed posts a warning and leaves the step as it was", "", F));
     g_object_class_install_property(g, PROP_LUT3D_STRENGTH, g_param_spec_double("lut3d-strength", "3D LUT strength", "how much of the 3D LUT's grade is applied, per sample between the input and the graded value; 0: off", 0.0, 1.0, 1.0, F));
+    g_object_class_install_property(g, PROP_DS_LUMA, g_param_spec_int("denoise-spatial-luma", "Spatial denoise luma", "spatial noise reduction on the GPU, edge-preserving, in front of the temporal filter: the luma noise amplitude in codes that is filtered fully -- with denoise-auto above 0 the upper bound of the measured strength; 0: off", 0, MI355ENC_DENOISE_SPATIAL_MAX, 0, F));
+    g_object_class_install_property(g, PROP_DS_CHROMA, g_param_spec_int("denoise-spatial-chroma", "Spatial denoise chroma", "spatial noise reduction on the GPU: the chroma noise amplitude in codes that is filtered fully -- with denoise-auto above 0 the upper bound of the measured strength; 0: off", 0, MI355ENC_DENOISE_SPATIAL_MAX, 0, F));
+    g_object_class_install_property(g, PROP_DS_AUTO, g_param_spec_double("denoise-auto", "Automatic denoise strength", "the spatial filter's strength as this multiple of the noise sigma measured per picture on the GPU (0.25 .. 8; a knob, not a tuned value); with both bounds 0 the noise is measured and reported and nothing is filtered; 0: manual", 0.0, 8.0, 0.0, F));
+    g_object_class_install_property(g, PROP_DS_PERCENTILE, g_param_spec_int("denoise-auto-percentile", "Automatic denoise percentile", "the percentile of the 8 x 8 blocks' noise estimates that is taken as the picture's noise level", 1, 50, 25, F));
+    g_object_class_install_property(g, PROP_DS_SPEED, g_param_spec_int("denoise-auto-speed", "Automatic denoise speed", "how fast the measured noise level follows the pictures, in 1/256 per picture; 256: at once", 1, 256, 32, F));
     g_object_class_install_property(g, PROP_DENOISE_LUMA, g_param_spec_int("denoise-luma", "Denoise luma", "temporal noise reduction on the GPU, motion-adaptive, in front of the picture controls: the luma noise amplitude in codes that is filtered fully; 0: off", 0, MI355ENC_DENOISE_MAX, 0, F));
     g_object_class_install_property(g, PROP_DENOISE_CHROMA, g_param_spec_int("denoise-chroma", "Denoise chroma", "temporal noise reduction on the GPU: the chroma noise amplitude in codes that is filtered fully; 0: off", 0, MI355ENC_DENOISE_MAX, 0, F));
     g_object_class_install_property(g, PROP_STABILIZE, g_param_spec_int("stabilize", "Stabilize", "electronic image stabilisation on the GPU: the margin in input samples per side that the crop may move by to follow the camera's shake (added to each of crop-*; odd values count as the even value below); 0: off", 0, MI355ENC_STABILIZE_MARGIN_MAX, 0, F));
@@ -1422,6 +1445,7 @@ static void gst_mi355h264enc_init(GstMi355H264Enc *s) {
     s->hdr_input = 0; s->hdr_peak = 0; s->hdr_target = 0;
     mi355enc_adjust_default(&s->adj);
     mi355enc_denoise_default(&s->dn);
+    mi355enc_denoise_spatial_default(&s->ds);
     mi355enc_autolevel_default(&s->al);
     s->lut_location = NULL; s->lut_nodes = NULL; s->lut_size = 0; s->lut_strength = 256;
     s->dn_motion = 0;

@@ -266,6 +266,14 @@ int k_launch_stab_match(const unsigned *prev, const unsigned *cur, int w, int h,
 int k_launch_autolevel_measure(const uint8_t *y, const uint8_t *uv, int W, int H, const int rect[4], int vw, int vh, int full_range, int reach, unsigned *slabs, hipStream_t s);
 int k_launch_autolevel_decide(const unsigned *slabs, int nslabs, unsigned NC, const int set[7], int full_range, int prime, int *state, int *rec, hipStream_t s);
 int k_launch_autolevel_apply(uint8_t *y, uint8_t *uv, int W, int H, const int rect[4], int luma, int chroma, const int *rec, hipStream_t s);
+/* The spatial noise filter and its noise estimate (k_dspatial.hip; the rule: DESIGN.md section 30, dspatial_host.h).  filter: one plane (chroma 0: luma, 1: the
+ * interleaved chroma plane) of NV12 surfaces of W x H (visible vw x vh) into another plane, inside rect; its weights R_s by value (weight, 256 bytes) or, with
+ * weight null, the strength from the device word rec and R_s from the device's 33 tables.  measure: the candidate blocks of the luma plane -> one slab of
+ * DS_SLAB_WORDS words per workgroup (plain stores: nothing to clear); returns their number (1 .. DS_SLABS_MAX).  decide: the slabs, NC candidates and the
+ * automatic setting's five fields -> the state (one word, read and written; prime: only written) and the record (DS_REC_WORDS words).  -1: arguments outside that */
+int k_launch_dspatial_filter(const uint8_t *src, uint8_t *out, int W, int H, int vw, int vh, const int rect[4], int chroma, const uint8_t *weight, const int *rec, const uint8_t *tabs, hipStream_t s);
+int k_launch_dspatial_measure(const uint8_t *y, int W, int H, const int rect[4], int vw, int vh, int full_range, unsigned *slabs, hipStream_t s);
+int k_launch_dspatial_decide(const unsigned *slabs, int nslabs, unsigned NC, const int set[5], int prime, int *state, int *rec, hipStream_t s);
 /* A 3D colour LUT (k_lut3d.hip; the rule: DESIGN.md section 29, lut3d_host.h) on NV12 surfaces of W x H at stride W inside rect, in place: nodes N^3 checked
  * words on the device, strength 1 .. 256, coef mi355enc_lut3d_coefficients', form 0 direct (nodes from global memory) or 1 staged (the table in LDS: N up to
  * LUT3D_STAGED_FIT, nodes 16-byte aligned).  -1: arguments outside that, and nothing is launched */

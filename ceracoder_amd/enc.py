@@ -41,6 +41,8 @@ STABILIZE_RANGE_MAX, STABILIZE_MARGIN_MAX = 32, 1024
 STAGE_WARP = 31  # the warp set last on slot 0's surfaces
 STAGE_AUTOLEVEL_MEASURE, STAGE_AUTOLEVEL_DECIDE, STAGE_AUTOLEVEL_APPLY = 32, 33, 34  # the launches of automatic levels and white balance
 WARP_BILINEAR, WARP_BICUBIC = 0, 1
+STAGE_DENOISE_SPATIAL, STAGE_DENOISE_SPATIAL_AUTO = 36, 37  # the spatial noise filter set last on slot 0's surfaces: manual / automatic, both planes
+DENOISE_SPATIAL_MAX = 32
 STAGE_LUT3D = 35  # the 3D colour LUT set last on slot 0's surfaces
 LUT3D_N_MIN, LUT3D_N_MAX = 2, 65
 LUT3D_DIRECT, LUT3D_STAGED = 0, 1  # the launch forms (lut3d_plan, lut3d_probe)
@@ -87,6 +89,10 @@ EXPORTS = [
     "mi355enc_debug_autolevel_bytes", "mi355enc_autolevel_probe_stage", "mi355enc_autolevel_probe_measure", "mi355enc_autolevel_probe_decide",
     "mi355enc_warp_params_default", "mi355enc_warp_coeff", "mi355enc_warp_mesh_size", "mi355enc_warp_mesh_check", "mi355enc_warp_build", "mi355enc_warp_apply_host",
     "mi355enc_set_warp", "mi355enc_set_warp_mesh", "mi355enc_get_warp", "mi355enc_last_warp", "mi355enc_debug_warp_bytes", "mi355enc_warp_probe", "mi355enc_warp_plan", "mi355enc_debug_warp_staging",
+    "mi355enc_denoise_spatial_default", "mi355enc_denoise_spatial_check", "mi355enc_denoise_spatial_tables", "mi355enc_denoise_spatial_apply_host",
+    "mi355enc_denoise_spatial_measure_host", "mi355enc_denoise_spatial_decide", "mi355enc_set_denoise_spatial", "mi355enc_get_denoise_spatial",
+    "mi355enc_last_denoise_spatial", "mi355enc_debug_denoise_spatial_bytes", "mi355enc_denoise_spatial_probe_stage", "mi355enc_denoise_spatial_probe_measure",
+    "mi355enc_denoise_spatial_probe_decide",
     "mi355enc_lut3d_coefficients", "mi355enc_lut3d_check", "mi355enc_lut3d_identity", "mi355enc_lut3d_parse_cube", "mi355enc_lut3d_apply_host", "mi355enc_lut3d_plan",
     "mi355enc_set_lut3d", "mi355enc_get_lut3d", "mi355enc_last_lut3d", "mi355enc_debug_lut3d_bytes", "mi355enc_lut3d_probe", "mi355enc_debug_lut3d_form",
 ]
@@ -192,6 +198,33 @@ class AutolevelInfo(C.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class DenoiseSpatial(C.Structure):
+    """mi355enc_denoise_spatial_t: luma / chroma 0 .. 32 (strengths, or with auto_gain their upper bounds), auto_gain 0 (manual) or 250 .. 8000 (thousandths of
+    the measured sigma), percentile 1 .. 50, speed 1 .. 256"""
+    NAMES = ("luma", "chroma", "auto_gain", "percentile", "speed")
+    _fields_ = [(n, C.c_int) for n in NAMES]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n in self.NAMES}
+
+
+class DenoiseSpatialMeas(C.Structure):
+    """mi355enc_denoise_spatial_meas_t: the voting blocks' histogram over the noise bins, the candidate blocks, the voters"""
+    _fields_ = [("hist", C.c_uint32 * 256), ("candidates", C.c_uint32), ("voters", C.c_uint32)]
+
+    def as_dict(self):
+        return dict(hist=np.array(self.hist, np.int64), candidates=int(self.candidates), voters=int(self.voters))
+
+
+class DenoiseSpatialInfo(C.Structure):
+    """mi355enc_denoise_spatial_info_t: a picture's record -- its measurement, the state behind it (1/256 bin), the strengths it was filtered with"""
+    NAMES = ("candidates", "voters", "v", "valid", "x", "s_luma", "s_chroma")
+    _fields_ = [(n, C.c_int) for n in NAMES + ("reserved",)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n in self.NAMES}
 
 
 class Lut3d(C.Structure):
@@ -409,6 +442,21 @@ def load():
         L.mi355enc_warp_probe.argtypes = [vp, C.POINTER(Warp), vp, vp, vp]
         L.mi355enc_warp_plan.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.mi355enc_debug_warp_staging.argtypes = [vp, C.c_int]
+        L.mi355enc_denoise_spatial_default.restype = None
+        L.mi355enc_denoise_spatial_default.argtypes = [C.POINTER(DenoiseSpatial)]
+        L.mi355enc_denoise_spatial_check.argtypes = [C.POINTER(DenoiseSpatial)]
+        L.mi355enc_denoise_spatial_tables.argtypes = [C.c_int, vp, vp]
+        L.mi355enc_denoise_spatial_apply_host.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(C.c_int * 4), C.c_int, C.c_int, C.c_int, C.c_int]
+        L.mi355enc_denoise_spatial_measure_host.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int * 4), C.c_int, C.c_int, C.c_int, C.POINTER(DenoiseSpatialMeas)]
+        L.mi355enc_denoise_spatial_decide.argtypes = [C.POINTER(DenoiseSpatialMeas), C.POINTER(DenoiseSpatial), C.c_int, C.POINTER(C.c_int32), C.POINTER(DenoiseSpatialInfo)]
+        L.mi355enc_set_denoise_spatial.argtypes = [vp, C.POINTER(DenoiseSpatial)]
+        L.mi355enc_get_denoise_spatial.argtypes = [vp, C.POINTER(DenoiseSpatial)]
+        L.mi355enc_last_denoise_spatial.argtypes = [vp, C.POINTER(DenoiseSpatial), C.POINTER(DenoiseSpatialInfo)]
+        L.mi355enc_debug_denoise_spatial_bytes.restype = C.c_size_t
+        L.mi355enc_debug_denoise_spatial_bytes.argtypes = [vp]
+        L.mi355enc_denoise_spatial_probe_stage.argtypes = [vp, C.POINTER(DenoiseSpatial), vp, vp, C.POINTER(DenoiseSpatialInfo)]
+        L.mi355enc_denoise_spatial_probe_measure.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(C.c_int * 4), C.c_int, C.c_int, C.c_int, C.POINTER(DenoiseSpatialMeas)]
+        L.mi355enc_denoise_spatial_probe_decide.argtypes = [vp, C.POINTER(DenoiseSpatialMeas), C.POINTER(DenoiseSpatial), C.c_int, C.POINTER(C.c_int32), C.POINTER(DenoiseSpatialInfo)]
         L.mi355enc_lut3d_coefficients.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int32 * 19)]
         L.mi355enc_lut3d_check.argtypes = [vp, C.c_int]
         L.mi355enc_lut3d_identity.argtypes = [C.c_int, vp]
@@ -698,6 +746,81 @@ def autolevel_decide(m, a, full_range=0, state=None, prime=False):
     """mi355enc_autolevel_decide (host only): a picture's decision from its measurement (an AutolevelMeas or dict(hist=, voters=, su=, sv=, chroma=)), a
     setting, the output range and the state {Lo, Hi, Du, Dv} going in -> (record, table, state coming out)"""
     return _autolevel_decide(load().mi355enc_autolevel_decide, "autolevel_decide", m, a, full_range, state, prime)
+
+
+def denoise_spatial(a=None, **kw):
+    """A DenoiseSpatial: the defaults (off: mi355enc_denoise_spatial_default), then a's (a DenoiseSpatial or a dict) and the keywords' on top.  Not checked here."""
+    st = DenoiseSpatial()
+    load().mi355enc_denoise_spatial_default(C.byref(st))
+    src = a.as_dict() if isinstance(a, DenoiseSpatial) else dict(a or {})
+    src.update(kw)
+    for k, v in src.items():
+        if k not in DenoiseSpatial.NAMES:
+            raise TypeError("denoise_spatial: no parameter %r" % (k,))
+        setattr(st, k, int(v))
+    return st
+
+
+def denoise_spatial_check(a=None, **kw):
+    """mi355enc_denoise_spatial_check (host only): 0, or the error code for a value outside its range"""
+    return load().mi355enc_denoise_spatial_check(C.byref(denoise_spatial(a, **kw)))
+
+
+def denoise_spatial_tables(s):
+    """mi355enc_denoise_spatial_tables (host only): (R_s, F_s) of a strength 0 .. 32"""
+    weight, filt = np.zeros(256, np.uint8), np.zeros(256, np.uint16)
+    r = load().mi355enc_denoise_spatial_tables(int(s), _p(weight), _p(filt))
+    if r:
+        raise EncoderError("denoise_spatial_tables: failed (%d)" % r)
+    return weight, filt
+
+
+def _surface_args(y, rect, visible):
+    H, W = y.shape
+    rect = rect if rect is not None else (0, W, 0, H)
+    vw, vh = visible if visible is not None else (W, H)
+    return W, H, C.byref((C.c_int * 4)(*[int(v) for v in rect])), int(vw), int(vh)
+
+
+def denoise_spatial_apply_host(y, uv, s_luma, s_chroma, rect=None, visible=None):
+    """mi355enc_denoise_spatial_apply_host (host only): the filter on NV12 surfaces y (H x W) / uv (H / 2 x W) inside rect (x0, x1, y0, y1; all of it without)
+    with the visible size (vw, vh); a strength of -1 leaves its plane alone -> new (y, uv)"""
+    y, uv = np.ascontiguousarray(y, np.uint8).copy(), np.ascontiguousarray(uv, np.uint8).copy()
+    r = load().mi355enc_denoise_spatial_apply_host(_p(y), _p(uv), *_surface_args(y, rect, visible), int(s_luma), int(s_chroma))
+    if r:
+        raise EncoderError("denoise_spatial_apply_host: failed (%d)" % r)
+    return y, uv
+
+
+def denoise_spatial_measure_host(y, rect=None, visible=None, full_range=0):
+    """mi355enc_denoise_spatial_measure_host (host only): dict(hist=, candidates=, voters=) of a luma surface"""
+    y, m = np.ascontiguousarray(y, np.uint8), DenoiseSpatialMeas()
+    r = load().mi355enc_denoise_spatial_measure_host(_p(y), *_surface_args(y, rect, visible), int(full_range), C.byref(m))
+    if r:
+        raise EncoderError("denoise_spatial_measure_host: failed (%d)" % r)
+    return m.as_dict()
+
+
+def denoise_spatial_meas(hist, candidates, voters):
+    m = DenoiseSpatialMeas()
+    m.hist[:] = [int(v) for v in hist]
+    m.candidates, m.voters = int(candidates), int(voters)
+    return m
+
+
+def _denoise_spatial_decide(fn, what, m, a, x, prime):
+    st, info = C.c_int32(int(x) if x is not None else 0), DenoiseSpatialInfo()
+    m = m if isinstance(m, DenoiseSpatialMeas) else denoise_spatial_meas(**m)
+    r = fn(C.byref(m), C.byref(denoise_spatial(a)), int(bool(prime)), C.byref(st), C.byref(info))
+    if r:
+        raise EncoderError("%s: failed (%d)" % (what, r))
+    return info.as_dict(), int(st.value)
+
+
+def denoise_spatial_decide(m, a, x=None, prime=False):
+    """mi355enc_denoise_spatial_decide (host only): a picture's decision from its measurement (a DenoiseSpatialMeas or dict(hist=, candidates=, voters=)), an
+    automatic setting and the state X going in -> (record, X coming out)"""
+    return _denoise_spatial_decide(load().mi355enc_denoise_spatial_decide, "denoise_spatial_decide", m, a, x, prime)
 
 
 def _lut3d_nodes(nodes):
@@ -1253,7 +1376,7 @@ class Encoder:
     (bitrate in bits/s as written through `bps`, key-int-max -> gop)."""
 
     def __init__(self, width, height, fps=60, gop=60, bitrate_bps=6_000_000, device_id=0, fixed_qp=-1, me_range=16,
-                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False, input_size=None, colorimetry=None, orientation=None, geometry=None, input_colorimetry=None, rate=None, hdr_input=None, adjust=None, denoise=None, stabilize=None, autolevel=None):
+                 pipeline_depth=0, profile_events=False, use_graphs=True, keep_prefilter=False, fps_den=1, deblock_mode=0, subpel=True, i4x4=True, transform8x8=False, intra_in_p=True, cavlc_threads=0, intra_mode=0, scenecut=True, exclusive=False, aq=False, single_stream=False, intra_slices=0, profile_overlap=False, partitions=False, i8x8=False, slices="mirror", slice_deblock="mirror", intra_refresh=False, input_size=None, colorimetry=None, orientation=None, geometry=None, input_colorimetry=None, rate=None, hdr_input=None, adjust=None, denoise=None, stabilize=None, autolevel=None, denoise_spatial=None):
         self.L = load()
         cfg = Cfg()
         self.L.mi355enc_default_cfg(C.byref(cfg), width, height, fps, fps_den)
@@ -1323,6 +1446,12 @@ class Encoder:
         if autolevel is not None:  # dict(levels=, balance=, ...) or an Autolevel: automatic levels and white balance from the first picture on
             try:
                 self.set_autolevel(autolevel)
+            except EncoderError:
+                self.close()
+                raise
+        if denoise_spatial is not None:  # dict(luma=, chroma=, auto_gain=, ...) or a DenoiseSpatial: the spatial noise filter from the first picture on
+            try:
+                self.set_denoise_spatial(denoise_spatial)
             except EncoderError:
                 self.close()
                 raise
@@ -1530,6 +1659,43 @@ class Encoder:
             self._chk(self.L.mi355enc_set_warp(self.h, None, None), "set_warp")
         else:
             self._chk(self.L.mi355enc_set_warp(self.h, C.byref(warp(s)), C.byref(warp_params(p, **kw))), "set_warp")
+
+    def set_denoise_spatial(self, a=None, **kw):
+        """mi355enc_set_denoise_spatial: from the next picture submitted on; nothing that filters or measures (or no argument): off"""
+        self._chk(self.L.mi355enc_set_denoise_spatial(self.h, C.byref(denoise_spatial(a, **kw))), "set_denoise_spatial")
+
+    def get_denoise_spatial(self):
+        st = DenoiseSpatial()
+        self._chk(self.L.mi355enc_get_denoise_spatial(self.h, C.byref(st)), "get_denoise_spatial")
+        return st.as_dict()
+
+    def last_denoise_spatial(self):
+        """-> (setting, record) of the last collected picture"""
+        st, info = DenoiseSpatial(), DenoiseSpatialInfo()
+        self._chk(self.L.mi355enc_last_denoise_spatial(self.h, C.byref(st), C.byref(info)), "last_denoise_spatial")
+        return st.as_dict(), info.as_dict()
+
+    def debug_denoise_spatial_bytes(self):
+        return int(self.L.mi355enc_debug_denoise_spatial_bytes(self.h))
+
+    def stage_denoise_spatial(self, a, y, uv):
+        """The step alone on host planes of the coded size (an automatic setting is primed by the picture) -> (y', uv', record)"""
+        y, uv = np.ascontiguousarray(y, np.uint8).copy(), np.ascontiguousarray(uv, np.uint8).copy()
+        info = DenoiseSpatialInfo()
+        self._chk(self.L.mi355enc_denoise_spatial_probe_stage(self.h, C.byref(denoise_spatial(a)), _p(y), _p(uv), C.byref(info)), "stage_denoise_spatial")
+        return y, uv, info.as_dict()
+
+    def denoise_spatial_probe_measure(self, y, rect=None, visible=None, full_range=0):
+        """The measure launch alone on a host luma surface -> dict(hist=, candidates=, voters=)"""
+        y, m = np.ascontiguousarray(y, np.uint8), DenoiseSpatialMeas()
+        self._chk(self.L.mi355enc_denoise_spatial_probe_measure(self.h, _p(y), *_surface_args(y, rect, visible), int(full_range), C.byref(m)), "denoise_spatial_probe_measure")
+        return m.as_dict()
+
+    def denoise_spatial_probe_decide(self, m, a, x=None, prime=False):
+        """The decide launch alone: denoise_spatial_decide's arguments and answer"""
+        def fn(*args):
+            return self.L.mi355enc_denoise_spatial_probe_decide(self.h, *args)
+        return _denoise_spatial_decide(fn, "denoise_spatial_probe_decide", m, a, x, prime)
 
     def set_lut3d(self, nodes_or_cube_text=None, strength=256):
         """A 3D colour LUT from the next picture submitted on (any time, any thread, no GPU call): N^3 packed nodes, or the text of a .cube file (str or

@@ -483,6 +483,67 @@ int mi355enc_autolevel_probe_measure(mi355enc_t *h, const uint8_t *y, const uint
                                      mi355enc_autolevel_meas_t *m);
 int mi355enc_autolevel_probe_decide(mi355enc_t *h, const mi355enc_autolevel_meas_t *m, const mi355enc_autolevel_t *a, int full_range, int prime, int32_t state[4],
                                     mi355enc_autolevel_info_t *info, uint8_t table[256]);
+/* Spatial noise reduction with a measured strength: an edge-preserving stencil on the picture's coded surfaces, directly in front of the
+ * temporal noise filter, and a per-picture noise estimate that can set its strength, all on the device.  Off by default, and off nothing is allocated or
+ * launched.  All integers; >> and floor() are floors; B and S are the output range's black level and scale (16 / 219 or 0 / 255).
+ *   setting      luma, chroma 0 .. 32 (the noise amplitude in codes that is filtered fully), auto_gain 0 (manual) or 250 .. 8000 (thousandths of the measured
+ *                sigma), percentile 1 .. 50, speed 1 .. 256 (256 follows at once).  manual: luma / chroma are the strengths, both 0: off.  automatic: they are
+ *                upper bounds of the measured strength; both 0: measure only -- the estimate is reported and nothing is filtered
+ *   tables       R_s[a] = clip(0, 16, floor(16 (3 s - a) / (2 s))), F_s[a] = a R_s[a] for s > 0 and a = 0 .. 255; F_0 = 0
+ *   luma         5 x 5, w = [1 4 6 4 1] x [1 4 6 4 1]; d_j = n_j - c: out = c + ((sum w_j sgn(d_j) F_s[|d_j|] + 2048) >> 12)
+ *   chroma       Cb and Cr each for itself, 3 x 3, w = 1 2 1 / 2 4 2 / 1 2 1: out = c + ((sum + 128) >> 8) with the chroma strength's table
+ *   edges        over the picture rectangle; neighbours are clamped to its visible part, a margin sample takes the result of its clamped visible position, a
+ *                letterbox border keeps its bytes
+ *   estimate     on the luma in front of the filter.  Candidates: the aligned 8 x 8 blocks wholly inside the rectangle's visible part (NC of them).  Per
+ *                block: L = the mask 1 -2 1 / -2 4 -2 / 1 -2 1 on its 36 interior samples, A = sum |L|, bin = min(255, (95 A + 1024) >> 11) (sigma in eighths
+ *                of a code); it votes iff its sample sum m has 64 (B + (S >> 4)) <= m <= 64 (B + S - (S >> 4)).  H[256] the voters' histogram, N their count;
+ *                v = the smallest bin with 100 cum(v) >= percentile N; valid iff N > 0 and 16 N >= NC
+ *   state        X in 1/256 bin: X += ((256 v - X) speed) >> 8; an invalid measurement leaves it.  Priming -- the first picture after off -> on or manual ->
+ *                automatic, and the stage calls -- sets X = 256 v (0 when invalid)
+ *   strength     s = floor((X auto_gain + 1024000) / 2048000); s_luma = min(luma, s), s_chroma = min(chroma, s)
+ * In automatic mode a plane whose bound is above 0 goes through the filter launch whatever s turns out to be (s = 0 copies it, margins as above): only the
+ * device knows s.  In manual mode a plane with strength 0 is neither read nor written. */
+#define MI355ENC_DENOISE_SPATIAL_MAX 32
+typedef struct {
+    int luma, chroma, auto_gain, percentile, speed;
+} mi355enc_denoise_spatial_t;
+typedef struct {
+    uint32_t hist[256]; /* H */
+    uint32_t candidates; /* NC */
+    uint32_t voters;     /* N */
+} mi355enc_denoise_spatial_meas_t;
+typedef struct {
+    int candidates, voters, v, valid; /* the picture's measurement (zeros in manual mode) */
+    int x;                            /* the state behind it */
+    int s_luma, s_chroma;             /* the strengths the picture was filtered with */
+    int reserved;
+} mi355enc_denoise_spatial_info_t;
+void mi355enc_denoise_spatial_default(mi355enc_denoise_spatial_t *a); /* off: {0, 0, 0, 25, 32} */
+int mi355enc_denoise_spatial_check(const mi355enc_denoise_spatial_t *a); /* host only: MI355ENC_OK or MI355ENC_ERR_ARG */
+/* host only: R_s and F_s of a strength 0 .. 32 (either pointer may be NULL, not both) */
+int mi355enc_denoise_spatial_tables(int s, uint8_t weight[256], uint16_t filter[256]);
+/* host only: the filter in place on NV12 surfaces of W x H (W a multiple of 16 up to 8192, H even up to 8192) at stride W; rect {x0, x1, y0, y1} (even, inside
+ * the surfaces), vw x vh the visible size (the rectangle's visible part not empty); s_luma, s_chroma 0 .. 32, or -1: the plane is not touched */
+int mi355enc_denoise_spatial_apply_host(uint8_t *y, uint8_t *uv, int W, int H, const int rect[4], int vw, int vh, int s_luma, int s_chroma);
+/* host only: the estimate's measurement of a luma plane (arguments as above) */
+int mi355enc_denoise_spatial_measure_host(const uint8_t *y, int W, int H, const int rect[4], int vw, int vh, int full_range, mi355enc_denoise_spatial_meas_t *m);
+/* host only: the decision of a picture (a: automatic).  *x: the state going in (0 .. 65280; ignored with prime) and coming out; m: candidates <= 2^20, the sum
+ * of hist = voters <= candidates */
+int mi355enc_denoise_spatial_decide(const mi355enc_denoise_spatial_meas_t *m, const mi355enc_denoise_spatial_t *a, int prime, int32_t *x, mi355enc_denoise_spatial_info_t *info);
+/* At any time and from any thread, no GPU call; latched once per input picture at its submit.  NULL or a setting that neither filters nor measures: off.  With
+ * an active setting mi355enc_submit_device never encodes in place: the caller's planes are only read. */
+int mi355enc_set_denoise_spatial(mi355enc_t *h, const mi355enc_denoise_spatial_t *a);
+int mi355enc_get_denoise_spatial(const mi355enc_t *h, mi355enc_denoise_spatial_t *a);
+/* of the last collected picture (either pointer may be NULL); MI355ENC_ERR_STATE before the first collect.  A picture the step did not run on reports zeros; a
+ * manual one zeros and its strengths */
+int mi355enc_last_denoise_spatial(mi355enc_t *h, mi355enc_denoise_spatial_t *a, mi355enc_denoise_spatial_info_t *info);
+size_t mi355enc_debug_denoise_spatial_bytes(const mi355enc_t *h); /* device bytes of the step: 0 until the first picture it runs on */
+/* the step alone (tests): host NV12 planes of the coded size, in and out, like mi355enc_stage_adjust; an automatic setting is primed by that picture.  The
+ * handle's own setting is not touched; a stream that follows primes.  info may be NULL */
+int mi355enc_denoise_spatial_probe_stage(mi355enc_t *h, const mi355enc_denoise_spatial_t *a, uint8_t *y, uint8_t *uv, mi355enc_denoise_spatial_info_t *info);
+/* the measure and the decide launch alone (tests), in the frame of the single-stage entry points: mi355enc_denoise_spatial_measure_host / _decide on the device */
+int mi355enc_denoise_spatial_probe_measure(mi355enc_t *h, const uint8_t *y, int W, int H, const int rect[4], int vw, int vh, int full_range, mi355enc_denoise_spatial_meas_t *m);
+int mi355enc_denoise_spatial_probe_decide(mi355enc_t *h, const mi355enc_denoise_spatial_meas_t *m, const mi355enc_denoise_spatial_t *a, int prime, int32_t *x, mi355enc_denoise_spatial_info_t *info);
 /* Lens, roll and keystone correction: the coded picture is resampled through a coarse mesh of source positions, the first step on the
  * coded surfaces (in front of the colour step, the noise filter, the picture controls, the mix, layers and text; behind the geometry and the stabiliser's
  * crop); off by default, and off nothing is allocated or launched.  All integers; >> is a floor.
@@ -980,6 +1041,9 @@ int mi355enc_stage_deblock(mi355enc_t *h, uint8_t *rec_y, uint8_t *rec_uv, const
  * 0's source surfaces: 32 measure, 33 decide (on the slabs of a measure launch in front of the timed ones), 34 apply (with that decision's table and
  * offsets, so the surfaces change with every launch).  They leave the state unprimed: the next picture submitted primes.
  * 35 the 3D LUT set last (mi355enc_set_lut3d; MI355ENC_ERR_STATE when it is off) on slot 0's source surfaces, in the form mi355enc_lut3d_plan names.
+ * 36 / 37 the spatial noise filter with the value set last (mi355enc_set_denoise_spatial) on slot 0's source surfaces: 36 the filter launches of a manual
+ * setting (both planes with both strengths above 0), 37 measure + decide + the filter launches of an automatic one (with both bounds 0: measure + decide
+ * alone); MI355ENC_ERR_STATE with a setting of the other kind or none.  37 leaves the state unprimed: the next picture submitted primes.
  * Uses whatever the handle's surfaces currently hold.  Returns average ms per launch. */
 int mi355enc_time_stage(mi355enc_t *h, int stage, int iters, double *avg_ms);
 
