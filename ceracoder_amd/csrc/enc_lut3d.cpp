@@ -58,11 +58,9 @@ int lut3d_latch(mi355enc_t *h, slot_t *s, bool own) {
 
 // the launch on surfaces of the coded size, inside the picture rectangle, in place
 static int lut3d_run(mi355enc_t *h, slot_t *s, const mi355enc_lut3d_t *set, const int32_t *coef, const uint32_t *d_nodes, int form, hipStream_t st) {
-    int rect[4]; // the picture part, without the coded padding: a quad's chroma comes from its own four samples, so graded padding would be no replica of the picture
-    yuv_rect(h, rect);
-    if (rect[1] > ((h->cfg.width + 1) & ~1)) rect[1] = (h->cfg.width + 1) & ~1;
-    if (rect[3] > ((h->cfg.height + 1) & ~1)) rect[3] = (h->cfg.height + 1) & ~1;
-    if (k_launch_lut3d(s->d_src_y, s->d_src_uv, h->W, h->H, rect, d_nodes, set->size, set->strength, coef, form < 0 ? mi355enc_lut3d_plan(set->size) : form, st)) return MI355ENC_ERR_ARG;
+    int rect[4]; // the picture part; the launch grades its visible samples and, where it reaches the visible edge, writes the coded padding as their replica: a quad's
+    yuv_rect(h, rect); // chroma comes from its own four samples, so padding graded as samples would be no replica of the graded picture
+    if (k_launch_lut3d(s->d_src_y, s->d_src_uv, h->W, h->H, h->cfg.width, h->cfg.height, rect, d_nodes, set->size, set->strength, coef, form < 0 ? mi355enc_lut3d_plan(set->size) : form, st)) return MI355ENC_ERR_ARG;
     HIPCHK(hipGetLastError());
     return MI355ENC_OK;
 }

@@ -277,7 +277,7 @@ int k_launch_dspatial_decide(const unsigned *slabs, int nslabs, unsigned NC, con
 /* A 3D colour LUT (k_lut3d.hip; the rule: DESIGN.md section 29, lut3d_host.h) on NV12 surfaces of W x H at stride W inside rect, in place: nodes N^3 checked
  * words on the device, strength 1 .. 256, coef mi355enc_lut3d_coefficients', form 0 direct (nodes from global memory) or 1 staged (the table in LDS: N up to
  * LUT3D_STAGED_FIT, nodes 16-byte aligned).  -1: arguments outside that, and nothing is launched */
-int k_launch_lut3d(uint8_t *y, uint8_t *uv, int W, int H, const int rect[4], const uint32_t *nodes, int N, int strength, const int32_t coef[19], int form, hipStream_t s);
+int k_launch_lut3d(uint8_t *y, uint8_t *uv, int W, int H, int vw, int vh, const int rect[4], const uint32_t *nodes, int N, int strength, const int32_t coef[19], int form, hipStream_t s);
 void k_launch_pack(const mb_info_t *d_mbi, const int16_t *d_levels, int nmb, int mbw, unsigned *d_off, mb_info_t *h_mbi, int16_t *h_packed,
                    unsigned *h_hdr, const unsigned *d_err, hipStream_t s);
 int k_deblock_diags(int mbw, int mbh);

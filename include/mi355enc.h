@@ -614,6 +614,11 @@ int mi355enc_warp_probe(mi355enc_t *h, const mi355enc_warp_t *s, const int32_t *
  *   4  Mf = floor(M / 1023 2^20 + 0.5); Y' = clamp((Mf[0] . g + (yoff << 20) + 2^19) >> 20, 0, 255) per sample; Cb' = clamp((the sum of the four samples'
  *      Mf[1] . g + (128 << 22) + 2^21) >> 22, 0, 255), Cr' likewise
  *   5  out = in + (((graded - in) strength + 128) >> 8) per luma and per chroma sample, strength 0 .. 256 (0: the step is off for that picture)
+ *   6  the coded margin: where the picture rectangle reaches the visible picture's right (bottom) edge, a margin sample takes the graded value of its clamped
+ *      visible position -- luma the last visible column / row, chroma the last visible pair / row, the corner both -- so the margin is the replica of the graded
+ *      picture, as every other step of the input chain leaves it (a quad's chroma comes from its own four samples, so a margin graded as samples would be no
+ *      replica, and a margin left alone is the replica of the ungraded picture: a stripe of the camera's picture coded beside the graded one).  A letterbox
+ *      border keeps its bytes.  Rule 6 is the handle's and the probe's; mi355enc_lut3d_apply_host grades the rectangle it is given and knows no margin
  * Host only, no device: */
 typedef struct {
     int size;     /* N */
@@ -648,7 +653,7 @@ size_t mi355enc_debug_lut3d_bytes(const mi355enc_t *h); /* device bytes of the s
  * cannot hold fails its submit (the picture is the same in both forms) */
 int mi355enc_debug_lut3d_form(mi355enc_t *h, int form);
 /* the launch alone (tests, measurements), in the frame of the single-stage entry points: y / uv are host planes of the coded size (16 mbw x 16 mbh, chroma
- * interleaved), graded in place inside the handle's picture rectangle with the handle's output matrix and range; form -1: the plan's, 0 / 1: that form
+ * interleaved), graded in place inside the handle's picture rectangle (rule 6 included) with the handle's output matrix and range; form -1: the plan's, 0 / 1: that form
  * (MI355ENC_ERR_ARG, and nothing launched, for the staged form with an N it cannot hold).  The handle's own setting plays no part */
 int mi355enc_lut3d_probe(mi355enc_t *h, const mi355enc_lut3d_t *set, const uint32_t *nodes, uint8_t *y, uint8_t *uv, int form);
 /* like mi355enc_submit, from host memory in `fmt`; planes[]/strides[]: as many entries as the format has planes */

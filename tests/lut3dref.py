@@ -60,14 +60,29 @@ def _interp(nodes, N, c):
     return np.stack(out, -1)
 
 
-def apply(nodes, N, strength, matrix, full, y, uv, rect=None):
-    """The rule on NV12 planes y (H x W) / uv (H / 2 x W) inside rect (x0, x1, y0, y1; all of it without) -> new (y, uv)"""
+def apply(nodes, N, strength, matrix, full, y, uv, rect=None, visible=None):
+    """The rule on NV12 planes y (H x W) / uv (H / 2 x W) inside rect (x0, x1, y0, y1; all of it without) -> new (y, uv).  visible (w, h): the planes are coded
+    surfaces with that visible size (rule 6): the rule runs on the rectangle's visible part, and where the rectangle reaches the surfaces' right (bottom) edge
+    the margin beside (below) it becomes what with_margins makes of the graded visible picture -- luma the last visible column / row, chroma the last pair / row"""
     y, uv = np.array(y, np.uint8), np.array(uv, np.uint8)
     H, W = y.shape
     x0, x1, y0, y1 = rect if rect is not None else (0, W, 0, H)
     assert N_MIN <= N <= N_MAX and len(nodes) == N ** 3 and 0 <= strength <= 256 and not (x0 | x1 | y0 | y1) & 1
     if strength == 0:
         return y, uv
+    if visible is not None:
+        vw, vh = visible
+        assert not (vw | vh) & 1 and x0 < vw and y0 < vh and (x1 <= vw or x1 == W) and (y1 <= vh or y1 == H)
+        gy, guv = apply(nodes, N, strength, matrix, full, y, uv, (x0, min(x1, vw), y0, min(y1, vh)))
+        if x1 > vw:  # the margin columns of the rectangle's visible rows
+            gy[y0:min(y1, vh), vw:] = gy[y0:min(y1, vh), vw - 1:vw]
+            c = guv.reshape(H // 2, W // 2, 2)
+            c[y0 // 2:min(y1, vh) // 2, vw // 2:] = c[y0 // 2:min(y1, vh) // 2, vw // 2 - 1:vw // 2]
+        if y1 > vh:  # the margin rows, of the rectangle's columns and of the margin columns just written: the corner is both
+            xe = W if x1 > vw else x1
+            gy[vh:, x0:xe] = gy[vh - 1:vh, x0:xe]
+            guv[vh // 2:, x0:xe] = guv[vh // 2 - 1:vh // 2, x0:xe]
+        return gy, guv
     co = coefficients(matrix, full)
     minv, mf, yoff = np.array(co[:9], np.int64).reshape(3, 3), np.array(co[9:18], np.int64).reshape(3, 3), co[18]
     Y = y[y0:y1, x0:x1].astype(np.int64)

@@ -16,9 +16,14 @@ pytestmark = pytest.mark.gpu
 
 GOP, QP, NPIC = 30, 28, 6
 MATRIX = 6  # what an unspecified matrix resolves to at these sizes
-# (visible size, geometry's input size and destination or None) -> coded surfaces 16 x 16, 80 x 80 (eight columns of padding), 208 x 128 (a letterbox inside)
-SHAPES = {"16x16": ((16, 16), None), "72x80": ((72, 80), None), "208x128-letterbox": ((208, 128), ((176, 108), (16, 10, 176, 108)))}
-RECTS = {"16x16": (0, 16, 0, 16), "72x80": (0, 72, 0, 80), "208x128-letterbox": (16, 192, 10, 118)}
+# (visible size, geometry's input size and destination or None) -> coded surfaces 16 x 16, 80 x 80 (eight columns of padding), 208 x 128 (a letterbox inside), and
+# 80 x 64 around 70 x 50 with a letterbox that reaches the bottom edge from a column that is no multiple of 8: to the right edge too (the corner), and to a
+# column inside the visible width that is no multiple of 8 either (border columns in the margin rows on both sides)
+SHAPES = {"16x16": ((16, 16), None), "72x80": ((72, 80), None), "208x128-letterbox": ((208, 128), ((176, 108), (16, 10, 176, 108))),
+          "70x50-letterbox-to-the-corner": ((70, 50), ((96, 64), (12, 8, 58, 42))), "70x50-letterbox-to-the-bottom": ((70, 50), ((96, 64), (12, 8, 42, 42)))}
+# the picture rectangle in the coded surfaces: it reaches their edge where it reaches the visible picture's (72 x 80: the eight margin columns belong to it)
+RECTS = {"16x16": (0, 16, 0, 16), "72x80": (0, 80, 0, 80), "208x128-letterbox": (16, 192, 10, 118), "70x50-letterbox-to-the-corner": (12, 80, 8, 64),
+         "70x50-letterbox-to-the-bottom": (12, 54, 8, 64)}
 COLORIMETRY = [(0, 1), (1, 1), (0, 6), (1, 9)]  # (full range, matrix)
 CUBES = {}
 
@@ -45,7 +50,7 @@ def encoder(E, shape, full=0, matrix=2, **kw):
 @pytest.mark.parametrize("form", [0, 1], ids=["direct", "staged"])
 @pytest.mark.parametrize("shape", list(SHAPES))
 def test_probe_is_byte_equal_to_the_reference(E, shape, form):
-    rect = RECTS[shape]
+    rect, (w, h) = RECTS[shape], SHAPES[shape][0]
     for k, (full, matrix) in enumerate(COLORIMETRY):
         e = encoder(E, shape, full, matrix)
         W, H = 16 * e.mbw, 16 * e.mbh
@@ -59,9 +64,13 @@ def test_probe_is_byte_equal_to_the_reference(E, shape, form):
                     continue  # (every N, cube and strength with the first pair; the other pairs with two sizes of each)
                 nodes = cube(kind, N)
                 gy, guv = e.lut3d_probe(nodes, y, uv, strength, form)
-                wy, wuv = R.apply(nodes, N, strength, matrix, full, y, uv, rect)
+                wy, wuv = R.apply(nodes, N, strength, matrix, full, y, uv, rect, visible=(w, h))
                 assert np.array_equal(gy, wy) and np.array_equal(guv, wuv), (N, kind, strength, full, matrix)
-                assert np.array_equal(gy[outside_y], y[outside_y]) and np.array_equal(guv[outside_uv], uv[outside_uv])
+                assert np.array_equal(gy[outside_y], y[outside_y]) and np.array_equal(guv[outside_uv], uv[outside_uv])  # the letterbox border keeps its bytes
+                # the coded margin (noise on the way in) comes out as the replica of the graded visible picture, inside the rectangle's columns and rows
+                ry, ruv = AL.with_margins(gy[:h, :w], guv[:h // 2, :w], W, H)
+                inside_y, inside_uv = ~outside_y, ~outside_uv
+                assert np.array_equal(gy[inside_y], ry[inside_y]) and np.array_equal(guv[inside_uv], ruv[inside_uv]), (N, kind, strength, full, matrix)
                 assert not np.array_equal(gy, y) and not np.array_equal(guv, uv)
         assert e.debug_lut3d_bytes() == 0 and e.get_lut3d() is None  # (the probe is no part of the handle's own step)
         e.close()
@@ -72,7 +81,7 @@ def test_the_plan_names_the_form_the_probe_takes(E):
     y, uv = noise_surfaces(80, 80, 3)
     for N in (2, 17, 33, 34, 35, 65):
         nodes = R.quantise(R.cube_noise(N, N))
-        want = R.apply(nodes, N, 200, MATRIX, 0, y, uv, RECTS["72x80"])
+        want = R.apply(nodes, N, 200, MATRIX, 0, y, uv, RECTS["72x80"], visible=(72, 80))
         got = e.lut3d_probe(nodes, y, uv, 200)
         assert E.lut3d_plan(N) in (E.LUT3D_DIRECT, E.LUT3D_STAGED) and np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
     e.close()
@@ -121,7 +130,7 @@ def stream(e, pics, depth=2, before=None):
     return (out, (e.fetch(0), e.fetch(1))), last
 
 
-@pytest.mark.parametrize("w,h", [(64, 48), (208, 128)], ids=lambda v: str(v))
+@pytest.mark.parametrize("w,h", [(64, 48), (208, 128), (72, 80), (70, 50)], ids=lambda v: str(v))
 def test_stream_equals_the_plain_encoder_fed_the_references_pictures(E, w, h):
     pics = nv12_clip(w, h, NPIC, 500)
     t = (cube("noise", 17), 17)
@@ -140,7 +149,7 @@ def test_stream_equals_the_plain_encoder_fed_the_references_pictures(E, w, h):
     e.close()
 
 
-@pytest.mark.parametrize("w,h", [(64, 48), (208, 128)], ids=lambda v: str(v))
+@pytest.mark.parametrize("w,h", [(64, 48), (208, 128), (72, 80), (70, 50)], ids=lambda v: str(v))
 def test_off_after_on_returns_to_plain_bytes(E, w, h):
     pics = nv12_clip(w, h, NPIC, 507)
     t = (cube("log", 33), 33)
@@ -149,7 +158,8 @@ def test_off_after_on_returns_to_plain_bytes(E, w, h):
     e.set_lut3d(t[0])
     got, last = stream(e, pics, before=lambda i: e.set_lut3d(None) if i == 3 else None)
     assert e.get_lut3d() is None and last[:3] == [(dict(size=33, strength=256), 1)] * 3 and last[3:] == [(dict(size=0, strength=0), 0)] * 3
-    assert np.array_equal(e.fetch(E.FETCH_SOURCE_Y), pics[-1][0]) and np.array_equal(e.fetch(E.FETCH_SOURCE_UV), pics[-1][1])
+    py, puv = AL.with_margins(*pics[-1], 16 * e.mbw, 16 * e.mbh)  # (off, the coded surfaces are the input path's: the picture and its replicas)
+    assert np.array_equal(e.fetch(E.FETCH_SOURCE_Y), py) and np.array_equal(e.fetch(E.FETCH_SOURCE_UV), puv)
     e.close()
     same(got, ref)
     # on and off again before the first picture: the plain stream, and nothing was allocated
