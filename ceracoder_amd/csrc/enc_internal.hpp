@@ -14,6 +14,7 @@
 //   enc_adjust.cpp    picture controls: setter, latch, the two launch forms and the scratch plane, its stage entry point
 //   enc_autolevel.cpp automatic levels and white balance: setter, latch, the three launches and the device block, the probes and the stage entry point
 //   enc_lut3d.cpp     3D colour LUT: setter, latch, the table's way to the device, the launch, its probe and timed stage
+//   enc_roi.cpp       region-of-interest quantisation: setter, the map's latch per picture and its pinned copies, the compose launch, the stage hook and the offsets probe
 //   enc_dspatial.cpp  spatial noise reduction: setter, latch, the estimate's two launches, the filter launches and their scratch planes, probes, stage entry point
 //   enc_denoise.cpp   temporal noise reduction: setter, latch, the launch and the handle's history, its stage entry point
 //   enc_stab.cpp      electronic image stabilisation: setter, latch, the estimate in front of every scale launch, its probes and timed stages
@@ -51,6 +52,7 @@
 #include "dspatial_host.h"
 #include "warp_host.h"
 #include "lut3d_host.h"
+#include "roi_host.h"
 #include "enc_plan.hpp"
 #include "enc_sync.hpp"
 
@@ -160,6 +162,10 @@ struct slot_t {
     // output matrix and range it met; lut_send: the slot's pinned copy holds that table and it travels in front of the launch; applied once, to the input's own
     // slot, in ingest_end
     bool lut_on, lut_send; mi355enc_lut3d_t lut; unsigned lut_gen; int32_t lut_coef[LUT3D_COEF_WORDS];
+    // region-of-interest quantisation: what enqueue_picture latched for this picture (roi_on false: no map, or an inactive one) -- the map's own pinned copy h_roi
+    // (nmb + 16 bytes, allocated by the slot's first picture with a map), which the compose launch reads and nothing writes again before the picture is collected,
+    // its background offset and the sum of its values; a recovery keeps all of it
+    bool roi_on; int roi_bg, roi_sum; int8_t *h_roi;
 };
 
 struct mi355enc {
@@ -194,7 +200,7 @@ struct mi355enc {
     uint16_t *d_surf[NSET]; // SAD surfaces of the motion search, SURF_U16 per macroblock; one set per picture in flight: the front stages of picture n+1 (n+2) run beside the back stages of n
     imv_t *d_imv[NSET][3];   // whole-sample vector fields (search result / selection iterations alternate), per set
     uint8_t *d_idec2[NSET];  // intra decisions per set (d_idec = set 0)
-    int8_t *d_qp_off[NSET];  // adaptive quantisation: QP offset per macroblock, per set (null unless cfg.aq_mode)
+    int8_t *d_qp_off[NSET];  // adaptive quantisation: QP offset per macroblock, per set (null unless cfg.aq_mode, or a picture with an active region-of-interest map has been submitted: enc_roi.cpp)
     uint8_t *d_psrc[2];   // padded source luma of the last two coded pictures: the search runs source against source
     int psrc_cur;         // which of them holds the last coded picture
     uint8_t *d_ip_strips;    // intra macroblocks of P pictures: the bottom lines they publish for the row below, IP_STRIP_BYTES per macroblock
@@ -345,6 +351,19 @@ struct mi355enc {
     uint32_t *d_lut = nullptr, *h_lut = nullptr;
     size_t lut_bytes = 0;
     int lut_form = -1; // (mi355enc_debug_lut3d_form: the launch form of the handle's own launches; -1: the plan's)
+    // region-of-interest quantisation (mi355enc_set_roi): what the control thread set last (under roi_mu: the configuration, the map t it
+    // stands for on the heap -- nmb bytes, kept from the first set on --, whether it is active, its background offset and sum; enqueue_picture latches it per
+    // picture) and what the last collected picture carried.  The offsets themselves are d_qp_off's: without aq_mode the first picture with an active map
+    // allocates the sets (roi_bytes: those bytes).  roi_stage: the map of the single-stage entry points (mi355enc_roi_probe_set_map; null: none).
+    std::mutex roi_mu;
+    std::atomic<bool> roi_set{false}; // (read without the mutex by every enqueue_picture: a handle the setter was never called on takes no lock per picture)
+    bool roi_active = false;
+    mi355enc_roi_t roi_cur = {};
+    int8_t *roi_map = nullptr, *roi_stage = nullptr;
+    int roi_bg = 0, roi_sum = 0;
+    bool roi_last_have = false;
+    int roi_last_active = 0, roi_last_bg = 0, roi_last_sum = 0;
+    size_t roi_bytes = 0;
     bool warp_staging = true; // (mi355enc_debug_warp_staging: false -- every workgroup of the launch takes the direct form)
     // frame-rate conversion (mi355enc_set_rate_conversion).  rate.mode 0: off, and nothing below is used but last_count.  rate.max_fill is
     // clamped to pipeline_depth.  rate_plan: the rule's state; ingest_begin steps a copy of it (rate_next, with what the step yields: rate_n pictures, their pts
@@ -430,7 +449,7 @@ bool host_range_pinned(const void *p, size_t bytes); // inside memory handed out
 int run_intra(mi355enc_t *h, int ci, const frame_ctx_t *hc, unsigned *band_done = nullptr);
 int run_pmb(mi355enc_t *h, const frame_ctx_t *hc, int refine, const pic_plan_t &plan, hipStream_t st); // the fused P stage as the plan gates it, booked (the default plan: in order)
 int run_deblock(mi355enc_t *h, int ci, const frame_ctx_t *hc, const pic_plan_t &plan = pic_plan_t(), int rec = -1); // (the defaults: in order on the main stream, no band-done words)
-void fill_ctx(mi355enc_t *h, frame_ctx_t *c, int qp, int drop, int idr, int set = 0);
+void fill_ctx(mi355enc_t *h, frame_ctx_t *c, int qp, int drop, int idr, int set = 0, int roi = 0); // roi: the picture carries an active region-of-interest map
 int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_t *src_uv, int src_stride, int64_t pts, int force_idr);
 void entropy_worker(mi355enc_t *h);
 // enc_input.cpp
@@ -567,6 +586,12 @@ bool lut3d_time_ready(mi355enc_t *h, int stage);             // mi355enc_time_st
 int lut3d_time_prepare(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // the table set last onto the device
 int lut3d_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x);
 void lut3d_time_done(mi355enc_t *h);                         // ... behind the timed launches: the next graded picture sends its table again
+// enc_roi.cpp (region-of-interest quantisation)
+int roi_latch(mi355enc_t *h, slot_t *s);                     // enqueue_picture of a newly submitted picture: the map set last becomes the slot's, in its pinned copy (an active one: the offset sets exist from here on)
+void roi_compose(mi355enc_t *h, const slot_t *s, int set, hipStream_t st); // the slot's map and (aq_mode) what aq_kernel left in d_qp_off[set] -> the picture's offsets there, behind everything enqueued on st so far
+int roi_stage_ctx(mi355enc_t *h, frame_ctx_t *c);            // a single-stage call's context: one QP per picture, or the probe's map on its way into d_qp_off[0] on the main stream
+void roi_collected(mi355enc_t *h, slot_t *s);                // collect(): books what the picture carried as the last picture's
+void roi_free(mi355enc_t *h);
 // enc_warp.cpp (lens, roll and keystone correction)
 int warp_latch(mi355enc_t *h, slot_t *s, bool own);          // the value set last becomes the slot's (beside stab_latch); own: the slot the input goes into, which also takes the mesh where it is a new one
 int warp_draw(mi355enc_t *h, slot_t *s, hipStream_t st);     // the slot's warp on its coded surfaces, behind everything enqueued on st so far (a new mesh travels in front of it); nothing with none

@@ -82,7 +82,7 @@ static const uint32_t k_drop_sad[DROP_MAX + 1] = {0, 384, 512, 768, 1024, 1536, 
 #define I8_QP_MAX 37 /* Intra_8x8 is tried up to this picture quantiser (oracle: ORC_I8_QP_MAX) */
 static const int32_t k_idrop_ac[DROP_MAX + 1] = {0, 1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 64, 0x7FFFFFFF};
 
-void fill_ctx(mi355enc_t *h, frame_ctx_t *c, int qp, int drop, int idr, int set) {
+void fill_ctx(mi355enc_t *h, frame_ctx_t *c, int qp, int drop, int idr, int set, int roi) {
     c->mbi = h->d_mbi; c->levels = h->d_levels; c->isad = h->d_isad; c->dbrec = h->d_dbrec; c->idec = h->d_idec2[set];
     c->stride = h->W; c->mbw = h->mbw; c->mbh = h->mbh;
     c->slice_rows = idr ? h->islice_rows : h->pslice_rows; c->slice_dbf = h->slice_dbf;
@@ -96,7 +96,7 @@ void fill_ctx(mi355enc_t *h, frame_ctx_t *c, int qp, int drop, int idr, int set)
     c->iac_drop = (idr && drop > 0 && drop <= DROP_MAX) ? k_idrop_ac[drop] : 0;
     if (c->iac_drop) c->i4x4 = 0; // on the ladder: Intra_16x16 only
     c->i8 = (idr && h->cfg.transform8x8 && h->cfg.i8x8 && h->cfg.intra_mode == 0 && !c->iac_drop && qp <= I8_QP_MAX) ? 1 : 0;
-    c->qp_off = h->cfg.aq_mode ? h->d_qp_off[set] : nullptr;
+    c->qp_off = (h->cfg.aq_mode || roi) ? h->d_qp_off[set] : nullptr; // (roi: this picture latched an active region-of-interest map)
     c->intra_p = h->cfg.intra_in_p ? (h->cfg.i4x4 && h->cfg.intra_in_p > 1 ? 2 : 1) : 0; // 2: Intra_4x4 as well
     c->ir_c0 = 0; c->ir_c1 = 0; c->ir_clean = -1; // (enqueue_picture sets the refresh columns of a picture of an intra-refresh stream)
 }
@@ -152,7 +152,7 @@ static int run_p_back(mi355enc_t *h, const frame_ctx_t *hc, slot_t *s, int prof,
 
 // ---- one picture: decide (host state) -> plan (enc_plan.hpp) -> enqueue from the plan -> book.  No decision is taken behind the picture's first launch.
 // what decide_picture() settles about a picture on the host
-struct pic_t { const uint8_t *src_y, *src_uv; int src_stride, idr, qp, drop, ir_j, all_skip, nxt, set, prof; }; // nxt: the reconstruction buffer it writes; set: its device set and context copy
+struct pic_t { const uint8_t *src_y, *src_uv; int src_stride, idr, qp, drop, ir_j, all_skip, nxt, set, prof, roi; }; // nxt: the reconstruction buffer it writes; set: its device set and context copy; roi: it carries an active region-of-interest map
 
 // Decide: IDR or P, rate control's pick, the position in the intra-refresh cycle, all-skip, buffers and device set, whether the stage timers are sampled
 static pic_t decide_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_t *src_uv, int src_stride, int force_idr) {
@@ -182,13 +182,13 @@ static pic_t decide_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, cons
     // (a sampled picture runs its stages strictly in order; IDR pictures: every other one, or at the P pictures' cadence in an all-intra stream)
     const int prof = !all_skip && h->cfg.profile_events > 0 &&
                      ((idr && h->cfg.gop > 1) ? (h->idr_count & 1) == 0 : h->n_submitted % (uint64_t)h->cfg.profile_events == 0);
-    return {src_y, src_uv, src_stride, idr, qp, drop, ir_j, all_skip, all_skip ? h->cur : (h->cur ^ 1) /* an all-skip picture IS its reference: nothing is written */, (int)(h->n_submitted % NSET), prof};
+    return {src_y, src_uv, src_stride, idr, qp, drop, ir_j, all_skip, all_skip ? h->cur : (h->cur ^ 1) /* an all-skip picture IS its reference: nothing is written */, (int)(h->n_submitted % NSET), prof, s->roi_on ? 1 : 0};
 }
 // Plan: what plan_picture() is asked with
 static plan_in_t plan_inputs(const mi355enc_t *h, const pic_t &p) {
     plan_in_t in;
     in.idr = p.idr != 0; in.all_skip = p.all_skip != 0; in.prof = p.prof != 0;
-    in.pipeline_depth = h->cfg.pipeline_depth; in.intra_mode = h->cfg.intra_mode; in.deblock_mode = h->cfg.deblock_mode; in.aq_mode = h->cfg.aq_mode;
+    in.pipeline_depth = h->cfg.pipeline_depth; in.intra_mode = h->cfg.intra_mode; in.deblock_mode = h->cfg.deblock_mode; in.aq_mode = h->cfg.aq_mode || p.roi; // (the plan's aq_mode: "offsets are present for this picture")
     in.intra_in_p = h->cfg.intra_in_p; in.i4x4 = h->cfg.i4x4; in.profile_overlap = h->cfg.profile_overlap;
     in.overlap_allowed = overlap_allowed(h); in.exclusive_device = exclusive_device(h); in.wait_room[0] = h->wait_room[0]; in.wait_room[1] = h->wait_room[1];
     in.keep_prefilter = h->d_pre_y != nullptr; in.ref_flags = h->words.rec_epoch(h->cur) != 0; in.pgate = h->pgate; in.fip_rows = h->fip_rows;
@@ -219,7 +219,7 @@ static int picture_ctx(mi355enc_t *h, frame_ctx_t *c, const pic_t &p) {
     c->ref_y = h->d_rec_y[h->cur]; c->ref_uv = h->d_rec_uv[h->cur];
     c->rec_y = h->d_rec_y[p.nxt]; c->rec_uv = h->d_rec_uv[p.nxt];
     c->vis_h = h->cfg.height;
-    fill_ctx(h, c, p.qp, p.drop, p.idr, p.set);
+    fill_ctx(h, c, p.qp, p.drop, p.idr, p.set, p.roi);
     c->mbi = h->d_mbi_set[p.set]; c->levels = h->d_levels_set[p.set];
     if (!p.idr && c->intra_p) { int r = h->words.ip_rows_stamp(c->epoch, h->stream); if (r) return r; }
     if (p.ir_j >= 0) {
@@ -237,7 +237,8 @@ static int enqueue_front(mi355enc_t *h, slot_t *s, const pic_t &p, const pic_pla
     frame_ctx_t *c = s->h_ctx;
     { int r = picture_ctx(h, c, p); if (r) return r; }
     if (plan.upload_ctx) HIPCHK(hipMemcpyAsync(h->d_ctx2[p.set], c, sizeof *c, hipMemcpyHostToDevice, h->stream));
-    if (c->qp_off) k_launch_aq(c, h->d_qp_off[p.set], h->fstream); // adaptive quantisation: the offsets of this picture's macroblocks
+    if (h->cfg.aq_mode) k_launch_aq(c, h->d_qp_off[p.set], h->fstream); // adaptive quantisation: the offsets of this picture's macroblocks
+    if (p.roi) roi_compose(h, s, p.set, h->fstream); // ... moved by the picture's region-of-interest map (alone: the map is the offsets)
     if (p.idr) k_launch_copy_luma(c, h->fstream);
     else { int r = run_p_front(h, c, s, p.prof); if (r) return r; }
     HIPCHK(hipEventRecord(s->ev_front, h->fstream));
@@ -322,6 +323,7 @@ static void book_picture(mi355enc_t *h, slot_t *s, const pic_t &p, int64_t pts, 
 // uploaded for this picture was enqueued on the same stream.
 int enqueue_picture(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_t *src_uv, int src_stride, int64_t pts, int force_idr) {
     if (!h->recovering) snapshot_latch(h, s); // stills: an armed request becomes this picture's (a picture recover() enqueues again keeps what it had)
+    if (!h->recovering) { int r = roi_latch(h, s); if (r) return r; } // the region-of-interest map set last likewise
     const pic_t p = decide_picture(h, s, src_y, src_uv, src_stride, force_idr);
     const pic_plan_t plan = plan_picture(plan_inputs(h, p)); // streams and device-side waits: all of them, before the first launch
     int r = p.all_skip ? enqueue_all_skip(h, s, p) : enqueue_front(h, s, p, plan);
@@ -542,6 +544,7 @@ int mi355enc_collect(mi355enc_t *h, uint8_t *out, size_t out_cap, size_t *out_le
     autolevel_collected(h, s);
     dspatial_collected(h, s);
     lut3d_collected(h, s);
+    roi_collected(h, s);
     denoise_collected(h, s);
     stab_collected(h, s);
     warp_collected(h, s);

@@ -22,7 +22,7 @@ static int stage_ctx(mi355enc_t *h, int qp, bool src_is_staging, int drop = 0, i
     fill_ctx(h, c, qp, drop, idr);
     c->slice_rows = h->stage_slice_rows; c->slice_dbf = h->stage_slice_dbf;
     c->all_intra = 0; // the single-stage deblocking entry point takes records of either picture type
-    c->qp_off = nullptr; // (single stages: one QP per picture)
+    { int r = roi_stage_ctx(h, c); if (r) return r; } // (single stages: one QP per picture, or the map of mi355enc_roi_probe_set_map)
     HIPCHK(hipMemcpyAsync(h->d_ctx, c, sizeof *c, hipMemcpyHostToDevice, h->stream));
     stage_touched(h);
     return 0;

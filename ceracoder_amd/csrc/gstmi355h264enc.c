@@ -121,6 +121,10 @@ typedef struct {
     /* a 3D colour LUT on the device (mi355enc_set_lut3d): lut3d-location, the path of a .cube file, read and parsed in the setter (""
      * or NULL: off; lut_nodes: its lut_size^3 nodes, NULL: none), and lut3d-strength, a double 0 .. 1 stored as round(256 x); under the object lock */
     gchar *lut_location; guint32 *lut_nodes; gint lut_size, lut_strength;
+    /* region-of-interest quantisation (mi355enc_set_roi): roi, the rectangles as "x,y,w,h,delta[,feather];..." (parsed in the setter; ""
+     * or NULL: off; roi_text: the string as it was accepted), and roi-balance, the cap of the background offset; under the object lock.  The library latches
+     * the map with the next frame submitted */
+    gchar *roi_text; mi355enc_roi_t roi;
     /* stabilize (mi355enc_set_stabilize): the margin in input samples per side (0: off; odd values count as the even value below), added
      * to each of crop-* when the geometry is built -- so a change while playing is a crop change --, and the estimator's range and leak */
     gint stab, stab_range, stab_leak;
@@ -160,7 +164,7 @@ enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME
        PROP_SNAP_LOCATION, PROP_SNAP_INTERVAL, PROP_SNAP_QUALITY, PROP_SNAP_REDUCE, PROP_SNAP_SOURCE,
        PROP_OUTPUT_COLORIMETRY, PROP_RATE_CONVERSION, PROP_OUTPUT_FRAMERATE, PROP_MAX_FILL, PROP_HDR_INPUT, PROP_HDR_PEAK_NITS, PROP_HDR_TARGET_NITS,
        PROP_ADJ_BRIGHTNESS, PROP_ADJ_CONTRAST, PROP_ADJ_HUE, PROP_ADJ_SATURATION, PROP_ADJ_GAMMA, PROP_ADJ_SHARPEN, PROP_ADJ_SHARPEN_THRESHOLD,
-       PROP_DENOISE_LUMA, PROP_DENOISE_CHROMA, PROP_DENOISE_MOTION, PROP_DS_LUMA, PROP_DS_CHROMA, PROP_DS_AUTO, PROP_DS_PERCENTILE, PROP_DS_SPEED, PROP_STABILIZE, PROP_STABILIZE_RANGE, PROP_STABILIZE_LEAK, PROP_AUTO_LEVELS, PROP_AUTO_BALANCE, PROP_AUTO_SPEED, PROP_AUTO_CLIP, PROP_AUTO_MAX_GAIN, PROP_LUT3D_LOCATION, PROP_LUT3D_STRENGTH,
+       PROP_DENOISE_LUMA, PROP_DENOISE_CHROMA, PROP_DENOISE_MOTION, PROP_DS_LUMA, PROP_DS_CHROMA, PROP_DS_AUTO, PROP_DS_PERCENTILE, PROP_DS_SPEED, PROP_STABILIZE, PROP_STABILIZE_RANGE, PROP_STABILIZE_LEAK, PROP_AUTO_LEVELS, PROP_AUTO_BALANCE, PROP_AUTO_SPEED, PROP_AUTO_CLIP, PROP_AUTO_MAX_GAIN, PROP_LUT3D_LOCATION, PROP_LUT3D_STRENGTH, PROP_ROI, PROP_ROI_BALANCE,
        PROP_LENS_K1, PROP_LENS_K2, PROP_LENS_ZOOM, PROP_ROLL, PROP_KEYSTONE_H, PROP_KEYSTONE_V, PROP_WARP_FILTER };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
@@ -388,8 +392,31 @@ static void lut3d_set_location(GstMi355H264Enc *s, const gchar *path) {
     GST_OBJECT_UNLOCK(s);
 }
 
+/* stored rectangles and balance -> the encoder, if one is open (object lock held; the library computes the map and stores it: no GPU call, any thread) */
+static void roi_forward(GstMi355H264Enc *s) {
+    if (!s->enc) return;
+    if (mi355enc_set_roi(s->enc, s->roi.n_rects > 0 ? &s->roi : NULL, NULL) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the region of interest: it keeps its previous one");
+}
+/* roi: parsed here, in the setter, outside the object lock (the warning goes to the bus).  "" or NULL: off.  A string the parser refuses leaves the map as it was */
+static void roi_set_text(GstMi355H264Enc *s, const gchar *text) {
+    mi355enc_roi_t c;
+    mi355enc_roi_default(&c);
+    if (mi355enc_roi_parse(text ? text : "", &c) != MI355ENC_OK) {
+        GST_ELEMENT_WARNING(s, LIBRARY, SETTINGS, ("mi355h264enc: roi \"%s\" is not a list of at most 8 rectangles x,y,w,h,delta[,feather] joined by ';' (delta -12 .. 12 and not 0, "
+                                                   "feather 0 .. 8): the region of interest stays as it was", text), (NULL));
+        return;
+    }
+    GST_OBJECT_LOCK(s);
+    c.balance = s->roi.balance;
+    s->roi = c;
+    g_free(s->roi_text); s->roi_text = g_strdup(text ? text : "");
+    roi_forward(s);
+    GST_OBJECT_UNLOCK(s);
+}
+
 static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *ps) {
     GstMi355H264Enc *s = GST_MI355H264ENC(obj);
+    if (id == PROP_ROI) { roi_set_text(s, g_value_get_string(val)); return; }
     if (id == PROP_IMG_LOCATION) { image_set_location(s, g_value_get_string(val)); return; }
     if (id == PROP_LUT3D_LOCATION) { lut3d_set_location(s, g_value_get_string(val)); return; }
     GST_OBJECT_LOCK(s);
@@ -418,6 +445,7 @@ static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *
     case PROP_AUTO_CLIP: s->al.clip_low = s->al.clip_high = (int)lround(100.0 * g_value_get_double(val)); autolevel_forward(s); break;
     case PROP_AUTO_MAX_GAIN: s->al.max_gain = (int)lround(1000.0 * g_value_get_double(val)); autolevel_forward(s); break;
     case PROP_LUT3D_STRENGTH: s->lut_strength = (int)lround(256.0 * g_value_get_double(val)); lut3d_forward(s); break;
+    case PROP_ROI_BALANCE: s->roi.balance = g_value_get_int(val); roi_forward(s); break;
     case PROP_DENOISE_LUMA: s->dn.luma = g_value_get_int(val); denoise_forward(s); break;
     case PROP_DENOISE_CHROMA: s->dn.chroma = g_value_get_int(val); denoise_forward(s); break;
     case PROP_DENOISE_MOTION: s->dn_motion = g_value_get_int(val); denoise_forward(s); break;
@@ -515,6 +543,8 @@ static void get_property(GObject *obj, guint id, GValue *val, GParamSpec *ps) {
     case PROP_AUTO_MAX_GAIN: g_value_set_double(val, s->al.max_gain / 1000.0); break;
     case PROP_LUT3D_LOCATION: g_value_set_string(val, s->lut_location ? s->lut_location : ""); break;
     case PROP_LUT3D_STRENGTH: g_value_set_double(val, s->lut_strength / 256.0); break;
+    case PROP_ROI: g_value_set_string(val, s->roi_text ? s->roi_text : ""); break;
+    case PROP_ROI_BALANCE: g_value_set_int(val, s->roi.balance); break;
     case PROP_DENOISE_LUMA: g_value_set_int(val, s->dn.luma); break;
     case PROP_DENOISE_CHROMA: g_value_set_int(val, s->dn.chroma); break;
     case PROP_DENOISE_MOTION: g_value_set_int(val, s->dn_motion); break;
@@ -938,6 +968,7 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     adjust_forward(s);                      /* ... nor the picture controls */
     autolevel_forward(s);                   /* ... nor the automatic levels and white balance */
     lut3d_forward(s);                       /* ... nor the 3D LUT */
+    roi_forward(s);                         /* ... nor the region of interest */
     denoise_forward(s);                     /* ... nor the noise filter */
     dspatial_forward(s);                    /* ... nor the spatial noise filter */
     stabilize_forward(s);                   /* ... nor the stabiliser */
@@ -1287,6 +1318,7 @@ static void finalize(GObject *obj) {
     g_free(GST_MI355H264ENC(obj)->img_rgba);
     g_free(GST_MI355H264ENC(obj)->snap_location);
     g_free(GST_MI355H264ENC(obj)->lut_location);
+    g_free(GST_MI355H264ENC(obj)->roi_text);
     g_free(GST_MI355H264ENC(obj)->lut_nodes);
     g_free(GST_MI355H264ENC(obj)->out_colorimetry);
     g_mutex_clear(&GST_MI355H264ENC(obj)->snap_mu); g_mutex_clear(&GST_MI355H264ENC(obj)->snap_enc_mu); g_cond_clear(&GST_MI355H264ENC(obj)->snap_cv);
@@ -1406,6 +1438,11 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
     g_object_class_install_property(g, PROP_LUT3D_LOCATION, g_param_spec_string("lut3d-location", "3D LUT location",
         "a 3D colour LUT on the GPU, behind the noise filter and in front of automatic levels and the picture controls: the path of a .cube file (LUT_3D_SIZE 2 .. 65, tetrahedral interpolation), read when the property is set, at any time; empty: off.  A file that cannot be read or parsed posts a warning and leaves the step as it was", "", F));
     g_object_class_install_property(g, PROP_LUT3D_STRENGTH, g_param_spec_double("lut3d-strength", "3D LUT strength", "how much of the 3D LUT's grade is applied, per sample between the input and the graded value; 0: off", 0.0, 1.0, 1.0, F));
+    g_object_class_install_property(g, PROP_ROI, g_param_spec_string("roi", "Regions of interest",
+        "Up to 8 rectangles \"x,y,w,h,delta[,feather]\" joined by ';': luma samples of the coded picture, a QP offset -12 .. 12 (negative: finer, not 0) inside and the macroblocks "
+        "0 .. 8 over which it ramps to 0 outside; takes effect with the next frame; empty: off", "", F));
+    g_object_class_install_property(g, PROP_ROI_BALANCE, g_param_spec_int("roi-balance", "Region-of-interest balance",
+        "The bits the regions of interest take are taken from the rest of the picture: the cap of the QP offset the macroblocks outside every region get; 0: off", 0, 12, 0, F));
     g_object_class_install_property(g, PROP_DS_LUMA, g_param_spec_int("denoise-spatial-luma", "Spatial denoise luma", "spatial noise reduction on the GPU, edge-preserving, in front of the temporal filter: the luma noise amplitude in codes that is filtered fully -- with denoise-auto above 0 the upper bound of the measured strength; 0: off", 0, MI355ENC_DENOISE_SPATIAL_MAX, 0, F));
     g_object_class_install_property(g, PROP_DS_CHROMA, g_param_spec_int("denoise-spatial-chroma", "Spatial denoise chroma", "spatial noise reduction on the GPU: the chroma noise amplitude in codes that is filtered fully -- with denoise-auto above 0 the upper bound of the measured strength; 0: off", 0, MI355ENC_DENOISE_SPATIAL_MAX, 0, F));
     g_object_class_install_property(g, PROP_DS_AUTO, g_param_spec_double("denoise-auto", "Automatic denoise strength", "the spatial filter's strength as this multiple of the noise sigma measured per picture on the GPU (0.25 .. 8; a knob, not a tuned value); with both bounds 0 the noise is measured and reported and nothing is filtered; 0: manual", 0.0, 8.0, 0.0, F));
@@ -1448,6 +1485,7 @@ static void gst_mi355h264enc_init(GstMi355H264Enc *s) {
     mi355enc_denoise_spatial_default(&s->ds);
     mi355enc_autolevel_default(&s->al);
     s->lut_location = NULL; s->lut_nodes = NULL; s->lut_size = 0; s->lut_strength = 256;
+    s->roi_text = NULL; mi355enc_roi_default(&s->roi);
     s->dn_motion = 0;
     s->stab = 0; s->stab_range = 16; s->stab_leak = 16;
     s->warp_k1 = s->warp_k2 = s->warp_roll = s->warp_kh = s->warp_kv = 0.0; s->warp_zoom = 1.0; s->warp_filter = 1;

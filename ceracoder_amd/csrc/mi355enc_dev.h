@@ -92,7 +92,7 @@ typedef struct {
     int32_t iac_drop;              /* I pictures on rate control's ladder: 0 off, else the sum of level magnitudes up to which a macroblock's luma / chroma
                                       residual is not sent */
     int32_t intra_p;               /* P macroblocks may be intra (the analysis of this picture's source is in isad / idec) */
-    const int8_t *qp_off;          /* adaptive quantisation: one QP offset per macroblock (aq_kernel), or null: one QP per picture */
+    const int8_t *qp_off;          /* adaptive quantisation and / or a region-of-interest map: one QP offset per macroblock (aq_kernel, roi_compose_kernel), or null: one QP per picture */
     int32_t partitions;            /* P macroblocks may be split (shape in the record's i16_mode: 1 16x8, 2 8x16, 3 8x8; the vectors of partitions 1 .. 3 in the
                                       luma-DC slot of the macroblock's levels); the deblocker then takes boundary strengths per 8x8 quadrant */
     int32_t slice_rows;            /* a new slice every so many macroblock rows (0: one slice); the row above a slice's first row is not available (6.4.8): intra prediction,
@@ -285,6 +285,10 @@ int k_deblock_diags(int mbw, int mbh);
  * final -- the QP_Y of macroblocks that send no mb_qp_delta (7.4.5: that of the macroblock before them), which the deblocker reads (orc_qp_chain) */
 void k_launch_aq(const frame_ctx_t *h_ctx, int8_t *d_off, hipStream_t s);
 void k_launch_qp_chain(mb_info_t *d_mbi, int nmb, int slice_qp, int slice_mbs, hipStream_t s);
+/* region-of-interest quantisation (k_roi.hip; the rule: DESIGN.md section 31, roi_host.h): d_off[m] = clamp(aq + t[m], -12, 12) for the nmb macroblocks of a
+ * picture -- aq what d_off holds (have_aq: aq_kernel ran in front on the same stream) or 0; t: nmb bytes the device can read (pinned host or device memory),
+ * 4-byte aligned like d_off */
+void k_launch_roi_compose(const int8_t *t, int8_t *d_off, int nmb, int have_aq, hipStream_t s);
 /* Quality metrics of one picture (k_quality.hip; the rule: DESIGN.md section 12): NV12 source against NV12 reconstruction over the visible width x height.
  * d_acc: QUALITY_ACC_WORDS 64-bit words on the device, zero before the first launch (every launch leaves them zero again): QUALITY_SHARDS sets of five
  * accumulators, QUALITY_SHARD_STRIDE words (4 KB: another memory channel) apart, and the ticket; out: five words (a block of QUALITY_WORDS) -- SSE of Y, Cb, Cr,

@@ -95,6 +95,8 @@ EXPORTS = [
     "mi355enc_denoise_spatial_probe_decide",
     "mi355enc_lut3d_coefficients", "mi355enc_lut3d_check", "mi355enc_lut3d_identity", "mi355enc_lut3d_parse_cube", "mi355enc_lut3d_apply_host", "mi355enc_lut3d_plan",
     "mi355enc_set_lut3d", "mi355enc_get_lut3d", "mi355enc_last_lut3d", "mi355enc_debug_lut3d_bytes", "mi355enc_lut3d_probe", "mi355enc_debug_lut3d_form",
+    "mi355enc_roi_default", "mi355enc_roi_check", "mi355enc_roi_map", "mi355enc_roi_parse", "mi355enc_set_roi", "mi355enc_get_roi", "mi355enc_last_roi",
+    "mi355enc_debug_roi_bytes", "mi355enc_roi_probe_set_map", "mi355enc_roi_probe_offsets",
 ]
 
 
@@ -233,6 +235,20 @@ class Lut3d(C.Structure):
 
     def as_dict(self):
         return dict(size=int(self.size), strength=int(self.strength))
+
+
+class RoiRect(C.Structure):
+    """mi355enc_roi_rect_t: a rectangle in luma samples, its QP offset -12 .. +12 (not 0) and its feather 0 .. 8 in macroblocks"""
+    _fields_ = [(n, C.c_int) for n in ("x", "y", "w", "h", "delta", "feather")]
+
+
+class Roi(C.Structure):
+    """mi355enc_roi_t: up to eight rectangles and the cap 0 .. 12 of the background offset"""
+    _fields_ = [("n_rects", C.c_int), ("rect", RoiRect * 8), ("balance", C.c_int)]
+
+    def as_dict(self):
+        n = max(0, min(8, int(self.n_rects)))
+        return dict(rects=[tuple(int(getattr(self.rect[k], f)) for f, _ in RoiRect._fields_) for k in range(n)], balance=int(self.balance))
 
 
 class Warp(C.Structure):
@@ -470,6 +486,18 @@ def load():
         L.mi355enc_debug_lut3d_bytes.argtypes = [vp]
         L.mi355enc_lut3d_probe.argtypes = [vp, C.POINTER(Lut3d), vp, vp, vp, C.c_int]
         L.mi355enc_debug_lut3d_form.argtypes = [vp, C.c_int]
+        L.mi355enc_roi_default.argtypes = [C.POINTER(Roi)]
+        L.mi355enc_roi_default.restype = None
+        L.mi355enc_roi_check.argtypes = [C.POINTER(Roi)]
+        L.mi355enc_roi_map.argtypes = [C.POINTER(Roi), vp, C.c_int, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.mi355enc_roi_parse.argtypes = [C.c_char_p, C.POINTER(Roi)]
+        L.mi355enc_set_roi.argtypes = [vp, C.POINTER(Roi), vp]
+        L.mi355enc_get_roi.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(Roi)]
+        L.mi355enc_last_roi.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.mi355enc_debug_roi_bytes.restype = C.c_size_t
+        L.mi355enc_debug_roi_bytes.argtypes = [vp]
+        L.mi355enc_roi_probe_set_map.argtypes = [vp, vp]
+        L.mi355enc_roi_probe_offsets.argtypes = [vp, vp, vp]
         L.mi355enc_set_quality_metrics.argtypes = [vp, C.c_int]
         L.mi355enc_last_quality.argtypes = [vp, C.POINTER(Quality)]
         L.mi355enc_quality_totals.argtypes = [vp, C.POINTER(Quality)]
@@ -821,6 +849,51 @@ def denoise_spatial_decide(m, a, x=None, prime=False):
     """mi355enc_denoise_spatial_decide (host only): a picture's decision from its measurement (a DenoiseSpatialMeas or dict(hist=, candidates=, voters=)), an
     automatic setting and the state X going in -> (record, X coming out)"""
     return _denoise_spatial_decide(load().mi355enc_denoise_spatial_decide, "denoise_spatial_decide", m, a, x, prime)
+
+
+def roi(rects=(), balance=0):
+    """A Roi from rects = [(x, y, w, h, delta[, feather]), ...] and the balance cap (or a Roi, or a dict of both, as it is); nothing is checked here"""
+    if isinstance(rects, Roi):
+        return rects
+    if isinstance(rects, dict):
+        rects, balance = rects.get("rects", ()), rects.get("balance", 0)
+    rects = list(rects)
+    if len(rects) > 8:
+        raise EncoderError("roi: more than 8 rectangles")
+    c = Roi()
+    c.n_rects, c.balance = len(rects), int(balance)
+    for k, r in enumerate(rects):
+        r = tuple(int(v) for v in r) + ((0,) if len(r) == 5 else ())
+        c.rect[k] = RoiRect(*r)
+    return c
+
+
+def roi_check(cfg):
+    """mi355enc_roi_check (host only): 0, or the error code for a field outside its range"""
+    return load().mi355enc_roi_check(C.byref(roi(cfg)))
+
+
+def roi_map(cfg, user, mbw, mbh):
+    """mi355enc_roi_map (host only): the map of cfg (None: no rectangle) and the caller's int8 map `user` (None: none) for mbw x mbh macroblocks ->
+    (t as int8 (mbh, mbw), active, background); EncoderError where it is refused"""
+    out, act, bg = np.zeros((int(mbh), int(mbw)), np.int8), C.c_int(-1), C.c_int(-1)
+    u = None if user is None else np.ascontiguousarray(user, np.int8).reshape(-1)
+    if u is not None and u.size != int(mbw) * int(mbh):
+        raise EncoderError("roi_map: the caller's map has %d values for %d macroblocks" % (u.size, int(mbw) * int(mbh)))
+    r = load().mi355enc_roi_map(None if cfg is None else C.byref(roi(cfg)), None if u is None else _p(u), int(mbw), int(mbh), _p(out), C.byref(act), C.byref(bg))
+    if r:
+        raise EncoderError("roi_map: refused (%d)" % r)
+    return out, bool(act.value), int(bg.value)
+
+
+def roi_parse(text, balance=0):
+    """mi355enc_roi_parse (host only): the element's string form "x,y,w,h,delta[,feather];..." -> a Roi with that balance; EncoderError where it is refused"""
+    c = Roi()
+    c.balance = int(balance)
+    r = load().mi355enc_roi_parse(text.encode() if isinstance(text, str) else text, C.byref(c))
+    if r:
+        raise EncoderError("roi_parse: refused (%d)" % r)
+    return c
 
 
 def _lut3d_nodes(nodes):
@@ -1735,6 +1808,43 @@ class Encoder:
         assert y.shape == (self.mbh * 16, self.mbw * 16) and uv.shape == (self.mbh * 8, self.mbw * 16)
         self._chk(self.L.mi355enc_lut3d_probe(self.h, C.byref(Lut3d(N, int(strength))), _p(n), _p(y), _p(uv), int(form)), "lut3d_probe")
         return y, uv
+
+    def set_roi(self, cfg=None, user_map=None):
+        """Region-of-interest quantisation from the next picture submitted on (any time, any thread, no GPU call): a roi() / Roi / dict of rectangles and
+        balance, and / or the caller's own int8 map of one offset -12 .. +12 per macroblock; both None: off.  Pictures in flight keep their map."""
+        u = None if user_map is None else np.ascontiguousarray(user_map, np.int8).reshape(-1)
+        if u is not None and u.size != self.mbw * self.mbh:
+            raise EncoderError("set_roi: the map has %d values for %d macroblocks" % (u.size, self.mbw * self.mbh))
+        self._chk(self.L.mi355enc_set_roi(self.h, None if cfg is None else C.byref(roi(cfg)), None if u is None else _p(u)), "set_roi")
+
+    def get_roi(self):
+        """the configuration set last as a dict(rects=, balance=), None when off"""
+        on, c = C.c_int(0), Roi()
+        self._chk(self.L.mi355enc_get_roi(self.h, C.byref(on), C.byref(c)), "get_roi")
+        return c.as_dict() if on.value else None
+
+    def last_roi(self):
+        """(active, background, sum) of the last collected picture's map; (False, 0, 0) for a picture without"""
+        a, b, s = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._chk(self.L.mi355enc_last_roi(self.h, C.byref(a), C.byref(b), C.byref(s)), "last_roi")
+        return bool(a.value), int(b.value), int(s.value)
+
+    def debug_roi_bytes(self):
+        return int(self.L.mi355enc_debug_roi_bytes(self.h))
+
+    def roi_probe_set_map(self, t=None):
+        """The single-stage entry points quantise with this int8 map of one offset per macroblock from now on (None: one QP per picture again); no device work"""
+        u = None if t is None else np.ascontiguousarray(t, np.int8).reshape(-1)
+        if u is not None and u.size != self.mbw * self.mbh:
+            raise EncoderError("roi_probe_set_map: the map has %d values for %d macroblocks" % (u.size, self.mbw * self.mbh))
+        self._chk(self.L.mi355enc_roi_probe_set_map(self.h, None if u is None else _p(u)), "roi_probe_set_map")
+
+    def roi_probe_offsets(self, y):
+        """The offsets a picture with the coded-size luma y would be coded with under the map set last: aq_kernel (aq on) and the compose launch -> int8 (mbh, mbw)"""
+        y, out = np.ascontiguousarray(y, np.uint8), np.zeros((self.mbh, self.mbw), np.int8)
+        assert y.shape == (self.mbh * 16, self.mbw * 16)
+        self._chk(self.L.mi355enc_roi_probe_offsets(self.h, _p(y), _p(out)), "roi_probe_offsets")
+        return out
 
     def set_warp_mesh(self, s, mesh):
         """... through the caller's own mesh, int32 (ny, nx, 2) for the coded visible size (s None: off)"""

@@ -656,6 +656,55 @@ int mi355enc_debug_lut3d_form(mi355enc_t *h, int form);
  * interleaved), graded in place inside the handle's picture rectangle (rule 6 included) with the handle's output matrix and range; form -1: the plan's, 0 / 1: that form
  * (MI355ENC_ERR_ARG, and nothing launched, for the staged form with an N it cannot hold).  The handle's own setting plays no part */
 int mi355enc_lut3d_probe(mi355enc_t *h, const mi355enc_lut3d_t *set, const uint32_t *nodes, uint8_t *y, uint8_t *uv, int form);
+/* Region-of-interest quantisation: the application says where the bits go -- a face, a scoreboard, the road ahead -- as up to eight
+ * rectangles with a QP offset each, optionally a map of its own, and the encoder quantises every macroblock with the picture's QP moved by its offset.  Off by
+ * default, and off nothing is allocated, launched or planned differently.  All integers; / of non-negative operands.
+ *   per macroblock m = (mx, my) of the mbw x mbh picture:
+ *   1  rectangle k: mx0 = x >> 4, mx1 = (x + w - 1) >> 4 (floors), rows likewise; d = max(mx0 - mx, mx - mx1, my0 - my, my - my1, 0), the Chebyshev distance in
+ *      macroblocks; c_k = delta for d = 0, sign(delta) ((|delta| (feather + 1 - d)) / (feather + 1)) for 1 <= d <= feather, 0 beyond.  A rectangle wholly
+ *      outside the 16 mbw x 16 mbh picture contributes nothing (feather included) and is no error
+ *   2  emphasis wins: e = min(0, min_k c_k), p = max(0, max_k c_k); the rectangle part is e where e < 0, else p
+ *   3  the caller's map (optional, mbw mbh values of -12 .. +12): t[m] = clamp(rectangle part + user[m], -12, 12)
+ *   4  balance ("move bits, do not add them"): with balance > 0, S = sum t[m] < 0 and N0 = #{m: t[m] = 0} > 0, every macroblock with t[m] = 0 gets
+ *      b = min(balance, (-S + N0 / 2) / N0); nothing changes otherwise
+ *   5  the map is active iff some t[m] != 0; an inactive map is the same as no map
+ *   6  on the device off[m] = clamp(aq[m] + t[m], -12, 12), aq[m] the adaptive-quantisation offset (0 without aq_mode); QP_Y = clamp(qp + off[m], 0, 51).  Two
+ *      macroblocks differ by at most 24, inside mb_qp_delta's -26 .. +25 (7.4.5).  Only quantisation and QP_Y change: search, refinement and mode decisions
+ *      keep the picture's lambda, and rate control is not told -- it sees the bytes
+ * Host only, no device: */
+typedef struct {
+    int x, y, w, h; /* luma samples of the coded picture's visible area; may reach beyond it (clipped).  |x|, |y| <= 65536, 1 <= w, h <= 65536 */
+    int delta;      /* -12 .. +12, not 0: the QP offset inside (negative: finer) */
+    int feather;    /* 0 .. 8: macroblocks over which the offset ramps to 0 outside */
+} mi355enc_roi_rect_t;
+typedef struct {
+    int n_rects;    /* 0 .. 8 */
+    mi355enc_roi_rect_t rect[8];
+    int balance;    /* 0: off; 1 .. 12: the cap of the background offset of rule 4 */
+} mi355enc_roi_t;
+void mi355enc_roi_default(mi355enc_roi_t *cfg);      /* no rectangle, no balance */
+int mi355enc_roi_check(const mi355enc_roi_t *cfg);   /* MI355ENC_ERR_ARG for any field outside its range */
+/* rules 1 .. 5 into out[mbw mbh] (1 <= mbw, mbh <= 512); cfg NULL: no rectangle and no balance; user NULL: none (a value outside -12 .. +12: MI355ENC_ERR_ARG,
+ * out untouched).  *active: rule 5; *background: the b rule 4 applied (0: none).  Either may be NULL */
+int mi355enc_roi_map(const mi355enc_roi_t *cfg, const int8_t *user, int mbw, int mbh, int8_t *out, int *active, int *background);
+/* the element's string form: rectangles "x,y,w,h,delta[,feather]" joined by ';', decimal integers, blanks around them allowed; an empty string: no rectangle.
+ * cfg->balance stays.  MI355ENC_ERR_ARG (cfg untouched) for anything else, a ninth rectangle or a value mi355enc_roi_check refuses */
+int mi355enc_roi_parse(const char *text, mi355enc_roi_t *cfg);
+/* On a handle.  set: at any time and from any thread, with pictures in flight, no GPU call: the map t is computed here (cfg and user as for mi355enc_roi_map;
+ * both NULL: off) and latched by the next submitted picture; pictures already submitted keep the map they were submitted with.  A picture with an active map is
+ * planned exactly as an aq_mode 1 picture is; one without is planned and coded as if the call had never been made */
+int mi355enc_set_roi(mi355enc_t *h, const mi355enc_roi_t *cfg, const int8_t *user_map);
+int mi355enc_get_roi(const mi355enc_t *h, int *on, mi355enc_roi_t *cfg); /* what was set last (the configuration: the caller's map is not kept apart; either pointer may be NULL) */
+/* of the last collected picture: whether its map was active, the background offset rule 4 gave it and the sum of its t (zeros for a picture without);
+ * MI355ENC_ERR_STATE before the first collect */
+int mi355enc_last_roi(mi355enc_t *h, int *active, int *background, int *sum);
+size_t mi355enc_debug_roi_bytes(const mi355enc_t *h); /* device bytes the feature holds: 0 until the first picture with an active map is submitted (and always with aq_mode, whose offsets it shares) */
+/* parity tests (named as the other features' probes are; both in the frame of the single-stage entry points).  probe_set_map: a setting of the handle like
+ * mi355enc_stage_set_slice_rows, no device work -- the single-stage entry points then quantise with this map of mbw mbh offsets (-12 .. +12; copied) instead
+ * of one QP per picture; NULL: as before.  probe_offsets: the offsets a picture of the stream would be coded with under the map set last (mi355enc_set_roi)
+ * -- aq_kernel on the coded-size host luma src_y if aq_mode, then the compose launch -- into off_out[mbw mbh] */
+int mi355enc_roi_probe_set_map(mi355enc_t *h, const int8_t *map);
+int mi355enc_roi_probe_offsets(mi355enc_t *h, const uint8_t *src_y, int8_t *off_out);
 /* like mi355enc_submit, from host memory in `fmt`; planes[]/strides[]: as many entries as the format has planes */
 int mi355enc_submit_fmt(mi355enc_t *h, int fmt, const uint8_t *const planes[3], const int strides[3], int64_t pts, int force_idr);
 /* conversion stage alone (tests): writes the coded-size NV12 surfaces (16*mbw x 16*mbh luma, then interleaved chroma) */
