@@ -349,6 +349,7 @@ void mi355enc_close(mi355enc_t *h) {
     dspatial_free(h);
     lut3d_close(h);
     roi_free(h);
+    mask_free(h);
     denoise_free(h);
     stab_free(h);
     warp_close(h);

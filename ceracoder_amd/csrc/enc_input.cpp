@@ -4,7 +4,7 @@
 //   its own argument checks
 //   ingest_begin   the pipeline-full check (with frame-rate conversion: the rule's step, which says how many pictures the submit yields), the slot, the latches (text, image layers)
 //   fill           its own way of filling the input target: copy | convert | decode | scale, ending in input_finish (the orientation launch)
-//   ingest_end     warp -> colour step -> spatial noise filter -> noise filter -> 3D LUT -> automatic levels -> picture controls -> [frame-rate conversion: mix / keep / repeat, per output picture] -> image layers -> text -> upload event -> enqueue_picture
+//   ingest_end     warp -> colour step -> spatial noise filter -> noise filter -> 3D LUT -> automatic levels -> picture controls -> [frame-rate conversion: mix / keep / repeat, per output picture] -> privacy masks -> image layers -> text -> upload event -> enqueue_picture
 //                  (enc_schedule.cpp) on the slot's own surfaces
 // The one exception is the in-place exit of mi355enc_submit_device.  A new step on the way in goes into ingest_end (one that works on the coded surfaces) or
 // in front of input_finish (one that works on the pre-orientation picture), never into a submit.
@@ -43,7 +43,8 @@ static int ingest_latch(mi355enc_t *h, slot_t *s) {
         denoise_latch(h, t, false); // (likewise; only the input's own slot launches and needs the tables)
         (void)stab_latch(h, t, false); // (likewise: the shake is measured on the input, once)
         (void)warp_latch(h, t, false); // (likewise: the input is warped, once)
-        int r = image_latch(h, t);
+        int r = mask_latch(h, t); // (every output picture is masked afresh, with its own latch: holds and blends keep their unmasked source)
+        if (!r) r = image_latch(h, t);
         if (r) return r;
     }
     overlay_latch(h, s);
@@ -54,6 +55,7 @@ static int ingest_latch(mi355enc_t *h, slot_t *s) {
     denoise_latch(h, s, true);
     { int r = stab_latch(h, s, true); if (r) return r; }
     { int r = warp_latch(h, s, true); if (r) return r; }
+    { int r = mask_latch(h, s); if (r) return r; }
     return image_latch(h, s);
 }
 // (apart only for mi355enc_submit_jpeg, which decodes into the slot between the two: after the state check -- with the pipeline full the slot's buffers
@@ -64,7 +66,8 @@ static int ingest_begin(mi355enc_t *h, slot_t **s, int64_t pts, int force_idr) {
 }
 // everything that is drawn into a picture on top of its samples, in this order, then the schedule
 static int draw_and_enqueue(mi355enc_t *h, slot_t *s, hipStream_t up, int64_t pts, int force_idr) {
-    int r = image_draw(h, s, up);
+    int r = mask_draw(h, s, up); // the privacy masks first: logos and the stats line stay sharp on top of them
+    if (!r) r = image_draw(h, s, up);
     if (!r) r = overlay_draw(h, s, up);
     if (!r) r = upload_done(h, s);
     return r ? r : enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
@@ -360,8 +363,8 @@ int mi355enc_submit_device(mi355enc_t *h, const void *d_y, int y_stride, const v
         r = input_finish(h, s, up, (const uint8_t *)d_y, y_stride, (const uint8_t *)d_uv, uv_stride);
     } else {
         const int w = h->cfg.width, ht = h->cfg.height;
-        // in place -- unless the frame rate is converted (the picture may be kept, repeated or mixed), the samples are to be warped, converted, filtered, graded or adjusted, a text drawn or an image blended in: that goes into the encoder's own surfaces, never into the caller's planes
-        const bool direct = !h->rate.mode && !s->warp_on && !s->yuv_step && !s->ds_on && !s->dn.parts && !s->lut_on && !s->al_on && !s->adj.parts && !s->ov_len && !image_active(s) && w == h->W && y_stride == uv_stride && (y_stride & 15) == 0 && (((uintptr_t)d_y | (uintptr_t)d_uv) & 15) == 0;
+        // in place -- unless the frame rate is converted (the picture may be kept, repeated or mixed), the samples are to be warped, converted, filtered, graded, adjusted or masked, a text drawn or an image blended in: that goes into the encoder's own surfaces, never into the caller's planes
+        const bool direct = !h->rate.mode && !s->warp_on && !s->yuv_step && !s->ds_on && !s->dn.parts && !s->lut_on && !s->al_on && !s->adj.parts && !s->mask_on && !s->ov_len && !image_active(s) && w == h->W && y_stride == uv_stride && (y_stride & 15) == 0 && (((uintptr_t)d_y | (uintptr_t)d_uv) & 15) == 0;
         if (direct) return enqueue_picture(h, s, (const uint8_t *)d_y, (const uint8_t *)d_uv, y_stride, pts, force_idr);
         HIPCHK(hipMemcpy2DAsync(s->d_src_y, h->W, d_y, y_stride, w, ht, hipMemcpyDeviceToDevice, up));
         HIPCHK(hipMemcpy2DAsync(s->d_src_uv, h->W, d_uv, uv_stride, w, ht / 2, hipMemcpyDeviceToDevice, up));

@@ -15,6 +15,7 @@
 //   enc_autolevel.cpp automatic levels and white balance: setter, latch, the three launches and the device block, the probes and the stage entry point
 //   enc_lut3d.cpp     3D colour LUT: setter, latch, the table's way to the device, the launch, its probe and timed stage
 //   enc_roi.cpp       region-of-interest quantisation: setter, the map's latch per picture and its pinned copies, the compose launch, the stage hook and the offsets probe
+//   enc_mask.cpp      privacy masks: setter, the latch per output picture, the handle's result surface and ping-pong planes, the launches, the probe and timed stages
 //   enc_dspatial.cpp  spatial noise reduction: setter, latch, the estimate's two launches, the filter launches and their scratch planes, probes, stage entry point
 //   enc_denoise.cpp   temporal noise reduction: setter, latch, the launch and the handle's history, its stage entry point
 //   enc_stab.cpp      electronic image stabilisation: setter, latch, the estimate in front of every scale launch, its probes and timed stages
@@ -53,6 +54,7 @@
 #include "warp_host.h"
 #include "lut3d_host.h"
 #include "roi_host.h"
+#include "mask_host.h"
 #include "enc_plan.hpp"
 #include "enc_sync.hpp"
 
@@ -166,6 +168,9 @@ struct slot_t {
     // (nmb + 16 bytes, allocated by the slot's first picture with a map), which the compose launch reads and nothing writes again before the picture is collected,
     // its background offset and the sum of its values; a recovery keeps all of it
     bool roi_on; int roi_bg, roi_sum; int8_t *h_roi;
+    // the privacy masks: what the picture latched in front of its draw (mask_on: some region reaches the visible picture and the launches run; mask: the
+    // configuration it carries, n 0 for none; mask_gen: the count of sets it belongs to) -- every output picture its own, drawn first in draw_and_enqueue
+    bool mask_on; mi355enc_mask_t mask; unsigned mask_gen;
 };
 
 struct mi355enc {
@@ -364,6 +369,17 @@ struct mi355enc {
     bool roi_last_have = false;
     int roi_last_active = 0, roi_last_bg = 0, roi_last_sum = 0;
     size_t roi_bytes = 0;
+    // privacy masks (mi355enc_set_mask): what the control thread set last (under mask_mu; every drawn picture latches it) and what the last
+    // collected picture carried.  d_mask: the result surface and the two ping-pong planes, a coded picture each, allocated by the first masked picture (mask_bytes)
+    // and used on the upload stream alone (the probe and the timed stages: on the main stream, with nothing in flight).
+    std::mutex mask_mu;
+    std::atomic<bool> mask_set{false}; // (read without the mutex by every latch: a handle the setter was never called on takes no lock per picture)
+    bool mask_on = false;
+    mi355enc_mask_t mask_cur = {}, mask_last = {};
+    unsigned mask_gen = 0, mask_last_gen = 0;
+    bool mask_last_have = false;
+    uint8_t *d_mask = nullptr;
+    size_t mask_bytes = 0;
     bool warp_staging = true; // (mi355enc_debug_warp_staging: false -- every workgroup of the launch takes the direct form)
     // frame-rate conversion (mi355enc_set_rate_conversion).  rate.mode 0: off, and nothing below is used but last_count.  rate.max_fill is
     // clamped to pipeline_depth.  rate_plan: the rule's state; ingest_begin steps a copy of it (rate_next, with what the step yields: rate_n pictures, their pts
@@ -592,6 +608,14 @@ void roi_compose(mi355enc_t *h, const slot_t *s, int set, hipStream_t st); // th
 int roi_stage_ctx(mi355enc_t *h, frame_ctx_t *c);            // a single-stage call's context: one QP per picture, or the probe's map on its way into d_qp_off[0] on the main stream
 void roi_collected(mi355enc_t *h, slot_t *s);                // collect(): books what the picture carried as the last picture's
 void roi_free(mi355enc_t *h);
+// enc_mask.cpp (privacy masks)
+int mask_latch(mi355enc_t *h, slot_t *s);                    // the value set last becomes the slot's: every picture that is drawn latches its own (one with a region on the picture: the surfaces exist from here on)
+int mask_draw(mi355enc_t *h, slot_t *s, hipStream_t st);     // the slot's masks on its coded surfaces, behind everything enqueued on st so far and in front of layers and text; nothing with none
+void mask_collected(mi355enc_t *h, slot_t *s);               // collect(): books what the picture carried as the last picture's
+void mask_free(mi355enc_t *h);
+bool mask_time_ready(mi355enc_t *h, int stage);              // mi355enc_time_stage 38 / 39: the value set last holds a fill or pixelate / a blur region
+int mask_time_prepare(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // the surfaces, and the value set last as slot 0's
+int mask_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // 38 the pixelate and commit launches, 39 the blur launches
 // enc_warp.cpp (lens, roll and keystone correction)
 int warp_latch(mi355enc_t *h, slot_t *s, bool own);          // the value set last becomes the slot's (beside stab_latch); own: the slot the input goes into, which also takes the mesh where it is a new one
 int warp_draw(mi355enc_t *h, slot_t *s, hipStream_t st);     // the slot's warp on its coded surfaces, behind everything enqueued on st so far (a new mesh travels in front of it); nothing with none

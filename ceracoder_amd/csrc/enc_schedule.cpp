@@ -545,6 +545,7 @@ int mi355enc_collect(mi355enc_t *h, uint8_t *out, size_t out_cap, size_t *out_le
     dspatial_collected(h, s);
     lut3d_collected(h, s);
     roi_collected(h, s);
+    mask_collected(h, s);
     denoise_collected(h, s);
     stab_collected(h, s);
     warp_collected(h, s);

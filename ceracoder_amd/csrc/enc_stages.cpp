@@ -46,7 +46,7 @@ static int download_picture(mi355enc_t *h, void *mbinfo, uint8_t *rec_y, uint8_t
 enum {
     TS_ME = 0, TS_INTER, TS_INTRA, TS_DEBLOCK, TS_SUBPEL, TS_CSC_I420, TS_CSC_YUY2, TS_CSC_UYVY, TS_ME_SELECT, TS_PMB, TS_INTRA_P, TS_QUALITY, TS_JPEG, TS_ORIENT, TS_SCALE,
     TS_IMAGE, TS_SNAPSHOT, TS_YUV_CONVERT, TS_RATE, TS_HDR_P010, TS_HDR_I420_10, TS_HDR_V210, TS_DEEP_P010, TS_ADJUST_POINT, TS_ADJUST_SHARPEN, TS_DENOISE,
-    TS_DENOISE_PRIME, TS_DENOISE_SEARCH, TS_DENOISE_MC, TS_STAB_PROJECT, TS_STAB_MATCH, TS_WARP, TS_AL_MEASURE, TS_AL_DECIDE, TS_AL_APPLY, TS_LUT3D, TS_DSPATIAL, TS_DSPATIAL_AUTO, TS_COUNT
+    TS_DENOISE_PRIME, TS_DENOISE_SEARCH, TS_DENOISE_MC, TS_STAB_PROJECT, TS_STAB_MATCH, TS_WARP, TS_AL_MEASURE, TS_AL_DECIDE, TS_AL_APPLY, TS_LUT3D, TS_DSPATIAL, TS_DSPATIAL_AUTO, TS_MASK_CELLS, TS_MASK_BLUR, TS_COUNT
 };
 // ready: the precondition (false: MI355ENC_ERR_STATE); prepare: once, outside the timed loop; launch: the body of the loop; done: behind the timed loop;
 // needs_raw: slot 0's raw staging buffer must exist (any bytes will do as a source: 0x55).  Null: nothing.
@@ -150,8 +150,10 @@ static constexpr ts_row_t k_ts[] = {
     {TS_LUT3D,          lut3d_time_ready,   lut3d_time_prepare,     lut3d_time_launch,     lut3d_time_done,   false}, // (mi355enc_set_lut3d first)
     {TS_DSPATIAL,       dspatial_time_ready, nullptr,               dspatial_time_launch,  dspatial_time_done, false}, // (mi355enc_set_denoise_spatial first: a manual setting)
     {TS_DSPATIAL_AUTO,  dspatial_time_ready, nullptr,               dspatial_time_launch,  dspatial_time_done, false}, // (... an automatic one)
+    {TS_MASK_CELLS,     mask_time_ready,    mask_time_prepare,      mask_time_launch,      nullptr,           false}, // (mi355enc_set_mask first: 38 with a fill or pixelate region, 39 with a blur region)
+    {TS_MASK_BLUR,      mask_time_ready,    mask_time_prepare,      mask_time_launch,      nullptr,           false},
 };
-static_assert(sizeof k_ts / sizeof k_ts[0] == 38 && TS_COUNT == 38, "one row per stage 0 .. 37");
+static_assert(sizeof k_ts / sizeof k_ts[0] == 40 && TS_COUNT == 40, "one row per stage 0 .. 39");
 template <size_t... I> static constexpr bool ts_rows_in_order(std::index_sequence<I...>) { return ((k_ts[I].stage == (int)I) && ...); }
 static_assert(ts_rows_in_order(std::make_index_sequence<TS_COUNT>()), "row i describes stage i");
 

@@ -125,6 +125,10 @@ typedef struct {
      * or NULL: off; roi_text: the string as it was accepted), and roi-balance, the cap of the background offset; under the object lock.  The library latches
      * the map with the next frame submitted */
     gchar *roi_text; mi355enc_roi_t roi;
+    /* privacy masks (mi355enc_set_mask): mask, the regions as "x,y,w,h,mode,param[,shape];..." (parsed in the setter; "" or NULL: off;
+     * mask_text: the string as it was accepted), and mask-color, the fill colour 0xRRGGBB every region takes; under the object lock.  The library latches the
+     * configuration with the next frame submitted */
+    gchar *mask_text; mi355enc_mask_t mask; guint mask_color;
     /* stabilize (mi355enc_set_stabilize): the margin in input samples per side (0: off; odd values count as the even value below), added
      * to each of crop-* when the geometry is built -- so a change while playing is a crop change --, and the estimator's range and leak */
     gint stab, stab_range, stab_leak;
@@ -164,7 +168,7 @@ enum { PROP_0, PROP_BPS, PROP_BITRATE, PROP_KEY_INT_MAX, PROP_DEVICE_ID, PROP_ME
        PROP_SNAP_LOCATION, PROP_SNAP_INTERVAL, PROP_SNAP_QUALITY, PROP_SNAP_REDUCE, PROP_SNAP_SOURCE,
        PROP_OUTPUT_COLORIMETRY, PROP_RATE_CONVERSION, PROP_OUTPUT_FRAMERATE, PROP_MAX_FILL, PROP_HDR_INPUT, PROP_HDR_PEAK_NITS, PROP_HDR_TARGET_NITS,
        PROP_ADJ_BRIGHTNESS, PROP_ADJ_CONTRAST, PROP_ADJ_HUE, PROP_ADJ_SATURATION, PROP_ADJ_GAMMA, PROP_ADJ_SHARPEN, PROP_ADJ_SHARPEN_THRESHOLD,
-       PROP_DENOISE_LUMA, PROP_DENOISE_CHROMA, PROP_DENOISE_MOTION, PROP_DS_LUMA, PROP_DS_CHROMA, PROP_DS_AUTO, PROP_DS_PERCENTILE, PROP_DS_SPEED, PROP_STABILIZE, PROP_STABILIZE_RANGE, PROP_STABILIZE_LEAK, PROP_AUTO_LEVELS, PROP_AUTO_BALANCE, PROP_AUTO_SPEED, PROP_AUTO_CLIP, PROP_AUTO_MAX_GAIN, PROP_LUT3D_LOCATION, PROP_LUT3D_STRENGTH, PROP_ROI, PROP_ROI_BALANCE,
+       PROP_DENOISE_LUMA, PROP_DENOISE_CHROMA, PROP_DENOISE_MOTION, PROP_DS_LUMA, PROP_DS_CHROMA, PROP_DS_AUTO, PROP_DS_PERCENTILE, PROP_DS_SPEED, PROP_STABILIZE, PROP_STABILIZE_RANGE, PROP_STABILIZE_LEAK, PROP_AUTO_LEVELS, PROP_AUTO_BALANCE, PROP_AUTO_SPEED, PROP_AUTO_CLIP, PROP_AUTO_MAX_GAIN, PROP_LUT3D_LOCATION, PROP_LUT3D_STRENGTH, PROP_ROI, PROP_ROI_BALANCE, PROP_MASK, PROP_MASK_COLOR,
        PROP_LENS_K1, PROP_LENS_K2, PROP_LENS_ZOOM, PROP_ROLL, PROP_KEYSTONE_H, PROP_KEYSTONE_V, PROP_WARP_FILTER };
 
 static GstStaticPadTemplate sink_tmpl = GST_STATIC_PAD_TEMPLATE("sink", GST_PAD_SINK, GST_PAD_ALWAYS,
@@ -414,8 +418,30 @@ static void roi_set_text(GstMi355H264Enc *s, const gchar *text) {
     GST_OBJECT_UNLOCK(s);
 }
 
+/* stored regions -> the encoder, if one is open (object lock held; the library checks and stores them: no GPU call, any thread) */
+static void mask_forward(GstMi355H264Enc *s) {
+    if (!s->enc) return;
+    for (int k = 0; k < s->mask.n; k++) s->mask.region[k].colour = s->mask_color;
+    if (mi355enc_set_mask(s->enc, s->mask.n > 0 ? &s->mask : NULL) != MI355ENC_OK) GST_WARNING_OBJECT(s, "the encoder refused the privacy masks: it keeps its previous ones");
+}
+/* mask: parsed here, in the setter, outside the object lock (the warning goes to the bus).  "" or NULL: off.  A string the parser refuses leaves the masks as they were */
+static void mask_set_text(GstMi355H264Enc *s, const gchar *text) {
+    mi355enc_mask_t c;
+    if (mi355enc_mask_parse(text ? text : "", 0, &c) != MI355ENC_OK) {
+        GST_ELEMENT_WARNING(s, LIBRARY, SETTINGS, ("mi355h264enc: mask \"%s\" is not a list of at most 8 regions x,y,w,h,mode,param[,shape] joined by ';' (mode 1 fill with param 0, "
+                                                   "2 pixelate with an even cell 4 .. 64, 3 blur with a radius 1 .. 32; shape 0 or 1): the masks stay as they were", text), (NULL));
+        return;
+    }
+    GST_OBJECT_LOCK(s);
+    s->mask = c;
+    g_free(s->mask_text); s->mask_text = g_strdup(text ? text : "");
+    mask_forward(s);
+    GST_OBJECT_UNLOCK(s);
+}
+
 static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *ps) {
     GstMi355H264Enc *s = GST_MI355H264ENC(obj);
+    if (id == PROP_MASK) { mask_set_text(s, g_value_get_string(val)); return; }
     if (id == PROP_ROI) { roi_set_text(s, g_value_get_string(val)); return; }
     if (id == PROP_IMG_LOCATION) { image_set_location(s, g_value_get_string(val)); return; }
     if (id == PROP_LUT3D_LOCATION) { lut3d_set_location(s, g_value_get_string(val)); return; }
@@ -446,6 +472,7 @@ static void set_property(GObject *obj, guint id, const GValue *val, GParamSpec *
     case PROP_AUTO_MAX_GAIN: s->al.max_gain = (int)lround(1000.0 * g_value_get_double(val)); autolevel_forward(s); break;
     case PROP_LUT3D_STRENGTH: s->lut_strength = (int)lround(256.0 * g_value_get_double(val)); lut3d_forward(s); break;
     case PROP_ROI_BALANCE: s->roi.balance = g_value_get_int(val); roi_forward(s); break;
+    case PROP_MASK_COLOR: s->mask_color = g_value_get_uint(val); mask_forward(s); break;
     case PROP_DENOISE_LUMA: s->dn.luma = g_value_get_int(val); denoise_forward(s); break;
     case PROP_DENOISE_CHROMA: s->dn.chroma = g_value_get_int(val); denoise_forward(s); break;
     case PROP_DENOISE_MOTION: s->dn_motion = g_value_get_int(val); denoise_forward(s); break;
@@ -545,6 +572,8 @@ static void get_property(GObject *obj, guint id, GValue *val, GParamSpec *ps) {
     case PROP_LUT3D_STRENGTH: g_value_set_double(val, s->lut_strength / 256.0); break;
     case PROP_ROI: g_value_set_string(val, s->roi_text ? s->roi_text : ""); break;
     case PROP_ROI_BALANCE: g_value_set_int(val, s->roi.balance); break;
+    case PROP_MASK: g_value_set_string(val, s->mask_text ? s->mask_text : ""); break;
+    case PROP_MASK_COLOR: g_value_set_uint(val, s->mask_color); break;
     case PROP_DENOISE_LUMA: g_value_set_int(val, s->dn.luma); break;
     case PROP_DENOISE_CHROMA: g_value_set_int(val, s->dn.chroma); break;
     case PROP_DENOISE_MOTION: g_value_set_int(val, s->dn_motion); break;
@@ -969,6 +998,7 @@ static gboolean enc_set_format(GstVideoEncoder *ve, GstVideoCodecState *state) {
     autolevel_forward(s);                   /* ... nor the automatic levels and white balance */
     lut3d_forward(s);                       /* ... nor the 3D LUT */
     roi_forward(s);                         /* ... nor the region of interest */
+    mask_forward(s);                        /* ... nor the privacy masks */
     denoise_forward(s);                     /* ... nor the noise filter */
     dspatial_forward(s);                    /* ... nor the spatial noise filter */
     stabilize_forward(s);                   /* ... nor the stabiliser */
@@ -1319,6 +1349,7 @@ static void finalize(GObject *obj) {
     g_free(GST_MI355H264ENC(obj)->snap_location);
     g_free(GST_MI355H264ENC(obj)->lut_location);
     g_free(GST_MI355H264ENC(obj)->roi_text);
+    g_free(GST_MI355H264ENC(obj)->mask_text);
     g_free(GST_MI355H264ENC(obj)->lut_nodes);
     g_free(GST_MI355H264ENC(obj)->out_colorimetry);
     g_mutex_clear(&GST_MI355H264ENC(obj)->snap_mu); g_mutex_clear(&GST_MI355H264ENC(obj)->snap_enc_mu); g_cond_clear(&GST_MI355H264ENC(obj)->snap_cv);
@@ -1441,6 +1472,10 @@ static void gst_mi355h264enc_class_init(GstMi355H264EncClass *k) {
     g_object_class_install_property(g, PROP_ROI, g_param_spec_string("roi", "Regions of interest",
         "Up to 8 rectangles \"x,y,w,h,delta[,feather]\" joined by ';': luma samples of the coded picture, a QP offset -12 .. 12 (negative: finer, not 0) inside and the macroblocks "
         "0 .. 8 over which it ramps to 0 outside; takes effect with the next frame; empty: off", "", F));
+    g_object_class_install_property(g, PROP_MASK, g_param_spec_string("mask", "Privacy masks",
+        "Up to 8 regions \"x,y,w,h,mode,param[,shape]\" joined by ';', made unreadable on the GPU under logos and text: luma samples of the coded picture; mode 1 fill (param 0, "
+        "in mask-color), 2 pixelate (param: the even cell size 4 .. 64), 3 blur (param: the radius 1 .. 32); shape 0 rectangle, 1 ellipse; takes effect with the next frame; empty: off", "", F));
+    g_object_class_install_property(g, PROP_MASK_COLOR, g_param_spec_uint("mask-color", "Mask colour", "The colour of filled mask regions, packed 0xRRGGBB", 0, 0xFFFFFF, 0, F));
     g_object_class_install_property(g, PROP_ROI_BALANCE, g_param_spec_int("roi-balance", "Region-of-interest balance",
         "The bits the regions of interest take are taken from the rest of the picture: the cap of the QP offset the macroblocks outside every region get; 0: off", 0, 12, 0, F));
     g_object_class_install_property(g, PROP_DS_LUMA, g_param_spec_int("denoise-spatial-luma", "Spatial denoise luma", "spatial noise reduction on the GPU, edge-preserving, in front of the temporal filter: the luma noise amplitude in codes that is filtered fully -- with denoise-auto above 0 the upper bound of the measured strength; 0: off", 0, MI355ENC_DENOISE_SPATIAL_MAX, 0, F));
@@ -1486,6 +1521,7 @@ static void gst_mi355h264enc_init(GstMi355H264Enc *s) {
     mi355enc_autolevel_default(&s->al);
     s->lut_location = NULL; s->lut_nodes = NULL; s->lut_size = 0; s->lut_strength = 256;
     s->roi_text = NULL; mi355enc_roi_default(&s->roi);
+    s->mask_text = NULL; memset(&s->mask, 0, sizeof s->mask); s->mask_color = 0;
     s->dn_motion = 0;
     s->stab = 0; s->stab_range = 16; s->stab_leak = 16;
     s->warp_k1 = s->warp_k2 = s->warp_roll = s->warp_kh = s->warp_kv = 0.0; s->warp_zoom = 1.0; s->warp_filter = 1;

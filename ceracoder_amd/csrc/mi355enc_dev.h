@@ -162,6 +162,7 @@ typedef struct {
 
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
+#include "mask_host.h"
 /* launchers (k_*.hip); all asynchronous on `s`.  h_ctx: HOST copy of the context, passed to the kernel by value
  * (kernarg segment); d_ctx: device copy, for the kernels that are replayed from a hipGraph. */
 /* (the P-picture launchers cover the whole picture: mbw x h_ctx->mbh macroblocks) */
@@ -289,6 +290,11 @@ void k_launch_qp_chain(mb_info_t *d_mbi, int nmb, int slice_qp, int slice_mbs, h
  * picture -- aq what d_off holds (have_aq: aq_kernel ran in front on the same stream) or 0; t: nmb bytes the device can read (pinned host or device memory),
  * 4-byte aligned like d_off */
 void k_launch_roi_compose(const int8_t *t, int8_t *d_off, int nmb, int have_aq, hipStream_t s);
+/* Privacy masks (k_mask.hip; the rule: DESIGN.md section 32, mask_host.h) on NV12 surfaces of W x H at stride W whose visible part is vw x vh, in place: tab
+ * mask_resolve's for that visible size; res a surface of the same layout, pa and pb plane_bytes (at least W H 3 / 2) each, 16-byte aligned, all three the
+ * caller's and used by no other stream; parts: 1 the pixelate launch, 2 the blur launches, 4 the commit launch (which is also the fill) -- a picture is 7.
+ * *launches (may be null): how many were enqueued.  -1: arguments outside that, and nothing is launched */
+int k_launch_mask(uint8_t *y, uint8_t *uv, int W, int H, int vw, int vh, const mask_tab_t *tab, uint8_t *res, uint8_t *pa, uint8_t *pb, size_t plane_bytes, int parts, int *launches, hipStream_t s);
 /* Quality metrics of one picture (k_quality.hip; the rule: DESIGN.md section 12): NV12 source against NV12 reconstruction over the visible width x height.
  * d_acc: QUALITY_ACC_WORDS 64-bit words on the device, zero before the first launch (every launch leaves them zero again): QUALITY_SHARDS sets of five
  * accumulators, QUALITY_SHARD_STRIDE words (4 KB: another memory channel) apart, and the ticket; out: five words (a block of QUALITY_WORDS) -- SSE of Y, Cb, Cr,

@@ -41,6 +41,7 @@ STABILIZE_RANGE_MAX, STABILIZE_MARGIN_MAX = 32, 1024
 STAGE_WARP = 31  # the warp set last on slot 0's surfaces
 STAGE_AUTOLEVEL_MEASURE, STAGE_AUTOLEVEL_DECIDE, STAGE_AUTOLEVEL_APPLY = 32, 33, 34  # the launches of automatic levels and white balance
 WARP_BILINEAR, WARP_BICUBIC = 0, 1
+STAGE_MASK_CELLS, STAGE_MASK_BLUR = 38, 39  # the privacy masks set last on slot 0's surfaces: the pixelate and commit launches (the fill is the commit's) / the blur launches
 STAGE_DENOISE_SPATIAL, STAGE_DENOISE_SPATIAL_AUTO = 36, 37  # the spatial noise filter set last on slot 0's surfaces: manual / automatic, both planes
 DENOISE_SPATIAL_MAX = 32
 STAGE_LUT3D = 35  # the 3D colour LUT set last on slot 0's surfaces
@@ -97,6 +98,8 @@ EXPORTS = [
     "mi355enc_set_lut3d", "mi355enc_get_lut3d", "mi355enc_last_lut3d", "mi355enc_debug_lut3d_bytes", "mi355enc_lut3d_probe", "mi355enc_debug_lut3d_form",
     "mi355enc_roi_default", "mi355enc_roi_check", "mi355enc_roi_map", "mi355enc_roi_parse", "mi355enc_set_roi", "mi355enc_get_roi", "mi355enc_last_roi",
     "mi355enc_debug_roi_bytes", "mi355enc_roi_probe_set_map", "mi355enc_roi_probe_offsets",
+    "mi355enc_mask_check", "mi355enc_mask_parse", "mi355enc_mask_apply_host", "mi355enc_mask_ellipse", "mi355enc_mask_mean", "mi355enc_mask_colour",
+    "mi355enc_set_mask", "mi355enc_get_mask", "mi355enc_last_mask", "mi355enc_debug_mask_bytes", "mi355enc_mask_probe",
 ]
 
 
@@ -249,6 +252,21 @@ class Roi(C.Structure):
     def as_dict(self):
         n = max(0, min(8, int(self.n_rects)))
         return dict(rects=[tuple(int(getattr(self.rect[k], f)) for f, _ in RoiRect._fields_) for k in range(n)], balance=int(self.balance))
+
+
+class MaskRegion(C.Structure):
+    """mi355enc_mask_region_t: a rectangle in luma samples, mode 1 fill / 2 pixelate / 3 blur, param (0 / the cell size / the radius), shape 0 rectangle / 1
+    ellipse, and the fill colour 0xRRGGBB"""
+    _fields_ = [(n, C.c_int) for n in ("x", "y", "w", "h", "mode", "param", "shape")] + [("colour", C.c_uint)]
+
+
+class Mask(C.Structure):
+    """mi355enc_mask_t: up to eight regions"""
+    _fields_ = [("n", C.c_int), ("region", MaskRegion * 8)]
+
+    def as_list(self):
+        n = max(0, min(8, int(self.n)))
+        return [tuple(int(getattr(self.region[k], f)) for f, _ in MaskRegion._fields_) for k in range(n)]
 
 
 class Warp(C.Structure):
@@ -498,6 +516,18 @@ def load():
         L.mi355enc_debug_roi_bytes.argtypes = [vp]
         L.mi355enc_roi_probe_set_map.argtypes = [vp, vp]
         L.mi355enc_roi_probe_offsets.argtypes = [vp, vp, vp]
+        L.mi355enc_mask_check.argtypes = [C.POINTER(Mask)]
+        L.mi355enc_mask_parse.argtypes = [C.c_char_p, C.c_uint, C.POINTER(Mask)]
+        L.mi355enc_mask_apply_host.argtypes = [C.POINTER(Mask), vp, C.c_int, C.c_int, vp, vp]
+        L.mi355enc_mask_ellipse.argtypes = [C.c_int] * 4
+        L.mi355enc_mask_mean.argtypes = [C.c_int] * 2
+        L.mi355enc_mask_colour.argtypes = [C.c_uint, vp, vp]
+        L.mi355enc_set_mask.argtypes = [vp, C.POINTER(Mask)]
+        L.mi355enc_get_mask.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(Mask)]
+        L.mi355enc_last_mask.argtypes = [vp, C.POINTER(Mask), C.POINTER(C.c_uint)]
+        L.mi355enc_debug_mask_bytes.restype = C.c_size_t
+        L.mi355enc_debug_mask_bytes.argtypes = [vp]
+        L.mi355enc_mask_probe.argtypes = [vp, C.POINTER(Mask), vp, vp]
         L.mi355enc_set_quality_metrics.argtypes = [vp, C.c_int]
         L.mi355enc_last_quality.argtypes = [vp, C.POINTER(Quality)]
         L.mi355enc_quality_totals.argtypes = [vp, C.POINTER(Quality)]
@@ -894,6 +924,67 @@ def roi_parse(text, balance=0):
     if r:
         raise EncoderError("roi_parse: refused (%d)" % r)
     return c
+
+
+def mask(regions=()):
+    """A Mask from regions = [(x, y, w, h, mode, param[, shape[, colour]]), ...] (or a Mask as it is; None: none); nothing is checked here"""
+    if isinstance(regions, Mask):
+        return regions
+    regions = list(regions or ())
+    if len(regions) > 8:
+        raise EncoderError("mask: more than 8 regions")
+    c = Mask()
+    c.n = len(regions)
+    for k, r in enumerate(regions):
+        r = tuple(int(v) for v in r)
+        c.region[k] = MaskRegion(*(r + (0,) * (8 - len(r))))
+    return c
+
+
+def mask_check(cfg):
+    """mi355enc_mask_check (host only): 0, or the error code for a field outside its range"""
+    return load().mi355enc_mask_check(C.byref(mask(cfg)))
+
+
+def mask_parse(text, colour=0):
+    """mi355enc_mask_parse (host only): the element's string form "x,y,w,h,mode,param[,shape];..." -> a Mask whose regions take `colour`; EncoderError where refused"""
+    c = Mask()
+    r = load().mi355enc_mask_parse(text.encode() if isinstance(text, str) else text, int(colour), C.byref(c))
+    if r:
+        raise EncoderError("mask_parse: refused (%d)" % r)
+    return c
+
+
+def mask_apply_host(cfg, y, uv, coef):
+    """mi355enc_mask_apply_host (host only): the scalar rule on planes of the visible size, y (h, w) and uv (h / 2, w), with the ten words `coef` of
+    csc_coefficients -> new (y, uv)"""
+    y, uv = np.array(y, np.uint8, order="C"), np.array(uv, np.uint8, order="C")
+    h, w = y.shape
+    assert uv.shape == (h // 2, w)
+    k = np.ascontiguousarray(coef, np.int32)
+    r = load().mi355enc_mask_apply_host(C.byref(mask(cfg)), _p(k), w, h, _p(y), _p(uv))
+    if r:
+        raise EncoderError("mask_apply_host: refused (%d)" % r)
+    return y, uv
+
+
+def mask_ellipse(W2, H2, qx, qy):
+    """mi355enc_mask_ellipse (host only): rule 2 for the quad at region-local (qx, qy) of a W2 x H2 region: 1 inside, 0 outside, negative: refused"""
+    return load().mi355enc_mask_ellipse(int(W2), int(H2), int(qx), int(qy))
+
+
+def mask_mean(total, r):
+    """mi355enc_mask_mean (host only): rule 6's rounded mean of `total` over 2r + 1 samples, by the reciprocal the kernels use; negative: refused"""
+    return load().mi355enc_mask_mean(int(total), int(r))
+
+
+def mask_colour(colour, coef):
+    """mi355enc_mask_colour (host only): rule 4, 0xRRGGBB -> (Y, Cb, Cr) with the ten words of csc_coefficients"""
+    out, k = np.zeros(3, np.uint8), np.ascontiguousarray(coef, np.int32)
+    r = load().mi355enc_mask_colour(int(colour), _p(k), _p(out))
+    if r:
+        raise EncoderError("mask_colour: refused (%d)" % r)
+    return tuple(int(v) for v in out)
 
 
 def _lut3d_nodes(nodes):
@@ -1845,6 +1936,33 @@ class Encoder:
         assert y.shape == (self.mbh * 16, self.mbw * 16)
         self._chk(self.L.mi355enc_roi_probe_offsets(self.h, _p(y), _p(out)), "roi_probe_offsets")
         return out
+
+    def set_mask(self, cfg=None):
+        """Privacy masks from the next picture submitted on (any time, any thread, no GPU call): a mask() / Mask / list of regions; None or empty: off.
+        Pictures in flight keep theirs."""
+        self._chk(self.L.mi355enc_set_mask(self.h, None if cfg is None else C.byref(mask(cfg))), "set_mask")
+
+    def get_mask(self):
+        """the regions set last as a list of tuples, None when off"""
+        on, c = C.c_int(0), Mask()
+        self._chk(self.L.mi355enc_get_mask(self.h, C.byref(on), C.byref(c)), "get_mask")
+        return c.as_list() if on.value else None
+
+    def last_mask(self):
+        """(regions, generation) of the last collected picture; ([], 0) for a picture without"""
+        c, g = Mask(), C.c_uint(0)
+        self._chk(self.L.mi355enc_last_mask(self.h, C.byref(c), C.byref(g)), "last_mask")
+        return c.as_list(), int(g.value)
+
+    def debug_mask_bytes(self):
+        return int(self.L.mi355enc_debug_mask_bytes(self.h))
+
+    def mask_probe(self, cfg, y, uv):
+        """The launches of a masked picture on a host picture of the coded size (margins as given) -> new (y, uv); the handle's own setting plays no part"""
+        y, uv = np.array(y, np.uint8, order="C"), np.array(uv, np.uint8, order="C")
+        assert y.shape == (self.mbh * 16, self.mbw * 16) and uv.shape == (self.mbh * 8, self.mbw * 16)
+        self._chk(self.L.mi355enc_mask_probe(self.h, C.byref(mask(cfg)), _p(y), _p(uv)), "mask_probe")
+        return y, uv
 
     def set_warp_mesh(self, s, mesh):
         """... through the caller's own mesh, int32 (ny, nx, 2) for the coded visible size (s None: off)"""

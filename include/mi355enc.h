@@ -705,6 +705,64 @@ size_t mi355enc_debug_roi_bytes(const mi355enc_t *h); /* device bytes the featur
  * -- aq_kernel on the coded-size host luma src_y if aq_mode, then the compose launch -- into off_out[mbw mbh] */
 int mi355enc_roi_probe_set_map(mi355enc_t *h, const int8_t *map);
 int mi355enc_roi_probe_offsets(mi355enc_t *h, const uint8_t *src_y, int8_t *off_out);
+/* Privacy masks: up to eight regions of the coded picture are made unreadable -- filled, pixelated or blurred -- on the device, in front
+ * of the image layers and the text, so that everything that leaves the handle shows them: the access units, the "coded picture" stills and the quality
+ * metrics' source.  Off by default, and off nothing is allocated or launched.  All integers; / of non-negative operands.  A region is {x, y, w, h, mode, param,
+ * shape, colour} in luma samples of the visible coded picture (cfg.width x cfg.height: after scaling, geometry, orientation, stabilisation and warp; a letterbox
+ * border is just samples here).
+ *   1  even rectangle: x0 = x & ~1, x1 = (x + w + 1) & ~1, rows likewise (floors): W2 x H2 = (x1 - x0) x (y1 - y0), the region's own size.  Its intersection
+ *      with the visible picture is the clipped rectangle C.  A region with an empty C contributes nothing and is no error
+ *   2  membership, per 2 x 2 luma quad, so that luma and chroma agree.  Rectangle: every quad of C.  Ellipse: for the quad at region-local (qx, qy) let
+ *      dx = 2 (2 qx + 1) - W2 and dy = 2 (2 qy + 1) - H2; the quad is inside iff dx^2 H2^2 + dy^2 W2^2 <= W2^2 H2^2, in 64 bits -- the unclipped size, so an ellipse
+ *      half off the picture stays that ellipse
+ *   3  sources: every region computes from the picture as it stood before any region was applied; a sample takes the value of the lowest-indexed region whose
+ *      shape contains it; samples in no shape keep their bytes
+ *   4  fill: the colour is 0xRRGGBB, converted with the output's matrix and range by the ten words c of mi355enc_csc_coefficients:
+ *      Y = clip255((c0 R + c1 G + c2 B + (c9 << 16) + 32768) >> 16), Cb = clip255((c3 R + c4 G + c5 B + (128 << 16) + 32768) >> 16), Cr with c6 .. c8 (>> floors)
+ *   5  pixelate: param is the cell size c, even, 4 .. 64.  Cells tile from (x0, y0) of the even rectangle, so the grid moves with the region.  A cell's luma
+ *      value is (sum + n / 2) / n over its samples inside C, n that count (edge and clipped cells are smaller); chroma likewise, per component, over the cell's
+ *      c / 2 chroma footprint inside C.  Means are taken over the rectangle's cell even under an ellipse: only membership is elliptical
+ *   6  blur: param is the radius r, 1 .. 32.  On C a 1-D box mean runs horizontally, then vertically, then both again (H, V, H, V: a triangle response), rounded
+ *      to 8 bits after every pass: out = (sum of 2r + 1 samples + r) / (2r + 1), neighbour positions clamped to C -- nothing outside the clipped rectangle is
+ *      read, so a region's result depends only on its own contents.  Chroma: radius (r + 1) >> 1, per component, on C's chroma rectangle
+ *   7  margins: where a region changes the last visible column, row or corner, the coded-size margin beside it is stored as the replica of the new values
+ *      (chroma: last pair and row).  Margin samples are never read
+ * Host only, no device: */
+typedef struct {
+    int x, y, w, h;  /* luma samples; may reach beyond the picture (clipped).  |x|, |y| <= 16384, 1 <= w, h <= 16384 */
+    int mode;        /* 1 fill, 2 pixelate, 3 blur */
+    int param;       /* fill: 0; pixelate: the cell size, even, 4 .. 64; blur: the radius 1 .. 32 */
+    int shape;       /* 0 rectangle, 1 the ellipse inscribed in it */
+    unsigned colour; /* fill: 0xRRGGBB (at most 0xFFFFFF in every mode) */
+} mi355enc_mask_region_t;
+typedef struct {
+    int n;           /* 0 .. 8 */
+    mi355enc_mask_region_t region[8];
+} mi355enc_mask_t;
+int mi355enc_mask_check(const mi355enc_mask_t *cfg); /* MI355ENC_ERR_ARG for any field outside its range */
+/* the element's string form: regions "x,y,w,h,mode,param[,shape]" joined by ';', decimal integers, blanks around them allowed; an empty string: no region.
+ * Every region takes `colour`.  MI355ENC_ERR_ARG (cfg untouched) for anything else, a ninth region or a value mi355enc_mask_check refuses */
+int mi355enc_mask_parse(const char *text, unsigned colour, mi355enc_mask_t *cfg);
+/* rules 1 .. 6, the scalar way, in place on planes of exactly the visible size w x h (even, 2 .. 16384; y: h rows of w, uv: h / 2 rows of w, interleaved);
+ * coef: the ten words of mi355enc_csc_coefficients for rule 4.  MI355ENC_ERR_NOMEM where its own scratch cannot be had */
+int mi355enc_mask_apply_host(const mi355enc_mask_t *cfg, const int32_t coef[10], int w, int h, uint8_t *y, uint8_t *uv);
+/* parts of the rule on their own, for tests: rule 2 for the quad at region-local (qx, qy) of a W2 x H2 region (1 inside, 0 outside; MI355ENC_ERR_ARG for sizes
+ * that are not even and 2 .. 32770 or a quad outside 0 .. W2 / 2 - 1, 0 .. H2 / 2 - 1); rule 6's rounded mean of `sum` over 2r + 1 samples as the kernels and
+ * mi355enc_mask_apply_host compute it, by a reciprocal (MI355ENC_ERR_ARG for r outside 1 .. 32 or a sum outside 0 .. 255 (2r + 1)); rule 4 into ycc[3] */
+int mi355enc_mask_ellipse(int W2, int H2, int qx, int qy);
+int mi355enc_mask_mean(int sum, int r);
+int mi355enc_mask_colour(unsigned colour, const int32_t coef[10], uint8_t ycc[3]);
+/* On a handle.  set: at any time and from any thread, with pictures in flight, no GPU call; cfg NULL or n = 0: off.  The configuration is latched by every
+ * picture submitted from then on -- with frame-rate conversion by every output picture, each masked afresh -- and pictures already submitted keep theirs.  A
+ * refused configuration leaves the handle's as it was.  While a picture carries an active mask, mi355enc_submit_device never codes from the caller's memory */
+int mi355enc_set_mask(mi355enc_t *h, const mi355enc_mask_t *cfg);
+int mi355enc_get_mask(const mi355enc_t *h, int *on, mi355enc_mask_t *cfg); /* what was set last (either pointer may be NULL; cfg: n = 0 when off) */
+/* of the last collected picture: the configuration it carried (n = 0: none) and the count of sets it belongs to (0: none); MI355ENC_ERR_STATE before the first collect */
+int mi355enc_last_mask(mi355enc_t *h, mi355enc_mask_t *cfg, unsigned *generation);
+size_t mi355enc_debug_mask_bytes(const mi355enc_t *h); /* device bytes the feature holds (a result surface and two ping-pong planes): 0 until the first masked picture */
+/* parity tests: the launches of a masked picture, on a host picture of the coded size (y: 16 mbh rows of 16 mbw, uv: 8 mbh rows of 16 mbw interleaved, margins
+ * as the caller made them) with the handle's output matrix and range, in place; the handle's own setting plays no part */
+int mi355enc_mask_probe(mi355enc_t *h, const mi355enc_mask_t *cfg, uint8_t *y, uint8_t *uv);
 /* like mi355enc_submit, from host memory in `fmt`; planes[]/strides[]: as many entries as the format has planes */
 int mi355enc_submit_fmt(mi355enc_t *h, int fmt, const uint8_t *const planes[3], const int strides[3], int64_t pts, int force_idr);
 /* conversion stage alone (tests): writes the coded-size NV12 surfaces (16*mbw x 16*mbh luma, then interleaved chroma) */
