@@ -10,10 +10,11 @@ static void adjust_make(const mi355enc_t *h, const mi355enc_adjust_t *a, adjust_
     (void)mi355enc_adjust_tables(a, h->col_full, out->luma, out->chroma);
 }
 
-void adjust_latch(mi355enc_t *h, slot_t *s) {
+int adjust_latch(mi355enc_t *h, slot_t *s, bool) {
     std::lock_guard<std::mutex> g(h->adj_mu);
     if (h->adj_cur.parts) s->adj = h->adj_cur;
     else { s->adj.parts = 0; mi355enc_adjust_default(&s->adj.a); }
+    return MI355ENC_OK;
 }
 
 void adjust_retable(mi355enc_t *h) {

@@ -26,12 +26,13 @@ static int al_alloc(mi355enc_t *h) {
     return MI355ENC_OK;
 }
 
-void autolevel_latch(mi355enc_t *h, slot_t *s, bool own) {
+int autolevel_latch(mi355enc_t *h, slot_t *s, bool own) {
     { std::lock_guard<std::mutex> g(h->al_mu); s->al = h->al_cur; }
     s->al_on = own && al_active(&s->al);
     s->al_done = false;
     s->al_full = h->col_full;
     if (own && !s->al_on) h->al_primed = false; // (off: the next picture it is on for primes)
+    return MI355ENC_OK;
 }
 
 static void al_fields(const mi355enc_autolevel_t *a, int set[7]) {

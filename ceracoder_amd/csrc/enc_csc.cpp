@@ -84,13 +84,14 @@ void yuv_rect(const mi355enc_t *h, int rect[4]) {
     if (rect[3] == h->cfg.height) rect[3] = h->H;
 }
 
-int yuv_draw(mi355enc_t *h, slot_t *s, hipStream_t st) {
+int yuv_run(mi355enc_t *h, slot_t *s, hipStream_t st) {
     int rect[4];
     yuv_rect(h, rect);
     if (k_launch_yuv_convert(s->d_src_y, s->d_src_uv, h->W, h->H, rect, h->yuv_coef, st)) return MI355ENC_ERR_ARG;
     HIPCHK(hipGetLastError());
     return MI355ENC_OK;
 }
+int yuv_draw(mi355enc_t *h, slot_t *s, hipStream_t st) { return s->yuv_step ? yuv_run(h, s, st) : MI355ENC_OK; }
 
 extern "C" {
 
@@ -131,7 +132,7 @@ int mi355enc_stage_yuv_convert(mi355enc_t *h, uint8_t *y, uint8_t *uv) {
     slot_t *s = &h->slot[0];
     int r = stage_enter(h);
     if (!r) r = stage_in(h, s, y, uv);
-    if (!r) r = yuv_draw(h, s, h->stream);
+    if (!r) r = yuv_run(h, s, h->stream);
     return r ? r : stage_out(h, s, y, uv);
 }
 

@@ -12,10 +12,11 @@ static void denoise_make(const mi355enc_denoise_t *d, denoise_set_t *out) {
     (void)mi355enc_denoise_tables(d, out->tabs, out->tabs + 256, out->tabs + 512);
 }
 
-void denoise_latch(mi355enc_t *h, slot_t *s, bool tables) {
+int denoise_latch(mi355enc_t *h, slot_t *s, bool own) {
     std::lock_guard<std::mutex> g(h->dn_mu);
     s->dn.d = h->dn_cur.d; s->dn.parts = h->dn_cur.parts; s->dn.range = h->dn_cur.range;
-    if (tables && h->dn_cur.parts) memcpy(s->dn.tabs, h->dn_cur.tabs, sizeof s->dn.tabs);
+    if (own && h->dn_cur.parts) memcpy(s->dn.tabs, h->dn_cur.tabs, sizeof s->dn.tabs); // (the tables: only the slot the step runs on needs them)
+    return MI355ENC_OK;
 }
 
 // what a picture with the set `n` launches, the previous picture through the step having had the strengths `prev`: a plane whose strength was 0 there has no

@@ -42,12 +42,13 @@ static int ds_alloc(mi355enc_t *h, const mi355enc_denoise_spatial_t *a) {
     return MI355ENC_OK;
 }
 
-void dspatial_latch(mi355enc_t *h, slot_t *s, bool own) {
+int dspatial_latch(mi355enc_t *h, slot_t *s, bool own) {
     { std::lock_guard<std::mutex> g(h->ds_mu); s->ds = h->ds_cur; }
     s->ds_on = own && ds_active(&s->ds);
     s->ds_done = false;
     s->ds_full = h->col_full;
     if (own && !(s->ds_on && ds_auto(&s->ds))) h->ds_primed = false; // (off or manual: the next measured picture primes)
+    return MI355ENC_OK;
 }
 
 static void ds_fields(const mi355enc_denoise_spatial_t *a, int set[5]) {

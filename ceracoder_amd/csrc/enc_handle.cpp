@@ -341,18 +341,10 @@ void mi355enc_close(mi355enc_t *h) {
     scale_free(h);
     quality_free(h);
     snapshot_free(h);
-    image_free(h);
+    steps_free(h); // the input steps' buffers, and the heap tables their latches read (every thread has stopped, every stream is drained)
     rate_free(h);
     hdr_free(h);
-    adjust_free(h);
-    autolevel_free(h);
-    dspatial_free(h);
-    lut3d_close(h);
     roi_free(h);
-    mask_free(h);
-    denoise_free(h);
-    stab_free(h);
-    warp_close(h);
     for (int k = 0; k < NSET; k++) {
         if (h->d_surf[k]) (void)hipFree(h->d_surf[k]);
         for (int i = 0; i < 3; i++) if (h->d_imv[k][i]) (void)hipFree(h->d_imv[k][i]);

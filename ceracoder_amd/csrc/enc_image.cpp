@@ -90,7 +90,7 @@ static int image_blend(mi355enc_t *h, slot_t *s, image_t *g, int x, int y, int o
     return MI355ENC_OK;
 }
 
-int image_latch(mi355enc_t *h, slot_t *s) {
+int image_latch(mi355enc_t *h, slot_t *s, bool) {
     std::lock_guard<std::mutex> g(h->img_mu);
     bool active = false;
     for (int l = 0; l < MI355ENC_IMAGE_LAYERS; l++) {

@@ -2,12 +2,13 @@
 //
 // Every submit entry point is four steps ("The input path"):
 //   its own argument checks
-//   ingest_begin   the pipeline-full check (with frame-rate conversion: the rule's step, which says how many pictures the submit yields), the slot, the latches (text, image layers)
+//   ingest_begin   the pipeline-full check (with frame-rate conversion: the rule's step, which says how many pictures the submit yields), the slot, the steps' latches
 //   fill           its own way of filling the input target: copy | convert | decode | scale, ending in input_finish (the orientation launch)
-//   ingest_end     warp -> colour step -> spatial noise filter -> noise filter -> 3D LUT -> automatic levels -> picture controls -> [frame-rate conversion: mix / keep / repeat, per output picture] -> privacy masks -> image layers -> text -> upload event -> enqueue_picture
-//                  (enc_schedule.cpp) on the slot's own surfaces
-// The one exception is the in-place exit of mi355enc_submit_device.  A new step on the way in goes into ingest_end (one that works on the coded surfaces) or
-// in front of input_finish (one that works on the pre-orientation picture), never into a submit.
+//   ingest_end     the per-input steps' draws -> [frame-rate conversion: mix / keep / repeat, per output picture] -> the per-output steps' draws -> upload event ->
+//                  enqueue_picture (enc_schedule.cpp) on the slot's own surfaces
+// Which steps there are, and in which order, is k_steps below and nowhere else: latch, draw, the in-place exit's test, collect and close all walk it.
+// The one exception to the sequence is the in-place exit of mi355enc_submit_device.  A new step on the way in is a row of k_steps (one that works on the coded
+// surfaces) or goes in front of input_finish (one that works on the pre-orientation picture), never into a submit.
 // Also here: what the fills share -- a format's planes, the raw staging upload, the two-launch form, the staging helper threads -- and mi355enc_stage_csc.
 #include "enc_internal.hpp"
 
@@ -31,32 +32,74 @@ static int ingest_slot(mi355enc_t *h, slot_t **s, int64_t pts, int force_idr) {
     (*s)->yuv_step = h->yuv_on;
     return MI355ENC_OK;
 }
-// what the control thread set last becomes the picture's -- every picture's that the submit yields: layers and text are drawn afresh into each
+
+// ---- the input steps ("The input path"): one row per step, in chain order.  Null: the step has nothing of that kind.
+//   latch      what the control thread set last becomes the slot's; own: the slot the step is applied on (false: the picture only reports the setting)
+//   draw       the step on the slot's coded surfaces, behind everything enqueued on the stream so far; nothing where the slot latched none
+//   active     the slot's picture is changed by the step: it goes into the encoder's own surfaces, never through the in-place exit
+//   collected  mi355enc_collect: books what the picture carried as the last picture's
+//   free       mi355enc_close: everything of the step
+// PER_INPUT: applied once, to the slot the input goes into; the other pictures of the same submit (frame-rate conversion) latch with own == false.  PER_OUTPUT:
+// latched and drawn afresh for every picture the submit yields -- holds and blends keep their undrawn source.  The mix sits between the two phases.
+enum step_phase_t { PER_INPUT, PER_OUTPUT };
+struct step_t {
+    const char *name;
+    int (*latch)(mi355enc_t *, slot_t *, bool own);
+    int (*draw)(mi355enc_t *, slot_t *, hipStream_t);
+    bool (*active)(const slot_t *);
+    void (*collected)(mi355enc_t *, slot_t *);
+    void (*free)(mi355enc_t *);
+    step_phase_t phase;
+};
+static constexpr step_t k_steps[] = {
+    // the stabiliser: measured on the input, once; its launches sit in front of the scale launch (input_scale), and it runs only under a geometry, where the in-place exit is not taken anyway
+    {"stabiliser", stab_latch, nullptr, nullptr, stab_collected, stab_free, PER_INPUT},
+    // geometry first: colours, filter, controls, mix, layers and text follow, so layers and text stay straight
+    {"warp", warp_latch, warp_draw, [](const slot_t *s) { return s->warp_on; }, warp_collected, warp_close, PER_INPUT},
+    // the colour step: layers and text are drawn in the output's colours.  Latched with the slot (ingest_slot); an RGB submit clears it
+    {"colour step", nullptr, yuv_draw, [](const slot_t *s) { return s->yuv_step; }, nullptr, nullptr, PER_INPUT},
+    // the spatial noise filter and its estimate: measured on the camera's picture, filtered in front of the temporal filter, whose block measure then sees less noise
+    {"spatial filter", dspatial_latch, dspatial_draw, [](const slot_t *s) { return s->ds_on; }, dspatial_collected, dspatial_free, PER_INPUT},
+    // the temporal noise filter: in front of the picture controls, so that sharpening never amplifies noise; only the input's own slot launches and needs the tables
+    {"temporal filter", denoise_latch, denoise_draw, [](const slot_t *s) { return s->dn.parts != 0; }, denoise_collected, denoise_free, PER_INPUT},
+    // the 3D LUT: behind the noise filter, whose history stays in the camera's domain; automatic levels measure the graded picture
+    {"3D LUT", lut3d_latch, lut3d_draw, [](const slot_t *s) { return s->lut_on; }, lut3d_collected, lut3d_close, PER_INPUT},
+    // automatic levels and white balance: measured on the filtered picture, and the manual controls trim on top of it
+    {"automatic levels", autolevel_latch, autolevel_draw, [](const slot_t *s) { return s->al_on; }, autolevel_collected, autolevel_free, PER_INPUT},
+    // picture controls: behind the colour step, in front of the mix, the layers and the text
+    {"picture controls", adjust_latch, adjust_draw, [](const slot_t *s) { return s->adj.parts != 0; }, adjust_collected, adjust_free, PER_INPUT},
+    // the privacy masks first of what is drawn on top: logos and the stats line stay sharp on top of them
+    {"masks", mask_latch, mask_draw, [](const slot_t *s) { return s->mask_on; }, mask_collected, mask_free, PER_OUTPUT},
+    // image layers, in index order; collected lets go of the slot's images
+    {"layers", image_latch, image_draw, image_active, image_collected, image_free, PER_OUTPUT},
+    // the text on top of everything
+    {"text", overlay_latch, overlay_draw, [](const slot_t *s) { return s->ov_len != 0; }, overlay_collected, nullptr, PER_OUTPUT},
+};
+// one slot's latches; own: the slot the input goes into (every other picture of the submit is latched afresh by the per-output steps alone)
+static int latch_slot(mi355enc_t *h, slot_t *s, bool own) {
+    for (const step_t &st : k_steps)
+        if (st.latch) { int r = st.latch(h, s, own || st.phase == PER_OUTPUT); if (r) return r; }
+    return MI355ENC_OK;
+}
+static int draw_steps(mi355enc_t *h, slot_t *s, hipStream_t up, step_phase_t phase) {
+    for (const step_t &st : k_steps)
+        if (st.draw && st.phase == phase) {
+            int r = st.draw(h, s, up);
+            if (r) { fprintf(stderr, "mi355enc: input step '%s' failed: %d\n", st.name, r); return r; }
+        }
+    return MI355ENC_OK;
+}
+bool steps_active(const slot_t *s) {
+    for (const step_t &st : k_steps) if (st.active && st.active(s)) return true;
+    return false;
+}
+void steps_collected(mi355enc_t *h, slot_t *s) { for (const step_t &st : k_steps) if (st.collected) st.collected(h, s); }
+void steps_free(mi355enc_t *h) { for (const step_t &st : k_steps) if (st.free) st.free(h); }
+
+// what the control thread set last becomes the picture's -- every picture's that the submit yields: the rate conversion's earlier ticks first, then the input's own slot
 static int ingest_latch(mi355enc_t *h, slot_t *s) {
-    for (int i = 0; h->rate.mode && i < h->rate_n - 1; i++) {
-        slot_t *t = &h->slot[(h->head + i) % NSLOT];
-        overlay_latch(h, t);
-        adjust_latch(h, t); // (what the tick's picture reports; the adjustment itself is applied to the input, once)
-        autolevel_latch(h, t, false); // (likewise: the input is measured and corrected, once)
-        (void)lut3d_latch(h, t, false); // (likewise: the input is graded, once)
-        dspatial_latch(h, t, false); // (likewise: the input is measured and filtered, once)
-        denoise_latch(h, t, false); // (likewise; only the input's own slot launches and needs the tables)
-        (void)stab_latch(h, t, false); // (likewise: the shake is measured on the input, once)
-        (void)warp_latch(h, t, false); // (likewise: the input is warped, once)
-        int r = mask_latch(h, t); // (every output picture is masked afresh, with its own latch: holds and blends keep their unmasked source)
-        if (!r) r = image_latch(h, t);
-        if (r) return r;
-    }
-    overlay_latch(h, s);
-    adjust_latch(h, s);
-    autolevel_latch(h, s, true);
-    { int r = lut3d_latch(h, s, true); if (r) return r; }
-    dspatial_latch(h, s, true);
-    denoise_latch(h, s, true);
-    { int r = stab_latch(h, s, true); if (r) return r; }
-    { int r = warp_latch(h, s, true); if (r) return r; }
-    { int r = mask_latch(h, s); if (r) return r; }
-    return image_latch(h, s);
+    for (int i = 0; h->rate.mode && i < h->rate_n - 1; i++) { int r = latch_slot(h, &h->slot[(h->head + i) % NSLOT], false); if (r) return r; }
+    return latch_slot(h, s, true);
 }
 // (apart only for mi355enc_submit_jpeg, which decodes into the slot between the two: after the state check -- with the pipeline full the slot's buffers
 // belong to a picture in flight -- and before anything is latched)
@@ -64,11 +107,9 @@ static int ingest_begin(mi355enc_t *h, slot_t **s, int64_t pts, int force_idr) {
     int r = ingest_slot(h, s, pts, force_idr);
     return r ? r : ingest_latch(h, *s);
 }
-// everything that is drawn into a picture on top of its samples, in this order, then the schedule
+// everything that is drawn into a picture on top of its samples (the per-output steps), then the schedule
 static int draw_and_enqueue(mi355enc_t *h, slot_t *s, hipStream_t up, int64_t pts, int force_idr) {
-    int r = mask_draw(h, s, up); // the privacy masks first: logos and the stats line stay sharp on top of them
-    if (!r) r = image_draw(h, s, up);
-    if (!r) r = overlay_draw(h, s, up);
+    int r = draw_steps(h, s, up, PER_OUTPUT);
     if (!r) r = upload_done(h, s);
     return r ? r : enqueue_picture(h, s, s->d_src_y, s->d_src_uv, h->W, pts, force_idr);
 }
@@ -93,17 +134,11 @@ static int ingest_end_rate(mi355enc_t *h, slot_t *s, hipStream_t up, int force_i
     if (!r) rate_commit(h, force_idr);
     return r;
 }
-// the slot's surfaces hold the oriented picture: everything that is drawn into it, in this order, then the schedule
+// the slot's surfaces hold the oriented picture: the per-input steps, the mix or nothing, then the per-output steps and the schedule
 static int ingest_end(mi355enc_t *h, slot_t *s, hipStream_t up, int64_t pts, int force_idr) {
-    int r = warp_draw(h, s, up); // geometry first: colours, filter, controls, mix, layers and text follow, so layers and text stay straight
-    if (!r && s->yuv_step) r = yuv_draw(h, s, up); // the colour step: layers and text are drawn in the output's colours
-    if (!r) r = dspatial_draw(h, s, up); // the spatial noise filter and its estimate: measured on the camera's picture, filtered in front of the temporal filter, whose block measure then sees less noise
-    if (!r) r = denoise_draw(h, s, up); // the temporal noise filter: in front of the picture controls, so that sharpening never amplifies noise
-    if (!r) r = lut3d_draw(h, s, up); // the 3D LUT: behind the noise filter, whose history stays in the camera's domain; automatic levels measure the graded picture
-    if (!r) r = autolevel_draw(h, s, up); // automatic levels and white balance: measured on the filtered picture, and the manual controls trim on top of it
-    if (!r) r = adjust_draw(h, s, up); // picture controls: behind the colour step, in front of the mix, the layers and the text
+    int r = draw_steps(h, s, up, PER_INPUT);
     if (r) return r;
-    if (h->rate.mode) return ingest_end_rate(h, s, up, force_idr); // (the mix sits here: between the colour step and the layers)
+    if (h->rate.mode) return ingest_end_rate(h, s, up, force_idr); // (the mix sits here: between the picture controls and the masks)
     r = draw_and_enqueue(h, s, up, pts, force_idr);
     if (!r) h->last_count = 1;
     return r;
@@ -363,8 +398,8 @@ int mi355enc_submit_device(mi355enc_t *h, const void *d_y, int y_stride, const v
         r = input_finish(h, s, up, (const uint8_t *)d_y, y_stride, (const uint8_t *)d_uv, uv_stride);
     } else {
         const int w = h->cfg.width, ht = h->cfg.height;
-        // in place -- unless the frame rate is converted (the picture may be kept, repeated or mixed), the samples are to be warped, converted, filtered, graded, adjusted or masked, a text drawn or an image blended in: that goes into the encoder's own surfaces, never into the caller's planes
-        const bool direct = !h->rate.mode && !s->warp_on && !s->yuv_step && !s->ds_on && !s->dn.parts && !s->lut_on && !s->al_on && !s->adj.parts && !s->mask_on && !s->ov_len && !image_active(s) && w == h->W && y_stride == uv_stride && (y_stride & 15) == 0 && (((uintptr_t)d_y | (uintptr_t)d_uv) & 15) == 0;
+        // in place -- unless the frame rate is converted (the picture may be kept, repeated or mixed) or a step changes the samples (steps_active): that goes into the encoder's own surfaces, never into the caller's planes
+        const bool direct = !h->rate.mode && !steps_active(s) && w == h->W && y_stride == uv_stride && (y_stride & 15) == 0 && (((uintptr_t)d_y | (uintptr_t)d_uv) & 15) == 0;
         if (direct) return enqueue_picture(h, s, (const uint8_t *)d_y, (const uint8_t *)d_uv, y_stride, pts, force_idr);
         HIPCHK(hipMemcpy2DAsync(s->d_src_y, h->W, d_y, y_stride, w, ht, hipMemcpyDeviceToDevice, up));
         HIPCHK(hipMemcpy2DAsync(s->d_src_uv, h->W, d_uv, uv_stride, w, ht / 2, hipMemcpyDeviceToDevice, up));

@@ -1,7 +1,8 @@
 // enc_internal.hpp -- what the translation units of the C-ABI shim share (not part of the ABI):
 // the handle, the per-picture slot, and the helpers used by more than one of
 //   enc_handle.cpp    open / close / setters / statistics / fetch
-//   enc_input.cpp     the input path: submit*, from the caller's picture to the slot's source surfaces (upload, conversion, the sequence around them)
+//   enc_input.cpp     the input path: submit*, from the caller's picture to the slot's source surfaces (upload, conversion, the sequence around them), and the
+//                     table of the input steps (k_steps): the one list of what is latched, drawn, collected and freed, in chain order
 //   enc_schedule.cpp  the picture pipeline: the stream schedule of one picture, the entropy worker, recovery, collect
 //   enc_plan.hpp      ... and that schedule's decisions as a value: plan_picture(), and the launches that follow from a plan: plan_launches(); plain C++ (included here)
 //   enc_sync.*        the words kernels wait on and the host's totals of them, under one owner: dev_words_t (mi355enc::words)
@@ -482,15 +483,30 @@ int quality_enqueue(mi355enc_t *h, slot_t *s, const uint8_t *src_y, const uint8_
 int quality_collect(mi355enc_t *h, slot_t *s); // waits for the slot's metrics, books them as the last picture's and into the totals
 // one launch on the handle's main stream with the block of the stage entry points, waited for
 int quality_run(mi355enc_t *h, const uint8_t *src_y, const uint8_t *src_uv, int src_stride, const uint8_t *rec_y, const uint8_t *rec_uv, mi355enc_quality_t *q);
-// enc_overlay.cpp
-void overlay_latch(mi355enc_t *h, slot_t *s);                 // the text and style set last become the slot's (the first thing a submit does)
-int overlay_draw(mi355enc_t *h, slot_t *s, hipStream_t st);   // the slot's text into its source surfaces, behind everything enqueued on st so far; nothing with no text
+// The input steps' hooks, as the rows of k_steps (enc_input.cpp) name them, in chain order.  One signature per kind, whatever the step:
+//   latch      the value set last becomes the slot's; own: the slot the step is applied on, which also takes a new table or mesh (a per-output step is always
+//              called with true).  stab_latch refuses there: ERR_STATE without a geometry, ERR_ARG for an input below 4 range; image_latch: ERR_ARG for an
+//              active layer and a matrix RGB cannot be converted with; every other answer but OK is an allocation's
+//   draw       the slot's step on its coded surfaces, behind everything enqueued on st so far; nothing where the slot latched none
+//   collected  collect(): books what the picture carried as the last picture's (image_collected lets go of the slot's images)
+//   free       close(): everything of the step (lut3d_close, warp_close: the heap table the latch reads too)
+int stab_latch(mi355enc_t *h, slot_t *s, bool own); void stab_collected(mi355enc_t *h, slot_t *s); void stab_free(mi355enc_t *h);
+int warp_latch(mi355enc_t *h, slot_t *s, bool own); int warp_draw(mi355enc_t *h, slot_t *s, hipStream_t st); void warp_collected(mi355enc_t *h, slot_t *s); void warp_close(mi355enc_t *h);
+int yuv_draw(mi355enc_t *h, slot_t *s, hipStream_t st);
+int dspatial_latch(mi355enc_t *h, slot_t *s, bool own); int dspatial_draw(mi355enc_t *h, slot_t *s, hipStream_t st); void dspatial_collected(mi355enc_t *h, slot_t *s); void dspatial_free(mi355enc_t *h);
+int denoise_latch(mi355enc_t *h, slot_t *s, bool own); int denoise_draw(mi355enc_t *h, slot_t *s, hipStream_t st); void denoise_collected(mi355enc_t *h, slot_t *s); void denoise_free(mi355enc_t *h);
+int lut3d_latch(mi355enc_t *h, slot_t *s, bool own); int lut3d_draw(mi355enc_t *h, slot_t *s, hipStream_t st); void lut3d_collected(mi355enc_t *h, slot_t *s); void lut3d_close(mi355enc_t *h);
+int autolevel_latch(mi355enc_t *h, slot_t *s, bool own); int autolevel_draw(mi355enc_t *h, slot_t *s, hipStream_t st); void autolevel_collected(mi355enc_t *h, slot_t *s); void autolevel_free(mi355enc_t *h);
+int adjust_latch(mi355enc_t *h, slot_t *s, bool own); int adjust_draw(mi355enc_t *h, slot_t *s, hipStream_t st); void adjust_collected(mi355enc_t *h, slot_t *s); void adjust_free(mi355enc_t *h);
+int mask_latch(mi355enc_t *h, slot_t *s, bool own); int mask_draw(mi355enc_t *h, slot_t *s, hipStream_t st); void mask_collected(mi355enc_t *h, slot_t *s); void mask_free(mi355enc_t *h);
+int image_latch(mi355enc_t *h, slot_t *s, bool own); int image_draw(mi355enc_t *h, slot_t *s, hipStream_t st); void image_collected(mi355enc_t *h, slot_t *s); void image_free(mi355enc_t *h);
+int overlay_latch(mi355enc_t *h, slot_t *s, bool own); int overlay_draw(mi355enc_t *h, slot_t *s, hipStream_t st);
+#pragma GCC visibility push(hidden)
+void overlay_collected(mi355enc_t *h, slot_t *s);
+int yuv_run(mi355enc_t *h, slot_t *s, hipStream_t st); // the colour step's launch whatever the slot latched: the stage entry points'
+#pragma GCC visibility pop
 // enc_image.cpp
-int image_latch(mi355enc_t *h, slot_t *s);                  // the layers set last become the slot's (beside overlay_latch); ERR_ARG: an active layer and a matrix RGB cannot be converted with
 static inline bool image_active(const slot_t *s) { for (int l = 0; l < MI355ENC_IMAGE_LAYERS; l++) if (s->img[l] && s->img_op[l]) return true; return false; }
-int image_draw(mi355enc_t *h, slot_t *s, hipStream_t st);   // the slot's layers into its source surfaces in index order, behind everything enqueued on st so far (an image not yet on the device goes there first); nothing with no layer
-void image_collected(mi355enc_t *h, slot_t *s);             // collect(): books what the picture carried as the last picture's and lets go of the slot's images
-void image_free(mi355enc_t *h);                             // close(): everything
 int image_time_prepare(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // mi355enc_time_stage 15: layer 0's image on the device, the launch's arguments (x->img) at its current place; ERR_STATE without one
 // enc_scale.cpp
 // the one place the input geometry of a handle is decided (both setters end here): validates, then rebuilds tables, sizes, SAR and staging buffers; ERR_ARG leaves the handle as it was
@@ -524,6 +540,10 @@ int input_nv12(mi355enc_t *h, slot_t *s, nv12_pic_t *c);
 int scale_nv12(mi355enc_t *h, slot_t *s, const nv12_pic_t *c, const in_target_t *t, const scale_plan_t *pl, hipStream_t up);
 // the planes' layout at rows of 16 n bytes, one behind the other from d on (a slot's raw staging buffer): where each lies and its stride -> the number of planes
 int raw_layout(int fmt, int w, int h, const uint8_t *d, const uint8_t *p[3], int st[3], fmt_plane_t pl[3]);
+// the walks over k_steps that other files need: some step changes the slot's picture (the in-place exit's test), collect()'s bookings, close()'s frees
+bool steps_active(const slot_t *s);
+void steps_collected(mi355enc_t *h, slot_t *s);
+void steps_free(mi355enc_t *h);
 #pragma GCC visibility pop
 // enc_jpeg.cpp
 int jpeg_alloc(mi355enc_t *h, slot_t *s);  // the slot's coefficient buffers (idempotent)
@@ -543,61 +563,35 @@ void snapshot_free(mi355enc_t *h);
 // enc_csc.cpp
 void csc_resolve(mi355enc_t *h); // fills csc_coef / csc_ok from col_mat, col_full and the coded size, and what the colour step follows from them
 static inline bool fmt_is_rgb(int fmt) { return fmt >= MI355ENC_FMT_BGRX && fmt <= MI355ENC_FMT_RGB; }
-// the colour step on the slot's coded surfaces, behind everything enqueued on st so far: the picture part (with a geometry: the oriented destination rectangle) is
-// converted in place, the border keeps its bytes
-int yuv_draw(mi355enc_t *h, slot_t *s, hipStream_t st);
+// (the colour step, yuv_draw / yuv_run: the picture part -- with a geometry the oriented destination rectangle -- is converted in place, the border keeps its bytes)
 void yuv_rect(const mi355enc_t *h, int rect[4]); // that picture part: x0, x1, y0, y1 in the coded surfaces (reaching their edge where it reaches the visible picture's)
 // enc_adjust.cpp (picture controls)
-void adjust_latch(mi355enc_t *h, slot_t *s);                 // the value set last becomes the slot's (beside overlay_latch)
 void adjust_retable(mi355enc_t *h);                          // mi355enc_set_colorimetry: the current value's tables again, for the new output range
-int adjust_draw(mi355enc_t *h, slot_t *s, hipStream_t st);   // the slot's adjustment on its coded surfaces, behind everything enqueued on st so far; nothing with none
-void adjust_collected(mi355enc_t *h, slot_t *s);             // collect(): books what the picture carried as the last picture's
-void adjust_free(mi355enc_t *h);
 bool adjust_time_ready(mi355enc_t *h, int stage);            // mi355enc_time_stage 23 / 24: the value set last is active and of that form (24: the stencil form)
 int adjust_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // ... and its launches on the main stream
 // enc_denoise.cpp (temporal noise reduction)
-void denoise_latch(mi355enc_t *h, slot_t *s, bool tables);   // the value set last becomes the slot's (beside adjust_latch); tables: with its tables (the slot the step runs on)
-int denoise_draw(mi355enc_t *h, slot_t *s, hipStream_t st);  // the slot's filter on its coded surfaces and the handle's history, behind everything enqueued on st so far; nothing with none
-void denoise_collected(mi355enc_t *h, slot_t *s);            // collect(): books what the picture carried as the last picture's
-void denoise_free(mi355enc_t *h);
 bool denoise_time_ready(mi355enc_t *h, int stage);           // mi355enc_time_stage 25 .. 28: the value set last is active (27 / 28: with a range above 0)
 int denoise_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // ... and its launch on the main stream: 25 filtering in place (priming where the history is not valid), 26 priming, 27 the search alone, 28 search and compensated filter
 void denoise_time_done(mi355enc_t *h);                       // ... behind the timed launches: the history they left is no stream's, the next picture primes
 // enc_stab.cpp (electronic image stabilisation)
-int stab_latch(mi355enc_t *h, slot_t *s, bool own);          // the value set last becomes the slot's (beside denoise_latch); own: the slot the input goes into -- checked there: ERR_STATE without a geometry, ERR_ARG for an input below 4 range
 // The one place a scale / geometry launch of a picture is enqueued (every submit path and mi355enc_stage_scale end here): with the slot stabilised, the estimate
 // (clear, projection launch, match launch, the record's copy to pinned memory) in front of it on the same stream, and the launch reads the offset the match
 // launch wrote.  An MI355ENC_* code
 int input_scale(mi355enc_t *h, slot_t *s, int fmt, const uint8_t *p0, const uint8_t *p1, const uint8_t *p2, int s0, int s1, int s2, const in_target_t *t, const scale_plan_t *pl, hipStream_t up);
-void stab_collected(mi355enc_t *h, slot_t *s);               // collect(): books what the picture carried as the last picture's
-void stab_free(mi355enc_t *h);
 bool stab_time_ready(mi355enc_t *h, int stage);              // mi355enc_time_stage 29 / 30: the value set last is on, and the handle has a geometry of a size it takes
 int stab_time_prepare(mi355enc_t *h, slot_t *s, ts_ctx_t *x);
 int stab_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // 29 the clear and the projection launch on the raw staging buffer, 30 the match launch
 void stab_time_done(mi355enc_t *h);                          // ... behind the timed launches: the next picture primes
 // enc_autolevel.cpp (automatic levels and white balance)
-void autolevel_latch(mi355enc_t *h, slot_t *s, bool own);    // the value set last becomes the slot's (beside adjust_latch); own: the slot the input goes into (off there: the next picture it is on for primes)
-int autolevel_draw(mi355enc_t *h, slot_t *s, hipStream_t st); // measure, decide, apply on the slot's coded surfaces and the record's copy to pinned memory, behind everything enqueued on st so far; nothing with none
-void autolevel_collected(mi355enc_t *h, slot_t *s);          // collect(): books what the picture carried as the last picture's
-void autolevel_free(mi355enc_t *h);
 bool autolevel_time_ready(mi355enc_t *h, int stage);         // mi355enc_time_stage 32 .. 34: the value set last is on
 int autolevel_time_prepare(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // the block, and a measure and a (priming) decide launch on slot 0's surfaces
 int autolevel_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // 32 measure, 33 decide, 34 apply
 void autolevel_time_done(mi355enc_t *h);                     // ... behind the timed launches: the next picture primes
 // enc_dspatial.cpp (the spatial noise filter and its noise estimate)
-void dspatial_latch(mi355enc_t *h, slot_t *s, bool own);     // the value set last becomes the slot's (beside denoise_latch); own: the slot the input goes into (not automatic there: the next measured picture primes)
-int dspatial_draw(mi355enc_t *h, slot_t *s, hipStream_t st); // measure, decide, the filter launches on the slot's coded surfaces and the record's copy to pinned memory, behind everything enqueued on st so far; nothing with none
-void dspatial_collected(mi355enc_t *h, slot_t *s);           // collect(): books what the picture carried as the last picture's
-void dspatial_free(mi355enc_t *h);
 bool dspatial_time_ready(mi355enc_t *h, int stage);          // mi355enc_time_stage 36 / 37: the value set last is on and manual / automatic
 int dspatial_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // 36 the filter launches, 37 measure, decide and the filter launches
 void dspatial_time_done(mi355enc_t *h);                      // ... behind the timed launches: the next picture primes
 // enc_lut3d.cpp (3D colour LUT)
-int lut3d_latch(mi355enc_t *h, slot_t *s, bool own);         // the value set last becomes the slot's (beside autolevel_latch); own: the slot the input goes into, which also takes the table where it is a new one
-int lut3d_draw(mi355enc_t *h, slot_t *s, hipStream_t st);    // the slot's LUT on its coded surfaces, behind everything enqueued on st so far (a new table travels in front of it); nothing with none
-void lut3d_collected(mi355enc_t *h, slot_t *s);              // collect(): books what the picture carried as the last picture's
-void lut3d_free(mi355enc_t *h);
-void lut3d_close(mi355enc_t *h);
 bool lut3d_time_ready(mi355enc_t *h, int stage);             // mi355enc_time_stage 35: the value set last is on
 int lut3d_time_prepare(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // the table set last onto the device
 int lut3d_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x);
@@ -609,18 +603,10 @@ int roi_stage_ctx(mi355enc_t *h, frame_ctx_t *c);            // a single-stage c
 void roi_collected(mi355enc_t *h, slot_t *s);                // collect(): books what the picture carried as the last picture's
 void roi_free(mi355enc_t *h);
 // enc_mask.cpp (privacy masks)
-int mask_latch(mi355enc_t *h, slot_t *s);                    // the value set last becomes the slot's: every picture that is drawn latches its own (one with a region on the picture: the surfaces exist from here on)
-int mask_draw(mi355enc_t *h, slot_t *s, hipStream_t st);     // the slot's masks on its coded surfaces, behind everything enqueued on st so far and in front of layers and text; nothing with none
-void mask_collected(mi355enc_t *h, slot_t *s);               // collect(): books what the picture carried as the last picture's
-void mask_free(mi355enc_t *h);
 bool mask_time_ready(mi355enc_t *h, int stage);              // mi355enc_time_stage 38 / 39: the value set last holds a fill or pixelate / a blur region
 int mask_time_prepare(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // the surfaces, and the value set last as slot 0's
 int mask_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x); // 38 the pixelate and commit launches, 39 the blur launches
 // enc_warp.cpp (lens, roll and keystone correction)
-int warp_latch(mi355enc_t *h, slot_t *s, bool own);          // the value set last becomes the slot's (beside stab_latch); own: the slot the input goes into, which also takes the mesh where it is a new one
-int warp_draw(mi355enc_t *h, slot_t *s, hipStream_t st);     // the slot's warp on its coded surfaces, behind everything enqueued on st so far (a new mesh travels in front of it); nothing with none
-void warp_collected(mi355enc_t *h, slot_t *s);               // collect(): books the generation the picture carried as the last picture's
-void warp_close(mi355enc_t *h);
 bool warp_time_ready(mi355enc_t *h, int stage);              // mi355enc_time_stage 31: the warp is on
 int warp_time_prepare(mi355enc_t *h, slot_t *s, ts_ctx_t *x);
 int warp_time_launch(mi355enc_t *h, slot_t *s, ts_ctx_t *x);

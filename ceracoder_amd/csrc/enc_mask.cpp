@@ -34,7 +34,7 @@ static bool mask_any(const mi355enc_t *h, const mi355enc_mask_t *cfg) { // some 
 
 // The value set last becomes the slot's: every picture that is drawn latches its own (with frame-rate conversion every output picture).  A configuration none
 // of whose regions reaches the picture is carried and reported, and launches nothing.
-int mask_latch(mi355enc_t *h, slot_t *s) {
+int mask_latch(mi355enc_t *h, slot_t *s, bool) {
     s->mask_on = false; s->mask_gen = 0; s->mask.n = 0;
     if (!h->mask_set) return MI355ENC_OK; // (only ever set to true, under the lock: a handle that never called the setter takes no lock per picture)
     {

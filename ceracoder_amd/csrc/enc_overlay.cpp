@@ -37,10 +37,11 @@ static bool overlay_layout(const char *text, int len, const mi355enc_overlay_sty
     return true;
 }
 
-void overlay_latch(mi355enc_t *h, slot_t *s) {
+int overlay_latch(mi355enc_t *h, slot_t *s, bool) {
     std::lock_guard<std::mutex> g(h->ov_mu);
     s->ov_len = h->ov_len;
     if (h->ov_len) { memcpy(s->ov_text, h->ov_text, (size_t)h->ov_len); s->ov_style = h->ov_style; }
+    return MI355ENC_OK;
 }
 
 // layout and launch: `len` bytes of text into the slot's source surfaces; nothing with no text, or with none of its box visible
@@ -53,6 +54,7 @@ static int overlay_run(mi355enc_t *h, slot_t *s, const char *text, int len, cons
     return MI355ENC_OK;
 }
 int overlay_draw(mi355enc_t *h, slot_t *s, hipStream_t st) { return overlay_run(h, s, s->ov_text, s->ov_len, s->ov_style, st); }
+void overlay_collected(mi355enc_t *h, slot_t *s) { h->ov_last_have = 1; h->ov_last_len = s->ov_len; if (s->ov_len) memcpy(h->ov_last, s->ov_text, (size_t)s->ov_len); }
 
 extern "C" {
 

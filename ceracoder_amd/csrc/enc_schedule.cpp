@@ -538,17 +538,8 @@ int mi355enc_collect(mi355enc_t *h, uint8_t *out, size_t out_cap, size_t *out_le
     h->st.frames++; h->st.idr_frames += s->is_idr; h->st.bytes += m;
     h->st.last_qp = (uint32_t)s->qp; h->st.last_drop = (uint32_t)s->drop; h->n_skip_pictures += s->all_skip; h->st.last_bytes = (uint32_t)m; h->st.target_bps = h->want_bps.load();
     h->last_slot = s; h->last_collected_rec = s->rec_index;
-    h->ov_last_have = 1; h->ov_last_len = s->ov_len; if (s->ov_len) memcpy(h->ov_last, s->ov_text, (size_t)s->ov_len);
-    image_collected(h, s);
-    adjust_collected(h, s);
-    autolevel_collected(h, s);
-    dspatial_collected(h, s);
-    lut3d_collected(h, s);
+    steps_collected(h, s); // what the picture carried through the input steps becomes the last picture's (each step books its own fields; the layers let go of their images)
     roi_collected(h, s);
-    mask_collected(h, s);
-    denoise_collected(h, s);
-    stab_collected(h, s);
-    warp_collected(h, s);
     h->tail = (h->tail + 1) % NSLOT; h->pending--;
     return MI355ENC_OK;
 }

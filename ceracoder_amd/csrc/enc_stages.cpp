@@ -108,7 +108,7 @@ static int ts_scale(mi355enc_t *h, slot_t *s, ts_ctx_t *x) {
     return k_launch_scale(MI355ENC_FMT_NV12, s->d_raw, s->d_raw + (size_t)ds * h->in_h, nullptr, ds, ds, 0, t.y, t.uv, t.W, t.H, x->scale, h->stream) ? MI355ENC_ERR_ARG : 0;
 }
 static int ts_image(mi355enc_t *h, slot_t *, ts_ctx_t *x) { k_launch_image_blend(&x->img, h->stream); return 0; }
-static int ts_yuv(mi355enc_t *h, slot_t *s, ts_ctx_t *) { return yuv_draw(h, s, h->stream); }            // the colour step, in place on slot 0's surfaces (whatever they hold)
+static int ts_yuv(mi355enc_t *h, slot_t *s, ts_ctx_t *) { return yuv_run(h, s, h->stream); }            // the colour step, in place on slot 0's surfaces (whatever they hold)
 static int ts_rate(mi355enc_t *h, slot_t *s, ts_ctx_t *) { return rate_mix(h, s, s, 128, true, h->stream); } // the mix of the keep buffer and slot 0's surfaces, in place as the encoder runs it
 static constexpr ts_row_t k_ts[] = {
     // stage                ready               prepare                 launch                 done               needs_raw

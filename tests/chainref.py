@@ -209,6 +209,7 @@ PICTURES = {
     "B": dict(size=(42, 26), geom=None, method=0),  # a partly visible 8 x 8 block row (26 & 7 = 2); the padding pass behind the plain NV12 copies
     "C": dict(size=(70, 50), geom=((8, 8, 80, 48), (12, 8, 58, 42), (70, 50)), method=0),  # a letterbox that reaches the visible right and bottom edge, border on the other two sides
     "D": dict(size=(50, 70), geom=(None, (6, 4, 52, 40), (70, 50)), method=1),  # 90r: the rectangle transposed and flipped, border on all four sides
+    "E": dict(size=(64, 48), geom=None, method=0),  # no margin at all: the smallest picture whose device planes can be coded where they lie (tests/test_input_steps_gpu.py)
 }
 _CACHE = {}
 

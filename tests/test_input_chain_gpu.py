@@ -206,8 +206,8 @@ def test_the_mix_alone_keeps_the_margins_replicas_and_the_stream_is_the_plain_en
 
 
 # ---- 2. every step at once
-def _submit(E, e, name, src):
-    return lambda i: e.submit(*src[i], pts=i), src, None
+def _submit(E, e, name, src, pts=None):
+    return lambda i: e.submit(*src[i], pts=pts[i] if pts else i), src, None
 
 
 def _submit_yuy2(E, e, name, src):
@@ -224,19 +224,20 @@ def _submit_jpeg(E, e, name, src):
     return lambda i: e.submit_jpeg(data[i], pts=i), vis, None
 
 
-def _submit_device(E, e, name, src):
-    """planes at an odd address and a stride of width + 5"""
+def _submit_device(E, e, name, src, stride=None, offset=1, pts=None):
+    """planes at an odd address and a stride of width + 5, unless the test names others (pts: the submits' time stamps; their indices otherwise)"""
     w, h = C.PICTURES[name]["size"]
-    dev = [device_planes(E, [y, uv], [h, h // 2], [w, w], w + 5, 1) for y, uv in src]
+    stride = stride or w + 5
+    dev = [device_planes(E, [y, uv], [h, h // 2], [w, w], stride, offset) for y, uv in src]
 
     def after():
         for (hip, buf, ptrs), (y, uv) in zip(dev, src):  # the caller's planes are unchanged
             for ptr, p in zip(ptrs, (y, uv)):
                 back = np.empty(p.shape, np.uint8)
-                assert hip.hipMemcpy2D(back.ctypes.data_as(C_.c_void_p), C_.c_size_t(w), C_.c_void_p(ptr), C_.c_size_t(w + 5), C_.c_size_t(w), C_.c_size_t(p.shape[0]), 2) == 0
+                assert hip.hipMemcpy2D(back.ctypes.data_as(C_.c_void_p), C_.c_size_t(w), C_.c_void_p(ptr), C_.c_size_t(stride), C_.c_size_t(w), C_.c_size_t(p.shape[0]), 2) == 0
                 assert np.array_equal(back, p)
             assert hip.hipFree(buf) == 0
-    return lambda i: e.submit_device(dev[i][2][0], w + 5, dev[i][2][1], w + 5, pts=i), src, after
+    return lambda i: e.submit_device(dev[i][2][0], stride, dev[i][2][1], stride, pts=pts[i] if pts else i), src, after
 
 
 ENTRY = {"submit": _submit, "submit_fmt-yuy2": _submit_yuy2, "submit_device": _submit_device, "submit_jpeg": _submit_jpeg}
